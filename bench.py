@@ -30,13 +30,25 @@ Workloads (BASELINE.json `configs`, 0-based):
   --mode predict    catalogue inference (predict.py:71-96): forward-only tower over the 10 M-row
                     table in chunks, rows/s, fp32 and (--precision bf16) config-4 precision.
 
+A plain run sets up, warms up, times exactly K steps and prints its line; everything that takes runs of its own (the
+gather record, the secondary records, the CPU baseline) is measured only with --full.
+  --full         after the headline: the `gather` record (and `roofline.gather`), the secondary records of the default
+                 N = 1 line and `cpu_baseline` (--no-extras / --no-cpu-baseline leave parts of it out)
+  --dump-outputs DIR   after the timed steps: what the last timed step computed, as DIR/<name>.npy (float32; float64 for
+                 the loss and the triplets' row ids) -- the loss, the step's embeddings, the updated weights W1, b1, W2,
+                 b2 and its triplets as [B, 3] catalogue row ids: anchor, positive, negative (-1: semi-hard mining
+                 found none) (--mode predict: a fixed sample of the catalogue's embeddings and
+                 their row ids).  An array of more than 2^22 elements is written as `<name>_sample`: the elements
+                 at a fixed, seeded choice of flat positions (numpy RandomState(0), sorted), so two builds compare
+                 element for element.  The inputs depend on the arguments alone (seeded catalogue, pairs, weights).
+
 Prints ONE JSON line (rank 0).  Beside the contract's fields:
   roofline       the dominant kernel (weight-gradient GEMM), timed live with events on the
                  launch stream inside the timed region; `traffic` from the committed PMC summary
                  named in `traffic_source` (a builder-run rocprofv3 --pmc pass, not this run)
-  gather         the HBM-bound fused sampler+gather: 10 launches per event pair (a pair around
-                 one 20-40 us launch costs 10-25 % of it), same arguments as the timed steps
-  cpu_baseline   BASELINE.md section 4: the CPU restatement of the reference step (oracle/
+  gather         (--full) the HBM-bound fused sampler+gather: 10 launches per event pair (a pair
+                 around one 20-40 us launch costs 10-25 % of it), same arguments as the timed steps
+  cpu_baseline   (--full) BASELINE.md section 4: the CPU restatement of the reference step (oracle/
                  tower_torch.py) on config 0's 10k x 1500 table, B = 128 and 1024, 1 and all
                  threads, fetch / train split, on this box's host cores
   comm           (N > 1) what the compute stream waits for: all-reduce and row exchange; which
@@ -45,8 +57,8 @@ Prints ONE JSON line (rank 0).  Beside the contract's fields:
   order / warmup_effective   what ran on the GPU before the timed region (N = 1: a 0.3-s clock-settle loop of steps of a
                  SECOND TrainStep of the same shape on its own buffers -- the measured job's state is untouched -- then the
                  W warm-up steps; DESIGN.md section 8 says why bare GEMM launches were not enough)
-Secondary records of the default N = 1 line (measured AFTER the headline; each in its own try; those that
-train run at the headline's precision):
+Secondary records of the default N = 1 line with --full (measured AFTER the headline; each in its own try; those
+that train run at the headline's precision):
   config1            BASELINE config 1 (1 M videos, batch 4096, in-batch negatives): the headline of rounds 1-4, a full
                      record (value, roofline, FC1 roofline, kernel breakdown, gather) so the round-to-round series continues
   config2_semihard   BASELINE config 2 (the same 1 M catalogue, semi-hard mining over all pairs of the batch, batch 8192)
@@ -357,6 +369,58 @@ def timed_steps(ts, steps, warmup, dev):
     return time.perf_counter() - t0
 
 
+# ------------------------------------------------------------- --dump-outputs ------
+DUMP_CAP = 1 << 22                 # elements per array; a larger output is written as a fixed, seeded sample
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+
+
+def step_triplets(ts):
+    """[B, 3] catalogue row ids (anchor, positive, negative) of the step's triplets.  Uniform negatives: the sampled
+    rows.  In-batch: the negative of triplet i is the positive of triplet (i + shift) mod B (oracle/sampler.py
+    device_inbatch).  Semi-hard: the row the miner picked (neg_row, an index into the 2B embedded rows), -1 where it
+    found none."""
+    if ts.mode == "uniform":
+        return ts.idx[:ts.R].view(ts.B, 3).long()
+    ap = ts.idx[:ts.R].view(ts.B, 2).long()
+    if ts.mode == "semihard":
+        nr = ts.neg_row.long()
+        neg = torch.where(nr >= 0, ts.idx[:ts.R].long()[nr.clamp_min(0)], torch.full_like(nr, -1))
+    else:
+        j = (torch.arange(ts.B, device=ap.device) + ts.shift[:1].long()) % ts.B
+        neg = ap[j, 1]
+    return torch.cat([ap, neg.view(-1, 1)], 1)
+
+
+def step_outputs(ts):
+    """What a caller of TrainStep.step() holds after its last step, copied to the host: the loss, the embeddings of the
+    step's rows, the updated weights and the row ids of its triplets."""
+    L = ts.layout
+    W1, b1, W2, b2 = ts.params.unpadded()
+    f32 = lambda t: t.detach().float().cpu().numpy()
+    return {"loss": ts.stats[:1].double().cpu().numpy(), "embeddings": f32(ts.ws.e[:ts.R, :L.D]),
+            "W1": f32(W1), "b1": f32(b1), "W2": f32(W2), "b2": f32(b2),
+            "triplet_row_ids": step_triplets(ts).double().cpu().numpy()}
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: each array as d/<name>.npy (float64 stays float64, everything else float32); one of more than
+    DUMP_CAP elements as d/<name>_sample.npy, its elements at DUMP_CAP flat positions drawn by RandomState(0), sorted.
+    More than DUMP_LIMIT_BYTES in all is refused before anything is written."""
+    files = {}
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+        if a.size > DUMP_CAP:
+            pos = np.sort(np.random.RandomState(0).choice(a.size, DUMP_CAP, replace=False))
+            a, name = a.reshape(-1)[pos], name + "_sample"
+        files[name] = a
+    total = sum(a.nbytes for a in files.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError("--dump-outputs: %d bytes, more than the %d allowed" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(d, exist_ok=True)
+    for name, a in files.items():
+        np.save(os.path.join(d, name + ".npy"), a)
+
+
 # ------------------------------------------------- kernel timers and their records ------
 def install_timers(kt, L, bf16):
     """Wrap the step's GEMM / tail / optimizer entry points of cdml_amd.ops with event pairs (active
@@ -568,11 +632,12 @@ def gather_record(ts, mode, bf16, dev, pmc_name=None, workload=None):
             "method": "%d back-to-back launches per event pair (inter-launch gaps included), median of %d" % (per, reps)}
 
 
-def measure_job(ts, steps, warmup, dev, bf16, timers=True, barrier=None):
+def measure_job(ts, steps, warmup, dev, bf16, timers=True, barrier=None, after_timed=None):
     """W warm-up steps, then EXACTLY `steps` timed steps bracketed by (barrier +) synchronize on both
     sides; kernel timers on every 4th timed step (every 8th in long runs): an event pair costs the
     stream ~5 us, seven pairs a step are 1.5 % of it; the sampled launches are launches of the timed
-    region.  Under graph replay the timers run on 8 extra EAGER steps after it.  Returns
+    region.  Under graph replay the timers run on 8 extra EAGER steps after it.  `after_timed()` is
+    called right after the timed region, before any of those.  Returns
     (elapsed_s, KernelTimer, sampled_steps, how)."""
     kt = KernelTimer()
     restore = install_timers(kt, ts.layout, bf16) if timers else (lambda: None)
@@ -596,6 +661,8 @@ def measure_job(ts, steps, warmup, dev, bf16, timers=True, barrier=None):
             torch.cuda.synchronize(dev)
         elapsed = time.perf_counter() - t0
         kt.on = False
+        if after_timed is not None:
+            after_timed()
         sampled = (steps + stride - 1) // stride
         how = "event pairs on every %dth timed step" % stride
         if graph_run and timers:                     # same kernels, launched eagerly, for the roofline
@@ -1130,10 +1197,12 @@ def rec_fusion(dev, args, n_s, n_w):
     return out
 
 
-def rec_predict(dev, precision, n_rows=10000000, chunk=100000, reps=2):
+def rec_predict(dev, precision, n_rows=10000000, chunk=100000, reps=2, warmup=1, outputs=None):
     """Catalogue inference (predict.py:71-96; the reference's chunk is 100 000 rows, predict.py:146):
     forward-only tower over every row of the HBM-resident table, embeddings left in HBM.  Algorithmic
-    work per row: 2*F*H + 2*H*D flop; F*s bytes read + D*4 written."""
+    work per row: 2*F*H + 2*H*D flop; F*s bytes read + D*4 written.  `warmup` untimed passes, `reps`
+    timed ones; `outputs` (a dict): filled with the embeddings of 16 384 rows drawn by RandomState(0)
+    and their row ids, from the last timed pass."""
     from cdml_amd import engine, engine_bf16, predict
     bf16 = precision == "bf16"
     Table = engine_bf16.FeatureTableF16 if bf16 else engine.FeatureTable
@@ -1142,13 +1211,18 @@ def rec_predict(dev, precision, n_rows=10000000, chunk=100000, reps=2):
     L = (engine_bf16.layout_bf16 if bf16 else engine_x3.layout_x3 if precision in ("f32x3", "f16x2") else engine.TowerLayout)(F, H, D)
     pr = predict.Prediction(params=engine.VNetParams(L, dev, 42), precision=precision)
     out = torch.empty((n_rows, D), dtype=torch.float32, device=dev)
-    pr.embed_table(table, chunk, out=out)
+    for _ in range(warmup):
+        pr.embed_table(table, chunk, out=out)
     torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
     for _ in range(reps):
         pr.embed_table(table, chunk, out=out)
     torch.cuda.synchronize(dev)
     el = (time.perf_counter() - t0) / reps
+    if outputs is not None:
+        rows = np.sort(np.random.RandomState(0).choice(n_rows, min(n_rows, 16384), replace=False))
+        outputs["embeddings_sample"] = out[torch.from_numpy(rows).to(dev)].cpu().numpy()
+        outputs["embeddings_sample_row_ids"] = rows.astype(np.float64)
     nrm = float((out[::9973].norm(dim=1) - 1).abs().max())
     flops = n_rows * (2.0 * F * H + 2.0 * H * D)
     peak = (PEAK_BF16_MFMA_TFLOPS if bf16 else round(PEAK_BF16_MFMA_TFLOPS / 6, 1) if precision == "f32x3"
@@ -1236,10 +1310,15 @@ def main():
                          "before the warm-up, the faster one is kept)")
     ap.add_argument("--capacity-factor", type=float, default=1.25,
                     help="N>1: headroom of the fixed-capacity row exchange over the mean share per peer")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure what takes runs of its own: the gather record, the secondary "
+                         "records of the default N=1 line and the CPU baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, <= 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--cpu-baseline-full", action="store_true", help="50 timed CPU steps in all four runs (minutes)")
     ap.add_argument("--no-kernel-timers", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the secondary records of the default N=1 line")
+    ap.add_argument("--no-extras", action="store_true", help="--full without the secondary records of the default N=1 line")
     ap.add_argument("--extras", default=None,
                     help="comma list of secondary records to run (default: all): config1,config2_semihard,dp_form_one_gpu,train_table,"
                          "config4_per_gpu,reference_recipe,fusion_resnet,predict,data_learnable,f32_mfma")
@@ -1248,6 +1327,10 @@ def main():
     ap.add_argument("--no-settle", action="store_true",
                     help="skip the 0.3 s GEMM loop before the warm-up steps (rocprof runs: keeps its launches out of the kernel averages)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and args.only:
+        ap.error("--dump-outputs writes the outputs of the job of the line; --only records have none")
 
     world = int(os.environ.get("WORLD_SIZE", "0") or 0)
     launched = "RANK" in os.environ and world >= 1
@@ -1286,9 +1369,12 @@ def main():
         set_phase("predict")
         if not args.no_settle:
             settle_gpu(dev, precision=args.precision[:5])
-        r = rec_predict(dev, args.precision, n_rows=args.rows or 10000000)
+        dumped = {} if args.dump_outputs else None
+        r = rec_predict(dev, args.precision, n_rows=args.rows or 10000000, reps=args.steps, warmup=args.warmup, outputs=dumped)
+        if dumped is not None:
+            dump_outputs(args.dump_outputs, dumped)
         out = {"metric": "catalogue rows embedded/sec", "value": r["value"], "unit": "rows/s", "n_gpus": 1,
-               "steps": r["passes_timed"], "warmup": 1, "ms_per_step": round(r["seconds"] * 1e3, 3),
+               "steps": r["passes_timed"], "warmup": args.warmup, "ms_per_step": round(r["seconds"] * 1e3, 3),
                "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": r["dtype"], "data": "synthetic",
                "config": {"workload": r["workload"]}, "predict": r}
         print(json.dumps(out), file=result_out, flush=True)
@@ -1429,8 +1515,10 @@ def main():
             if ts.prefetch is not None:
                 ts.prefetch.acquire = comm_kt.wrap("exchange_wait", ts.prefetch.acquire)
             comm_kt.on = True
+        dumped = {}
+        snapshot = (lambda: dumped.update(step_outputs(ts))) if (args.dump_outputs and rank == 0) else None
         elapsed, kt, sampled, how = measure_job(ts, args.steps, args.warmup, dev, "h2" if h2 else None if x3 else bf16, timers_on,
-                                                barrier if world > 1 else None)
+                                                barrier if world > 1 else None, after_timed=snapshot)
         if comm_kt is not None:
             comm_kt.on = False
         elapsed_local = elapsed
@@ -1463,6 +1551,8 @@ def main():
         raise
 
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, dumped)
         rpt = ts.rows_per_triplet
         R = B * rpt
         ms = elapsed / args.steps * 1e3
@@ -1529,7 +1619,7 @@ def main():
             out.update(h2_records(kt, R, sampled, how, workload=wkey if world == 1 else None))
         elif timers_on:
             out.update(gemm_records(kt, R, bf16, sampled, how, world == 1, x3_products=x3, workload=wkey))
-        if world == 1 and not args.train_table:
+        if world == 1 and not args.train_table and args.full:
             set_phase("gather record")
             out["gather"] = gather_record(ts, mode, bf16, dev, workload=wkey)
             if "roofline" in out:
@@ -1562,11 +1652,12 @@ def main():
                                            "scratch buffers.  No state of the measured job is touched: the chip needs ~100 ms of "
                                            "this kind of work to reach the clock it then holds (a 20-step run from idle reads "
                                            "3-4 % above the 200-step rate)"}
-        out["order"] = ("%swarm-up + timed steps, then the secondary records, cpu_baseline last"
-                        % ("" if args.no_settle else "0.3 s settle loop (%s), " % settle_how))
+        out["order"] = ("%swarm-up + timed steps%s"
+                        % ("" if args.no_settle else "0.3 s settle loop (%s), " % settle_how,
+                           ", then the gather record, the secondary records, cpu_baseline last (--full)" if args.full else ""))
 
-        # ---- secondary records (after the headline; the failure of one must not cost the line) ----
-        run_extras = default_job and not args.no_extras and not args.train_table and x3 in (0, 6) and not h2
+        # ---- secondary records (--full; after the headline; the failure of one must not cost the line) ----
+        run_extras = args.full and default_job and not args.no_extras and not args.train_table and x3 in (0, 6) and not h2
         if run_extras:
             del ts
             torch.cuda.empty_cache()
@@ -1611,7 +1702,7 @@ def main():
             attempt("predict", lambda: {"f32": rec_predict(dev, "f32"), "f32x3": rec_predict(dev, "f32x3"),
                                         "f16x2": rec_predict(dev, "f16x2"), "bf16": rec_predict(dev, "bf16")})
             attempt("knn", lambda: dict(rec_knn(dev), f16x2=rec_knn(dev, precision="f16x2")))
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             set_phase("cpu_baseline")
             out["cpu_baseline"] = cpu_baseline(args.cpu_baseline_full)
         print(json.dumps(out), file=result_out, flush=True)

@@ -52,3 +52,55 @@ def test_pmc_traffic_is_withheld_when_the_kernel_sources_changed(tmp_path, monke
     assert bench.pmc_traffic("k_gemm_bf16_256<true, 3, true, true", name="latest_pmc_x3")[0] is None
     assert bench.pmc_traffic("k_gemm_bf16_256<true, 3", name="no_such_summary") == (None, None)
     assert real_root == ROOT
+
+
+def test_dump_outputs_writes_float_arrays_and_a_seeded_sample(tmp_path):
+    """--dump-outputs: float64 stays float64, everything else is written as float32; an array of more than DUMP_CAP
+    elements is written as <name>_sample, the same elements in every run; more than 64 MB in all is refused."""
+    import numpy as np
+    import pytest
+    arrays = {"loss": np.array([0.25]), "ids": np.arange(7, dtype=np.int32),
+              "W": np.arange(bench.DUMP_CAP + 1000, dtype=np.float32)}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    assert sorted(os.listdir(tmp_path / "a")) == ["W_sample.npy", "ids.npy", "loss.npy"]
+    assert np.load(tmp_path / "a" / "loss.npy").dtype == np.float64
+    ids = np.load(tmp_path / "a" / "ids.npy")
+    assert ids.dtype == np.float32 and np.array_equal(ids, np.arange(7))
+    w = np.load(tmp_path / "a" / "W_sample.npy")
+    assert w.dtype == np.float32 and w.shape == (bench.DUMP_CAP,) and np.all(np.diff(w) > 0)
+    assert np.array_equal(w, np.load(tmp_path / "b" / "W_sample.npy"))
+    with pytest.raises(RuntimeError, match="more than"):
+        bench.dump_outputs(str(tmp_path / "c"), {"x%d" % i: np.zeros(bench.DUMP_CAP, np.float32) for i in range(4)})
+    assert not (tmp_path / "c").exists()                 # refused before anything was written
+
+
+def test_step_triplets_names_the_negative_of_every_mode():
+    """The dumped triplets are (anchor, positive, negative) catalogue rows: uniform negatives as sampled; in-batch the
+    positive of triplet (i + shift) mod B (oracle.sampler.device_inbatch); semi-hard the mined row, -1 where none."""
+    import types
+    import numpy as np
+    import torch
+    from oracle import sampler as osampler
+    B = 6
+    pairs = np.stack([np.arange(0, 40, 2), np.arange(1, 40, 2)], 1).astype(np.int32)
+    rows, tri, _, s = osampler.device_inbatch(pairs, 1234, 5, B)
+    ts = types.SimpleNamespace(mode="inbatch", B=B, R=2 * B, idx=torch.from_numpy(rows), shift=torch.tensor([s], dtype=torch.int32))
+    assert np.array_equal(bench.step_triplets(ts).numpy(), rows[tri])
+    neg_row = torch.tensor([3, -1, 0, 11, 5, 2], dtype=torch.int32)
+    ts = types.SimpleNamespace(mode="semihard", B=B, R=2 * B, idx=torch.from_numpy(rows), neg_row=neg_row)
+    got = bench.step_triplets(ts).numpy()
+    assert np.array_equal(got[:, :2], rows.reshape(B, 2))
+    assert list(got[:, 2]) == [rows[3], -1, rows[0], rows[11], rows[5], rows[2]]
+    u = torch.arange(3 * B, dtype=torch.int32)
+    ts = types.SimpleNamespace(mode="uniform", B=B, R=3 * B, idx=u)
+    assert np.array_equal(bench.step_triplets(ts).numpy(), u.view(B, 3).numpy())
+
+
+def test_bench_refuses_arguments_it_cannot_honour():
+    """--steps sets the number of timed steps (0 is refused, not divided by); --only records have no job outputs to dump.
+    Both are refused before anything touches a GPU."""
+    import subprocess
+    for extra, word in ((["--steps", "0"], "--steps must be >= 1"), (["--only", "f16x2", "--dump-outputs", "out"], "--only records have none")):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + extra, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 2 and word in r.stderr, r.stderr[-2000:]

@@ -9,7 +9,7 @@ export TMPDIR=/tmp
 python -m pytest tests/test_abi_host.py "tests/test_gpu_dist.py::test_two_rank_trainer_saves_once" \
   "tests/test_gpu_dist.py::test_overflow_on_one_rank_raises_on_every_rank_and_nothing_is_saved" -x -q > $O/r05a_tests.txt 2>&1
 echo "[r05a] tests rc=$? $(tail -1 $O/r05a_tests.txt)"
-python bench.py --steps 20 --warmup 5 > $O/r05a_bench.json 2> $O/r05a_bench.err
+python bench.py --full --steps 20 --warmup 5 > $O/r05a_bench.json 2> $O/r05a_bench.err
 echo "[r05a] bench rc=$? $(wc -c < $O/r05a_bench.json) bytes"
 python tools/graph_vs_eager.py --blocks 4 --steps 200 > $O/r05a_graph_vs_eager.txt 2>&1
 echo "[r05a] graph_vs_eager rc=$?"; cat $O/r05a_graph_vs_eager.txt | tail -6

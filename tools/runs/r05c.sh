@@ -12,7 +12,7 @@ python tools/gather_sweep.py --kind f16 --mode 0 --steps 2,3,4 > $O/r05c_gather_
 python tools/gather_sweep.py --kind x3 --steps 1,2,4 >> $O/r05c_gather_sweep.txt 2>&1
 python tools/gather_sweep.py --kind x3 --rows 1000000 --batch 4096 --steps 2,3,4 >> $O/r05c_gather_sweep.txt 2>&1
 grep gather $O/r05c_gather_sweep.txt | cut -c1-200
-python bench.py --steps 20 --warmup 5 > $O/r05c_bench.json 2> $O/r05c_bench.err
+python bench.py --full --steps 20 --warmup 5 > $O/r05c_bench.json 2> $O/r05c_bench.err
 echo "[r05c] bench rc=$?"
 python - <<'PY'
 import json

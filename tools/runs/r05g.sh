@@ -10,7 +10,7 @@ for S in 60 120 60 120; do
   python -c "
 import json; d=json.load(open('$O/r05g_recipe_$S.json')); r=d['reference_recipe']; print('recipe slab=$S', r['ms_per_step'], r['kernels'])" | tee -a $O/r05g_recipe.txt
 done
-python bench.py --steps 20 --warmup 5 > $O/r05g_bench.json 2> $O/r05g_bench.err
+python bench.py --full --steps 20 --warmup 5 > $O/r05g_bench.json 2> $O/r05g_bench.err
 echo "[r05g] bench rc=$?"
 python - <<'PY'
 import json

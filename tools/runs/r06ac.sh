@@ -6,7 +6,7 @@ timeout -k 10 1000 python -m pytest tests -m gpu -q > $O/r06ac_gpu_tests.txt 2>&
 echo "[r06ac] gpu suite rc=$? $(tail -1 $O/r06ac_gpu_tests.txt)"; grep -E "^(FAILED|ERROR)" $O/r06ac_gpu_tests.txt | head
 timeout -k 10 300 python __graft_entry__.py --smoke > $O/r06ac_smoke.txt 2>&1
 echo "[r06ac] smoke rc=$?"; grep smoke $O/r06ac_smoke.txt
-timeout -k 10 500 python bench.py --steps 20 --warmup 5 > $O/r06_bench_driver_style.json 2> $O/r06ac_bench.err
+timeout -k 10 500 python bench.py --full --steps 20 --warmup 5 > $O/r06_bench_driver_style.json 2> $O/r06ac_bench.err
 echo "[r06ac] bench rc=$?"; python - <<'PY'
 import json
 d=json.load(open('gpurun_out/r06_bench_driver_style.json'))

@@ -3,7 +3,7 @@
 set -o pipefail
 ROOT=$(pwd); O=$ROOT/gpurun_out; mkdir -p $O; export TMPDIR=/tmp
 T0=$(date +%s)
-timeout -k 10 900 python bench.py > $O/r06ag_default_bench.json 2> $O/r06ag_default_bench.err
+timeout -k 10 900 python bench.py --full > $O/r06ag_default_bench.json 2> $O/r06ag_default_bench.err
 echo "[r06ag] default bench rc=$? wall $(( $(date +%s) - T0 )) s"
 python - <<'PY'
 import json

@@ -5,7 +5,7 @@ set -o pipefail
 ROOT=$(pwd); O=$ROOT/gpurun_out; mkdir -p $O; export TMPDIR=/tmp
 timeout -k 10 900 python -m pytest tests/test_gpu_parity.py tests/test_gpu_f32x3.py tests/test_gpu_knn.py tests/test_gpu_table.py -m gpu -q -x > $O/r06d_tests.txt 2>&1
 echo "[r06d] tests rc=$? $(tail -1 $O/r06d_tests.txt)"; grep -E "^(FAILED|ERROR)" $O/r06d_tests.txt | head
-timeout -k 10 600 python bench.py --steps 30 --warmup 5 --no-cpu-baseline --extras config2_semihard,train_table,knn > $O/r06d_bench.json 2> $O/r06d_bench.err
+timeout -k 10 600 python bench.py --full --steps 30 --warmup 5 --no-cpu-baseline --extras config2_semihard,train_table,knn > $O/r06d_bench.json 2> $O/r06d_bench.err
 echo "[r06d] bench rc=$?"; python - <<'PY'
 import json
 d=json.load(open('gpurun_out/r06d_bench.json'))

@@ -4,7 +4,7 @@ set -o pipefail
 ROOT=$(pwd); O=$ROOT/gpurun_out; mkdir -p $O; export TMPDIR=/tmp
 timeout -k 10 900 python -m pytest tests -m gpu -q > $O/r06o2_gpu_tests.txt 2>&1
 echo "[r06o2] gpu suite rc=$? $(tail -1 $O/r06o2_gpu_tests.txt)"; grep -E "^(FAILED|ERROR)" $O/r06o2_gpu_tests.txt | head
-timeout -k 10 400 python bench.py --steps 20 --warmup 5 > $O/r06_bench_driver_style.json 2> $O/r06o2_bench.err
+timeout -k 10 400 python bench.py --full --steps 20 --warmup 5 > $O/r06_bench_driver_style.json 2> $O/r06o2_bench.err
 echo "[r06o2] bench rc=$?"; python - <<'PY'
 import json
 d=json.load(open('gpurun_out/r06_bench_driver_style.json'))
