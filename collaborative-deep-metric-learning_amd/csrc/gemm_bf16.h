@@ -30,7 +30,11 @@ enum { BE_BIAS_LRELU_BF16 = 0, BE_BIAS_LRELU_F32 = 1, BE_MASK_BF16 = 2, BE_F32 =
        // exact kNN (faiss_knn.py:82-131) as the epilogue of the query x catalogue score product: nothing of the scores is
        // written -- an element whose distance is within its query's current k-th best (BArgs::knn_*) is appended to the
        // query's candidate list (gemm_bf16_256.hip "knn filter", knn.hip cdml_knn_filter_x3)
-       BE_KNN_X3 = 13 };
+       BE_KNN_X3 = 13,
+       // exact retrieval ranks as the epilogue of the same query x catalogue product: nothing of the scores is written --
+       // every query row counts the catalogue rows ranked ahead of its partner (BArgs::rank_*; gemm_bf16_256.hip "rank
+       // count", knn.hip cdml_rank_count_x3)
+       BE_RANK_X3 = 14 };
 
 // one candidate pair of an anchor over some set of columns: the closest eligible column with d > d_p ("outside"; ties ->
 // smaller column) and the farthest eligible one; c = 0x7fffffff: none
@@ -77,6 +81,13 @@ struct BArgs {
   // element with d <= knn_tau[row] takes slot atomicAdd(knn_cnt + row, 1) of the row's knn_cap-slot list knn_cand
   // ((d, id) pairs; a slot beyond the capacity is dropped -- the count says so)
   const float *knn_qsq, *knn_bsq, *knn_tau; int32_t *knn_cnt; uint2 *knn_cand; int knn_cap, knn_col0, knn_n_valid;
+  // BE_RANK_X3: A = the queries' planes (query i = its anchor's row), B = a block of the catalogue's planes; knn_bsq,
+  // knn_col0 and knn_n_valid as for BE_KNN_X3, d as there.  rank_cnt[i] += #{columns c: id = knn_col0 + c < knn_n_valid,
+  // id != rank_self[i], id != rank_pos[i], d < rank_tau[i] or (d == rank_tau[i] and id < rank_pos[i])} (integer atomics).
+  // rank_tau_out != null: the DIAGONAL launch instead (tiles_n = 1; tile row tm is multiplied with tile column tm, B row i =
+  // the partner of query i): element (i, i) is written to rank_tau_out[i] -- the partner's distance in exactly the
+  // arithmetic the count compares it with
+  const float *rank_qsq, *rank_tau; const int32_t *rank_pos, *rank_self; int32_t *rank_cnt; float *rank_tau_out;
   // Two-plane fp16 form ("f16x2": gemm_f16x2_256.hip = this kernel compiled with CDML_F16X2): the operands hold
   // a 2^sa and b 2^sb as fp16 planes hi | lo, so the accumulator holds 2^(sa + sb) a.b: out_scale = 2^-(sa + sb) multiplies it
   // before anything else of the epilogue; a plane output is written as the fp16 planes of (value * c_scale), clamped to fp16's range
@@ -100,6 +111,9 @@ int launch_gemm_f16x2_knn(const BArgs &g, hipStream_t stream);      // BE_KNN_X3
 int launch_gemm_x3_mine(const BArgs &g, hipStream_t stream);
 // the query x catalogue score product of the kNN export with the threshold filter as its epilogue (BE_KNN_X3)
 int launch_gemm_x3_knn(const BArgs &g, hipStream_t stream);
+// the same product with the rank count as its epilogue (BE_RANK_X3; g.rank_tau_out set: the diagonal launch); x3 / fp16 planes
+int launch_gemm_x3_rank(const BArgs &g, hipStream_t stream);
+int launch_gemm_f16x2_rank(const BArgs &g, hipStream_t stream);
 // the k-strided product on k8-INTERLEAVED operands ([plane][k / 8][column][8 k]; g.lda / g.ldb = elements per k-group,
 // g.x3_plane_* = elements per plane): the resident-plane walk with one 16-B LDS read per fragment
 int launch_gemm_x3_tnk(const BArgs &g, int splits, hipStream_t stream);

@@ -175,8 +175,8 @@ __device__ __forceinline__ void run_tile(const BArgs &g, const int tm, const int
                 "the 128 x 256 half tile exists for the plane-output products of the resident-plane walk and for the fp32 slabs of the narrow layer");
   static_assert(X3 || (EPI != BE_BIAS_LRELU_X3 && EPI != BE_MASK_X3 && EPI != BE_ROWBIAS_LRELU_X3),
                 "plane outputs belong to the split-fp32 form");
-  static_assert((EPI != BE_MINE_X3 && EPI != BE_KNN_X3) || (X3 && S16 && R6 && !TN && !NARROW),
-                "the mining / kNN-filter epilogues ride on the resident-plane walk");
+  static_assert((EPI != BE_MINE_X3 && EPI != BE_KNN_X3 && EPI != BE_RANK_X3) || (X3 && S16 && R6 && !TN && !NARROW),
+                "the mining / kNN-filter / rank-count epilogues ride on the resident-plane walk");
   static_assert(!KI || (TN && X3 && S16 && R6), "the k8-interleaved operands exist for the k-strided resident-plane walk");
   const int t = threadIdx.x;
   const int lane = t & 63;
@@ -193,7 +193,7 @@ __device__ __forceinline__ void run_tile(const BArgs &g, const int tm, const int
   // strip, no barrier -- and measured SLOWER: FC1 + 4 %, the data gradient + 30 %, profiles/r06_swapped_plane_epilogue_ab.txt.
   // A store instruction then writes 16 rows x 32 B and a 128-B line is assembled from four of them; the LDS transpose of
   // tail16 below is what makes every store a whole line.  The swapped layout stays where nothing of the tile is stored.)
-  constexpr bool kSwap = EPI == BE_MINE_X3 || EPI == BE_KNN_X3;
+  constexpr bool kSwap = EPI == BE_MINE_X3 || EPI == BE_KNN_X3 || EPI == BE_RANK_X3;
 
   const int k_rows = X3 ? g.x3_tpp * kTileK : g.K;              // k-strided form: rows of the operands in memory
   const i32x4 srd_a = make_srd(g.A, KI ? 3 * g.x3_plane_a * 2 : (int64_t)(TN ? k_rows : g.M) * g.lda * 2);
@@ -1292,6 +1292,89 @@ __device__ __forceinline__ void run_tile(const BArgs &g, const int tm, const int
     return;
   }
 
+  // ---- exact retrieval ranks as the epilogue of the query x catalogue product (evaluate.py Evaluation.ranks) -------------
+  // Query i is a directed co-watch pair (anchor a, partner p): A row i = a's planes.  Its rank is the number of catalogue
+  // rows j != a, p ahead of p in a's list: d(a, j) < tau = d(a, p), or equal with j < p (ties by id, as the kNN export
+  // orders them).  Nothing of the tile is written: a lane counts its 16 elements of a row, the four lanes that share the row
+  // (same operand-swapped layout as the kNN filter: lane (l15, q) holds row rbb*16 + l15, columns cb*16 + 4q .. + 3) add
+  // theirs in two cross-lane steps, and one integer atomic per row and wave adds the sum -- order-independent, so the counts
+  // do not depend on the schedule.  tau comes from the DIAGONAL launch of this same kernel (rank_tau_out set): the partner's
+  // distance in exactly the arithmetic the count compares with (one explicit fma), so an exact duplicate of p ties with it
+  // bit for bit.  The count per element is d < tau and d == tau only; the rule's other terms -- the anchor's and the
+  // partner's own columns, ties, tau = 0 (where the clamp at 0 makes ties), the padding rows of the last tile -- concern a
+  // few elements per ROW of the whole catalogue, and a lane that holds one of them recounts its row with the full rule.
+  if constexpr (EPI == BE_RANK_X3) {
+    int lane_e = lane;                                       // (opaque: nothing of this is hoisted above the K loop)
+    asm volatile("" : "+v"(lane_e));
+    const int l15 = lane_e & 15, q16 = lane_e >> 4;
+    const int cbase = n0 + wc * 64 + 4 * q16;                // launch-local column of the lane's first element
+    const float m2s = kF16 ? -2.0f * g.out_scale : -2.0f;    // d = fma(-2 s, <q, b>, |q|^2 + |b|^2), clamped at 0
+    f32x4 bsv[4];
+#pragma unroll
+    for (int cb = 0; cb < 4; ++cb) bsv[cb] = *reinterpret_cast<const f32x4 *>(g.knn_bsq + cbase + cb * 16);
+    const int row_base = m0 + grp * 128 + l15;
+    if (g.rank_tau_out) {                                    // diagonal launch (n0 == m0): element (i, i) only
+#pragma unroll
+      for (int rbb = 0; rbb < 8; ++rbb) {
+        const int i = row_base + rbb * 16;
+        const float qs = g.rank_qsq[min(i, g.M - 1)];
+#pragma unroll
+        for (int cb = 0; cb < 4; ++cb)
+#pragma unroll
+          for (int r = 0; r < 4; ++r)
+            if (cbase + cb * 16 + r == i && i < g.M)
+              g.rank_tau_out[i] = fmaxf(__builtin_fmaf(m2s, acc16[rbb][cb][r], qs + bsv[cb][r]), 0.f);
+      }
+      return;
+    }
+    const int id0 = g.knn_col0 + cbase;                      // catalogue id of the lane's element (cb, r): id0 + cb*16 + r
+    const bool pad_tile = g.knn_col0 + n0 + kTileN > g.knn_n_valid;
+    float qs8[8], tau8[8];
+    int pos8[8], self8[8];
+#pragma unroll
+    for (int rbb = 0; rbb < 8; ++rbb) {
+      const int i = min(row_base + rbb * 16, g.M - 1);
+      qs8[rbb] = g.rank_qsq[i];
+      tau8[rbb] = g.rank_tau[i];
+      pos8[rbb] = g.rank_pos[i];
+      self8[rbb] = g.rank_self[i];
+    }
+    auto in_lane = [&](int id) {                             // id is one of the lane's 16 columns
+      const unsigned l = (unsigned)(id - id0);
+      return l < 52u && (l & 12u) == 0u;
+    };
+#pragma unroll
+    for (int rbb = 0; rbb < 8; ++rbb) {
+      const float qs = qs8[rbb], tau = tau8[rbb];
+      const int pid = pos8[rbb], sid = self8[rbb];
+      int n = 0, eq = 0;
+#pragma unroll
+      for (int cb = 0; cb < 4; ++cb)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {                        // (tau > 0 here: unclamped d orders the same)
+          const float d = __builtin_fmaf(m2s, acc16[rbb][cb][r], qs + bsv[cb][r]);
+          n += d < tau ? 1 : 0;
+          eq += d == tau ? 1 : 0;
+        }
+      if (eq != 0 || !(tau > 0.f) || pad_tile || in_lane(sid) || in_lane(pid)) {   // rare: the full rule
+        n = 0;
+#pragma unroll
+        for (int cb = 0; cb < 4; ++cb)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int id = id0 + cb * 16 + r;
+            const float d = fmaxf(__builtin_fmaf(m2s, acc16[rbb][cb][r], qs + bsv[cb][r]), 0.f);
+            n += (id < g.knn_n_valid && id != sid && id != pid && (d < tau || (d == tau && id < pid))) ? 1 : 0;
+          }
+      }
+      n += __shfl_xor(n, 16, 64);
+      n += __shfl_xor(n, 32, 64);
+      const int i = row_base + rbb * 16;
+      if (q16 == 0 && i < g.M && n) atomicAdd(g.rank_cnt + i, n);
+    }
+    return;
+  }
+
   // ---- epilogue: per wave, 32x64 strips through its private 16 KiB of LDS ----
   float *sC = reinterpret_cast<float *>(smem + wave * 16384);
   const int c4 = lane & 15;
@@ -1631,8 +1714,11 @@ __device__ __forceinline__ void block_of_launch(const BArgs &g, int bid, unsigne
       bid = g.narrow_first + (bid >> 1);
     }
   }
-  if (EPI != BE_MINE_X3 && EPI != BE_KNN_X3 && g.K <= (X3 ? 3072 : 512)) tile_of_block_rowmajor(bid, nwg, g.tiles_n, tm, tn);   // output-bound
+  if (EPI != BE_MINE_X3 && EPI != BE_KNN_X3 && EPI != BE_RANK_X3 && g.K <= (X3 ? 3072 : 512)) tile_of_block_rowmajor(bid, nwg, g.tiles_n, tm, tn);   // output-bound
   else tile_of_block(bid, nwg, g.tiles_m, g.tiles_n, tm, tn);
+  if constexpr (EPI == BE_RANK_X3) {
+    if (g.rank_tau_out) tn = tm;                             // the rank count's diagonal launch (tiles_n = 1)
+  }
   const int m0 = tm * kTileM + half * (kTileM / 2), n0 = tn * kTileN;
   const int split = blockIdx.y;
   const int k_begin = split * g.k_per_split;
@@ -1933,6 +2019,9 @@ int launch_gemm_f16x2_mine(const BArgs &g, hipStream_t s) {
 int launch_gemm_f16x2_knn(const BArgs &g, hipStream_t s) {
   return launch_x3_1<false, BE_KNN_X3, false, false, true>(g, g.tiles_m * g.tiles_n, 1, s);
 }
+int launch_gemm_f16x2_rank(const BArgs &g, hipStream_t s) {
+  return launch_x3_1<false, BE_RANK_X3, false, false, true>(g, g.tiles_m * g.tiles_n, 1, s);
+}
 int launch_gemm_f16x2_256(const BArgs &g, bool tn, int epilogue, int splits, hipStream_t s) {
   if (tn) return launch_x3<true, BE_F32>(g, splits, s);
   switch (epilogue) {
@@ -1963,6 +2052,10 @@ int launch_gemm_x3_mine(const BArgs &g, hipStream_t s) {
 
 int launch_gemm_x3_knn(const BArgs &g, hipStream_t s) {
   return launch_x3_1<false, BE_KNN_X3, false, false, true>(g, g.tiles_m * g.tiles_n, 1, s);
+}
+
+int launch_gemm_x3_rank(const BArgs &g, hipStream_t s) {
+  return launch_x3_1<false, BE_RANK_X3, false, false, true>(g, g.tiles_m * g.tiles_n, 1, s);
 }
 
 int launch_gemm_bf16_256_x3(const BArgs &g, bool tn, int epilogue, int splits, hipStream_t s) {

@@ -15,6 +15,7 @@
 //   k_knn_merge_list  (round 6) the same per-query list fed from a CANDIDATE list instead of a score row: the plane GEMM's
 //                  kNN-filter epilogue (gemm_bf16_256.hip, BE_KNN_X3) appends every element within a query's current
 //                  k-th best distance to that query's list; no score block is written at all.
+// The host side of the retrieval ranks (cdml_rank_tau_x3 / cdml_rank_count_x3, below) shares the filter's product.
 #include "gemm_bf16.h"
 
 namespace cdml {
@@ -302,4 +303,105 @@ extern "C" int cdml_knn_merge(const float *scores, int64_t lds, int nq, int nb, 
                      (hipStream_t)stream, scores, lds, nq, nb, col0, n_valid, q_sq, b_sq, k, best_d, best_i,
                      first);
   return check_launch("knn_merge");
+}
+
+// Exact retrieval ranks for the evaluation metrics (evaluate.py Evaluation.ranks / retrieval_metrics: Recall@k, nDCG@k,
+// MAP@k, MRR -- the stubs Evaluation.knn / nDCG / MAP of the reference's evaluate.py).  A query is one directed co-watch
+// pair (anchor a, partner p); its rank is p's 0-based position in a's list of the whole catalogue (a excluded, ties by id).
+// Both launches are the plane GEMM of the kNN filter (gemm_bf16_256.hip, epilogue BE_RANK_X3) on the queries' anchor rows:
+//   cdml_rank_tau_x3    the DIAGONAL product: query i against its own partner only (one tile per 256 queries), the
+//                       partner's distance tau[i] in the arithmetic of the count
+//   cdml_rank_count_x3  query i against a catalogue block: count[i] += the rows ahead of the partner; no score is written
+// The _h2 forms take two fp16 planes per row (precision "f16x2") and the scale of the accumulated product.
+static int rank_check_planes(const char *what, int np1, const uint16_t *Q, int64_t ldq, int64_t plane_q, const uint16_t *Bk,
+                             int64_t ldb, int64_t plane_b, int D) {
+  CDML_REQUIRE(aligned16(Q) && aligned16(Bk) && !(ldq & 7) && !(ldb & 7) && !(plane_q & 7) && !(plane_b & 7) && plane_q >= D &&
+                   plane_b >= D && ldq >= np1 * plane_q + D && ldb >= np1 * plane_b + D,
+               CDML_E_ALIGN, "%s: 16-B aligned operands, strides multiples of 8, ld >= %d plane + D", what, np1);
+  return CDML_OK;
+}
+
+static void rank_gemm_args(BArgs &g, bool h2, float out_scale, const uint16_t *Q, int64_t ldq, int64_t plane_q,
+                           const uint16_t *Bk, int64_t ldb, int64_t plane_b, int nq, int n_cols, int D) {
+  g.A = reinterpret_cast<const bf16 *>(Q); g.lda = ldq;
+  g.B = reinterpret_cast<const bf16 *>(Bk); g.ldb = ldb;
+  g.M = nq; g.N = n_cols;
+  const int prod = h2 ? 3 : 6;
+  g.x3_tpp = D / 64; g.x3_plane_a = plane_q; g.x3_plane_b = plane_b; g.x3_products = prod;
+  g.K = prod * g.x3_tpp * 64; g.k_per_split = g.K;
+  g.out_scale = h2 ? out_scale : 1.0f; g.c_scale = 1.0f;
+  g.tiles_m = (nq + 255) / 256; g.tiles_n = n_cols / 256;
+}
+
+static int rank_count_impl(float out_scale, const uint16_t *Q, int64_t ldq, int64_t plane_q, const uint16_t *Bk, int64_t ldb,
+                           int64_t plane_b, int nq, int n_cols, int D, const float *q_sq, const float *b_sq, const float *tau,
+                           const int32_t *pos_id, const int32_t *self_id, int col0, int n_valid, int32_t *count,
+                           cdml_stream_t stream) {
+  const bool h2 = out_scale > 0.f;
+  CDML_REQUIRE(Q && Bk && q_sq && b_sq && tau && pos_id && self_id && count, CDML_E_BADARG, "rank_count: null pointer");
+  CDML_REQUIRE(nq > 0 && n_cols > 0 && D > 0 && col0 >= 0 && n_valid > 0, CDML_E_BADARG, "rank_count: bad size");
+  CDML_REQUIRE(n_cols % 256 == 0 && D % 64 == 0, CDML_E_UNSUPPORTED,
+               "rank_count: the catalogue block must be a multiple of 256 rows and D of 64, got %d, %d", n_cols, D);
+  int rc = rank_check_planes("rank_count", h2 ? 1 : 2, Q, ldq, plane_q, Bk, ldb, plane_b, D);
+  if (rc) return rc;
+  CDML_REQUIRE(aligned16(b_sq), CDML_E_ALIGN, "rank_count: b_sq must be 16-B aligned");
+  CDML_REQUIRE(((int64_t)nq + 256) * ldq * 2 < ((int64_t)1 << 31) && (int64_t)n_cols * ldb * 2 < ((int64_t)1 << 31), CDML_E_UNSUPPORTED,
+               "rank_count: an operand exceeds the 2 GiB buffer-descriptor range (split the launch)");
+  CDML_REQUIRE((int64_t)((nq + 255) / 256) * (n_cols / 256) < ((int64_t)1 << 31), CDML_E_UNSUPPORTED, "rank_count: too many tiles");
+  BArgs g{};
+  rank_gemm_args(g, h2, out_scale, Q, ldq, plane_q, Bk, ldb, plane_b, nq, n_cols, D);
+  g.knn_bsq = b_sq; g.knn_col0 = col0; g.knn_n_valid = n_valid;
+  g.rank_qsq = q_sq; g.rank_tau = tau; g.rank_pos = pos_id; g.rank_self = self_id; g.rank_cnt = count;
+  return h2 ? launch_gemm_f16x2_rank(g, (hipStream_t)stream) : launch_gemm_x3_rank(g, (hipStream_t)stream);
+}
+
+static int rank_tau_impl(float out_scale, const uint16_t *Q, int64_t ldq, int64_t plane_q, const uint16_t *P, int64_t ldp,
+                         int64_t plane_p, int nq, int D, const float *q_sq, const float *p_sq, float *tau_out,
+                         cdml_stream_t stream) {
+  const bool h2 = out_scale > 0.f;
+  CDML_REQUIRE(Q && P && q_sq && p_sq && tau_out, CDML_E_BADARG, "rank_tau: null pointer");
+  CDML_REQUIRE(nq > 0 && D > 0, CDML_E_BADARG, "rank_tau: bad size");
+  CDML_REQUIRE(D % 64 == 0, CDML_E_UNSUPPORTED, "rank_tau: D must be a multiple of 64, got %d", D);
+  int rc = rank_check_planes("rank_tau", h2 ? 1 : 2, Q, ldq, plane_q, P, ldp, plane_p, D);
+  if (rc) return rc;
+  CDML_REQUIRE(aligned16(p_sq), CDML_E_ALIGN, "rank_tau: p_sq must be 16-B aligned");
+  const int64_t n_pad = ((int64_t)nq + 255) / 256 * 256;
+  CDML_REQUIRE(((int64_t)nq + 256) * ldq * 2 < ((int64_t)1 << 31) && n_pad * ldp * 2 < ((int64_t)1 << 31), CDML_E_UNSUPPORTED,
+               "rank_tau: an operand exceeds the 2 GiB buffer-descriptor range (split the launch)");
+  BArgs g{};
+  rank_gemm_args(g, h2, out_scale, Q, ldq, plane_q, P, ldp, plane_p, nq, (int)n_pad, D);
+  g.tiles_n = 1;                                             // tile row tm x tile column tm: the diagonal only
+  g.knn_bsq = p_sq; g.knn_col0 = 0; g.knn_n_valid = (int)n_pad;
+  g.rank_qsq = q_sq; g.rank_tau_out = tau_out;
+  return h2 ? launch_gemm_f16x2_rank(g, (hipStream_t)stream) : launch_gemm_x3_rank(g, (hipStream_t)stream);
+}
+
+extern "C" int cdml_rank_count_x3(const uint16_t *Q, int64_t ldq, int64_t plane_q, const uint16_t *Bk, int64_t ldb,
+                                  int64_t plane_b, int nq, int n_cols, int D, const float *q_sq, const float *b_sq,
+                                  const float *tau, const int32_t *pos_id, const int32_t *self_id, int col0, int n_valid,
+                                  int32_t *count, cdml_stream_t stream) {
+  return rank_count_impl(0.f, Q, ldq, plane_q, Bk, ldb, plane_b, nq, n_cols, D, q_sq, b_sq, tau, pos_id, self_id, col0, n_valid,
+                         count, stream);
+}
+
+extern "C" int cdml_rank_count_h2(const uint16_t *Q, int64_t ldq, int64_t plane_q, const uint16_t *Bk, int64_t ldb,
+                                  int64_t plane_b, int nq, int n_cols, int D, float out_scale, const float *q_sq,
+                                  const float *b_sq, const float *tau, const int32_t *pos_id, const int32_t *self_id, int col0,
+                                  int n_valid, int32_t *count, cdml_stream_t stream) {
+  CDML_REQUIRE(out_scale > 0.f, CDML_E_BADARG, "rank_count_h2: a positive out_scale");
+  return rank_count_impl(out_scale, Q, ldq, plane_q, Bk, ldb, plane_b, nq, n_cols, D, q_sq, b_sq, tau, pos_id, self_id, col0,
+                         n_valid, count, stream);
+}
+
+extern "C" int cdml_rank_tau_x3(const uint16_t *Q, int64_t ldq, int64_t plane_q, const uint16_t *P, int64_t ldp,
+                                int64_t plane_p, int nq, int D, const float *q_sq, const float *p_sq, float *tau_out,
+                                cdml_stream_t stream) {
+  return rank_tau_impl(0.f, Q, ldq, plane_q, P, ldp, plane_p, nq, D, q_sq, p_sq, tau_out, stream);
+}
+
+extern "C" int cdml_rank_tau_h2(const uint16_t *Q, int64_t ldq, int64_t plane_q, const uint16_t *P, int64_t ldp,
+                                int64_t plane_p, int nq, int D, float out_scale, const float *q_sq, const float *p_sq,
+                                float *tau_out, cdml_stream_t stream) {
+  CDML_REQUIRE(out_scale > 0.f, CDML_E_BADARG, "rank_tau_h2: a positive out_scale");
+  return rank_tau_impl(out_scale, Q, ldq, plane_q, P, ldp, plane_p, nq, D, q_sq, p_sq, tau_out, stream);
 }

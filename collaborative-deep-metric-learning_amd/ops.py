@@ -386,6 +386,43 @@ def knn_filter_h2(Q2, plane_q, B2, plane_b, nq, n_cols, D, out_scale, q_sq, b_sq
          n_valid, _p(cnt, torch.int32), _p(cand, torch.int32), cap, _stream())
 
 
+def rank_tau_x3(Q3, plane_q, P3, plane_p, nq, D, q_sq, p_sq, tau_out):
+    """tau_out[i] = d(anchor i, partner i) on the plane kernels, in the arithmetic of rank_count_x3 (the product's diagonal):
+    Q3 = the anchors' planes [nq, >= 3 plane], P3 = the partners' planes, rows rounded up to a multiple of 256."""
+    qp, qld = _mat16(Q3)
+    pp, pld = _mat16(P3)
+    if P3.shape[0] < (nq + 255) // 256 * 256 or p_sq.numel() < P3.shape[0]:
+        raise ValueError("the partners' planes and norms need nq rounded up to 256 rows")
+    call("cdml_rank_tau_x3", qp, qld, plane_q, pp, pld, plane_p, nq, D, _p(q_sq), _p(p_sq), _p(tau_out), _stream())
+
+
+def rank_tau_h2(Q2, plane_q, P2, plane_p, nq, D, out_scale, q_sq, p_sq, tau_out):
+    """rank_tau_x3 on two fp16 planes per row (one scale s for both operands; out_scale = 1 / s^2)."""
+    qp, qld = _mat16(Q2)
+    pp, pld = _mat16(P2)
+    if P2.shape[0] < (nq + 255) // 256 * 256 or p_sq.numel() < P2.shape[0]:
+        raise ValueError("the partners' planes and norms need nq rounded up to 256 rows")
+    call("cdml_rank_tau_h2", qp, qld, plane_q, pp, pld, plane_p, nq, D, float(out_scale), _p(q_sq), _p(p_sq), _p(tau_out),
+         _stream())
+
+
+def rank_count_x3(Q3, plane_q, B3, plane_b, nq, n_cols, D, q_sq, b_sq, tau, pos_id, self_id, col0, n_valid, count):
+    """The query x catalogue-block inner products on the plane kernels with the rank count as their epilogue: count[i] (int32,
+    accumulated) += the catalogue rows col0 .. col0 + n_cols - 1 ranked ahead of pos_id[i] in self_id[i]'s list."""
+    qp, qld = _mat16(Q3)
+    bp, bld = _mat16(B3)
+    call("cdml_rank_count_x3", qp, qld, plane_q, bp, bld, plane_b, nq, n_cols, D, _p(q_sq), _p(b_sq), _p(tau),
+         _p(pos_id, torch.int32), _p(self_id, torch.int32), col0, n_valid, _p(count, torch.int32), _stream())
+
+
+def rank_count_h2(Q2, plane_q, B2, plane_b, nq, n_cols, D, out_scale, q_sq, b_sq, tau, pos_id, self_id, col0, n_valid, count):
+    """rank_count_x3 on two fp16 planes per row (one scale s for queries and catalogue; out_scale = 1 / s^2)."""
+    qp, qld = _mat16(Q2)
+    bp, bld = _mat16(B2)
+    call("cdml_rank_count_h2", qp, qld, plane_q, bp, bld, plane_b, nq, n_cols, D, float(out_scale), _p(q_sq), _p(b_sq), _p(tau),
+         _p(pos_id, torch.int32), _p(self_id, torch.int32), col0, n_valid, _p(count, torch.int32), _stream())
+
+
 def knn_merge_list(cand, cnt, cap, nq, k, best_d, best_i, overflow):
     call("cdml_knn_merge_list", _p(cand, torch.int32), _p(cnt, torch.int32), cap, nq, k, _p(best_d), _p(best_i, torch.int32),
          _p(overflow, torch.int32), _stream())

@@ -944,13 +944,19 @@ class Trainer:
       * at the end of data the last model is saved if its eval_dist beats the
         best -- train.py:301-305.
 
+    ``eval_retrieval_ks`` (e.g. (10, 50)): each evaluation also computes the exact
+    retrieval metrics of the held-out pairs (``Evaluation.retrieval_metrics`` on
+    the same embeddings) and records eval/recall@k, eval/ndcg@k, eval/map@k and
+    eval/mrr beside eval_dist; model selection and early stopping stay on
+    eval_dist.  None (default): no extra work and no extra keys.
+
     Unlike the reference (which always re-initialises, train.py:280) a
     checkpoint also carries optimizer slots, step and sampler state, so
     ``resume()`` continues a run exactly."""
 
     def __init__(self, train_step, num_epochs, n_pairs, checkpoint_dir=None, eval_features=None,
                  eval_cowatches=None, check_stop_epoch=3, best_eval_dist=1.0, eval_per_epoch=100,
-                 require_improve_num=10, logger=None, summary_path=None):
+                 require_improve_num=10, logger=None, summary_path=None, eval_retrieval_ks=None):
         from .evaluate import Evaluation
         from .predict import Prediction
         self.ts = train_step
@@ -968,6 +974,8 @@ class Trainer:
         self.require_improve_num = require_improve_num
         self.log = logger or logging.getLogger("cdml.train")
         self.history, self.eval_history, self.saved = [], [], []
+        self.eval_retrieval_ks = tuple(int(k) for k in eval_retrieval_ks) if eval_retrieval_ks else None
+        self.eval_retrieval = None
         # the reference's TensorBoard scalars (train.py:154-160, 246-249; losses.py:40-41) as one JSON line per
         # evaluation, under its names: `summary_path` (default <checkpoint_dir>/summaries.jsonl; rank 0 writes)
         if summary_path is None and checkpoint_dir:
@@ -1029,6 +1037,8 @@ class Trainer:
         self.ts.check_inputs()
         emb = self.predictor.run_features(self.evaluater.features, batch_size=10000)
         self.eval_dist = self.evaluater.mean_dist(emb, self.evaluater.cowatches)
+        if self.eval_retrieval_ks:
+            self.eval_retrieval = self.evaluater.retrieval_metrics(emb, self.evaluater.cowatches, ks=self.eval_retrieval_ks)
         if global_step <= self.check_stop_step:
             self.last_improve_num = self.total_eval_num                 # no early stop yet
         elif self.eval_dist < self.best_eval_dist:
@@ -1039,6 +1049,12 @@ class Trainer:
         self._emit_summaries(global_step)
         self.log.info("Eval %d | step %d eval_dist %.6f best %.6f", self.total_eval_num, global_step,
                       self.eval_dist, self.best_eval_dist)
+        if self.eval_retrieval_ks:
+            self.log.info("Eval %d | %s", self.total_eval_num,
+                          " ".join("%s %.6f" % (name, self.eval_retrieval[name]) for name in self._retrieval_names()))
+
+    def _retrieval_names(self):
+        return [m % k for k in self.eval_retrieval_ks for m in ("recall@%d", "ndcg@%d", "map@%d")] + ["mrr"]
 
     def _emit_summaries(self, global_step):
         """One record per evaluation with the reference's scalar names (train.py:326-327 runs summary_op exactly here)."""
@@ -1046,6 +1062,9 @@ class Trainer:
         rec.update(self.ts.summaries())
         rec["eval/eval_dist"] = float(self.eval_dist)                   # train.py:246-249
         rec["eval/best_eval_dist"] = float(self.best_eval_dist)
+        if self.eval_retrieval_ks:
+            for name in self._retrieval_names():
+                rec["eval/" + name] = float(self.eval_retrieval[name])
         self.summaries.append(rec)
         rank = torch.distributed.get_rank() if (torch.distributed.is_available() and torch.distributed.is_initialized()) else 0
         if self.summary_path and rank == 0:

@@ -360,6 +360,37 @@ int cdml_knn_filter_x3(const uint16_t *Q, int64_t ldq, int64_t plane_q, const ui
 int cdml_knn_merge_list(const void *cand, int32_t *cnt, int cap, int nq, int k, float *best_d, int32_t *best_i,
                         int32_t *overflow, cdml_stream_t stream);
 
+/* ---- exact retrieval ranks (evaluate.py: the reference's Evaluation.knn / nDCG / MAP stubs; Recall@k, nDCG@k, MAP@k,
+ * MRR are computed from them on the host side).  A query is one directed co-watch pair (anchor a, partner p); its rank
+ * pos(a, p) = #{catalogue rows j: j != a, j != p, j < n_valid, d(a,j) < d(a,p), or d(a,j) == d(a,p) and j < p} -- p's
+ * 0-based position in a's list of the whole catalogue with a itself removed, ties by id as in the kNN export; other
+ * partners of a are NOT removed.  d = max(|q|^2 + |b|^2 - 2 q.b, 0) as in cdml_knn_filter_x3, the inner products on the
+ * plane kernels; nothing of the scores is written.
+ * cdml_rank_tau_x3: tau_out[i] = d(query i, partner i) in exactly that arithmetic (the diagonal of the product: one tile
+ *   per 256 queries).  Q = the queries' anchor rows as three bf16 planes [nq][hi D | mid D | lo D] (cdml_split_f32_bf16x3);
+ *   P = their partners' rows, row i = the partner of query i, ROUNDED UP to a multiple of 256 rows (the pad rows zero);
+ *   q_sq[nq] / p_sq[that many] = |row|^2 (cdml_row_sqnorm), p_sq 16-B aligned.
+ * cdml_rank_count_x3: count[i] += #{the rule above over the n_cols (a multiple of 256) catalogue rows starting at row col0;
+ *   rows >= n_valid are padding}; tau = cdml_rank_tau_x3's, pos_id[i] = p, self_id[i] = a (catalogue row ids).  count
+ *   ACCUMULATES over launches (the caller zeroes it once): the catalogue goes through in blocks, integer adds, the same
+ *   counts in any order.  D % 64 == 0; every operand inside the 2 GiB window of a buffer descriptor (split the launch).
+ * The _h2 forms: two fp16 planes per row (cdml_split_f32_f16x2 at one scale s for queries and catalogue), out_scale =
+ * 1 / s^2.  Bad arguments return a status with cdml_last_error() before any HIP call. */
+int cdml_rank_tau_x3(const uint16_t *Q, int64_t ldq, int64_t plane_q, const uint16_t *P, int64_t ldp,
+                     int64_t plane_p, int nq, int D, const float *q_sq, const float *p_sq, float *tau_out,
+                     cdml_stream_t stream);
+int cdml_rank_count_x3(const uint16_t *Q, int64_t ldq, int64_t plane_q, const uint16_t *Bk, int64_t ldb,
+                       int64_t plane_b, int nq, int n_cols, int D, const float *q_sq, const float *b_sq,
+                       const float *tau, const int32_t *pos_id, const int32_t *self_id, int col0, int n_valid,
+                       int32_t *count, cdml_stream_t stream);
+int cdml_rank_tau_h2(const uint16_t *Q, int64_t ldq, int64_t plane_q, const uint16_t *P, int64_t ldp,
+                     int64_t plane_p, int nq, int D, float out_scale, const float *q_sq, const float *p_sq,
+                     float *tau_out, cdml_stream_t stream);
+int cdml_rank_count_h2(const uint16_t *Q, int64_t ldq, int64_t plane_q, const uint16_t *Bk, int64_t ldb,
+                       int64_t plane_b, int nq, int n_cols, int D, float out_scale, const float *q_sq,
+                       const float *b_sq, const float *tau, const int32_t *pos_id, const int32_t *self_id, int col0,
+                       int n_valid, int32_t *count, cdml_stream_t stream);
+
 /* cdml_adam_step on a weight matrix W[K][N] (row-major, contiguous: ld = N) that also writes the
  * bf16 operand copies the config-4 GEMMs read -- W^T as bf16 [N][ldt] (wt_bf16, nullable) and W as
  * bf16 [K][ldc] (wc_bf16, nullable), round-to-nearest-even of the UPDATED weights: the optimizer
