@@ -113,6 +113,8 @@ SIGNATURES = {
     "cdml_knn_filter_x3": (_i, [_p, _i64, _i64, _p, _i64, _i64, _i, _i, _i, _p, _p, _p, _i, _i, _p, _p, _i, _p]),
     "cdml_knn_filter_h2": (_i, [_p, _i64, _i64, _p, _i64, _i64, _i, _i, _i, _f, _p, _p, _p, _i, _i, _p, _p, _i, _p]),
     "cdml_knn_merge_list": (_i, [_p, _p, _i, _i, _i, _p, _p, _p, _p]),
+    "cdml_knn_desim_prep": (_i, [_p, _i, _i64, _p, _i64, _i, _i, _f, _p, _i, _p]),
+    "cdml_knn_desim": (_i, [_p, _i64, _i, _i, _p, _i, _p, _i, _i, _p, _i64, _p]),
     "cdml_rank_tau_x3": (_i, [_p, _i64, _i64, _p, _i64, _i64, _i, _i, _p, _p, _p, _p]),
     "cdml_rank_tau_h2": (_i, [_p, _i64, _i64, _p, _i64, _i64, _i, _i, _f, _p, _p, _p, _p]),
     "cdml_rank_count_x3": (_i, [_p, _i64, _i64, _p, _i64, _i64, _i, _i, _i, _p, _p, _p, _p, _p, _i, _i, _p, _p]),

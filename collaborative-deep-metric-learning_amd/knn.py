@@ -173,3 +173,159 @@ def calc_knn(embeddings, q_embeddings=None, nearest_num=51, l2_norm=True, M=80, 
     q = emb if q_embeddings is None else q_embeddings
     D, I = knn_search(emb, q, int(nearest_num), l2_norm=l2_norm, device=device, precision=precision)
     return D.cpu().numpy(), I.cpu().numpy()
+
+
+# ----------------------------------------------------------------------------------------------------------------------------
+# The rest of faiss_knn.main (faiss_knn.py:134-400): the raw-feature kNN, the cross search, near-duplicate suppression
+# ("desim") on the device (csrc/knn_desim.hip) and the text writer.
+
+DESIM_THRESHOLD = 1.4       # faiss_knn.py:187 fD_threshold
+DESIM_FI_END = 31           # faiss_knn.py:187 fI_end
+
+
+def _dev_tensor(a, dtype, device):
+    t = a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))
+    return t.to(device=device, dtype=dtype).contiguous()
+
+
+def _like(out, ref):
+    """out (a device tensor) in the kind of ``ref``: a tensor (ref's dtype and device) or an ndarray (ref's dtype)."""
+    if torch.is_tensor(ref):
+        return out.to(device=ref.device, dtype=ref.dtype)
+    return out.cpu().numpy().astype(np.asarray(ref).dtype, copy=False)
+
+
+def desim(eI, fI, fD, fD_threshold=DESIM_THRESHOLD, fI_end=DESIM_FI_END, query_ids=None, device="cuda:0"):
+    """Near-duplicate suppression of kNN lists, the rule of the reference's ``iter_desim_mp`` (faiss_knn.py:187-244) on the
+    GPU.  ``eI`` [nq, ke <= 128]: embedding-neighbour ids per query row; ``fI`` / ``fD`` [n_f, kf]: the raw-feature kNN of
+    the whole catalogue (ids / squared distances, ``calc_knn(features, ...)``).  Per row, left to right, a neighbour j that
+    is still kept removes every LATER kept neighbour found among fI[j, :fI_end] with fD <= fD_threshold (a float32 compare;
+    j itself and -1 entries excluded); the query's own id -- ``query_ids[i]``, by default the row index i, the global row
+    order of a strict or a cross list -- is removed at the end.  Removed entries become -1.  Ids < 0 or >= n_f in eI are
+    never kept.  Returns the kind and dtype of ``eI``."""
+    if eI.ndim != 2 or fI.ndim != 2 or tuple(fI.shape) != tuple(fD.shape):
+        raise ValueError("eI [nq, ke], fI and fD [n_f, kf] of one shape")
+    nq, ke = eI.shape
+    n_f, kf = fI.shape
+    fI_end = min(int(fI_end), kf)                         # fI[...][:, :f_end] (faiss_knn.py:174)
+    if not 1 <= ke <= ops.knn_list_capacity():
+        raise ValueError("desim takes at most %d columns" % ops.knn_list_capacity())
+    if not 1 <= fI_end <= 64:
+        raise ValueError("fI_end must be in [1, 64]")
+    if nq == 0:
+        return _like(torch.empty((0, ke), dtype=torch.int32), eI)
+    e = _dev_tensor(eI, torch.int64, device).clamp(-1, 2 ** 31 - 1).to(torch.int32)
+    int32 = fI.dtype == torch.int32 if torch.is_tensor(fI) else np.asarray(fI).dtype == np.int32
+    fi = _dev_tensor(fI, torch.int32 if int32 else torch.int64, device)            # (both id types read as they are)
+    fd = _dev_tensor(fD, torch.float32, device)
+    kp = 32 if fI_end <= 32 else 64
+    ff = torch.empty((n_f, kp), dtype=torch.int32, device=device)
+    ops.knn_desim_prep(fi, fd, fI_end, float(np.float32(fD_threshold)), ff)
+    qid = None if query_ids is None else _dev_tensor(query_ids, torch.int32, device)
+    out = torch.empty((nq, ke), dtype=torch.int32, device=device)
+    ops.knn_desim(e, ff, out, query_id=qid)
+    return _like(out, eI)
+
+
+def iter_desim_mp(eI, fI, fD, fD_threshold=DESIM_THRESHOLD, fI_end=DESIM_FI_END, process_num=22):
+    """The reference's signature (faiss_knn.py:187); ``process_num`` is accepted and ignored (one launch does every row)."""
+    return desim(eI, fI, fD, fD_threshold=fD_threshold, fI_end=fI_end)
+
+
+def cross_knn(embeddings, doc_location, nearest_num=81, precision="f32x3", device="cuda:0"):
+    """(crossD, crossI) as faiss_knn.py:325-336 builds them: rows [0, doc_location) (videos) search the documents, their
+    ids offset by ``doc_location`` into global ids; rows [doc_location, n) (documents) search the videos.  Rows are in
+    global order, so the query of row r is r.  The exact search (``knn_search``) stands for the reference's HNSW.  A -1
+    ("no neighbour": a side with fewer than nearest_num rows) stays -1 instead of taking the offset.  Returns the kind
+    of ``embeddings``."""
+    t = embeddings if torch.is_tensor(embeddings) else torch.from_numpy(np.asarray(embeddings, dtype=np.float32))
+    video, doc = t[:doc_location], t[doc_location:]
+    vdD, vdI = knn_search(doc, video, int(nearest_num), device=device, precision=precision)
+    vdI = torch.where(vdI >= 0, vdI + doc_location, vdI)
+    dvD, dvI = knn_search(video, doc, int(nearest_num), device=device, precision=precision)
+    D, I = torch.cat([vdD, dvD]), torch.cat([vdI, dvI])
+    if torch.is_tensor(embeddings):
+        return D, I
+    return D.cpu().numpy(), I.cpu().numpy()
+
+
+def load_decode_map(path):
+    """(decode_map {int row: guid}, encode_map {guid: int row}) from the export's JSON (faiss_knn.py:52-61)."""
+    import json
+    with open(path, "r") as f:
+        index2guid = json.load(f)
+    decode_map, encode_map = {}, {}
+    for k, v in index2guid.items():
+        decode_map[int(k)] = v
+        encode_map[v] = int(k)
+    return decode_map, encode_map
+
+
+def _host(a):
+    return a.cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+
+
+def write_knn(out_dir, D, I, decode_map, split_num=10, prefix="knn_result"):
+    """The text lists of faiss_knn.py:267-305 (``write_knn`` / ``write_process``), byte for byte: ``split_num`` files
+    ``prefix + str(index)``, parts of ``n // split_num`` rows, the remainder in the last one.  A line is
+    ``decode_map[row] + "," + "".join(decode_map[id] + "#" + str(d) + "<")`` over columns 1.. where id > 0 and
+    0.0 < d < 1.4 (d a float32, printed as its shortest repr).  Reproduced as the reference has them: column 0 is skipped
+    in every mode (in a cross list it is a real neighbour), and catalogue row 0 never appears as a neighbour (id > 0).
+    ``decode_map`` is an argument (the reference's workers read a global its ``main`` never sets)."""
+    import os
+    D, I = _host(D), _host(I)
+    if D.shape != I.shape or D.ndim != 2:
+        raise ValueError("D and I of one shape [n, k]")
+    os.makedirs(out_dir, exist_ok=True)
+    n = D.shape[0]
+    Dt = D[:, 1:].astype(np.float32, copy=False)
+    It = I[:, 1:].astype(np.int64, copy=False)
+    ok = (It > 0) & (Dt > np.float32(0.0)) & (Dt < np.float32(1.4))       # the float32 compares numpy makes
+    patch = n // split_num
+    for s in range(split_num):
+        b = s * patch
+        e = n if s == split_num - 1 else (s + 1) * patch
+        m = ok[b:e]
+        ds = Dt[b:e][m].astype(str).tolist()         # one call for the part: numpy's str of a float32 is its shortest repr
+        ids = It[b:e][m].tolist()
+        ends = np.cumsum(m.sum(1)).tolist()
+        lines, p = [], 0
+        for r, q in zip(range(b, e), ends):
+            lines.append(decode_map[r] + "," + "".join([decode_map[ids[t]] + "#" + ds[t] + "<" for t in range(p, q)]) + "\n")
+            p = q
+        with open(os.path.join(out_dir, prefix + str(s)), "w", encoding="utf-8", newline="\n") as f:
+            f.write("".join(lines))
+
+
+def export(embeddings, features, decode_map, out_dir, doc_location=343455, nearest_num=81, desim_nearest_num=26,
+           fD_threshold=DESIM_THRESHOLD, fI_end=DESIM_FI_END, precision="f32x3", device="cuda:0", split_num=10):
+    """faiss_knn.main (faiss_knn.py:359-400) with explicit arguments: the raw-feature kNN (fD, fI; k = min(desim_nearest_num,
+    nearest_num)), then -- cross mode when 0 < doc_location < n, strict mode otherwise -- the embedding kNN, desim and the
+    text lists.  Writes fD.npy, fI.npy, {strict,cross}D.npy, {strict,cross}I.npy, {strict,cross}I_desim.npy, the
+    ``split_num`` text files {strict,cross}_knn<i> and decode_map.json.  The text lists are written from the DESIMMED ids
+    in both modes (the reference's cross branch writes the un-desimmed crossI: faiss_knn.py:350, marked TODO; crossI.npy
+    keeps those).  Returns (D, I_desim) as device tensors."""
+    import json
+    import os
+    os.makedirs(out_dir, exist_ok=True)
+    n = embeddings.shape[0]
+    k_f = min(int(desim_nearest_num), int(nearest_num))
+    fD, fI = knn_search(features, features, k_f, device=device, precision=precision)
+    np.save(os.path.join(out_dir, "fD.npy"), fD.cpu().numpy())
+    np.save(os.path.join(out_dir, "fI.npy"), fI.cpu().numpy())
+    emb = embeddings if torch.is_tensor(embeddings) else torch.from_numpy(np.asarray(embeddings, dtype=np.float32))
+    if 0 < doc_location < n:
+        mode = "cross"
+        D, I = cross_knn(emb.to(device), doc_location, nearest_num=nearest_num, precision=precision, device=device)
+    else:
+        mode = "strict"
+        D, I = knn_search(emb, emb, int(nearest_num), device=device, precision=precision)
+    np.save(os.path.join(out_dir, mode + "D.npy"), D.cpu().numpy())
+    np.save(os.path.join(out_dir, mode + "I.npy"), I.cpu().numpy())
+    I_desim = desim(I, fI, fD, fD_threshold=fD_threshold, fI_end=fI_end, device=device)
+    np.save(os.path.join(out_dir, mode + "I_desim.npy"), I_desim.cpu().numpy())
+    write_knn(out_dir, D, I_desim, decode_map, split_num=split_num, prefix=mode + "_knn")
+    dm = decode_map if isinstance(decode_map, dict) else dict(enumerate(decode_map))
+    with open(os.path.join(out_dir, "decode_map.json"), "w") as f:
+        json.dump({str(k): v for k, v in dm.items()}, f)
+    return D, I_desim

@@ -428,6 +428,36 @@ def knn_merge_list(cand, cnt, cap, nq, k, best_d, best_i, overflow):
          _p(overflow, torch.int32), _stream())
 
 
+def knn_desim_prep(fI, fD, fI_end, threshold, out):
+    """The raw-feature lists fI (int32 | int64 [n_f, kf]) with their distances fD (fp32) filtered into out (int32
+    [n_f, kp], kp = 32 | 64): fI[r, t] for t < fI_end where fD <= threshold (float32), fI != r, fI >= 0; else -1."""
+    if fI.dtype not in (torch.int32, torch.int64):
+        raise ValueError("fI must be int32 or int64")
+    fp, fld = _mat(fI, fI.dtype)
+    dp, dld = _mat(fD)
+    op, _ = _mat(out, torch.int32)
+    if not out.is_contiguous() or out.shape[0] != fI.shape[0] or fD.shape[0] != fI.shape[0]:
+        raise ValueError("fI, fD and out must have the same rows (out contiguous)")
+    call("cdml_knn_desim_prep", fp, int(fI.dtype == torch.int64), fld, dp, dld, fI.shape[0], int(fI_end), float(threshold),
+         op, out.shape[1], _stream())
+    return out
+
+
+def knn_desim(eI, f_filtered, out, query_id=None, row0=0):
+    """The greedy near-duplicate rule of iter_desim_mp on every row of eI (int32 [nq, ke]) into out (int32 [nq, ke]):
+    f_filtered = knn_desim_prep's matrix; query_id (int32 [nq], optional; default row0 + i) is removed at the end."""
+    ep, eld = _mat(eI, torch.int32)
+    op, old = _mat(out, torch.int32)
+    fp, _ = _mat(f_filtered, torch.int32)
+    if not f_filtered.is_contiguous() or out.shape[0] < eI.shape[0] or out.shape[1] < eI.shape[1]:
+        raise ValueError("f_filtered must be contiguous and out at least eI's shape")
+    if query_id is not None and (not query_id.is_contiguous() or query_id.numel() < eI.shape[0]):
+        raise ValueError("query_id must be a contiguous int32 vector of nq ids")
+    call("cdml_knn_desim", ep, eld, eI.shape[0], eI.shape[1], _p(query_id, torch.int32), int(row0), fp, f_filtered.shape[1],
+         f_filtered.shape[0], op, old, _stream())
+    return out
+
+
 # ------------------------------------------------- fusion towers (N4) ---------
 EW_MUL, EW_MUL_RES, EW_ADD = 0, 1, 2
 

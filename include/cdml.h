@@ -360,6 +360,21 @@ int cdml_knn_filter_x3(const uint16_t *Q, int64_t ldq, int64_t plane_q, const ui
 int cdml_knn_merge_list(const void *cand, int32_t *cnt, int cap, int nq, int k, float *best_d, int32_t *best_i,
                         int32_t *overflow, cdml_stream_t stream);
 
+/* ---- near-duplicate suppression of the kNN export (faiss_knn.py:146-244: fliter_fI + iter_desim_mp).
+ * cdml_knn_desim_prep: the raw-feature lists (fI int32 | int64 [n_f][ldf], fD fp32 [n_f][ldd], the first fI_end columns)
+ *   filtered into out int32 [n_f][kp], kp = 32 | 64 (16-B aligned): out[r][t] = fI[r][t] where t < fI_end,
+ *   !(fD[r][t] > threshold) (a float32 compare: fD == threshold is kept), fI[r][t] != r and fI[r][t] >= 0; else -1.
+ * cdml_knn_desim: per query row i (nq rows of eI [nq][lde], ke <= CDML_KNN_LIST columns), the reference's greedy rule:
+ *   keep[c] = 0 <= eI[i][c] < n_f; for c = 0..ke-1 with keep[c]: every c2 > c with keep[c2] and eI[i][c2] in
+ *   f_filtered[eI[i][c]][:] loses keep; then keep[c] &= eI[i][c] != query_id[i] (query_id nullable: row0 + i).
+ *   out[i][c] = keep[c] ? eI[i][c] : -1 (out [nq][ldo]).  An id >= n_f is never kept (a device-side rule: no error).
+ * Both are enqueue-only and deterministic (no atomics).  Bad arguments return a status with cdml_last_error() before
+ * any HIP call. */
+int cdml_knn_desim_prep(const void *fI, int fI_is_int64, int64_t ldf, const float *fD, int64_t ldd, int n_f, int fI_end,
+                        float threshold, int32_t *out, int kp, cdml_stream_t stream);
+int cdml_knn_desim(const int32_t *eI, int64_t lde, int nq, int ke, const int32_t *query_id, int row0,
+                   const int32_t *f_filtered, int kp, int n_f, int32_t *out, int64_t ldo, cdml_stream_t stream);
+
 /* ---- exact retrieval ranks (evaluate.py: the reference's Evaluation.knn / nDCG / MAP stubs; Recall@k, nDCG@k, MAP@k,
  * MRR are computed from them on the host side).  A query is one directed co-watch pair (anchor a, partner p); its rank
  * pos(a, p) = #{catalogue rows j: j != a, j != p, j < n_valid, d(a,j) < d(a,p), or d(a,j) == d(a,p) and j < p} -- p's
