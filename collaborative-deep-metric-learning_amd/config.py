@@ -35,8 +35,11 @@ class TrainConfig:
     train_dir: str = ""
     checkpoint_dir: str = ""
     # the build's own switches (no reference counterpart)
-    mode: str = "uniform"                     # the reference's negative rule (inputs.py:125-127); "inbatch" / "semihard": BASELINE configs 1 / 2
+    mode: str = "uniform"                     # the reference's negative rule (inputs.py:125-127); "inbatch" / "semihard": BASELINE configs 1 / 2;
+                                              # "npair": the multi-class N-pair (in-batch softmax) loss instead of the hinge
     precision: str = "f32x3"                  # "f32": the fp32 MFMA; "bf16": BASELINE config 4 (fp16 catalogue)
+    temperature: float = 0.1                  # mode "npair": softmax temperature (build-defined)
+    symmetric: bool = True                    # mode "npair": also the positive -> anchor term (build-defined)
     seed: int = 1234
     weight_seed: int = 42
 
@@ -70,6 +73,8 @@ class TrainConfig:
                   learning_rate_decay=self.learning_rate_decay, seed=self.seed, weight_seed=self.weight_seed, device=device,
                   precision=self.precision, clip_gradient_norm=self.clip_gradient_norm,
                   regularization_penalty=self.regularization_penalty)
+        if self.mode == "npair":
+            kw.update(temperature=self.temperature, symmetric=self.symmetric)
         kw.update(overrides)
         return train.TrainStep(table, pairs, self.batch_size, **kw)
 

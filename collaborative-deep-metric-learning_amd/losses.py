@@ -50,3 +50,56 @@ class HingeLoss(BaseLoss):
                 "pos_dist": pos.view(-1, 1),
                 "neg_dist": neg.view(-1, 1),
                 "hinge_dist": hinge.view(-1, 1)}
+
+
+class _NPairFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pairs, temperature, symmetric, ids):
+        B, _, D = pairs.shape
+        dev = pairs.device
+        # the chain's tile rules: B up to a multiple of 256 pairs, D up to a multiple of 64 columns, zero rows / columns
+        # (a zero pair has no video id of its own: it is never read past B)
+        tile = ops.NPAIR_TILE["f32x3"]
+        Bp, Dp = (B + tile - 1) // tile * tile, (D + 63) // 64 * 64
+        e = torch.zeros((2 * Bp, Dp), dtype=torch.float32, device=dev)
+        e[:2 * B, :D] = pairs.reshape(2 * B, D)
+        rows = None
+        if ids is not None:
+            rows = torch.zeros(2 * Bp, dtype=torch.int32, device=dev)
+            rows[:2 * B] = ids.reshape(-1).to(device=dev, dtype=torch.int32)
+        ws = ops.NPairWorkspace(Bp, Dp, "f32x3", dev)
+        de = torch.zeros_like(e) if pairs.requires_grad else None
+        stats = torch.zeros(4, dtype=torch.float32, device=dev)
+        ops.npair_loss(e, rows, B, Dp, temperature, symmetric, "f32x3", de=de, stats=stats, ws=ws)
+        part = ws.ws[:4 * B].view(B, 4)                   # per anchor: loss term, 2 - 2 <a, p>, negatives' sum, their count
+        pos = part[:, 1].clone()
+        neg = part[:, 2] / part[:, 3].clamp(min=1.0)
+        ctx.de = None if de is None else de[:2 * B, :D].reshape(B, 2, D)
+        ctx.mark_non_differentiable(pos, neg, stats)
+        return stats[0].clone(), pos, neg, stats
+
+    @staticmethod
+    def backward(ctx, g_loss, *_unused):
+        return ctx.de * g_loss, None, None, None
+
+
+class NPairLoss(BaseLoss):
+    def calculate_loss(self, pairs, temperature=0.1, symmetric=True, ids=None):
+        """Multi-class N-pair (in-batch softmax) loss -- build-defined, the reference has no such loss.  pairs: float32
+        [batch, 2, embedding] device tensor of unit rows (anchor, positive); every other pair's positive is a negative of
+        an anchor, and with ``symmetric`` every other anchor a negative of a positive.  ``ids`` (int [batch, 2] video ids of
+        the rows, optional): a negative that is the same video as the anchor or its positive does not count.
+        ``temperature`` 0.1 and ``symmetric`` True are the build's defaults.  Distances are SQUARED L2 of unit rows:
+        pos_dist = |a_i - p_i|^2, neg_dist = the mean over anchor i's counted negatives ([batch, 1])."""
+        if pairs.dim() != 3 or pairs.shape[1] != 2:
+            raise ValueError("pairs must be [batch, 2, embedding]")
+        if ids is not None and ids.numel() != 2 * pairs.shape[0]:
+            raise ValueError("ids must hold one video id per row ([batch, 2])")
+        pairs = pairs.to(torch.float32)
+        loss, pos, neg, stats = _NPairFunction.apply(pairs, float(temperature), bool(symmetric), ids)
+        self.summary = {"mean_pos_dist": stats[1], "mean_neg_dist": stats[2]}
+        return {"npair_loss": loss,
+                "anchors": pairs[:, 0:1, :],
+                "positives": pairs[:, 1:2, :],
+                "pos_dist": pos.view(-1, 1),
+                "neg_dist": neg.view(-1, 1)}

@@ -311,6 +311,135 @@ def triplet_hinge_indexed(e, neg_row, B, D, margin, pos, neg, hinge, scale_scrat
          _p(hinge), _p(stats), _p(scale_scratch), dep, deld, zp, zld, lrelu_alpha, dzp, dzld, bp, bld, plane_bf, _stream())
 
 
+# ---- multi-class N-pair loss (in-batch softmax, csrc/npair.hip; build-defined) ----
+NPAIR_PRECISIONS = ("f32x3", "f32")
+# pairs per batch must be a multiple of: f32x3 -- the plane GEMMs' 256 x 256 tiles (S is B x B, the two gradient products
+# contract over B); f32 -- the fp32 GEMMs' 64-wide K tiles (fc_bwd_data / fc_bwd_weight contract over B)
+NPAIR_TILE = {"f32x3": 256, "f32": 64}
+
+
+def npair_workspace(B):
+    return int(load_library().cdml_npair_workspace(int(B)))
+
+
+def npair_stats(S, rows, B, temperature, symmetric, lse, stats, workspace):
+    """lse[:B] (and lse[B:2B] with ``symmetric``) and stats[0..3] from the score matrix S [>= B, >= B] (cdml_npair_stats).
+    rows: int32 [2B] video ids (row 2i = anchor i, 2i+1 = positive i) or None (no duplicates)."""
+    sp, sld = _mat(S)
+    call("cdml_npair_stats", sp, sld, _p(rows, torch.int32), int(B), float(temperature), 1 if symmetric else 0, _p(lse),
+         _p(stats), _p(workspace), workspace.numel() * workspace.element_size(), _stream())
+    return lse, stats
+
+
+def npair_grad_x3(S, rows, B, temperature, symmetric, lse, W_planes, plane):
+    """W_planes bf16 [>= B, >= 2 plane + B] <- the three bf16 planes of the gradient weights (cdml_npair_grad_x3)."""
+    sp, sld = _mat(S)
+    wp, wld = _mat16(W_planes)
+    call("cdml_npair_grad_x3", sp, sld, _p(rows, torch.int32), int(B), float(temperature), 1 if symmetric else 0, _p(lse),
+         wp, wld, int(plane), _stream())
+    return W_planes
+
+
+def npair_grad_f32(S, rows, B, temperature, symmetric, lse, W):
+    """W fp32 [>= B, >= B] <- the gradient weights (cdml_npair_grad_f32)."""
+    sp, sld = _mat(S)
+    wp, wld = _mat(W)
+    call("cdml_npair_grad_f32", sp, sld, _p(rows, torch.int32), int(B), float(temperature), 1 if symmetric else 0, _p(lse),
+         wp, wld, _stream())
+    return W
+
+
+class NPairWorkspace:
+    """Every buffer of the N-pair chain for Bp pairs of Dp-wide rows (Bp a multiple of NPAIR_TILE[precision]), allocated
+    once: ``npair_loss`` then allocates nothing (hipGraph-capturable).  Pad rows and columns of W stay zero."""
+
+    def __init__(self, Bp, Dp, precision, device):
+        if precision not in NPAIR_PRECISIONS:
+            raise ValueError("the N-pair loss runs on precision 'f32x3' or 'f32', not %r" % (precision,))
+        tile = NPAIR_TILE[precision]
+        if Bp < tile or Bp % tile:
+            raise ValueError("precision %r: the N-pair loss needs a batch that is a multiple of %d pairs (got %d)"
+                             % (precision, tile, Bp))
+        if Dp % 64:
+            raise ValueError("the N-pair loss needs an embedding width that is a multiple of 64 (got %d)" % Dp)
+        self.Bp, self.Dp, self.precision = int(Bp), int(Dp), precision
+        f32 = lambda *s: torch.zeros(s, dtype=torch.float32, device=device)
+        bf = lambda *s: torch.zeros(s, dtype=torch.bfloat16, device=device)
+        self.S = f32(Bp, Bp)
+        self.lse = f32(2 * Bp)
+        self.ws = torch.zeros(npair_workspace(Bp) // 4, dtype=torch.float32, device=device)
+        if precision == "f32x3":
+            self.Dq = Dq = (Dp + 255) // 256 * 256          # the plane GEMMs' N tile: narrower rows are zero-padded
+            self.A3, self.P3 = bf(Bp, 3 * Dq), bf(Bp, 3 * Dq)
+            self.PT3 = bf(Dq, 3 * Bp)                       # the positives transposed: dA = W . P's k-contiguous operand
+            self.W3 = bf(Bp, 3 * Bp)
+            nb = max(gemm_bf16x3_workspace(False, Bp, Bp, Dq), gemm_bf16x3_workspace(False, Bp, Dq, Bp),
+                     gemm_bf16x3_workspace(True, Bp, Dq, Bp), 16)
+            self.gemm_ws = torch.zeros(nb // 4, dtype=torch.float32, device=device)
+            self.dA = f32(Bp, Dq) if Dq != Dp else None     # (rows narrower than the tile: the products land here first)
+            self.dP = f32(Bp, Dq) if Dq != Dp else None
+        else:
+            self.Wf = f32(Bp, Bp)
+            self.zero_bias = f32(Dp)
+            self.bw = torch.zeros(max(fc_bwd_weight_workspace(Bp, Bp, Dp), 16) // 4, dtype=torch.float32, device=device)
+
+    def W(self):
+        """the gradient weights as one fp32 tensor [Bp, Bp] (tests, debugging)"""
+        if self.precision == "f32":
+            return self.Wf
+        Bp = self.Bp
+        return self.W3[:, :Bp].float() + self.W3[:, Bp:2 * Bp].float() + self.W3[:, 2 * Bp:].float()
+
+
+def npair_loss(e, rows, B, Dp, temperature=0.1, symmetric=True, precision="f32x3", de=None, stats=None, ws=None):
+    """The multi-class N-pair loss of B pairs and its gradient (include/cdml.h, "multi-class N-pair loss").
+    e: fp32 [2 Bp, Dp] unit rows, row 2i = anchor i, row 2i+1 = positive i (rows >= 2B zero: padding); rows: int32 [2 Bp]
+    video ids or None.  The chain: S = A P^T -> row (and column) log-sum-exp + step scalars -> W -> dA = W P, dP = W^T A,
+    written into de[0::2] / de[1::2] (fp32 [2 Bp, Dp]; None: loss only).  Precision "f32x3": fp32 operands as three
+    bf16 planes on the plane GEMMs; "f32": the fp32-MFMA GEMMs.  stats: fp32 [>= 4] (loss, mean positive distance,
+    mean counted-negative distance, fraction of counted negatives).  ws: an NPairWorkspace (allocated here if None).
+    Returns (stats, lse): lse[:B] the rows', lse[B:2B] the columns' (symmetric)."""
+    if not (temperature > 0.0) or temperature == float("inf"):
+        raise ValueError("temperature must be finite and > 0, got %r" % (temperature,))
+    Bp = e.shape[0] // 2
+    if e.shape[0] != 2 * Bp or not 1 <= B <= Bp:
+        raise ValueError("e must hold 2 Bp rows with 1 <= B <= Bp")
+    if ws is None:
+        ws = NPairWorkspace(Bp, Dp, precision, e.device)
+    elif (ws.Bp, ws.Dp, ws.precision) != (Bp, Dp, precision):
+        raise ValueError("NPairWorkspace is for %d pairs x %d columns on %s" % (ws.Bp, ws.Dp, ws.precision))
+    if stats is None:
+        stats = torch.zeros(4, dtype=torch.float32, device=e.device)
+    A, P = e[0::2, :Dp], e[1::2, :Dp]
+    lse = ws.lse
+    if precision == "f32x3":
+        Dq = ws.Dq
+        split_f32_bf16x3(A, ws.A3, Dq)
+        split_f32_bf16x3(P, ws.P3, Dq)
+        split_f32_bf16x3(P, ws.PT3, Bp, transpose=True)
+        gemm_bf16x3_nt(BE_F32, ws.A3, Dq, ws.P3, Dq, ws.S, Bp, Bp, Dq, workspace=ws.gemm_ws)
+    else:
+        fc_bwd_data(A, P, None, ws.S, Bp, Bp, Dp)              # S[i][j] = <a_i, p_j>
+    npair_stats(ws.S, rows, B, temperature, symmetric, lse, stats, ws.ws)
+    if de is None:
+        return stats, lse
+    dA, dP = de[0::2], de[1::2]
+    if precision == "f32x3":
+        npair_grad_x3(ws.S, rows, B, temperature, symmetric, lse, ws.W3, Bp)
+        oA = dA if ws.dA is None else ws.dA
+        oP = dP if ws.dP is None else ws.dP
+        gemm_bf16x3_nt(BE_F32, ws.W3, Bp, ws.PT3, Bp, oA, Bp, Dq, Bp, workspace=ws.gemm_ws)      # dA = W . P
+        gemm_bf16x3_tn(ws.W3, Bp, ws.A3, Dq, oP, Bp, Dq, Bp, workspace=ws.gemm_ws)               # dP = W^T . A
+        if ws.dA is not None:
+            dA.copy_(ws.dA[:, :Dp])
+            dP.copy_(ws.dP[:, :Dp])
+    else:
+        npair_grad_f32(ws.S, rows, B, temperature, symmetric, lse, ws.Wf)
+        fc_lrelu_fwd(ws.Wf, P, ws.zero_bias, dA, Bp, Bp, Dp, alpha=1.0)      # dA = W . P (x W form, identity activation)
+        fc_bwd_weight(ws.Wf, A, dP, None, ws.bw, Bp, Bp, Dp)                 # dP = W^T . A (x^T dy form)
+    return stats, lse
+
+
 def pair_dist(e, pairs, D, sqdist, dot, means=None):
     ep, eld = _mat(e)
     call("cdml_pair_dist", ep, eld, e.shape[0], _p(pairs, torch.int32), pairs.shape[0], D, _p(sqdist),

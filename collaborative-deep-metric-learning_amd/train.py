@@ -24,8 +24,9 @@ from . import engine, engine_bf16, engine_f16x2, engine_x3, ops
 from .inputs import MODE_INBATCH, MODE_UNIFORM
 
 # sampler mode per negative policy: "semihard" samples like "inbatch" (rows a_i, p_i)
-# and mines the negative among the embedded rows of the batch (BASELINE config 2)
-_MODES = {"uniform": MODE_UNIFORM, "inbatch": MODE_INBATCH, "semihard": MODE_INBATCH}
+# and mines the negative among the embedded rows of the batch (BASELINE config 2); "npair" samples like "inbatch" too and
+# takes the multi-class N-pair loss over every in-batch positive (build-defined: ops.npair_loss)
+_MODES = {"uniform": MODE_UNIFORM, "inbatch": MODE_INBATCH, "semihard": MODE_INBATCH, "npair": MODE_INBATCH}
 
 
 def exponential_decay(base_lr, global_step, decay_steps, decay_rate, staircase=True):
@@ -46,7 +47,7 @@ class TrainStep:
                  exchange=None, grad_sync=None, slot0=0, batch_global=None, use_graph=False,
                  prefetch=True, precision="auto", train_table=False, gather_ahead="auto",
                  clip_gradient_norm=0.0, regularization_penalty=0.0, l2_penalty=1e-8,
-                 grad_sync_mode="bucketed"):
+                 grad_sync_mode="bucketed", temperature=0.1, symmetric=True):
         """table: FeatureTable (whole catalogue, or this rank's shard when
         ``exchange`` is given); pairs: int32 [P,2] device tensor; ``exchange`` /
         ``grad_sync``: the multi-GPU hooks of cdml_amd.dist (None on one GPU).
@@ -83,9 +84,30 @@ class TrainStep:
         follow); "two" = the first layer's weight gradient as ONE full split-K launch, its all-reduce
         (86 % of the bytes) under the second layer's launch, [dW2|db2] after it; "single" = the one
         stream-K launch of the single-GPU step followed by ONE all-reduce of the whole flat gradient
-        (fastest kernels, the collective exposed)."""
+        (fastest kernels, the collective exposed).
+        ``mode="npair"``: the multi-class N-pair (in-batch softmax) loss over the in-batch sampler's pairs instead of the
+        hinge -- ``temperature`` (default 0.1) and ``symmetric`` (default True: the mean of the anchor->positive and
+        positive->anchor terms), both build-defined; the reference has no such loss.  One GPU, fp32 catalogue, precision
+        "f32x3" (a batch that is a multiple of 256 pairs; what "auto" picks then) or "f32" (a multiple of 64); the
+        embeddings' gradient goes through the separate l2norm backward (no fused tail, so no ``variance`` summary)."""
         if mode not in _MODES:
-            raise ValueError("mode must be 'uniform', 'inbatch' or 'semihard'")
+            raise ValueError("mode must be 'uniform', 'inbatch', 'semihard' or 'npair'")
+        if mode == "npair":
+            if exchange is not None or grad_sync is not None:
+                raise ValueError("mode 'npair' runs on one GPU: data parallelism (exchange / grad_sync) is not supported")
+            if train_table:
+                raise ValueError("mode 'npair' does not train the catalogue (train_table=True is not supported)")
+            if precision in ("auto", None) and table.data.dtype != torch.float16:
+                precision = "f32x3" if int(batch_size) % ops.NPAIR_TILE["f32x3"] == 0 else "f32"
+            if precision not in ops.NPAIR_PRECISIONS:
+                raise ValueError("mode 'npair' runs on precision 'f32x3' or 'f32' (an fp32 catalogue), not %r" % (precision,))
+            tile = ops.NPAIR_TILE[precision]
+            if int(batch_size) % tile:
+                raise ValueError("mode 'npair' on precision %r needs a batch that is a multiple of %d pairs (got %d)"
+                                 % (precision, tile, int(batch_size)))
+            temperature = float(temperature)
+            if not (0.0 < temperature < float("inf")):
+                raise ValueError("temperature must be finite and > 0, got %r" % (temperature,))
         if optimizer not in ("adam", "lars", "momentum"):
             raise ValueError("optimizer must be 'adam', 'lars' or 'momentum'")
         self.device = torch.device(device)
@@ -108,6 +130,7 @@ class TrainStep:
         self.rows_per_triplet = 3 if mode == "uniform" else 2
         self.R = self.B * self.rows_per_triplet
         self.margin = float(margin)
+        self.temperature, self.symmetric = float(temperature), bool(symmetric)
         self.seed = int(seed)
         self.optimizer = optimizer
         self.base_lr = float(base_learning_rate)
@@ -202,6 +225,8 @@ class TrainStep:
             self.sqn = torch.zeros(2 * self.B, dtype=f32, device=dev)
             self.neg_row = torch.zeros(self.B, dtype=i32, device=dev)
             self.scale = torch.zeros(self.B, dtype=f32, device=dev)
+        if mode == "npair":                                  # S, W and the plane copies of the loss chain
+            self.npair_ws = ops.NPairWorkspace(self.B, self.layout.Dp, precision, dev)
         self.step_dev = torch.zeros(1, dtype=torch.int64, device=dev)
         self.lr_dev = torch.full((1,), self.base_lr, dtype=f32, device=dev)
         self._lr_host = self.base_lr
@@ -450,7 +475,7 @@ class TrainStep:
     def _forward_loss(self, with_grad=True):
         # uniform / in-batch negatives: one launch normalises z, takes the loss and starts the
         # backward pass (semi-hard mining needs every embedded row first: separate kernels)
-        fused = with_grad and self.mode != "semihard"
+        fused = with_grad and self.mode not in ("semihard", "npair")
         # (semi-hard mining on the plane kernels: the miner's prep launch normalises z itself -- round 6)
         mine_norm = (self.mode == "semihard" and getattr(self, "mine_fused", False)
                      and os.environ.get("CDML_MINE_NORM", "1") != "0")
@@ -473,7 +498,11 @@ class TrainStep:
             self.ws.dz2_planes_done = self.x3 or self.h2
             return
         de = self.ws.de if with_grad else None
-        if self.mode == "uniform":
+        if self.mode == "npair":
+            # S = A P^T -> row / column log-sum-exp -> W -> dA = W P, dP = W^T A into de; tower_backward takes de from there
+            ops.npair_loss(self.ws.e, self.idx, self.B, L.Dp, self.temperature, self.symmetric, self.precision, de=de,
+                           stats=self.stats, ws=self.npair_ws)
+        elif self.mode == "uniform":
             ops.triplet_hinge(self.ws.e, self.B, L.Dp, self.margin, self.pos, self.neg, self.hinge,
                               self.stats, de)
         elif self.mode == "semihard":
@@ -982,7 +1011,7 @@ class Trainer:
             summary_path = os.path.join(checkpoint_dir, "summaries.jsonl")
         self.summary_path = summary_path
         self.summaries = []
-        if summary_path and train_step.mode != "semihard" and train_step.var_ws is None:
+        if summary_path and train_step.mode not in ("semihard", "npair") and train_step.var_ws is None:
             train_step.enable_variance()                                # calc_var (train.py:67-71,151) rides in the fused tail
         self.evaluater = None
         if eval_cowatches is not None:

@@ -300,6 +300,32 @@ int cdml_triplet_hinge_indexed_tail(const float *e, int64_t lde, const int32_t *
                                     uint16_t *dz2_bf16, int64_t ldbf, int64_t plane_bf,
                                     cdml_stream_t stream);
 
+/* ---- multi-class N-pair loss (in-batch softmax; build-defined, the reference has only the hinge) --------------
+ * A batch of B pairs: S[i][j] = <a_i, p_j> fp32 [B][lds] (the anchor x positive product), ids int32[2B] with
+ * ids[2i] = id(a_i), ids[2i+1] = id(p_i) (TrainStep.idx of the in-batch sampler; NULL = every row its own video),
+ * t = temperature.  Column j counts for row i when j == i or id(p_j) is neither id(a_i) nor id(p_i);
+ * row i counts for column j (symmetric) when i == j or id(a_i) is neither id(a_j) nor id(p_j).
+ * cdml_npair_stats: lse[i] = log sum_j (counted) exp(S_ij / t); symmetric != 0 also lse[B + j] = the column's
+ *   (lse float[2B]).  stats[0] = mean_i (lse_i - S_ii / t), or the mean of that and the column term (symmetric);
+ *   [1] = mean 2 - 2 S_ii, [2] = mean 2 - 2 S_ij over the counted row-term negatives, [3] = their fraction of the
+ *   B (B - 1) off-diagonal entries (squared distances of unit rows).  workspace: cdml_npair_workspace(B) bytes,
+ *   16-B aligned.
+ * cdml_npair_grad_x3 / _f32: the gradient weights W_ij = (c_ij exp(S_ij / t - lse_i) - [i == j]) / (B t), c the row
+ *   rule; symmetric: the mean of that and the column term's.  Entries a rule does not count get exactly 0 from it.
+ *   dL/da_i = sum_j W_ij p_j, dL/dp_j = sum_i W_ij a_i.  _x3 writes W as three exact bf16 planes
+ *   (cdml_split_f32_bf16x3's split) W[i][p * plane + j] (8-B aligned, plane >= B, ldw >= 2 plane + B); _f32 as fp32
+ *   W[B][ldw] (16-B aligned, ldw >= B).  Only columns < B are written: a caller padding B to a GEMM tile keeps the pad
+ *   of W zero.  S 16-B aligned, lds >= B; leading dimensions multiples of 4.
+ * Enqueue-only, no atomics, fixed summation orders: bit-reproducible.  Bad arguments (null pointers, B < 1, t <= 0 or
+ * not finite, short or misaligned leading dimensions, a short workspace) return CDML_E_BADARG before any HIP call. */
+size_t cdml_npair_workspace(int B);
+int cdml_npair_stats(const float *S, int64_t lds, const int32_t *ids, int B, float temperature, int symmetric,
+                     float *lse, float *stats, void *workspace, size_t workspace_bytes, cdml_stream_t stream);
+int cdml_npair_grad_x3(const float *S, int64_t lds, const int32_t *ids, int B, float temperature, int symmetric,
+                       const float *lse, uint16_t *W, int64_t ldw, int64_t plane, cdml_stream_t stream);
+int cdml_npair_grad_f32(const float *S, int64_t lds, const int32_t *ids, int B, float temperature, int symmetric,
+                        const float *lse, float *W, int64_t ldw, cdml_stream_t stream);
+
 /* ---- evaluation metric: Evaluation.mean_dist / mean_cos_dist (evaluate.py:57-90)
  * e[n_rows][lde] embeddings; pairs int32[P][2] row indices (must be < n_rows).
  * sqdist[P] = sum (a-b)^2, dot[P] = sum a*b; means float[4] (may be NULL):
