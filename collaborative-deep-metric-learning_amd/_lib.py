@@ -107,6 +107,12 @@ SIGNATURES = {
     "cdml_npair_stats": (_i, [_p, _i64, _p, _i, _f, _i, _p, _p, _p, _sz, _p]),
     "cdml_npair_grad_x3": (_i, [_p, _i64, _p, _i, _f, _i, _p, _p, _i64, _i64, _p]),
     "cdml_npair_grad_f32": (_i, [_p, _i64, _p, _i, _f, _i, _p, _p, _i64, _p]),
+    "cdml_npair_memory_workspace": (_sz, [_i, _i]),
+    "cdml_npair_memory_stats": (_i, [_p, _i64, _p, _i, _i64, _p, _i, _f, _i, _p, _p, _p, _sz, _p]),
+    "cdml_npair_memory_grad_x3": (_i, [_p, _i64, _p, _i, _i64, _p, _i, _f, _i, _p, _p, _i64, _i64, _p]),
+    "cdml_npair_memory_grad_f32": (_i, [_p, _i64, _p, _i, _i64, _p, _i, _f, _i, _p, _p, _i64, _p]),
+    "cdml_npair_memory_push": (_i, [_p, _i64, _p, _i, _i, _u64, _p, _i64, _i, _p, _i64, _p, _p, _i64, _i64, _p, _i64,
+                                    _i64, _p]),
     "cdml_pair_dist": (_i, [_p, _i64, _i, _p, _i, _i, _p, _p, _p, _p]),
     "cdml_cowatch_workspace": (_sz, [_i64]),
     "cdml_cowatch_graph": (_i, [_p, _i64, _p, _p, _p, _p, _p, _sz, _p]),

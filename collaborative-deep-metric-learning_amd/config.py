@@ -40,6 +40,8 @@ class TrainConfig:
     precision: str = "f32x3"                  # "f32": the fp32 MFMA; "bf16": BASELINE config 4 (fp16 catalogue)
     temperature: float = 0.1                  # mode "npair": softmax temperature (build-defined)
     symmetric: bool = True                    # mode "npair": also the positive -> anchor term (build-defined)
+    memory_size: int = 0                      # mode "npair": rows of the cross-batch memory of negatives (0 = none; build-defined)
+    memory_start: int = 0                     # mode "npair": the first step that pushes into that memory
     seed: int = 1234
     weight_seed: int = 42
 
@@ -74,7 +76,10 @@ class TrainConfig:
                   precision=self.precision, clip_gradient_norm=self.clip_gradient_norm,
                   regularization_penalty=self.regularization_penalty)
         if self.mode == "npair":
-            kw.update(temperature=self.temperature, symmetric=self.symmetric)
+            kw.update(temperature=self.temperature, symmetric=self.symmetric, memory_size=self.memory_size,
+                      memory_start=self.memory_start)
+        elif self.memory_size:
+            kw.update(memory_size=self.memory_size)       # (TrainStep refuses it outside mode "npair")
         kw.update(overrides)
         return train.TrainStep(table, pairs, self.batch_size, **kw)
 

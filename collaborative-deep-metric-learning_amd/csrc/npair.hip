@@ -17,6 +17,13 @@
 //   k_npair_stats     one block: the step scalars from the per-row partials in a fixed order (as k_loss_stats does)
 //   k_npair_w<X3>     W, four columns per lane, as three exact bf16 planes [B][hi | mid | lo] (the operand layout of the
 //                     plane GEMMs, split as cdml_split_f32_bf16x3 splits) or as fp32 (precision "f32")
+//
+// Cross-batch memory (cdml_npair_memory_*): S = A [P; Mem]^T is [B][B + M], the memory's M columns at mem_col.  The row term
+// also counts slot k when mem_id[k] >= 0 is neither id(a_i) nor id(p_i); the column term stays over the in-batch block.
+//   k_npair_rows<true>   the row pass going on over the memory columns (float4 / int4 per lane)
+//   k_npair_mem_w<X3>    W's memory block, c_ik exp(S_ik / t - lse_i) / (B t) (halved with `symmetric`)
+//   k_npair_mem_push<X3> the ring push of the step's positives (after the products that read the memory), fp32 rows + ids,
+//                        and for X3 the slots' row-plane and transposed-plane operand images
 #include "common.h"
 #include <math.h>
 
@@ -63,10 +70,26 @@ __device__ __forceinline__ bool col_counts(const int32_t *ids, int i, int j, int
   return q != idaj && q != idpj;
 }
 
+// memory slot k counts for anchor i when it holds a row (mem_id >= 0) of neither the anchor's nor its positive's video
+__device__ __forceinline__ bool mem_counts(const int32_t *ids, int q, int ida, int idp) {
+  return q >= 0 && (!ids || (q != ida && q != idp));
+}
+
+__device__ __forceinline__ void mem_add(const int32_t *ids, float v, int q, int ida, int idp, float inv_t, float &m, float &s,
+                                        float &nsum, float &ncnt) {
+  if (!mem_counts(ids, q, ida, idp)) return;
+  lse_add(m, s, v * inv_t);
+  nsum += 2.f - 2.f * v;
+  ncnt += 1.f;
+}
+
 // part[4 i .. 4 i + 3] = {lse_i - S_ii / t, 2 - 2 S_ii, sum over the counted j != i of 2 - 2 S_ij, their count}
+// MEM: the row goes on over the n_mem memory columns at mem_col .. mem_col + n_mem - 1 of S (cross-batch memory, slot ids mem_id;
+// four columns per lane per pass, after the in-batch columns: the same fixed order on every run)
+template <bool MEM>
 __global__ void __launch_bounds__(kNpThreads)
 k_npair_rows(const float *__restrict__ S, int64_t lds, const int32_t *__restrict__ ids, int B, float inv_t,
-             float *__restrict__ lse, float *__restrict__ part) {
+             float *__restrict__ lse, float *__restrict__ part, int64_t mem_col, const int32_t *__restrict__ mem_id, int n_mem) {
   __shared__ float sm[kNpThreads / kWave][4];
   const int i = blockIdx.x;
   const float *row = S + (int64_t)i * lds;
@@ -79,6 +102,17 @@ k_npair_rows(const float *__restrict__ S, int64_t lds, const int32_t *__restrict
     if (j != i) {
       nsum += 2.f - 2.f * v;
       ncnt += 1.f;
+    }
+  }
+  if constexpr (MEM) {
+    const float *mrow = row + mem_col;
+    for (int k = 4 * threadIdx.x; k < n_mem; k += 4 * kNpThreads) {
+      const float4 v = *reinterpret_cast<const float4 *>(mrow + k);
+      const int4 q = *reinterpret_cast<const int4 *>(mem_id + k);
+      mem_add(ids, v.x, q.x, ida, idp, inv_t, m, s, nsum, ncnt);
+      mem_add(ids, v.y, q.y, ida, idp, inv_t, m, s, nsum, ncnt);
+      mem_add(ids, v.z, q.z, ida, idp, inv_t, m, s, nsum, ncnt);
+      mem_add(ids, v.w, q.w, ida, idp, inv_t, m, s, nsum, ncnt);
     }
   }
 #pragma unroll
@@ -142,9 +176,10 @@ k_npair_col_fold(const float *__restrict__ S, int64_t lds, int B, int chunks, fl
 }
 
 // stats[0] = loss, [1] = mean |a_i - p_i|^2, [2] = mean |a_i - p_j|^2 over the counted row-term negatives, [3] = the fraction
-// of off-diagonal row-term entries that count (squared distances of unit rows: 2 - 2 S)
+// of off-diagonal row-term entries that count (squared distances of unit rows: 2 - 2 S); M > 0: the memory's B M entries
+// are row-term negatives too
 __global__ void __launch_bounds__(1024)
-k_npair_stats(const float *__restrict__ part, const float *__restrict__ closs, int B, int symmetric,
+k_npair_stats(const float *__restrict__ part, const float *__restrict__ closs, int B, int symmetric, int M,
               float *__restrict__ stats) {
   __shared__ float sm[5][1024 / kWave];
   float acc[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
@@ -171,7 +206,8 @@ k_npair_stats(const float *__restrict__ part, const float *__restrict__ closs, i
     stats[0] = symmetric ? 0.5f * (t[0] / fb + t[4] / fb) : t[0] / fb;
     stats[1] = t[1] / fb;
     stats[2] = t[3] > 0.f ? t[2] / t[3] : 0.f;
-    stats[3] = B > 1 ? t[3] / (fb * (float)(B - 1)) : 0.f;
+    const float den = M ? fb * (float)(B - 1) + fb * (float)M : fb * (float)(B - 1);
+    stats[3] = den > 0.f ? t[3] / den : 0.f;
   }
 }
 
@@ -243,6 +279,95 @@ k_npair_w(const float *__restrict__ S, int64_t lds, const int32_t *__restrict__ 
   }
 }
 
+// The memory block of W: W[i][mem_col + k] = c_ik exp(S[i][mem_col + k] / t - lse_i) * scale (scale = 1 / (B t), halved
+// with `symmetric`: the column term has no memory part).  Row i = blockIdx.x, slots 4 (blockIdx.y * kNpThreads +
+// threadIdx.x) .. + 3 (M a multiple of 4)
+template <bool X3>
+__global__ void __launch_bounds__(kNpThreads)
+k_npair_mem_w(const float *__restrict__ S, int64_t lds, int64_t mem_col, const int32_t *__restrict__ ids,
+              const int32_t *__restrict__ mem_id, int M, float inv_t, const float *__restrict__ lse, float scale,
+              void *__restrict__ Wout, int64_t ldw, int64_t plane) {
+  const int i = blockIdx.x;
+  const int k0 = (blockIdx.y * kNpThreads + threadIdx.x) * 4;
+  if (k0 >= M) return;
+  const int ida = ids ? ids[2 * i] : 0, idp = ids ? ids[2 * i + 1] : 0;
+  const float lr = lse[i];
+  const float4 v = *reinterpret_cast<const float4 *>(S + (int64_t)i * lds + mem_col + k0);
+  const int4 q = *reinterpret_cast<const int4 *>(mem_id + k0);
+  const float w[4] = {mem_counts(ids, q.x, ida, idp) ? expf(v.x * inv_t - lr) * scale : 0.f,
+                      mem_counts(ids, q.y, ida, idp) ? expf(v.y * inv_t - lr) * scale : 0.f,
+                      mem_counts(ids, q.z, ida, idp) ? expf(v.z * inv_t - lr) * scale : 0.f,
+                      mem_counts(ids, q.w, ida, idp) ? expf(v.w * inv_t - lr) * scale : 0.f};
+  if (X3) {
+    using bf4 = __attribute__((ext_vector_type(4))) __bf16;
+    bf4 h, m, l;
+    for (int c = 0; c < 4; ++c) {
+      __bf16 a, b, d;
+      np_split3(w[c], a, b, d);
+      h[c] = a;
+      m[c] = b;
+      l[c] = d;
+    }
+    __bf16 *dst = static_cast<__bf16 *>(Wout) + (int64_t)i * ldw + mem_col + k0;
+    *reinterpret_cast<bf4 *>(dst) = h;
+    *reinterpret_cast<bf4 *>(dst + plane) = m;
+    *reinterpret_cast<bf4 *>(dst + 2 * plane) = l;
+  } else {
+    *reinterpret_cast<float4 *>(static_cast<float *>(Wout) + (int64_t)i * ldw + mem_col + k0) =
+        make_float4(w[0], w[1], w[2], w[3]);
+  }
+}
+
+constexpr int kPushTile = 64;
+
+// The ring push of step t = step_imm + *step_dev (when t >= start): slots s .. s + B - 1, s = ((t - start) mod (M / B)) B,
+// take the B positives P[r] (fp32 rows, D columns) and their ids ids[2 r + 1].  X3: also the slots' operand images --
+// R3[s + r][p * plane_r + c] and T3[c][p * plane_t + s + r] = bf16 plane p of P[r][c] (cdml_split_f32_bf16x3's split),
+// the transposed one through a 64 x 64 LDS tile so that both stores run along contiguous addresses
+template <bool X3>
+__global__ void __launch_bounds__(kNpThreads)
+k_npair_mem_push(const float *__restrict__ P, int64_t ldp, const int32_t *__restrict__ ids, int B, int D, uint64_t step_imm,
+                 const uint64_t *__restrict__ step_dev, int64_t start, int M, float *__restrict__ mem, int64_t ldm,
+                 int32_t *__restrict__ mem_id, __bf16 *__restrict__ R3, int64_t ldr, int64_t plane_r,
+                 __bf16 *__restrict__ T3, int64_t ldt, int64_t plane_t) {
+  __shared__ float tile[kPushTile][kPushTile + 1];
+  const uint64_t t = step_imm + (step_dev ? *step_dev : 0);
+  if (t < (uint64_t)start) return;
+  const int64_t s = (int64_t)((t - (uint64_t)start) % (uint64_t)(M / B)) * B;
+  const int c0 = blockIdx.x * kPushTile, r0 = blockIdx.y * kPushTile;
+  const int lane = threadIdx.x % kPushTile, sub = threadIdx.x / kPushTile;
+  constexpr int kStep = kNpThreads / kPushTile;
+  if (blockIdx.x == 0 && threadIdx.x < kPushTile && r0 + (int)threadIdx.x < B)
+    mem_id[s + r0 + threadIdx.x] = ids[2 * (r0 + threadIdx.x) + 1];
+  for (int r = sub; r < kPushTile; r += kStep) {
+    const int gr = r0 + r, gc = c0 + lane;
+    if (gr >= B || gc >= D) continue;
+    const float v = P[(int64_t)gr * ldp + gc];
+    mem[(s + gr) * ldm + gc] = v;
+    if (X3) {
+      __bf16 h, m, l;
+      np_split3(v, h, m, l);
+      __bf16 *d = R3 + (s + gr) * ldr + gc;
+      d[0] = h;
+      d[plane_r] = m;
+      d[2 * plane_r] = l;
+      tile[r][lane] = v;
+    }
+  }
+  if (!X3) return;
+  __syncthreads();
+  for (int c = sub; c < kPushTile; c += kStep) {
+    const int gr = r0 + lane, gc = c0 + c;
+    if (gr >= B || gc >= D) continue;
+    __bf16 h, m, l;
+    np_split3(tile[lane][c], h, m, l);
+    __bf16 *d = T3 + (int64_t)gc * ldt + s + gr;
+    d[0] = h;
+    d[plane_t] = m;
+    d[2 * plane_t] = l;
+  }
+}
+
 int np_chunks(int B) { return (B + kNpChunk - 1) / kNpChunk; }
 
 // workspace floats: part [4B] | closs [B] | cm [chunks B] | cs [chunks B]
@@ -281,7 +406,8 @@ extern "C" int cdml_npair_stats(const float *S, int64_t lds, const int32_t *ids,
   float *part = static_cast<float *>(workspace), *closs = part + 4 * (size_t)B;
   float *cm = closs + B, *cs = cm + (size_t)chunks * B;
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(k_npair_rows, dim3(B), dim3(kNpThreads), 0, st, S, lds, ids, B, inv_t, lse, part);
+  hipLaunchKernelGGL(k_npair_rows<false>, dim3(B), dim3(kNpThreads), 0, st, S, lds, ids, B, inv_t, lse, part, (int64_t)0,
+                     (const int32_t *)nullptr, 0);
   if (int rc = check_launch("npair_stats rows")) return rc;
   if (symmetric) {
     const unsigned gx = (unsigned)((B + kNpThreads - 1) / kNpThreads);
@@ -290,7 +416,7 @@ extern "C" int cdml_npair_stats(const float *S, int64_t lds, const int32_t *ids,
     hipLaunchKernelGGL(k_npair_col_fold, dim3(gx), dim3(kNpThreads), 0, st, S, lds, B, chunks, inv_t, cm, cs, lse, closs);
     if (int rc = check_launch("npair_stats column fold")) return rc;
   }
-  hipLaunchKernelGGL(k_npair_stats, dim3(1), dim3(1024), 0, st, part, closs, B, symmetric ? 1 : 0, stats);
+  hipLaunchKernelGGL(k_npair_stats, dim3(1), dim3(1024), 0, st, part, closs, B, symmetric ? 1 : 0, 0, stats);
   return check_launch("npair_stats");
 }
 
@@ -319,4 +445,112 @@ extern "C" int cdml_npair_grad_f32(const float *S, int64_t lds, const int32_t *i
   hipLaunchKernelGGL(k_npair_w<false>, grid, dim3(kNpThreads), 0, (hipStream_t)stream, S, lds, ids, B, 1.0f / temperature,
                      symmetric ? 1 : 0, lse, 1.0f / ((float)B * temperature), (void *)W, ldw, (int64_t)0);
   return check_launch("npair_grad_f32");
+}
+
+// ---- cross-batch memory (XBM, Wang et al. 2020): a ring of M earlier positives as extra row-term columns of S ----------
+
+namespace cdml {
+namespace {
+
+int npm_check(const char *who, const float *S, int64_t lds, int B, int64_t mem_col, const int32_t *mem_id, int M,
+              float temperature, const float *lse) {
+  CDML_REQUIRE(S && lse && mem_id, CDML_E_BADARG, "%s: null pointer", who);
+  CDML_REQUIRE(B >= 1, CDML_E_BADARG, "%s: B must be >= 1, got %d", who, B);
+  CDML_REQUIRE(M >= 4 && (M & 3) == 0, CDML_E_BADARG, "%s: the memory size M must be a positive multiple of 4, got %d", who, M);
+  CDML_REQUIRE(isfinite(temperature) && temperature > 0.f, CDML_E_BADARG, "%s: temperature must be finite and > 0, got %g",
+               who, (double)temperature);
+  CDML_REQUIRE(mem_col >= B && (mem_col & 3) == 0 && lds >= mem_col + M && (lds & 3) == 0 && aligned16(S) && aligned16(mem_id),
+               CDML_E_BADARG,
+               "%s: S and mem_id need 16-B aligned bases, mem_col >= B (%d) and lds >= mem_col + M (%d), multiples of 4 "
+               "(got mem_col %lld, lds %lld)", who, B, M, (long long)mem_col, (long long)lds);
+  return CDML_OK;
+}
+
+}  // namespace
+}  // namespace cdml
+
+extern "C" size_t cdml_npair_memory_workspace(int B, int M) { return M >= 0 ? np_ws_bytes(B) : 0; }
+
+extern "C" int cdml_npair_memory_stats(const float *S, int64_t lds, const int32_t *ids, int B, int64_t mem_col,
+                                       const int32_t *mem_id, int M, float temperature, int symmetric, float *lse,
+                                       float *stats, void *workspace, size_t workspace_bytes, cdml_stream_t stream) {
+  if (int rc = npm_check("npair_memory_stats", S, lds, B, mem_col, mem_id, M, temperature, lse)) return rc;
+  CDML_REQUIRE(stats && workspace, CDML_E_BADARG, "npair_memory_stats: null pointer");
+  CDML_REQUIRE(aligned16(workspace) && workspace_bytes >= np_ws_bytes(B), CDML_E_BADARG,
+               "npair_memory_stats: the workspace must be 16-B aligned and hold cdml_npair_memory_workspace(%d, %d) = %zu "
+               "bytes (got %zu)", B, M, np_ws_bytes(B), workspace_bytes);
+  const float inv_t = 1.0f / temperature;
+  const int chunks = np_chunks(B);
+  float *part = static_cast<float *>(workspace), *closs = part + 4 * (size_t)B;
+  float *cm = closs + B, *cs = cm + (size_t)chunks * B;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(k_npair_rows<true>, dim3(B), dim3(kNpThreads), 0, st, S, lds, ids, B, inv_t, lse, part, mem_col, mem_id,
+                     M);
+  if (int rc = check_launch("npair_memory_stats rows")) return rc;
+  if (symmetric) {                                   // the column term: the in-batch block as it stands, through lds
+    const unsigned gx = (unsigned)((B + kNpThreads - 1) / kNpThreads);
+    hipLaunchKernelGGL(k_npair_cols, dim3(gx, chunks), dim3(kNpThreads), 0, st, S, lds, ids, B, inv_t, cm, cs);
+    if (int rc = check_launch("npair_memory_stats columns")) return rc;
+    hipLaunchKernelGGL(k_npair_col_fold, dim3(gx), dim3(kNpThreads), 0, st, S, lds, B, chunks, inv_t, cm, cs, lse, closs);
+    if (int rc = check_launch("npair_memory_stats column fold")) return rc;
+  }
+  hipLaunchKernelGGL(k_npair_stats, dim3(1), dim3(1024), 0, st, part, closs, B, symmetric ? 1 : 0, M, stats);
+  return check_launch("npair_memory_stats");
+}
+
+extern "C" int cdml_npair_memory_grad_x3(const float *S, int64_t lds, const int32_t *ids, int B, int64_t mem_col,
+                                         const int32_t *mem_id, int M, float temperature, int symmetric, const float *lse,
+                                         uint16_t *W, int64_t ldw, int64_t plane, cdml_stream_t stream) {
+  if (int rc = npm_check("npair_memory_grad_x3", S, lds, B, mem_col, mem_id, M, temperature, lse)) return rc;
+  CDML_REQUIRE(W, CDML_E_BADARG, "npair_memory_grad_x3: null pointer");
+  CDML_REQUIRE(plane >= mem_col + M && ldw >= 2 * plane + mem_col + M && (plane & 3) == 0 && (ldw & 3) == 0 &&
+                   (reinterpret_cast<uintptr_t>(W) & 7) == 0,
+               CDML_E_BADARG,
+               "npair_memory_grad_x3: W needs an 8-B aligned base, plane >= mem_col + M (%lld) and ldw >= 2 plane + mem_col + M, "
+               "both multiples of 4 (got plane %lld, ldw %lld)", (long long)(mem_col + M), (long long)plane, (long long)ldw);
+  const dim3 grid((unsigned)B, (unsigned)((M + 4 * kNpThreads - 1) / (4 * kNpThreads)));
+  const float scale = (symmetric ? 0.5f : 1.0f) / ((float)B * temperature);
+  hipLaunchKernelGGL(k_npair_mem_w<true>, grid, dim3(kNpThreads), 0, (hipStream_t)stream, S, lds, mem_col, ids, mem_id, M,
+                     1.0f / temperature, lse, scale, (void *)W, ldw, plane);
+  return check_launch("npair_memory_grad_x3");
+}
+
+extern "C" int cdml_npair_memory_grad_f32(const float *S, int64_t lds, const int32_t *ids, int B, int64_t mem_col,
+                                          const int32_t *mem_id, int M, float temperature, int symmetric, const float *lse,
+                                          float *W, int64_t ldw, cdml_stream_t stream) {
+  if (int rc = npm_check("npair_memory_grad_f32", S, lds, B, mem_col, mem_id, M, temperature, lse)) return rc;
+  CDML_REQUIRE(W, CDML_E_BADARG, "npair_memory_grad_f32: null pointer");
+  CDML_REQUIRE(ldw >= mem_col + M && (ldw & 3) == 0 && aligned16(W), CDML_E_BADARG,
+               "npair_memory_grad_f32: W needs a 16-B aligned base and ldw >= mem_col + M (%lld), a multiple of 4 (got %lld)",
+               (long long)(mem_col + M), (long long)ldw);
+  const dim3 grid((unsigned)B, (unsigned)((M + 4 * kNpThreads - 1) / (4 * kNpThreads)));
+  const float scale = (symmetric ? 0.5f : 1.0f) / ((float)B * temperature);
+  hipLaunchKernelGGL(k_npair_mem_w<false>, grid, dim3(kNpThreads), 0, (hipStream_t)stream, S, lds, mem_col, ids, mem_id, M,
+                     1.0f / temperature, lse, scale, (void *)W, ldw, (int64_t)0);
+  return check_launch("npair_memory_grad_f32");
+}
+
+extern "C" int cdml_npair_memory_push(const float *P, int64_t ldp, const int32_t *ids, int B, int D, uint64_t step,
+                                      const uint64_t *step_dev, int64_t start, int M, float *mem, int64_t ldm,
+                                      int32_t *mem_id, uint16_t *R3, int64_t ldr, int64_t plane_r, uint16_t *T3,
+                                      int64_t ldt, int64_t plane_t, cdml_stream_t stream) {
+  CDML_REQUIRE(P && ids && mem && mem_id, CDML_E_BADARG, "npair_memory_push: null pointer");
+  CDML_REQUIRE(B >= 1 && D >= 1 && M >= B && M % B == 0, CDML_E_BADARG,
+               "npair_memory_push: needs B >= 1, D >= 1 and M a multiple of B (got B %d, D %d, M %d)", B, D, M);
+  CDML_REQUIRE(ldp >= D && ldm >= D && start >= 0, CDML_E_BADARG,
+               "npair_memory_push: ldp and ldm must be >= D (%d) and start >= 0 (got ldp %lld, ldm %lld, start %lld)", D,
+               (long long)ldp, (long long)ldm, (long long)start);
+  CDML_REQUIRE(!R3 == !T3, CDML_E_BADARG, "npair_memory_push: the plane images R3 and T3 go together");
+  CDML_REQUIRE(!R3 || (plane_r >= D && ldr >= 2 * plane_r + D && plane_t >= M && ldt >= 2 * plane_t + M), CDML_E_BADARG,
+               "npair_memory_push: plane images need plane_r >= D, ldr >= 2 plane_r + D, plane_t >= M and ldt >= 2 plane_t + M "
+               "(got %lld, %lld, %lld, %lld)", (long long)plane_r, (long long)ldr, (long long)plane_t, (long long)ldt);
+  const dim3 grid((unsigned)((D + kPushTile - 1) / kPushTile), (unsigned)((B + kPushTile - 1) / kPushTile));
+  hipStream_t st = (hipStream_t)stream;
+  if (R3)
+    hipLaunchKernelGGL(k_npair_mem_push<true>, grid, dim3(kNpThreads), 0, st, P, ldp, ids, B, D, step, step_dev, start, M, mem,
+                       ldm, mem_id, reinterpret_cast<__bf16 *>(R3), ldr, plane_r, reinterpret_cast<__bf16 *>(T3), ldt, plane_t);
+  else
+    hipLaunchKernelGGL(k_npair_mem_push<false>, grid, dim3(kNpThreads), 0, st, P, ldp, ids, B, D, step, step_dev, start, M, mem,
+                       ldm, mem_id, (__bf16 *)nullptr, (int64_t)0, (int64_t)0, (__bf16 *)nullptr, (int64_t)0, (int64_t)0);
+  return check_launch("npair_memory_push");
 }

@@ -351,9 +351,11 @@ def npair_grad_f32(S, rows, B, temperature, symmetric, lse, W):
 
 class NPairWorkspace:
     """Every buffer of the N-pair chain for Bp pairs of Dp-wide rows (Bp a multiple of NPAIR_TILE[precision]), allocated
-    once: ``npair_loss`` then allocates nothing (hipGraph-capturable).  Pad rows and columns of W stay zero."""
+    once: ``npair_loss`` then allocates nothing (hipGraph-capturable).  Pad rows and columns of W stay zero.
+    ``in_batch=False``: without the in-batch chain's S, W and positive planes (a chain that always runs with an NPairMemory,
+    which holds its own concatenated ones)."""
 
-    def __init__(self, Bp, Dp, precision, device):
+    def __init__(self, Bp, Dp, precision, device, in_batch=True):
         if precision not in NPAIR_PRECISIONS:
             raise ValueError("the N-pair loss runs on precision 'f32x3' or 'f32', not %r" % (precision,))
         tile = NPAIR_TILE[precision]
@@ -362,24 +364,26 @@ class NPairWorkspace:
                              % (precision, tile, Bp))
         if Dp % 64:
             raise ValueError("the N-pair loss needs an embedding width that is a multiple of 64 (got %d)" % Dp)
-        self.Bp, self.Dp, self.precision = int(Bp), int(Dp), precision
+        self.Bp, self.Dp, self.precision, self.in_batch = int(Bp), int(Dp), precision, bool(in_batch)
         f32 = lambda *s: torch.zeros(s, dtype=torch.float32, device=device)
         bf = lambda *s: torch.zeros(s, dtype=torch.bfloat16, device=device)
-        self.S = f32(Bp, Bp)
+        self.S = f32(Bp, Bp) if in_batch else None
         self.lse = f32(2 * Bp)
         self.ws = torch.zeros(npair_workspace(Bp) // 4, dtype=torch.float32, device=device)
         if precision == "f32x3":
             self.Dq = Dq = (Dp + 255) // 256 * 256          # the plane GEMMs' N tile: narrower rows are zero-padded
-            self.A3, self.P3 = bf(Bp, 3 * Dq), bf(Bp, 3 * Dq)
-            self.PT3 = bf(Dq, 3 * Bp)                       # the positives transposed: dA = W . P's k-contiguous operand
-            self.W3 = bf(Bp, 3 * Bp)
-            nb = max(gemm_bf16x3_workspace(False, Bp, Bp, Dq), gemm_bf16x3_workspace(False, Bp, Dq, Bp),
-                     gemm_bf16x3_workspace(True, Bp, Dq, Bp), 16)
-            self.gemm_ws = torch.zeros(nb // 4, dtype=torch.float32, device=device)
+            self.A3 = bf(Bp, 3 * Dq)
+            if in_batch:
+                self.P3 = bf(Bp, 3 * Dq)
+                self.PT3 = bf(Dq, 3 * Bp)                   # the positives transposed: dA = W . P's k-contiguous operand
+                self.W3 = bf(Bp, 3 * Bp)
+                nb = max(gemm_bf16x3_workspace(False, Bp, Bp, Dq), gemm_bf16x3_workspace(False, Bp, Dq, Bp),
+                         gemm_bf16x3_workspace(True, Bp, Dq, Bp), 16)
+                self.gemm_ws = torch.zeros(nb // 4, dtype=torch.float32, device=device)
             self.dA = f32(Bp, Dq) if Dq != Dp else None     # (rows narrower than the tile: the products land here first)
             self.dP = f32(Bp, Dq) if Dq != Dp else None
         else:
-            self.Wf = f32(Bp, Bp)
+            self.Wf = f32(Bp, Bp) if in_batch else None
             self.zero_bias = f32(Dp)
             self.bw = torch.zeros(max(fc_bwd_weight_workspace(Bp, Bp, Dp), 16) // 4, dtype=torch.float32, device=device)
 
@@ -391,13 +395,124 @@ class NPairWorkspace:
         return self.W3[:, :Bp].float() + self.W3[:, Bp:2 * Bp].float() + self.W3[:, 2 * Bp:].float()
 
 
-def npair_loss(e, rows, B, Dp, temperature=0.1, symmetric=True, precision="f32x3", de=None, stats=None, ws=None):
+def npair_memory_workspace(B, M):
+    return int(load_library().cdml_npair_memory_workspace(int(B), int(M)))
+
+
+def npair_memory_stats(S, rows, B, mem_col, mem_id, temperature, symmetric, lse, stats, workspace):
+    """cdml_npair_memory_stats: npair_stats over S = A [P; Mem]^T, the memory's M = mem_id.numel() columns at mem_col."""
+    sp, sld = _mat(S)
+    call("cdml_npair_memory_stats", sp, sld, _p(rows, torch.int32), int(B), int(mem_col), _p(mem_id, torch.int32),
+         mem_id.numel(), float(temperature), 1 if symmetric else 0, _p(lse), _p(stats), _p(workspace),
+         workspace.numel() * workspace.element_size(), _stream())
+    return lse, stats
+
+
+def npair_memory_grad_x3(S, rows, B, mem_col, mem_id, temperature, symmetric, lse, W_planes, plane):
+    """W_planes' memory block (columns mem_col .. mem_col + M - 1 of each plane) <- cdml_npair_memory_grad_x3."""
+    sp, sld = _mat(S)
+    wp, wld = _mat16(W_planes)
+    call("cdml_npair_memory_grad_x3", sp, sld, _p(rows, torch.int32), int(B), int(mem_col), _p(mem_id, torch.int32),
+         mem_id.numel(), float(temperature), 1 if symmetric else 0, _p(lse), wp, wld, int(plane), _stream())
+    return W_planes
+
+
+def npair_memory_grad_f32(S, rows, B, mem_col, mem_id, temperature, symmetric, lse, W):
+    """W's memory block (columns mem_col .. mem_col + M - 1) <- cdml_npair_memory_grad_f32."""
+    sp, sld = _mat(S)
+    wp, wld = _mat(W)
+    call("cdml_npair_memory_grad_f32", sp, sld, _p(rows, torch.int32), int(B), int(mem_col), _p(mem_id, torch.int32),
+         mem_id.numel(), float(temperature), 1 if symmetric else 0, _p(lse), wp, wld, _stream())
+    return W
+
+
+def npair_memory_push(P, rows, B, D, step, step_dev, start, mem, mem_id, R3=None, plane_r=0, T3=None, plane_t=0):
+    """cdml_npair_memory_push: the positives P [>= B, >= D] and their ids rows[1::2] into the ring slots of step
+    ``step`` + *step_dev (mem fp32 [M, >= D], mem_id int32 [M]); R3 / T3: the slots' plane images (precision f32x3)."""
+    pp, pld = _mat(P)
+    mp, mld = _mat(mem)
+    rp, rld = (C.c_void_p(0), 0) if R3 is None else _mat16(R3)
+    tp, tld = (C.c_void_p(0), 0) if T3 is None else _mat16(T3)
+    call("cdml_npair_memory_push", pp, pld, _p(rows, torch.int32), int(B), int(D), 0 if step is None else int(step),
+         _p(step_dev, torch.int64), int(start), mem_id.numel(), mp, mld, _p(mem_id, torch.int32), rp, rld, int(plane_r),
+         tp, tld, int(plane_t), _stream())
+
+
+class NPairMemory:
+    """The cross-batch memory of the N-pair loss (XBM, Wang et al. 2020; build-defined): a FIFO ring of the last M
+    positives (fp32 unit rows ``rows`` [M, Dp] and video ids ``ids`` [M], -1 = empty) that ``npair_loss(memory=...)``
+    uses as M more negatives of every anchor, without a gradient.  It owns the chain's concatenated buffers, allocated once
+    (hipGraph-capturable): S [Bp, Bp + M] and W over K = Bp + M, and the operand [P; Mem] -- f32x3: its row planes
+    ``PM3`` [Bp + M, 3 Dq] and transposed planes ``PMT3`` [Dq, 3 (Bp + M)], the ring's part written by the push (never
+    re-split); f32: fp32 ``PM`` [Bp + M, Dp], whose last M rows ARE ``rows``.  Step t pushes its Bp positives into slots
+    ((t - start) mod (M / Bp)) Bp ..; steps before ``start`` push nothing.  M: a multiple of Bp and of
+    NPAIR_TILE[precision]."""
+
+    def __init__(self, size, Bp, Dp, precision, device, start=0):
+        if precision not in NPAIR_PRECISIONS:
+            raise ValueError("the N-pair loss runs on precision 'f32x3' or 'f32', not %r" % (precision,))
+        M, tile = int(size), NPAIR_TILE[precision]
+        if M < 1 or M % int(Bp) or M % tile:
+            raise ValueError("precision %r: the memory size must be a positive multiple of the batch (%d pairs) and of %d "
+                             "(got %d)" % (precision, Bp, tile, M))
+        if int(start) < 0:
+            raise ValueError("memory_start must be >= 0, got %r" % (start,))
+        self.M, self.Bp, self.Dp, self.precision, self.start = M, int(Bp), int(Dp), precision, int(start)
+        self.K = K = self.Bp + M                            # the contraction of dA = W [P; Mem]
+        f32 = lambda *s: torch.zeros(s, dtype=torch.float32, device=device)
+        bf = lambda *s: torch.zeros(s, dtype=torch.bfloat16, device=device)
+        self.ids = torch.full((M,), -1, dtype=torch.int32, device=device)
+        self.S = f32(Bp, K)
+        if precision == "f32x3":
+            self.Dq = Dq = (Dp + 255) // 256 * 256
+            self.rows = f32(M, Dp)
+            self.PM3, self.PMT3 = bf(K, 3 * Dq), bf(Dq, 3 * K)
+            self.W3 = bf(Bp, 3 * K)
+            nb = max(gemm_bf16x3_workspace(False, Bp, K, Dq), gemm_bf16x3_workspace(False, Bp, Dq, K),
+                     gemm_bf16x3_workspace(True, Bp, Dq, Bp), 16)
+            self.gemm_ws = torch.zeros(nb // 4, dtype=torch.float32, device=device)
+        else:
+            self.PM = f32(K, Dp)
+            self.rows = self.PM[Bp:]
+            self.Wf = f32(Bp, K)
+
+    def load(self, rows, ids):
+        """Set the ring: rows fp32 [M, Dp], ids int [M] (-1 = empty); the f32x3 planes are re-derived (hi + mid + lo is
+        exactly the fp32 value, so they are the bits the pushes would have written)."""
+        if tuple(rows.shape) != (self.M, self.Dp) or tuple(ids.shape) != (self.M,):
+            raise ValueError("a ring of %d rows x %d columns and %d ids, got %s and %s"
+                             % (self.M, self.Dp, self.M, tuple(rows.shape), tuple(ids.shape)))
+        self.rows.copy_(rows.to(device=self.rows.device, dtype=torch.float32))
+        self.ids.copy_(ids.to(device=self.ids.device, dtype=torch.int32))
+        if self.precision == "f32x3":
+            split_f32_bf16x3(self.rows, self.PM3[self.Bp:], self.Dq)
+            split_f32_bf16x3(self.rows, self.PMT3[:, self.Bp:], self.K, transpose=True)
+
+    def clear(self):
+        self.load(torch.zeros_like(self.rows), torch.full_like(self.ids, -1))
+
+    def W(self):
+        """the gradient weights as one fp32 tensor [Bp, Bp + M] (tests, debugging)"""
+        if self.precision == "f32":
+            return self.Wf
+        K = self.K
+        return self.W3[:, :K].float() + self.W3[:, K:2 * K].float() + self.W3[:, 2 * K:].float()
+
+    def state_dict(self):
+        return {"size": self.M, "rows": self.rows.detach().cpu().clone(), "ids": self.ids.detach().cpu().clone()}
+
+
+def npair_loss(e, rows, B, Dp, temperature=0.1, symmetric=True, precision="f32x3", de=None, stats=None, ws=None,
+               memory=None, step=0, step_dev=None):
     """The multi-class N-pair loss of B pairs and its gradient (include/cdml.h, "multi-class N-pair loss").
     e: fp32 [2 Bp, Dp] unit rows, row 2i = anchor i, row 2i+1 = positive i (rows >= 2B zero: padding); rows: int32 [2 Bp]
     video ids or None.  The chain: S = A P^T -> row (and column) log-sum-exp + step scalars -> W -> dA = W P, dP = W^T A,
     written into de[0::2] / de[1::2] (fp32 [2 Bp, Dp]; None: loss only).  Precision "f32x3": fp32 operands as three
     bf16 planes on the plane GEMMs; "f32": the fp32-MFMA GEMMs.  stats: fp32 [>= 4] (loss, mean positive distance,
     mean counted-negative distance, fraction of counted negatives).  ws: an NPairWorkspace (allocated here if None).
+    memory: an NPairMemory (B == Bp, video ids given): its ring adds M negatives to every anchor's row term -- S = A [P;
+    Mem]^T -> statistics -> W (the in-batch block + the memory block) -> dA = W [P; Mem] over K = Bp + M, dP = W^T A ->
+    with ``de``, the push of this step's positives (step number ``step`` + *step_dev, the sampler's convention).
     Returns (stats, lse): lse[:B] the rows', lse[B:2B] the columns' (symmetric)."""
     if not (temperature > 0.0) or temperature == float("inf"):
         raise ValueError("temperature must be finite and > 0, got %r" % (temperature,))
@@ -410,6 +525,10 @@ def npair_loss(e, rows, B, Dp, temperature=0.1, symmetric=True, precision="f32x3
         raise ValueError("NPairWorkspace is for %d pairs x %d columns on %s" % (ws.Bp, ws.Dp, ws.precision))
     if stats is None:
         stats = torch.zeros(4, dtype=torch.float32, device=e.device)
+    if memory is None and not ws.in_batch:
+        raise ValueError("this NPairWorkspace was allocated for the cross-batch memory's chain only (in_batch=False)")
+    if memory is not None:
+        return _npair_memory_loss(e, rows, B, Dp, temperature, symmetric, precision, de, stats, ws, memory, step, step_dev)
     A, P = e[0::2, :Dp], e[1::2, :Dp]
     lse = ws.lse
     if precision == "f32x3":
@@ -437,6 +556,48 @@ def npair_loss(e, rows, B, Dp, temperature=0.1, symmetric=True, precision="f32x3
         npair_grad_f32(ws.S, rows, B, temperature, symmetric, lse, ws.Wf)
         fc_lrelu_fwd(ws.Wf, P, ws.zero_bias, dA, Bp, Bp, Dp, alpha=1.0)      # dA = W . P (x W form, identity activation)
         fc_bwd_weight(ws.Wf, A, dP, None, ws.bw, Bp, Bp, Dp)                 # dP = W^T . A (x^T dy form)
+    return stats, lse
+
+
+def _npair_memory_loss(e, rows, B, Dp, temperature, symmetric, precision, de, stats, ws, mem, step, step_dev):
+    Bp, M, K = ws.Bp, mem.M, mem.K
+    if (mem.Bp, mem.Dp, mem.precision) != (Bp, Dp, precision):
+        raise ValueError("NPairMemory is for %d pairs x %d columns on %s" % (mem.Bp, mem.Dp, mem.precision))
+    if B != Bp or rows is None:
+        raise ValueError("the cross-batch memory needs an unpadded batch (B == Bp) and the rows' video ids")
+    A, P = e[0::2, :Dp], e[1::2, :Dp]
+    lse = ws.lse
+    if precision == "f32x3":
+        Dq = ws.Dq
+        split_f32_bf16x3(A, ws.A3, Dq)
+        split_f32_bf16x3(P, mem.PM3[:Bp], Dq)                        # [P; Mem]: the batch's part of both operand images
+        split_f32_bf16x3(P, mem.PMT3, K, transpose=True)
+        gemm_bf16x3_nt(BE_F32, ws.A3, Dq, mem.PM3, Dq, mem.S, Bp, K, Dq, workspace=mem.gemm_ws)     # S = A [P; Mem]^T
+    else:
+        mem.PM[:Bp].copy_(P)
+        fc_bwd_data(A, mem.PM, None, mem.S, Bp, K, Dp)
+    npair_memory_stats(mem.S, rows, B, Bp, mem.ids, temperature, symmetric, lse, stats, ws.ws)
+    if de is None:
+        return stats, lse
+    dA, dP = de[0::2], de[1::2]
+    if precision == "f32x3":
+        npair_grad_x3(mem.S, rows, B, temperature, symmetric, lse, mem.W3, K)
+        npair_memory_grad_x3(mem.S, rows, B, Bp, mem.ids, temperature, symmetric, lse, mem.W3, K)
+        oA = dA if ws.dA is None else ws.dA
+        oP = dP if ws.dP is None else ws.dP
+        gemm_bf16x3_nt(BE_F32, mem.W3, K, mem.PMT3, K, oA, Bp, Dq, K, workspace=mem.gemm_ws)      # dA = W . [P; Mem]
+        gemm_bf16x3_tn(mem.W3, K, ws.A3, Dq, oP, Bp, Dq, Bp, workspace=mem.gemm_ws)               # dP = W^T . A
+        if ws.dA is not None:
+            dA.copy_(ws.dA[:, :Dp])
+            dP.copy_(ws.dP[:, :Dp])
+        npair_memory_push(P, rows, Bp, Dp, step, step_dev, mem.start, mem.rows, mem.ids, R3=mem.PM3[Bp:], plane_r=Dq,
+                          T3=mem.PMT3[:, Bp:], plane_t=K)
+    else:
+        npair_grad_f32(mem.S, rows, B, temperature, symmetric, lse, mem.Wf)
+        npair_memory_grad_f32(mem.S, rows, B, Bp, mem.ids, temperature, symmetric, lse, mem.Wf)
+        fc_lrelu_fwd(mem.Wf, mem.PM, ws.zero_bias, dA, Bp, K, Dp, alpha=1.0)          # dA = W . [P; Mem]
+        fc_bwd_weight(mem.Wf[:, :Bp], A, dP, None, ws.bw, Bp, Bp, Dp)                 # dP = W^T . A
+        npair_memory_push(P, rows, Bp, Dp, step, step_dev, mem.start, mem.rows, mem.ids)
     return stats, lse
 
 

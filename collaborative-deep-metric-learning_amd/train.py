@@ -47,7 +47,7 @@ class TrainStep:
                  exchange=None, grad_sync=None, slot0=0, batch_global=None, use_graph=False,
                  prefetch=True, precision="auto", train_table=False, gather_ahead="auto",
                  clip_gradient_norm=0.0, regularization_penalty=0.0, l2_penalty=1e-8,
-                 grad_sync_mode="bucketed", temperature=0.1, symmetric=True):
+                 grad_sync_mode="bucketed", temperature=0.1, symmetric=True, memory_size=0, memory_start=0):
         """table: FeatureTable (whole catalogue, or this rank's shard when
         ``exchange`` is given); pairs: int32 [P,2] device tensor; ``exchange`` /
         ``grad_sync``: the multi-GPU hooks of cdml_amd.dist (None on one GPU).
@@ -89,9 +89,19 @@ class TrainStep:
         hinge -- ``temperature`` (default 0.1) and ``symmetric`` (default True: the mean of the anchor->positive and
         positive->anchor terms), both build-defined; the reference has no such loss.  One GPU, fp32 catalogue, precision
         "f32x3" (a batch that is a multiple of 256 pairs; what "auto" picks then) or "f32" (a multiple of 64); the
-        embeddings' gradient goes through the separate l2norm backward (no fused tail, so no ``variance`` summary)."""
+        embeddings' gradient goes through the separate l2norm backward (no fused tail, so no ``variance`` summary).
+        ``memory_size`` (mode "npair"; 0 = none): a cross-batch memory of the last ``memory_size`` positives (XBM, Wang et
+        al. 2020; ops.NPairMemory) -- extra softmax columns of every anchor's row term, without a gradient.  Step t
+        computes its loss against the ring as it stood before step t and then pushes its B positives (steps before
+        ``memory_start`` push nothing).  A multiple of the batch and of the precision's tile (256 pairs on f32x3, 64 on f32);
+        the ring is part of ``state_dict``."""
         if mode not in _MODES:
             raise ValueError("mode must be 'uniform', 'inbatch', 'semihard' or 'npair'")
+        memory_size, memory_start = int(memory_size), int(memory_start)
+        if memory_size and mode != "npair":
+            raise ValueError("memory_size > 0 goes with mode 'npair' (the cross-batch memory of its softmax), not %r" % (mode,))
+        if memory_size < 0 or memory_start < 0:
+            raise ValueError("memory_size and memory_start must be >= 0, got %d and %d" % (memory_size, memory_start))
         if mode == "npair":
             if exchange is not None or grad_sync is not None:
                 raise ValueError("mode 'npair' runs on one GPU: data parallelism (exchange / grad_sync) is not supported")
@@ -108,6 +118,9 @@ class TrainStep:
             temperature = float(temperature)
             if not (0.0 < temperature < float("inf")):
                 raise ValueError("temperature must be finite and > 0, got %r" % (temperature,))
+            if memory_size % int(batch_size) or memory_size % tile:
+                raise ValueError("memory_size must be a multiple of the batch (%d pairs) and of %d on precision %r (got %d)"
+                                 % (int(batch_size), tile, precision, memory_size))
         if optimizer not in ("adam", "lars", "momentum"):
             raise ValueError("optimizer must be 'adam', 'lars' or 'momentum'")
         self.device = torch.device(device)
@@ -225,8 +238,13 @@ class TrainStep:
             self.sqn = torch.zeros(2 * self.B, dtype=f32, device=dev)
             self.neg_row = torch.zeros(self.B, dtype=i32, device=dev)
             self.scale = torch.zeros(self.B, dtype=f32, device=dev)
+        self.memory_size, self.memory_start = memory_size, memory_start
+        self.npair_memory = None
         if mode == "npair":                                  # S, W and the plane copies of the loss chain
-            self.npair_ws = ops.NPairWorkspace(self.B, self.layout.Dp, precision, dev)
+            # (with a cross-batch memory, the memory object holds the concatenated S, W and [P; Mem] operands)
+            self.npair_ws = ops.NPairWorkspace(self.B, self.layout.Dp, precision, dev, in_batch=not memory_size)
+            if memory_size:
+                self.npair_memory = ops.NPairMemory(memory_size, self.B, self.layout.Dp, precision, dev, start=memory_start)
         self.step_dev = torch.zeros(1, dtype=torch.int64, device=dev)
         self.lr_dev = torch.full((1,), self.base_lr, dtype=f32, device=dev)
         self._lr_host = self.base_lr
@@ -500,8 +518,9 @@ class TrainStep:
         de = self.ws.de if with_grad else None
         if self.mode == "npair":
             # S = A P^T -> row / column log-sum-exp -> W -> dA = W P, dP = W^T A into de; tower_backward takes de from there
+            # (cross-batch memory: the step number for the ring push is the device counter, which replays follow)
             ops.npair_loss(self.ws.e, self.idx, self.B, L.Dp, self.temperature, self.symmetric, self.precision, de=de,
-                           stats=self.stats, ws=self.npair_ws)
+                           stats=self.stats, ws=self.npair_ws, memory=self.npair_memory, step=0, step_dev=self.step_dev)
         elif self.mode == "uniform":
             ops.triplet_hinge(self.ws.e, self.B, L.Dp, self.margin, self.pos, self.neg, self.hinge,
                               self.stats, de)
@@ -914,6 +933,8 @@ class TrainStep:
         if self.h2:                                      # precision f16x2: the plane scales are state (a resumed run keeps the
             sc = self.ws.scales                          # straight run's bits only with the scales that run would hold)
             state["plane_scales"] = dict(sc.state(), calibrated=sc.calibrated, changes=sc.changes, last=dict(sc.last))
+        if self.npair_memory is not None:                # the ring as fp32 rows + ids (the planes are re-derived on load)
+            state["npair_memory"] = self.npair_memory.state_dict()
         return state
 
     def load_state_dict(self, state):
@@ -943,6 +964,15 @@ class TrainStep:
                 sc.calibrated = False                    # (a checkpoint of another precision: the next step calibrates)
         if self.x3:
             engine_x3.refresh_weights(self.params, self.ws)
+        ring = state.get("npair_memory")
+        if ring is not None and int(ring["size"]) != self.memory_size:
+            raise ValueError("the checkpoint holds a cross-batch memory of %d rows, this step one of %d"
+                             % (int(ring["size"]), self.memory_size))
+        if self.npair_memory is not None:                # (a checkpoint without a ring: an empty one)
+            if ring is None:
+                self.npair_memory.clear()
+            else:
+                self.npair_memory.load(ring["rows"], ring["ids"])
         self.global_step = int(state["global_step"])
         self.step_dev.fill_(self.global_step)
         self.seed = int(state["seed"])

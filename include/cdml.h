@@ -326,6 +326,41 @@ int cdml_npair_grad_x3(const float *S, int64_t lds, const int32_t *ids, int B, f
 int cdml_npair_grad_f32(const float *S, int64_t lds, const int32_t *ids, int B, float temperature, int symmetric,
                         const float *lse, float *W, int64_t ldw, cdml_stream_t stream);
 
+/* ---- cross-batch memory of negatives for the N-pair loss (XBM, Wang et al. 2020; build-defined) ---------------
+ * A ring of M slots: fp32 unit rows mem[k] and ids mem_id[k] (int32, -1 = empty).  S fp32 [B][lds] is A [P; Mem]^T:
+ * the in-batch block at columns 0 .. B-1, the memory block at columns mem_col .. mem_col + M - 1 (mem_col >= B).  Slot k
+ * counts for anchor i when mem_id[k] >= 0 and mem_id[k] is neither id(a_i) nor id(p_i) (ids NULL: when it is filled).
+ * cdml_npair_memory_stats: cdml_npair_stats with lse[i] = log(sum of the counted in-batch exp(S_ij / t) + sum of the counted
+ *   memory exp(S_ik / t)); the column term (symmetric) stays over the in-batch block.  stats[2] / [3] count the memory's
+ *   negatives too ([3]'s denominator B (B - 1) + B M).  workspace: cdml_npair_memory_workspace(B, M) bytes, 16-B aligned.
+ * cdml_npair_memory_grad_x3 / _f32: the memory block of W, W[i][mem_col + k] = c_ik exp(S_ik / t - lse_i) / (B t) (halved
+ *   with symmetric), the in-batch block being cdml_npair_grad_*'s with this lse.  dA = W [P; Mem] is one product over
+ *   K = mem_col + M; dP = W^T A reads the in-batch block only (the memory gets no gradient).  _x3: three bf16 planes, plane
+ *   >= mem_col + M, ldw >= 2 plane + mem_col + M (8-B aligned); _f32: ldw >= mem_col + M (16-B aligned).
+ * cdml_npair_memory_push: the step t = step + (step_dev ? *step_dev : 0) (the sampler's convention) writes, when t >= start,
+ *   its B positives P[r] (D fp32 columns, row stride ldp) and ids[2r + 1] into slots s + r, s = ((t - start) mod (M / B)) B:
+ *   mem[(s + r) ldm + c] and mem_id[s + r].  R3 / T3 (both or neither; precision f32x3): also the slots' operand images,
+ *   R3[(s + r) ldr + p plane_r + c] and T3[c ldt + p plane_t + s + r] = bf16 plane p of P[r][c] (cdml_split_f32_bf16x3's
+ *   split), so the memory is never re-split.  M a multiple of B: a push never wraps.  Enqueue after every product that
+ *   reads the memory.
+ * Enqueue-only, no atomics, fixed summation orders.  Bad arguments (null pointers, B < 1, M not a positive multiple of 4 --
+ * of B for the push --, t <= 0 or not finite, short or misaligned leading dimensions, a short workspace) return
+ * CDML_E_BADARG before any HIP call. */
+size_t cdml_npair_memory_workspace(int B, int M);
+int cdml_npair_memory_stats(const float *S, int64_t lds, const int32_t *ids, int B, int64_t mem_col, const int32_t *mem_id,
+                            int M, float temperature, int symmetric, float *lse, float *stats, void *workspace,
+                            size_t workspace_bytes, cdml_stream_t stream);
+int cdml_npair_memory_grad_x3(const float *S, int64_t lds, const int32_t *ids, int B, int64_t mem_col,
+                              const int32_t *mem_id, int M, float temperature, int symmetric, const float *lse,
+                              uint16_t *W, int64_t ldw, int64_t plane, cdml_stream_t stream);
+int cdml_npair_memory_grad_f32(const float *S, int64_t lds, const int32_t *ids, int B, int64_t mem_col,
+                               const int32_t *mem_id, int M, float temperature, int symmetric, const float *lse,
+                               float *W, int64_t ldw, cdml_stream_t stream);
+int cdml_npair_memory_push(const float *P, int64_t ldp, const int32_t *ids, int B, int D, uint64_t step,
+                           const uint64_t *step_dev, int64_t start, int M, float *mem, int64_t ldm, int32_t *mem_id,
+                           uint16_t *R3, int64_t ldr, int64_t plane_r, uint16_t *T3, int64_t ldt, int64_t plane_t,
+                           cdml_stream_t stream);
+
 /* ---- evaluation metric: Evaluation.mean_dist / mean_cos_dist (evaluate.py:57-90)
  * e[n_rows][lde] embeddings; pairs int32[P][2] row indices (must be < n_rows).
  * sqdist[P] = sum (a-b)^2, dot[P] = sum a*b; means float[4] (may be NULL):
