@@ -113,6 +113,16 @@ SIGNATURES = {
     "cdml_npair_memory_grad_f32": (_i, [_p, _i64, _p, _i, _i64, _p, _i, _f, _i, _p, _p, _i64, _p]),
     "cdml_npair_memory_push": (_i, [_p, _i64, _p, _i, _i, _u64, _p, _i64, _i, _p, _i64, _p, _p, _i64, _i64, _p, _i64,
                                     _i64, _p]),
+    "cdml_npair_logq_stats": (_i, [_p, _i64, _p, _i, _p, _f, _i, _p, _p, _p, _sz, _p]),
+    "cdml_npair_logq_grad_x3": (_i, [_p, _i64, _p, _i, _p, _f, _i, _p, _p, _i64, _i64, _p]),
+    "cdml_npair_logq_grad_f32": (_i, [_p, _i64, _p, _i, _p, _f, _i, _p, _p, _i64, _p]),
+    "cdml_npair_memory_logq_stats": (_i, [_p, _i64, _p, _i, _p, _i64, _p, _p, _i, _f, _i, _p, _p, _p, _sz, _p]),
+    "cdml_npair_memory_logq_grad_x3": (_i, [_p, _i64, _p, _i, _i64, _p, _p, _i, _f, _i, _p, _p, _i64, _i64, _p]),
+    "cdml_npair_memory_logq_grad_f32": (_i, [_p, _i64, _p, _i, _i64, _p, _p, _i, _f, _i, _p, _p, _i64, _p]),
+    "cdml_logq_table_gather": (_i, [_p, _i64, _p, _i, _p, _i, _p, _p, _p]),
+    "cdml_logq_stream_gather": (_i, [_p, _p, _i64, _p, _i, _p, _i, _p, _p, _p, _p, _p]),
+    "cdml_logq_stream_update": (_i, [_p, _p, _i64, _p, _i, _p, _p, _f, _u64, _p, _p]),
+    "cdml_logq_stream_reset": (_i, [_p, _p, _i64, _f, _p]),
     "cdml_pair_dist": (_i, [_p, _i64, _i, _p, _i, _i, _p, _p, _p, _p]),
     "cdml_cowatch_workspace": (_sz, [_i64]),
     "cdml_cowatch_graph": (_i, [_p, _i64, _p, _p, _p, _p, _p, _sz, _p]),

@@ -42,6 +42,8 @@ class TrainConfig:
     symmetric: bool = True                    # mode "npair": also the positive -> anchor term (build-defined)
     memory_size: int = 0                      # mode "npair": rows of the cross-batch memory of negatives (0 = none; build-defined)
     memory_start: int = 0                     # mode "npair": the first step that pushes into that memory
+    logq: str = ""                            # mode "npair": "stream" = the sampling-bias (logQ) correction, estimated on the fly
+    logq_alpha: float = 0.01                  # mode "npair": that estimator's smoothing rate (build-defined)
     seed: int = 1234
     weight_seed: int = 42
 
@@ -77,9 +79,12 @@ class TrainConfig:
                   regularization_penalty=self.regularization_penalty)
         if self.mode == "npair":
             kw.update(temperature=self.temperature, symmetric=self.symmetric, memory_size=self.memory_size,
-                      memory_start=self.memory_start)
-        elif self.memory_size:
-            kw.update(memory_size=self.memory_size)       # (TrainStep refuses it outside mode "npair")
+                      memory_start=self.memory_start, logq=self.logq or None, logq_alpha=self.logq_alpha)
+        else:
+            if self.memory_size:
+                kw.update(memory_size=self.memory_size)   # (TrainStep refuses it outside mode "npair")
+            if self.logq:
+                kw.update(logq=self.logq)                 # (and this)
         kw.update(overrides)
         return train.TrainStep(table, pairs, self.batch_size, **kw)
 

@@ -24,6 +24,12 @@
 //   k_npair_mem_w<X3>    W's memory block, c_ik exp(S_ik / t - lse_i) / (B t) (halved with `symmetric`)
 //   k_npair_mem_push<X3> the ring push of the step's positives (after the products that read the memory), fp32 rows + ids,
 //                        and for X3 the slots' row-plane and transposed-plane operand images
+//
+// Sampling-bias correction (logQ, Yi et al. 2019; cdml_npair_logq_* / cdml_npair_memory_logq_*): every logit that enters a
+// log-sum-exp or the diagonal loses the log sampling probability of its candidate -- row term column j: S_ij / t - lq(p_j),
+// memory slot k: S_ik / t - lq(mem_id[k]), column term row i: S_ij / t - lq(a_i).  The passes read it per slot, bias[2i] =
+// lq(a_i), bias[2i + 1] = lq(p_i) (laid out like ids) and mem_bias[k]: the BIAS instantiations of the kernels below; the
+// BIAS = false ones are the arithmetic of the uncorrected loss.  csrc/npair_logq.hip fills the vectors.
 #include "common.h"
 #include <math.h>
 
@@ -75,10 +81,14 @@ __device__ __forceinline__ bool mem_counts(const int32_t *ids, int q, int ida, i
   return q >= 0 && (!ids || (q != ida && q != idp));
 }
 
-__device__ __forceinline__ void mem_add(const int32_t *ids, float v, int q, int ida, int idp, float inv_t, float &m, float &s,
-                                        float &nsum, float &ncnt) {
+template <bool BIAS>
+__device__ __forceinline__ void mem_add(const int32_t *ids, float v, int q, float b, int ida, int idp, float inv_t, float &m,
+                                        float &s, float &nsum, float &ncnt) {
   if (!mem_counts(ids, q, ida, idp)) return;
-  lse_add(m, s, v * inv_t);
+  if constexpr (BIAS)
+    lse_add(m, s, v * inv_t - b);
+  else
+    lse_add(m, s, v * inv_t);
   nsum += 2.f - 2.f * v;
   ncnt += 1.f;
 }
@@ -86,10 +96,12 @@ __device__ __forceinline__ void mem_add(const int32_t *ids, float v, int q, int 
 // part[4 i .. 4 i + 3] = {lse_i - S_ii / t, 2 - 2 S_ii, sum over the counted j != i of 2 - 2 S_ij, their count}
 // MEM: the row goes on over the n_mem memory columns at mem_col .. mem_col + n_mem - 1 of S (cross-batch memory, slot ids mem_id;
 // four columns per lane per pass, after the in-batch columns: the same fixed order on every run)
-template <bool MEM>
+// BIAS: column j's logit less bias[2j + 1], slot k's less mem_bias[k] (part[4 i] too: lse_i - (S_ii / t - bias[2i + 1]))
+template <bool MEM, bool BIAS>
 __global__ void __launch_bounds__(kNpThreads)
 k_npair_rows(const float *__restrict__ S, int64_t lds, const int32_t *__restrict__ ids, int B, float inv_t,
-             float *__restrict__ lse, float *__restrict__ part, int64_t mem_col, const int32_t *__restrict__ mem_id, int n_mem) {
+             float *__restrict__ lse, float *__restrict__ part, int64_t mem_col, const int32_t *__restrict__ mem_id, int n_mem,
+             const float *__restrict__ bias, const float *__restrict__ mem_bias) {
   __shared__ float sm[kNpThreads / kWave][4];
   const int i = blockIdx.x;
   const float *row = S + (int64_t)i * lds;
@@ -98,7 +110,10 @@ k_npair_rows(const float *__restrict__ S, int64_t lds, const int32_t *__restrict
   for (int j = threadIdx.x; j < B; j += kNpThreads) {
     if (!row_counts(ids, i, j, ida, idp)) continue;
     const float v = row[j];
-    lse_add(m, s, v * inv_t);
+    if constexpr (BIAS)
+      lse_add(m, s, v * inv_t - bias[2 * j + 1]);
+    else
+      lse_add(m, s, v * inv_t);
     if (j != i) {
       nsum += 2.f - 2.f * v;
       ncnt += 1.f;
@@ -109,10 +124,12 @@ k_npair_rows(const float *__restrict__ S, int64_t lds, const int32_t *__restrict
     for (int k = 4 * threadIdx.x; k < n_mem; k += 4 * kNpThreads) {
       const float4 v = *reinterpret_cast<const float4 *>(mrow + k);
       const int4 q = *reinterpret_cast<const int4 *>(mem_id + k);
-      mem_add(ids, v.x, q.x, ida, idp, inv_t, m, s, nsum, ncnt);
-      mem_add(ids, v.y, q.y, ida, idp, inv_t, m, s, nsum, ncnt);
-      mem_add(ids, v.z, q.z, ida, idp, inv_t, m, s, nsum, ncnt);
-      mem_add(ids, v.w, q.w, ida, idp, inv_t, m, s, nsum, ncnt);
+      float4 b = make_float4(0.f, 0.f, 0.f, 0.f);
+      if constexpr (BIAS) b = *reinterpret_cast<const float4 *>(mem_bias + k);
+      mem_add<BIAS>(ids, v.x, q.x, b.x, ida, idp, inv_t, m, s, nsum, ncnt);
+      mem_add<BIAS>(ids, v.y, q.y, b.y, ida, idp, inv_t, m, s, nsum, ncnt);
+      mem_add<BIAS>(ids, v.z, q.z, b.z, ida, idp, inv_t, m, s, nsum, ncnt);
+      mem_add<BIAS>(ids, v.w, q.w, b.w, ida, idp, inv_t, m, s, nsum, ncnt);
     }
   }
 #pragma unroll
@@ -140,14 +157,21 @@ k_npair_rows(const float *__restrict__ S, int64_t lds, const int32_t *__restrict
     const float sii = row[i];
     const float l = M + logf(Sx);
     lse[i] = l;
-    *reinterpret_cast<float4 *>(part + 4 * (int64_t)i) = make_float4(l - sii * inv_t, 2.f - 2.f * sii, ns, nc);
+    float d;
+    if constexpr (BIAS)
+      d = sii * inv_t - bias[2 * i + 1];
+    else
+      d = sii * inv_t;
+    *reinterpret_cast<float4 *>(part + 4 * (int64_t)i) = make_float4(l - d, 2.f - 2.f * sii, ns, nc);
   }
 }
 
 // cm / cs [chunk][B]: the (max, sum-exp) of column j over rows chunk * kNpChunk .. + kNpChunk - 1
+// BIAS: row i's logit less bias[2i] (the anchor's: one value per row, the same for every lane of the wave)
+template <bool BIAS>
 __global__ void __launch_bounds__(kNpThreads)
 k_npair_cols(const float *__restrict__ S, int64_t lds, const int32_t *__restrict__ ids, int B, float inv_t,
-             float *__restrict__ cm, float *__restrict__ cs) {
+             float *__restrict__ cm, float *__restrict__ cs, const float *__restrict__ bias) {
   const int j = blockIdx.x * kNpThreads + threadIdx.x;
   const int c = blockIdx.y;
   if (j >= B) return;
@@ -156,23 +180,30 @@ k_npair_cols(const float *__restrict__ S, int64_t lds, const int32_t *__restrict
   float m = -INFINITY, s = 0.f;
   for (int i = i0; i < i1; ++i) {
     if (!col_counts(ids, i, j, idaj, idpj)) continue;
-    lse_add(m, s, S[(int64_t)i * lds + j] * inv_t);
+    if constexpr (BIAS)
+      lse_add(m, s, S[(int64_t)i * lds + j] * inv_t - bias[2 * i]);
+    else
+      lse_add(m, s, S[(int64_t)i * lds + j] * inv_t);
   }
   cm[(int64_t)c * B + j] = m;
   cs[(int64_t)c * B + j] = s;
 }
 
-// lse[B + j] = lse'_j, closs[j] = lse'_j - S_jj / t: the chunks folded in order
+// lse[B + j] = lse'_j, closs[j] = lse'_j - S_jj / t (BIAS: - (S_jj / t - bias[2j])): the chunks folded in order
+template <bool BIAS>
 __global__ void __launch_bounds__(kNpThreads)
 k_npair_col_fold(const float *__restrict__ S, int64_t lds, int B, int chunks, float inv_t, const float *__restrict__ cm,
-                 const float *__restrict__ cs, float *__restrict__ lse, float *__restrict__ closs) {
+                 const float *__restrict__ cs, float *__restrict__ lse, float *__restrict__ closs, const float *__restrict__ bias) {
   const int j = blockIdx.x * kNpThreads + threadIdx.x;
   if (j >= B) return;
   float m = -INFINITY, s = 0.f;
   for (int c = 0; c < chunks; ++c) lse_merge(m, s, cm[(int64_t)c * B + j], cs[(int64_t)c * B + j]);
   const float l = m + logf(s);
   lse[B + j] = l;
-  closs[j] = l - S[(int64_t)j * lds + j] * inv_t;
+  if constexpr (BIAS)
+    closs[j] = l - (S[(int64_t)j * lds + j] * inv_t - bias[2 * j]);
+  else
+    closs[j] = l - S[(int64_t)j * lds + j] * inv_t;
 }
 
 // stats[0] = loss, [1] = mean |a_i - p_i|^2, [2] = mean |a_i - p_j|^2 over the counted row-term negatives, [3] = the fraction
@@ -211,13 +242,23 @@ k_npair_stats(const float *__restrict__ part, const float *__restrict__ closs, i
   }
 }
 
+// BIAS: the row term's logit less bp = bias[2j + 1] (positive j's), the column term's less ba = bias[2i] (anchor i's)
+template <bool BIAS>
 __device__ __forceinline__ float npair_w(const int32_t *ids, int i, int j, int ida, int idp, float v, float inv_t, float lse_r,
-                                         const float *lse_c, int symmetric, float scale) {
-  float r = row_counts(ids, i, j, ida, idp) ? expf(v * inv_t - lse_r) : 0.f;
+                                         const float *lse_c, int symmetric, float scale, float bp, float ba) {
+  float r;
+  if constexpr (BIAS)
+    r = row_counts(ids, i, j, ida, idp) ? expf(v * inv_t - bp - lse_r) : 0.f;
+  else
+    r = row_counts(ids, i, j, ida, idp) ? expf(v * inv_t - lse_r) : 0.f;
   if (j == i) r -= 1.f;
   if (symmetric) {
     const int idaj = ids ? ids[2 * j] : 0, idpj = ids ? ids[2 * j + 1] : 0;
-    float c = col_counts(ids, i, j, idaj, idpj) ? expf(v * inv_t - lse_c[j]) : 0.f;
+    float c;
+    if constexpr (BIAS)
+      c = col_counts(ids, i, j, idaj, idpj) ? expf(v * inv_t - ba - lse_c[j]) : 0.f;
+    else
+      c = col_counts(ids, i, j, idaj, idpj) ? expf(v * inv_t - lse_c[j]) : 0.f;
     if (j == i) c -= 1.f;
     r = 0.5f * (r + c);
   }
@@ -225,10 +266,11 @@ __device__ __forceinline__ float npair_w(const int32_t *ids, int i, int j, int i
 }
 
 // row i = blockIdx.x, columns 4 (blockIdx.y * kNpThreads + threadIdx.x) .. + 3; columns >= B are not written
-template <bool X3>
+template <bool X3, bool BIAS>
 __global__ void __launch_bounds__(kNpThreads)
 k_npair_w(const float *__restrict__ S, int64_t lds, const int32_t *__restrict__ ids, int B, float inv_t, int symmetric,
-          const float *__restrict__ lse, float scale, void *__restrict__ Wout, int64_t ldw, int64_t plane) {
+          const float *__restrict__ lse, float scale, void *__restrict__ Wout, int64_t ldw, int64_t plane,
+          const float *__restrict__ bias) {
   const int i = blockIdx.x;
   const int j0 = (blockIdx.y * kNpThreads + threadIdx.x) * 4;
   if (j0 >= B) return;
@@ -236,16 +278,24 @@ k_npair_w(const float *__restrict__ S, int64_t lds, const int32_t *__restrict__ 
   const float lr = lse[i];
   const float *lc = lse + B;
   const float *row = S + (int64_t)i * lds;
+  const float ba = BIAS ? bias[2 * i] : 0.f;
   float w[4];
   if (j0 + 3 < B) {
     const float4 v = *reinterpret_cast<const float4 *>(row + j0);
-    w[0] = npair_w(ids, i, j0, ida, idp, v.x, inv_t, lr, lc, symmetric, scale);
-    w[1] = npair_w(ids, i, j0 + 1, ida, idp, v.y, inv_t, lr, lc, symmetric, scale);
-    w[2] = npair_w(ids, i, j0 + 2, ida, idp, v.z, inv_t, lr, lc, symmetric, scale);
-    w[3] = npair_w(ids, i, j0 + 3, ida, idp, v.w, inv_t, lr, lc, symmetric, scale);
+    float4 b0 = make_float4(0.f, 0.f, 0.f, 0.f), b1 = b0;
+    if constexpr (BIAS) {                            // the four columns' slots 2j .. 2j + 7: two 16-B loads, positives odd
+      b0 = *reinterpret_cast<const float4 *>(bias + 2 * j0);
+      b1 = *reinterpret_cast<const float4 *>(bias + 2 * j0 + 4);
+    }
+    w[0] = npair_w<BIAS>(ids, i, j0, ida, idp, v.x, inv_t, lr, lc, symmetric, scale, b0.y, ba);
+    w[1] = npair_w<BIAS>(ids, i, j0 + 1, ida, idp, v.y, inv_t, lr, lc, symmetric, scale, b0.w, ba);
+    w[2] = npair_w<BIAS>(ids, i, j0 + 2, ida, idp, v.z, inv_t, lr, lc, symmetric, scale, b1.y, ba);
+    w[3] = npair_w<BIAS>(ids, i, j0 + 3, ida, idp, v.w, inv_t, lr, lc, symmetric, scale, b1.w, ba);
   } else {
     for (int q = 0; q < 4; ++q)
-      w[q] = (j0 + q < B) ? npair_w(ids, i, j0 + q, ida, idp, row[j0 + q], inv_t, lr, lc, symmetric, scale) : 0.f;
+      w[q] = (j0 + q < B) ? npair_w<BIAS>(ids, i, j0 + q, ida, idp, row[j0 + q], inv_t, lr, lc, symmetric, scale,
+                                          BIAS ? bias[2 * (j0 + q) + 1] : 0.f, ba)
+                          : 0.f;
   }
   const int n = min(4, B - j0);
   if (X3) {
@@ -281,12 +331,12 @@ k_npair_w(const float *__restrict__ S, int64_t lds, const int32_t *__restrict__ 
 
 // The memory block of W: W[i][mem_col + k] = c_ik exp(S[i][mem_col + k] / t - lse_i) * scale (scale = 1 / (B t), halved
 // with `symmetric`: the column term has no memory part).  Row i = blockIdx.x, slots 4 (blockIdx.y * kNpThreads +
-// threadIdx.x) .. + 3 (M a multiple of 4)
-template <bool X3>
+// threadIdx.x) .. + 3 (M a multiple of 4).  BIAS: slot k's logit less mem_bias[k]
+template <bool X3, bool BIAS>
 __global__ void __launch_bounds__(kNpThreads)
 k_npair_mem_w(const float *__restrict__ S, int64_t lds, int64_t mem_col, const int32_t *__restrict__ ids,
               const int32_t *__restrict__ mem_id, int M, float inv_t, const float *__restrict__ lse, float scale,
-              void *__restrict__ Wout, int64_t ldw, int64_t plane) {
+              void *__restrict__ Wout, int64_t ldw, int64_t plane, const float *__restrict__ mem_bias) {
   const int i = blockIdx.x;
   const int k0 = (blockIdx.y * kNpThreads + threadIdx.x) * 4;
   if (k0 >= M) return;
@@ -294,10 +344,19 @@ k_npair_mem_w(const float *__restrict__ S, int64_t lds, int64_t mem_col, const i
   const float lr = lse[i];
   const float4 v = *reinterpret_cast<const float4 *>(S + (int64_t)i * lds + mem_col + k0);
   const int4 q = *reinterpret_cast<const int4 *>(mem_id + k0);
-  const float w[4] = {mem_counts(ids, q.x, ida, idp) ? expf(v.x * inv_t - lr) * scale : 0.f,
-                      mem_counts(ids, q.y, ida, idp) ? expf(v.y * inv_t - lr) * scale : 0.f,
-                      mem_counts(ids, q.z, ida, idp) ? expf(v.z * inv_t - lr) * scale : 0.f,
-                      mem_counts(ids, q.w, ida, idp) ? expf(v.w * inv_t - lr) * scale : 0.f};
+  float w[4];
+  if constexpr (BIAS) {
+    const float4 b = *reinterpret_cast<const float4 *>(mem_bias + k0);
+    w[0] = mem_counts(ids, q.x, ida, idp) ? expf(v.x * inv_t - b.x - lr) * scale : 0.f;
+    w[1] = mem_counts(ids, q.y, ida, idp) ? expf(v.y * inv_t - b.y - lr) * scale : 0.f;
+    w[2] = mem_counts(ids, q.z, ida, idp) ? expf(v.z * inv_t - b.z - lr) * scale : 0.f;
+    w[3] = mem_counts(ids, q.w, ida, idp) ? expf(v.w * inv_t - b.w - lr) * scale : 0.f;
+  } else {
+    w[0] = mem_counts(ids, q.x, ida, idp) ? expf(v.x * inv_t - lr) * scale : 0.f;
+    w[1] = mem_counts(ids, q.y, ida, idp) ? expf(v.y * inv_t - lr) * scale : 0.f;
+    w[2] = mem_counts(ids, q.z, ida, idp) ? expf(v.z * inv_t - lr) * scale : 0.f;
+    w[3] = mem_counts(ids, q.w, ida, idp) ? expf(v.w * inv_t - lr) * scale : 0.f;
+  }
   if (X3) {
     using bf4 = __attribute__((ext_vector_type(4))) __bf16;
     bf4 h, m, l;
@@ -387,6 +446,67 @@ int np_check(const char *who, const float *S, int64_t lds, int B, float temperat
   return CDML_OK;
 }
 
+int np_bias_check(const char *who, const float *bias) {
+  CDML_REQUIRE(bias, CDML_E_BADARG, "%s: null pointer (bias)", who);
+  CDML_REQUIRE(aligned16(bias), CDML_E_BADARG, "%s: bias needs a 16-B aligned base", who);
+  return CDML_OK;
+}
+
+// the statistics launches (rows, columns + fold with `symmetric`, step scalars); MEM: S's memory block at mem_col
+template <bool MEM, bool BIAS>
+int np_stats_launch(const char *who, const float *S, int64_t lds, const int32_t *ids, int B, const float *bias,
+                    int64_t mem_col, const int32_t *mem_id, const float *mem_bias, int M, float temperature, int symmetric,
+                    float *lse, float *stats, void *workspace, size_t workspace_bytes, cdml_stream_t stream) {
+  CDML_REQUIRE(stats && workspace, CDML_E_BADARG, "%s: null pointer", who);
+  CDML_REQUIRE(aligned16(workspace) && workspace_bytes >= np_ws_bytes(B), CDML_E_BADARG,
+               "%s: the workspace must be 16-B aligned and hold cdml_npair%s_workspace(%d) = %zu bytes (got %zu)", who,
+               MEM ? "_memory" : "", B, np_ws_bytes(B), workspace_bytes);
+  const float inv_t = 1.0f / temperature;
+  const int chunks = np_chunks(B);
+  float *part = static_cast<float *>(workspace), *closs = part + 4 * (size_t)B;
+  float *cm = closs + B, *cs = cm + (size_t)chunks * B;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL((k_npair_rows<MEM, BIAS>), dim3(B), dim3(kNpThreads), 0, st, S, lds, ids, B, inv_t, lse, part, mem_col,
+                     mem_id, M, bias, mem_bias);
+  if (int rc = check_launch(MEM ? "npair_memory_stats rows" : "npair_stats rows")) return rc;
+  if (symmetric) {                                   // (with a memory: the in-batch block as it stands, through lds)
+    const unsigned gx = (unsigned)((B + kNpThreads - 1) / kNpThreads);
+    hipLaunchKernelGGL(k_npair_cols<BIAS>, dim3(gx, chunks), dim3(kNpThreads), 0, st, S, lds, ids, B, inv_t, cm, cs, bias);
+    if (int rc = check_launch(MEM ? "npair_memory_stats columns" : "npair_stats columns")) return rc;
+    hipLaunchKernelGGL(k_npair_col_fold<BIAS>, dim3(gx), dim3(kNpThreads), 0, st, S, lds, B, chunks, inv_t, cm, cs, lse, closs,
+                       bias);
+    if (int rc = check_launch(MEM ? "npair_memory_stats column fold" : "npair_stats column fold")) return rc;
+  }
+  hipLaunchKernelGGL(k_npair_stats, dim3(1), dim3(1024), 0, st, part, closs, B, symmetric ? 1 : 0, MEM ? M : 0, stats);
+  return check_launch(who);
+}
+
+int np_w_x3_check(const char *who, int B, const uint16_t *W, int64_t ldw, int64_t plane) {
+  CDML_REQUIRE(W, CDML_E_BADARG, "%s: null pointer", who);
+  CDML_REQUIRE(plane >= B && ldw >= 2 * plane + B && (plane & 3) == 0 && (ldw & 3) == 0 &&
+                   (reinterpret_cast<uintptr_t>(W) & 7) == 0,
+               CDML_E_BADARG,
+               "%s: W needs an 8-B aligned base, plane >= B (%d) and ldw >= 2 plane + B, both multiples of 4 "
+               "(got plane %lld, ldw %lld)", who, B, (long long)plane, (long long)ldw);
+  return CDML_OK;
+}
+
+int np_w_f32_check(const char *who, int B, const float *W, int64_t ldw) {
+  CDML_REQUIRE(W, CDML_E_BADARG, "%s: null pointer", who);
+  CDML_REQUIRE(ldw >= B && (ldw & 3) == 0 && aligned16(W), CDML_E_BADARG,
+               "%s: W needs a 16-B aligned base and ldw >= B (%d), a multiple of 4 (got %lld)", who, B, (long long)ldw);
+  return CDML_OK;
+}
+
+template <bool X3, bool BIAS>
+int np_w_launch(const char *who, const float *S, int64_t lds, const int32_t *ids, int B, const float *bias, float temperature,
+                int symmetric, const float *lse, void *W, int64_t ldw, int64_t plane, cdml_stream_t stream) {
+  const dim3 grid((unsigned)B, (unsigned)((B + 4 * kNpThreads - 1) / (4 * kNpThreads)));
+  hipLaunchKernelGGL((k_npair_w<X3, BIAS>), grid, dim3(kNpThreads), 0, (hipStream_t)stream, S, lds, ids, B, 1.0f / temperature,
+                     symmetric ? 1 : 0, lse, 1.0f / ((float)B * temperature), W, ldw, plane, bias);
+  return check_launch(who);
+}
+
 }  // namespace
 }  // namespace cdml
 
@@ -397,54 +517,52 @@ extern "C" size_t cdml_npair_workspace(int B) { return np_ws_bytes(B); }
 extern "C" int cdml_npair_stats(const float *S, int64_t lds, const int32_t *ids, int B, float temperature, int symmetric,
                                 float *lse, float *stats, void *workspace, size_t workspace_bytes, cdml_stream_t stream) {
   if (int rc = np_check("npair_stats", S, lds, B, temperature, lse)) return rc;
-  CDML_REQUIRE(stats && workspace, CDML_E_BADARG, "npair_stats: null pointer");
-  CDML_REQUIRE(aligned16(workspace) && workspace_bytes >= np_ws_bytes(B), CDML_E_BADARG,
-               "npair_stats: the workspace must be 16-B aligned and hold cdml_npair_workspace(%d) = %zu bytes (got %zu)", B,
-               np_ws_bytes(B), workspace_bytes);
-  const float inv_t = 1.0f / temperature;
-  const int chunks = np_chunks(B);
-  float *part = static_cast<float *>(workspace), *closs = part + 4 * (size_t)B;
-  float *cm = closs + B, *cs = cm + (size_t)chunks * B;
-  hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(k_npair_rows<false>, dim3(B), dim3(kNpThreads), 0, st, S, lds, ids, B, inv_t, lse, part, (int64_t)0,
-                     (const int32_t *)nullptr, 0);
-  if (int rc = check_launch("npair_stats rows")) return rc;
-  if (symmetric) {
-    const unsigned gx = (unsigned)((B + kNpThreads - 1) / kNpThreads);
-    hipLaunchKernelGGL(k_npair_cols, dim3(gx, chunks), dim3(kNpThreads), 0, st, S, lds, ids, B, inv_t, cm, cs);
-    if (int rc = check_launch("npair_stats columns")) return rc;
-    hipLaunchKernelGGL(k_npair_col_fold, dim3(gx), dim3(kNpThreads), 0, st, S, lds, B, chunks, inv_t, cm, cs, lse, closs);
-    if (int rc = check_launch("npair_stats column fold")) return rc;
-  }
-  hipLaunchKernelGGL(k_npair_stats, dim3(1), dim3(1024), 0, st, part, closs, B, symmetric ? 1 : 0, 0, stats);
-  return check_launch("npair_stats");
+  return np_stats_launch<false, false>("npair_stats", S, lds, ids, B, nullptr, 0, nullptr, nullptr, 0, temperature, symmetric,
+                                       lse, stats, workspace, workspace_bytes, stream);
 }
 
 extern "C" int cdml_npair_grad_x3(const float *S, int64_t lds, const int32_t *ids, int B, float temperature, int symmetric,
                                   const float *lse, uint16_t *W, int64_t ldw, int64_t plane, cdml_stream_t stream) {
   if (int rc = np_check("npair_grad_x3", S, lds, B, temperature, lse)) return rc;
-  CDML_REQUIRE(W, CDML_E_BADARG, "npair_grad_x3: null pointer");
-  CDML_REQUIRE(plane >= B && ldw >= 2 * plane + B && (plane & 3) == 0 && (ldw & 3) == 0 &&
-                   (reinterpret_cast<uintptr_t>(W) & 7) == 0,
-               CDML_E_BADARG,
-               "npair_grad_x3: W needs an 8-B aligned base, plane >= B (%d) and ldw >= 2 plane + B, both multiples of 4 "
-               "(got plane %lld, ldw %lld)", B, (long long)plane, (long long)ldw);
-  const dim3 grid((unsigned)B, (unsigned)((B + 4 * kNpThreads - 1) / (4 * kNpThreads)));
-  hipLaunchKernelGGL(k_npair_w<true>, grid, dim3(kNpThreads), 0, (hipStream_t)stream, S, lds, ids, B, 1.0f / temperature,
-                     symmetric ? 1 : 0, lse, 1.0f / ((float)B * temperature), (void *)W, ldw, plane);
-  return check_launch("npair_grad_x3");
+  if (int rc = np_w_x3_check("npair_grad_x3", B, W, ldw, plane)) return rc;
+  return np_w_launch<true, false>("npair_grad_x3", S, lds, ids, B, nullptr, temperature, symmetric, lse, W, ldw, plane, stream);
 }
 
 extern "C" int cdml_npair_grad_f32(const float *S, int64_t lds, const int32_t *ids, int B, float temperature, int symmetric,
                                    const float *lse, float *W, int64_t ldw, cdml_stream_t stream) {
   if (int rc = np_check("npair_grad_f32", S, lds, B, temperature, lse)) return rc;
-  CDML_REQUIRE(W, CDML_E_BADARG, "npair_grad_f32: null pointer");
-  CDML_REQUIRE(ldw >= B && (ldw & 3) == 0 && aligned16(W), CDML_E_BADARG,
-               "npair_grad_f32: W needs a 16-B aligned base and ldw >= B (%d), a multiple of 4 (got %lld)", B, (long long)ldw);
-  const dim3 grid((unsigned)B, (unsigned)((B + 4 * kNpThreads - 1) / (4 * kNpThreads)));
-  hipLaunchKernelGGL(k_npair_w<false>, grid, dim3(kNpThreads), 0, (hipStream_t)stream, S, lds, ids, B, 1.0f / temperature,
-                     symmetric ? 1 : 0, lse, 1.0f / ((float)B * temperature), (void *)W, ldw, (int64_t)0);
-  return check_launch("npair_grad_f32");
+  if (int rc = np_w_f32_check("npair_grad_f32", B, W, ldw)) return rc;
+  return np_w_launch<false, false>("npair_grad_f32", S, lds, ids, B, nullptr, temperature, symmetric, lse, W, ldw, 0, stream);
+}
+
+// ---- the sampling-bias (logQ) corrected loss: bias[2B] per row as ids, laid out by csrc/npair_logq.hip ------------------
+
+extern "C" int cdml_npair_logq_stats(const float *S, int64_t lds, const int32_t *ids, int B, const float *bias,
+                                     float temperature, int symmetric, float *lse, float *stats, void *workspace,
+                                     size_t workspace_bytes, cdml_stream_t stream) {
+  if (int rc = np_check("npair_logq_stats", S, lds, B, temperature, lse)) return rc;
+  if (int rc = np_bias_check("npair_logq_stats", bias)) return rc;
+  return np_stats_launch<false, true>("npair_logq_stats", S, lds, ids, B, bias, 0, nullptr, nullptr, 0, temperature, symmetric,
+                                      lse, stats, workspace, workspace_bytes, stream);
+}
+
+extern "C" int cdml_npair_logq_grad_x3(const float *S, int64_t lds, const int32_t *ids, int B, const float *bias,
+                                       float temperature, int symmetric, const float *lse, uint16_t *W, int64_t ldw,
+                                       int64_t plane, cdml_stream_t stream) {
+  if (int rc = np_check("npair_logq_grad_x3", S, lds, B, temperature, lse)) return rc;
+  if (int rc = np_bias_check("npair_logq_grad_x3", bias)) return rc;
+  if (int rc = np_w_x3_check("npair_logq_grad_x3", B, W, ldw, plane)) return rc;
+  return np_w_launch<true, true>("npair_logq_grad_x3", S, lds, ids, B, bias, temperature, symmetric, lse, W, ldw, plane,
+                                 stream);
+}
+
+extern "C" int cdml_npair_logq_grad_f32(const float *S, int64_t lds, const int32_t *ids, int B, const float *bias,
+                                        float temperature, int symmetric, const float *lse, float *W, int64_t ldw,
+                                        cdml_stream_t stream) {
+  if (int rc = np_check("npair_logq_grad_f32", S, lds, B, temperature, lse)) return rc;
+  if (int rc = np_bias_check("npair_logq_grad_f32", bias)) return rc;
+  if (int rc = np_w_f32_check("npair_logq_grad_f32", B, W, ldw)) return rc;
+  return np_w_launch<false, true>("npair_logq_grad_f32", S, lds, ids, B, bias, temperature, symmetric, lse, W, ldw, 0, stream);
 }
 
 // ---- cross-batch memory (XBM, Wang et al. 2020): a ring of M earlier positives as extra row-term columns of S ----------
@@ -466,6 +584,41 @@ int npm_check(const char *who, const float *S, int64_t lds, int B, int64_t mem_c
   return CDML_OK;
 }
 
+int npm_mem_bias_check(const char *who, const float *mem_bias) {
+  CDML_REQUIRE(mem_bias, CDML_E_BADARG, "%s: null pointer (mem_bias)", who);
+  CDML_REQUIRE(aligned16(mem_bias), CDML_E_BADARG, "%s: mem_bias needs a 16-B aligned base", who);
+  return CDML_OK;
+}
+
+int npm_w_x3_check(const char *who, int64_t mem_col, int M, const uint16_t *W, int64_t ldw, int64_t plane) {
+  CDML_REQUIRE(W, CDML_E_BADARG, "%s: null pointer", who);
+  CDML_REQUIRE(plane >= mem_col + M && ldw >= 2 * plane + mem_col + M && (plane & 3) == 0 && (ldw & 3) == 0 &&
+                   (reinterpret_cast<uintptr_t>(W) & 7) == 0,
+               CDML_E_BADARG,
+               "%s: W needs an 8-B aligned base, plane >= mem_col + M (%lld) and ldw >= 2 plane + mem_col + M, "
+               "both multiples of 4 (got plane %lld, ldw %lld)", who, (long long)(mem_col + M), (long long)plane, (long long)ldw);
+  return CDML_OK;
+}
+
+int npm_w_f32_check(const char *who, int64_t mem_col, int M, const float *W, int64_t ldw) {
+  CDML_REQUIRE(W, CDML_E_BADARG, "%s: null pointer", who);
+  CDML_REQUIRE(ldw >= mem_col + M && (ldw & 3) == 0 && aligned16(W), CDML_E_BADARG,
+               "%s: W needs a 16-B aligned base and ldw >= mem_col + M (%lld), a multiple of 4 (got %lld)", who,
+               (long long)(mem_col + M), (long long)ldw);
+  return CDML_OK;
+}
+
+template <bool X3, bool BIAS>
+int npm_w_launch(const char *who, const float *S, int64_t lds, const int32_t *ids, int B, int64_t mem_col,
+                 const int32_t *mem_id, const float *mem_bias, int M, float temperature, int symmetric, const float *lse,
+                 void *W, int64_t ldw, int64_t plane, cdml_stream_t stream) {
+  const dim3 grid((unsigned)B, (unsigned)((M + 4 * kNpThreads - 1) / (4 * kNpThreads)));
+  const float scale = (symmetric ? 0.5f : 1.0f) / ((float)B * temperature);
+  hipLaunchKernelGGL((k_npair_mem_w<X3, BIAS>), grid, dim3(kNpThreads), 0, (hipStream_t)stream, S, lds, mem_col, ids, mem_id, M,
+                     1.0f / temperature, lse, scale, W, ldw, plane, mem_bias);
+  return check_launch(who);
+}
+
 }  // namespace
 }  // namespace cdml
 
@@ -475,59 +628,58 @@ extern "C" int cdml_npair_memory_stats(const float *S, int64_t lds, const int32_
                                        const int32_t *mem_id, int M, float temperature, int symmetric, float *lse,
                                        float *stats, void *workspace, size_t workspace_bytes, cdml_stream_t stream) {
   if (int rc = npm_check("npair_memory_stats", S, lds, B, mem_col, mem_id, M, temperature, lse)) return rc;
-  CDML_REQUIRE(stats && workspace, CDML_E_BADARG, "npair_memory_stats: null pointer");
-  CDML_REQUIRE(aligned16(workspace) && workspace_bytes >= np_ws_bytes(B), CDML_E_BADARG,
-               "npair_memory_stats: the workspace must be 16-B aligned and hold cdml_npair_memory_workspace(%d, %d) = %zu "
-               "bytes (got %zu)", B, M, np_ws_bytes(B), workspace_bytes);
-  const float inv_t = 1.0f / temperature;
-  const int chunks = np_chunks(B);
-  float *part = static_cast<float *>(workspace), *closs = part + 4 * (size_t)B;
-  float *cm = closs + B, *cs = cm + (size_t)chunks * B;
-  hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(k_npair_rows<true>, dim3(B), dim3(kNpThreads), 0, st, S, lds, ids, B, inv_t, lse, part, mem_col, mem_id,
-                     M);
-  if (int rc = check_launch("npair_memory_stats rows")) return rc;
-  if (symmetric) {                                   // the column term: the in-batch block as it stands, through lds
-    const unsigned gx = (unsigned)((B + kNpThreads - 1) / kNpThreads);
-    hipLaunchKernelGGL(k_npair_cols, dim3(gx, chunks), dim3(kNpThreads), 0, st, S, lds, ids, B, inv_t, cm, cs);
-    if (int rc = check_launch("npair_memory_stats columns")) return rc;
-    hipLaunchKernelGGL(k_npair_col_fold, dim3(gx), dim3(kNpThreads), 0, st, S, lds, B, chunks, inv_t, cm, cs, lse, closs);
-    if (int rc = check_launch("npair_memory_stats column fold")) return rc;
-  }
-  hipLaunchKernelGGL(k_npair_stats, dim3(1), dim3(1024), 0, st, part, closs, B, symmetric ? 1 : 0, M, stats);
-  return check_launch("npair_memory_stats");
+  return np_stats_launch<true, false>("npair_memory_stats", S, lds, ids, B, nullptr, mem_col, mem_id, nullptr, M, temperature,
+                                      symmetric, lse, stats, workspace, workspace_bytes, stream);
 }
 
 extern "C" int cdml_npair_memory_grad_x3(const float *S, int64_t lds, const int32_t *ids, int B, int64_t mem_col,
                                          const int32_t *mem_id, int M, float temperature, int symmetric, const float *lse,
                                          uint16_t *W, int64_t ldw, int64_t plane, cdml_stream_t stream) {
   if (int rc = npm_check("npair_memory_grad_x3", S, lds, B, mem_col, mem_id, M, temperature, lse)) return rc;
-  CDML_REQUIRE(W, CDML_E_BADARG, "npair_memory_grad_x3: null pointer");
-  CDML_REQUIRE(plane >= mem_col + M && ldw >= 2 * plane + mem_col + M && (plane & 3) == 0 && (ldw & 3) == 0 &&
-                   (reinterpret_cast<uintptr_t>(W) & 7) == 0,
-               CDML_E_BADARG,
-               "npair_memory_grad_x3: W needs an 8-B aligned base, plane >= mem_col + M (%lld) and ldw >= 2 plane + mem_col + M, "
-               "both multiples of 4 (got plane %lld, ldw %lld)", (long long)(mem_col + M), (long long)plane, (long long)ldw);
-  const dim3 grid((unsigned)B, (unsigned)((M + 4 * kNpThreads - 1) / (4 * kNpThreads)));
-  const float scale = (symmetric ? 0.5f : 1.0f) / ((float)B * temperature);
-  hipLaunchKernelGGL(k_npair_mem_w<true>, grid, dim3(kNpThreads), 0, (hipStream_t)stream, S, lds, mem_col, ids, mem_id, M,
-                     1.0f / temperature, lse, scale, (void *)W, ldw, plane);
-  return check_launch("npair_memory_grad_x3");
+  if (int rc = npm_w_x3_check("npair_memory_grad_x3", mem_col, M, W, ldw, plane)) return rc;
+  return npm_w_launch<true, false>("npair_memory_grad_x3", S, lds, ids, B, mem_col, mem_id, nullptr, M, temperature, symmetric,
+                                   lse, W, ldw, plane, stream);
 }
 
 extern "C" int cdml_npair_memory_grad_f32(const float *S, int64_t lds, const int32_t *ids, int B, int64_t mem_col,
                                           const int32_t *mem_id, int M, float temperature, int symmetric, const float *lse,
                                           float *W, int64_t ldw, cdml_stream_t stream) {
   if (int rc = npm_check("npair_memory_grad_f32", S, lds, B, mem_col, mem_id, M, temperature, lse)) return rc;
-  CDML_REQUIRE(W, CDML_E_BADARG, "npair_memory_grad_f32: null pointer");
-  CDML_REQUIRE(ldw >= mem_col + M && (ldw & 3) == 0 && aligned16(W), CDML_E_BADARG,
-               "npair_memory_grad_f32: W needs a 16-B aligned base and ldw >= mem_col + M (%lld), a multiple of 4 (got %lld)",
-               (long long)(mem_col + M), (long long)ldw);
-  const dim3 grid((unsigned)B, (unsigned)((M + 4 * kNpThreads - 1) / (4 * kNpThreads)));
-  const float scale = (symmetric ? 0.5f : 1.0f) / ((float)B * temperature);
-  hipLaunchKernelGGL(k_npair_mem_w<false>, grid, dim3(kNpThreads), 0, (hipStream_t)stream, S, lds, mem_col, ids, mem_id, M,
-                     1.0f / temperature, lse, scale, (void *)W, ldw, (int64_t)0);
-  return check_launch("npair_memory_grad_f32");
+  if (int rc = npm_w_f32_check("npair_memory_grad_f32", mem_col, M, W, ldw)) return rc;
+  return npm_w_launch<false, false>("npair_memory_grad_f32", S, lds, ids, B, mem_col, mem_id, nullptr, M, temperature,
+                                    symmetric, lse, W, ldw, 0, stream);
+}
+
+extern "C" int cdml_npair_memory_logq_stats(const float *S, int64_t lds, const int32_t *ids, int B, const float *bias,
+                                            int64_t mem_col, const int32_t *mem_id, const float *mem_bias, int M,
+                                            float temperature, int symmetric, float *lse, float *stats, void *workspace,
+                                            size_t workspace_bytes, cdml_stream_t stream) {
+  if (int rc = npm_check("npair_memory_logq_stats", S, lds, B, mem_col, mem_id, M, temperature, lse)) return rc;
+  if (int rc = np_bias_check("npair_memory_logq_stats", bias)) return rc;
+  if (int rc = npm_mem_bias_check("npair_memory_logq_stats", mem_bias)) return rc;
+  return np_stats_launch<true, true>("npair_memory_logq_stats", S, lds, ids, B, bias, mem_col, mem_id, mem_bias, M, temperature,
+                                     symmetric, lse, stats, workspace, workspace_bytes, stream);
+}
+
+extern "C" int cdml_npair_memory_logq_grad_x3(const float *S, int64_t lds, const int32_t *ids, int B, int64_t mem_col,
+                                              const int32_t *mem_id, const float *mem_bias, int M, float temperature,
+                                              int symmetric, const float *lse, uint16_t *W, int64_t ldw, int64_t plane,
+                                              cdml_stream_t stream) {
+  if (int rc = npm_check("npair_memory_logq_grad_x3", S, lds, B, mem_col, mem_id, M, temperature, lse)) return rc;
+  if (int rc = npm_mem_bias_check("npair_memory_logq_grad_x3", mem_bias)) return rc;
+  if (int rc = npm_w_x3_check("npair_memory_logq_grad_x3", mem_col, M, W, ldw, plane)) return rc;
+  return npm_w_launch<true, true>("npair_memory_logq_grad_x3", S, lds, ids, B, mem_col, mem_id, mem_bias, M, temperature,
+                                  symmetric, lse, W, ldw, plane, stream);
+}
+
+extern "C" int cdml_npair_memory_logq_grad_f32(const float *S, int64_t lds, const int32_t *ids, int B, int64_t mem_col,
+                                               const int32_t *mem_id, const float *mem_bias, int M, float temperature,
+                                               int symmetric, const float *lse, float *W, int64_t ldw, cdml_stream_t stream) {
+  if (int rc = npm_check("npair_memory_logq_grad_f32", S, lds, B, mem_col, mem_id, M, temperature, lse)) return rc;
+  if (int rc = npm_mem_bias_check("npair_memory_logq_grad_f32", mem_bias)) return rc;
+  if (int rc = npm_w_f32_check("npair_memory_logq_grad_f32", mem_col, M, W, ldw)) return rc;
+  return npm_w_launch<false, true>("npair_memory_logq_grad_f32", S, lds, ids, B, mem_col, mem_id, mem_bias, M, temperature,
+                                   symmetric, lse, W, ldw, 0, stream);
 }
 
 extern "C" int cdml_npair_memory_push(const float *P, int64_t ldp, const int32_t *ids, int B, int D, uint64_t step,

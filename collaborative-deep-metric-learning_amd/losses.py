@@ -54,7 +54,7 @@ class HingeLoss(BaseLoss):
 
 class _NPairFunction(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, pairs, temperature, symmetric, ids):
+    def forward(ctx, pairs, temperature, symmetric, ids, logq=None):
         B, _, D = pairs.shape
         dev = pairs.device
         # the chain's tile rules: B up to a multiple of 256 pairs, D up to a multiple of 64 columns, zero rows / columns
@@ -70,7 +70,11 @@ class _NPairFunction(torch.autograd.Function):
         ws = ops.NPairWorkspace(Bp, Dp, "f32x3", dev)
         de = torch.zeros_like(e) if pairs.requires_grad else None
         stats = torch.zeros(4, dtype=torch.float32, device=dev)
-        ops.npair_loss(e, rows, B, Dp, temperature, symmetric, "f32x3", de=de, stats=stats, ws=ws)
+        bias = None
+        if logq is not None:                              # each row's lq, laid out like rows (padded pairs: 0)
+            bias = torch.zeros(2 * Bp, dtype=torch.float32, device=dev)
+            bias[:2 * B] = logq.reshape(-1).to(device=dev, dtype=torch.float32)
+        ops.npair_loss(e, rows, B, Dp, temperature, symmetric, "f32x3", de=de, stats=stats, ws=ws, logq=bias)
         part = ws.ws[:4 * B].view(B, 4)                   # per anchor: loss term, 2 - 2 <a, p>, negatives' sum, their count
         pos = part[:, 1].clone()
         neg = part[:, 2] / part[:, 3].clamp(min=1.0)
@@ -80,23 +84,30 @@ class _NPairFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_loss, *_unused):
-        return ctx.de * g_loss, None, None, None
+        return ctx.de * g_loss, None, None, None, None
 
 
 class NPairLoss(BaseLoss):
-    def calculate_loss(self, pairs, temperature=0.1, symmetric=True, ids=None):
+    def calculate_loss(self, pairs, temperature=0.1, symmetric=True, ids=None, logq=None):
         """Multi-class N-pair (in-batch softmax) loss -- build-defined, the reference has no such loss.  pairs: float32
         [batch, 2, embedding] device tensor of unit rows (anchor, positive); every other pair's positive is a negative of
         an anchor, and with ``symmetric`` every other anchor a negative of a positive.  ``ids`` (int [batch, 2] video ids of
         the rows, optional): a negative that is the same video as the anchor or its positive does not count.
         ``temperature`` 0.1 and ``symmetric`` True are the build's defaults.  Distances are SQUARED L2 of unit rows:
-        pos_dist = |a_i - p_i|^2, neg_dist = the mean over anchor i's counted negatives ([batch, 1])."""
+        pos_dist = |a_i - p_i|^2, neg_dist = the mean over anchor i's counted negatives ([batch, 1]).  ``logq`` (float
+        [batch, 2], optional): each row's log sampling probability -- the sampling-bias correction of Yi et al. 2019, every
+        logit less its candidate's logq (the anchor's in the column term, the positive's in the row term)."""
         if pairs.dim() != 3 or pairs.shape[1] != 2:
             raise ValueError("pairs must be [batch, 2, embedding]")
         if ids is not None and ids.numel() != 2 * pairs.shape[0]:
             raise ValueError("ids must hold one video id per row ([batch, 2])")
+        if logq is not None:
+            if logq.numel() != 2 * pairs.shape[0]:
+                raise ValueError("logq must hold one log-probability per row ([batch, 2])")
+            if not bool(torch.isfinite(logq).all()):
+                raise ValueError("every logq entry must be finite")
         pairs = pairs.to(torch.float32)
-        loss, pos, neg, stats = _NPairFunction.apply(pairs, float(temperature), bool(symmetric), ids)
+        loss, pos, neg, stats = _NPairFunction.apply(pairs, float(temperature), bool(symmetric), ids, logq)
         self.summary = {"mean_pos_dist": stats[1], "mean_neg_dist": stats[2]}
         return {"npair_loss": loss,
                 "anchors": pairs[:, 0:1, :],

@@ -369,6 +369,7 @@ class NPairWorkspace:
         bf = lambda *s: torch.zeros(s, dtype=torch.bfloat16, device=device)
         self.S = f32(Bp, Bp) if in_batch else None
         self.lse = f32(2 * Bp)
+        self.bias = f32(2 * Bp)                             # logQ correction: lq of every row, laid out like the ids
         self.ws = torch.zeros(npair_workspace(Bp) // 4, dtype=torch.float32, device=device)
         if precision == "f32x3":
             self.Dq = Dq = (Dp + 255) // 256 * 256          # the plane GEMMs' N tile: narrower rows are zero-padded
@@ -462,6 +463,7 @@ class NPairMemory:
         f32 = lambda *s: torch.zeros(s, dtype=torch.float32, device=device)
         bf = lambda *s: torch.zeros(s, dtype=torch.bfloat16, device=device)
         self.ids = torch.full((M,), -1, dtype=torch.int32, device=device)
+        self.bias = f32(M)                                  # logQ correction: lq of every slot's video
         self.S = f32(Bp, K)
         if precision == "f32x3":
             self.Dq = Dq = (Dp + 255) // 256 * 256
@@ -502,8 +504,160 @@ class NPairMemory:
         return {"size": self.M, "rows": self.rows.detach().cpu().clone(), "ids": self.ids.detach().cpu().clone()}
 
 
+# ---- sampling-bias (logQ) correction of the N-pair loss (Yi et al. 2019; csrc/npair_logq.hip; build-defined) ----
+def npair_logq_stats(S, rows, B, bias, temperature, symmetric, lse, stats, workspace):
+    """npair_stats with every logit less its candidate's lq (bias fp32 [>= 2B], laid out like rows)."""
+    sp, sld = _mat(S)
+    call("cdml_npair_logq_stats", sp, sld, _p(rows, torch.int32), int(B), _p(bias, torch.float32), float(temperature),
+         1 if symmetric else 0, _p(lse), _p(stats), _p(workspace), workspace.numel() * workspace.element_size(), _stream())
+    return lse, stats
+
+
+def npair_logq_grad_x3(S, rows, B, bias, temperature, symmetric, lse, W_planes, plane):
+    sp, sld = _mat(S)
+    wp, wld = _mat16(W_planes)
+    call("cdml_npair_logq_grad_x3", sp, sld, _p(rows, torch.int32), int(B), _p(bias, torch.float32), float(temperature),
+         1 if symmetric else 0, _p(lse), wp, wld, int(plane), _stream())
+    return W_planes
+
+
+def npair_logq_grad_f32(S, rows, B, bias, temperature, symmetric, lse, W):
+    sp, sld = _mat(S)
+    wp, wld = _mat(W)
+    call("cdml_npair_logq_grad_f32", sp, sld, _p(rows, torch.int32), int(B), _p(bias, torch.float32), float(temperature),
+         1 if symmetric else 0, _p(lse), wp, wld, _stream())
+    return W
+
+
+def npair_memory_logq_stats(S, rows, B, bias, mem_col, mem_id, mem_bias, temperature, symmetric, lse, stats, workspace):
+    sp, sld = _mat(S)
+    call("cdml_npair_memory_logq_stats", sp, sld, _p(rows, torch.int32), int(B), _p(bias, torch.float32), int(mem_col),
+         _p(mem_id, torch.int32), _p(mem_bias, torch.float32), mem_id.numel(), float(temperature), 1 if symmetric else 0,
+         _p(lse), _p(stats), _p(workspace), workspace.numel() * workspace.element_size(), _stream())
+    return lse, stats
+
+
+def npair_memory_logq_grad_x3(S, rows, B, mem_col, mem_id, mem_bias, temperature, symmetric, lse, W_planes, plane):
+    sp, sld = _mat(S)
+    wp, wld = _mat16(W_planes)
+    call("cdml_npair_memory_logq_grad_x3", sp, sld, _p(rows, torch.int32), int(B), int(mem_col), _p(mem_id, torch.int32),
+         _p(mem_bias, torch.float32), mem_id.numel(), float(temperature), 1 if symmetric else 0, _p(lse), wp, wld, int(plane),
+         _stream())
+    return W_planes
+
+
+def npair_memory_logq_grad_f32(S, rows, B, mem_col, mem_id, mem_bias, temperature, symmetric, lse, W):
+    sp, sld = _mat(S)
+    wp, wld = _mat(W)
+    call("cdml_npair_memory_logq_grad_f32", sp, sld, _p(rows, torch.int32), int(B), int(mem_col), _p(mem_id, torch.int32),
+         _p(mem_bias, torch.float32), mem_id.numel(), float(temperature), 1 if symmetric else 0, _p(lse), wp, wld, _stream())
+    return W
+
+
+def logq_table_gather(table, rows, B, mem_id, bias, mem_bias):
+    """bias[:2B] <- table[rows[:2B]], mem_bias <- table[mem_id] (0 for -1 and for ids outside the table)."""
+    call("cdml_logq_table_gather", _p(table, torch.float32), table.numel(), _p(rows, torch.int32), int(B),
+         _p(mem_id, torch.int32), 0 if mem_id is None else mem_id.numel(), _p(bias, torch.float32),
+         _p(mem_bias, torch.float32), _stream())
+
+
+def logq_stream_gather(last, gap, rows, B, mem_id, bias, mem_bias, snap_last, snap_gap):
+    call("cdml_logq_stream_gather", _p(last, torch.int32), _p(gap, torch.float32), gap.numel(), _p(rows, torch.int32),
+         int(B), _p(mem_id, torch.int32), 0 if mem_id is None else mem_id.numel(), _p(bias, torch.float32),
+         _p(mem_bias, torch.float32), _p(snap_last, torch.int32), _p(snap_gap, torch.float32), _stream())
+
+
+def logq_stream_update(last, gap, rows, B, snap_last, snap_gap, alpha, step, step_dev):
+    call("cdml_logq_stream_update", _p(last, torch.int32), _p(gap, torch.float32), gap.numel(), _p(rows, torch.int32),
+         int(B), _p(snap_last, torch.int32), _p(snap_gap, torch.float32), float(alpha), 0 if step is None else int(step),
+         _p(step_dev, torch.int64), _stream())
+
+
+def logq_stream_reset(last, gap, g0):
+    call("cdml_logq_stream_reset", _p(last, torch.int32), _p(gap, torch.float32), gap.numel(), float(g0), _stream())
+
+
+class LogQTable:
+    """A fixed per-video log sampling probability lq(v) = logq[v] (fp32 [n_videos], every entry finite) as the source of
+    ``npair_loss(logq=...)``'s correction -- e.g. the log of each video's share of the co-watch degrees."""
+
+    def __init__(self, logq, device):
+        t = torch.as_tensor(logq).detach().to(device=device, dtype=torch.float32).reshape(-1).contiguous()
+        if t.numel() < 1:
+            raise ValueError("a logQ table needs at least one entry")
+        if not bool(torch.isfinite(t).all()):
+            raise ValueError("every entry of the logQ table must be finite")
+        self.table, self.n_videos = t, t.numel()
+
+    def logq(self):
+        return self.table
+
+    def gather(self, rows, B, mem_id, bias, mem_bias):
+        logq_table_gather(self.table, rows, B, mem_id, bias, mem_bias)
+
+    def update(self, rows, B, step, step_dev):
+        pass                                                # a fixed table does not learn
+
+    def state_dict(self):
+        return {"logq": self.table.detach().cpu().clone()}
+
+    def load(self, state):
+        t = torch.as_tensor(state["logq"]).reshape(-1)
+        if t.numel() != self.n_videos or not bool(torch.isfinite(t).all()):
+            raise ValueError("a logQ table of %d finite entries, got %d" % (self.n_videos, t.numel()))
+        self.table.copy_(t.to(device=self.table.device, dtype=torch.float32))
+
+
+class LogQEstimator:
+    """Yi et al.'s streaming estimate of each video's sampling probability, indexed by video id: ``last`` int32
+    [n_videos] (the step the video was last drawn as a positive, -1 = unseen) and ``gap`` fp32 [n_videos] (the smoothed
+    steps between draws, initially g0 = ``init_gap`` or max(1, n_videos / Bp)); lq(v) = -log(gap[v]).  Step t updates every
+    positive video of its batch once, after the products that read the bias: gap = (1 - alpha) gap + alpha (t - last)
+    when seen before, last = t (csrc/npair_logq.hip).  Bp: the batch's pairs (the snapshot buffers)."""
+
+    def __init__(self, n_videos, Bp, alpha=0.01, init_gap=None, device="cuda"):
+        n, Bp, alpha = int(n_videos), int(Bp), float(alpha)
+        if n < 1 or n > 2 ** 31 - 1:
+            raise ValueError("n_videos must be in [1, 2^31 - 1], got %d" % n)
+        if not 0.0 < alpha <= 1.0:
+            raise ValueError("logq_alpha must be in (0, 1], got %r" % (alpha,))
+        g0 = max(1.0, n / Bp) if init_gap is None else float(init_gap)
+        if not (1.0 <= g0 < float("inf")):
+            raise ValueError("logq_init_gap must be finite and >= 1, got %r" % (init_gap,))
+        self.n_videos, self.Bp, self.alpha, self.init_gap = n, Bp, alpha, g0
+        self.last = torch.empty(n, dtype=torch.int32, device=device)
+        self.gap = torch.empty(n, dtype=torch.float32, device=device)
+        self.snap_last = torch.zeros(Bp, dtype=torch.int32, device=device)
+        self.snap_gap = torch.zeros(Bp, dtype=torch.float32, device=device)
+        self.reset()
+
+    def reset(self):
+        logq_stream_reset(self.last, self.gap, self.init_gap)
+
+    def logq(self):
+        return -torch.log(self.gap)
+
+    def gather(self, rows, B, mem_id, bias, mem_bias):
+        logq_stream_gather(self.last, self.gap, rows, B, mem_id, bias, mem_bias, self.snap_last, self.snap_gap)
+
+    def update(self, rows, B, step, step_dev):
+        logq_stream_update(self.last, self.gap, rows, B, self.snap_last, self.snap_gap, self.alpha, step, step_dev)
+
+    def state_dict(self):
+        return {"last": self.last.detach().cpu().clone(), "gap": self.gap.detach().cpu().clone(), "alpha": self.alpha,
+                "init_gap": self.init_gap}
+
+    def load(self, state):
+        if tuple(state["last"].shape) != (self.n_videos,) or tuple(state["gap"].shape) != (self.n_videos,):
+            raise ValueError("a logQ estimator of %d videos, got %s / %s"
+                             % (self.n_videos, tuple(state["last"].shape), tuple(state["gap"].shape)))
+        self.alpha, self.init_gap = float(state["alpha"]), float(state["init_gap"])
+        self.last.copy_(state["last"].to(device=self.last.device, dtype=torch.int32))
+        self.gap.copy_(state["gap"].to(device=self.gap.device, dtype=torch.float32))
+
+
 def npair_loss(e, rows, B, Dp, temperature=0.1, symmetric=True, precision="f32x3", de=None, stats=None, ws=None,
-               memory=None, step=0, step_dev=None):
+               memory=None, step=0, step_dev=None, logq=None):
     """The multi-class N-pair loss of B pairs and its gradient (include/cdml.h, "multi-class N-pair loss").
     e: fp32 [2 Bp, Dp] unit rows, row 2i = anchor i, row 2i+1 = positive i (rows >= 2B zero: padding); rows: int32 [2 Bp]
     video ids or None.  The chain: S = A P^T -> row (and column) log-sum-exp + step scalars -> W -> dA = W P, dP = W^T A,
@@ -513,6 +667,10 @@ def npair_loss(e, rows, B, Dp, temperature=0.1, symmetric=True, precision="f32x3
     memory: an NPairMemory (B == Bp, video ids given): its ring adds M negatives to every anchor's row term -- S = A [P;
     Mem]^T -> statistics -> W (the in-batch block + the memory block) -> dA = W [P; Mem] over K = Bp + M, dP = W^T A ->
     with ``de``, the push of this step's positives (step number ``step`` + *step_dev, the sampler's convention).
+    logq: the sampling-bias correction (Yi et al. 2019) -- every logit less its candidate's log sampling probability lq.
+    A LogQTable or LogQEstimator (video ids ``rows`` required): one gather launch fills ws.bias (and the memory's bias)
+    before the statistics, and with ``de`` an estimator's update follows the gradient weights (before the push); or a
+    fp32 tensor [>= 2B] of each row's lq, laid out like ``rows`` (no memory).  None: the uncorrected chain, launch for launch.
     Returns (stats, lse): lse[:B] the rows', lse[B:2B] the columns' (symmetric)."""
     if not (temperature > 0.0) or temperature == float("inf"):
         raise ValueError("temperature must be finite and > 0, got %r" % (temperature,))
@@ -527,8 +685,19 @@ def npair_loss(e, rows, B, Dp, temperature=0.1, symmetric=True, precision="f32x3
         stats = torch.zeros(4, dtype=torch.float32, device=e.device)
     if memory is None and not ws.in_batch:
         raise ValueError("this NPairWorkspace was allocated for the cross-batch memory's chain only (in_batch=False)")
+    if logq is not None:
+        if isinstance(logq, torch.Tensor):
+            if memory is not None:
+                raise ValueError("a per-row logQ tensor has no memory part: give a LogQTable / LogQEstimator with a memory")
+            if logq.numel() < 2 * B:
+                raise ValueError("a per-row logQ tensor needs 2B = %d entries, got %d" % (2 * B, logq.numel()))
+        elif rows is None:
+            raise ValueError("the logQ correction needs the rows' video ids")
+        if memory is None:
+            return _npair_logq_loss(e, rows, B, Dp, temperature, symmetric, precision, de, stats, ws, logq, step, step_dev)
     if memory is not None:
-        return _npair_memory_loss(e, rows, B, Dp, temperature, symmetric, precision, de, stats, ws, memory, step, step_dev)
+        return _npair_memory_loss(e, rows, B, Dp, temperature, symmetric, precision, de, stats, ws, memory, step, step_dev,
+                                  logq)
     A, P = e[0::2, :Dp], e[1::2, :Dp]
     lse = ws.lse
     if precision == "f32x3":
@@ -559,7 +728,49 @@ def npair_loss(e, rows, B, Dp, temperature=0.1, symmetric=True, precision="f32x3
     return stats, lse
 
 
-def _npair_memory_loss(e, rows, B, Dp, temperature, symmetric, precision, de, stats, ws, mem, step, step_dev):
+def _npair_logq_loss(e, rows, B, Dp, temperature, symmetric, precision, de, stats, ws, logq, step, step_dev):
+    """npair_loss's in-batch chain with the logQ correction (the gather, the BIAS passes, the estimator's update)."""
+    Bp = ws.Bp
+    A, P = e[0::2, :Dp], e[1::2, :Dp]
+    lse, bias = ws.lse, ws.bias
+    if isinstance(logq, torch.Tensor):
+        bias[:2 * B].copy_(logq.reshape(-1)[:2 * B])
+        logq = None
+    else:
+        logq.gather(rows, B, None, bias, None)
+    if precision == "f32x3":
+        Dq = ws.Dq
+        split_f32_bf16x3(A, ws.A3, Dq)
+        split_f32_bf16x3(P, ws.P3, Dq)
+        split_f32_bf16x3(P, ws.PT3, Bp, transpose=True)
+        gemm_bf16x3_nt(BE_F32, ws.A3, Dq, ws.P3, Dq, ws.S, Bp, Bp, Dq, workspace=ws.gemm_ws)
+    else:
+        fc_bwd_data(A, P, None, ws.S, Bp, Bp, Dp)
+    npair_logq_stats(ws.S, rows, B, bias, temperature, symmetric, lse, stats, ws.ws)
+    if de is None:
+        return stats, lse
+    dA, dP = de[0::2], de[1::2]
+    if precision == "f32x3":
+        npair_logq_grad_x3(ws.S, rows, B, bias, temperature, symmetric, lse, ws.W3, Bp)
+        if logq is not None:
+            logq.update(rows, B, step, step_dev)
+        oA = dA if ws.dA is None else ws.dA
+        oP = dP if ws.dP is None else ws.dP
+        gemm_bf16x3_nt(BE_F32, ws.W3, Bp, ws.PT3, Bp, oA, Bp, Dq, Bp, workspace=ws.gemm_ws)
+        gemm_bf16x3_tn(ws.W3, Bp, ws.A3, Dq, oP, Bp, Dq, Bp, workspace=ws.gemm_ws)
+        if ws.dA is not None:
+            dA.copy_(ws.dA[:, :Dp])
+            dP.copy_(ws.dP[:, :Dp])
+    else:
+        npair_logq_grad_f32(ws.S, rows, B, bias, temperature, symmetric, lse, ws.Wf)
+        if logq is not None:
+            logq.update(rows, B, step, step_dev)
+        fc_lrelu_fwd(ws.Wf, P, ws.zero_bias, dA, Bp, Bp, Dp, alpha=1.0)
+        fc_bwd_weight(ws.Wf, A, dP, None, ws.bw, Bp, Bp, Dp)
+    return stats, lse
+
+
+def _npair_memory_loss(e, rows, B, Dp, temperature, symmetric, precision, de, stats, ws, mem, step, step_dev, logq=None):
     Bp, M, K = ws.Bp, mem.M, mem.K
     if (mem.Bp, mem.Dp, mem.precision) != (Bp, Dp, precision):
         raise ValueError("NPairMemory is for %d pairs x %d columns on %s" % (mem.Bp, mem.Dp, mem.precision))
@@ -576,13 +787,22 @@ def _npair_memory_loss(e, rows, B, Dp, temperature, symmetric, precision, de, st
     else:
         mem.PM[:Bp].copy_(P)
         fc_bwd_data(A, mem.PM, None, mem.S, Bp, K, Dp)
-    npair_memory_stats(mem.S, rows, B, Bp, mem.ids, temperature, symmetric, lse, stats, ws.ws)
+    if logq is None:
+        npair_memory_stats(mem.S, rows, B, Bp, mem.ids, temperature, symmetric, lse, stats, ws.ws)
+    else:                                                       # (the gather reads the ring's ids before this step's push)
+        logq.gather(rows, B, mem.ids, ws.bias, mem.bias)
+        npair_memory_logq_stats(mem.S, rows, B, ws.bias, Bp, mem.ids, mem.bias, temperature, symmetric, lse, stats, ws.ws)
     if de is None:
         return stats, lse
     dA, dP = de[0::2], de[1::2]
     if precision == "f32x3":
-        npair_grad_x3(mem.S, rows, B, temperature, symmetric, lse, mem.W3, K)
-        npair_memory_grad_x3(mem.S, rows, B, Bp, mem.ids, temperature, symmetric, lse, mem.W3, K)
+        if logq is None:
+            npair_grad_x3(mem.S, rows, B, temperature, symmetric, lse, mem.W3, K)
+            npair_memory_grad_x3(mem.S, rows, B, Bp, mem.ids, temperature, symmetric, lse, mem.W3, K)
+        else:
+            npair_logq_grad_x3(mem.S, rows, B, ws.bias, temperature, symmetric, lse, mem.W3, K)
+            npair_memory_logq_grad_x3(mem.S, rows, B, Bp, mem.ids, mem.bias, temperature, symmetric, lse, mem.W3, K)
+            logq.update(rows, B, step, step_dev)
         oA = dA if ws.dA is None else ws.dA
         oP = dP if ws.dP is None else ws.dP
         gemm_bf16x3_nt(BE_F32, mem.W3, K, mem.PMT3, K, oA, Bp, Dq, K, workspace=mem.gemm_ws)      # dA = W . [P; Mem]
@@ -593,8 +813,13 @@ def _npair_memory_loss(e, rows, B, Dp, temperature, symmetric, precision, de, st
         npair_memory_push(P, rows, Bp, Dp, step, step_dev, mem.start, mem.rows, mem.ids, R3=mem.PM3[Bp:], plane_r=Dq,
                           T3=mem.PMT3[:, Bp:], plane_t=K)
     else:
-        npair_grad_f32(mem.S, rows, B, temperature, symmetric, lse, mem.Wf)
-        npair_memory_grad_f32(mem.S, rows, B, Bp, mem.ids, temperature, symmetric, lse, mem.Wf)
+        if logq is None:
+            npair_grad_f32(mem.S, rows, B, temperature, symmetric, lse, mem.Wf)
+            npair_memory_grad_f32(mem.S, rows, B, Bp, mem.ids, temperature, symmetric, lse, mem.Wf)
+        else:
+            npair_logq_grad_f32(mem.S, rows, B, ws.bias, temperature, symmetric, lse, mem.Wf)
+            npair_memory_logq_grad_f32(mem.S, rows, B, Bp, mem.ids, mem.bias, temperature, symmetric, lse, mem.Wf)
+            logq.update(rows, B, step, step_dev)
         fc_lrelu_fwd(mem.Wf, mem.PM, ws.zero_bias, dA, Bp, K, Dp, alpha=1.0)          # dA = W . [P; Mem]
         fc_bwd_weight(mem.Wf[:, :Bp], A, dP, None, ws.bw, Bp, Bp, Dp)                 # dP = W^T . A
         npair_memory_push(P, rows, Bp, Dp, step, step_dev, mem.start, mem.rows, mem.ids)

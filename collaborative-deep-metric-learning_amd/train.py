@@ -47,7 +47,8 @@ class TrainStep:
                  exchange=None, grad_sync=None, slot0=0, batch_global=None, use_graph=False,
                  prefetch=True, precision="auto", train_table=False, gather_ahead="auto",
                  clip_gradient_norm=0.0, regularization_penalty=0.0, l2_penalty=1e-8,
-                 grad_sync_mode="bucketed", temperature=0.1, symmetric=True, memory_size=0, memory_start=0):
+                 grad_sync_mode="bucketed", temperature=0.1, symmetric=True, memory_size=0, memory_start=0,
+                 logq=None, logq_alpha=0.01, logq_init_gap=None):
         """table: FeatureTable (whole catalogue, or this rank's shard when
         ``exchange`` is given); pairs: int32 [P,2] device tensor; ``exchange`` /
         ``grad_sync``: the multi-GPU hooks of cdml_amd.dist (None on one GPU).
@@ -94,7 +95,14 @@ class TrainStep:
         al. 2020; ops.NPairMemory) -- extra softmax columns of every anchor's row term, without a gradient.  Step t
         computes its loss against the ring as it stood before step t and then pushes its B positives (steps before
         ``memory_start`` push nothing).  A multiple of the batch and of the precision's tile (256 pairs on f32x3, 64 on f32);
-        the ring is part of ``state_dict``."""
+        the ring is part of ``state_dict``.
+        ``logq`` (mode "npair"; None = none): the sampling-bias correction of Yi et al. 2019 -- every softmax logit less
+        the log probability lq that its candidate is drawn into a batch, so that popular videos are not over-penalised as
+        negatives.  "stream": the streaming estimator (ops.LogQEstimator: step t's loss uses the estimate from before
+        step t, then the batch's positives update it; ``logq_alpha`` in (0, 1], default 0.01, and ``logq_init_gap`` >= 1,
+        default max(1, n_videos / batch), both build-defined; its state is part of ``state_dict``); or a float tensor of
+        one finite lq per catalogue row (ops.LogQTable: an argument, not checkpoint state).  ``sampling_logq()`` returns
+        the current per-video lq."""
         if mode not in _MODES:
             raise ValueError("mode must be 'uniform', 'inbatch', 'semihard' or 'npair'")
         memory_size, memory_start = int(memory_size), int(memory_start)
@@ -102,6 +110,24 @@ class TrainStep:
             raise ValueError("memory_size > 0 goes with mode 'npair' (the cross-batch memory of its softmax), not %r" % (mode,))
         if memory_size < 0 or memory_start < 0:
             raise ValueError("memory_size and memory_start must be >= 0, got %d and %d" % (memory_size, memory_start))
+        logq_stream = isinstance(logq, str)
+        if logq is not None:
+            if mode != "npair":
+                raise ValueError("logq goes with mode 'npair' (the sampling-bias correction of its softmax), not %r" % (mode,))
+            if logq_stream and logq != "stream":
+                raise ValueError("logq must be None, 'stream' or a tensor of one log-probability per video, not %r" % (logq,))
+            logq_alpha = float(logq_alpha)
+            if not 0.0 < logq_alpha <= 1.0:
+                raise ValueError("logq_alpha must be in (0, 1], got %r" % (logq_alpha,))
+            if logq_init_gap is not None and not 1.0 <= float(logq_init_gap) < float("inf"):
+                raise ValueError("logq_init_gap must be finite and >= 1, got %r" % (logq_init_gap,))
+            if not logq_stream:
+                logq = torch.as_tensor(logq)
+                if logq.dim() != 1 or logq.numel() != table.n_rows_global:
+                    raise ValueError("a logq table needs one entry per catalogue row (%d), got shape %s"
+                                     % (table.n_rows_global, tuple(logq.shape)))
+                if not logq.is_floating_point() or not bool(torch.isfinite(logq).all()):
+                    raise ValueError("every entry of the logq table must be a finite float")
         if mode == "npair":
             if exchange is not None or grad_sync is not None:
                 raise ValueError("mode 'npair' runs on one GPU: data parallelism (exchange / grad_sync) is not supported")
@@ -245,6 +271,10 @@ class TrainStep:
             self.npair_ws = ops.NPairWorkspace(self.B, self.layout.Dp, precision, dev, in_batch=not memory_size)
             if memory_size:
                 self.npair_memory = ops.NPairMemory(memory_size, self.B, self.layout.Dp, precision, dev, start=memory_start)
+        self.npair_logq = None                               # the sampling-bias correction's source (ops.LogQ*)
+        if logq is not None:
+            self.npair_logq = (ops.LogQEstimator(table.n_rows_global, self.B, logq_alpha, logq_init_gap, dev) if logq_stream
+                               else ops.LogQTable(logq, dev))
         self.step_dev = torch.zeros(1, dtype=torch.int64, device=dev)
         self.lr_dev = torch.full((1,), self.base_lr, dtype=f32, device=dev)
         self._lr_host = self.base_lr
@@ -519,8 +549,10 @@ class TrainStep:
         if self.mode == "npair":
             # S = A P^T -> row / column log-sum-exp -> W -> dA = W P, dP = W^T A into de; tower_backward takes de from there
             # (cross-batch memory: the step number for the ring push is the device counter, which replays follow)
+            # (logQ correction: the estimator's update takes the same device step number)
             ops.npair_loss(self.ws.e, self.idx, self.B, L.Dp, self.temperature, self.symmetric, self.precision, de=de,
-                           stats=self.stats, ws=self.npair_ws, memory=self.npair_memory, step=0, step_dev=self.step_dev)
+                           stats=self.stats, ws=self.npair_ws, memory=self.npair_memory, step=0, step_dev=self.step_dev,
+                           logq=self.npair_logq)
         elif self.mode == "uniform":
             ops.triplet_hinge(self.ws.e, self.B, L.Dp, self.margin, self.pos, self.neg, self.hinge,
                               self.stats, de)
@@ -917,6 +949,12 @@ class TrainStep:
             self.check_inputs()
         return v
 
+    def sampling_logq(self):
+        """The per-video log sampling probability lq the logQ correction uses now (fp32 [n_videos] device tensor)."""
+        if self.npair_logq is None:
+            raise ValueError("this step has no logQ correction (TrainStep(mode='npair', logq=...))")
+        return self.npair_logq.logq()
+
     # ------------------------------------------------------------ checkpoint --
     def state_dict(self):
         """Weights under their slim variable names (fully_connected{,_1}/{weights,
@@ -935,6 +973,8 @@ class TrainStep:
             state["plane_scales"] = dict(sc.state(), calibrated=sc.calibrated, changes=sc.changes, last=dict(sc.last))
         if self.npair_memory is not None:                # the ring as fp32 rows + ids (the planes are re-derived on load)
             state["npair_memory"] = self.npair_memory.state_dict()
+        if isinstance(self.npair_logq, ops.LogQEstimator):   # (a fixed logQ table is an argument, not state)
+            state["npair_logq"] = self.npair_logq.state_dict()
         return state
 
     def load_state_dict(self, state):
@@ -973,6 +1013,12 @@ class TrainStep:
                 self.npair_memory.clear()
             else:
                 self.npair_memory.load(ring["rows"], ring["ids"])
+        if isinstance(self.npair_logq, ops.LogQEstimator):   # (a checkpoint without an estimator: a fresh one)
+            est = state.get("npair_logq")
+            if est is None:
+                self.npair_logq.reset()
+            else:
+                self.npair_logq.load(est)
         self.global_step = int(state["global_step"])
         self.step_dev.fill_(self.global_step)
         self.seed = int(state["seed"])

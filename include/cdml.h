@@ -361,6 +361,52 @@ int cdml_npair_memory_push(const float *P, int64_t ldp, const int32_t *ids, int 
                            uint16_t *R3, int64_t ldr, int64_t plane_r, uint16_t *T3, int64_t ldt, int64_t plane_t,
                            cdml_stream_t stream);
 
+/* ---- sampling-bias (logQ) correction of the N-pair loss (Yi et al., RecSys 2019; build-defined) ------------------
+ * lq(v) = the log probability that video v is drawn into a batch.  Every logit that enters a log-sum-exp or the diagonal
+ * loses its candidate's lq: the row term's column j S_ij / t - lq(p_j), memory slot k S_ik / t - lq(mem_id[k]), the column
+ * term's row i S_ij / t - lq(a_i).  The masks are unchanged.  bias float[2B] holds it per slot as ids does (bias[2i] =
+ * lq(a_i), bias[2i + 1] = lq(p_i); 16-B aligned), mem_bias float[M] per memory slot (16-B aligned).
+ * cdml_npair_logq_stats / cdml_npair_memory_logq_stats: cdml_npair_stats / cdml_npair_memory_stats over those logits;
+ *   stats[0] = mean_i (lse_i - (S_ii / t - lq(p_i))) (and the column term's with lq(a_j)); stats[1..3] as before.
+ * cdml_npair_logq_grad_x3 / _f32: W_ij = (c_ij exp(S_ij / t - lq(p_j) - lse_i) - [i == j]) / (B t) (+ the column term's
+ *   with lq(a_i), halved); cdml_npair_memory_logq_grad_x3 / _f32: the memory block with mem_bias.  Layouts and checks as
+ *   the uncorrected entry points, plus a null or misaligned bias / mem_bias.
+ * cdml_logq_table_gather: bias / mem_bias <- table[v] of the slots' ids (ids[2B], mem_id[M]; M = 0: no memory).
+ * cdml_logq_stream_gather: bias / mem_bias <- -log(gap[v]) of the streaming estimator (last int32[n_videos], -1 = unseen;
+ *   gap float[n_videos]), and snap_last / snap_gap [B] <- (last, gap) of the B positives ids[2r + 1].
+ *   Both gathers write 0 for an empty slot (-1) and for an id outside [0, n_videos); they read no entry there.
+ * cdml_logq_stream_update: at step t = step + (step_dev ? *step_dev : 0) (the sampler's convention), every positive
+ *   v = ids[2r + 1] in [0, n_videos) gets gap[v] = (1 - alpha) snap_gap[r] + alpha (t - snap_last[r]) when snap_last[r] >= 0
+ *   (fp32, each product and sum rounded on its own), else snap_gap[r]; last[v] = t.  Positives of one video write the
+ *   same values.  Enqueue after every launch that reads the bias of this step.
+ * cdml_logq_stream_reset: last = -1, gap = g0 (g0 finite, >= 1) over n_videos entries.
+ * Enqueue-only, no atomics.  Bad arguments (null pointers, n_videos outside [1, 2^31 - 1], B < 1, M < 0, alpha outside
+ * (0, 1], g0 < 1, t <= 0 or not finite, short or misaligned buffers) return CDML_E_BADARG before any HIP call. */
+int cdml_npair_logq_stats(const float *S, int64_t lds, const int32_t *ids, int B, const float *bias, float temperature,
+                          int symmetric, float *lse, float *stats, void *workspace, size_t workspace_bytes,
+                          cdml_stream_t stream);
+int cdml_npair_logq_grad_x3(const float *S, int64_t lds, const int32_t *ids, int B, const float *bias, float temperature,
+                            int symmetric, const float *lse, uint16_t *W, int64_t ldw, int64_t plane, cdml_stream_t stream);
+int cdml_npair_logq_grad_f32(const float *S, int64_t lds, const int32_t *ids, int B, const float *bias, float temperature,
+                             int symmetric, const float *lse, float *W, int64_t ldw, cdml_stream_t stream);
+int cdml_npair_memory_logq_stats(const float *S, int64_t lds, const int32_t *ids, int B, const float *bias, int64_t mem_col,
+                                 const int32_t *mem_id, const float *mem_bias, int M, float temperature, int symmetric,
+                                 float *lse, float *stats, void *workspace, size_t workspace_bytes, cdml_stream_t stream);
+int cdml_npair_memory_logq_grad_x3(const float *S, int64_t lds, const int32_t *ids, int B, int64_t mem_col,
+                                   const int32_t *mem_id, const float *mem_bias, int M, float temperature, int symmetric,
+                                   const float *lse, uint16_t *W, int64_t ldw, int64_t plane, cdml_stream_t stream);
+int cdml_npair_memory_logq_grad_f32(const float *S, int64_t lds, const int32_t *ids, int B, int64_t mem_col,
+                                    const int32_t *mem_id, const float *mem_bias, int M, float temperature, int symmetric,
+                                    const float *lse, float *W, int64_t ldw, cdml_stream_t stream);
+int cdml_logq_table_gather(const float *table, int64_t n_videos, const int32_t *ids, int B, const int32_t *mem_id, int M,
+                           float *bias, float *mem_bias, cdml_stream_t stream);
+int cdml_logq_stream_gather(const int32_t *last, const float *gap, int64_t n_videos, const int32_t *ids, int B,
+                            const int32_t *mem_id, int M, float *bias, float *mem_bias, int32_t *snap_last, float *snap_gap,
+                            cdml_stream_t stream);
+int cdml_logq_stream_update(int32_t *last, float *gap, int64_t n_videos, const int32_t *ids, int B, const int32_t *snap_last,
+                            const float *snap_gap, float alpha, uint64_t step, const uint64_t *step_dev, cdml_stream_t stream);
+int cdml_logq_stream_reset(int32_t *last, float *gap, int64_t n_videos, float g0, cdml_stream_t stream);
+
 /* ---- evaluation metric: Evaluation.mean_dist / mean_cos_dist (evaluate.py:57-90)
  * e[n_rows][lde] embeddings; pairs int32[P][2] row indices (must be < n_rows).
  * sqdist[P] = sum (a-b)^2, dot[P] = sum a*b; means float[4] (may be NULL):
