@@ -654,7 +654,15 @@ int cdml_x3_slab_steps(int steps);
  * output row; 9 = 6 that ALSO writes the sign bitmask of its result to aux (as uint8 [M][ldaux BYTES], bit j of byte b of
  * row r = C[r][8 b + j] > 0); 10 = 7 reading that bitmask (leaky-relu' of the hidden layer, models.py:59 / train.py:141,
  * as one bit per element instead of a 2-byte value).  The narrow forward layer (N == 256) splits its contraction into
- * slabs of 60 K-tile steps when given the workspace -- a partition that depends on K alone. */
+ * slabs of 60 K-tile steps when given the workspace -- a partition that depends on K alone.
+ * 12 = 10 (7 without a mask when aux is NULL) with the result's planes k8-INTERLEAVED: C = bf16 [3 planes][M / 8][ldc][8 rows],
+ * element (plane p, row r, column c) at p * plane_c + ((r / 8) * ldc + c) * 8 + r % 8 (what cdml_interleave8_bf16x3 makes of
+ * the row-major planes).  It stores whole 8-row groups, so M must be a multiple of 8 -- of 8 only: a last row tile or half
+ * tile that is partly filled is fine -- and CDML_E_ALIGN otherwise; ldc = the columns per row group, a multiple of 8, >= N
+ * (columns N .. ldc - 1 of a group are not written); plane_c >= M * ldc elements; bf16 planes only (the step uses it, and it
+ * is tested, with six products).
+ * Every epilogue writes rows < M and columns < N of each plane only: plane gaps, the ldc - N tail of a row and, for the
+ * bitmask, bytes >= N / 8 of a row are left as they were. */
 size_t cdml_gemm_bf16x3_workspace(int tn, int M, int N, int K, int products);
 /* The weight gradients (train.py:141) on k8-INTERLEAVED operands, round 5: an operand whose contraction runs over the batch
  * rows stored as bf16 [3 planes][rows / 8][columns][8 rows], so that a fragment of the k-strided product is one aligned

@@ -4,9 +4,15 @@ precision; the reference computes in fp32).  Kernel-level checks are exact-ish
 end-to-end tolerance this path claims is 5e-3 absolute on unit-norm embeddings
 and 2e-2 on the loss against the fp64 oracle run on the same fp16-rounded
 features and fp32 master weights."""
+import os
+import sys
+
 import numpy as np
 import pytest
 import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import footprint as fp  # noqa: E402
 
 from oracle import sampler as osampler, synth as osynth, tower as otower
 
@@ -52,25 +58,25 @@ def test_gemm_bf16_epilogues(cd, M, N, K, tile, mfma, monkeypatch):
     dbias = torch.as_tensor(bias, dtype=torch.float32).to(cd.dev)
     lrelu = lambda v: np.maximum(v, 0.2 * v)
     tol = dict(atol=2e-5 * np.sqrt(K / 64), rtol=0)
-    out = torch.empty((M, N), dtype=torch.float32, device=cd.dev)
+    out = fp.poisoned((M, N), dtype=torch.float32, device=cd.dev)
     cd.ops.gemm_bf16_nt(cd.ops.BE_BIAS_LRELU_F32, dA, dB, out, M, N, K, bias=dbias)
     want = lrelu(ref + bias.astype(np.float32))
     np.testing.assert_allclose(out.cpu().numpy(), want, **tol)
-    outb = torch.empty((M, N), dtype=torch.bfloat16, device=cd.dev)
+    outb = fp.poisoned((M, N), dtype=torch.bfloat16, device=cd.dev)
     cd.ops.gemm_bf16_nt(cd.ops.BE_BIAS_LRELU_BF16, dA, dB, outb, M, N, K, bias=dbias)
     np.testing.assert_allclose(outb.float().cpu().numpy(), want, rtol=2 ** -8, atol=1e-4)
     daux = dbf(aux, cd.dev)
     cd.ops.gemm_bf16_nt(cd.ops.BE_MASK_BF16, dA, dB, outb, M, N, K, aux=daux)
     want_m = ref * np.where(bf(aux) > 0, 1.0, 0.2)
     np.testing.assert_allclose(outb.float().cpu().numpy(), want_m, rtol=2 ** -8, atol=1e-4)
-    ws = torch.empty(max(cd.ops.gemm_bf16_workspace(M, N, K), 16) // 4, device=cd.dev)
+    ws = fp.poisoned(max(cd.ops.gemm_bf16_workspace(M, N, K), 16) // 4, device=cd.dev)
     cd.ops.gemm_bf16_nt(cd.ops.BE_F32, dA, dB, out, M, N, K, workspace=ws)
     np.testing.assert_allclose(out.cpu().numpy(), ref, **tol)
     # epilogue 1 with a workspace: split-K + combine(bias, lrelu) where the layer is narrow
-    out1 = torch.empty_like(out)
+    out1 = fp.poisoned_like(out)
     cd.ops.gemm_bf16_nt(cd.ops.BE_BIAS_LRELU_F32, dA, dB, out1, M, N, K, bias=dbias, workspace=ws)
     np.testing.assert_allclose(out1.cpu().numpy(), want, **tol)
-    out2 = torch.empty_like(out)
+    out2 = fp.poisoned_like(out)
     cd.ops.gemm_bf16_nt(cd.ops.BE_F32, dA, dB, out2, M, N, K, workspace=ws)
     assert torch.equal(out, out2)                                  # deterministic split-K
 
@@ -88,11 +94,11 @@ def test_gemm_bf16_tn_weight_gradient_form(cd, M, N, K, mfma, monkeypatch):
     ref = bf(A).T @ bf(B)
     dA, dB = dbf(A, cd.dev), dbf(B, cd.dev)
     assert cd.ops.gemm_bf16_tn_supported(M, N, K, M, N)
-    ws = torch.empty(max(cd.ops.gemm_bf16_tn_workspace(M, N, K), 16) // 4, device=cd.dev)
-    out = torch.empty((M, N), dtype=torch.float32, device=cd.dev)
+    ws = fp.poisoned(max(cd.ops.gemm_bf16_tn_workspace(M, N, K), 16) // 4, device=cd.dev)
+    out = fp.poisoned((M, N), dtype=torch.float32, device=cd.dev)
     cd.ops.gemm_bf16_tn(dA, dB, out, M, N, K, workspace=ws)
     np.testing.assert_allclose(out.cpu().numpy(), ref, atol=1e-4 * np.sqrt(K / 64), rtol=0)
-    out2 = torch.empty_like(out)
+    out2 = fp.poisoned_like(out)
     cs = torch.full((N,), 7.0, dtype=torch.float32, device=cd.dev)
     cd.ops.gemm_bf16_tn(dA, dB, out2, M, N, K, workspace=ws, colsum=cs)      # + bias gradient
     assert torch.equal(out, out2)
@@ -124,7 +130,7 @@ def test_gemm_bf16_tn2_joint_weight_gradients(cd, M1, N1, M2, N2, K, mfma, monke
     B2 = rnd(K, N2 + 8, 1.0).bfloat16()
     nbytes = ops.gemm_bf16_tn2_workspace(M1, N1, M2, N2, K)
     assert nbytes > 0 and ops.gemm_bf16_tn2_workspace(M1 + 8, N1, M2, N2, K) == 0
-    ws = torch.empty(nbytes // 4, device=cd.dev)
+    ws = fp.poisoned(nbytes // 4, device=cd.dev)
     C1 = torch.full((M1, N1 + 4), 5.0, device=cd.dev)
     C2 = torch.full((M2, N2), 5.0, device=cd.dev)
     d1, d2 = torch.full((N1,), 5.0, device=cd.dev), torch.full((N2,), 5.0, device=cd.dev)
@@ -139,13 +145,13 @@ def test_gemm_bf16_tn2_joint_weight_gradients(cd, M1, N1, M2, N2, K, mfma, monke
     assert float((d1.double() - B1.double().sum(0)).abs().max()) <= 2e-4 * K ** 0.5
     assert float((d2.double() - B2[:, :N2].double().sum(0)).abs().max()) <= 2e-4 * K ** 0.5
     # the one-product entry point: same products, other split of K
-    ws1 = torch.empty(max(ops.gemm_bf16_tn_workspace(M1, N1, K), ops.gemm_bf16_tn_workspace(M2, N2, K), 16) // 4, device=cd.dev)
-    S1, S2 = torch.empty((M1, N1), device=cd.dev), torch.empty((M2, N2), device=cd.dev)
+    ws1 = fp.poisoned(max(ops.gemm_bf16_tn_workspace(M1, N1, K), ops.gemm_bf16_tn_workspace(M2, N2, K), 16) // 4, device=cd.dev)
+    S1, S2 = fp.poisoned((M1, N1), device=cd.dev), fp.poisoned((M2, N2), device=cd.dev)
     ops.gemm_bf16_tn(A1[:, :M1], B1, S1, M1, N1, K, workspace=ws1)
     ops.gemm_bf16_tn(A2, B2[:, :N2], S2, M2, N2, K, workspace=ws1)
     assert float((C1[:, :N1] - S1).abs().max()) <= tol and float((C2 - S2).abs().max()) <= tol
     for _ in range(3):                                                   # bit-identical repetition, no bias gradients asked
-        E1, E2 = torch.empty_like(C1), torch.empty_like(C2)
+        E1, E2 = fp.poisoned_like(C1), fp.poisoned_like(C2)
         run(E1, E2, None, None)
         assert torch.equal(E1[:, :N1], C1[:, :N1]) and torch.equal(E2, C2)
 
@@ -167,15 +173,16 @@ def test_gemm_bf16_k256_streaming_data_gradient(cd, M, N, monkeypatch):
     err = (out.double() - ref).abs().max().item()
     assert err <= 2 ** -8 * ref.abs().max().item() + 1e-4, err
     monkeypatch.setenv("CDML_BF16_TILE", "256" if N % 256 == 0 and M >= 256 else "128")
-    tiled = torch.empty_like(out)
+    tiled = fp.poisoned_like(out)
     cd.ops.gemm_bf16_nt(cd.ops.BE_MASK_BF16, A, B, tiled, M, N, K, aux=aux)
     monkeypatch.delenv("CDML_BF16_TILE")
     assert torch.equal(out, tiled)
-    for _ in range(20):                                              # same buffers, every launch bit-equal
-        again = torch.empty_like(out)
+    again = fp.poisoned_like(out)
+    for it in range(20):                                             # same buffers, every launch bit-equal
+        fp.poison_(again, it)                                        # (re-poisoned: a block the allocator recycles holds no answer)
         cd.ops.gemm_bf16_nt(cd.ops.BE_MASK_BF16, A, B, again, M, N, K, aux=aux)
         assert torch.equal(out, again)
-    plain = torch.empty_like(out)                                    # no mask: plain bf16 product
+    plain = fp.poisoned_like(out)                                    # no mask: plain bf16 product
     cd.ops.gemm_bf16_nt(cd.ops.BE_MASK_BF16, A, B, plain, M, N, K)
     ref_p = A.double() @ B.double().T
     assert (plain.double() - ref_p).abs().max().item() <= 2 ** -8 * ref_p.abs().max().item() + 1e-4
@@ -202,8 +209,8 @@ def test_adam_matrix_bf16_equals_adam_then_copies(cd, K, N):
     step = torch.tensor([6], dtype=torch.int64, device=cd.dev)              # t = 1 + 6
     w0, m0, v0 = W.clone(), M.clone(), V.clone()
     cd.ops.adam_step(w0, G, m0, v0, 0.0, 1, lr_dev=lr, t_dev=step)
-    wt0 = torch.empty((N, K), dtype=torch.bfloat16, device=cd.dev)
-    wc0 = torch.empty((K, N), dtype=torch.bfloat16, device=cd.dev)
+    wt0 = fp.poisoned((N, K), dtype=torch.bfloat16, device=cd.dev)
+    wc0 = fp.poisoned((K, N), dtype=torch.bfloat16, device=cd.dev)
     cd.ops.transpose_to_bf16(w0, wt0, K, N)
     cd.ops.cast_f32_bf16(w0, wc0, K, N)
     w1, m1, v1 = W.clone(), M.clone(), V.clone()
@@ -252,8 +259,8 @@ def test_bitmask_epilogues_equal_value_mask(cd, M):
     A = (torch.randn(M, K1, device=cd.dev, generator=g_) / K1 ** 0.5).bfloat16()
     B = torch.randn(N, K1, device=cd.dev, generator=g_).bfloat16()
     bias = torch.randn(N, device=cd.dev, generator=g_) * 0.1
-    h0 = torch.empty((M, N), dtype=torch.bfloat16, device=cd.dev)
-    h1 = torch.empty_like(h0)
+    h0 = fp.poisoned((M, N), dtype=torch.bfloat16, device=cd.dev)
+    h1 = fp.poisoned_like(h0)
     bits = torch.full((M + 2, N // 8 + 16), 0xAA, dtype=torch.uint8, device=cd.dev)
     ops.gemm_bf16_nt(ops.BE_BIAS_LRELU_BF16, A, B, h0, M, N, K1, bias=bias)
     ops.gemm_bf16_nt(ops.BE_BIAS_LRELU_BF16_BITS, A, B, h1, M, N, K1, bias=bias, aux=bits[:M, :N // 8])
@@ -265,7 +272,7 @@ def test_bitmask_epilogues_equal_value_mask(cd, M):
     assert 0.3 < frac < 0.7                                                  # both signs are exercised
     dz2 = (torch.randn(M, K2, device=cd.dev, generator=g_) / 16).bfloat16()
     W2 = torch.randn(N, K2, device=cd.dev, generator=g_).bfloat16()
-    d0 = torch.empty((M, N), dtype=torch.bfloat16, device=cd.dev)
+    d0 = fp.poisoned((M, N), dtype=torch.bfloat16, device=cd.dev)
     d1 = torch.full((M, N), 3.0, dtype=torch.bfloat16, device=cd.dev)
     ops.gemm_bf16_nt(ops.BE_MASK_BF16, dz2, W2, d0, M, N, K2, aux=h0)
     ops.gemm_bf16_nt(ops.BE_MASKBITS_BF16, dz2, W2, d1, M, N, K2, aux=bits[:M, :N // 8])
@@ -287,21 +294,24 @@ def test_gemm_bf16_256_race_screen(cd, monkeypatch):
     A = (torch.randn(M, K, device=cd.dev, generator=g) / 32).bfloat16()
     B = torch.randn(N, K, device=cd.dev, generator=g).bfloat16()
     bias = torch.zeros(N, device=cd.dev)
-    out = torch.empty((M, N), dtype=torch.float32, device=cd.dev)
+    out = fp.poisoned((M, N), dtype=torch.float32, device=cd.dev)
     cd.ops.gemm_bf16_nt(cd.ops.BE_BIAS_LRELU_F32, A, B, out, M, N, K, bias=bias)
     ref = (A.float() @ B.float().T)
     ref = torch.maximum(ref, 0.2 * ref)
     assert (out - ref).abs().max().item() < 2e-3
     first = out.clone()
-    for _ in range(60):
+    for it in range(60):
+        fp.poison_(out, it)                                  # a launch that stores nothing or drops a tile leaves NaNs behind
         cd.ops.gemm_bf16_nt(cd.ops.BE_BIAS_LRELU_F32, A, B, out, M, N, K, bias=bias)
         assert torch.equal(out, first)
     At, Bt = A.t().contiguous(), B.t().contiguous()  # [K][M], [K][N]
-    ws = torch.empty(max(cd.ops.gemm_bf16_tn_workspace(M, N, K), 16) // 4, device=cd.dev)
+    ws = fp.poisoned(max(cd.ops.gemm_bf16_tn_workspace(M, N, K), 16) // 4, device=cd.dev)
     cd.ops.gemm_bf16_tn(At, Bt, out, M, N, K, workspace=ws)
     assert (out - A.float() @ B.float().T).abs().max().item() < 2e-3
     first = out.clone()
-    for _ in range(60):
+    for it in range(60):
+        fp.poison_(out, it)
+        fp.poison_(ws, it)
         cd.ops.gemm_bf16_tn(At, Bt, out, M, N, K, workspace=ws)
         assert torch.equal(out, first)
 
@@ -311,18 +321,18 @@ def test_gemm_bf16_tn_refuses_other_shapes(cd):
     a = torch.zeros((128, 192), dtype=torch.bfloat16, device=cd.dev)
     b = torch.zeros((128, 256), dtype=torch.bfloat16, device=cd.dev)
     with pytest.raises(cd.pkg.CdmlError):
-        cd.ops.gemm_bf16_tn(a, b, torch.empty((192, 256), device=cd.dev), 192, 256, 128)
+        cd.ops.gemm_bf16_tn(a, b, fp.poisoned((192, 256), device=cd.dev), 192, 256, 128)
 
 
 def test_gemm_bf16_identity_asymmetric_and_errors(cd):
     K = N = 128
     Bm = (np.arange(N * K).reshape(N, K) % 251 - 100).astype(np.float64)     # exact in bf16
-    out = torch.empty((K, N), dtype=torch.float32, device=cd.dev)
+    out = fp.poisoned((K, N), dtype=torch.float32, device=cd.dev)
     cd.ops.gemm_bf16_nt(cd.ops.BE_F32, dbf(np.eye(K), cd.dev), dbf(Bm, cd.dev), out, K, N, K)
     np.testing.assert_array_equal(out.cpu().numpy(), Bm.T)                   # C = I . B^T
     with pytest.raises(cd.pkg.CdmlError):
         cd.ops.gemm_bf16_nt(cd.ops.BE_F32, dbf(np.eye(64), cd.dev), dbf(np.eye(64), cd.dev),
-                            torch.empty((64, 64), device=cd.dev), 64, 64, 64)      # N % 128
+                            fp.poisoned((64, 64), device=cd.dev), 64, 64, 64)      # N % 128
 
 
 def test_transpose_cast_colsum(cd):
@@ -339,8 +349,8 @@ def test_transpose_cast_colsum(cd):
     cd.ops.cast_f32_bf16(dx, c, 300, 200)
     np.testing.assert_array_equal(c.float().cpu().numpy(), bf(x))
     for src, ref in ((dx, x.astype(np.float64)), (c, bf(x))):
-        out = torch.empty(200, device=cd.dev)
-        ws = torch.empty(cd.ops.colsum_workspace_floats(300, 200), device=cd.dev)
+        out = fp.poisoned(200, device=cd.dev)
+        ws = fp.poisoned(cd.ops.colsum_workspace_floats(300, 200), device=cd.dev)
         cd.ops.colsum(src, 300, 200, out, ws)
         np.testing.assert_allclose(out.cpu().numpy(), ref.sum(0), atol=1e-4)
 

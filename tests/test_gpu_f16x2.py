@@ -4,9 +4,15 @@ precision "f32x3" was admitted under (tests/test_gpu_f32x3.py): erro
 kernel's on the same operands.  Reference lines: models.py:59-61, train.py:141."""
 import math
 
+import os
+import sys
+
 import numpy as np
 import pytest
 import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import footprint as fp  # noqa: E402
 
 from cdml_amd import engine, engine_f16x2, engine_x3, ops, predict, train
 from oracle import sampler as osampler, synth as osynth, tower as otower
@@ -36,7 +42,7 @@ def _value(p, width, scale):
 
 
 def _ws(tn, M, N, K):
-    return torch.empty(max(ops.gemm_f16x2_workspace(tn, M, N, K), 16) // 4, device=_dev())
+    return fp.poisoned(max(ops.gemm_f16x2_workspace(tn, M, N, K), 16) // 4, device=_dev())
 
 
 def test_split_planes_hold_22_bits_and_saturate():
@@ -81,9 +87,9 @@ def test_error_at_the_five_production_shapes_against_the_fp32_mfma_kernels():
     W1T2, W2T2, W22 = _planes(W1, F, sw1, transpose=True), _planes(W2, H, sw2, transpose=True), _planes(W2, D, sw2)
     # FC1: fp32 output, and the planes + sign bitmask the step uses
     ref = lrelu(x.double() @ W1.double() + b1.double())
-    c32 = torch.empty(R, H, device=dev)
+    c32 = fp.poisoned(R, H, device=dev)
     ops.fc_lrelu_fwd(x, W1, b1, c32, R, F, H, alpha=0.2)
-    c2 = torch.empty(R, H, device=dev)
+    c2 = fp.poisoned(R, H, device=dev)
     ops.gemm_f16x2_nt(ops.BE_BIAS_LRELU_F32, x2, F, W1T2, F, c2, R, H, F, 1.0 / (sx * sw1), bias=b1, alpha=0.2)
     res["FC1"] = (err(c2, ref), err(c32, ref))
     hp = torch.zeros(R, 2 * H, dtype=torch.float16, device=dev)
@@ -96,23 +102,23 @@ def test_error_at_the_five_production_shapes_against_the_fp32_mfma_kernels():
     assert flips.sum().item() <= 4 and (ref.abs()[flips] < 1e-6).all()                  # a sign only where the value is rounding noise
     # FC2 (K-slabs)
     ref = lrelu(h1.double() @ W2.double() + b2.double())
-    c32 = torch.empty(R, D, device=dev)
+    c32 = fp.poisoned(R, D, device=dev)
     ops.fc_lrelu_fwd(h1, W2, b2, c32, R, H, D, alpha=0.2)
-    c2 = torch.empty(R, D, device=dev)
+    c2 = fp.poisoned(R, D, device=dev)
     ops.gemm_f16x2_nt(ops.BE_BIAS_LRELU_F32, h12, H, W2T2, H, c2, R, D, H, 1.0 / (sh * sw2), bias=b2, alpha=0.2, workspace=_ws(False, R, D, H))
     res["FC2"] = (err(c2, ref), err(c32, ref))
     # dH1: the product itself (fp32 output, no mask) under the gate as it stands ...
     ref = dz2.double() @ W2.double().t()
-    c32 = torch.empty(R, H, device=dev)
+    c32 = fp.poisoned(R, H, device=dev)
     ops.fc_bwd_data(dz2, W2, None, c32, R, H, D)
-    c2 = torch.empty(R, H, device=dev)
+    c2 = fp.poisoned(R, H, device=dev)
     ops.gemm_f16x2_nt(ops.BE_F32, dz22, D, W22, D, c2, R, H, D, 1.0 / (sg2 * sw2))
     res["dH1"] = (err(c2, ref), err(c32, ref))
     # ... and as the step runs it: times leaky-relu' of h1 from the bitmask, written as planes.  A pair of fp16 planes holds 22
     # significant bits (2^-23 of a value as its representation error) where fp32 holds 24, and this product's own error
     # is at fp32's rounding floor (K = 256): the bound for the PLANES is the gate + 2^-23
     ref = (dz2.double() @ W2.double().t()) * torch.where(got_bits, 1.0, 0.2).double()
-    c32 = torch.empty(R, H, device=dev)
+    c32 = fp.poisoned(R, H, device=dev)
     ops.fc_bwd_data(dz2, W2, torch.where(got_bits, 1.0, -1.0).float(), c32, R, H, D, alpha=0.2)
     o2 = torch.zeros(R, 2 * H, dtype=torch.float16, device=dev)
     ops.gemm_f16x2_nt(ops.BE_MASKBITS_X3, dz22, D, W22, D, o2, R, H, D, 1.0 / (sg2 * sw2), c_scale=sg1, plane_c=H, aux=bits, alpha=0.2)
@@ -122,10 +128,10 @@ def test_error_at_the_five_production_shapes_against_the_fp32_mfma_kernels():
                                                      ("dW2", h1, h12, H, sh, dz2, dz22, D, sg2, H, D)):
         ref = a.double().t() @ g.double()
         refb = g.double().sum(0)
-        c32, db32 = torch.empty(M, N, device=dev), torch.empty(N, device=dev)
-        ws32 = torch.empty(max(ops.fc_bwd_weight_workspace(R, M, N), 16) // 4, device=dev)
+        c32, db32 = fp.poisoned(M, N, device=dev), fp.poisoned(N, device=dev)
+        ws32 = fp.poisoned(max(ops.fc_bwd_weight_workspace(R, M, N), 16) // 4, device=dev)
         ops.fc_bwd_weight(a, g, c32, db32, ws32, R, M, N)
-        c2, db2 = torch.empty(M, N, device=dev), torch.empty(N, device=dev)
+        c2, db2 = fp.poisoned(M, N, device=dev), fp.poisoned(N, device=dev)
         ops.gemm_f16x2_tn(a2, pa, g2, pg, c2, M, N, R, 1.0 / (sa * sg), workspace=_ws(True, M, N, R), colsum=db2, colsum_scale=1.0 / sg)
         res[name] = (err(c2, ref), err(c32, ref))
         res["db" + name[2]] = (err(db2, refb), err(db32, refb))
@@ -276,20 +282,30 @@ def test_resident_plane_walk_equals_the_general_loop(monkeypatch):
     torch.manual_seed(11)
     dev = _dev()
 
-    def both(fn):
+    def both(fn):                                          # the two forms write into guarded outputs armed with DIFFERENT poisons
         monkeypatch.setenv("CDML_X3_WALK", "general")
-        a = fn()
+        a = fn(0)
         monkeypatch.delenv("CDML_X3_WALK")
-        b = fn()
+        b = fn(1)
+        torch.cuda.synchronize()
+        for g in guards:
+            g.assert_guards_intact()
+        del guards[:]
         return a, b
+
+    guards = []
+
+    def guarded(shape, pat):
+        guards.append(fp.Guarded(shape, torch.float32, dev, pattern=pat))
+        return guards[-1].view
     for (M, N, K) in ((1000, 512, 384), (4096, 1024, 1536), (2048, 256, 5120)):
         A, B = torch.randn(M, K, device=dev), torch.randn(N, K, device=dev) * 0.1
         sa, sb = _scale(A), _scale(B)
         A2, B2 = _planes(A, K, sa), _planes(B, K, sb)
         ws = _ws(False, M, N, K)
 
-        def nt():
-            c = torch.zeros(M, N, device=dev)
+        def nt(pat):
+            c = guarded((M, N), pat)
             ops.gemm_f16x2_nt(ops.BE_F32, A2, K, B2, K, c, M, N, K, 1.0 / (sa * sb), workspace=ws)
             return c
         g, r = both(nt)
@@ -301,8 +317,8 @@ def test_resident_plane_walk_equals_the_general_loop(monkeypatch):
     x2, d2 = _planes(x, F, sx), _planes(dz, H, sd)
     ws = _ws(True, F, H, R)
 
-    def tn():
-        c, db = torch.zeros(F, H, device=dev), torch.zeros(H, device=dev)
+    def tn(pat):
+        c, db = guarded((F, H), pat), guarded((H,), pat)
         ops.gemm_f16x2_tn(x2, F, d2, H, c, F, H, R, 1.0 / (sx * sd), workspace=ws, colsum=db, colsum_scale=1.0 / sd)
         return torch.cat([c.flatten(), db])
     g, r = both(tn)

@@ -1,9 +1,15 @@
 """Split-fp32 GEMMs (precision "f32x3", csrc/gemm_bf16x3.hip): fp32 operands as three bf16 planes, six plane
 products on the bf16 MFMA.  Checked against fp64 at the fp32 kernels' own error level (the reference computes
 these products in fp32: models.py:59-60, train.py:141) and against the fp32 HIP kernels."""
+import os
+import sys
+
 import numpy as np
 import pytest
 import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import footprint as fp  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -26,9 +32,15 @@ def _planes(x, plane):
     return out
 
 
+def _guarded_planes(M, N, pattern, dtype=torch.bfloat16, n=3):
+    """a plane output [M][n x N] in a guarded buffer armed with ``pattern``: (Guarded, its view)"""
+    g = fp.Guarded((M, n * N), dtype, _dev(), pattern=pattern)
+    return g, g.view
+
+
 def _ws(tn, M, N, K, products=6):
     n = ops.gemm_bf16x3_workspace(tn, M, N, K, products)
-    return torch.empty(max(n, 16) // 4, dtype=torch.float32, device=_dev())
+    return fp.poisoned(max(n, 16) // 4, dtype=torch.float32, device=_dev())
 
 
 @pytest.mark.parametrize("rows,cols,transpose", [(64, 128, False), (300, 132, False), (200, 96, True), (1500, 260, True)])
@@ -61,13 +73,13 @@ def test_gemm_x3_nt_matches_fp64_like_fp32(M, N, K, products):
     ref = A.double() @ B.double().t() + bias.double()
     ref = torch.maximum(ref, 0.2 * ref)
     A3, B3 = _planes(A, K), _planes(B, K)
-    C = torch.empty(M, N, device=dev)
+    C = fp.poisoned(M, N, device=dev)
     ops.gemm_bf16x3_nt(ops.BE_BIAS_LRELU_F32, A3, K, B3, K, C, M, N, K, products=products, bias=bias, alpha=0.2,
                        workspace=_ws(False, M, N, K, products))
     scale = ref.abs().max().item()
     err = (C.double() - ref).abs().max().item() / scale
     # the fp32 MFMA kernel on the same operands: err ~ 1e-7 .. 3e-6 at these K; six products stay at that level
-    c32 = torch.empty(M, N, device=dev)
+    c32 = fp.poisoned(M, N, device=dev)
     if K % 32 == 0 and N % 64 == 0:
         ops.fc_lrelu_fwd(A, B.t().contiguous(), bias, c32, M, K, N, alpha=0.2)
         err32 = (c32.double() - ref).abs().max().item() / scale
@@ -112,8 +124,8 @@ def test_gemm_x3_tn_weight_gradient(M, N, K, products):
     X = X / X.norm(dim=1, keepdim=True)
     dY = torch.randn(K, N, device=dev) * 1e-3
     X3, dY3 = _planes(X, M), _planes(dY, N)
-    C = torch.empty(M, N, device=dev)
-    db = torch.empty(N, device=dev)
+    C = fp.poisoned(M, N, device=dev)
+    db = fp.poisoned(N, device=dev)
     ops.gemm_bf16x3_tn(X3, M, dY3, N, C, M, N, K, products=products, workspace=_ws(True, M, N, K, products), colsum=db)
     ref = X.double().t() @ dY.double()
     err = (C.double() - ref).abs().max().item() / ref.abs().max().item()
@@ -247,8 +259,8 @@ def test_gemm_x3_nt_row_bias_planes_and_colsum():
     ref = A.double() @ B.double().t() + bias.double()[:, None]
     ref = torch.maximum(ref, 0.2 * ref)
     assert (got.double() - ref).abs().max().item() <= 3e-6 * ref.abs().max().item()
-    C = torch.empty(M, N, device=dev)
-    cs = torch.empty(N, device=dev)
+    C = fp.poisoned(M, N, device=dev)
+    cs = fp.poisoned(N, device=dev)
     ops.gemm_bf16x3_nt(ops.BE_F32, A3, K, B3, K, C, M, N, K, workspace=_ws(False, M, N, K), colsum=cs)
     ref2 = A.double() @ B.double().t()
     assert (C.double() - ref2).abs().max().item() <= 3e-6 * ref2.abs().max().item()
@@ -263,7 +275,7 @@ def test_gemm_x3_tn_with_bias():
     X = torch.randn(K, M, device=dev) * 0.05
     W = torch.randn(K, N, device=dev) * 0.05
     bias = torch.randn(N, device=dev) * 0.1
-    C = torch.empty(M, N, device=dev)
+    C = fp.poisoned(M, N, device=dev)
     ops.gemm_bf16x3_tn(_planes(X, M), M, _planes(W, N), N, C, M, N, K, workspace=_ws(True, M, N, K), bias=bias, alpha=0.2)
     ref = X.double().t() @ W.double() + bias.double()
     ref = torch.maximum(ref, 0.2 * ref)
@@ -294,21 +306,21 @@ def test_error_at_the_five_production_shapes_against_the_fp32_mfma_kernels():
     W1T3, W2T3, W23 = _planes(W1.t().contiguous(), F), _planes(W2.t().contiguous(), H), _planes(W2, D)
     # FC1
     ref = lrelu(x.double() @ W1.double() + b1.double())
-    c32 = torch.empty(R, H, device=dev)
+    c32 = fp.poisoned(R, H, device=dev)
     ops.fc_lrelu_fwd(x, W1, b1, c32, R, F, H, alpha=0.2)
-    c3 = torch.empty(R, H, device=dev)
+    c3 = fp.poisoned(R, H, device=dev)
     ops.gemm_bf16x3_nt(ops.BE_BIAS_LRELU_F32, x3, F, W1T3, F, c3, R, H, F, bias=b1, alpha=0.2)
     res["FC1"] = (err(c3, ref), err(c32, ref))
     # FC2
     ref = lrelu(h1.double() @ W2.double() + b2.double())
-    c32 = torch.empty(R, D, device=dev)
+    c32 = fp.poisoned(R, D, device=dev)
     ops.fc_lrelu_fwd(h1, W2, b2, c32, R, H, D, alpha=0.2)
-    c3 = torch.empty(R, D, device=dev)
+    c3 = fp.poisoned(R, D, device=dev)
     ops.gemm_bf16x3_nt(ops.BE_BIAS_LRELU_F32, h13, H, W2T3, H, c3, R, D, H, bias=b2, alpha=0.2, workspace=_ws(False, R, D, H))
     res["FC2"] = (err(c3, ref), err(c32, ref))
     # dH1 (times leaky-relu' of h1)
     ref = (dz2.double() @ W2.double().t()) * torch.where(h1 > 0, 1.0, 0.2).double()
-    c32 = torch.empty(R, H, device=dev)
+    c32 = fp.poisoned(R, H, device=dev)
     ops.fc_bwd_data(dz2, W2, h1, c32, R, H, D, alpha=0.2)
     o3 = torch.zeros(R, 3 * H, dtype=torch.bfloat16, device=dev)
     ops.gemm_bf16x3_nt(ops.BE_MASK_X3, dz23, D, W23, D, o3, R, H, D, plane_c=H, aux=h13, alpha=0.2)
@@ -318,10 +330,10 @@ def test_error_at_the_five_production_shapes_against_the_fp32_mfma_kernels():
     for name, a, a3, pa, g, g3, pg, M, N in (("dW1", x, x3, F, dz1, dz13, H, F, H), ("dW2", h1, h13, H, dz2, dz23, D, H, D)):
         ref = a.double().t() @ g.double()
         refb = g.double().sum(0)
-        c32, db32 = torch.empty(M, N, device=dev), torch.empty(N, device=dev)
-        ws32 = torch.empty(max(ops.fc_bwd_weight_workspace(R, M, N), 16) // 4, device=dev)
+        c32, db32 = fp.poisoned(M, N, device=dev), fp.poisoned(N, device=dev)
+        ws32 = fp.poisoned(max(ops.fc_bwd_weight_workspace(R, M, N), 16) // 4, device=dev)
         ops.fc_bwd_weight(a, g, c32, db32, ws32, R, M, N)
-        c3, db3 = torch.empty(M, N, device=dev), torch.empty(N, device=dev)
+        c3, db3 = fp.poisoned(M, N, device=dev), fp.poisoned(N, device=dev)
         ops.gemm_bf16x3_tn(a3, pa, g3, pg, c3, M, N, R, workspace=_ws(True, M, N, R), colsum=db3)
         res[name] = (err(c3, ref), err(c32, ref))
         res["db" + name[2]] = (err(db3, refb), err(db32, refb))
@@ -406,9 +418,10 @@ def test_sign_bitmask_epilogues_equal_the_value_mask():
     B = torch.randn(N, K, device=dev) * 0.1
     bias = torch.randn(N, device=dev) * 0.05
     A3, B3 = _planes(A, K), _planes(B, K)
-    o6 = torch.zeros(M, 3 * N, dtype=torch.bfloat16, device=dev)
-    o9 = torch.zeros_like(o6)
-    bits = torch.full((M, N // 8), 0xAA, dtype=torch.uint8, device=dev)
+    g6, o6 = _guarded_planes(M, N, 0)                         # the two forms: guarded outputs under different poisons
+    g9, o9 = _guarded_planes(M, N, 1)
+    gb = fp.Guarded((M, N // 8), torch.uint8, dev, pattern=0)
+    bits = gb.view
     ops.gemm_bf16x3_nt(ops.BE_BIAS_LRELU_X3, A3, K, B3, K, o6, M, N, K, plane_c=N, bias=bias, alpha=0.2)
     ops.gemm_bf16x3_nt(ops.BE_BIAS_LRELU_X3_BITS, A3, K, B3, K, o9, M, N, K, plane_c=N, bias=bias, alpha=0.2, aux=bits)
     assert torch.equal(o6, o9)
@@ -420,8 +433,8 @@ def test_sign_bitmask_epilogues_equal_the_value_mask():
     G = torch.randn(M, 256, device=dev) * 1e-3
     W = torch.randn(N, 256, device=dev) * 0.05
     G3, W3 = _planes(G, 256), _planes(W, 256)
-    d7 = torch.zeros(M, 3 * N, dtype=torch.bfloat16, device=dev)
-    d10 = torch.zeros_like(d7)
+    g7, d7 = _guarded_planes(M, N, 0)
+    g10, d10 = _guarded_planes(M, N, 1)
     ops.gemm_bf16x3_nt(ops.BE_MASK_X3, G3, 256, W3, 256, d7, M, N, 256, plane_c=N, aux=o9, alpha=0.2)
     ops.gemm_bf16x3_nt(ops.BE_MASKBITS_X3, G3, 256, W3, 256, d10, M, N, 256, plane_c=N, aux=bits, alpha=0.2)
     # (the hi plane of a tiny positive fp32 value can round to +0: the bit form takes the sign of the fp32 value itself)
@@ -430,6 +443,8 @@ def test_sign_bitmask_epilogues_equal_the_value_mask():
     v7 = d7[:, :N].float() + d7[:, N:2 * N].float() + d7[:, 2 * N:].float()
     v10 = d10[:, :N].float() + d10[:, N:2 * N].float() + d10[:, 2 * N:].float()
     assert torch.equal(v7[same], v10[same])
+    for g in (g6, g9, gb, g7, g10):
+        g.assert_guards_intact()
 
 
 def test_resident_plane_walk_race_screen():
@@ -444,12 +459,13 @@ def test_resident_plane_walk_race_screen():
         A = torch.randn(M, K, device=dev) / 32
         B = torch.randn(N, K, device=dev)
         A3, B3 = _planes(A, K), _planes(B, K)
-        out = torch.empty(M, N, device=dev)
+        out = fp.poisoned(M, N, device=dev)
         ops.gemm_bf16x3_nt(ops.BE_F32, A3, K, B3, K, out, M, N, K)
         ref = A.double() @ B.double().t()
         assert (out.double() - ref).abs().max().item() <= 5e-6 * ref.abs().max().item()
         first = out.clone()
-        for _ in range(40):
+        for it in range(40):
+            fp.poison_(out, it)                              # a launch that stores nothing or drops a tile leaves NaNs behind
             ops.gemm_bf16x3_nt(ops.BE_F32, A3, K, B3, K, out, M, N, K)
             assert torch.equal(out, first)
     # k-strided form with the bias gradient riding along: 6 x 20 tiles x 2 K-halves (the weight gradient's launch shape)
@@ -457,13 +473,15 @@ def test_resident_plane_walk_race_screen():
     X = torch.randn(K, M, device=dev) / 16
     dY = torch.randn(K, N, device=dev) * 1e-2
     X3, dY3 = _planes(X, M), _planes(dY, N)
-    C, db = torch.empty(M, N, device=dev), torch.empty(N, device=dev)
+    C, db = fp.poisoned(M, N, device=dev), fp.poisoned(N, device=dev)
     ws = _ws(True, M, N, K)
     ops.gemm_bf16x3_tn(X3, M, dY3, N, C, M, N, K, workspace=ws, colsum=db)
     ref = X.double().t() @ dY.double()
     assert (C.double() - ref).abs().max().item() <= 5e-6 * ref.abs().max().item()
     c0, d0 = C.clone(), db.clone()
-    for _ in range(40):
+    for it in range(40):
+        for t in (C, db, ws):                                # output, bias gradient and split-K workspace re-poisoned
+            fp.poison_(t, it)
         ops.gemm_bf16x3_tn(X3, M, dY3, N, C, M, N, K, workspace=ws, colsum=db)
         assert torch.equal(C, c0) and torch.equal(db, d0)
 
@@ -486,16 +504,21 @@ def test_half_tiles_of_the_last_round_are_bit_identical(M, N, K, monkeypatch):
 
     def run(half):
         monkeypatch.setenv("CDML_X3_HALFTILES", "1" if half else "0")
-        o = torch.zeros(M, 3 * N, dtype=torch.bfloat16, device=dev)
-        bits = torch.zeros(M, N // 8, dtype=torch.uint8, device=dev)
+        pat = 1 if half else 0                               # full-tile and half-tile launches under different poisons
+        guards = [fp.Guarded((M, 3 * N), torch.bfloat16, dev, pattern=pat) for _ in range(3)]
+        guards += [fp.Guarded((M, N // 8), torch.uint8, dev, pattern=pat), fp.Guarded((M, N), torch.float32, dev, pattern=pat)]
+        o, bits = guards[0].view, guards[3].view
         ops.gemm_bf16x3_nt(ops.BE_BIAS_LRELU_X3_BITS, A3, K, B3, K, o, M, N, K, plane_c=N, bias=bias, alpha=0.2, aux=bits)
-        d = torch.zeros(M, 3 * N, dtype=torch.bfloat16, device=dev)
+        d = guards[1].view
         ops.gemm_bf16x3_nt(ops.BE_MASKBITS_X3, A3, K, B3, K, d, M, N, K, plane_c=N, aux=bits, alpha=0.2)
-        dv = torch.zeros(M, 3 * N, dtype=torch.bfloat16, device=dev)
+        dv = guards[2].view
         ops.gemm_bf16x3_nt(ops.BE_MASK_X3, A3, K, B3, K, dv, M, N, K, plane_c=N, aux=o, alpha=0.2)
         # round 6: the unsplit fp32-output product too (the trainable table's row gradient dz1 . W1^T)
-        c = torch.zeros(M, N, device=dev)
+        c = guards[4].view
         ops.gemm_bf16x3_nt(ops.BE_F32, A3, K, B3, K, c, M, N, K)
+        torch.cuda.synchronize()
+        for g in guards:
+            g.assert_guards_intact()
         return o, bits, d, dv, c
 
     full = run(False)
@@ -536,16 +559,16 @@ def test_embedding_bits_do_not_depend_on_the_chunk():
     M, K = 512, 2560
     A3 = _planes(torch.randn(M, K, device=dev) * 0.1, K)
     B3 = _planes(torch.randn(256, K, device=dev) * 0.1, K)
-    C = torch.empty((M, 256), device=dev)
+    C = fp.poisoned((M, 256), device=dev)
     bias = torch.zeros(256, device=dev)
     ops.gemm_bf16x3_nt(ops.BE_BIAS_LRELU_F32, A3, K, B3, K, C, M, 256, K, bias=bias, alpha=0.2)           # single pass
     with pytest.raises(_lib.CdmlError, match="slab form needs"):
         ops.gemm_bf16x3_nt(ops.BE_BIAS_LRELU_F32, A3, K, B3, K, C, M, 256, K, bias=bias, alpha=0.2,
-                           workspace=torch.empty(1024, device=dev))
+                           workspace=fp.poisoned(1024, device=dev))
     # round 6: the slab LENGTH follows the row-tile class -- within a class a batch gives the same bits whole or in row
     # blocks; a pin (what the inference workspaces above use) holds ONE length across classes
-    ws = torch.empty(max(ops.gemm_bf16x3_workspace(False, 16640, 256, K, 6), 16) // 4, device=dev)
-    run = lambda A_, M_, **kw: ops.gemm_bf16x3_nt(ops.BE_BIAS_LRELU_F32, A_, K, B3, K, torch.empty((M_, 256), device=dev), M_, 256,
+    ws = fp.poisoned(max(ops.gemm_bf16x3_workspace(False, 16640, 256, K, 6), 16) // 4, device=dev)
+    run = lambda A_, M_, **kw: ops.gemm_bf16x3_nt(ops.BE_BIAS_LRELU_F32, A_, K, B3, K, fp.poisoned((M_, 256), device=dev), M_, 256,
                                                   K, bias=bias, alpha=0.2, workspace=ws, **kw)
     whole = run(A3, M)                                       # 2 row tiles x 2 slabs of 120 <= 64 tiles: the 60-step class
     halves = torch.cat([run(A3[:256], 256), run(A3[256:], 256)])
@@ -569,9 +592,9 @@ def test_split_k_geometry_has_no_empty_split():
     B = torch.randn(K, N, device=dev, generator=g) * 0.1
     A3, B3 = _planes(A, M), _planes(B, N)
     nbytes = ops.gemm_bf16x3_workspace(True, M, N, K, 6)
-    C = torch.empty((M, N), device=dev)
-    cs = torch.empty(N, device=dev)
-    ops.gemm_bf16x3_tn(A3, M, B3, N, C, M, N, K, workspace=torch.empty(max(nbytes, 16) // 4, device=dev), colsum=cs)
+    C = fp.poisoned((M, N), device=dev)
+    cs = fp.poisoned(N, device=dev)
+    ops.gemm_bf16x3_tn(A3, M, B3, N, C, M, N, K, workspace=fp.poisoned(max(nbytes, 16) // 4, device=dev), colsum=cs)
     torch.cuda.synchronize()
     want = (A.double().t() @ B.double())
     assert ((C.double() - want).abs().max() / want.abs().max()).item() < 5e-6
@@ -590,20 +613,22 @@ def test_gemm_x3_tnk_equals_tn(M, N, K, a0, b0):
     A = torch.randn(K, ma, device=dev, generator=g) * 0.05
     B = torch.randn(K, nb, device=dev, generator=g) * 0.02
     A3, B3 = _planes(A, ma), _planes(B, nb)
-    Ai = torch.empty(3 * K * ma, dtype=torch.bfloat16, device=dev)
-    Bi = torch.empty(3 * K * nb, dtype=torch.bfloat16, device=dev)
+    Ai = fp.poisoned(3 * K * ma, dtype=torch.bfloat16, device=dev)
+    Bi = fp.poisoned(3 * K * nb, dtype=torch.bfloat16, device=dev)
     ops.interleave8_bf16x3(A3, ma, K, ma, Ai)
     ops.interleave8_bf16x3(B3, nb, K, nb, Bi)
     # the interleave itself: element (plane p, row r, column c) at ((p * K/8 + r/8) * cols + c) * 8 + r % 8
     v = Ai.view(3, K // 8, ma, 8)
     assert torch.equal(v.permute(0, 1, 3, 2).reshape(3, K, ma)[1], A3[:, ma:2 * ma])
     ws = _ws(True, M, N, K)
-    C1, C2 = torch.empty((M, N), device=dev), torch.full((M, N), float("nan"), device=dev)
-    cs1, cs2 = torch.empty(N, device=dev), torch.full((N,), float("nan"), device=dev)
+    gs = [fp.Guarded((M, N), torch.float32, dev, pattern=p) for p in (0, 1)] + [fp.Guarded((N,), torch.float32, dev, pattern=p) for p in (0, 1)]
+    C1, C2, cs1, cs2 = (g.view for g in gs)                   # the two forms: guarded outputs under different poisons
     ops.gemm_bf16x3_tn(A3[:, a0:], ma, B3[:, b0:], nb, C1, M, N, K, workspace=ws, colsum=cs1)
     ops.gemm_bf16x3_tnk(Ai, ma, a0, Bi, nb, b0, C2, M, N, K, workspace=ws, colsum=cs2)
     torch.cuda.synchronize()
     assert torch.equal(C1, C2) and torch.equal(cs1, cs2)
+    for g in gs:
+        g.assert_guards_intact()
     want = A[:, a0:a0 + M].double().t() @ B[:, b0:b0 + N].double()
     assert ((C2.double() - want).abs().max() / want.abs().max()).item() < 5e-6
 
@@ -622,15 +647,18 @@ def test_data_gradient_epilogue_writes_interleaved_planes(M, N):
     B3 = _planes(torch.randn(N, K, device=dev, generator=g) * 0.1, K)
     bits = torch.randint(0, 256, (M, N // 8), device=dev, generator=g, dtype=torch.uint8)
     for aux in (bits, None):
-        rowmajor = torch.zeros((M, 3 * N), dtype=torch.bfloat16, device=dev)
+        grow, rowmajor = _guarded_planes(M, N, 0)             # the two forms: guarded outputs under different poisons
         ops.gemm_bf16x3_nt(ops.BE_MASKBITS_X3 if aux is not None else ops.BE_MASK_X3, A3, K, B3, K, rowmajor, M, N, K, plane_c=N,
                            aux=aux, alpha=0.2)
-        want = torch.empty(3 * M * N, dtype=torch.bfloat16, device=dev)
+        want = fp.poisoned(3 * M * N, dtype=torch.bfloat16, device=dev)
         ops.interleave8_bf16x3(rowmajor, N, M, N, want)
-        got = torch.full((3 * M * N,), float("nan"), dtype=torch.bfloat16, device=dev)
+        ggot = fp.Guarded((3 * M * N,), torch.bfloat16, dev, pattern=1)
+        got = ggot.view
         ops.gemm_bf16x3_nt(ops.BE_MASKBITS_X3_KI, A3, K, B3, K, got, M, N, K, plane_c=M * N, aux=aux, alpha=0.2, ldc=N)
         torch.cuda.synchronize()
         assert torch.equal(got.view(torch.int16), want.view(torch.int16))
+        grow.assert_guards_intact()
+        ggot.assert_guards_intact()
 
 
 @pytest.mark.parametrize("mode,steps", [(0, 1), (1, 2), (1, 4)])
@@ -659,7 +687,7 @@ def test_sample_gather_writes_the_interleaved_copy(mode, steps):
     torch.cuda.synchronize()
     assert torch.equal(x0.view(torch.int16), x1.view(torch.int16)) and torch.equal(i0, i1) and torch.equal(s0, s1)
     for st in range(steps):
-        want = torch.empty(3 * R * Fp, dtype=torch.bfloat16, device=dev)
+        want = fp.poisoned(3 * R * Fp, dtype=torch.bfloat16, device=dev)
         ops.interleave8_bf16x3(x1[st], Fp, R, Fp, want)
         assert torch.equal(xk[st].view(torch.int16), want.view(torch.int16)), st
 

@@ -8,9 +8,14 @@ their magnitude.
 import json
 import os
 
+import sys
+
 import numpy as np
 import pytest
 import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import footprint as fp  # noqa: E402
 
 from oracle import sampler as osampler, synth as osynth, tower as otower
 
@@ -65,7 +70,7 @@ def test_sampler_uniform_bit_exact(cd, n_rows, batch):
     pairs = rng.randint(0, n_rows, size=(1000, 2))
     pairs = pairs[pairs[:, 0] != pairs[:, 1]].astype(np.int32)
     dp = dt(pairs, cd.dev, torch.int32)
-    out = torch.empty((batch, 3), dtype=torch.int32, device=cd.dev)
+    out = fp.poisoned((batch, 3), dtype=torch.int32, device=cd.dev)
     for step in (0, 1, 5, 2 ** 33 + 9):
         cd.ops.sample_uniform(dp, n_rows, 1234, step, batch, out)
         want = osampler.device_triplets_vec(pairs, n_rows, 1234, step, batch)
@@ -83,7 +88,7 @@ def test_sampler_uniform_bit_exact(cd, n_rows, batch):
 
 def test_sampler_scalar_spec_small(cd):
     pairs = np.array([[0, 1], [1, 2], [2, 0]], dtype=np.int32)
-    out = torch.empty((32, 3), dtype=torch.int32, device=cd.dev)
+    out = fp.poisoned((32, 3), dtype=torch.int32, device=cd.dev)
     cd.ops.sample_uniform(dt(pairs, cd.dev, torch.int32), 3, 5, 2, 32, out)
     np.testing.assert_array_equal(out.cpu().numpy(), osampler.device_triplets(pairs, 3, 5, 2, 32))
 
@@ -92,8 +97,8 @@ def test_sampler_inbatch_bit_exact(cd):
     pairs = osynth.cowatch_pairs(500, 100, 1)
     dp = dt(pairs, cd.dev, torch.int32)
     for B in (2, 16, 4096):
-        rows = torch.empty(2 * B, dtype=torch.int32, device=cd.dev)
-        shift = torch.empty(1, dtype=torch.int32, device=cd.dev)
+        rows = fp.poisoned(2 * B, dtype=torch.int32, device=cd.dev)
+        shift = fp.poisoned(1, dtype=torch.int32, device=cd.dev)
         for step in (0, 3, 2 ** 32 + 1):
             cd.ops.sample_inbatch(dp, 77, step, B, rows, shift)
             wrows, _, _, ws = osampler.device_inbatch(pairs, 77, step, B)
@@ -111,7 +116,7 @@ def test_gather_rows(cd, F):
     didx = dt(idx, cd.dev, torch.int32)
     stride = ru(F, 64)
     out = torch.full((77, stride), 9.0, device=cd.dev)
-    inv = torch.empty(77, device=cd.dev)
+    inv = fp.poisoned(77, device=cd.dev)
     cd.ops.gather_rows(table.data, 0, didx, F, out, normalize=True, inv_norm_out=inv)
     want, winv = otower.l2_normalize(osampler.gather(feats, idx), np.float32)
     got = out.cpu().numpy()
@@ -119,7 +124,7 @@ def test_gather_rows(cd, F):
     assert np.all(got[:, F:] == 0)
     np.testing.assert_allclose(inv.cpu().numpy(), winv[:, 0], rtol=1e-6)
     # raw gather is a bit-exact copy (inputs.py:158)
-    raw = torch.empty((77, ru(F, 4)), device=cd.dev)
+    raw = fp.poisoned((77, ru(F, 4)), device=cd.dev)
     cd.ops.gather_rows(table.data, 0, didx, F, raw, normalize=False)
     np.testing.assert_array_equal(raw.cpu().numpy()[:, :F], feats[idx])
 
@@ -128,7 +133,7 @@ def test_gather_shard_and_oob_flag(cd):
     feats = np.random.RandomState(1).random_sample((50, 8)).astype(np.float32)
     table = cd.engine.FeatureTable.from_numpy(feats, cd.dev, row0=100, n_rows_global=200)
     flag = torch.zeros(1, dtype=torch.int32, device=cd.dev)
-    out = torch.empty((3, 8), device=cd.dev)
+    out = fp.poisoned((3, 8), device=cd.dev)
     cd.ops.gather_rows(table.data, 100, dt([100, 149, 120], cd.dev, torch.int32), 8, out,
                        normalize=False, oob_flag=flag)
     np.testing.assert_array_equal(out.cpu().numpy(), feats[[0, 49, 20]])
@@ -215,10 +220,10 @@ def test_fused_sample_gather_equals_separate(cd, mode):
     pairs = dt(osynth.cowatch_pairs(N, 200, 0), cd.dev, torch.int32)
     rpt = 3 if mode == 0 else 2
     Fp = table.data.shape[1]
-    x1 = torch.empty((rpt * B, Fp), device=cd.dev)
-    x2 = torch.empty_like(x1)
-    i1 = torch.empty(rpt * B, dtype=torch.int32, device=cd.dev)
-    i2 = torch.empty_like(i1)
+    x1 = fp.poisoned((rpt * B, Fp), device=cd.dev)
+    x2 = fp.poisoned_like(x1)
+    i1 = fp.poisoned(rpt * B, dtype=torch.int32, device=cd.dev)
+    i2 = fp.poisoned_like(i1)
     s1 = torch.zeros(1, dtype=torch.int32, device=cd.dev)
     s2 = torch.zeros_like(s1)
     cd.ops.sample_gather(mode, pairs, 5, 11, B, table.data, F, i1, x1, shift_out=s1)
@@ -240,13 +245,13 @@ def test_l2norm_fwd_bwd(cd):
     z[4] = 1e-8
     g = rng.randn(70, 256).astype(np.float32)
     dz_, dg = dt(z, cd.dev), dt(g, cd.dev)
-    y = torch.empty_like(dz_)
-    inv = torch.empty(70, device=cd.dev)
+    y = fp.poisoned_like(dz_)
+    inv = fp.poisoned(70, device=cd.dev)
     cd.ops.l2norm_fwd(dz_, 256, y, inv)
     wy, winv = otower.l2_normalize(z, np.float64)
     np.testing.assert_allclose(y.cpu().numpy(), wy, atol=1e-6)
     np.testing.assert_allclose(inv.cpu().numpy(), winv[:, 0], rtol=1e-6)
-    out = torch.empty_like(dz_)
+    out = fp.poisoned_like(dz_)
     cd.ops.l2norm_bwd(dz_, dg, 256, out, lrelu_alpha=-1.0)
     want = otower.l2_normalize_backward(z.astype(np.float64), winv, g, np.float64)
     scale = np.abs(want).max(axis=1, keepdims=True) + 1e-30
@@ -275,7 +280,7 @@ def test_fc_bwd_weight2_stream_k(cd, M, K1, N1, K2, N2):
     dy2 = torch.randn(M, N2, device=cd.dev, generator=g) / 8
     nb = cd.ops.fc_bwd_weight2_workspace(M, K1, N1, K2, N2)
     assert nb > 0
-    ws = torch.empty(nb // 4, device=cd.dev)
+    ws = fp.poisoned(nb // 4, device=cd.dev)
     f = lambda *s: torch.full(s, 7.0, device=cd.dev)
     dW1, db1, dW2, db2 = f(K1, N1), f(N1), f(K2, N2), f(N2)
     cd.ops.fc_bwd_weight2(x1, dy1, dW1, db1, K1, N1, x2, dy2, dW2, db2, K2, N2, M, ws)
@@ -305,18 +310,20 @@ def test_fc_race_screen(cd):
     W = torch.randn(K, N, device=cd.dev, generator=g)
     dy = torch.randn(M, N, device=cd.dev, generator=g)
     b = torch.zeros(N, device=cd.dev)
-    y = torch.empty((M, N), device=cd.dev)
+    y = fp.poisoned((M, N), device=cd.dev)
     cd.ops.fc_lrelu_fwd(x, W, b, y, M, K, N)
     first = y.clone()
-    ws = torch.empty(cd.ops.fc_bwd_weight_workspace(M, K, N) // 4, device=cd.dev)
-    dW, db = torch.empty((K, N), device=cd.dev), torch.empty(N, device=cd.dev)
+    ws = fp.poisoned(cd.ops.fc_bwd_weight_workspace(M, K, N) // 4, device=cd.dev)
+    dW, db = fp.poisoned((K, N), device=cd.dev), fp.poisoned(N, device=cd.dev)
     cd.ops.fc_bwd_weight(x, dy, dW, db, ws, M, K, N)
-    dW0 = dW.clone()
-    for _ in range(40):
+    dW0, db0 = dW.clone(), db.clone()
+    for it in range(40):
+        for t in (y, dW, db, ws):                            # outputs and split-K workspace re-poisoned before every relaunch
+            fp.poison_(t, it)
         cd.ops.fc_lrelu_fwd(x, W, b, y, M, K, N)
         assert torch.equal(y, first)
         cd.ops.fc_bwd_weight(x, dy, dW, db, ws, M, K, N)
-        assert torch.equal(dW, dW0)
+        assert torch.equal(dW, dW0) and torch.equal(db, db0)
 
 
 @pytest.mark.parametrize("M,K,N", FC_SHAPES)
@@ -337,7 +344,7 @@ def test_fc_fwd_identity_asymmetric(cd):
     """A = I with an asymmetric B catches a transposed C/D register map."""
     K = N = 128
     Bm = np.arange(K * N, dtype=np.float64).reshape(K, N) % 251 - 100
-    y = torch.empty((K, N), device=cd.dev)
+    y = fp.poisoned((K, N), device=cd.dev)
     cd.ops.fc_lrelu_fwd(dt(np.eye(K), cd.dev), dt(Bm, cd.dev), dt(np.zeros(N), cd.dev), y, K, K, N,
                         alpha=1.0)
     np.testing.assert_array_equal(y.cpu().numpy(), Bm.astype(np.float32))
@@ -349,7 +356,7 @@ def test_fc_bwd_data(cd, M, K, N):
     dy = rng.randn(M, N) / np.sqrt(N)
     W = rng.randn(K, N) * 0.5
     xp = rng.randn(M, K)
-    dx = torch.empty((M, K), device=cd.dev)
+    dx = fp.poisoned((M, K), device=cd.dev)
     cd.ops.fc_bwd_data(dt(dy, cd.dev), dt(W, cd.dev), dt(xp, cd.dev), dx, M, K, N)
     f = lambda a: a.astype(np.float32).astype(np.float64)
     want = otower.leaky_relu_backward(f(xp), f(dy) @ f(W).T)
@@ -373,7 +380,7 @@ def test_fc_bwd_data_output_layer_shapes(cd, M, K):
     ref = (dy.double() @ W.double().T) * torch.where(xp > 0, 1.0, 0.2).double()
     assert (dx.double() - ref).abs().max().item() <= TOL
     for _ in range(5):
-        again = torch.empty_like(dx)
+        again = fp.poisoned_like(dx)
         cd.ops.fc_bwd_data(dy, W, xp, again, M, K, N)
         assert torch.equal(dx, again)
     cd.ops.fc_bwd_data(dy, W, None, dx, M, K, N)
@@ -398,15 +405,15 @@ def test_fc_bwd_weight(cd, M, K, N):
     dy = rng.randn(M, N)
     nb = cd.ops.fc_bwd_weight_workspace(M, K, N)
     assert nb > 0
-    ws = torch.empty(nb // 4, device=cd.dev)
-    dW = torch.empty((K, N), device=cd.dev)
-    db = torch.empty(N, device=cd.dev)
+    ws = fp.poisoned(nb // 4, device=cd.dev)
+    dW = fp.poisoned((K, N), device=cd.dev)
+    db = fp.poisoned(N, device=cd.dev)
     cd.ops.fc_bwd_weight(dt(x, cd.dev), dt(dy, cd.dev), dW, db, ws, M, K, N)
     f = lambda a: a.astype(np.float32).astype(np.float64)
     np.testing.assert_allclose(dW.cpu().numpy(), f(x).T @ f(dy), atol=2e-5)
     np.testing.assert_allclose(db.cpu().numpy(), f(dy).sum(0), atol=2e-5 * np.sqrt(M))
     # deterministic: a second run is bit-identical
-    dW2 = torch.empty_like(dW)
+    dW2 = fp.poisoned_like(dW)
     cd.ops.fc_bwd_weight(dt(x, cd.dev), dt(dy, cd.dev), dW2, db, ws, M, K, N)
     assert torch.equal(dW, dW2)
 
@@ -431,9 +438,9 @@ def test_hinge_known_answer_facade(cd, golden_dir, margin):
 def test_hinge_fwd_bwd_vs_oracle(cd, B, D):
     rng = np.random.RandomState(B)
     e = otower.l2_normalize(rng.randn(3 * B, D), np.float64)[0]
-    de = torch.empty((3 * B, D), device=cd.dev)
-    pos, neg, hinge = (torch.empty(B, device=cd.dev) for _ in range(3))
-    stats = torch.empty(4, device=cd.dev)
+    de = fp.poisoned((3 * B, D), device=cd.dev)
+    pos, neg, hinge = (fp.poisoned(B, device=cd.dev) for _ in range(3))
+    stats = fp.poisoned(4, device=cd.dev)
     cd.ops.triplet_hinge(dt(e, cd.dev), B, D, 0.8, pos, neg, hinge, stats, de)
     e32 = e.astype(np.float32).astype(np.float64).reshape(B, 3, D)
     w = otower.hinge_loss(e32, 0.8, np.float64)
@@ -455,10 +462,10 @@ def test_hinge_inbatch_vs_oracle(cd):
     for step in range(4):
         rows, tri, valid, s = osampler.device_inbatch(pairs, 3, step, B)
         n_invalid += int((valid == 0).sum())
-        pos, neg, hinge = (torch.empty(B, device=cd.dev) for _ in range(3))
-        v = torch.empty(B, dtype=torch.uint8, device=cd.dev)
-        stats = torch.empty(4, device=cd.dev)
-        de = torch.empty((2 * B, D), device=cd.dev)
+        pos, neg, hinge = (fp.poisoned(B, device=cd.dev) for _ in range(3))
+        v = fp.poisoned(B, dtype=torch.uint8, device=cd.dev)
+        stats = fp.poisoned(4, device=cd.dev)
+        de = fp.poisoned((2 * B, D), device=cd.dev)
         cd.ops.triplet_hinge_inbatch(dt(e, cd.dev), dt(rows, cd.dev, torch.int32),
                                      dt([s], cd.dev, torch.int32), B, D, 0.8, pos, neg, hinge, v,
                                      stats, de)
@@ -922,17 +929,17 @@ def test_memory_triplet_pipe(cd):
 
 
 def test_errors_are_raised_not_swallowed(cd):
-    y = torch.empty((8, 64), device=cd.dev)
-    x = torch.empty((8, 48), device=cd.dev)
-    W = torch.empty((48, 64), device=cd.dev)
-    b = torch.empty(64, device=cd.dev)
+    y = fp.poisoned((8, 64), device=cd.dev)
+    x = fp.poisoned((8, 48), device=cd.dev)
+    W = fp.poisoned((48, 64), device=cd.dev)
+    b = fp.poisoned(64, device=cd.dev)
     with pytest.raises(cd.pkg.CdmlError) as ei:
         cd.ops.fc_lrelu_fwd(x, W, b, y, 8, 48, 64)           # K not a multiple of 32
     assert ei.value.code == -4 and "multiple of 32" in str(ei.value)
     with pytest.raises(cd.pkg.CdmlError):
         cd.ops.fc_lrelu_fwd(x[:, 1:33], W[:32], b, y, 8, 32, 64)    # misaligned base
     with pytest.raises(ValueError):
-        cd.ops.l2norm_fwd(torch.empty((4, 8)), 8, torch.empty((4, 8)))   # CPU tensors: no fallback
+        cd.ops.l2norm_fwd(fp.poisoned((4, 8)), 8, fp.poisoned((4, 8)))   # CPU tensors: no fallback
     with pytest.raises(cd.pkg.CdmlError):
         cd.ops.sample_inbatch(torch.zeros((4, 2), dtype=torch.int32, device=cd.dev), 1, 0, 1,
                               torch.zeros(2, dtype=torch.int32, device=cd.dev),
@@ -993,11 +1000,11 @@ def test_semihard_select_and_indexed_loss(cd):
         if trial:
             rows[:8] = 0; rows[8:] = rng.randint(0, 2, size=2 * B - 8)   # anchors with nothing eligible
         de_, dr = dt(E, cd.dev), dt(rows, cd.dev, torch.int32)
-        S = torch.empty((B, 2 * B), device=cd.dev)
+        S = fp.poisoned((B, 2 * B), device=cd.dev)
         cd.ops.fc_bwd_data(de_[0::2], de_, None, S, B, 2 * B, D)
         np.testing.assert_allclose(S.cpu().numpy(), E[0::2].astype(np.float64) @ E.T.astype(np.float64), atol=1e-5)
-        neg_row = torch.empty(B, dtype=torch.int32, device=cd.dev)
-        cd.ops.semihard_select(S, de_, dr, B, D, torch.empty(2 * B, device=cd.dev), neg_row)
+        neg_row = fp.poisoned(B, dtype=torch.int32, device=cd.dev)
+        cd.ops.semihard_select(S, de_, dr, B, D, fp.poisoned(2 * B, device=cd.dev), neg_row)
         got = neg_row.cpu().numpy()
         want, dist = otower.semihard_select(E.astype(np.float64), rows)
         d_p = dist[np.arange(B), 2 * np.arange(B) + 1]
@@ -1020,16 +1027,16 @@ def test_semihard_select_and_indexed_loss(cd):
             assert (want < 0).any()
         # loss + gradient on the DEVICE's selection vs the oracle's indexed loss
         tri, valid = otower.semihard_triplets(got)
-        pos, neg, hinge, scale = (torch.empty(B, device=cd.dev) for _ in range(4))
-        stats = torch.empty(4, device=cd.dev)
-        dE = torch.empty((2 * B, D), device=cd.dev)
+        pos, neg, hinge, scale = (fp.poisoned(B, device=cd.dev) for _ in range(4))
+        stats = fp.poisoned(4, device=cd.dev)
+        dE = fp.poisoned((2 * B, D), device=cd.dev)
         cd.ops.triplet_hinge_indexed(de_, neg_row, B, D, 0.8, pos, neg, hinge, scale, stats, dE)
         w = otower.hinge_loss_indexed(E.astype(np.float64), tri, valid, 0.8, np.float64)
         np.testing.assert_allclose(hinge.cpu().numpy(), w["hinge_dist"], atol=TOL)
         np.testing.assert_allclose(stats[0].item(), w["hinge_loss"], atol=TOL)
         wd = otower.hinge_loss_indexed_backward(E.astype(np.float64), tri, valid, 0.8, np.float64)
         np.testing.assert_allclose(dE.cpu().numpy(), wd, atol=TOL)
-        dE2 = torch.empty_like(dE)
+        dE2 = fp.poisoned_like(dE)
         cd.ops.triplet_hinge_indexed(de_, neg_row, B, D, 0.8, pos, neg, hinge, scale, stats, dE2)
         assert torch.equal(dE, dE2)                   # deterministic accumulation
 
@@ -1057,9 +1064,9 @@ def test_indexed_hinge_backward_block_scan_and_fused_tail(cd, B, D, skew):
         nr[rng.rand(B) < 0.4] = -1
     nr = nr.astype(np.int32)
     dz_, de_, dn = dt(Z, cd.dev), dt(E, cd.dev), dt(nr, cd.dev, torch.int32)
-    pos, neg, hinge, scale = (torch.empty(B, device=cd.dev) for _ in range(4))
-    stats = torch.empty(4, device=cd.dev)
-    dE = torch.empty((2 * B, D), device=cd.dev)
+    pos, neg, hinge, scale = (fp.poisoned(B, device=cd.dev) for _ in range(4))
+    stats = fp.poisoned(4, device=cd.dev)
+    dE = fp.poisoned((2 * B, D), device=cd.dev)
     cd.ops.triplet_hinge_indexed(de_, dn, B, D, 0.8, pos, neg, hinge, scale, stats, dE)
     tri, valid = otower.semihard_triplets(nr)
     w = otower.hinge_loss_indexed(E.astype(np.float64), tri, valid, 0.8, np.float64)
@@ -1072,13 +1079,13 @@ def test_indexed_hinge_backward_block_scan_and_fused_tail(cd, B, D, skew):
         pytest.skip("a triplet sits on the hinge's corner in this draw")
     np.testing.assert_allclose(got, wd, atol=5e-5 if skew == "one-row" else TOL)     # (one row sums B terms: fp32 accumulation)
     # the separate launches of the tail ...
-    dz2_a = torch.empty((2 * B, D), device=cd.dev)
+    dz2_a = fp.poisoned((2 * B, D), device=cd.dev)
     cd.ops.l2norm_bwd(dz_, dE, D, dz2_a, lrelu_alpha=cd.ops.LRELU_ALPHA)
     pl_a = torch.zeros((2 * B, 3 * D), dtype=torch.bfloat16, device=cd.dev)
     cd.ops.split_f32_bf16x3(dz2_a, pl_a, D)
     # ... against the fused form, three planes and plain bf16
     for planes in (True, False):
-        dE_b, dz2_b = torch.empty_like(dE), torch.empty_like(dz2_a)
+        dE_b, dz2_b = fp.poisoned_like(dE), fp.poisoned_like(dz2_a)
         bf = torch.zeros((2 * B, 3 * D if planes else D), dtype=torch.bfloat16, device=cd.dev)
         cd.ops.triplet_hinge_indexed(de_, dn, B, D, 0.8, pos, neg, hinge, scale, stats, dE_b, z=dz_, dz2=dz2_b, dz2_bf16=bf,
                                      plane_bf=D if planes else 0)
@@ -1152,14 +1159,14 @@ def test_semihard_mine_fused_into_the_score_product(cd, B, D, h2):
         if trial:
             assert (want < 0).any()
         # and the unfused kernels on the same input agree (both within rounding of the oracle)
-        S = torch.empty((B, 2 * B), device=cd.dev)
+        S = fp.poisoned((B, 2 * B), device=cd.dev)
         if D % 32 == 0:
             cd.ops.fc_bwd_data(de_[0::2], de_, None, S, B, 2 * B, D)
-            old = torch.empty(B, dtype=torch.int32, device=cd.dev)
-            cd.ops.semihard_select(S, de_, dr, B, D, torch.empty(2 * B, device=cd.dev), old)
+            old = fp.poisoned(B, dtype=torch.int32, device=cd.dev)
+            cd.ops.semihard_select(S, de_, dr, B, D, fp.poisoned(2 * B, device=cd.dev), old)
             assert (old.cpu().numpy() == got).mean() > 0.95
         # deterministic
-        again = torch.empty_like(neg_row)
+        again = fp.poisoned_like(neg_row)
         cd.ops.semihard_mine_x3(de_, dr, B, D, e3, D, sqn, dpd, wsp, again, h2_scale=hs)
         assert torch.equal(again, neg_row)
 
@@ -1265,7 +1272,7 @@ def test_prediction_embed_table_production_shape(cd, precision):
     want = otower.vnet_forward(feats.astype(np.float64), *W, dtype=np.float64)["l2_norm"]
     np.testing.assert_allclose(out.cpu().numpy(), want, atol=TOL if precision != "bf16" else 5e-3)
     np.testing.assert_allclose(out.norm(dim=1).cpu().numpy(), 1.0, atol=1e-5)
-    again = torch.empty_like(out)
+    again = fp.poisoned_like(out)
     pred.embed_table(table, 777, out=again)                                 # other chunking, caller's buffer
     np.testing.assert_allclose(again.cpu().numpy(), out.cpu().numpy(), atol=2e-6 if precision != "bf16" else 1e-3)
     np.testing.assert_array_equal(pred.run_features(table, chunk), out.cpu().numpy())        # the ndarray API on top
