@@ -24,8 +24,8 @@ def lib_path():
 
 
 def source_id(csrc=None, header=None):
-    """sha256[:16] over the sources the library is built from -- csrc/*.hip, csrc/*.h (sorted by name) and
-    include/cdml.h.  __graft_entry__.build() compiles it into the library (``cdml_build_id()``); ``load_library``
+    """sha256[:16] over the sources the library is built from -- csrc/*.hip, csrc/*.h (sorted by name),
+    include/cdml.h and the feature headers beside it (include/cdml_*.h, sorted by name).  __graft_entry__.build() compiles it into the library (``cdml_build_id()``); ``load_library``
     compares the two, so a prebuilt .so that travelled with a tree it was not built from is refused instead of
     silently passing for it (file times say nothing after a copy).  None when the tree has no sources."""
     import glob
@@ -36,7 +36,7 @@ def source_id(csrc=None, header=None):
     if not files or not os.path.exists(header):
         return None
     h = hashlib.sha256()
-    for f in files + [header]:
+    for f in files + [header] + sorted(glob.glob(os.path.join(os.path.dirname(header), "cdml_*.h"))):
         h.update(os.path.basename(f).encode())
         h.update(open(f, "rb").read())
     return h.hexdigest()[:16]
@@ -202,6 +202,16 @@ SIGNATURES = {
                                      _p, _p, _p]),
 }
 
+# name -> (restype, argtypes); must list every symbol include/cdml_npair_mixed.h declares (the N-pair loss with mixed
+# negative sampling: a header and a table of its own)
+SIGNATURES_MIXED = {
+    "cdml_npair_mixed_workspace": (_sz, [_i, _i]),
+    "cdml_npair_mixed_stats": (_i, [_p, _i64, _p, _i, _i64, _i64, _p, _i, _p, _f, _p, _f, _i, _p, _p, _p, _sz, _p]),
+    "cdml_npair_mixed_grad_x3": (_i, [_p, _i64, _p, _i, _i64, _i64, _p, _i, _p, _f, _p, _f, _i, _p, _p, _i64, _i64, _p]),
+    "cdml_npair_mixed_grad_f32": (_i, [_p, _i64, _p, _i, _i64, _i64, _p, _i, _p, _f, _p, _f, _i, _p, _p, _i64, _p]),
+    "cdml_npair_mixed_split_x3": (_i, [_p, _i64, _i, _i, _p, _i64, _i64, _p, _i64, _i64, _p, _i64, _i64, _i64, _p]),
+}
+
 _lib = None
 
 
@@ -220,7 +230,7 @@ def load_library():
     # its launches then fail with "no ROCm-capable device is detected".
     import torch  # noqa: F401
     lib = C.CDLL(path)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_MIXED.items()):
         fn = getattr(lib, name)          # AttributeError if the ABI lost a symbol
         fn.restype = res
         fn.argtypes = args

@@ -9,6 +9,7 @@ carries exactly these names with exactly these defaults (+ the build's own switc
 builds the ``TrainStep`` / ``Trainer`` pair ("Config / flags")."""
 import dataclasses
 import json
+import typing
 
 
 @dataclasses.dataclass
@@ -44,6 +45,8 @@ class TrainConfig:
     memory_start: int = 0                     # mode "npair": the first step that pushes into that memory
     logq: str = ""                            # mode "npair": "stream" = the sampling-bias (logQ) correction, estimated on the fly
     logq_alpha: float = 0.01                  # mode "npair": that estimator's smoothing rate (build-defined)
+    uniform_negatives: bool = False           # mode "npair": mixed negative sampling -- a uniform catalogue negative per pair in the softmax
+    uniform_logq: typing.Optional[float] = None   # with logq: the uniform block's log sampling probability (None: derived from logq)
     seed: int = 1234
     weight_seed: int = 42
 
@@ -79,8 +82,11 @@ class TrainConfig:
                   regularization_penalty=self.regularization_penalty)
         if self.mode == "npair":
             kw.update(temperature=self.temperature, symmetric=self.symmetric, memory_size=self.memory_size,
-                      memory_start=self.memory_start, logq=self.logq or None, logq_alpha=self.logq_alpha)
+                      memory_start=self.memory_start, logq=self.logq or None, logq_alpha=self.logq_alpha,
+                      uniform_negatives=self.uniform_negatives, uniform_logq=self.uniform_logq)
         else:
+            if self.uniform_negatives:
+                kw.update(uniform_negatives=True)         # (TrainStep refuses it outside mode "npair")
             if self.memory_size:
                 kw.update(memory_size=self.memory_size)   # (TrainStep refuses it outside mode "npair")
             if self.logq:

@@ -1,0 +1,583 @@
+// The N-pair loss with mixed negative sampling (Yang et al., WWW 2020 companion; build-defined -- the reference's only
+// negative rule is the uniform draw itself, parse_data.py:292-298): the softmax of every anchor runs over the in-batch
+// positives AND the batch's uniformly drawn catalogue negatives (and the cross-batch memory), and the uniform negatives
+// receive a gradient.  include/cdml_npair_mixed.h states the definition; csrc/npair.hip the in-batch / memory rules.
+//
+// The chain reads the uniform sampler's own layout -- ids[3i], [3i+1], [3i+2] = a_i, p_i, n_i and the embedded rows
+// e[3i], e[3i+1], e[3i+2] -- so nothing is repacked: a lane takes FOUR triplets' twelve ids as three 16-B loads.
+//   k_mixed_split     the three bf16 planes of A, P, N from e's stride-3 rows into the operand images of the plane
+//                     GEMMs: A3, the row image [P; N; ..] and (through a 64 x 64 LDS tile) the transposed image
+//   k_mixed_rows      one block per anchor: one pass over S[i][:] -- the in-batch and the uniform block four columns per
+//                     lane from the same id loads, then the memory block -- with an online (max, sum-exp) per lane,
+//                     combined by a fixed butterfly and then wave by wave
+//   k_mixed_cols / k_mixed_col_fold   (symmetric) the column term over the in-batch block, as k_npair_cols / _fold
+//   k_mixed_stats     one block: the step scalars from the per-row partials in a fixed order
+//   k_mixed_w<X3>     W of all blocks in ONE launch, four columns per lane, as three bf16 planes or fp32
+// BIAS (template switch): the logQ correction -- in-batch logits less bias[2j + 1] (the [2B] layout of the logQ gather),
+// the uniform block's less the scalar lq_u, a slot's less mem_bias[k].  No atomics; every sum in a fixed order.
+#include "common.h"
+#include "../../include/cdml_npair_mixed.h"
+#include <math.h>
+
+namespace cdml {
+namespace {
+
+constexpr int kMxThreads = 256;
+constexpr int kMxChunk = 256;          // rows per block of the column pass
+constexpr int kMxTile = 64;            // the split's tile
+
+using bf4 = __attribute__((ext_vector_type(4))) __bf16;
+
+__device__ __forceinline__ void mx_split3(float v, __bf16 &h, __bf16 &m, __bf16 &l) {
+  h = (__bf16)v;
+  const float r = v - (float)h;
+  m = (__bf16)r;
+  l = (__bf16)(r - (float)m);
+}
+
+__device__ __forceinline__ void mx_split4(const float (&w)[4], bf4 &h, bf4 &m, bf4 &l) {
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    __bf16 a, b, c;
+    mx_split3(w[q], a, b, c);
+    h[q] = a;
+    m[q] = b;
+    l[q] = c;
+  }
+}
+
+__device__ __forceinline__ void mx_merge(float &m, float &s, float m2, float s2) {
+  const float mx = fmaxf(m, m2);
+  if (mx == -INFINITY) return;
+  s = s * expf(m - mx) + s2 * expf(m2 - mx);
+  m = mx;
+}
+
+__device__ __forceinline__ void mx_add(float &m, float &s, float x) {
+  if (x > m) {
+    s = s * expf(m - x) + 1.f;
+    m = x;
+  } else {
+    s += expf(x - m);
+  }
+}
+
+// the ids of triplets j0 .. j0 + 3 (j0 a multiple of 4): twelve consecutive int32, three 16-B loads
+__device__ __forceinline__ void mx_ids4(const int32_t *ids, int j0, int (&a)[4], int (&p)[4], int (&n)[4]) {
+  const int4 *src = reinterpret_cast<const int4 *>(ids + 3 * (int64_t)j0);
+  const int4 x = src[0], y = src[1], z = src[2];
+  a[0] = x.x; p[0] = x.y; n[0] = x.z;
+  a[1] = x.w; p[1] = y.x; n[1] = y.y;
+  a[2] = y.z; p[2] = y.w; n[2] = z.x;
+  a[3] = z.y; p[3] = z.z; n[3] = z.w;
+}
+
+__device__ __forceinline__ bool mx_other(int q, int ida, int idp) { return q != ida && q != idp; }
+
+// part[4 i .. 4 i + 3] = {lse_i - (S_ii / t - lq(p_i)), 2 - 2 S_ii, sum over the counted negatives of 2 - 2 S, their count}
+template <bool MEM, bool BIAS>
+__global__ void __launch_bounds__(kMxThreads)
+k_mixed_rows(const float *__restrict__ S, int64_t lds, const int32_t *__restrict__ ids, int B, float inv_t,
+             float *__restrict__ lse, float *__restrict__ part, int64_t neg_col, int64_t mem_col,
+             const int32_t *__restrict__ mem_id, int n_mem, const float *__restrict__ bias, float lq_u,
+             const float *__restrict__ mem_bias) {
+  __shared__ float sm[kMxThreads / kWave][4];
+  const int i = blockIdx.x;
+  const float *row = S + (int64_t)i * lds;
+  const int ida = ids ? ids[3 * (int64_t)i] : 0, idp = ids ? ids[3 * (int64_t)i + 1] : 0;
+  float m = -INFINITY, s = 0.f, nsum = 0.f, ncnt = 0.f;
+  for (int j0 = 4 * threadIdx.x; j0 < B; j0 += 4 * kMxThreads) {
+    const float4 v4 = *reinterpret_cast<const float4 *>(row + j0);
+    const float4 u4 = *reinterpret_cast<const float4 *>(row + neg_col + j0);
+    const float v[4] = {v4.x, v4.y, v4.z, v4.w}, u[4] = {u4.x, u4.y, u4.z, u4.w};
+    int a[4] = {0, 0, 0, 0}, p[4] = {0, 0, 0, 0}, n[4] = {0, 0, 0, 0};
+    if (ids) mx_ids4(ids, j0, a, p, n);
+    float bp[4] = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (BIAS) {                                // slots 2 j0 .. 2 j0 + 7 of the [2B] layout: the positives' are odd
+      const float4 b0 = *reinterpret_cast<const float4 *>(bias + 2 * (int64_t)j0);
+      const float4 b1 = *reinterpret_cast<const float4 *>(bias + 2 * (int64_t)j0 + 4);
+      bp[0] = b0.y; bp[1] = b0.w; bp[2] = b1.y; bp[3] = b1.w;
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {                        // the in-batch block
+      const int j = j0 + q;
+      if (j != i && ids && !mx_other(p[q], ida, idp)) continue;
+      if constexpr (BIAS)
+        mx_add(m, s, v[q] * inv_t - bp[q]);
+      else
+        mx_add(m, s, v[q] * inv_t);
+      if (j != i) {
+        nsum += 2.f - 2.f * v[q];
+        ncnt += 1.f;
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {                        // the uniform block: no special diagonal
+      if (ids && !mx_other(n[q], ida, idp)) continue;
+      if constexpr (BIAS)
+        mx_add(m, s, u[q] * inv_t - lq_u);
+      else
+        mx_add(m, s, u[q] * inv_t);
+      nsum += 2.f - 2.f * u[q];
+      ncnt += 1.f;
+    }
+  }
+  if constexpr (MEM) {
+    const float *mrow = row + mem_col;
+    for (int k = 4 * threadIdx.x; k < n_mem; k += 4 * kMxThreads) {
+      const float4 v4 = *reinterpret_cast<const float4 *>(mrow + k);
+      const int4 q4 = *reinterpret_cast<const int4 *>(mem_id + k);
+      const float v[4] = {v4.x, v4.y, v4.z, v4.w};
+      const int q[4] = {q4.x, q4.y, q4.z, q4.w};
+      float b[4] = {0.f, 0.f, 0.f, 0.f};
+      if constexpr (BIAS) {
+        const float4 b4 = *reinterpret_cast<const float4 *>(mem_bias + k);
+        b[0] = b4.x; b[1] = b4.y; b[2] = b4.z; b[3] = b4.w;
+      }
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        if (q[c] < 0 || (ids && !mx_other(q[c], ida, idp))) continue;
+        if constexpr (BIAS)
+          mx_add(m, s, v[c] * inv_t - b[c]);
+        else
+          mx_add(m, s, v[c] * inv_t);
+        nsum += 2.f - 2.f * v[c];
+        ncnt += 1.f;
+      }
+    }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const float m2 = __shfl_xor(m, off, 64), s2 = __shfl_xor(s, off, 64);
+    mx_merge(m, s, m2, s2);
+  }
+  nsum = wave_sum(nsum);
+  ncnt = wave_sum(ncnt);
+  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+  if (lane == 0) {
+    sm[wave][0] = m;
+    sm[wave][1] = s;
+    sm[wave][2] = nsum;
+    sm[wave][3] = ncnt;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float M = sm[0][0], Sx = sm[0][1], ns = sm[0][2], nc = sm[0][3];
+    for (int w = 1; w < kMxThreads / kWave; ++w) {
+      mx_merge(M, Sx, sm[w][0], sm[w][1]);
+      ns += sm[w][2];
+      nc += sm[w][3];
+    }
+    const float sii = row[i];
+    const float l = M + logf(Sx);
+    lse[i] = l;
+    float d;
+    if constexpr (BIAS)
+      d = sii * inv_t - bias[2 * (int64_t)i + 1];
+    else
+      d = sii * inv_t;
+    *reinterpret_cast<float4 *>(part + 4 * (int64_t)i) = make_float4(l - d, 2.f - 2.f * sii, ns, nc);
+  }
+}
+
+// cm / cs [chunk][B]: the (max, sum-exp) of in-batch column j over rows chunk * kMxChunk .. + kMxChunk - 1
+// (row i counts for column j when i == j or id(a_i) is neither id(a_j) nor id(p_j); BIAS: row i's logit less bias[2i])
+template <bool BIAS>
+__global__ void __launch_bounds__(kMxThreads)
+k_mixed_cols(const float *__restrict__ S, int64_t lds, const int32_t *__restrict__ ids, int B, float inv_t,
+             float *__restrict__ cm, float *__restrict__ cs, const float *__restrict__ bias) {
+  const int j = blockIdx.x * kMxThreads + threadIdx.x;
+  const int c = blockIdx.y;
+  if (j >= B) return;
+  const int idaj = ids ? ids[3 * (int64_t)j] : 0, idpj = ids ? ids[3 * (int64_t)j + 1] : 0;
+  const int i0 = c * kMxChunk, i1 = min(B, i0 + kMxChunk);
+  float m = -INFINITY, s = 0.f;
+  for (int i = i0; i < i1; ++i) {
+    if (i != j && ids && !mx_other(ids[3 * (int64_t)i], idaj, idpj)) continue;
+    if constexpr (BIAS)
+      mx_add(m, s, S[(int64_t)i * lds + j] * inv_t - bias[2 * (int64_t)i]);
+    else
+      mx_add(m, s, S[(int64_t)i * lds + j] * inv_t);
+  }
+  cm[(int64_t)c * B + j] = m;
+  cs[(int64_t)c * B + j] = s;
+}
+
+template <bool BIAS>
+__global__ void __launch_bounds__(kMxThreads)
+k_mixed_col_fold(const float *__restrict__ S, int64_t lds, int B, int chunks, float inv_t, const float *__restrict__ cm,
+                 const float *__restrict__ cs, float *__restrict__ lse, float *__restrict__ closs,
+                 const float *__restrict__ bias) {
+  const int j = blockIdx.x * kMxThreads + threadIdx.x;
+  if (j >= B) return;
+  float m = -INFINITY, s = 0.f;
+  for (int c = 0; c < chunks; ++c) mx_merge(m, s, cm[(int64_t)c * B + j], cs[(int64_t)c * B + j]);
+  const float l = m + logf(s);
+  lse[B + j] = l;
+  if constexpr (BIAS)
+    closs[j] = l - (S[(int64_t)j * lds + j] * inv_t - bias[2 * (int64_t)j]);
+  else
+    closs[j] = l - S[(int64_t)j * lds + j] * inv_t;
+}
+
+// stats[0] = loss, [1] = mean |a_i - p_i|^2, [2] = mean squared distance over the counted negatives of the three blocks,
+// [3] = their fraction of B (B - 1) + B B + B M
+__global__ void __launch_bounds__(1024)
+k_mixed_stats(const float *__restrict__ part, const float *__restrict__ closs, int B, int symmetric, int M,
+              float *__restrict__ stats) {
+  __shared__ float sm[5][1024 / kWave];
+  float acc[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+  for (int i = threadIdx.x; i < B; i += 1024) {
+    const float4 p = *reinterpret_cast<const float4 *>(part + 4 * (int64_t)i);
+    acc[0] += p.x;
+    acc[1] += p.y;
+    acc[2] += p.z;
+    acc[3] += p.w;
+    if (symmetric) acc[4] += closs[i];
+  }
+  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+#pragma unroll
+  for (int c = 0; c < 5; ++c) {
+    const float v = wave_sum(acc[c]);
+    if (lane == 0) sm[c][wave] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float t[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+    for (int w = 0; w < 1024 / kWave; ++w)
+      for (int c = 0; c < 5; ++c) t[c] += sm[c][w];
+    const float fb = (float)B;
+    stats[0] = symmetric ? 0.5f * (t[0] / fb + t[4] / fb) : t[0] / fb;
+    stats[1] = t[1] / fb;
+    stats[2] = t[3] > 0.f ? t[2] / t[3] : 0.f;
+    const float den = fb * (float)(B - 1) + fb * fb + fb * (float)M;
+    stats[3] = t[3] / den;
+  }
+}
+
+// Row i = blockIdx.x, columns c0 = 4 (blockIdx.y * kMxThreads + threadIdx.x) .. c0 + 3 of the span [0, mem_col + M) (without
+// a memory: [0, neg_col + B)).  Every block starts and ends on a multiple of 4, so the four columns lie in one block or in a
+// gap between two, which is not written.  scale = 1 / (B t); the uniform and the memory block halve it with `symmetric`.
+template <bool X3, bool MEM, bool BIAS>
+__global__ void __launch_bounds__(kMxThreads)
+k_mixed_w(const float *__restrict__ S, int64_t lds, const int32_t *__restrict__ ids, int B, int64_t neg_col, int64_t mem_col,
+          const int32_t *__restrict__ mem_id, int M, float inv_t, int symmetric, const float *__restrict__ lse, float scale,
+          void *__restrict__ Wout, int64_t ldw, int64_t plane, const float *__restrict__ bias, float lq_u,
+          const float *__restrict__ mem_bias) {
+  const int i = blockIdx.x;
+  const int64_t c0 = ((int64_t)blockIdx.y * kMxThreads + threadIdx.x) * 4;
+  const int64_t span = MEM ? mem_col + M : neg_col + B;
+  if (c0 >= span) return;
+  const int ida = ids ? ids[3 * (int64_t)i] : 0, idp = ids ? ids[3 * (int64_t)i + 1] : 0;
+  const float lr = lse[i];
+  const float4 v4 = *reinterpret_cast<const float4 *>(S + (int64_t)i * lds + c0);
+  const float v[4] = {v4.x, v4.y, v4.z, v4.w};
+  const float side = symmetric ? 0.5f * scale : scale;
+  float w[4];
+  if (c0 < B) {                                          // the in-batch block (k_npair_w's arithmetic)
+    const int j0 = (int)c0;
+    int a[4] = {0, 0, 0, 0}, p[4] = {0, 0, 0, 0}, n[4];
+    if (ids) mx_ids4(ids, j0, a, p, n);
+    float bp[4] = {0.f, 0.f, 0.f, 0.f}, ba = 0.f;
+    if constexpr (BIAS) {
+      const float4 b0 = *reinterpret_cast<const float4 *>(bias + 2 * (int64_t)j0);
+      const float4 b1 = *reinterpret_cast<const float4 *>(bias + 2 * (int64_t)j0 + 4);
+      bp[0] = b0.y; bp[1] = b0.w; bp[2] = b1.y; bp[3] = b1.w;
+      ba = bias[2 * (int64_t)i];
+    }
+    float lc[4] = {0.f, 0.f, 0.f, 0.f};
+    if (symmetric) {
+      const float4 l4 = *reinterpret_cast<const float4 *>(lse + B + j0);
+      lc[0] = l4.x; lc[1] = l4.y; lc[2] = l4.z; lc[3] = l4.w;
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int j = j0 + q;
+      const bool rc = j == i || !ids || mx_other(p[q], ida, idp);
+      float r;
+      if constexpr (BIAS)
+        r = rc ? expf(v[q] * inv_t - bp[q] - lr) : 0.f;
+      else
+        r = rc ? expf(v[q] * inv_t - lr) : 0.f;
+      if (j == i) r -= 1.f;
+      if (symmetric) {
+        const bool cc = j == i || !ids || mx_other(ida, a[q], p[q]);
+        float c;
+        if constexpr (BIAS)
+          c = cc ? expf(v[q] * inv_t - ba - lc[q]) : 0.f;
+        else
+          c = cc ? expf(v[q] * inv_t - lc[q]) : 0.f;
+        if (j == i) c -= 1.f;
+        r = 0.5f * (r + c);
+      }
+      w[q] = r * scale;
+    }
+  } else if (c0 >= neg_col && c0 < neg_col + B) {        // the uniform block
+    const int j0 = (int)(c0 - neg_col);
+    int a[4], p[4], n[4] = {0, 0, 0, 0};
+    if (ids) mx_ids4(ids, j0, a, p, n);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const bool cn = !ids || mx_other(n[q], ida, idp);
+      if constexpr (BIAS)
+        w[q] = cn ? expf(v[q] * inv_t - lq_u - lr) * side : 0.f;
+      else
+        w[q] = cn ? expf(v[q] * inv_t - lr) * side : 0.f;
+    }
+  } else if (MEM && c0 >= mem_col) {                     // the memory block (k_npair_mem_w's arithmetic)
+    const int64_t k0 = c0 - mem_col;
+    const int4 q4 = *reinterpret_cast<const int4 *>(mem_id + k0);
+    const int qk[4] = {q4.x, q4.y, q4.z, q4.w};
+    float b[4] = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (BIAS) {
+      const float4 b4 = *reinterpret_cast<const float4 *>(mem_bias + k0);
+      b[0] = b4.x; b[1] = b4.y; b[2] = b4.z; b[3] = b4.w;
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const bool cm = qk[q] >= 0 && (!ids || mx_other(qk[q], ida, idp));
+      if constexpr (BIAS)
+        w[q] = cm ? expf(v[q] * inv_t - b[q] - lr) * side : 0.f;
+      else
+        w[q] = cm ? expf(v[q] * inv_t - lr) * side : 0.f;
+    }
+  } else {
+    return;                                              // a gap between two blocks
+  }
+  if (X3) {
+    bf4 h, m, l;
+    mx_split4(w, h, m, l);
+    __bf16 *dst = static_cast<__bf16 *>(Wout) + (int64_t)i * ldw + c0;
+    *reinterpret_cast<bf4 *>(dst) = h;
+    *reinterpret_cast<bf4 *>(dst + plane) = m;
+    *reinterpret_cast<bf4 *>(dst + 2 * plane) = l;
+  } else {
+    *reinterpret_cast<float4 *>(static_cast<float *>(Wout) + (int64_t)i * ldw + c0) = make_float4(w[0], w[1], w[2], w[3]);
+  }
+}
+
+// blockIdx.z = the role of the rows this block splits: 0 anchors (e[3r] -> A3[r]), 1 positives (e[3r + 1] -> R3[r] and
+// T3[.][r]), 2 uniform negatives (e[3r + 2] -> R3[neg_row + r] and T3[.][neg_row + r]).  A 64 x 64 tile per block: a lane
+// loads 16 B of a row and stores 8 B per plane; the transposed image goes through LDS so that its stores run along r too.
+__global__ void __launch_bounds__(kMxThreads)
+k_mixed_split(const float *__restrict__ e, int64_t lde, int B, int D, __bf16 *__restrict__ A3, int64_t lda, int64_t plane_a,
+              __bf16 *__restrict__ R3, int64_t ldr, int64_t plane_r, __bf16 *__restrict__ T3, int64_t ldt, int64_t plane_t,
+              int64_t neg_row) {
+  __shared__ float tile[kMxTile][kMxTile + 1];
+  const int role = blockIdx.z;
+  const int c0 = blockIdx.x * kMxTile, r0 = blockIdx.y * kMxTile;
+  const int64_t base = role == 2 ? neg_row : 0;
+  const int g = threadIdx.x & 15, sub = threadIdx.x >> 4;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int r = sub + 16 * k;
+    const int gr = r0 + r, gc = c0 + 4 * g;
+    if (gr >= B || gc >= D) continue;
+    const float4 v4 = *reinterpret_cast<const float4 *>(e + (3 * (int64_t)gr + role) * lde + gc);
+    const float v[4] = {v4.x, v4.y, v4.z, v4.w};
+    bf4 h, m, l;
+    mx_split4(v, h, m, l);
+    __bf16 *dst = role == 0 ? A3 + (int64_t)gr * lda + gc : R3 + (base + gr) * ldr + gc;
+    const int64_t pl = role == 0 ? plane_a : plane_r;
+    *reinterpret_cast<bf4 *>(dst) = h;
+    *reinterpret_cast<bf4 *>(dst + pl) = m;
+    *reinterpret_cast<bf4 *>(dst + 2 * pl) = l;
+    if (role != 0) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) tile[r][4 * g + q] = v[q];
+    }
+  }
+  if (role == 0) return;
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int c = sub + 16 * k;
+    const int gc = c0 + c, gr = r0 + 4 * g;
+    if (gc >= D || gr >= B) continue;
+    const float v[4] = {tile[4 * g][c], tile[4 * g + 1][c], tile[4 * g + 2][c], tile[4 * g + 3][c]};
+    bf4 h, m, l;
+    mx_split4(v, h, m, l);
+    __bf16 *dst = T3 + (int64_t)gc * ldt + base + gr;
+    *reinterpret_cast<bf4 *>(dst) = h;
+    *reinterpret_cast<bf4 *>(dst + plane_t) = m;
+    *reinterpret_cast<bf4 *>(dst + 2 * plane_t) = l;
+  }
+}
+
+int mx_chunks(int B) { return (B + kMxChunk - 1) / kMxChunk; }
+
+// workspace floats: part [4B] | closs [B] | cm [chunks B] | cs [chunks B]
+size_t mx_ws_bytes(int B) {
+  if (B < 1) return 0;
+  const size_t f = (size_t)B * (5 + 2 * (size_t)mx_chunks(B));
+  return (f * sizeof(float) + 255) / 256 * 256;
+}
+
+bool mult4(int64_t v) { return (v & 3) == 0; }
+
+// the arguments the statistics and the W launches share
+int mx_check(const char *who, const float *S, int64_t lds, const int32_t *ids, int B, int64_t neg_col, int64_t mem_col,
+             const int32_t *mem_id, int M, const float *bias, float lq_u, const float *mem_bias, float temperature,
+             const float *lse) {
+  CDML_REQUIRE(S && lse, CDML_E_BADARG, "%s: null pointer", who);
+  CDML_REQUIRE(B >= 4 && mult4(B), CDML_E_BADARG, "%s: B must be a positive multiple of 4, got %d", who, B);
+  CDML_REQUIRE(M >= 0 && mult4(M), CDML_E_BADARG, "%s: the memory size M must be 0 or a positive multiple of 4, got %d", who, M);
+  CDML_REQUIRE(!M || mem_id, CDML_E_BADARG, "%s: null pointer (M > 0 needs mem_id)", who);
+  CDML_REQUIRE(isfinite(temperature) && temperature > 0.f, CDML_E_BADARG, "%s: temperature must be finite and > 0, got %g",
+               who, (double)temperature);
+  CDML_REQUIRE(neg_col >= B && mult4(neg_col), CDML_E_BADARG, "%s: neg_col must be >= B (%d) and a multiple of 4, got %lld", who,
+               B, (long long)neg_col);
+  CDML_REQUIRE(!M || (mem_col >= neg_col + B && mult4(mem_col)), CDML_E_BADARG,
+               "%s: mem_col must be >= neg_col + B (%lld) and a multiple of 4, got %lld", who, (long long)(neg_col + B),
+               (long long)mem_col);
+  const int64_t span = M ? mem_col + M : neg_col + B;
+  CDML_REQUIRE(lds >= span && mult4(lds) && aligned16(S) && aligned16(lse) && aligned16(ids) && aligned16(mem_id), CDML_E_BADARG,
+               "%s: S, lse, ids and mem_id need 16-B aligned bases and lds >= %lld, a multiple of 4 (got %lld)", who,
+               (long long)span, (long long)lds);
+  if (bias) {
+    CDML_REQUIRE(aligned16(bias) && isfinite(lq_u), CDML_E_BADARG, "%s: bias needs a 16-B aligned base and lq_u must be finite (got %g)",
+                 who, (double)lq_u);
+    CDML_REQUIRE(!M || (mem_bias && aligned16(mem_bias)), CDML_E_BADARG,
+                 "%s: the corrected loss with a memory needs mem_bias (16-B aligned)", who);
+  }
+  return CDML_OK;
+}
+
+template <bool MEM, bool BIAS>
+int mx_stats_launch(const float *S, int64_t lds, const int32_t *ids, int B, int64_t neg_col, int64_t mem_col,
+                    const int32_t *mem_id, int M, const float *bias, float lq_u, const float *mem_bias, float temperature,
+                    int symmetric, float *lse, float *stats, void *workspace, cdml_stream_t stream) {
+  const float inv_t = 1.0f / temperature;
+  const int chunks = mx_chunks(B);
+  float *part = static_cast<float *>(workspace), *closs = part + 4 * (size_t)B;
+  float *cm = closs + B, *cs = cm + (size_t)chunks * B;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL((k_mixed_rows<MEM, BIAS>), dim3(B), dim3(kMxThreads), 0, st, S, lds, ids, B, inv_t, lse, part, neg_col,
+                     mem_col, mem_id, M, bias, lq_u, mem_bias);
+  if (int rc = check_launch("npair_mixed_stats rows")) return rc;
+  if (symmetric) {
+    const unsigned gx = (unsigned)((B + kMxThreads - 1) / kMxThreads);
+    hipLaunchKernelGGL(k_mixed_cols<BIAS>, dim3(gx, chunks), dim3(kMxThreads), 0, st, S, lds, ids, B, inv_t, cm, cs, bias);
+    if (int rc = check_launch("npair_mixed_stats columns")) return rc;
+    hipLaunchKernelGGL(k_mixed_col_fold<BIAS>, dim3(gx), dim3(kMxThreads), 0, st, S, lds, B, chunks, inv_t, cm, cs, lse, closs,
+                       bias);
+    if (int rc = check_launch("npair_mixed_stats column fold")) return rc;
+  }
+  hipLaunchKernelGGL(k_mixed_stats, dim3(1), dim3(1024), 0, st, part, closs, B, symmetric ? 1 : 0, M, stats);
+  return check_launch("npair_mixed_stats");
+}
+
+template <bool X3>
+int mx_w_launch(const char *who, const float *S, int64_t lds, const int32_t *ids, int B, int64_t neg_col, int64_t mem_col,
+                const int32_t *mem_id, int M, const float *bias, float lq_u, const float *mem_bias, float temperature,
+                int symmetric, const float *lse, void *W, int64_t ldw, int64_t plane, cdml_stream_t stream) {
+  const int64_t span = M ? mem_col + M : neg_col + B;
+  const dim3 grid((unsigned)B, (unsigned)((span + 4 * kMxThreads - 1) / (4 * kMxThreads)));
+  const float inv_t = 1.0f / temperature, scale = 1.0f / ((float)B * temperature);
+  const int sym = symmetric ? 1 : 0;
+  hipStream_t st = (hipStream_t)stream;
+#define CDML_MX_W(MEM, BIAS)                                                                                                   \
+  hipLaunchKernelGGL((k_mixed_w<X3, MEM, BIAS>), grid, dim3(kMxThreads), 0, st, S, lds, ids, B, neg_col, mem_col, mem_id, M,    \
+                     inv_t, sym, lse, scale, W, ldw, plane, bias, lq_u, mem_bias)
+  if (M && bias) {
+    CDML_MX_W(true, true);
+  } else if (M) {
+    CDML_MX_W(true, false);
+  } else if (bias) {
+    CDML_MX_W(false, true);
+  } else {
+    CDML_MX_W(false, false);
+  }
+#undef CDML_MX_W
+  return check_launch(who);
+}
+
+}  // namespace
+}  // namespace cdml
+
+using namespace cdml;
+
+extern "C" size_t cdml_npair_mixed_workspace(int B, int M) { return M >= 0 ? mx_ws_bytes(B) : 0; }
+
+extern "C" int cdml_npair_mixed_stats(const float *S, int64_t lds, const int32_t *ids, int B, int64_t neg_col, int64_t mem_col,
+                                      const int32_t *mem_id, int M, const float *bias, float lq_u, const float *mem_bias,
+                                      float temperature, int symmetric, float *lse, float *stats, void *workspace,
+                                      size_t workspace_bytes, cdml_stream_t stream) {
+  const char *who = "npair_mixed_stats";
+  if (int rc = mx_check(who, S, lds, ids, B, neg_col, mem_col, mem_id, M, bias, lq_u, mem_bias, temperature, lse)) return rc;
+  CDML_REQUIRE(stats && workspace, CDML_E_BADARG, "%s: null pointer", who);
+  CDML_REQUIRE(aligned16(workspace) && workspace_bytes >= mx_ws_bytes(B), CDML_E_BADARG,
+               "%s: the workspace must be 16-B aligned and hold cdml_npair_mixed_workspace(%d, %d) = %zu bytes (got %zu)", who, B,
+               M, mx_ws_bytes(B), workspace_bytes);
+  if (M) {
+    if (bias)
+      return mx_stats_launch<true, true>(S, lds, ids, B, neg_col, mem_col, mem_id, M, bias, lq_u, mem_bias, temperature,
+                                         symmetric, lse, stats, workspace, stream);
+    return mx_stats_launch<true, false>(S, lds, ids, B, neg_col, mem_col, mem_id, M, bias, lq_u, mem_bias, temperature, symmetric,
+                                        lse, stats, workspace, stream);
+  }
+  if (bias)
+    return mx_stats_launch<false, true>(S, lds, ids, B, neg_col, mem_col, mem_id, M, bias, lq_u, mem_bias, temperature, symmetric,
+                                        lse, stats, workspace, stream);
+  return mx_stats_launch<false, false>(S, lds, ids, B, neg_col, mem_col, mem_id, M, bias, lq_u, mem_bias, temperature, symmetric,
+                                       lse, stats, workspace, stream);
+}
+
+extern "C" int cdml_npair_mixed_grad_x3(const float *S, int64_t lds, const int32_t *ids, int B, int64_t neg_col,
+                                        int64_t mem_col, const int32_t *mem_id, int M, const float *bias, float lq_u,
+                                        const float *mem_bias, float temperature, int symmetric, const float *lse, uint16_t *W,
+                                        int64_t ldw, int64_t plane, cdml_stream_t stream) {
+  const char *who = "npair_mixed_grad_x3";
+  if (int rc = mx_check(who, S, lds, ids, B, neg_col, mem_col, mem_id, M, bias, lq_u, mem_bias, temperature, lse)) return rc;
+  const int64_t span = M ? mem_col + M : neg_col + B;
+  CDML_REQUIRE(W, CDML_E_BADARG, "%s: null pointer", who);
+  CDML_REQUIRE(plane >= span && ldw >= 2 * plane + span && mult4(plane) && mult4(ldw) && (reinterpret_cast<uintptr_t>(W) & 7) == 0,
+               CDML_E_BADARG,
+               "%s: W needs an 8-B aligned base, plane >= the column span (%lld) and ldw >= 2 plane + span, both multiples "
+               "of 4 (got plane %lld, ldw %lld)", who, (long long)span, (long long)plane, (long long)ldw);
+  return mx_w_launch<true>(who, S, lds, ids, B, neg_col, mem_col, mem_id, M, bias, lq_u, mem_bias, temperature, symmetric, lse, W,
+                           ldw, plane, stream);
+}
+
+extern "C" int cdml_npair_mixed_grad_f32(const float *S, int64_t lds, const int32_t *ids, int B, int64_t neg_col,
+                                         int64_t mem_col, const int32_t *mem_id, int M, const float *bias, float lq_u,
+                                         const float *mem_bias, float temperature, int symmetric, const float *lse, float *W,
+                                         int64_t ldw, cdml_stream_t stream) {
+  const char *who = "npair_mixed_grad_f32";
+  if (int rc = mx_check(who, S, lds, ids, B, neg_col, mem_col, mem_id, M, bias, lq_u, mem_bias, temperature, lse)) return rc;
+  const int64_t span = M ? mem_col + M : neg_col + B;
+  CDML_REQUIRE(W, CDML_E_BADARG, "%s: null pointer", who);
+  CDML_REQUIRE(ldw >= span && mult4(ldw) && aligned16(W), CDML_E_BADARG,
+               "%s: W needs a 16-B aligned base and ldw >= the column span (%lld), a multiple of 4 (got %lld)", who,
+               (long long)span, (long long)ldw);
+  return mx_w_launch<false>(who, S, lds, ids, B, neg_col, mem_col, mem_id, M, bias, lq_u, mem_bias, temperature, symmetric, lse,
+                            W, ldw, 0, stream);
+}
+
+extern "C" int cdml_npair_mixed_split_x3(const float *e, int64_t lde, int B, int D, uint16_t *A3, int64_t lda, int64_t plane_a,
+                                         uint16_t *R3, int64_t ldr, int64_t plane_r, uint16_t *T3, int64_t ldt,
+                                         int64_t plane_t, int64_t neg_row, cdml_stream_t stream) {
+  const char *who = "npair_mixed_split_x3";
+  CDML_REQUIRE(e && A3 && R3 && T3, CDML_E_BADARG, "%s: null pointer", who);
+  CDML_REQUIRE(B >= 4 && mult4(B) && D >= 4 && mult4(D), CDML_E_BADARG, "%s: B and D must be positive multiples of 4 (got %d, %d)",
+               who, B, D);
+  CDML_REQUIRE(lde >= D && mult4(lde) && aligned16(e), CDML_E_BADARG,
+               "%s: e needs a 16-B aligned base and lde >= D (%d), a multiple of 4 (got %lld)", who, D, (long long)lde);
+  CDML_REQUIRE(neg_row >= B && mult4(neg_row), CDML_E_BADARG, "%s: neg_row must be >= B (%d) and a multiple of 4, got %lld", who, B,
+               (long long)neg_row);
+  const auto al8 = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; };
+  CDML_REQUIRE(al8(A3) && al8(R3) && al8(T3) && mult4(lda) && mult4(plane_a) && mult4(ldr) && mult4(plane_r) && mult4(ldt) &&
+                   mult4(plane_t),
+               CDML_E_BADARG, "%s: the plane images need 8-B aligned bases, leading dimensions and plane strides multiples of 4", who);
+  CDML_REQUIRE(plane_a >= D && lda >= 2 * plane_a + D && plane_r >= D && ldr >= 2 * plane_r + D, CDML_E_BADARG,
+               "%s: row images need plane >= D (%d) and ld >= 2 plane + D (got A3 %lld / %lld, R3 %lld / %lld)", who, D,
+               (long long)plane_a, (long long)lda, (long long)plane_r, (long long)ldr);
+  CDML_REQUIRE(plane_t >= neg_row + B && ldt >= 2 * plane_t + neg_row + B, CDML_E_BADARG,
+               "%s: the transposed image needs plane_t >= neg_row + B (%lld) and ldt >= 2 plane_t + neg_row + B (got %lld / %lld)",
+               who, (long long)(neg_row + B), (long long)plane_t, (long long)ldt);
+  const dim3 grid((unsigned)((D + kMxTile - 1) / kMxTile), (unsigned)((B + kMxTile - 1) / kMxTile), 3);
+  hipLaunchKernelGGL(k_mixed_split, grid, dim3(kMxThreads), 0, (hipStream_t)stream, e, lde, B, D,
+                     reinterpret_cast<__bf16 *>(A3), lda, plane_a, reinterpret_cast<__bf16 *>(R3), ldr, plane_r,
+                     reinterpret_cast<__bf16 *>(T3), ldt, plane_t, neg_row);
+  return check_launch(who);
+}

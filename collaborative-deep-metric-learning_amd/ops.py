@@ -826,6 +826,248 @@ def _npair_memory_loss(e, rows, B, Dp, temperature, symmetric, precision, de, st
     return stats, lse
 
 
+# ---- mixed negative sampling for the N-pair loss (Yang et al. 2020; csrc/npair_mixed.hip, include/cdml_npair_mixed.h) ----
+def npair_mixed_workspace(B, M):
+    return int(load_library().cdml_npair_mixed_workspace(int(B), int(M)))
+
+
+def _mixed_args(S, rows3, B, neg_col, mem_col, mem_id, bias, lq_u, mem_bias, temperature, symmetric):
+    sp, sld = _mat(S)
+    return (sp, sld, _p(rows3, torch.int32), int(B), int(neg_col), int(mem_col), _p(mem_id, torch.int32),
+            0 if mem_id is None else mem_id.numel(), _p(bias, torch.float32), float(lq_u), _p(mem_bias, torch.float32),
+            float(temperature), 1 if symmetric else 0)
+
+
+def npair_mixed_stats(S, rows3, B, neg_col, mem_col, mem_id, bias, lq_u, mem_bias, temperature, symmetric, lse, stats,
+                      workspace):
+    """cdml_npair_mixed_stats: lse and stats[0..3] over S = A [P; N; Mem]^T (blocks at columns 0, neg_col, mem_col), the
+    ids rows3 int32 [3B] in the uniform sampler's layout (a, p, n per triplet) or None.  bias None: uncorrected."""
+    call("cdml_npair_mixed_stats", *_mixed_args(S, rows3, B, neg_col, mem_col, mem_id, bias, lq_u, mem_bias, temperature,
+                                                symmetric), _p(lse), _p(stats), _p(workspace),
+         workspace.numel() * workspace.element_size(), _stream())
+    return lse, stats
+
+
+def npair_mixed_grad_x3(S, rows3, B, neg_col, mem_col, mem_id, bias, lq_u, mem_bias, temperature, symmetric, lse, W_planes,
+                        plane):
+    """W_planes bf16 [>= B, >= 2 plane + span] <- the gradient weights of all blocks as three planes, one launch."""
+    wp, wld = _mat16(W_planes)
+    call("cdml_npair_mixed_grad_x3", *_mixed_args(S, rows3, B, neg_col, mem_col, mem_id, bias, lq_u, mem_bias, temperature,
+                                                  symmetric), _p(lse), wp, wld, int(plane), _stream())
+    return W_planes
+
+
+def npair_mixed_grad_f32(S, rows3, B, neg_col, mem_col, mem_id, bias, lq_u, mem_bias, temperature, symmetric, lse, W):
+    wp, wld = _mat(W)
+    call("cdml_npair_mixed_grad_f32", *_mixed_args(S, rows3, B, neg_col, mem_col, mem_id, bias, lq_u, mem_bias, temperature,
+                                                   symmetric), _p(lse), wp, wld, _stream())
+    return W
+
+
+def npair_mixed_split_x3(e3, B, D, A3, plane_a, R3, plane_r, T3, plane_t, neg_row):
+    """cdml_npair_mixed_split_x3: the plane images of A, P, N from the stride-3 rows of e3 fp32 [3B, >= D] -- A3 [B, ..],
+    the row image R3 (P at rows 0.., N at rows neg_row..) and the transposed image T3 (the same columns)."""
+    ep, eld = _mat(e3)
+    ap, ald = _mat16(A3)
+    rp, rld = _mat16(R3)
+    tp, tld = _mat16(T3)
+    call("cdml_npair_mixed_split_x3", ep, eld, int(B), int(D), ap, ald, int(plane_a), rp, rld, int(plane_r), tp, tld,
+         int(plane_t), int(neg_row), _stream())
+
+
+class _MixedRing(NPairMemory):
+    """The NPairMemory ring of an NPairMixed: the ring itself (``rows``, ``ids``, ``bias``; push slots, ``state_dict`` and
+    ``load`` are NPairMemory's) without NPairMemory's own S, W and [P; Mem] buffers -- the ring's operand images are the
+    last M rows / columns of the owner's [P; N; Mem] ones."""
+
+    def __init__(self, size, owner, device, start=0):
+        Bp, Dp, precision = owner.Bp, owner.Dp, owner.precision
+        M, tile = int(size), NPAIR_TILE[precision]
+        if M < 1 or M % Bp or M % tile:
+            raise ValueError("precision %r: the memory size must be a positive multiple of the batch (%d pairs) and of %d "
+                             "(got %d)" % (precision, Bp, tile, M))
+        if int(start) < 0:
+            raise ValueError("memory_start must be >= 0, got %r" % (start,))
+        self.M, self.Bp, self.Dp, self.precision, self.start = M, Bp, Dp, precision, int(start)
+        self.K = 2 * Bp + M
+        self.ids = torch.full((M,), -1, dtype=torch.int32, device=device)
+        self.bias = torch.zeros(M, dtype=torch.float32, device=device)
+        self.owner = owner
+        self.rows = None                                    # set by the owner (f32: a view of its [P; N; Mem] operand)
+
+    def load(self, rows, ids):
+        if tuple(rows.shape) != (self.M, self.Dp) or tuple(ids.shape) != (self.M,):
+            raise ValueError("a ring of %d rows x %d columns and %d ids, got %s and %s"
+                             % (self.M, self.Dp, self.M, tuple(rows.shape), tuple(ids.shape)))
+        self.rows.copy_(rows.to(device=self.rows.device, dtype=torch.float32))
+        self.ids.copy_(ids.to(device=self.ids.device, dtype=torch.int32))
+        if self.precision == "f32x3":
+            o = self.owner
+            split_f32_bf16x3(self.rows, o.R3[2 * self.Bp:], o.Dq)
+            split_f32_bf16x3(self.rows, o.T3[:, 2 * self.Bp:], o.K, transpose=True)
+
+    def W(self):
+        return self.owner.W()
+
+
+class NPairMixed:
+    """Every buffer of the N-pair chain with mixed negative sampling (``npair_mixed_loss``) for Bp triplets of Dp-wide rows,
+    allocated once (hipGraph-capturable): S fp32 [Bp, K] and W over the column set [P | N | Mem], K = 2 Bp + M, with the
+    uniform block at column ``neg_col`` = Bp and the memory block at ``mem_col`` = 2 Bp; the operand [P; N; Mem] -- f32x3:
+    its row planes ``R3`` [K, 3 Dq] and transposed planes ``T3`` [Dq, 3 K] (the batch's part written by the split launch,
+    the ring's by the push), and the anchors' planes ``A3``; f32: fp32 ``PNM`` [K, Dp].  ``memory_size`` > 0: ``ring``, an
+    NPairMemory ring of M positives (a multiple of Bp and of NPAIR_TILE[precision])."""
+
+    def __init__(self, Bp, Dp, precision, device, memory_size=0, memory_start=0):
+        if precision not in NPAIR_PRECISIONS:
+            raise ValueError("the N-pair loss runs on precision 'f32x3' or 'f32', not %r" % (precision,))
+        tile = NPAIR_TILE[precision]
+        if Bp < tile or Bp % tile:
+            raise ValueError("precision %r: the N-pair loss needs a batch that is a multiple of %d pairs (got %d)"
+                             % (precision, tile, Bp))
+        if Dp % 64:
+            raise ValueError("the N-pair loss needs an embedding width that is a multiple of 64 (got %d)" % Dp)
+        self.Bp, self.Dp, self.precision = int(Bp), int(Dp), precision
+        self.ring = _MixedRing(memory_size, self, device, memory_start) if int(memory_size) else None
+        self.M = M = self.ring.M if self.ring is not None else 0
+        self.K = K = 2 * self.Bp + M
+        self.neg_col, self.mem_col = self.Bp, 2 * self.Bp
+        f32 = lambda *s: torch.zeros(s, dtype=torch.float32, device=device)
+        bf = lambda *s: torch.zeros(s, dtype=torch.bfloat16, device=device)
+        self.S = f32(Bp, K)
+        self.lse = f32(2 * Bp)
+        self.bias = f32(2 * Bp)                              # logQ correction: lq(a_i), lq(p_i), the [2B] layout
+        self.rows2 = torch.zeros(2 * Bp, dtype=torch.int32, device=device)   # (a, p) ids for the ring push / the estimator
+        self.ws = torch.zeros(npair_mixed_workspace(Bp, M) // 4, dtype=torch.float32, device=device)
+        if precision == "f32x3":
+            self.Dq = Dq = (Dp + 255) // 256 * 256
+            self.A3 = bf(Bp, 3 * Dq)
+            self.R3, self.T3 = bf(K, 3 * Dq), bf(Dq, 3 * K)
+            self.W3 = bf(Bp, 3 * K)
+            nb = max(gemm_bf16x3_workspace(False, Bp, K, Dq), gemm_bf16x3_workspace(False, Bp, Dq, K),
+                     gemm_bf16x3_workspace(True, Bp, Dq, Bp), 16)
+            self.gemm_ws = torch.zeros(nb // 4, dtype=torch.float32, device=device)
+            self.dA, self.dP, self.dN = (f32(Bp, Dq), f32(Bp, Dq), f32(Bp, Dq)) if Dq != Dp else (None, None, None)
+            if self.ring is not None:
+                self.ring.rows = f32(M, Dp)
+        else:
+            self.PNM = f32(K, Dp)
+            self.Wf = f32(Bp, K)
+            self.zero_bias = f32(Dp)
+            self.bw = torch.zeros(max(fc_bwd_weight_workspace(Bp, Bp, Dp), 16) // 4, dtype=torch.float32, device=device)
+            if self.ring is not None:
+                self.ring.rows = self.PNM[2 * Bp:]
+
+    def W(self):
+        """the gradient weights as one fp32 tensor [Bp, 2 Bp + M] = [W_p | W_n | W_mem] (tests, debugging)"""
+        if self.precision == "f32":
+            return self.Wf
+        K = self.K
+        return self.W3[:, :K].float() + self.W3[:, K:2 * K].float() + self.W3[:, 2 * K:].float()
+
+
+def uniform_logq(logq, value=None):
+    """lq_u, the one log sampling probability of the uniform block: ``value`` when given (a finite float); else, for a
+    LogQEstimator, -log(g0) -- exactly the lq an unseen video has in the other blocks --, for a LogQTable (per-draw
+    shares) -log(n_videos); 0 without a correction."""
+    import math
+    if logq is None:
+        if value is not None:
+            raise ValueError("uniform_logq goes with a logQ correction (logq=...)")
+        return 0.0
+    if value is not None:
+        value = float(value)
+        if not math.isfinite(value):
+            raise ValueError("uniform_logq must be a finite float, got %r" % (value,))
+        return value
+    if isinstance(logq, LogQEstimator):
+        return -math.log(logq.init_gap)
+    return -math.log(logq.n_videos)
+
+
+def npair_mixed_loss(e3, rows3, B, Dp, temperature=0.1, symmetric=True, precision="f32x3", de=None, stats=None, ws=None,
+                     step=0, step_dev=None, logq=None, lq_u=0.0):
+    """The N-pair loss with mixed negative sampling (include/cdml_npair_mixed.h) of B triplets and its gradient.
+    e3: fp32 [3 B, >= Dp] unit rows in the uniform sampler's layout (row 3i = anchor, 3i+1 = positive, 3i+2 = uniform
+    negative); rows3: int32 [3 B] video ids laid out the same, or None (no ring, no correction).  The chain: the plane
+    split of A, P, N from the stride-3 rows -> S = A [P; N; Mem]^T -> statistics -> W (one launch) -> dA = W [P; N; Mem]
+    over K = 2 B + M into de[0::3], dP = W_p^T A into de[1::3], dN = W_n^T A into de[2::3] (de fp32 [3 B, Dp]; None: loss
+    only) -> with a ring, the push of the step's positives.  ws: an NPairMixed (B == ws.Bp).  logq: a LogQTable /
+    LogQEstimator (bias of the in-batch and memory blocks; an estimator is updated by the positives after W), or a fp32
+    tensor [2 B] of lq(a_i), lq(p_i) per pair (no ring), with the uniform block's scalar ``lq_u`` (``uniform_logq``).
+    Returns (stats, lse)."""
+    if not (temperature > 0.0) or temperature == float("inf"):
+        raise ValueError("temperature must be finite and > 0, got %r" % (temperature,))
+    if ws is None:
+        ws = NPairMixed(B, Dp, precision, e3.device)
+    if (ws.Bp, ws.Dp, ws.precision) != (B, Dp, precision) or e3.shape[0] != 3 * B:
+        raise ValueError("NPairMixed is for %d triplets x %d columns on %s and needs e3 of 3 B rows (unpadded)"
+                         % (ws.Bp, ws.Dp, ws.precision))
+    ring = ws.ring
+    row_logq = logq if isinstance(logq, torch.Tensor) else None
+    if row_logq is not None:
+        if ring is not None or row_logq.numel() != 2 * B:
+            raise ValueError("a per-row logQ tensor holds 2B = %d entries (a_i, p_i per pair) and has no memory part" % (2 * B))
+        logq = None
+    if rows3 is None and (ring is not None or logq is not None):
+        raise ValueError("the cross-batch memory and the logQ correction need the rows' video ids")
+    if logq is None and row_logq is None and lq_u:
+        raise ValueError("lq_u goes with a logQ correction (logq=...)")
+    if stats is None:
+        stats = torch.zeros(4, dtype=torch.float32, device=e3.device)
+    Bp, K, nc, mc = ws.Bp, ws.K, ws.neg_col, ws.mem_col
+    A, P, N = e3[0::3, :Dp], e3[1::3, :Dp], e3[2::3, :Dp]
+    mem_id = ring.ids if ring is not None else None
+    rows2 = None
+    if ring is not None or logq is not None:                # the ring push and the estimator take ids laid out [2B]: (a, p)
+        rows2 = ws.rows2
+        rows2.view(Bp, 2).copy_(rows3.view(Bp, 3)[:, :2])
+    bias = mem_bias = None
+    if logq is not None:                                    # (the gather reads the ring's ids before this step's push)
+        bias, mem_bias = ws.bias, (ring.bias if ring is not None else None)
+        logq.gather(rows2, B, mem_id, bias, mem_bias)
+    elif row_logq is not None:
+        bias = ws.bias
+        bias.copy_(row_logq.reshape(-1))
+    lse = ws.lse
+    if precision == "f32x3":
+        Dq = ws.Dq
+        npair_mixed_split_x3(e3, B, Dp, ws.A3, Dq, ws.R3, Dq, ws.T3, K, nc)
+        gemm_bf16x3_nt(BE_F32, ws.A3, Dq, ws.R3, Dq, ws.S, Bp, K, Dq, workspace=ws.gemm_ws)        # S = A [P; N; Mem]^T
+    else:
+        ws.PNM[:2 * Bp].view(2, Bp, Dp).copy_(e3.unflatten(0, (Bp, 3))[:, 1:, :Dp].transpose(0, 1))
+        fc_bwd_data(A, ws.PNM, None, ws.S, Bp, K, Dp)
+    npair_mixed_stats(ws.S, rows3, B, nc, mc, mem_id, bias, lq_u, mem_bias, temperature, symmetric, lse, stats, ws.ws)
+    if de is None:
+        return stats, lse
+    dA, dP, dN = de[0::3], de[1::3], de[2::3]
+    if precision == "f32x3":
+        npair_mixed_grad_x3(ws.S, rows3, B, nc, mc, mem_id, bias, lq_u, mem_bias, temperature, symmetric, lse, ws.W3, K)
+        if logq is not None:
+            logq.update(rows2, B, step, step_dev)
+        oA, oP, oN = (dA, dP, dN) if ws.dA is None else (ws.dA, ws.dP, ws.dN)
+        gemm_bf16x3_nt(BE_F32, ws.W3, K, ws.T3, K, oA, Bp, Dq, K, workspace=ws.gemm_ws)            # dA = W . [P; N; Mem]
+        gemm_bf16x3_tn(ws.W3, K, ws.A3, Dq, oP, Bp, Dq, Bp, workspace=ws.gemm_ws)                  # dP = W_p^T . A
+        gemm_bf16x3_tn(ws.W3[:, nc:], K, ws.A3, Dq, oN, Bp, Dq, Bp, workspace=ws.gemm_ws)          # dN = W_n^T . A
+        if ws.dA is not None:
+            dA.copy_(ws.dA[:, :Dp])
+            dP.copy_(ws.dP[:, :Dp])
+            dN.copy_(ws.dN[:, :Dp])
+        if ring is not None:
+            npair_memory_push(P, rows2, Bp, Dp, step, step_dev, ring.start, ring.rows, ring.ids, R3=ws.R3[mc:], plane_r=Dq,
+                              T3=ws.T3[:, mc:], plane_t=K)
+    else:
+        npair_mixed_grad_f32(ws.S, rows3, B, nc, mc, mem_id, bias, lq_u, mem_bias, temperature, symmetric, lse, ws.Wf)
+        if logq is not None:
+            logq.update(rows2, B, step, step_dev)
+        fc_lrelu_fwd(ws.Wf, ws.PNM, ws.zero_bias, dA, Bp, K, Dp, alpha=1.0)          # dA = W . [P; N; Mem]
+        fc_bwd_weight(ws.Wf[:, :Bp], A, dP, None, ws.bw, Bp, Bp, Dp)                 # dP = W_p^T . A
+        fc_bwd_weight(ws.Wf[:, nc:nc + Bp], A, dN, None, ws.bw, Bp, Bp, Dp)          # dN = W_n^T . A
+        if ring is not None:
+            npair_memory_push(P, rows2, Bp, Dp, step, step_dev, ring.start, ring.rows, ring.ids)
+    return stats, lse
+
+
 def pair_dist(e, pairs, D, sqdist, dot, means=None):
     ep, eld = _mat(e)
     call("cdml_pair_dist", ep, eld, e.shape[0], _p(pairs, torch.int32), pairs.shape[0], D, _p(sqdist),

@@ -48,7 +48,7 @@ class TrainStep:
                  prefetch=True, precision="auto", train_table=False, gather_ahead="auto",
                  clip_gradient_norm=0.0, regularization_penalty=0.0, l2_penalty=1e-8,
                  grad_sync_mode="bucketed", temperature=0.1, symmetric=True, memory_size=0, memory_start=0,
-                 logq=None, logq_alpha=0.01, logq_init_gap=None):
+                 logq=None, logq_alpha=0.01, logq_init_gap=None, uniform_negatives=False, uniform_logq=None):
         """table: FeatureTable (whole catalogue, or this rank's shard when
         ``exchange`` is given); pairs: int32 [P,2] device tensor; ``exchange`` /
         ``grad_sync``: the multi-GPU hooks of cdml_amd.dist (None on one GPU).
@@ -102,7 +102,14 @@ class TrainStep:
         step t, then the batch's positives update it; ``logq_alpha`` in (0, 1], default 0.01, and ``logq_init_gap`` >= 1,
         default max(1, n_videos / batch), both build-defined; its state is part of ``state_dict``); or a float tensor of
         one finite lq per catalogue row (ops.LogQTable: an argument, not checkpoint state).  ``sampling_logq()`` returns
-        the current per-video lq."""
+        the current per-video lq.
+        ``uniform_negatives`` (mode "npair"; default False): mixed negative sampling (Yang et al. 2020; build-defined) -- the
+        step samples like ``mode="uniform"`` (three rows per triplet: anchor, positive and a uniform catalogue negative
+        rejected against the pair) and every anchor's softmax runs over the in-batch positives, the batch's B uniform
+        negatives and the memory; the uniform negatives go through the tower and receive a gradient
+        (ops.npair_mixed_loss).  The memory still holds positives only.  ``uniform_logq`` (with ``logq``): the one log
+        sampling probability of the uniform block; None = -log(g0) of the streaming estimator (an unseen video's lq) or
+        -log(n_videos) with a fixed table."""
         if mode not in _MODES:
             raise ValueError("mode must be 'uniform', 'inbatch', 'semihard' or 'npair'")
         memory_size, memory_start = int(memory_size), int(memory_start)
@@ -128,6 +135,17 @@ class TrainStep:
                                      % (table.n_rows_global, tuple(logq.shape)))
                 if not logq.is_floating_point() or not bool(torch.isfinite(logq).all()):
                     raise ValueError("every entry of the logq table must be a finite float")
+        uniform_negatives = bool(uniform_negatives)
+        if uniform_negatives and mode != "npair":
+            raise ValueError("uniform_negatives goes with mode 'npair' (mixed negative sampling of its softmax), not %r" % (mode,))
+        if uniform_logq is not None:
+            if not uniform_negatives:
+                raise ValueError("uniform_logq goes with uniform_negatives=True (the uniform block's log sampling probability)")
+            if logq is None:
+                raise ValueError("uniform_logq goes with a logQ correction (logq=...): without one no logit is corrected")
+            uniform_logq = float(uniform_logq)
+            if not (float("-inf") < uniform_logq < float("inf")):
+                raise ValueError("uniform_logq must be a finite float, got %r" % (uniform_logq,))
         if mode == "npair":
             if exchange is not None or grad_sync is not None:
                 raise ValueError("mode 'npair' runs on one GPU: data parallelism (exchange / grad_sync) is not supported")
@@ -166,7 +184,10 @@ class TrainStep:
                                  % (lo, hi, table.n_rows_global))
         self.B = int(batch_size)
         self.mode = mode
-        self.rows_per_triplet = 3 if mode == "uniform" else 2
+        self.uniform_negatives = uniform_negatives
+        # (mode "npair" with uniform negatives samples like mode "uniform": a, p and a uniform catalogue negative)
+        self.sampler_mode = MODE_UNIFORM if uniform_negatives else _MODES[mode]
+        self.rows_per_triplet = 3 if self.sampler_mode == MODE_UNIFORM else 2
         self.R = self.B * self.rows_per_triplet
         self.margin = float(margin)
         self.temperature, self.symmetric = float(temperature), bool(symmetric)
@@ -266,7 +287,11 @@ class TrainStep:
             self.scale = torch.zeros(self.B, dtype=f32, device=dev)
         self.memory_size, self.memory_start = memory_size, memory_start
         self.npair_memory = None
-        if mode == "npair":                                  # S, W and the plane copies of the loss chain
+        self.npair_mixed = None
+        if uniform_negatives:                                # the mixed chain's S, W and [P; N; Mem] operands (and the ring)
+            self.npair_mixed = ops.NPairMixed(self.B, self.layout.Dp, precision, dev, memory_size, memory_start)
+            self.npair_memory = self.npair_mixed.ring
+        elif mode == "npair":                                # S, W and the plane copies of the loss chain
             # (with a cross-batch memory, the memory object holds the concatenated S, W and [P; Mem] operands)
             self.npair_ws = ops.NPairWorkspace(self.B, self.layout.Dp, precision, dev, in_batch=not memory_size)
             if memory_size:
@@ -275,6 +300,7 @@ class TrainStep:
         if logq is not None:
             self.npair_logq = (ops.LogQEstimator(table.n_rows_global, self.B, logq_alpha, logq_init_gap, dev) if logq_stream
                                else ops.LogQTable(logq, dev))
+        self.uniform_lq = ops.uniform_logq(self.npair_logq, uniform_logq) if uniform_negatives else 0.0
         self.step_dev = torch.zeros(1, dtype=torch.int64, device=dev)
         self.lr_dev = torch.full((1,), self.base_lr, dtype=f32, device=dev)
         self._lr_host = self.base_lr
@@ -429,7 +455,7 @@ class TrainStep:
         sd = None
         if self.device.type == "cuda" and torch.cuda.is_current_stream_capturing():
             step, sd = 1, self.step_dev
-        if _MODES[self.mode] == MODE_UNIFORM:
+        if self.sampler_mode == MODE_UNIFORM:
             ops.sample_uniform(self.pairs, self.table.n_rows_global, self.seed, step, self.B,
                                self._idx[b], slot0=self.slot0, batch_global=self.batch_global, step_dev=sd)
         else:
@@ -453,7 +479,7 @@ class TrainStep:
     def _gather_block(self, step=None):
         """Sample + gather the steps step .. step+gather_ahead-1 in one launch (step None: the
         device counter's value when the kernel runs)."""
-        ops.sample_gather(_MODES[self.mode], self.pairs, self.seed, step, self.B, self.table.data,
+        ops.sample_gather(self.sampler_mode, self.pairs, self.seed, step, self.B, self.table.data,
                           self.table.feature_size, self._idxa, self._xa, shift_out=self._shifta,
                           slot0=self.slot0, batch_global=self.batch_global,
                           step_dev=self.step_dev if step is None else None, n_steps=self.gather_ahead,
@@ -461,7 +487,7 @@ class TrainStep:
 
     def fetch(self):
         """Sampler + gather (+ input l2norm): fills ws.x_hat and self.idx."""
-        m = _MODES[self.mode]
+        m = self.sampler_mode
         if self.gather_ahead > 1:
             off = self._ahead_offset()
             if off == 0:
@@ -546,7 +572,12 @@ class TrainStep:
             self.ws.dz2_planes_done = self.x3 or self.h2
             return
         de = self.ws.de if with_grad else None
-        if self.mode == "npair":
+        if self.npair_mixed is not None:
+            # mixed negative sampling: the chain over [P | N | Mem] on the uniform sampler's rows, de[2::3] = dN included
+            ops.npair_mixed_loss(self.ws.e, self.idx, self.B, L.Dp, self.temperature, self.symmetric, self.precision, de=de,
+                                 stats=self.stats, ws=self.npair_mixed, step=0, step_dev=self.step_dev, logq=self.npair_logq,
+                                 lq_u=self.uniform_lq)
+        elif self.mode == "npair":
             # S = A P^T -> row / column log-sum-exp -> W -> dA = W P, dP = W^T A into de; tower_backward takes de from there
             # (cross-batch memory: the step number for the ring push is the device counter, which replays follow)
             # (logQ correction: the estimator's update takes the same device step number)
