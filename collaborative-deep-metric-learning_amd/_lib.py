@@ -212,6 +212,17 @@ SIGNATURES_MIXED = {
     "cdml_npair_mixed_split_x3": (_i, [_p, _i64, _i, _i, _p, _i64, _i64, _p, _i64, _i64, _p, _i64, _i64, _i64, _p]),
 }
 
+# name -> (restype, argtypes); must list every symbol include/cdml_npair_dp.h declares (the data-parallel N-pair loss)
+SIGNATURES_DP = {
+    "cdml_npair_dp_workspace": (_sz, [_i, _i]),
+    "cdml_npair_dp_local_stats": (_i, [_p, _i64, _p, _i, _i, _i, _f, _i, _p, _p, _p, _sz, _p]),
+    "cdml_npair_dp_col_fold": (_i, [_p, _i, _i, _p, _p]),
+    "cdml_npair_dp_stats": (_i, [_p, _i64, _i, _i, _i, _f, _i, _p, _p, _p, _sz, _p]),
+    "cdml_npair_dp_grad_x3": (_i, [_p, _i64, _p, _i, _i, _i, _f, _i, _p, _p, _p, _i64, _i64, _p]),
+    "cdml_npair_dp_grad_f32": (_i, [_p, _i64, _p, _i, _i, _i, _f, _i, _p, _p, _p, _i64, _p]),
+    "cdml_npair_dp_pos_fold": (_i, [_p, _i64, _i, _i, _i, _p, _i64, _p]),
+}
+
 _lib = None
 
 
@@ -230,7 +241,7 @@ def load_library():
     # its launches then fail with "no ROCm-capable device is detected".
     import torch  # noqa: F401
     lib = C.CDLL(path)
-    for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_MIXED.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_MIXED.items()) + list(SIGNATURES_DP.items()):
         fn = getattr(lib, name)          # AttributeError if the ABI lost a symbol
         fn.restype = res
         fn.argtypes = args

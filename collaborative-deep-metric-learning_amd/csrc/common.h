@@ -51,6 +51,15 @@ __device__ __forceinline__ float f16_chunk_sumsq(cdml_half8 &x, int q, int F, fl
   return ss;
 }
 
+// v = hi + mid + lo exactly, each a bf16: THE split of cdml_split_f32_bf16x3 (csrc/gemm_bf16x3.hip k_split3), shared by the
+// kernels that write operand planes themselves
+__device__ __forceinline__ void split3_bf16(float v, __bf16 &h, __bf16 &m, __bf16 &l) {
+  h = (__bf16)v;
+  const float r = v - (float)h;
+  m = (__bf16)r;
+  l = (__bf16)(r - (float)m);
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);

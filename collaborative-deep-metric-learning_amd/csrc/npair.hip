@@ -39,12 +39,7 @@ namespace {
 constexpr int kNpThreads = 256;
 constexpr int kNpChunk = 256;          // rows per block of the column pass
 
-__device__ __forceinline__ void np_split3(float v, __bf16 &h, __bf16 &m, __bf16 &l) {
-  h = (__bf16)v;
-  const float r = v - (float)h;
-  m = (__bf16)r;
-  l = (__bf16)(r - (float)m);
-}
+__device__ __forceinline__ void np_split3(float v, __bf16 &h, __bf16 &m, __bf16 &l) { split3_bf16(v, h, m, l); }
 
 // (m, s) <- the pair for the values summarised by (m, s) and by (m2, s2); an empty pair is (-inf, 0)
 __device__ __forceinline__ void lse_merge(float &m, float &s, float m2, float s2) {

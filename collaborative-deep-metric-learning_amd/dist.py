@@ -388,6 +388,56 @@ class GradSync:
         return flat_grad
 
 
+def all_gather(out, inp, group=None):
+    """Equal-split all-gather: rank r's ``inp`` lands in the r-th block of ``out`` (both contiguous, out.numel() = world x
+    inp.numel())."""
+    o, i = out.view(-1), inp.view(-1)
+    if inp.is_cuda and _host_staged(group):
+        h = torch.empty(o.shape, dtype=o.dtype)
+        dist.all_gather_into_tensor(h, i.cpu(), group=group)
+        o.copy_(h)
+    else:
+        if inp.is_cuda:
+            EagerCollectiveStreams.note()
+        dist.all_gather_into_tensor(o, i, group=group)
+    return out
+
+
+class NPairSync:
+    """The collectives of the data-parallel N-pair loss (ops.npair_dp_loss): the positives of every rank enter every
+    rank's softmax.  Per step: an all-gather of the positives' fp32 rows and video ids (rows cross the wire in fp32 and
+    are split into planes on arrival, as the row exchange does), an all-gather of the column statistics (8 G bytes per
+    rank; symmetric loss only) and an all-to-all that carries each rank's partial gradient of the positives back to their
+    owners (B Dp 4 bytes to each peer) -- an all-to-all plus a fixed-order sum kernel, not a reduce-scatter, so the
+    summation order is the build's own: the result does not depend on the backend and the replicas stay bit-identical.
+    Give it a group of its own (as RowExchange): collectives of one group run in issue order, and these must not
+    interleave with the prefetcher's exchange of the next step on one communicator.  Eager only (not captured into a
+    hipGraph).  ``skip_self``: a single rank copies its own blocks and issues no collective (False keeps the RCCL calls:
+    they then run even at world size 1)."""
+
+    def __init__(self, group=None, skip_self=True):
+        self.group = group
+        self.skip_self = bool(skip_self)
+        self.world = dist.get_world_size(group)
+        self.rank = dist.get_rank(group)
+
+    def _local(self):
+        return self.world == 1 and self.skip_self
+
+    def all_gather(self, out, inp):
+        if self._local():
+            out.view(-1).copy_(inp.view(-1))
+            return out
+        return all_gather(out, inp, self.group)
+
+    def all_to_all(self, out, inp):
+        if self._local():
+            out.view(-1).copy_(inp.view(-1))
+            return out
+        all_to_all(out.view(-1), inp.view(-1), self.group)
+        return out
+
+
 def reduce_input_flags(oob, overflow, group=None, world=None, extra=None):
     """The device-side input flags of ONE rank -- ``oob`` (int32[1]: a pair id outside the catalogue) and ``overflow``
     (RowExchange.overflow, int32[1] bit field: 1 = a peer segment overflowed, 2 = a requested id outside the catalogue;

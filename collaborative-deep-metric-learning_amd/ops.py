@@ -1068,6 +1068,247 @@ def npair_mixed_loss(e3, rows3, B, Dp, temperature=0.1, symmetric=True, precisio
     return stats, lse
 
 
+# ---- the data-parallel N-pair loss: one softmax over every rank's positives (csrc/npair_dp.hip, include/cdml_npair_dp.h) ----
+def npair_dp_workspace(B, G):
+    return int(load_library().cdml_npair_dp_workspace(int(B), int(G)))
+
+
+def npair_dp_local_stats(S, ids_all, B, G, col0, temperature, symmetric, lse_row, colpart, workspace):
+    """cdml_npair_dp_local_stats: lse_row [B] over all G columns of this rank's row block S [B, >= G], the rows' partials
+    into ``workspace`` (npair_dp_stats reads them) and, with ``symmetric``, colpart [G, 2] = every global column's (max,
+    sum-exp) over this rank's rows.  ids_all: int32 [2G], the global batch's ids laid out like npair_stats' rows."""
+    sp, sld = _mat(S)
+    call("cdml_npair_dp_local_stats", sp, sld, _p(ids_all, torch.int32), int(B), int(G), int(col0), float(temperature),
+         1 if symmetric else 0, _p(lse_row, torch.float32), _p(colpart if symmetric else None), _p(workspace),
+         workspace.numel() * workspace.element_size(), _stream())
+    return lse_row, colpart
+
+
+def npair_dp_col_fold(colpart_all, lse_col):
+    """cdml_npair_dp_col_fold: lse_col [G] from the gathered partials colpart_all [world, G, 2] (contiguous), the ranks
+    folded in the order 0 .. world - 1."""
+    if colpart_all.dim() != 3 or colpart_all.shape[2] != 2 or not colpart_all.is_contiguous():
+        raise ValueError("colpart_all must be a contiguous [world, G, 2] tensor")
+    world, G = colpart_all.shape[0], colpart_all.shape[1]
+    if lse_col.numel() < G:
+        raise ValueError("lse_col needs G = %d entries, got %d" % (G, lse_col.numel()))
+    call("cdml_npair_dp_col_fold", _p(colpart_all, torch.float32), int(world), int(G), _p(lse_col, torch.float32), _stream())
+    return lse_col
+
+
+def npair_dp_stats(S, B, G, col0, temperature, symmetric, lse_col, stats, workspace):
+    """cdml_npair_dp_stats: this rank's stats[0..3] from the partials npair_dp_local_stats left in ``workspace`` (and,
+    with ``symmetric``, the column term of the columns col0 .. col0 + B - 1 it owns)."""
+    sp, sld = _mat(S)
+    call("cdml_npair_dp_stats", sp, sld, int(B), int(G), int(col0), float(temperature), 1 if symmetric else 0,
+         _p(lse_col if symmetric else None), _p(stats, torch.float32), _p(workspace),
+         workspace.numel() * workspace.element_size(), _stream())
+    return stats
+
+
+def npair_dp_grad_x3(S, ids_all, B, G, col0, temperature, symmetric, lse_row, lse_col, W_planes, plane):
+    """W_planes bf16 [>= B, >= 2 plane + G] <- the three bf16 planes of this rank's gradient weights (cdml_npair_dp_grad_x3)."""
+    sp, sld = _mat(S)
+    wp, wld = _mat16(W_planes)
+    call("cdml_npair_dp_grad_x3", sp, sld, _p(ids_all, torch.int32), int(B), int(G), int(col0), float(temperature),
+         1 if symmetric else 0, _p(lse_row), _p(lse_col if symmetric else None), wp, wld, int(plane), _stream())
+    return W_planes
+
+
+def npair_dp_grad_f32(S, ids_all, B, G, col0, temperature, symmetric, lse_row, lse_col, W):
+    """W fp32 [>= B, >= G] <- this rank's gradient weights (cdml_npair_dp_grad_f32)."""
+    sp, sld = _mat(S)
+    wp, wld = _mat(W)
+    call("cdml_npair_dp_grad_f32", sp, sld, _p(ids_all, torch.int32), int(B), int(G), int(col0), float(temperature),
+         1 if symmetric else 0, _p(lse_row), _p(lse_col if symmetric else None), wp, wld, _stream())
+    return W
+
+
+def npair_dp_pos_fold(recv, B, D, de):
+    """de[2i + 1, :D] = recv[0, i] + recv[1, i] + ... (fp32, in rank order): recv [world, B, >= D] contiguous blocks of the
+    partial positive gradients, de fp32 [>= 2B, >= D] (cdml_npair_dp_pos_fold).  Rows 2i of de are not touched."""
+    if recv.dim() != 3 or recv.shape[1] != B or recv.stride(2) != 1 or recv.stride(0) != B * recv.stride(1):
+        raise ValueError("recv must be [world, B, >= D] with the ranks' blocks back to back")
+    if de.shape[0] < 2 * B:
+        raise ValueError("de needs 2B = %d rows, got %d" % (2 * B, de.shape[0]))
+    dp, dld = _mat(de)
+    call("cdml_npair_dp_pos_fold", _p(recv, torch.float32), recv.stride(1), recv.shape[0], int(B), int(D), dp, dld, _stream())
+    return de
+
+
+NPAIR_DP_WIRE_PAD = 4      # words behind a positive's fp32 row on the wire: its pair's two video ids (bits), two zero words
+
+
+class NPairDP:
+    """Every buffer of the data-parallel N-pair chain of one rank, allocated once: B local pairs against the G = world B
+    global positives, Dp-wide rows (B == Bp: no padding; B a multiple of NPAIR_TILE[precision], Dp of 64).
+    ``send`` [B, Dp + 4] / ``wire`` [G, Dp + 4]: the positives as they cross the wire (all-gather) -- the fp32 row, then the
+    pair's two video ids as bit patterns -- so rows and ids travel in ONE collective; ``ids_all`` int32 [2G] and the plane
+    images are derived on arrival.  ``colpart`` [G, 2] / ``colpart_all`` [world, G, 2]: the column statistics (all-gather).
+    ``dP_part`` [G, Dw] / ``recv`` [world, B, Dw]: this rank's partial gradient of every positive and the blocks it
+    receives for its own (all-to-all; Dw = Dp, on f32x3 the plane GEMMs' 256-column tile)."""
+
+    def __init__(self, B, G, Dp, precision, device):
+        if precision not in NPAIR_PRECISIONS:
+            raise ValueError("the N-pair loss runs on precision 'f32x3' or 'f32', not %r" % (precision,))
+        B, G, Dp = int(B), int(G), int(Dp)
+        tile = NPAIR_TILE[precision]
+        if B < tile or B % tile:
+            raise ValueError("precision %r: the data-parallel N-pair loss needs a local batch that is a multiple of %d pairs "
+                             "(got %d)" % (precision, tile, B))
+        if G < B or G % B:
+            raise ValueError("the global batch must be a multiple of the local batch (%d pairs), got %d" % (B, G))
+        if Dp % 64:
+            raise ValueError("the N-pair loss needs an embedding width that is a multiple of 64 (got %d)" % Dp)
+        # the GEMMs address an operand through one 2 GiB buffer descriptor: W_r's planes [B + a 256-row tile, 3 G] bf16 on
+        # f32x3, W_r [B, G] fp32 on f32 (at B = 8192: G <= 40 960 pairs on f32x3; a blocked gradient product is later work)
+        wbytes = (B + 256) * 3 * G * 2 if precision == "f32x3" else B * G * 4
+        if wbytes >= 1 << 31:
+            raise ValueError("precision %r: the gradient weights of %d x %d pairs exceed the GEMMs' 2 GiB operand range "
+                             "(use a smaller local batch or fewer ranks)" % (precision, B, G))
+        self.B, self.G, self.Dp, self.precision, self.world = B, G, Dp, precision, G // B
+        f32 = lambda *s: torch.zeros(s, dtype=torch.float32, device=device)
+        bf = lambda *s: torch.zeros(s, dtype=torch.bfloat16, device=device)
+        Dw = Dp + NPAIR_DP_WIRE_PAD
+        self.send, self.wire = f32(B, Dw), f32(G, Dw)
+        self.ids_all = torch.zeros(2 * G, dtype=torch.int32, device=device)
+        self.S = f32(B, G)
+        self.lse_row, self.lse_col = f32(B), f32(G)
+        self.colpart, self.colpart_all = f32(G, 2), f32(self.world, G, 2)
+        self.ws = torch.zeros(npair_dp_workspace(B, G) // 4, dtype=torch.float32, device=device)
+        if precision == "f32x3":
+            self.Dq = Dq = (Dp + 255) // 256 * 256          # the plane GEMMs' N tile: narrower rows are zero-padded
+            self.A3 = bf(B, 3 * Dq)
+            self.PA3, self.PAT3 = bf(G, 3 * Dq), bf(Dq, 3 * G)   # every rank's positives: row planes and transposed planes
+            self.W3 = bf(B, 3 * G)
+            nb = max(gemm_bf16x3_workspace(False, B, G, Dq), gemm_bf16x3_workspace(False, B, Dq, G),
+                     gemm_bf16x3_workspace(True, G, Dq, B), 16)
+            self.gemm_ws = torch.zeros(nb // 4, dtype=torch.float32, device=device)
+            self.dA = f32(B, Dq) if Dq != Dp else None
+            self.dP_part, self.recv = f32(G, Dq), f32(self.world, B, Dq)
+        else:
+            self.Wf = f32(B, G)
+            self.zero_bias = f32(Dp)
+            self.bw = torch.zeros(max(fc_bwd_weight_workspace(B, G, Dp), 16) // 4, dtype=torch.float32, device=device)
+            self.dP_part, self.recv = f32(G, Dp), f32(self.world, B, Dp)
+
+    def P_all(self):
+        """every rank's positives, fp32 [G, Dp] (a view of ``wire``)"""
+        return self.wire[:, :self.Dp]
+
+    def W(self):
+        """this rank's gradient weights as one fp32 tensor [B, G] (tests, debugging)"""
+        if self.precision == "f32":
+            return self.Wf
+        G = self.G
+        return self.W3[:, :G].float() + self.W3[:, G:2 * G].float() + self.W3[:, 2 * G:].float()
+
+
+def _npair_dp_args(e, B, ws, rank):
+    if e.shape[0] != 2 * B or B != ws.B:
+        raise ValueError("the data-parallel N-pair loss needs an unpadded batch: e must hold exactly 2 B = %d rows (got %d)"
+                         % (2 * ws.B, e.shape[0]))
+    if not 0 <= int(rank) < ws.world:
+        raise ValueError("rank %r outside the world of %d" % (rank, ws.world))
+    return int(rank) * B
+
+
+def npair_dp_pack(e, rows, ws):
+    """ws.send <- this rank's positives (rows 2i + 1 of e) and its pairs' video ids (rows int32 [2B]) in wire form."""
+    B, Dp = ws.B, ws.Dp
+    if rows is None:
+        raise ValueError("the data-parallel N-pair loss needs the rows' video ids")
+    ws.send[:, :Dp].copy_(e[1::2, :Dp])
+    ws.send.view(torch.int32)[:, Dp:Dp + 2].copy_(rows.view(B, 2))
+    return ws.send
+
+
+def npair_dp_phase1(e, rank, ws, temperature=0.1, symmetric=True):
+    """From this rank's embedded rows e [2B, Dp] and the gathered positives in ``ws.wire``: ws.ids_all, the operand planes,
+    S_r = A_r P_all^T, ws.lse_row and (symmetric) ws.colpart.  No communication."""
+    B, G, Dp = ws.B, ws.G, ws.Dp
+    col0 = _npair_dp_args(e, B, ws, rank)
+    ws.ids_all.view(G, 2).copy_(ws.wire.view(torch.int32)[:, Dp:Dp + 2])
+    A, P = e[0::2, :Dp], ws.P_all()
+    if ws.precision == "f32x3":
+        Dq = ws.Dq
+        split_f32_bf16x3(A, ws.A3, Dq)
+        split_f32_bf16x3(P, ws.PA3, Dq)
+        split_f32_bf16x3(P, ws.PAT3, G, transpose=True)
+        gemm_bf16x3_nt(BE_F32, ws.A3, Dq, ws.PA3, Dq, ws.S, B, G, Dq, workspace=ws.gemm_ws)
+    else:
+        fc_bwd_data(A, P, None, ws.S, B, G, Dp)                 # S[i][j] = <a_i, p_j>
+    npair_dp_local_stats(ws.S, ws.ids_all, B, G, col0, temperature, symmetric, ws.lse_row, ws.colpart, ws.ws)
+    return ws.lse_row, ws.colpart
+
+
+def npair_dp_phase2(e, rank, ws, temperature=0.1, symmetric=True, de=None, stats=None):
+    """From the gathered column partials in ``ws.colpart_all``: ws.lse_col, this rank's stats, and with ``de`` (fp32 [2B,
+    Dp]) W_r, dA = W_r P_all into rows 2i of de and the partial positive gradient ws.dP_part = W_r^T A_r [G, .].  No
+    communication."""
+    B, G, Dp = ws.B, ws.G, ws.Dp
+    col0 = _npair_dp_args(e, B, ws, rank)
+    if stats is None:
+        stats = torch.zeros(4, dtype=torch.float32, device=e.device)
+    if symmetric:
+        npair_dp_col_fold(ws.colpart_all, ws.lse_col)
+    npair_dp_stats(ws.S, B, G, col0, temperature, symmetric, ws.lse_col, stats, ws.ws)
+    if de is None:
+        return stats
+    A, dA = e[0::2, :Dp], de[0::2]
+    if ws.precision == "f32x3":
+        Dq = ws.Dq
+        npair_dp_grad_x3(ws.S, ws.ids_all, B, G, col0, temperature, symmetric, ws.lse_row, ws.lse_col, ws.W3, G)
+        oA = dA if ws.dA is None else ws.dA
+        gemm_bf16x3_nt(BE_F32, ws.W3, G, ws.PAT3, G, oA, B, Dq, G, workspace=ws.gemm_ws)             # dA = W . P_all
+        gemm_bf16x3_tn(ws.W3, G, ws.A3, Dq, ws.dP_part, G, Dq, B, workspace=ws.gemm_ws)              # W^T . A, all G rows
+        if ws.dA is not None:
+            dA.copy_(ws.dA[:, :Dp])
+    else:
+        npair_dp_grad_f32(ws.S, ws.ids_all, B, G, col0, temperature, symmetric, ws.lse_row, ws.lse_col, ws.Wf)
+        fc_lrelu_fwd(ws.Wf, ws.P_all(), ws.zero_bias, dA, B, G, Dp, alpha=1.0)
+        fc_bwd_weight(ws.Wf, A, ws.dP_part, None, ws.bw, B, G, Dp)
+    return stats
+
+
+def npair_dp_phase3(ws, de):
+    """rows 2i + 1 of de <- the received partial positive gradients ``ws.recv`` summed in rank order.  No communication."""
+    return npair_dp_pos_fold(ws.recv, ws.B, ws.Dp, de)
+
+
+def npair_dp_loss(e, rows, B, Dp, temperature=0.1, symmetric=True, precision="f32x3", de=None, stats=None, ws=None, sync=None):
+    """The N-pair loss of the GLOBAL batch -- ``sync.world`` ranks of B pairs, one softmax over all of their positives --
+    and this rank's part of its gradient (include/cdml_npair_dp.h).  e: this rank's fp32 [2B, Dp] unit rows (B == Bp, no
+    padding), rows: its int32 [2B] video ids; sync: a dist.NPairSync.  Three phases with the hook's collectives between
+    them: all-gather of the positives' rows + ids -> S_r, row statistics, column partials -> (symmetric) all-gather of the
+    column partials -> column fold, stats, W_r, dA, partial dP -> (with ``de``) all-to-all of the dP blocks -> their
+    rank-order sum into de[1::2].  W_r carries 1 / (B t): averaging the ranks' parameter gradients (GradSync) gives the
+    global mean's.  stats[0] is this rank's share (the mean over the ranks is the global loss).  Returns (stats, lse_row
+    [B], lse_col [G])."""
+    if sync is None:
+        raise ValueError("npair_dp_loss needs the NPairSync hook that carries the positives between the ranks")
+    if not (temperature > 0.0) or temperature == float("inf"):
+        raise ValueError("temperature must be finite and > 0, got %r" % (temperature,))
+    G = int(B) * sync.world
+    if ws is None:
+        ws = NPairDP(B, G, Dp, precision, e.device)
+    elif (ws.B, ws.G, ws.Dp, ws.precision) != (B, G, Dp, precision):
+        raise ValueError("NPairDP is for %d of %d pairs x %d columns on %s" % (ws.B, ws.G, ws.Dp, ws.precision))
+    if stats is None:
+        stats = torch.zeros(4, dtype=torch.float32, device=e.device)
+    _npair_dp_args(e, B, ws, sync.rank)
+    npair_dp_pack(e, rows, ws)
+    sync.all_gather(ws.wire, ws.send)
+    npair_dp_phase1(e, sync.rank, ws, temperature, symmetric)
+    if symmetric:
+        sync.all_gather(ws.colpart_all, ws.colpart)
+    npair_dp_phase2(e, sync.rank, ws, temperature, symmetric, de=de, stats=stats)
+    if de is not None:
+        sync.all_to_all(ws.recv, ws.dP_part)
+        npair_dp_phase3(ws, de)
+    return stats, ws.lse_row, ws.lse_col
+
+
 def pair_dist(e, pairs, D, sqdist, dot, means=None):
     ep, eld = _mat(e)
     call("cdml_pair_dist", ep, eld, e.shape[0], _p(pairs, torch.int32), pairs.shape[0], D, _p(sqdist),

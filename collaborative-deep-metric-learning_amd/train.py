@@ -48,7 +48,8 @@ class TrainStep:
                  prefetch=True, precision="auto", train_table=False, gather_ahead="auto",
                  clip_gradient_norm=0.0, regularization_penalty=0.0, l2_penalty=1e-8,
                  grad_sync_mode="bucketed", temperature=0.1, symmetric=True, memory_size=0, memory_start=0,
-                 logq=None, logq_alpha=0.01, logq_init_gap=None, uniform_negatives=False, uniform_logq=None):
+                 logq=None, logq_alpha=0.01, logq_init_gap=None, uniform_negatives=False, uniform_logq=None,
+                 npair_sync=None):
         """table: FeatureTable (whole catalogue, or this rank's shard when
         ``exchange`` is given); pairs: int32 [P,2] device tensor; ``exchange`` /
         ``grad_sync``: the multi-GPU hooks of cdml_amd.dist (None on one GPU).
@@ -109,9 +110,33 @@ class TrainStep:
         negatives and the memory; the uniform negatives go through the tower and receive a gradient
         (ops.npair_mixed_loss).  The memory still holds positives only.  ``uniform_logq`` (with ``logq``): the one log
         sampling probability of the uniform block; None = -log(g0) of the streaming estimator (an unseen video's lq) or
-        -log(n_videos) with a fixed table."""
+        -log(n_videos) with a fixed table.
+        ``npair_sync`` (mode "npair"; a dist.NPairSync): the data-parallel N-pair loss -- ONE softmax over the positives of
+        every rank ("global negatives"), equal to the single-rank step on the global batch (ops.npair_dp_loss).  With it
+        ``exchange`` / ``grad_sync`` are accepted: this rank samples its slice (``slot0`` = rank x batch, ``batch_global`` =
+        world x batch), the positives' rows and ids are all-gathered, the column statistics folded across the ranks in a
+        fixed order, and the positives' partial gradients return to their owners through an all-to-all; the gradient weights
+        carry the local mean's 1 / (B t), so ``grad_sync``'s average gives the global mean's.  ``loss()`` is this rank's
+        share: the mean over the ranks is the global-batch loss.  Steps eagerly (``use_graph`` is ignored with a warning);
+        not with ``memory_size``, ``logq``, ``uniform_negatives`` or ``train_table``.  Limit: this rank's gradient weights
+        [batch x world batch] must fit the GEMMs' 2 GiB operand range (f32x3: (batch + 256) x 3 world batch bf16 -- at
+        batch 8192 at most 5 ranks, 8 ranks at batch <= 6400); ops.NPairDP raises a ValueError beyond it."""
         if mode not in _MODES:
             raise ValueError("mode must be 'uniform', 'inbatch', 'semihard' or 'npair'")
+        if npair_sync is not None:
+            if mode != "npair":
+                raise ValueError("npair_sync goes with mode 'npair' (it carries the positives of its softmax between the ranks), "
+                                 "not %r" % (mode,))
+            for name, on in (("memory_size", int(memory_size) != 0), ("logq", logq is not None),
+                             ("uniform_negatives", bool(uniform_negatives)), ("train_table", bool(train_table))):
+                if on:
+                    raise ValueError("npair_sync does not go with %s yet: the data-parallel N-pair loss is the plain in-batch "
+                                     "softmax over every rank's positives" % name)
+            bg = int(batch_size) if batch_global is None else int(batch_global)
+            if bg != int(batch_size) * npair_sync.world or int(slot0) != npair_sync.rank * int(batch_size):
+                raise ValueError("npair_sync over %d ranks needs batch_global = world x batch = %d and slot0 = rank x batch = %d "
+                                 "(got %d and %d)" % (npair_sync.world, int(batch_size) * npair_sync.world,
+                                                      npair_sync.rank * int(batch_size), bg, int(slot0)))
         memory_size, memory_start = int(memory_size), int(memory_start)
         if memory_size and mode != "npair":
             raise ValueError("memory_size > 0 goes with mode 'npair' (the cross-batch memory of its softmax), not %r" % (mode,))
@@ -147,8 +172,9 @@ class TrainStep:
             if not (float("-inf") < uniform_logq < float("inf")):
                 raise ValueError("uniform_logq must be a finite float, got %r" % (uniform_logq,))
         if mode == "npair":
-            if exchange is not None or grad_sync is not None:
-                raise ValueError("mode 'npair' runs on one GPU: data parallelism (exchange / grad_sync) is not supported")
+            if (exchange is not None or grad_sync is not None) and npair_sync is None:
+                raise ValueError("mode 'npair' runs on one GPU unless npair_sync (dist.NPairSync) carries its positives between "
+                                 "the ranks")
             if train_table:
                 raise ValueError("mode 'npair' does not train the catalogue (train_table=True is not supported)")
             if precision in ("auto", None) and table.data.dtype != torch.float16:
@@ -286,11 +312,14 @@ class TrainStep:
             self.neg_row = torch.zeros(self.B, dtype=i32, device=dev)
             self.scale = torch.zeros(self.B, dtype=f32, device=dev)
         self.memory_size, self.memory_start = memory_size, memory_start
+        self.npair_sync, self.npair_dp = npair_sync, None
         self.npair_memory = None
         self.npair_mixed = None
         if uniform_negatives:                                # the mixed chain's S, W and [P; N; Mem] operands (and the ring)
             self.npair_mixed = ops.NPairMixed(self.B, self.layout.Dp, precision, dev, memory_size, memory_start)
             self.npair_memory = self.npair_mixed.ring
+        elif mode == "npair" and npair_sync is not None:     # the data-parallel chain: this rank's rows x every rank's positives
+            self.npair_dp = ops.NPairDP(self.B, self.B * npair_sync.world, self.layout.Dp, precision, dev)
         elif mode == "npair":                                # S, W and the plane copies of the loss chain
             # (with a cross-batch memory, the memory object holds the concatenated S, W and [P; Mem] operands)
             self.npair_ws = ops.NPairWorkspace(self.B, self.layout.Dp, precision, dev, in_batch=not memory_size)
@@ -370,6 +399,10 @@ class TrainStep:
         # the data-parallel step is enqueue-only too (fixed-capacity exchange, no host counts), so
         # it captures like the single-GPU one: one graph per prefetch buffer
         self.use_graph = "split" if use_graph == "split" else bool(use_graph)
+        if self.use_graph and npair_sync is not None:
+            self.use_graph = False                       # its three collectives are not captured
+            logging.getLogger("cdml.train").warning(
+                "use_graph ignored: the data-parallel N-pair loss (npair_sync) steps eagerly")
         if self.use_graph and self.train_table and exchange is not None:
             self.use_graph = False                       # scatter_back sizes its scratch on the fly
             logging.getLogger("cdml.train").warning("use_graph ignored: trainable sharded table runs eagerly")
@@ -577,6 +610,15 @@ class TrainStep:
             ops.npair_mixed_loss(self.ws.e, self.idx, self.B, L.Dp, self.temperature, self.symmetric, self.precision, de=de,
                                  stats=self.stats, ws=self.npair_mixed, step=0, step_dev=self.step_dev, logq=self.npair_logq,
                                  lq_u=self.uniform_lq)
+        elif self.npair_dp is not None:
+            # the global batch's softmax: all-gather of the positives -> S_r, statistics -> all-gather of the column partials
+            # -> W_r, dA, partial dP -> all-to-all -> the positives' gradient, summed in rank order (ops.npair_dp_loss)
+            if self.prefetch is not None:
+                # the exchange of step t+1 has run under the tower's forward GEMMs; the loss's collectives start once it is
+                # through, so the two communicators never run side by side (as for the gradient all-reduce below)
+                self.prefetch.wait_ready(1 - self.global_step % 2)
+            ops.npair_dp_loss(self.ws.e, self.idx, self.B, L.Dp, self.temperature, self.symmetric, self.precision, de=de,
+                              stats=self.stats, ws=self.npair_dp, sync=self.npair_sync)
         elif self.mode == "npair":
             # S = A P^T -> row / column log-sum-exp -> W -> dA = W P, dP = W^T A into de; tower_backward takes de from there
             # (cross-batch memory: the step number for the ring push is the device counter, which replays follow)
