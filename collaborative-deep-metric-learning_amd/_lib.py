@@ -223,6 +223,17 @@ SIGNATURES_DP = {
     "cdml_npair_dp_pos_fold": (_i, [_p, _i64, _i, _i, _i, _p, _i64, _p]),
 }
 
+# name -> (restype, argtypes); must list every symbol include/cdml_npair_bf16.h declares (the N-pair loss on the config-4
+# precision: one-plane bf16 operands and gradient weights)
+SIGNATURES_BF16 = {
+    "cdml_npair_operands_bf16": (_i, [_p, _i64, _i, _i, _p, _i64, _p, _i64, _p, _i64, _p]),
+    "cdml_npair_grad_bf16": (_i, [_p, _i64, _p, _i, _f, _i, _p, _p, _i64, _p]),
+    "cdml_npair_logq_grad_bf16": (_i, [_p, _i64, _p, _i, _p, _f, _i, _p, _p, _i64, _p]),
+    "cdml_npair_memory_grad_bf16": (_i, [_p, _i64, _p, _i, _i64, _p, _i, _f, _i, _p, _p, _i64, _p]),
+    "cdml_npair_memory_logq_grad_bf16": (_i, [_p, _i64, _p, _i, _i64, _p, _p, _i, _f, _i, _p, _p, _i64, _p]),
+    "cdml_npair_memory_push_bf16": (_i, [_p, _i64, _p, _i, _i, _u64, _p, _i64, _i, _p, _i64, _p, _p, _i64, _p, _i64, _p]),
+}
+
 _lib = None
 
 
@@ -241,7 +252,8 @@ def load_library():
     # its launches then fail with "no ROCm-capable device is detected".
     import torch  # noqa: F401
     lib = C.CDLL(path)
-    for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_MIXED.items()) + list(SIGNATURES_DP.items()):
+    for name, (res, args) in (list(SIGNATURES.items()) + list(SIGNATURES_MIXED.items()) + list(SIGNATURES_DP.items())
+                               + list(SIGNATURES_BF16.items())):
         fn = getattr(lib, name)          # AttributeError if the ABI lost a symbol
         fn.restype = res
         fn.argtypes = args

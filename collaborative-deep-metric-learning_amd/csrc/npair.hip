@@ -15,13 +15,14 @@
 //                     online (max, sum-exp) per column and chunk
 //   k_npair_col_fold  one lane per column folds the chunks in order -> lse'_j and the column's loss term
 //   k_npair_stats     one block: the step scalars from the per-row partials in a fixed order (as k_loss_stats does)
-//   k_npair_w<X3>     W, four columns per lane, as three exact bf16 planes [B][hi | mid | lo] (the operand layout of the
-//                     plane GEMMs, split as cdml_split_f32_bf16x3 splits) or as fp32 (precision "f32")
+//   k_npair_w<FMT>    W, four columns per lane, as three exact bf16 planes [B][hi | mid | lo] (the operand layout of the
+//                     plane GEMMs, split as cdml_split_f32_bf16x3 splits), as fp32 (precision "f32") or as ONE bf16 plane,
+//                     the round-to-nearest-even of that fp32 value (precision "bf16": include/cdml_npair_bf16.h)
 //
 // Cross-batch memory (cdml_npair_memory_*): S = A [P; Mem]^T is [B][B + M], the memory's M columns at mem_col.  The row term
 // also counts slot k when mem_id[k] >= 0 is neither id(a_i) nor id(p_i); the column term stays over the in-batch block.
 //   k_npair_rows<true>   the row pass going on over the memory columns (float4 / int4 per lane)
-//   k_npair_mem_w<X3>    W's memory block, c_ik exp(S_ik / t - lse_i) / (B t) (halved with `symmetric`)
+//   k_npair_mem_w<FMT>   W's memory block, c_ik exp(S_ik / t - lse_i) / (B t) (halved with `symmetric`)
 //   k_npair_mem_push<X3> the ring push of the step's positives (after the products that read the memory), fp32 rows + ids,
 //                        and for X3 the slots' row-plane and transposed-plane operand images
 //
@@ -31,6 +32,7 @@
 // lq(a_i), bias[2i + 1] = lq(p_i) (laid out like ids) and mem_bias[k]: the BIAS instantiations of the kernels below; the
 // BIAS = false ones are the arithmetic of the uncorrected loss.  csrc/npair_logq.hip fills the vectors.
 #include "common.h"
+#include "../../include/cdml_npair_bf16.h"
 #include <math.h>
 
 namespace cdml {
@@ -38,6 +40,8 @@ namespace {
 
 constexpr int kNpThreads = 256;
 constexpr int kNpChunk = 256;          // rows per block of the column pass
+// what k_npair_w / k_npair_mem_w store: fp32, three exact bf16 planes, or one bf16 plane (the rounded fp32 value)
+enum : int { kWF32 = 0, kWX3 = 1, kWBf16 = 2 };
 
 __device__ __forceinline__ void np_split3(float v, __bf16 &h, __bf16 &m, __bf16 &l) { split3_bf16(v, h, m, l); }
 
@@ -261,7 +265,7 @@ __device__ __forceinline__ float npair_w(const int32_t *ids, int i, int j, int i
 }
 
 // row i = blockIdx.x, columns 4 (blockIdx.y * kNpThreads + threadIdx.x) .. + 3; columns >= B are not written
-template <bool X3, bool BIAS>
+template <int FMT, bool BIAS>
 __global__ void __launch_bounds__(kNpThreads)
 k_npair_w(const float *__restrict__ S, int64_t lds, const int32_t *__restrict__ ids, int B, float inv_t, int symmetric,
           const float *__restrict__ lse, float scale, void *__restrict__ Wout, int64_t ldw, int64_t plane,
@@ -293,7 +297,7 @@ k_npair_w(const float *__restrict__ S, int64_t lds, const int32_t *__restrict__ 
                           : 0.f;
   }
   const int n = min(4, B - j0);
-  if (X3) {
+  if constexpr (FMT == kWX3) {
     using bf4 = __attribute__((ext_vector_type(4))) __bf16;
     bf4 h, m, l;
     for (int q = 0; q < 4; ++q) {
@@ -315,6 +319,15 @@ k_npair_w(const float *__restrict__ S, int64_t lds, const int32_t *__restrict__ 
         dst[2 * plane + q] = l[q];
       }
     }
+  } else if constexpr (FMT == kWBf16) {
+    using bf4 = __attribute__((ext_vector_type(4))) __bf16;
+    bf4 r;
+    for (int q = 0; q < 4; ++q) r[q] = (__bf16)w[q];
+    __bf16 *dst = static_cast<__bf16 *>(Wout) + (int64_t)i * ldw + j0;
+    if (n == 4)
+      *reinterpret_cast<bf4 *>(dst) = r;
+    else
+      for (int q = 0; q < n; ++q) dst[q] = r[q];
   } else {
     float *dst = static_cast<float *>(Wout) + (int64_t)i * ldw + j0;
     if (n == 4)
@@ -327,7 +340,7 @@ k_npair_w(const float *__restrict__ S, int64_t lds, const int32_t *__restrict__ 
 // The memory block of W: W[i][mem_col + k] = c_ik exp(S[i][mem_col + k] / t - lse_i) * scale (scale = 1 / (B t), halved
 // with `symmetric`: the column term has no memory part).  Row i = blockIdx.x, slots 4 (blockIdx.y * kNpThreads +
 // threadIdx.x) .. + 3 (M a multiple of 4).  BIAS: slot k's logit less mem_bias[k]
-template <bool X3, bool BIAS>
+template <int FMT, bool BIAS>
 __global__ void __launch_bounds__(kNpThreads)
 k_npair_mem_w(const float *__restrict__ S, int64_t lds, int64_t mem_col, const int32_t *__restrict__ ids,
               const int32_t *__restrict__ mem_id, int M, float inv_t, const float *__restrict__ lse, float scale,
@@ -352,7 +365,7 @@ k_npair_mem_w(const float *__restrict__ S, int64_t lds, int64_t mem_col, const i
     w[2] = mem_counts(ids, q.z, ida, idp) ? expf(v.z * inv_t - lr) * scale : 0.f;
     w[3] = mem_counts(ids, q.w, ida, idp) ? expf(v.w * inv_t - lr) * scale : 0.f;
   }
-  if (X3) {
+  if constexpr (FMT == kWX3) {
     using bf4 = __attribute__((ext_vector_type(4))) __bf16;
     bf4 h, m, l;
     for (int c = 0; c < 4; ++c) {
@@ -366,6 +379,11 @@ k_npair_mem_w(const float *__restrict__ S, int64_t lds, int64_t mem_col, const i
     *reinterpret_cast<bf4 *>(dst) = h;
     *reinterpret_cast<bf4 *>(dst + plane) = m;
     *reinterpret_cast<bf4 *>(dst + 2 * plane) = l;
+  } else if constexpr (FMT == kWBf16) {
+    using bf4 = __attribute__((ext_vector_type(4))) __bf16;
+    bf4 r;
+    for (int c = 0; c < 4; ++c) r[c] = (__bf16)w[c];
+    *reinterpret_cast<bf4 *>(static_cast<__bf16 *>(Wout) + (int64_t)i * ldw + mem_col + k0) = r;
   } else {
     *reinterpret_cast<float4 *>(static_cast<float *>(Wout) + (int64_t)i * ldw + mem_col + k0) =
         make_float4(w[0], w[1], w[2], w[3]);
@@ -493,11 +511,11 @@ int np_w_f32_check(const char *who, int B, const float *W, int64_t ldw) {
   return CDML_OK;
 }
 
-template <bool X3, bool BIAS>
+template <int FMT, bool BIAS>
 int np_w_launch(const char *who, const float *S, int64_t lds, const int32_t *ids, int B, const float *bias, float temperature,
                 int symmetric, const float *lse, void *W, int64_t ldw, int64_t plane, cdml_stream_t stream) {
   const dim3 grid((unsigned)B, (unsigned)((B + 4 * kNpThreads - 1) / (4 * kNpThreads)));
-  hipLaunchKernelGGL((k_npair_w<X3, BIAS>), grid, dim3(kNpThreads), 0, (hipStream_t)stream, S, lds, ids, B, 1.0f / temperature,
+  hipLaunchKernelGGL((k_npair_w<FMT, BIAS>), grid, dim3(kNpThreads), 0, (hipStream_t)stream, S, lds, ids, B, 1.0f / temperature,
                      symmetric ? 1 : 0, lse, 1.0f / ((float)B * temperature), W, ldw, plane, bias);
   return check_launch(who);
 }
@@ -520,14 +538,14 @@ extern "C" int cdml_npair_grad_x3(const float *S, int64_t lds, const int32_t *id
                                   const float *lse, uint16_t *W, int64_t ldw, int64_t plane, cdml_stream_t stream) {
   if (int rc = np_check("npair_grad_x3", S, lds, B, temperature, lse)) return rc;
   if (int rc = np_w_x3_check("npair_grad_x3", B, W, ldw, plane)) return rc;
-  return np_w_launch<true, false>("npair_grad_x3", S, lds, ids, B, nullptr, temperature, symmetric, lse, W, ldw, plane, stream);
+  return np_w_launch<kWX3, false>("npair_grad_x3", S, lds, ids, B, nullptr, temperature, symmetric, lse, W, ldw, plane, stream);
 }
 
 extern "C" int cdml_npair_grad_f32(const float *S, int64_t lds, const int32_t *ids, int B, float temperature, int symmetric,
                                    const float *lse, float *W, int64_t ldw, cdml_stream_t stream) {
   if (int rc = np_check("npair_grad_f32", S, lds, B, temperature, lse)) return rc;
   if (int rc = np_w_f32_check("npair_grad_f32", B, W, ldw)) return rc;
-  return np_w_launch<false, false>("npair_grad_f32", S, lds, ids, B, nullptr, temperature, symmetric, lse, W, ldw, 0, stream);
+  return np_w_launch<kWF32, false>("npair_grad_f32", S, lds, ids, B, nullptr, temperature, symmetric, lse, W, ldw, 0, stream);
 }
 
 // ---- the sampling-bias (logQ) corrected loss: bias[2B] per row as ids, laid out by csrc/npair_logq.hip ------------------
@@ -547,7 +565,7 @@ extern "C" int cdml_npair_logq_grad_x3(const float *S, int64_t lds, const int32_
   if (int rc = np_check("npair_logq_grad_x3", S, lds, B, temperature, lse)) return rc;
   if (int rc = np_bias_check("npair_logq_grad_x3", bias)) return rc;
   if (int rc = np_w_x3_check("npair_logq_grad_x3", B, W, ldw, plane)) return rc;
-  return np_w_launch<true, true>("npair_logq_grad_x3", S, lds, ids, B, bias, temperature, symmetric, lse, W, ldw, plane,
+  return np_w_launch<kWX3, true>("npair_logq_grad_x3", S, lds, ids, B, bias, temperature, symmetric, lse, W, ldw, plane,
                                  stream);
 }
 
@@ -557,7 +575,7 @@ extern "C" int cdml_npair_logq_grad_f32(const float *S, int64_t lds, const int32
   if (int rc = np_check("npair_logq_grad_f32", S, lds, B, temperature, lse)) return rc;
   if (int rc = np_bias_check("npair_logq_grad_f32", bias)) return rc;
   if (int rc = np_w_f32_check("npair_logq_grad_f32", B, W, ldw)) return rc;
-  return np_w_launch<false, true>("npair_logq_grad_f32", S, lds, ids, B, bias, temperature, symmetric, lse, W, ldw, 0, stream);
+  return np_w_launch<kWF32, true>("npair_logq_grad_f32", S, lds, ids, B, bias, temperature, symmetric, lse, W, ldw, 0, stream);
 }
 
 // ---- cross-batch memory (XBM, Wang et al. 2020): a ring of M earlier positives as extra row-term columns of S ----------
@@ -603,13 +621,13 @@ int npm_w_f32_check(const char *who, int64_t mem_col, int M, const float *W, int
   return CDML_OK;
 }
 
-template <bool X3, bool BIAS>
+template <int FMT, bool BIAS>
 int npm_w_launch(const char *who, const float *S, int64_t lds, const int32_t *ids, int B, int64_t mem_col,
                  const int32_t *mem_id, const float *mem_bias, int M, float temperature, int symmetric, const float *lse,
                  void *W, int64_t ldw, int64_t plane, cdml_stream_t stream) {
   const dim3 grid((unsigned)B, (unsigned)((M + 4 * kNpThreads - 1) / (4 * kNpThreads)));
   const float scale = (symmetric ? 0.5f : 1.0f) / ((float)B * temperature);
-  hipLaunchKernelGGL((k_npair_mem_w<X3, BIAS>), grid, dim3(kNpThreads), 0, (hipStream_t)stream, S, lds, mem_col, ids, mem_id, M,
+  hipLaunchKernelGGL((k_npair_mem_w<FMT, BIAS>), grid, dim3(kNpThreads), 0, (hipStream_t)stream, S, lds, mem_col, ids, mem_id, M,
                      1.0f / temperature, lse, scale, W, ldw, plane, mem_bias);
   return check_launch(who);
 }
@@ -632,7 +650,7 @@ extern "C" int cdml_npair_memory_grad_x3(const float *S, int64_t lds, const int3
                                          uint16_t *W, int64_t ldw, int64_t plane, cdml_stream_t stream) {
   if (int rc = npm_check("npair_memory_grad_x3", S, lds, B, mem_col, mem_id, M, temperature, lse)) return rc;
   if (int rc = npm_w_x3_check("npair_memory_grad_x3", mem_col, M, W, ldw, plane)) return rc;
-  return npm_w_launch<true, false>("npair_memory_grad_x3", S, lds, ids, B, mem_col, mem_id, nullptr, M, temperature, symmetric,
+  return npm_w_launch<kWX3, false>("npair_memory_grad_x3", S, lds, ids, B, mem_col, mem_id, nullptr, M, temperature, symmetric,
                                    lse, W, ldw, plane, stream);
 }
 
@@ -641,7 +659,7 @@ extern "C" int cdml_npair_memory_grad_f32(const float *S, int64_t lds, const int
                                           float *W, int64_t ldw, cdml_stream_t stream) {
   if (int rc = npm_check("npair_memory_grad_f32", S, lds, B, mem_col, mem_id, M, temperature, lse)) return rc;
   if (int rc = npm_w_f32_check("npair_memory_grad_f32", mem_col, M, W, ldw)) return rc;
-  return npm_w_launch<false, false>("npair_memory_grad_f32", S, lds, ids, B, mem_col, mem_id, nullptr, M, temperature,
+  return npm_w_launch<kWF32, false>("npair_memory_grad_f32", S, lds, ids, B, mem_col, mem_id, nullptr, M, temperature,
                                     symmetric, lse, W, ldw, 0, stream);
 }
 
@@ -663,7 +681,7 @@ extern "C" int cdml_npair_memory_logq_grad_x3(const float *S, int64_t lds, const
   if (int rc = npm_check("npair_memory_logq_grad_x3", S, lds, B, mem_col, mem_id, M, temperature, lse)) return rc;
   if (int rc = npm_mem_bias_check("npair_memory_logq_grad_x3", mem_bias)) return rc;
   if (int rc = npm_w_x3_check("npair_memory_logq_grad_x3", mem_col, M, W, ldw, plane)) return rc;
-  return npm_w_launch<true, true>("npair_memory_logq_grad_x3", S, lds, ids, B, mem_col, mem_id, mem_bias, M, temperature,
+  return npm_w_launch<kWX3, true>("npair_memory_logq_grad_x3", S, lds, ids, B, mem_col, mem_id, mem_bias, M, temperature,
                                   symmetric, lse, W, ldw, plane, stream);
 }
 
@@ -673,7 +691,7 @@ extern "C" int cdml_npair_memory_logq_grad_f32(const float *S, int64_t lds, cons
   if (int rc = npm_check("npair_memory_logq_grad_f32", S, lds, B, mem_col, mem_id, M, temperature, lse)) return rc;
   if (int rc = npm_mem_bias_check("npair_memory_logq_grad_f32", mem_bias)) return rc;
   if (int rc = npm_w_f32_check("npair_memory_logq_grad_f32", mem_col, M, W, ldw)) return rc;
-  return npm_w_launch<false, true>("npair_memory_logq_grad_f32", S, lds, ids, B, mem_col, mem_id, mem_bias, M, temperature,
+  return npm_w_launch<kWF32, true>("npair_memory_logq_grad_f32", S, lds, ids, B, mem_col, mem_id, mem_bias, M, temperature,
                                    symmetric, lse, W, ldw, 0, stream);
 }
 
@@ -700,4 +718,58 @@ extern "C" int cdml_npair_memory_push(const float *P, int64_t ldp, const int32_t
     hipLaunchKernelGGL(k_npair_mem_push<false>, grid, dim3(kNpThreads), 0, st, P, ldp, ids, B, D, step, step_dev, start, M, mem,
                        ldm, mem_id, (__bf16 *)nullptr, (int64_t)0, (int64_t)0, (__bf16 *)nullptr, (int64_t)0, (int64_t)0);
   return check_launch("npair_memory_push");
+}
+
+// ---- precision "bf16" (include/cdml_npair_bf16.h): W as ONE bf16 plane, the round-to-nearest-even of the fp32 value the
+// _f32 entry points write -- the kWBf16 format of k_npair_w / k_npair_mem_w.  (The operand images and the ring push of that
+// precision are csrc/npair_bf16.hip.) ----------------------------------------------------------------------------------
+
+namespace cdml {
+namespace {
+
+int np_w_bf16_check(const char *who, int64_t span, const uint16_t *W, int64_t ldw) {
+  CDML_REQUIRE(W, CDML_E_BADARG, "%s: null pointer", who);
+  CDML_REQUIRE(ldw >= span && (ldw & 3) == 0 && (reinterpret_cast<uintptr_t>(W) & 7) == 0, CDML_E_BADARG,
+               "%s: W needs an 8-B aligned base and ldw >= %lld, a multiple of 4 (got %lld)", who, (long long)span,
+               (long long)ldw);
+  return CDML_OK;
+}
+
+}  // namespace
+}  // namespace cdml
+
+extern "C" int cdml_npair_grad_bf16(const float *S, int64_t lds, const int32_t *ids, int B, float temperature, int symmetric,
+                                    const float *lse, uint16_t *W, int64_t ldw, cdml_stream_t stream) {
+  if (int rc = np_check("npair_grad_bf16", S, lds, B, temperature, lse)) return rc;
+  if (int rc = np_w_bf16_check("npair_grad_bf16", B, W, ldw)) return rc;
+  return np_w_launch<kWBf16, false>("npair_grad_bf16", S, lds, ids, B, nullptr, temperature, symmetric, lse, W, ldw, 0, stream);
+}
+
+extern "C" int cdml_npair_logq_grad_bf16(const float *S, int64_t lds, const int32_t *ids, int B, const float *bias,
+                                         float temperature, int symmetric, const float *lse, uint16_t *W, int64_t ldw,
+                                         cdml_stream_t stream) {
+  if (int rc = np_check("npair_logq_grad_bf16", S, lds, B, temperature, lse)) return rc;
+  if (int rc = np_bias_check("npair_logq_grad_bf16", bias)) return rc;
+  if (int rc = np_w_bf16_check("npair_logq_grad_bf16", B, W, ldw)) return rc;
+  return np_w_launch<kWBf16, true>("npair_logq_grad_bf16", S, lds, ids, B, bias, temperature, symmetric, lse, W, ldw, 0, stream);
+}
+
+extern "C" int cdml_npair_memory_grad_bf16(const float *S, int64_t lds, const int32_t *ids, int B, int64_t mem_col,
+                                           const int32_t *mem_id, int M, float temperature, int symmetric, const float *lse,
+                                           uint16_t *W, int64_t ldw, cdml_stream_t stream) {
+  if (int rc = npm_check("npair_memory_grad_bf16", S, lds, B, mem_col, mem_id, M, temperature, lse)) return rc;
+  if (int rc = np_w_bf16_check("npair_memory_grad_bf16", mem_col + M, W, ldw)) return rc;
+  return npm_w_launch<kWBf16, false>("npair_memory_grad_bf16", S, lds, ids, B, mem_col, mem_id, nullptr, M, temperature,
+                                     symmetric, lse, W, ldw, 0, stream);
+}
+
+extern "C" int cdml_npair_memory_logq_grad_bf16(const float *S, int64_t lds, const int32_t *ids, int B, int64_t mem_col,
+                                                const int32_t *mem_id, const float *mem_bias, int M, float temperature,
+                                                int symmetric, const float *lse, uint16_t *W, int64_t ldw,
+                                                cdml_stream_t stream) {
+  if (int rc = npm_check("npair_memory_logq_grad_bf16", S, lds, B, mem_col, mem_id, M, temperature, lse)) return rc;
+  if (int rc = npm_mem_bias_check("npair_memory_logq_grad_bf16", mem_bias)) return rc;
+  if (int rc = np_w_bf16_check("npair_memory_logq_grad_bf16", mem_col + M, W, ldw)) return rc;
+  return npm_w_launch<kWBf16, true>("npair_memory_logq_grad_bf16", S, lds, ids, B, mem_col, mem_id, mem_bias, M, temperature,
+                                    symmetric, lse, W, ldw, 0, stream);
 }

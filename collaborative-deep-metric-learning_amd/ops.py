@@ -312,10 +312,14 @@ def triplet_hinge_indexed(e, neg_row, B, D, margin, pos, neg, hinge, scale_scrat
 
 
 # ---- multi-class N-pair loss (in-batch softmax, csrc/npair.hip; build-defined) ----
-NPAIR_PRECISIONS = ("f32x3", "f32")
+NPAIR_PRECISIONS = ("f32x3", "f32", "bf16")
+# (the mixed-negatives and data-parallel chains have no one-plane form yet: NPairMixed / NPairDP)
+NPAIR_FP32_PRECISIONS = ("f32x3", "f32")
 # pairs per batch must be a multiple of: f32x3 -- the plane GEMMs' 256 x 256 tiles (S is B x B, the two gradient products
-# contract over B); f32 -- the fp32 GEMMs' 64-wide K tiles (fc_bwd_data / fc_bwd_weight contract over B)
-NPAIR_TILE = {"f32x3": 256, "f32": 64}
+# contract over B); f32 -- the fp32 GEMMs' 64-wide K tiles (fc_bwd_data / fc_bwd_weight contract over B); bf16 -- the bf16
+# GEMMs' 256 x 256 tiles (dP = W^T A on gemm_bf16_tn: M and N multiples of 256, K of 128)
+NPAIR_TILE = {"f32x3": 256, "f32": 64, "bf16": 256}
+_NPAIR_PRECISION_MSG = "the N-pair loss runs on precision 'f32x3', 'f32' or 'bf16', not %r"
 
 
 def npair_workspace(B):
@@ -349,6 +353,66 @@ def npair_grad_f32(S, rows, B, temperature, symmetric, lse, W):
     return W
 
 
+# ---- the config-4 precision (fp16 catalogue, bf16 MFMA): one bf16 plane of every operand and of W (csrc/npair_bf16.hip,
+# include/cdml_npair_bf16.h) ----
+def npair_operands_bf16(e, B, D, A, P, PT):
+    """cdml_npair_operands_bf16: A, P bf16 [>= B, >= D] <- the rounded rows e[0::2] / e[1::2] (e fp32 [>= 2B, >= D]) and
+    PT bf16 [>= D, >= B] <- P^T, in one launch; nothing else of the three images is written."""
+    ep, eld = _mat(e)
+    ap, ald = _mat16(A)
+    pp, pld = _mat16(P)
+    tp, tld = _mat16(PT)
+    call("cdml_npair_operands_bf16", ep, eld, int(B), int(D), ap, ald, pp, pld, tp, tld, _stream())
+
+
+def npair_grad_bf16(S, rows, B, temperature, symmetric, lse, W, bias=None):
+    """W bf16 [>= B, >= B] <- the gradient weights npair_grad_f32 (bias: npair_logq_grad_f32) writes, rounded to nearest even."""
+    sp, sld = _mat(S)
+    wp, wld = _mat16(W)
+    if bias is None:
+        call("cdml_npair_grad_bf16", sp, sld, _p(rows, torch.int32), int(B), float(temperature), 1 if symmetric else 0,
+             _p(lse), wp, wld, _stream())
+    else:
+        call("cdml_npair_logq_grad_bf16", sp, sld, _p(rows, torch.int32), int(B), _p(bias, torch.float32), float(temperature),
+             1 if symmetric else 0, _p(lse), wp, wld, _stream())
+    return W
+
+
+def npair_memory_grad_bf16(S, rows, B, mem_col, mem_id, temperature, symmetric, lse, W, mem_bias=None):
+    """W's memory block (columns mem_col .. mem_col + M - 1) <- npair_memory_grad_f32's (mem_bias: _logq_grad_f32's) values,
+    rounded to nearest even."""
+    sp, sld = _mat(S)
+    wp, wld = _mat16(W)
+    if mem_bias is None:
+        call("cdml_npair_memory_grad_bf16", sp, sld, _p(rows, torch.int32), int(B), int(mem_col), _p(mem_id, torch.int32),
+             mem_id.numel(), float(temperature), 1 if symmetric else 0, _p(lse), wp, wld, _stream())
+    else:
+        call("cdml_npair_memory_logq_grad_bf16", sp, sld, _p(rows, torch.int32), int(B), int(mem_col), _p(mem_id, torch.int32),
+             _p(mem_bias, torch.float32), mem_id.numel(), float(temperature), 1 if symmetric else 0, _p(lse), wp, wld,
+             _stream())
+    return W
+
+
+def npair_memory_push_bf16(P, rows, B, D, step, step_dev, start, mem, mem_id, R, T):
+    """cdml_npair_memory_push_bf16: npair_memory_push with the slots' one-plane images R bf16 [M, >= D], T bf16 [>= D, >= M]."""
+    pp, pld = _mat(P)
+    mp, mld = _mat(mem)
+    rp, rld = _mat16(R)
+    tp, tld = _mat16(T)
+    call("cdml_npair_memory_push_bf16", pp, pld, _p(rows, torch.int32), int(B), int(D), 0 if step is None else int(step),
+         _p(step_dev, torch.int64), int(start), mem_id.numel(), mp, mld, _p(mem_id, torch.int32), rp, rld, tp, tld, _stream())
+
+
+def _npair_bf16_gemm_ws(Bp, K, Dq, device):
+    """The split-K workspace of the chain's three bf16 products: S = A [P; Mem]^T (Bp x K over Dq), dA = W [P; Mem]
+    (Bp x Dq over K), dP = W^T A (Bp x Dq over Bp)."""
+    if not gemm_bf16_tn_supported(Bp, Dq, Bp, K, Dq):
+        raise ValueError("precision 'bf16': dP = W^T A (%d x %d over %d, W's leading dimension %d) does not fit gemm_bf16_tn"
+                         % (Bp, Dq, Bp, K))
+    nb = max(gemm_bf16_workspace(Bp, K, Dq), gemm_bf16_workspace(Bp, Dq, K), gemm_bf16_tn_workspace(Bp, Dq, Bp), 16)
+    return torch.zeros(nb // 4, dtype=torch.float32, device=device)
+
+
 class NPairWorkspace:
     """Every buffer of the N-pair chain for Bp pairs of Dp-wide rows (Bp a multiple of NPAIR_TILE[precision]), allocated
     once: ``npair_loss`` then allocates nothing (hipGraph-capturable).  Pad rows and columns of W stay zero.
@@ -357,7 +421,7 @@ class NPairWorkspace:
 
     def __init__(self, Bp, Dp, precision, device, in_batch=True):
         if precision not in NPAIR_PRECISIONS:
-            raise ValueError("the N-pair loss runs on precision 'f32x3' or 'f32', not %r" % (precision,))
+            raise ValueError(_NPAIR_PRECISION_MSG % (precision,))
         tile = NPAIR_TILE[precision]
         if Bp < tile or Bp % tile:
             raise ValueError("precision %r: the N-pair loss needs a batch that is a multiple of %d pairs (got %d)"
@@ -383,6 +447,16 @@ class NPairWorkspace:
                 self.gemm_ws = torch.zeros(nb // 4, dtype=torch.float32, device=device)
             self.dA = f32(Bp, Dq) if Dq != Dp else None     # (rows narrower than the tile: the products land here first)
             self.dP = f32(Bp, Dq) if Dq != Dp else None
+        elif precision == "bf16":                           # one bf16 plane of every operand (include/cdml_npair_bf16.h)
+            self.Dq = Dq = (Dp + 255) // 256 * 256          # gemm_bf16_tn's N tile: narrower rows are zero-padded
+            self.A16 = bf(Bp, Dq)
+            if in_batch:
+                self.P16 = bf(Bp, Dq)
+                self.PT16 = bf(Dq, Bp)                      # the positives transposed: dA = W . P's k-contiguous operand
+                self.W16 = bf(Bp, Bp)
+                self.gemm_ws = _npair_bf16_gemm_ws(Bp, Bp, Dq, device)
+            self.dA = f32(Bp, Dq) if Dq != Dp else None
+            self.dP = f32(Bp, Dq) if Dq != Dp else None
         else:
             self.Wf = f32(Bp, Bp) if in_batch else None
             self.zero_bias = f32(Dp)
@@ -392,6 +466,8 @@ class NPairWorkspace:
         """the gradient weights as one fp32 tensor [Bp, Bp] (tests, debugging)"""
         if self.precision == "f32":
             return self.Wf
+        if self.precision == "bf16":
+            return self.W16.float()
         Bp = self.Bp
         return self.W3[:, :Bp].float() + self.W3[:, Bp:2 * Bp].float() + self.W3[:, 2 * Bp:].float()
 
@@ -451,7 +527,7 @@ class NPairMemory:
 
     def __init__(self, size, Bp, Dp, precision, device, start=0):
         if precision not in NPAIR_PRECISIONS:
-            raise ValueError("the N-pair loss runs on precision 'f32x3' or 'f32', not %r" % (precision,))
+            raise ValueError(_NPAIR_PRECISION_MSG % (precision,))
         M, tile = int(size), NPAIR_TILE[precision]
         if M < 1 or M % int(Bp) or M % tile:
             raise ValueError("precision %r: the memory size must be a positive multiple of the batch (%d pairs) and of %d "
@@ -473,6 +549,12 @@ class NPairMemory:
             nb = max(gemm_bf16x3_workspace(False, Bp, K, Dq), gemm_bf16x3_workspace(False, Bp, Dq, K),
                      gemm_bf16x3_workspace(True, Bp, Dq, Bp), 16)
             self.gemm_ws = torch.zeros(nb // 4, dtype=torch.float32, device=device)
+        elif precision == "bf16":                           # [P; Mem] and its transpose in one bf16 plane each
+            self.Dq = Dq = (Dp + 255) // 256 * 256
+            self.rows = f32(M, Dp)
+            self.PM16, self.PMT16 = bf(K, Dq), bf(Dq, K)
+            self.W16 = bf(Bp, K)
+            self.gemm_ws = _npair_bf16_gemm_ws(Bp, K, Dq, device)
         else:
             self.PM = f32(K, Dp)
             self.rows = self.PM[Bp:]
@@ -480,7 +562,8 @@ class NPairMemory:
 
     def load(self, rows, ids):
         """Set the ring: rows fp32 [M, Dp], ids int [M] (-1 = empty); the f32x3 planes are re-derived (hi + mid + lo is
-        exactly the fp32 value, so they are the bits the pushes would have written)."""
+        exactly the fp32 value, so they are the bits the pushes would have written), and so are the bf16 images (the
+        round-to-nearest-even of the fp32 rows, as the push writes them)."""
         if tuple(rows.shape) != (self.M, self.Dp) or tuple(ids.shape) != (self.M,):
             raise ValueError("a ring of %d rows x %d columns and %d ids, got %s and %s"
                              % (self.M, self.Dp, self.M, tuple(rows.shape), tuple(ids.shape)))
@@ -489,6 +572,9 @@ class NPairMemory:
         if self.precision == "f32x3":
             split_f32_bf16x3(self.rows, self.PM3[self.Bp:], self.Dq)
             split_f32_bf16x3(self.rows, self.PMT3[:, self.Bp:], self.K, transpose=True)
+        elif self.precision == "bf16":
+            cast_f32_bf16(self.rows, self.PM16[self.Bp:], self.M, self.Dp)
+            transpose_to_bf16(self.rows, self.PMT16[:, self.Bp:], self.M, self.Dp)
 
     def clear(self):
         self.load(torch.zeros_like(self.rows), torch.full_like(self.ids, -1))
@@ -497,6 +583,8 @@ class NPairMemory:
         """the gradient weights as one fp32 tensor [Bp, Bp + M] (tests, debugging)"""
         if self.precision == "f32":
             return self.Wf
+        if self.precision == "bf16":
+            return self.W16.float()
         K = self.K
         return self.W3[:, :K].float() + self.W3[:, K:2 * K].float() + self.W3[:, 2 * K:].float()
 
@@ -662,7 +750,9 @@ def npair_loss(e, rows, B, Dp, temperature=0.1, symmetric=True, precision="f32x3
     e: fp32 [2 Bp, Dp] unit rows, row 2i = anchor i, row 2i+1 = positive i (rows >= 2B zero: padding); rows: int32 [2 Bp]
     video ids or None.  The chain: S = A P^T -> row (and column) log-sum-exp + step scalars -> W -> dA = W P, dP = W^T A,
     written into de[0::2] / de[1::2] (fp32 [2 Bp, Dp]; None: loss only).  Precision "f32x3": fp32 operands as three
-    bf16 planes on the plane GEMMs; "f32": the fp32-MFMA GEMMs.  stats: fp32 [>= 4] (loss, mean positive distance,
+    bf16 planes on the plane GEMMs; "f32": the fp32-MFMA GEMMs; "bf16": the config-4 precision -- the rows rounded to ONE
+    bf16 plane, W in one bf16 plane, each product one pass of the bf16 GEMMs with fp32 accumulation (S, the statistics and
+    the gradient stay fp32; the same chain with a memory and with logQ: _npair_bf16_loss).  stats: fp32 [>= 4] (loss, mean positive distance,
     mean counted-negative distance, fraction of counted negatives).  ws: an NPairWorkspace (allocated here if None).
     memory: an NPairMemory (B == Bp, video ids given): its ring adds M negatives to every anchor's row term -- S = A [P;
     Mem]^T -> statistics -> W (the in-batch block + the memory block) -> dA = W [P; Mem] over K = Bp + M, dP = W^T A ->
@@ -693,8 +783,10 @@ def npair_loss(e, rows, B, Dp, temperature=0.1, symmetric=True, precision="f32x3
                 raise ValueError("a per-row logQ tensor needs 2B = %d entries, got %d" % (2 * B, logq.numel()))
         elif rows is None:
             raise ValueError("the logQ correction needs the rows' video ids")
-        if memory is None:
+        if memory is None and precision != "bf16":
             return _npair_logq_loss(e, rows, B, Dp, temperature, symmetric, precision, de, stats, ws, logq, step, step_dev)
+    if precision == "bf16":
+        return _npair_bf16_loss(e, rows, B, Dp, temperature, symmetric, de, stats, ws, memory, step, step_dev, logq)
     if memory is not None:
         return _npair_memory_loss(e, rows, B, Dp, temperature, symmetric, precision, de, stats, ws, memory, step, step_dev,
                                   logq)
@@ -725,6 +817,62 @@ def npair_loss(e, rows, B, Dp, temperature=0.1, symmetric=True, precision="f32x3
         npair_grad_f32(ws.S, rows, B, temperature, symmetric, lse, ws.Wf)
         fc_lrelu_fwd(ws.Wf, P, ws.zero_bias, dA, Bp, Bp, Dp, alpha=1.0)      # dA = W . P (x W form, identity activation)
         fc_bwd_weight(ws.Wf, A, dP, None, ws.bw, Bp, Bp, Dp)                 # dP = W^T . A (x^T dy form)
+    return stats, lse
+
+
+def _npair_bf16_loss(e, rows, B, Dp, temperature, symmetric, de, stats, ws, mem, step, step_dev, logq):
+    """npair_loss on precision "bf16", with or without a memory and a logQ correction -- the launches in the order of the
+    other precisions' chains: the logQ gather, the operand images (one launch), S = A [P; Mem]^T, the statistics (the fp32
+    launches as they are: S is the bf16 GEMM's fp32 output), W in one bf16 plane (the in-batch block, the memory block),
+    the estimator's update, dA = W [P; Mem] against the transposed image, dP = W^T A over the in-batch block, the ring push."""
+    Bp, Dq, lse = ws.Bp, ws.Dq, ws.lse
+    if mem is None:
+        K, P16, PT16, S, W16, gws = Bp, ws.P16, ws.PT16, ws.S, ws.W16, ws.gemm_ws
+    else:
+        if (mem.Bp, mem.Dp, mem.precision) != (Bp, Dp, "bf16"):
+            raise ValueError("NPairMemory is for %d pairs x %d columns on %s" % (mem.Bp, mem.Dp, mem.precision))
+        if B != Bp or rows is None:
+            raise ValueError("the cross-batch memory needs an unpadded batch (B == Bp) and the rows' video ids")
+        K, P16, PT16, S, W16, gws = mem.K, mem.PM16, mem.PMT16, mem.S, mem.W16, mem.gemm_ws
+    bias = mem_bias = None
+    if logq is not None:
+        bias = ws.bias
+        if isinstance(logq, torch.Tensor):
+            bias[:2 * B].copy_(logq.reshape(-1)[:2 * B])
+            logq = None
+        elif mem is None:
+            logq.gather(rows, B, None, bias, None)
+        else:                                                   # (the gather reads the ring's ids before this step's push)
+            mem_bias = mem.bias
+            logq.gather(rows, B, mem.ids, bias, mem_bias)
+    npair_operands_bf16(e, Bp, Dp, ws.A16, P16, PT16)            # [P; Mem]: the batch's part of both operand images
+    gemm_bf16_nt(BE_F32, ws.A16, P16, S, Bp, K, Dq, workspace=gws)
+    if mem is None and bias is None:
+        npair_stats(S, rows, B, temperature, symmetric, lse, stats, ws.ws)
+    elif mem is None:
+        npair_logq_stats(S, rows, B, bias, temperature, symmetric, lse, stats, ws.ws)
+    elif bias is None:
+        npair_memory_stats(S, rows, B, Bp, mem.ids, temperature, symmetric, lse, stats, ws.ws)
+    else:
+        npair_memory_logq_stats(S, rows, B, bias, Bp, mem.ids, mem_bias, temperature, symmetric, lse, stats, ws.ws)
+    if de is None:
+        return stats, lse
+    dA, dP = de[0::2], de[1::2]
+    npair_grad_bf16(S, rows, B, temperature, symmetric, lse, W16, bias=bias)
+    if mem is not None:
+        npair_memory_grad_bf16(S, rows, B, Bp, mem.ids, temperature, symmetric, lse, W16, mem_bias=mem_bias)
+    if logq is not None:
+        logq.update(rows, B, step, step_dev)
+    oA = dA if ws.dA is None else ws.dA
+    oP = dP if ws.dP is None else ws.dP
+    gemm_bf16_nt(BE_F32, W16, PT16, oA, Bp, Dq, K, workspace=gws)          # dA = W . [P; Mem]
+    gemm_bf16_tn(W16, ws.A16, oP, Bp, Dq, Bp, workspace=gws)               # dP = W^T . A (the in-batch block of W)
+    if ws.dA is not None:
+        dA.copy_(ws.dA[:, :Dp])
+        dP.copy_(ws.dP[:, :Dp])
+    if mem is not None:
+        npair_memory_push_bf16(e[1::2, :Dp], rows, Bp, Dp, step, step_dev, mem.start, mem.rows, mem.ids, mem.PM16[Bp:],
+                               mem.PMT16[:, Bp:])
     return stats, lse
 
 
@@ -919,8 +1067,8 @@ class NPairMixed:
     NPairMemory ring of M positives (a multiple of Bp and of NPAIR_TILE[precision])."""
 
     def __init__(self, Bp, Dp, precision, device, memory_size=0, memory_start=0):
-        if precision not in NPAIR_PRECISIONS:
-            raise ValueError("the N-pair loss runs on precision 'f32x3' or 'f32', not %r" % (precision,))
+        if precision not in NPAIR_FP32_PRECISIONS:
+            raise ValueError("the N-pair loss with mixed negatives runs on precision 'f32x3' or 'f32', not %r" % (precision,))
         tile = NPAIR_TILE[precision]
         if Bp < tile or Bp % tile:
             raise ValueError("precision %r: the N-pair loss needs a batch that is a multiple of %d pairs (got %d)"
@@ -1149,8 +1297,8 @@ class NPairDP:
     receives for its own (all-to-all; Dw = Dp, on f32x3 the plane GEMMs' 256-column tile)."""
 
     def __init__(self, B, G, Dp, precision, device):
-        if precision not in NPAIR_PRECISIONS:
-            raise ValueError("the N-pair loss runs on precision 'f32x3' or 'f32', not %r" % (precision,))
+        if precision not in NPAIR_FP32_PRECISIONS:
+            raise ValueError("the data-parallel N-pair loss runs on precision 'f32x3' or 'f32', not %r" % (precision,))
         B, G, Dp = int(B), int(G), int(Dp)
         tile = NPAIR_TILE[precision]
         if B < tile or B % tile:

@@ -89,13 +89,16 @@ class TrainStep:
         (fastest kernels, the collective exposed).
         ``mode="npair"``: the multi-class N-pair (in-batch softmax) loss over the in-batch sampler's pairs instead of the
         hinge -- ``temperature`` (default 0.1) and ``symmetric`` (default True: the mean of the anchor->positive and
-        positive->anchor terms), both build-defined; the reference has no such loss.  One GPU, fp32 catalogue, precision
-        "f32x3" (a batch that is a multiple of 256 pairs; what "auto" picks then) or "f32" (a multiple of 64); the
+        positive->anchor terms), both build-defined; the reference has no such loss.  One GPU; fp32 catalogue, precision
+        "f32x3" (a batch that is a multiple of 256 pairs; what "auto" picks then) or "f32" (a multiple of 64), or an fp16
+        catalogue on precision "bf16" (config 4; a multiple of 256 pairs; "auto" there): the rows and the gradient weights in
+        one bf16 plane each, every product one pass of the bf16 GEMMs (ops._npair_bf16_loss) -- with ``memory_size`` and
+        ``logq``, not with ``uniform_negatives``, ``npair_sync`` or ``train_table``; the
         embeddings' gradient goes through the separate l2norm backward (no fused tail, so no ``variance`` summary).
         ``memory_size`` (mode "npair"; 0 = none): a cross-batch memory of the last ``memory_size`` positives (XBM, Wang et
         al. 2020; ops.NPairMemory) -- extra softmax columns of every anchor's row term, without a gradient.  Step t
         computes its loss against the ring as it stood before step t and then pushes its B positives (steps before
-        ``memory_start`` push nothing).  A multiple of the batch and of the precision's tile (256 pairs on f32x3, 64 on f32);
+        ``memory_start`` push nothing).  A multiple of the batch and of the precision's tile (256 pairs on f32x3 and bf16, 64 on f32);
         the ring is part of ``state_dict``.
         ``logq`` (mode "npair"; None = none): the sampling-bias correction of Yi et al. 2019 -- every softmax logit less
         the log probability lq that its candidate is drawn into a batch, so that popular videos are not over-penalised as
@@ -177,10 +180,21 @@ class TrainStep:
                                  "the ranks")
             if train_table:
                 raise ValueError("mode 'npair' does not train the catalogue (train_table=True is not supported)")
-            if precision in ("auto", None) and table.data.dtype != torch.float16:
-                precision = "f32x3" if int(batch_size) % ops.NPAIR_TILE["f32x3"] == 0 else "f32"
+            if precision in ("auto", None):
+                if table.data.dtype == torch.float16:
+                    precision = "bf16"
+                else:
+                    precision = "f32x3" if int(batch_size) % ops.NPAIR_TILE["f32x3"] == 0 else "f32"
             if precision not in ops.NPAIR_PRECISIONS:
-                raise ValueError("mode 'npair' runs on precision 'f32x3' or 'f32' (an fp32 catalogue), not %r" % (precision,))
+                raise ValueError("mode 'npair' runs on precision 'f32x3' or 'f32' (an fp32 catalogue) or 'bf16' (an fp16 "
+                                 "catalogue), not %r" % (precision,))
+            if precision == "bf16":
+                # the config-4 chain (ops._npair_bf16_loss) is the in-batch softmax with a memory and logQ; the mixed and
+                # the data-parallel chains have no one-plane form
+                for name, on in (("uniform_negatives", uniform_negatives), ("npair_sync", npair_sync is not None)):
+                    if on:
+                        raise ValueError("mode 'npair' on precision 'bf16' does not take %s (precision 'f32x3' or 'f32' does)"
+                                         % name)
             tile = ops.NPAIR_TILE[precision]
             if int(batch_size) % tile:
                 raise ValueError("mode 'npair' on precision %r needs a batch that is a multiple of %d pairs (got %d)"
