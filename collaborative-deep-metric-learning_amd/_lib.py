@@ -234,6 +234,17 @@ SIGNATURES_BF16 = {
     "cdml_npair_memory_push_bf16": (_i, [_p, _i64, _p, _i, _i, _u64, _p, _i64, _i, _p, _i64, _p, _p, _i64, _p, _i64, _p]),
 }
 
+# name -> (restype, argtypes); must list every symbol include/cdml_hardneg.h declares (listed "hard" negatives: sampler mode 2)
+SIGNATURES_HARDNEG = {
+    "cdml_sample_listed": (_i, [_p, _i64, _i64, _u64, _u64, _p, _i, _i64, _i64, _p, _i64, _i, _u64, _p, _p, _p]),
+    "cdml_sample_gather_listed": (_i, [_p, _i64, _u64, _u64, _p, _i, _i64, _i64, _p, _i64, _i64, _i, _p, _i64, _i, _u64,
+                                       _p, _p, _p, _i64, _i, _i64, _i64, _i64, _p, _p]),
+    "cdml_sample_gather_listed_x3": (_i, [_p, _i64, _u64, _u64, _p, _i, _i64, _i64, _p, _i64, _i64, _i, _p, _i64, _i, _u64,
+                                          _p, _p, _p, _i64, _i, _i64, _i64, _i64, _p, _p, _i64, _p]),
+    "cdml_sample_gather_listed_f16": (_i, [_p, _i64, _u64, _u64, _p, _i, _i64, _i64, _p, _i64, _i64, _i, _p, _i64, _i, _u64,
+                                           _p, _p, _p, _i64, _i, _i64, _i64, _i64, _p, _p]),
+}
+
 _lib = None
 
 
@@ -253,7 +264,7 @@ def load_library():
     import torch  # noqa: F401
     lib = C.CDLL(path)
     for name, (res, args) in (list(SIGNATURES.items()) + list(SIGNATURES_MIXED.items()) + list(SIGNATURES_DP.items())
-                               + list(SIGNATURES_BF16.items())):
+                               + list(SIGNATURES_BF16.items()) + list(SIGNATURES_HARDNEG.items())):
         fn = getattr(lib, name)          # AttributeError if the ABI lost a symbol
         fn.restype = res
         fn.argtypes = args

@@ -11,6 +11,7 @@
 // a row's loads issued before the first use, wave-shuffle reduction for the
 // norm.  Rows start 128-B aligned when row_stride*4 is a multiple of 128.
 #include "common.h"
+#include "../../include/cdml_hardneg.h"
 
 namespace cdml {
 namespace {
@@ -77,6 +78,60 @@ k_sample_uniform(const int32_t *__restrict__ pairs, int64_t n_pairs, uint32_t n_
   idx_out[3 * i + 0] = a;
   idx_out[3 * i + 1] = p;
   idx_out[3 * i + 2] = n;
+}
+
+// Listed ("hard") negatives (include/cdml_hardneg.h; host model: tests/hardneg_ref.py).  Word 0 of the purpose-2 stream
+// decides hard or not; a hard draw takes its four list positions FIRST, so the four list loads do not depend on one
+// another, and returns the first entry that is a catalogue row other than a and p.  Everything else is the uniform draw.
+constexpr uint32_t kPurposeListedNeg = 2;
+struct ListedNeg {
+  const int32_t *lists = nullptr;   // [n_rows][ldl], L valid columns per row, -1 = empty
+  int64_t ldl = 0;
+  uint32_t L = 1;
+  uint64_t hard_thresh = 0;         // round(hard_fraction * 2^32)
+  int32_t *kind_out = nullptr;      // [n_steps][batch], steps kind_step_stride apart; null = not wanted
+  int64_t kind_step_stride = 0;
+};
+
+__device__ __forceinline__ int32_t sample_listed_negative(uint64_t seed, uint64_t step, uint32_t slot, int32_t a, int32_t p,
+                                                          uint32_t n_rows, const ListedNeg &ln, int32_t &kind) {
+  WordStream hs(seed, step, slot, kPurposeListedNeg);
+  const uint32_t w0 = hs.next();
+  if ((uint64_t)w0 < ln.hard_thresh && a >= 0 && (uint32_t)a < n_rows) {
+    int64_t j[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) j[t] = hs.bounded(ln.L);
+    const int32_t *row = ln.lists + (int64_t)a * ln.ldl;
+    int32_t c[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) c[t] = j[t] >= 0 ? row[j[t]] : -1;
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+      if (c[t] >= 0 && (uint32_t)c[t] < n_rows && c[t] != a && c[t] != p) {
+        kind = 1;
+        return c[t];
+      }
+  }
+  kind = 0;
+  return sample_uniform_negative(seed, step, slot, a, p, n_rows);
+}
+
+__global__ void __launch_bounds__(kThreads)
+k_sample_listed(const int32_t *__restrict__ pairs, int64_t n_pairs, uint32_t n_rows, uint64_t seed, uint64_t step_imm,
+                const uint64_t *__restrict__ step_dev, int batch, int64_t slot0, int64_t batch_global, ListedNeg ln,
+                int32_t *__restrict__ idx_out) {
+  const uint64_t step = step_imm + (step_dev ? *step_dev : 0);
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= batch) return;
+  const uint64_t slot = (uint64_t)(slot0 + i);
+  const uint64_t q = (step * (uint64_t)batch_global + slot) % (uint64_t)n_pairs;
+  const int32_t a = pairs[2 * q], p = pairs[2 * q + 1];
+  int32_t kind;
+  const int32_t n = sample_listed_negative(seed, step, (uint32_t)slot, a, p, n_rows, ln, kind);
+  idx_out[3 * i + 0] = a;
+  idx_out[3 * i + 1] = p;
+  idx_out[3 * i + 2] = n;
+  if (ln.kind_out) ln.kind_out[i] = kind;
 }
 
 __global__ void __launch_bounds__(kThreads)
@@ -240,7 +295,7 @@ k_gather_rows_planes(const float *__restrict__ src, int64_t n_rows, int64_t row_
 // training steps (the sampler is counter-based, so the triplets of step t+1 are known at step
 // t; two or more steps per launch amortise the launch ramp and the ids -> row latency chain of
 // a kernel that is otherwise only ~16 us of HBM traffic long).
-//   * the launch's rows (n_steps x RPT x batch; RPT = 3 uniform, 2 in-batch) are cut into
+//   * the launch's rows (n_steps x RPT x batch; RPT = 3 uniform or listed, 2 in-batch) are cut into
 //     chunks of kChunkRows; a block walks chunks c, c + grid, ...;
 //   * the ids of a chunk are produced once by the block's first lanes -- pair stream position,
 //     pair load, the Philox negative where the row is one -- and STAGED IN LDS (also written to
@@ -249,7 +304,8 @@ k_gather_rows_planes(const float *__restrict__ src, int64_t n_rows, int64_t row_
 //   * every wave then owns kRowsPerWave = 2 rows of the chunk: both rows' loads (NCH x 1 KiB
 //     each, 16 B per lane = whole 128-B lines) are issued before the first use, then the
 //     wave-shuffle norm and the stores.
-// MODE 0 = uniform negatives, MODE 1 = in-batch negatives.
+// MODE 0 = uniform negatives, MODE 1 = in-batch negatives, MODE 2 = listed negatives (3 rows per triplet as MODE 0; only
+// the id-staging lanes differ: the negative's lane reads the anchor's list, one more hop of the chain pair -> id -> row).
 #ifndef CDML_GATHER_ROWS_PER_WAVE
 #define CDML_GATHER_ROWS_PER_WAVE 2   // rows a wave keeps in flight (A/B'd: tools/gather_variants.sh)
 #endif
@@ -538,8 +594,9 @@ k_sample_gather(const int32_t *__restrict__ pairs, int64_t n_pairs, uint64_t see
                 int64_t n_rows, int64_t row_stride, int F, int32_t *__restrict__ idx_out,
                 int32_t *__restrict__ shift_out, typename ROW::Out *__restrict__ x_out, int64_t out_stride,
                 int n_steps, int64_t x_step_stride, int64_t idx_step_stride,
-                int32_t *__restrict__ oob_flag, __bf16 *__restrict__ x_ki = nullptr, int64_t ki_step_stride = 0) {
-  constexpr int RPT = (MODE == 0) ? 3 : 2;  // rows per triplet
+                int32_t *__restrict__ oob_flag, __bf16 *__restrict__ x_ki = nullptr, int64_t ki_step_stride = 0,
+                ListedNeg ln = ListedNeg()) {
+  constexpr int RPT = (MODE == 1) ? 2 : 3;  // rows per triplet
   constexpr int kRPW = ROW::kRows, kCR = kRPW * kWavesPerBlock;   // rows per wave / per chunk
   __shared__ int32_t s_id[2][kCR];
   __shared__ __attribute__((aligned(16))) __bf16 s_il[KI ? 3 : 1][KI ? 8 : 1][KI ? 256 : 4];
@@ -565,6 +622,10 @@ k_sample_gather(const int32_t *__restrict__ pairs, int64_t n_pairs, uint64_t see
         const uint64_t q = (step * (uint64_t)batch_global + slot) % (uint64_t)n_pairs;
         if (MODE == 0 && k == 2) {
           id = sample_uniform_negative(seed, step, (uint32_t)slot, pairs[2 * q], pairs[2 * q + 1], (uint32_t)n_rows);
+        } else if (MODE == 2 && k == 2) {
+          int32_t kind;
+          id = sample_listed_negative(seed, step, (uint32_t)slot, pairs[2 * q], pairs[2 * q + 1], (uint32_t)n_rows, ln, kind);
+          if (ln.kind_out) ln.kind_out[(int64_t)s * ln.kind_step_stride + i] = kind;
         } else {
           id = pairs[2 * q + (k ? 1 : 0)];
           // a pair id outside the catalogue (the reference raises IndexError, inputs.py:158): the row
@@ -769,6 +830,31 @@ extern "C" int cdml_sample_uniform(const int32_t *pairs, int64_t n_pairs, int64_
   return check_launch("sample_uniform");
 }
 
+// the listed draw's own arguments (cdml_hardneg.h), checked before any HIP call
+static int check_listed(const char *who, const int32_t *lists, int64_t ldl, int L, uint64_t hard_thresh) {
+  CDML_REQUIRE(lists, CDML_E_BADARG, "%s: lists is null", who);
+  CDML_REQUIRE(L >= 1 && L <= 1024, CDML_E_BADARG, "%s: L = %d outside [1, 1024]", who, L);
+  CDML_REQUIRE(ldl >= L, CDML_E_BADARG, "%s: ldl < L", who);
+  CDML_REQUIRE(hard_thresh <= (1ull << 32), CDML_E_BADARG, "%s: hard_thresh > 2^32", who);
+  return CDML_OK;
+}
+
+extern "C" int cdml_sample_listed(const int32_t *pairs, int64_t n_pairs, int64_t n_rows, uint64_t seed, uint64_t step,
+                                  const uint64_t *step_dev, int batch, int64_t slot0, int64_t batch_global,
+                                  const int32_t *lists, int64_t ldl, int L, uint64_t hard_thresh, int32_t *idx_out,
+                                  int32_t *kind_out, cdml_stream_t stream) {
+  CDML_REQUIRE(pairs && idx_out && n_pairs > 0 && batch > 0 && slot0 >= 0, CDML_E_BADARG, "sample_listed: bad argument");
+  CDML_REQUIRE(n_rows >= 3 && n_rows <= 0x7FFFFFFFll, CDML_E_BADARG, "sample_listed: n_rows must be in [3, 2^31)");
+  CDML_REQUIRE(batch_global >= slot0 + batch, CDML_E_BADARG, "sample_listed: batch_global < slot0 + batch");
+  int rc = check_listed("sample_listed", lists, ldl, L, hard_thresh);
+  if (rc) return rc;
+  ListedNeg ln;
+  ln.lists = lists, ln.ldl = ldl, ln.L = (uint32_t)L, ln.hard_thresh = hard_thresh, ln.kind_out = kind_out;
+  hipLaunchKernelGGL(k_sample_listed, dim3((batch + kThreads - 1) / kThreads), dim3(kThreads), 0, (hipStream_t)stream,
+                     pairs, n_pairs, (uint32_t)n_rows, seed, step, step_dev, batch, slot0, batch_global, ln, idx_out);
+  return check_launch("sample_listed");
+}
+
 extern "C" int cdml_sample_inbatch(const int32_t *pairs, int64_t n_pairs, uint64_t seed,
                                    uint64_t step, const uint64_t *step_dev, int batch,
                                    int64_t slot0, int64_t batch_global, int32_t *rows_out,
@@ -845,38 +931,42 @@ extern "C" int cdml_gather_rows_x3(const float *src, int64_t n_rows, int64_t row
   return check_launch("gather_rows_x3");
 }
 
-extern "C" int cdml_sample_gather(int mode, const int32_t *pairs, int64_t n_pairs, uint64_t seed,
+// mode 2 = listed negatives (ln: the listed entry points below); 0 and 1 are cdml_sample_gather's
+static int sample_gather_f32_impl(int mode, const int32_t *pairs, int64_t n_pairs, uint64_t seed,
                                   uint64_t step, const uint64_t *step_dev, int batch, int64_t slot0,
                                   int64_t batch_global, const float *table, int64_t n_rows,
                                   int64_t row_stride, int F, int32_t *idx_out, int32_t *shift_out,
                                   float *x_out, int64_t out_stride, int n_steps, int64_t x_step_stride,
-                                  int64_t idx_step_stride, int32_t *oob_flag, cdml_stream_t stream) {
-  CDML_REQUIRE(mode == 0 || mode == 1, CDML_E_BADARG, "sample_gather: mode must be 0 or 1");
+                                  int64_t idx_step_stride, int32_t *oob_flag, const ListedNeg &ln, cdml_stream_t stream) {
   CDML_REQUIRE(n_steps >= 1 && n_steps <= 64, CDML_E_BADARG, "sample_gather: n_steps must be in [1, 64]");
-  CDML_REQUIRE(n_steps == 1 || (x_step_stride >= (int64_t)batch * (mode == 0 ? 3 : 2) * out_stride &&
-                                (x_step_stride & 3) == 0 && idx_step_stride >= (int64_t)batch * (mode == 0 ? 3 : 2)),
+  CDML_REQUIRE(n_steps == 1 || (x_step_stride >= (int64_t)batch * (mode == 1 ? 2 : 3) * out_stride &&
+                                (x_step_stride & 3) == 0 && idx_step_stride >= (int64_t)batch * (mode == 1 ? 2 : 3)),
                CDML_E_BADARG, "sample_gather: per-step strides too small for the batch");
   CDML_REQUIRE(pairs && table && idx_out && x_out && n_pairs > 0 && slot0 >= 0, CDML_E_BADARG,
                "sample_gather: bad argument");
   CDML_REQUIRE(n_rows >= 3 && n_rows <= 0x7FFFFFFFll, CDML_E_BADARG,
                "sample_gather: n_rows must be in [3, 2^31)");
   CDML_REQUIRE(batch >= (mode == 1 ? 2 : 1), CDML_E_BADARG, "sample_gather: batch too small");
-  CDML_REQUIRE(mode == 0 || shift_out, CDML_E_BADARG, "sample_gather: shift_out required in mode 1");
+  CDML_REQUIRE(mode != 1 || shift_out, CDML_E_BADARG, "sample_gather: shift_out required in mode 1");
   CDML_REQUIRE(batch_global >= slot0 + batch, CDML_E_BADARG,
                "sample_gather: batch_global < slot0 + batch");
   int rc = check_gather_layout("sample_gather", table, row_stride, F, x_out, out_stride);
   if (rc) return rc;
-  const int grid = grid_for((int64_t)batch * (mode == 0 ? 3 : 2) * n_steps, RowF32<6>::kRows * kWavesPerBlock);
+  const int grid = grid_for((int64_t)batch * (mode == 1 ? 2 : 3) * n_steps, RowF32<6>::kRows * kWavesPerBlock);
   const int nch = ((F + 3) / 4 + kWave - 1) / kWave;
 #define CDML_LAUNCH_SG(M, N)                                                                      \
   hipLaunchKernelGGL((k_sample_gather<M, RowF32<N>>), dim3(grid), dim3(kThreads), 0, (hipStream_t)stream, \
                      pairs, n_pairs, seed, step, step_dev, batch, slot0, batch_global, table,     \
                      n_rows, row_stride, F, idx_out, shift_out, x_out, out_stride, n_steps,       \
-                     x_step_stride, idx_step_stride, oob_flag)
+                     x_step_stride, idx_step_stride, oob_flag, (__bf16 *)nullptr, (int64_t)0, ln)
   if (mode == 0) {
     if (nch <= 2) CDML_LAUNCH_SG(0, 2);
     else if (nch <= 6) CDML_LAUNCH_SG(0, 6);
     else CDML_LAUNCH_SG(0, 8);
+  } else if (mode == 2) {
+    if (nch <= 2) CDML_LAUNCH_SG(2, 2);
+    else if (nch <= 6) CDML_LAUNCH_SG(2, 6);
+    else CDML_LAUNCH_SG(2, 8);
   } else {
     if (nch <= 2) CDML_LAUNCH_SG(1, 2);
     else if (nch <= 6) CDML_LAUNCH_SG(1, 6);
@@ -884,6 +974,43 @@ extern "C" int cdml_sample_gather(int mode, const int32_t *pairs, int64_t n_pair
   }
 #undef CDML_LAUNCH_SG
   return check_launch("sample_gather");
+}
+
+extern "C" int cdml_sample_gather(int mode, const int32_t *pairs, int64_t n_pairs, uint64_t seed,
+                                  uint64_t step, const uint64_t *step_dev, int batch, int64_t slot0,
+                                  int64_t batch_global, const float *table, int64_t n_rows,
+                                  int64_t row_stride, int F, int32_t *idx_out, int32_t *shift_out,
+                                  float *x_out, int64_t out_stride, int n_steps, int64_t x_step_stride,
+                                  int64_t idx_step_stride, int32_t *oob_flag, cdml_stream_t stream) {
+  CDML_REQUIRE(mode == 0 || mode == 1, CDML_E_BADARG, "sample_gather: mode must be 0 or 1");
+  return sample_gather_f32_impl(mode, pairs, n_pairs, seed, step, step_dev, batch, slot0, batch_global, table, n_rows, row_stride,
+                                F, idx_out, shift_out, x_out, out_stride, n_steps, x_step_stride, idx_step_stride, oob_flag,
+                                ListedNeg(), stream);
+}
+
+// ---- listed negatives (include/cdml_hardneg.h): the fused launch in sampler mode 2, one entry point per row format ----
+static int listed_args(const char *who, const int32_t *lists, int64_t ldl, int L, uint64_t hard_thresh, int32_t *kind_out,
+                       int batch, int n_steps, int64_t kind_step_stride, ListedNeg &ln) {
+  int rc = check_listed(who, lists, ldl, L, hard_thresh);
+  if (rc) return rc;
+  CDML_REQUIRE(!kind_out || n_steps <= 1 || kind_step_stride >= batch, CDML_E_BADARG, "%s: kind_step_stride < batch", who);
+  ln.lists = lists, ln.ldl = ldl, ln.L = (uint32_t)L, ln.hard_thresh = hard_thresh;
+  ln.kind_out = kind_out, ln.kind_step_stride = kind_step_stride;
+  return CDML_OK;
+}
+
+extern "C" int cdml_sample_gather_listed(const int32_t *pairs, int64_t n_pairs, uint64_t seed, uint64_t step,
+                                         const uint64_t *step_dev, int batch, int64_t slot0, int64_t batch_global,
+                                         const float *table, int64_t n_rows, int64_t row_stride, int F,
+                                         const int32_t *lists, int64_t ldl, int L, uint64_t hard_thresh, int32_t *idx_out,
+                                         int32_t *kind_out, float *x_out, int64_t out_stride, int n_steps,
+                                         int64_t x_step_stride, int64_t idx_step_stride, int64_t kind_step_stride,
+                                         int32_t *oob_flag, cdml_stream_t stream) {
+  ListedNeg ln;
+  int rc = listed_args("sample_gather_listed", lists, ldl, L, hard_thresh, kind_out, batch, n_steps, kind_step_stride, ln);
+  if (rc) return rc;
+  return sample_gather_f32_impl(2, pairs, n_pairs, seed, step, step_dev, batch, slot0, batch_global, table, n_rows, row_stride, F,
+                                idx_out, nullptr, x_out, out_stride, n_steps, x_step_stride, idx_step_stride, oob_flag, ln, stream);
 }
 
 // The fused sampler + gather writing each row as three bf16 planes (precision "f32x3"): x_out = bf16
@@ -894,10 +1021,10 @@ static int sample_gather_x3_impl(int mode, const int32_t *pairs, int64_t n_pairs
                                  int64_t row_stride, int F, int32_t *idx_out, int32_t *shift_out,
                                  uint16_t *x_out_planes, int64_t out_stride, int n_steps, int64_t x_step_stride,
                                  int64_t idx_step_stride, int32_t *oob_flag, uint16_t *x_ki, int64_t ki_step_stride,
-                                 cdml_stream_t stream) {
-  CDML_REQUIRE(mode == 0 || mode == 1, CDML_E_BADARG, "sample_gather_x3: mode must be 0 or 1");
+                                 cdml_stream_t stream, const ListedNeg &ln = ListedNeg()) {
+  CDML_REQUIRE(mode == 0 || mode == 1 || (mode == 2 && ln.lists), CDML_E_BADARG, "sample_gather_x3: mode must be 0 or 1");
   CDML_REQUIRE(n_steps >= 1 && n_steps <= 64, CDML_E_BADARG, "sample_gather_x3: n_steps must be in [1, 64]");
-  const int rpt = mode == 0 ? 3 : 2;
+  const int rpt = mode == 1 ? 2 : 3;
   CDML_REQUIRE(n_steps == 1 || (x_step_stride >= (int64_t)batch * rpt * out_stride && (x_step_stride & 3) == 0 &&
                                 idx_step_stride >= (int64_t)batch * rpt),
                CDML_E_BADARG, "sample_gather_x3: per-step strides too small for the batch");
@@ -905,7 +1032,7 @@ static int sample_gather_x3_impl(int mode, const int32_t *pairs, int64_t n_pairs
                "sample_gather_x3: bad argument");
   CDML_REQUIRE(n_rows >= 3 && n_rows <= 0x7FFFFFFFll, CDML_E_BADARG, "sample_gather_x3: n_rows must be in [3, 2^31)");
   CDML_REQUIRE(batch >= (mode == 1 ? 2 : 1), CDML_E_BADARG, "sample_gather_x3: batch too small");
-  CDML_REQUIRE(mode == 0 || shift_out, CDML_E_BADARG, "sample_gather_x3: shift_out required in mode 1");
+  CDML_REQUIRE(mode != 1 || shift_out, CDML_E_BADARG, "sample_gather_x3: shift_out required in mode 1");
   CDML_REQUIRE(batch_global >= slot0 + batch, CDML_E_BADARG, "sample_gather_x3: batch_global < slot0 + batch");
   CDML_REQUIRE(F > 0 && F <= 2048, CDML_E_UNSUPPORTED, "sample_gather_x3: feature size %d outside (0, 2048]", F);
   CDML_REQUIRE(row_stride >= F && (row_stride & 3) == 0 && out_stride % 3 == 0 && out_stride / 3 >= F &&
@@ -926,15 +1053,19 @@ static int sample_gather_x3_impl(int mode, const int32_t *pairs, int64_t n_pairs
   hipLaunchKernelGGL((k_sample_gather<M, RowF32X3<N>, KI>), dim3(grid), dim3(kThreads), 0, (hipStream_t)stream, \
                      pairs, n_pairs, seed, step, step_dev, batch, slot0, batch_global, table,               \
                      n_rows, row_stride, F, idx_out, shift_out, reinterpret_cast<__bf16 *>(x_out_planes),   \
-                     out_stride, n_steps, x_step_stride, idx_step_stride, oob_flag, reinterpret_cast<__bf16 *>(x_ki), ki_step_stride)
+                     out_stride, n_steps, x_step_stride, idx_step_stride, oob_flag, reinterpret_cast<__bf16 *>(x_ki), ki_step_stride, ln)
   if (x_ki) {
     if (mode == 0) {
       if (nch <= 6) CDML_LAUNCH_SGX(0, 6, true); else CDML_LAUNCH_SGX(0, 8, true);
+    } else if (mode == 2) {
+      if (nch <= 6) CDML_LAUNCH_SGX(2, 6, true); else CDML_LAUNCH_SGX(2, 8, true);
     } else {
       if (nch <= 6) CDML_LAUNCH_SGX(1, 6, true); else CDML_LAUNCH_SGX(1, 8, true);
     }
   } else if (mode == 0) {
     if (nch <= 6) CDML_LAUNCH_SGX(0, 6, false); else CDML_LAUNCH_SGX(0, 8, false);
+  } else if (mode == 2) {
+    if (nch <= 6) CDML_LAUNCH_SGX(2, 6, false); else CDML_LAUNCH_SGX(2, 8, false);
   } else {
     if (nch <= 6) CDML_LAUNCH_SGX(1, 6, false); else CDML_LAUNCH_SGX(1, 8, false);
   }
@@ -966,6 +1097,23 @@ extern "C" int cdml_sample_gather_x3k(int mode, const int32_t *pairs, int64_t n_
   return sample_gather_x3_impl(mode, pairs, n_pairs, seed, step, step_dev, batch, slot0, batch_global, table, n_rows, row_stride, F,
                                idx_out, shift_out, x_out_planes, out_stride, n_steps, x_step_stride, idx_step_stride, oob_flag,
                                x_ki, ki_step_stride, stream);
+}
+
+// listed negatives, three-plane rows; x_ki null = no k8-interleaved copy (cdml_sample_gather_x3's form), else _x3k's
+extern "C" int cdml_sample_gather_listed_x3(const int32_t *pairs, int64_t n_pairs, uint64_t seed, uint64_t step,
+                                            const uint64_t *step_dev, int batch, int64_t slot0, int64_t batch_global,
+                                            const float *table, int64_t n_rows, int64_t row_stride, int F,
+                                            const int32_t *lists, int64_t ldl, int L, uint64_t hard_thresh,
+                                            int32_t *idx_out, int32_t *kind_out, uint16_t *x_out_planes, int64_t out_stride,
+                                            int n_steps, int64_t x_step_stride, int64_t idx_step_stride,
+                                            int64_t kind_step_stride, int32_t *oob_flag, uint16_t *x_ki,
+                                            int64_t ki_step_stride, cdml_stream_t stream) {
+  ListedNeg ln;
+  int rc = listed_args("sample_gather_listed_x3", lists, ldl, L, hard_thresh, kind_out, batch, n_steps, kind_step_stride, ln);
+  if (rc) return rc;
+  return sample_gather_x3_impl(2, pairs, n_pairs, seed, step, step_dev, batch, slot0, batch_global, table, n_rows, row_stride, F,
+                               idx_out, nullptr, x_out_planes, out_stride, n_steps, x_step_stride, idx_step_stride, oob_flag,
+                               x_ki, ki_step_stride, stream, ln);
 }
 
 // The fused sampler + gather writing each row as the two fp16 planes of x_hat * 2^14 (precision "f16x2"): x_out = fp16
@@ -1031,22 +1179,21 @@ extern "C" int cdml_scatter_rows(const float *src, int64_t ld_src, const int32_t
   return check_launch("scatter_rows");
 }
 
-extern "C" int cdml_sample_gather_f16(int mode, const int32_t *pairs, int64_t n_pairs, uint64_t seed,
-                                      uint64_t step, const uint64_t *step_dev, int batch, int64_t slot0,
-                                      int64_t batch_global, const uint16_t *table, int64_t n_rows,
-                                      int64_t row_stride, int F, int32_t *idx_out, int32_t *shift_out,
-                                      uint16_t *x_out_bf16, int64_t out_stride, int n_steps,
-                                      int64_t x_step_stride, int64_t idx_step_stride, int32_t *oob_flag,
-                                      cdml_stream_t stream) {
-  CDML_REQUIRE(mode == 0 || mode == 1, CDML_E_BADARG, "sample_gather_f16: mode must be 0 or 1");
+static int sample_gather_f16_impl(int mode, const int32_t *pairs, int64_t n_pairs, uint64_t seed,
+                                  uint64_t step, const uint64_t *step_dev, int batch, int64_t slot0,
+                                  int64_t batch_global, const uint16_t *table, int64_t n_rows,
+                                  int64_t row_stride, int F, int32_t *idx_out, int32_t *shift_out,
+                                  uint16_t *x_out_bf16, int64_t out_stride, int n_steps,
+                                  int64_t x_step_stride, int64_t idx_step_stride, int32_t *oob_flag,
+                                  const ListedNeg &ln, cdml_stream_t stream) {
   CDML_REQUIRE(pairs && table && idx_out && x_out_bf16 && n_pairs > 0 && slot0 >= 0, CDML_E_BADARG,
                "sample_gather_f16: bad argument");
   CDML_REQUIRE(n_rows >= 3 && n_rows <= 0x7FFFFFFFll, CDML_E_BADARG, "sample_gather_f16: n_rows must be in [3, 2^31)");
   CDML_REQUIRE(batch >= (mode == 1 ? 2 : 1), CDML_E_BADARG, "sample_gather_f16: batch too small");
-  CDML_REQUIRE(mode == 0 || shift_out, CDML_E_BADARG, "sample_gather_f16: shift_out required in mode 1");
+  CDML_REQUIRE(mode != 1 || shift_out, CDML_E_BADARG, "sample_gather_f16: shift_out required in mode 1");
   CDML_REQUIRE(batch_global >= slot0 + batch, CDML_E_BADARG, "sample_gather_f16: batch_global < slot0 + batch");
   CDML_REQUIRE(n_steps >= 1 && n_steps <= 64, CDML_E_BADARG, "sample_gather_f16: n_steps must be in [1, 64]");
-  const int rpt = mode == 0 ? 3 : 2;
+  const int rpt = mode == 1 ? 2 : 3;
   CDML_REQUIRE(n_steps == 1 || (x_step_stride >= (int64_t)batch * rpt * out_stride && (x_step_stride & 7) == 0 &&
                                 idx_step_stride >= (int64_t)batch * rpt),
                CDML_E_BADARG, "sample_gather_f16: per-step strides too small for the batch");
@@ -1061,12 +1208,43 @@ extern "C" int cdml_sample_gather_f16(int mode, const int32_t *pairs, int64_t n_
                      pairs, n_pairs, seed, step, step_dev, batch, slot0, batch_global,                       \
                      reinterpret_cast<const _Float16 *>(table), n_rows, row_stride, F, idx_out, shift_out,   \
                      reinterpret_cast<__bf16 *>(x_out_bf16), out_stride, n_steps, x_step_stride, idx_step_stride, \
-                     oob_flag)
+                     oob_flag, (__bf16 *)nullptr, (int64_t)0, ln)
   if (mode == 0) {
     if (nch <= 1) CDML_LAUNCH_SGH(0, 1); else if (nch <= 3) CDML_LAUNCH_SGH(0, 3); else CDML_LAUNCH_SGH(0, 8);
+  } else if (mode == 2) {
+    if (nch <= 1) CDML_LAUNCH_SGH(2, 1); else if (nch <= 3) CDML_LAUNCH_SGH(2, 3); else CDML_LAUNCH_SGH(2, 8);
   } else {
     if (nch <= 1) CDML_LAUNCH_SGH(1, 1); else if (nch <= 3) CDML_LAUNCH_SGH(1, 3); else CDML_LAUNCH_SGH(1, 8);
   }
 #undef CDML_LAUNCH_SGH
   return check_launch("sample_gather_f16");
+}
+
+extern "C" int cdml_sample_gather_f16(int mode, const int32_t *pairs, int64_t n_pairs, uint64_t seed,
+                                      uint64_t step, const uint64_t *step_dev, int batch, int64_t slot0,
+                                      int64_t batch_global, const uint16_t *table, int64_t n_rows,
+                                      int64_t row_stride, int F, int32_t *idx_out, int32_t *shift_out,
+                                      uint16_t *x_out_bf16, int64_t out_stride, int n_steps,
+                                      int64_t x_step_stride, int64_t idx_step_stride, int32_t *oob_flag,
+                                      cdml_stream_t stream) {
+  CDML_REQUIRE(mode == 0 || mode == 1, CDML_E_BADARG, "sample_gather_f16: mode must be 0 or 1");
+  return sample_gather_f16_impl(mode, pairs, n_pairs, seed, step, step_dev, batch, slot0, batch_global, table, n_rows, row_stride,
+                                F, idx_out, shift_out, x_out_bf16, out_stride, n_steps, x_step_stride, idx_step_stride, oob_flag,
+                                ListedNeg(), stream);
+}
+
+// listed negatives, fp16 table -> bf16 rows
+extern "C" int cdml_sample_gather_listed_f16(const int32_t *pairs, int64_t n_pairs, uint64_t seed, uint64_t step,
+                                             const uint64_t *step_dev, int batch, int64_t slot0, int64_t batch_global,
+                                             const uint16_t *table, int64_t n_rows, int64_t row_stride, int F,
+                                             const int32_t *lists, int64_t ldl, int L, uint64_t hard_thresh,
+                                             int32_t *idx_out, int32_t *kind_out, uint16_t *x_out_bf16, int64_t out_stride,
+                                             int n_steps, int64_t x_step_stride, int64_t idx_step_stride,
+                                             int64_t kind_step_stride, int32_t *oob_flag, cdml_stream_t stream) {
+  ListedNeg ln;
+  int rc = listed_args("sample_gather_listed_f16", lists, ldl, L, hard_thresh, kind_out, batch, n_steps, kind_step_stride, ln);
+  if (rc) return rc;
+  return sample_gather_f16_impl(2, pairs, n_pairs, seed, step, step_dev, batch, slot0, batch_global, table, n_rows, row_stride, F,
+                                idx_out, nullptr, x_out_bf16, out_stride, n_steps, x_step_stride, idx_step_stride, oob_flag, ln,
+                                stream);
 }

@@ -127,6 +127,78 @@ def sample_gather(mode, pairs, seed, step, batch, table, feature_size, idx_out, 
     return x_out
 
 
+def hard_threshold(hard_fraction):
+    """round(hard_fraction * 2^32): the listed draw's integer threshold (include/cdml_hardneg.h)."""
+    h = float(hard_fraction)
+    if not 0.0 <= h <= 1.0:
+        raise ValueError("hard_fraction must be in [0, 1], got %r" % (hard_fraction,))
+    return int(round(h * 4294967296.0))
+
+
+def _lists_args(lists, n_rows, hard_fraction):
+    """(pointer, ldl, L, hard_thresh) of a listed draw: lists int32 [n_rows, L] (unit inner stride), one row per video."""
+    if lists.dim() != 2 or lists.stride(1) != 1 or lists.shape[0] != n_rows or lists.shape[1] < 1:
+        raise ValueError("negative lists must be an int32 [n_rows = %d, L >= 1] tensor with unit inner stride, got %s"
+                         % (n_rows, tuple(lists.shape)))
+    return _p(lists, torch.int32), lists.stride(0), lists.shape[1], hard_threshold(hard_fraction)
+
+
+def sample_listed(pairs, n_rows, seed, step, batch, lists, hard_fraction, idx_out, kind_out=None, slot0=0, batch_global=None,
+                  step_dev=None):
+    """The ids of the listed ("hard") negative draw, the twin of sample_uniform: idx_out int32 [3 * batch]; kind_out (int32
+    [batch] or None) = 1 where the negative came from the anchor's list."""
+    bg = batch if batch_global is None else batch_global
+    lp, ldl, L, thresh = _lists_args(lists, n_rows, hard_fraction)
+    call("cdml_sample_listed", _p(pairs, torch.int32), pairs.shape[0], n_rows, seed, 0 if step is None else step,
+         _p(step_dev, torch.int64), batch, slot0, bg, lp, ldl, L, thresh, _p(idx_out, torch.int32), _p(kind_out, torch.int32),
+         _stream())
+    return idx_out
+
+
+def sample_gather_listed(pairs, seed, step, batch, table, feature_size, lists, hard_fraction, idx_out, x_out, kind_out=None,
+                         slot0=0, batch_global=None, step_dev=None, n_steps=1, oob_flag=None, x_ki=None):
+    """sample_gather in sampler mode 2 (listed negatives, three rows per triplet): the row format follows the table's and
+    x_out's types as there (fp32 rows, three bf16 planes with or without x_ki, fp16 table -> bf16 rows; the two-fp16-plane
+    output has no listed form).  kind_out: int32 [batch], or [n_steps, batch] with n_steps > 1."""
+    bg = batch if batch_global is None else batch_global
+    f16 = table.dtype == torch.float16
+    x3 = not f16 and x_out.dtype == torch.bfloat16
+    if not f16 and x_out.dtype == torch.float16:
+        raise ValueError("the two-fp16-plane rows (precision 'f16x2') have no listed form")
+    mat = _mat16 if f16 else _mat
+    omat = _mat16 if (f16 or x3) else _mat
+    tp, tld = mat(table)
+    lp, ldl, L, thresh = _lists_args(lists, table.shape[0], hard_fraction)
+    if n_steps > 1:
+        if x_out.dim() != 3 or idx_out.dim() != 2 or x_out.shape[0] != n_steps or idx_out.shape[0] != n_steps:
+            raise ValueError("n_steps > 1 needs x_out [n_steps, rows, stride] and idx_out [n_steps, rows]")
+        if kind_out is not None and (kind_out.dim() != 2 or kind_out.shape[0] != n_steps or kind_out.stride(1) != 1):
+            raise ValueError("n_steps > 1 needs kind_out [n_steps, batch]")
+        xp, xld = omat(x_out[0])
+        xss, iss = x_out.stride(0), idx_out.stride(0)
+        kss = kind_out.stride(0) if kind_out is not None else 0
+    else:
+        xp, xld = omat(x_out)
+        xss = iss = kss = 0
+    if kind_out is not None and kind_out.numel() < n_steps * batch:
+        raise ValueError("kind_out needs one int32 per triplet")
+    head = (_p(pairs, torch.int32), pairs.shape[0], seed, 0 if step is None else step, _p(step_dev, torch.int64), batch, slot0,
+            bg, tp, table.shape[0], tld, feature_size, lp, ldl, L, thresh, _p(idx_out, torch.int32),
+            _p(kind_out, torch.int32), xp, xld, n_steps, xss, iss, kss, _p(oob_flag, torch.int32))
+    if x3:
+        kis = 0
+        if x_ki is not None:
+            if x_ki.dtype != torch.bfloat16 or not x_ki.is_contiguous():
+                raise ValueError("x_ki must be a contiguous bf16 buffer")
+            kis = x_ki.stride(0) if (n_steps > 1 and x_ki.dim() > 1) else 0
+        call("cdml_sample_gather_listed_x3", *head, _p(x_ki), kis, _stream())
+        return x_out
+    if x_ki is not None:
+        raise ValueError("x_ki goes with the three-plane output")
+    call("cdml_sample_gather_listed_f16" if f16 else "cdml_sample_gather_listed", *head, _stream())
+    return x_out
+
+
 def route_rows(ids, rows_per_shard, world, capacity, send_ids, slot_out, overflow_flag):
     call("cdml_route_rows", _p(ids, torch.int32), ids.numel(), rows_per_shard, world, capacity,
          _p(send_ids, torch.int32), _p(slot_out, torch.int32), _p(overflow_flag, torch.int32), _stream())

@@ -49,7 +49,7 @@ class TrainStep:
                  clip_gradient_norm=0.0, regularization_penalty=0.0, l2_penalty=1e-8,
                  grad_sync_mode="bucketed", temperature=0.1, symmetric=True, memory_size=0, memory_start=0,
                  logq=None, logq_alpha=0.01, logq_init_gap=None, uniform_negatives=False, uniform_logq=None,
-                 npair_sync=None):
+                 npair_sync=None, negative_lists=None, hard_fraction=1.0):
         """table: FeatureTable (whole catalogue, or this rank's shard when
         ``exchange`` is given); pairs: int32 [P,2] device tensor; ``exchange`` /
         ``grad_sync``: the multi-GPU hooks of cdml_amd.dist (None on one GPU).
@@ -123,7 +123,41 @@ class TrainStep:
         share: the mean over the ranks is the global-batch loss.  Steps eagerly (``use_graph`` is ignored with a warning);
         not with ``memory_size``, ``logq``, ``uniform_negatives`` or ``train_table``.  Limit: this rank's gradient weights
         [batch x world batch] must fit the GEMMs' 2 GiB operand range (f32x3: (batch + 256) x 3 world batch bf16 -- at
-        batch 8192 at most 5 ranks, 8 ranks at batch <= 6400); ops.NPairDP raises a ValueError beyond it."""
+        batch 8192 at most 5 ranks, 8 ranks at batch <= 6400); ops.NPairDP raises a ValueError beyond it.
+        ``negative_lists`` (int32 [n_rows, L] tensor, L in [1, 1024], -1 = an empty entry; None = none): hard negatives
+        (ANCE, Xiong et al. 2020; build-defined) -- a triplet's negative is drawn from its ANCHOR's candidate list with
+        probability ``hard_fraction`` (in [0, 1], default 1.0) and uniformly otherwise, or whenever four list draws find no
+        catalogue row other than the pair's (the draw: include/cdml_hardneg.h; lists: hardneg.mine_lists).  With
+        ``mode="uniform"`` the hinge takes that negative; with ``mode="npair", uniform_negatives=True`` the N block of the
+        mixed softmax is the drawn negatives (validity rule, memory and logQ handling unchanged; ``lq_u`` stays ONE scalar,
+        so with lists the block's correction is approximate -- a listed draw is not uniform -- and ``uniform_logq``
+        overrides it).  Precisions "f32", "f32x3" and "bf16"; not with precision "f16x2", ``exchange`` / ``grad_sync`` /
+        ``npair_sync``, ``train_table`` or a mode that draws no negative.  The step keeps ONE device copy of the lists:
+        ``set_negative_lists(t)`` copies into it in place (captured graphs stay valid), ``refresh_negative_lists(k)`` mines
+        them from the current weights, ``hard_share()`` is the last step's share of listed negatives; the lists and
+        ``hard_fraction`` are part of ``state_dict``.  ``gather_ahead`` is 1 while lists are set: a refresh must not race
+        rows fetched ahead."""
+        if negative_lists is not None:
+            # hard negatives, first form: one GPU, a frozen catalogue, a sampler that draws a negative
+            for name, on in (("exchange", exchange is not None), ("grad_sync", grad_sync is not None),
+                             ("npair_sync", npair_sync is not None), ("train_table", bool(train_table))):
+                if on:
+                    raise ValueError("negative_lists does not go with %s yet: listed negatives run on one GPU over a frozen "
+                                     "catalogue" % name)
+            if precision == "f16x2":
+                raise ValueError("negative_lists does not go with precision 'f16x2' (its gather has no listed form): use "
+                                 "'f32x3', 'f32' or 'bf16'")
+            if not (mode == "uniform" or (mode == "npair" and uniform_negatives)):
+                raise ValueError("negative_lists goes with a mode that draws a negative (mode 'uniform', or mode 'npair' with "
+                                 "uniform_negatives=True), not mode %r" % (mode,))
+            hard_fraction = float(hard_fraction)
+            if not 0.0 <= hard_fraction <= 1.0:
+                raise ValueError("hard_fraction must be in [0, 1], got %r" % (hard_fraction,))
+            negative_lists = torch.as_tensor(negative_lists)
+            if (negative_lists.dim() != 2 or negative_lists.dtype != torch.int32
+                    or negative_lists.shape[0] != table.n_rows_global or not 1 <= negative_lists.shape[1] <= 1024):
+                raise ValueError("negative_lists must be an int32 [n_rows = %d, L in [1, 1024]] tensor, got %s %s"
+                                 % (table.n_rows_global, negative_lists.dtype, tuple(negative_lists.shape)))
         if mode not in _MODES:
             raise ValueError("mode must be 'uniform', 'inbatch', 'semihard' or 'npair'")
         if npair_sync is not None:
@@ -344,6 +378,12 @@ class TrainStep:
             self.npair_logq = (ops.LogQEstimator(table.n_rows_global, self.B, logq_alpha, logq_init_gap, dev) if logq_stream
                                else ops.LogQTable(logq, dev))
         self.uniform_lq = ops.uniform_logq(self.npair_logq, uniform_logq) if uniform_negatives else 0.0
+        # hard negatives: ONE device copy of the lists (set_negative_lists copies into it) and the last step's kinds
+        self.neg_lists = None
+        self.hard_fraction = float(hard_fraction)
+        if negative_lists is not None:
+            self.neg_lists = negative_lists.to(dev).contiguous().clone()
+            self.kind = torch.zeros(self.B, dtype=i32, device=dev)
         self.step_dev = torch.zeros(1, dtype=torch.int64, device=dev)
         self.lr_dev = torch.full((1,), self.base_lr, dtype=f32, device=dev)
         self._lr_host = self.base_lr
@@ -392,8 +432,8 @@ class TrainStep:
             target = 230e6 if self.bf16 else 300e6                                  # (fp16 -> bf16 rows: half the bytes read per byte written)
             gather_ahead = min(4, max(1, int(round(target / (self.R * row_bytes)))))
         self.gather_ahead = max(1, int(gather_ahead))
-        if exchange is not None or self.train_table:
-            self.gather_ahead = 1
+        if exchange is not None or self.train_table or self.neg_lists is not None:
+            self.gather_ahead = 1                            # (lists: a refresh must not race rows fetched ahead)
         self._ahead_base = None
         if self.gather_ahead > 1:
             # (fetching the NEXT block on a side stream under this block's GEMMs was measured: the
@@ -549,7 +589,13 @@ class TrainStep:
             self.prefetch.acquire(b)
             self.ws.x_hat, self.idx, self.shift = self._x[b], self._idx[b], self._shift[b]
             return
-        if self.exchange is None:
+        if self.neg_lists is not None:
+            ops.sample_gather_listed(self.pairs, self.seed, None, self.B, self.table.data, self.table.feature_size,
+                                     self.neg_lists, self.hard_fraction, self.idx, self.ws.x_hat, kind_out=self.kind,
+                                     slot0=self.slot0, batch_global=self.batch_global, step_dev=self.step_dev,
+                                     oob_flag=self.oob,
+                                     x_ki=self.ws.xk if (self.x3 and getattr(self.ws, "kint", False)) else None)
+        elif self.exchange is None:
             ops.sample_gather(m, self.pairs, self.seed, None, self.B, self.table.data,
                               self.table.feature_size, self.idx, self.ws.x_hat,
                               shift_out=self.shift, slot0=self.slot0,
@@ -565,6 +611,43 @@ class TrainStep:
                                    slot0=self.slot0, batch_global=self.batch_global,
                                    step_dev=self.step_dev)
             self.exchange.gather(self.table, self.idx, self.ws.x_hat)
+
+    # ------------------------------------------------------- hard negatives --
+    def set_negative_lists(self, lists):
+        """Copy new candidate lists (int32 [n_rows, L], the shape given at construction) into the step's device copy IN
+        PLACE: the kernels keep reading the same buffer, so captured graphs stay valid and nothing is re-captured."""
+        if self.neg_lists is None:
+            raise ValueError("this step has no negative lists (TrainStep(negative_lists=...))")
+        lists = torch.as_tensor(lists)
+        if lists.dtype != torch.int32 or tuple(lists.shape) != tuple(self.neg_lists.shape):
+            raise ValueError("negative lists must stay int32 %s, got %s %s"
+                             % (tuple(self.neg_lists.shape), lists.dtype, tuple(lists.shape)))
+        self.neg_lists.copy_(lists)
+
+    def hard_share(self):
+        """The share of the last step's triplets whose negative came from a list (synchronises)."""
+        if self.neg_lists is None:
+            raise ValueError("this step has no negative lists (TrainStep(negative_lists=...))")
+        return float(self.kind.sum().item()) / self.B
+
+    def refresh_negative_lists(self, k, skip_top=0, drop_partners=True):
+        """Embed the catalogue with the CURRENT weights (the catalogue-inference path: predict.Prediction.embed_table),
+        mine every row's k nearest neighbours behind the ``skip_top`` nearest (hardneg.mine_lists; ``drop_partners``: less the
+        row's known co-watch partners, the step's own pairs) and copy them into the step's lists.  L = k rounded up to a
+        multiple of 4 must be the width the step was built with.  Off the step path (allocates and synchronises)."""
+        from . import hardneg
+        from .predict import Prediction
+        if self.neg_lists is None:
+            raise ValueError("this step has no negative lists (TrainStep(negative_lists=...))")
+        if hardneg.list_width(k) != self.neg_lists.shape[1]:
+            raise ValueError("k = %d gives lists of width %d, this step holds lists of width %d"
+                             % (k, hardneg.list_width(k), self.neg_lists.shape[1]))
+        if getattr(self, "_list_predictor", None) is None:
+            self._list_predictor = Prediction(params=self.params, precision="bf16" if self.bf16 else "f32x3" if self.x3 else "f32")
+        emb = self._list_predictor.embed_table(self.table, 16384)
+        lists = hardneg.mine_lists(emb, k, skip_top=skip_top, pairs=self.pairs if drop_partners else None, device=self.device)
+        self.set_negative_lists(lists)
+        return lists
 
     def enable_variance(self, on=True):
         """Also compute build_graph's ``variance`` summary (calc_var, train.py:67-71,151) each
@@ -1062,6 +1145,9 @@ class TrainStep:
             state["npair_memory"] = self.npair_memory.state_dict()
         if isinstance(self.npair_logq, ops.LogQEstimator):   # (a fixed logQ table is an argument, not state)
             state["npair_logq"] = self.npair_logq.state_dict()
+        if self.neg_lists is not None:                   # hard negatives: the lists the next step draws from
+            state["negative_lists"] = self.neg_lists.detach().cpu().clone()
+            state["hard_fraction"] = self.hard_fraction
         return state
 
     def load_state_dict(self, state):
@@ -1106,6 +1192,13 @@ class TrainStep:
                 self.npair_logq.reset()
             else:
                 self.npair_logq.load(est)
+        lists = state.get("negative_lists")
+        if (lists is None) != (self.neg_lists is None):
+            raise ValueError("the checkpoint %s negative lists, this step %s" % (
+                "holds" if lists is not None else "holds no", "has none" if self.neg_lists is None else "draws from them"))
+        if lists is not None:
+            self.set_negative_lists(lists.to(self.device))
+            self.hard_fraction = float(state["hard_fraction"])
         self.global_step = int(state["global_step"])
         self.step_dev.fill_(self.global_step)
         self.seed = int(state["seed"])
@@ -1142,13 +1235,18 @@ class Trainer:
     eval/mrr beside eval_dist; model selection and early stopping stay on
     eval_dist.  None (default): no extra work and no extra keys.
 
+    ``refresh_negatives_every`` (steps; None = never): before every step whose number is a multiple of it, the step's
+    hard-negative lists are re-mined from the current weights (``TrainStep.refresh_negative_lists(negative_k,
+    skip_top=negative_skip_top)``; ``negative_k`` defaults to the lists' width).
+
     Unlike the reference (which always re-initialises, train.py:280) a
     checkpoint also carries optimizer slots, step and sampler state, so
     ``resume()`` continues a run exactly."""
 
     def __init__(self, train_step, num_epochs, n_pairs, checkpoint_dir=None, eval_features=None,
                  eval_cowatches=None, check_stop_epoch=3, best_eval_dist=1.0, eval_per_epoch=100,
-                 require_improve_num=10, logger=None, summary_path=None, eval_retrieval_ks=None):
+                 require_improve_num=10, logger=None, summary_path=None, eval_retrieval_ks=None,
+                 refresh_negatives_every=None, negative_k=None, negative_skip_top=0):
         from .evaluate import Evaluation
         from .predict import Prediction
         self.ts = train_step
@@ -1168,6 +1266,13 @@ class Trainer:
         self.history, self.eval_history, self.saved = [], [], []
         self.eval_retrieval_ks = tuple(int(k) for k in eval_retrieval_ks) if eval_retrieval_ks else None
         self.eval_retrieval = None
+        # hard negatives: re-mine the step's candidate lists every n steps (TrainStep.refresh_negative_lists)
+        self.refresh_negatives_every = int(refresh_negatives_every) if refresh_negatives_every else None
+        self.negative_skip_top = int(negative_skip_top)
+        if self.refresh_negatives_every:
+            if self.refresh_negatives_every < 1 or train_step.neg_lists is None:
+                raise ValueError("refresh_negatives_every needs a positive step count and a TrainStep(negative_lists=...)")
+            self.negative_k = int(negative_k) if negative_k else int(train_step.neg_lists.shape[1])
         # the reference's TensorBoard scalars (train.py:154-160, 246-249; losses.py:40-41) as one JSON line per
         # evaluation, under its names: `summary_path` (default <checkpoint_dir>/summaries.jsonl; rank 0 writes)
         if summary_path is None and checkpoint_dir:
@@ -1275,6 +1380,8 @@ class Trainer:
                     and gs > self.check_stop_step):
                 stopped = "early stop"
                 break
+            if self.refresh_negatives_every and gs % self.refresh_negatives_every == 0:
+                self.ts.refresh_negative_lists(self.negative_k, skip_top=self.negative_skip_top)
             self.ts.step()
             gs += 1
             if gs % self.show_step == 0 or gs == n:
