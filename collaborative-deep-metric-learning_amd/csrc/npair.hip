@@ -8,13 +8,15 @@
 //   loss         L_row, or (L_row + L_col) / 2 with `symmetric`
 //   gradient     W_ij = (m_ij exp(S_ij / t - lse_i) - d_ij) / (B t)  [+ the column term's, halved]:  dA = W P, dP = W^T A
 //
-// Four launches, all enqueue-only, no atomics, every sum in a fixed order (the results are bit-reproducible):
+// Four launches, all enqueue-only, no atomics, every sum in a fixed order (the results are bit-reproducible); the building
+// blocks shared with the mixed-negatives and the data-parallel chain are csrc/npair_common.h:
 //   k_npair_rows      one block per anchor row: one coalesced pass over S[i][:] with an online (max, sum-exp) per lane,
-//                     combined by a fixed butterfly and then wave by wave -> lse_i and the row's loss / stat partials
-//   k_npair_cols      (symmetric) a 256-row chunk x 256 columns per block, one column per lane: coalesced rows of S,
-//                     online (max, sum-exp) per column and chunk
-//   k_npair_col_fold  one lane per column folds the chunks in order -> lse'_j and the column's loss term
-//   k_npair_stats     one block: the step scalars from the per-row partials in a fixed order (as k_loss_stats does)
+//                     combined by a fixed butterfly and then wave by wave (row_fold) -> lse_i and the row's loss / stat
+//                     partials
+//   k_npair_cols      (npair_common.h; symmetric) a 256-row chunk x 256 columns per block, one column per lane: coalesced
+//                     rows of S, online (max, sum-exp) per column and chunk
+//   k_npair_col_fold  (npair_common.h) one lane per column folds the chunks in order -> lse'_j and the column's loss term
+//   k_npair_stats     one block: the step scalars from the per-row partials in a fixed order (step_scalars)
 //   k_npair_w<FMT>    W, four columns per lane, as three exact bf16 planes [B][hi | mid | lo] (the operand layout of the
 //                     plane GEMMs, split as cdml_split_f32_bf16x3 splits), as fp32 (precision "f32") or as ONE bf16 plane,
 //                     the round-to-nearest-even of that fp32 value (precision "bf16": include/cdml_npair_bf16.h)
@@ -23,56 +25,27 @@
 // also counts slot k when mem_id[k] >= 0 is neither id(a_i) nor id(p_i); the column term stays over the in-batch block.
 //   k_npair_rows<true>   the row pass going on over the memory columns (float4 / int4 per lane)
 //   k_npair_mem_w<FMT>   W's memory block, c_ik exp(S_ik / t - lse_i) / (B t) (halved with `symmetric`)
-//   k_npair_mem_push<X3> the ring push of the step's positives (after the products that read the memory), fp32 rows + ids,
-//                        and for X3 the slots' row-plane and transposed-plane operand images
+//   k_npair_mem_push<FMT> the ring push of the step's positives (after the products that read the memory), fp32 rows + ids,
+//                        and the slots' row and transposed operand images: none (kWF32), three planes (kWX3) or one bf16
+//                        plane (kWBf16: cdml_npair_memory_push_bf16)
 //
 // Sampling-bias correction (logQ, Yi et al. 2019; cdml_npair_logq_* / cdml_npair_memory_logq_*): every logit that enters a
 // log-sum-exp or the diagonal loses the log sampling probability of its candidate -- row term column j: S_ij / t - lq(p_j),
 // memory slot k: S_ik / t - lq(mem_id[k]), column term row i: S_ij / t - lq(a_i).  The passes read it per slot, bias[2i] =
 // lq(a_i), bias[2i + 1] = lq(p_i) (laid out like ids) and mem_bias[k]: the BIAS instantiations of the kernels below; the
 // BIAS = false ones are the arithmetic of the uncorrected loss.  csrc/npair_logq.hip fills the vectors.
-#include "common.h"
+#include "npair_common.h"
 #include "../../include/cdml_npair_bf16.h"
 #include <math.h>
 
 namespace cdml {
 namespace {
 
-constexpr int kNpThreads = 256;
-constexpr int kNpChunk = 256;          // rows per block of the column pass
-// what k_npair_w / k_npair_mem_w store: fp32, three exact bf16 planes, or one bf16 plane (the rounded fp32 value)
-enum : int { kWF32 = 0, kWX3 = 1, kWBf16 = 2 };
-
-__device__ __forceinline__ void np_split3(float v, __bf16 &h, __bf16 &m, __bf16 &l) { split3_bf16(v, h, m, l); }
-
-// (m, s) <- the pair for the values summarised by (m, s) and by (m2, s2); an empty pair is (-inf, 0)
-__device__ __forceinline__ void lse_merge(float &m, float &s, float m2, float s2) {
-  const float mx = fmaxf(m, m2);
-  if (mx == -INFINITY) return;
-  s = s * expf(m - mx) + s2 * expf(m2 - mx);
-  m = mx;
-}
-
-__device__ __forceinline__ void lse_add(float &m, float &s, float x) {
-  if (x > m) {
-    s = s * expf(m - x) + 1.f;
-    m = x;
-  } else {
-    s += expf(x - m);
-  }
-}
-
 // ids: int32[2B], 2i = id(a_i), 2i+1 = id(p_i); NULL = every row a video of its own
 __device__ __forceinline__ bool row_counts(const int32_t *ids, int i, int j, int ida, int idp) {
   if (j == i || !ids) return true;
   const int q = ids[2 * j + 1];
   return q != ida && q != idp;
-}
-
-__device__ __forceinline__ bool col_counts(const int32_t *ids, int i, int j, int idaj, int idpj) {
-  if (i == j || !ids) return true;
-  const int q = ids[2 * i];
-  return q != idaj && q != idpj;
 }
 
 // memory slot k counts for anchor i when it holds a row (mem_id >= 0) of neither the anchor's nor its positive's video
@@ -101,7 +74,6 @@ __global__ void __launch_bounds__(kNpThreads)
 k_npair_rows(const float *__restrict__ S, int64_t lds, const int32_t *__restrict__ ids, int B, float inv_t,
              float *__restrict__ lse, float *__restrict__ part, int64_t mem_col, const int32_t *__restrict__ mem_id, int n_mem,
              const float *__restrict__ bias, const float *__restrict__ mem_bias) {
-  __shared__ float sm[kNpThreads / kWave][4];
   const int i = blockIdx.x;
   const float *row = S + (int64_t)i * lds;
   const int ida = ids ? ids[2 * i] : 0, idp = ids ? ids[2 * i + 1] : 0;
@@ -131,78 +103,15 @@ k_npair_rows(const float *__restrict__ S, int64_t lds, const int32_t *__restrict
       mem_add<BIAS>(ids, v.w, q.w, b.w, ida, idp, inv_t, m, s, nsum, ncnt);
     }
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const float m2 = __shfl_xor(m, off, 64), s2 = __shfl_xor(s, off, 64);
-    lse_merge(m, s, m2, s2);
-  }
-  nsum = wave_sum(nsum);
-  ncnt = wave_sum(ncnt);
-  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-  if (lane == 0) {
-    sm[wave][0] = m;
-    sm[wave][1] = s;
-    sm[wave][2] = nsum;
-    sm[wave][3] = ncnt;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float M = sm[0][0], Sx = sm[0][1], ns = sm[0][2], nc = sm[0][3];
-    for (int w = 1; w < kNpThreads / kWave; ++w) {
-      lse_merge(M, Sx, sm[w][0], sm[w][1]);
-      ns += sm[w][2];
-      nc += sm[w][3];
-    }
-    const float sii = row[i];
-    const float l = M + logf(Sx);
-    lse[i] = l;
-    float d;
-    if constexpr (BIAS)
-      d = sii * inv_t - bias[2 * i + 1];
-    else
-      d = sii * inv_t;
-    *reinterpret_cast<float4 *>(part + 4 * (int64_t)i) = make_float4(l - d, 2.f - 2.f * sii, ns, nc);
-  }
-}
-
-// cm / cs [chunk][B]: the (max, sum-exp) of column j over rows chunk * kNpChunk .. + kNpChunk - 1
-// BIAS: row i's logit less bias[2i] (the anchor's: one value per row, the same for every lane of the wave)
-template <bool BIAS>
-__global__ void __launch_bounds__(kNpThreads)
-k_npair_cols(const float *__restrict__ S, int64_t lds, const int32_t *__restrict__ ids, int B, float inv_t,
-             float *__restrict__ cm, float *__restrict__ cs, const float *__restrict__ bias) {
-  const int j = blockIdx.x * kNpThreads + threadIdx.x;
-  const int c = blockIdx.y;
-  if (j >= B) return;
-  const int idaj = ids ? ids[2 * j] : 0, idpj = ids ? ids[2 * j + 1] : 0;
-  const int i0 = c * kNpChunk, i1 = min(B, i0 + kNpChunk);
-  float m = -INFINITY, s = 0.f;
-  for (int i = i0; i < i1; ++i) {
-    if (!col_counts(ids, i, j, idaj, idpj)) continue;
-    if constexpr (BIAS)
-      lse_add(m, s, S[(int64_t)i * lds + j] * inv_t - bias[2 * i]);
-    else
-      lse_add(m, s, S[(int64_t)i * lds + j] * inv_t);
-  }
-  cm[(int64_t)c * B + j] = m;
-  cs[(int64_t)c * B + j] = s;
-}
-
-// lse[B + j] = lse'_j, closs[j] = lse'_j - S_jj / t (BIAS: - (S_jj / t - bias[2j])): the chunks folded in order
-template <bool BIAS>
-__global__ void __launch_bounds__(kNpThreads)
-k_npair_col_fold(const float *__restrict__ S, int64_t lds, int B, int chunks, float inv_t, const float *__restrict__ cm,
-                 const float *__restrict__ cs, float *__restrict__ lse, float *__restrict__ closs, const float *__restrict__ bias) {
-  const int j = blockIdx.x * kNpThreads + threadIdx.x;
-  if (j >= B) return;
-  float m = -INFINITY, s = 0.f;
-  for (int c = 0; c < chunks; ++c) lse_merge(m, s, cm[(int64_t)c * B + j], cs[(int64_t)c * B + j]);
-  const float l = m + logf(s);
-  lse[B + j] = l;
+  float M, Sx, ns, nc;
+  if (!row_fold<kNpThreads>(m, s, nsum, ncnt, M, Sx, ns, nc)) return;
+  const float sii = row[i];
+  float d;
   if constexpr (BIAS)
-    closs[j] = l - (S[(int64_t)j * lds + j] * inv_t - bias[2 * j]);
+    d = sii * inv_t - bias[2 * i + 1];
   else
-    closs[j] = l - S[(int64_t)j * lds + j] * inv_t;
+    d = sii * inv_t;
+  row_store(M, Sx, ns, nc, sii, d, i, lse, part);
 }
 
 // stats[0] = loss, [1] = mean |a_i - p_i|^2, [2] = mean |a_i - p_j|^2 over the counted row-term negatives, [3] = the fraction
@@ -211,34 +120,9 @@ k_npair_col_fold(const float *__restrict__ S, int64_t lds, int B, int chunks, fl
 __global__ void __launch_bounds__(1024)
 k_npair_stats(const float *__restrict__ part, const float *__restrict__ closs, int B, int symmetric, int M,
               float *__restrict__ stats) {
-  __shared__ float sm[5][1024 / kWave];
-  float acc[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-  for (int i = threadIdx.x; i < B; i += 1024) {
-    const float4 p = *reinterpret_cast<const float4 *>(part + 4 * (int64_t)i);
-    acc[0] += p.x;
-    acc[1] += p.y;
-    acc[2] += p.z;
-    acc[3] += p.w;
-    if (symmetric) acc[4] += closs[i];
-  }
-  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-#pragma unroll
-  for (int c = 0; c < 5; ++c) {
-    const float v = wave_sum(acc[c]);
-    if (lane == 0) sm[c][wave] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float t[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-    for (int w = 0; w < 1024 / kWave; ++w)
-      for (int c = 0; c < 5; ++c) t[c] += sm[c][w];
-    const float fb = (float)B;
-    stats[0] = symmetric ? 0.5f * (t[0] / fb + t[4] / fb) : t[0] / fb;
-    stats[1] = t[1] / fb;
-    stats[2] = t[3] > 0.f ? t[2] / t[3] : 0.f;
-    const float den = M ? fb * (float)(B - 1) + fb * (float)M : fb * (float)(B - 1);
-    stats[3] = den > 0.f ? t[3] / den : 0.f;
-  }
+  const float fb = (float)B;
+  const float den = M ? fb * (float)(B - 1) + fb * (float)M : fb * (float)(B - 1);
+  step_scalars<true>(part, B, symmetric, [&](int i) { return closs[i]; }, den, stats);
 }
 
 // BIAS: the row term's logit less bp = bias[2j + 1] (positive j's), the column term's less ba = bias[2i] (anchor i's)
@@ -255,9 +139,9 @@ __device__ __forceinline__ float npair_w(const int32_t *ids, int i, int j, int i
     const int idaj = ids ? ids[2 * j] : 0, idpj = ids ? ids[2 * j + 1] : 0;
     float c;
     if constexpr (BIAS)
-      c = col_counts(ids, i, j, idaj, idpj) ? expf(v * inv_t - ba - lse_c[j]) : 0.f;
+      c = col_counts<2>(ids, i, j, idaj, idpj) ? expf(v * inv_t - ba - lse_c[j]) : 0.f;
     else
-      c = col_counts(ids, i, j, idaj, idpj) ? expf(v * inv_t - lse_c[j]) : 0.f;
+      c = col_counts<2>(ids, i, j, idaj, idpj) ? expf(v * inv_t - lse_c[j]) : 0.f;
     if (j == i) c -= 1.f;
     r = 0.5f * (r + c);
   }
@@ -296,45 +180,7 @@ k_npair_w(const float *__restrict__ S, int64_t lds, const int32_t *__restrict__ 
                                           BIAS ? bias[2 * (j0 + q) + 1] : 0.f, ba)
                           : 0.f;
   }
-  const int n = min(4, B - j0);
-  if constexpr (FMT == kWX3) {
-    using bf4 = __attribute__((ext_vector_type(4))) __bf16;
-    bf4 h, m, l;
-    for (int q = 0; q < 4; ++q) {
-      __bf16 a, b, c;
-      np_split3(w[q], a, b, c);
-      h[q] = a;
-      m[q] = b;
-      l[q] = c;
-    }
-    __bf16 *dst = static_cast<__bf16 *>(Wout) + (int64_t)i * ldw + j0;
-    if (n == 4) {
-      *reinterpret_cast<bf4 *>(dst) = h;
-      *reinterpret_cast<bf4 *>(dst + plane) = m;
-      *reinterpret_cast<bf4 *>(dst + 2 * plane) = l;
-    } else {
-      for (int q = 0; q < n; ++q) {
-        dst[q] = h[q];
-        dst[plane + q] = m[q];
-        dst[2 * plane + q] = l[q];
-      }
-    }
-  } else if constexpr (FMT == kWBf16) {
-    using bf4 = __attribute__((ext_vector_type(4))) __bf16;
-    bf4 r;
-    for (int q = 0; q < 4; ++q) r[q] = (__bf16)w[q];
-    __bf16 *dst = static_cast<__bf16 *>(Wout) + (int64_t)i * ldw + j0;
-    if (n == 4)
-      *reinterpret_cast<bf4 *>(dst) = r;
-    else
-      for (int q = 0; q < n; ++q) dst[q] = r[q];
-  } else {
-    float *dst = static_cast<float *>(Wout) + (int64_t)i * ldw + j0;
-    if (n == 4)
-      *reinterpret_cast<float4 *>(dst) = make_float4(w[0], w[1], w[2], w[3]);
-    else
-      for (int q = 0; q < n; ++q) dst[q] = w[q];
-  }
+  store_w4<FMT>(Wout, i, ldw, plane, j0, w, min(4, B - j0));
 }
 
 // The memory block of W: W[i][mem_col + k] = c_ik exp(S[i][mem_col + k] / t - lse_i) * scale (scale = 1 / (B t), halved
@@ -365,46 +211,39 @@ k_npair_mem_w(const float *__restrict__ S, int64_t lds, int64_t mem_col, const i
     w[2] = mem_counts(ids, q.z, ida, idp) ? expf(v.z * inv_t - lr) * scale : 0.f;
     w[3] = mem_counts(ids, q.w, ida, idp) ? expf(v.w * inv_t - lr) * scale : 0.f;
   }
-  if constexpr (FMT == kWX3) {
-    using bf4 = __attribute__((ext_vector_type(4))) __bf16;
-    bf4 h, m, l;
-    for (int c = 0; c < 4; ++c) {
-      __bf16 a, b, d;
-      np_split3(w[c], a, b, d);
-      h[c] = a;
-      m[c] = b;
-      l[c] = d;
-    }
-    __bf16 *dst = static_cast<__bf16 *>(Wout) + (int64_t)i * ldw + mem_col + k0;
-    *reinterpret_cast<bf4 *>(dst) = h;
-    *reinterpret_cast<bf4 *>(dst + plane) = m;
-    *reinterpret_cast<bf4 *>(dst + 2 * plane) = l;
-  } else if constexpr (FMT == kWBf16) {
-    using bf4 = __attribute__((ext_vector_type(4))) __bf16;
-    bf4 r;
-    for (int c = 0; c < 4; ++c) r[c] = (__bf16)w[c];
-    *reinterpret_cast<bf4 *>(static_cast<__bf16 *>(Wout) + (int64_t)i * ldw + mem_col + k0) = r;
-  } else {
-    *reinterpret_cast<float4 *>(static_cast<float *>(Wout) + (int64_t)i * ldw + mem_col + k0) =
-        make_float4(w[0], w[1], w[2], w[3]);
-  }
+  store_w4<FMT>(Wout, i, ldw, plane, mem_col + k0, w, 4);
 }
 
 constexpr int kPushTile = 64;
 
+// plane p of v at d[p * plane]: the three planes of cdml_split_f32_bf16x3's split, or the one rounded plane
+template <int FMT>
+__device__ __forceinline__ void push_image(float v, __bf16 *d, int64_t plane) {
+  if constexpr (FMT == kWX3) {
+    __bf16 h, m, l;
+    split3_bf16(v, h, m, l);
+    d[0] = h;
+    d[plane] = m;
+    d[2 * plane] = l;
+  } else {
+    d[0] = (__bf16)v;
+  }
+}
+
 // The ring push of step t = step_imm + *step_dev (when t >= start): slots s .. s + B - 1, s = ((t - start) mod (M / B)) B,
-// take the B positives P[r] (fp32 rows, D columns) and their ids ids[2 r + 1].  X3: also the slots' operand images --
-// R3[s + r][p * plane_r + c] and T3[c][p * plane_t + s + r] = bf16 plane p of P[r][c] (cdml_split_f32_bf16x3's split),
-// the transposed one through a 64 x 64 LDS tile so that both stores run along contiguous addresses
-template <bool X3>
+// take the B positives P[r] (fp32 rows, D columns) and their ids ids[2 r + 1].  FMT kWX3 / kWBf16: also the slots' operand
+// images -- R[s + r][p * plane_r + c] and T[c][p * plane_t + s + r] = bf16 plane p of P[r][c] (three planes) or bf16(P[r][c])
+// (one plane, p = 0), the transposed one through a 64 x 64 LDS tile so that both stores run along contiguous addresses.
+// kWF32: rows and ids only
+template <int FMT>
 __global__ void __launch_bounds__(kNpThreads)
 k_npair_mem_push(const float *__restrict__ P, int64_t ldp, const int32_t *__restrict__ ids, int B, int D, uint64_t step_imm,
                  const uint64_t *__restrict__ step_dev, int64_t start, int M, float *__restrict__ mem, int64_t ldm,
-                 int32_t *__restrict__ mem_id, __bf16 *__restrict__ R3, int64_t ldr, int64_t plane_r,
-                 __bf16 *__restrict__ T3, int64_t ldt, int64_t plane_t) {
+                 int32_t *__restrict__ mem_id, __bf16 *__restrict__ R, int64_t ldr, int64_t plane_r, __bf16 *__restrict__ T,
+                 int64_t ldt, int64_t plane_t) {
   __shared__ float tile[kPushTile][kPushTile + 1];
   const uint64_t t = step_imm + (step_dev ? *step_dev : 0);
-  if (t < (uint64_t)start) return;
+  if (t < (uint64_t)start) return;                 // (the whole grid takes the same branch: no barrier is skipped by some)
   const int64_t s = (int64_t)((t - (uint64_t)start) % (uint64_t)(M / B)) * B;
   const int c0 = blockIdx.x * kPushTile, r0 = blockIdx.y * kPushTile;
   const int lane = threadIdx.x % kPushTile, sub = threadIdx.x / kPushTile;
@@ -416,52 +255,40 @@ k_npair_mem_push(const float *__restrict__ P, int64_t ldp, const int32_t *__rest
     if (gr >= B || gc >= D) continue;
     const float v = P[(int64_t)gr * ldp + gc];
     mem[(s + gr) * ldm + gc] = v;
-    if (X3) {
-      __bf16 h, m, l;
-      np_split3(v, h, m, l);
-      __bf16 *d = R3 + (s + gr) * ldr + gc;
-      d[0] = h;
-      d[plane_r] = m;
-      d[2 * plane_r] = l;
+    if constexpr (FMT != kWF32) {
+      push_image<FMT>(v, R + (s + gr) * ldr + gc, plane_r);
       tile[r][lane] = v;
     }
   }
-  if (!X3) return;
-  __syncthreads();
-  for (int c = sub; c < kPushTile; c += kStep) {
-    const int gr = r0 + lane, gc = c0 + c;
-    if (gr >= B || gc >= D) continue;
-    __bf16 h, m, l;
-    np_split3(tile[lane][c], h, m, l);
-    __bf16 *d = T3 + (int64_t)gc * ldt + s + gr;
-    d[0] = h;
-    d[plane_t] = m;
-    d[2 * plane_t] = l;
+  if constexpr (FMT != kWF32) {
+    __syncthreads();
+    for (int c = sub; c < kPushTile; c += kStep) {
+      const int gr = r0 + lane, gc = c0 + c;
+      if (gr >= B || gc >= D) continue;            // (the same rows and columns as above: every entry read was written)
+      push_image<FMT>(tile[lane][c], T + (int64_t)gc * ldt + s + gr, plane_t);
+    }
   }
-}
-
-int np_chunks(int B) { return (B + kNpChunk - 1) / kNpChunk; }
-
-// workspace floats: part [4B] | closs [B] | cm [chunks B] | cs [chunks B]
-size_t np_ws_bytes(int B) {
-  if (B < 1) return 0;
-  const size_t f = (size_t)B * (5 + 2 * (size_t)np_chunks(B));
-  return (f * sizeof(float) + 255) / 256 * 256;
 }
 
 int np_check(const char *who, const float *S, int64_t lds, int B, float temperature, const float *lse) {
   CDML_REQUIRE(S && lse, CDML_E_BADARG, "%s: null pointer", who);
   CDML_REQUIRE(B >= 1, CDML_E_BADARG, "%s: B must be >= 1, got %d", who, B);
-  CDML_REQUIRE(isfinite(temperature) && temperature > 0.f, CDML_E_BADARG, "%s: temperature must be finite and > 0, got %g",
-               who, (double)temperature);
-  CDML_REQUIRE(lds >= B && (lds & 3) == 0 && aligned16(S), CDML_E_BADARG,
+  if (int rc = np_temperature_check(who, temperature)) return rc;
+  CDML_REQUIRE(lds >= B && mult4(lds) && aligned16(S), CDML_E_BADARG,
                "%s: S needs a 16-B aligned base and lds >= B (%d), a multiple of 4 (got %lld)", who, B, (long long)lds);
   return CDML_OK;
 }
 
-int np_bias_check(const char *who, const float *bias) {
-  CDML_REQUIRE(bias, CDML_E_BADARG, "%s: null pointer (bias)", who);
-  CDML_REQUIRE(aligned16(bias), CDML_E_BADARG, "%s: bias needs a 16-B aligned base", who);
+int npm_check(const char *who, const float *S, int64_t lds, int B, int64_t mem_col, const int32_t *mem_id, int M,
+              float temperature, const float *lse) {
+  CDML_REQUIRE(S && lse && mem_id, CDML_E_BADARG, "%s: null pointer", who);
+  CDML_REQUIRE(B >= 1, CDML_E_BADARG, "%s: B must be >= 1, got %d", who, B);
+  CDML_REQUIRE(M >= 4 && mult4(M), CDML_E_BADARG, "%s: the memory size M must be a positive multiple of 4, got %d", who, M);
+  if (int rc = np_temperature_check(who, temperature)) return rc;
+  CDML_REQUIRE(mem_col >= B && mult4(mem_col) && lds >= mem_col + M && mult4(lds) && aligned16(S) && aligned16(mem_id),
+               CDML_E_BADARG,
+               "%s: S and mem_id need 16-B aligned bases, mem_col >= B (%d) and lds >= mem_col + M (%d), multiples of 4 "
+               "(got mem_col %lld, lds %lld)", who, B, M, (long long)mem_col, (long long)lds);
   return CDML_OK;
 }
 
@@ -470,53 +297,64 @@ template <bool MEM, bool BIAS>
 int np_stats_launch(const char *who, const float *S, int64_t lds, const int32_t *ids, int B, const float *bias,
                     int64_t mem_col, const int32_t *mem_id, const float *mem_bias, int M, float temperature, int symmetric,
                     float *lse, float *stats, void *workspace, size_t workspace_bytes, cdml_stream_t stream) {
-  CDML_REQUIRE(stats && workspace, CDML_E_BADARG, "%s: null pointer", who);
-  CDML_REQUIRE(aligned16(workspace) && workspace_bytes >= np_ws_bytes(B), CDML_E_BADARG,
-               "%s: the workspace must be 16-B aligned and hold cdml_npair%s_workspace(%d) = %zu bytes (got %zu)", who,
-               MEM ? "_memory" : "", B, np_ws_bytes(B), workspace_bytes);
+  CDML_REQUIRE(stats, CDML_E_BADARG, "%s: null pointer (stats)", who);
+  if (int rc = np_ws_check(who, workspace, workspace_bytes, np_ws_bytes(B),
+                           MEM ? "cdml_npair_memory_workspace(B, M)" : "cdml_npair_workspace(B)"))
+    return rc;
   const float inv_t = 1.0f / temperature;
-  const int chunks = np_chunks(B);
-  float *part = static_cast<float *>(workspace), *closs = part + 4 * (size_t)B;
-  float *cm = closs + B, *cs = cm + (size_t)chunks * B;
+  float *part = static_cast<float *>(workspace);
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL((k_npair_rows<MEM, BIAS>), dim3(B), dim3(kNpThreads), 0, st, S, lds, ids, B, inv_t, lse, part, mem_col,
                      mem_id, M, bias, mem_bias);
   if (int rc = check_launch(MEM ? "npair_memory_stats rows" : "npair_stats rows")) return rc;
-  if (symmetric) {                                   // (with a memory: the in-batch block as it stands, through lds)
-    const unsigned gx = (unsigned)((B + kNpThreads - 1) / kNpThreads);
-    hipLaunchKernelGGL(k_npair_cols<BIAS>, dim3(gx, chunks), dim3(kNpThreads), 0, st, S, lds, ids, B, inv_t, cm, cs, bias);
-    if (int rc = check_launch(MEM ? "npair_memory_stats columns" : "npair_stats columns")) return rc;
-    hipLaunchKernelGGL(k_npair_col_fold<BIAS>, dim3(gx), dim3(kNpThreads), 0, st, S, lds, B, chunks, inv_t, cm, cs, lse, closs,
-                       bias);
-    if (int rc = check_launch(MEM ? "npair_memory_stats column fold" : "npair_stats column fold")) return rc;
-  }
-  hipLaunchKernelGGL(k_npair_stats, dim3(1), dim3(1024), 0, st, part, closs, B, symmetric ? 1 : 0, MEM ? M : 0, stats);
+  if (symmetric)                                     // (with a memory: the in-batch block as it stands, through lds)
+    if (int rc = np_cols_launch<BIAS, 2>(MEM ? "npair_memory_stats columns" : "npair_stats columns",
+                                         MEM ? "npair_memory_stats column fold" : "npair_stats column fold", S, lds, ids, B,
+                                         inv_t, bias, lse, part, st))
+      return rc;
+  hipLaunchKernelGGL(k_npair_stats, dim3(1), dim3(1024), 0, st, part, part + 4 * (size_t)B, B, symmetric ? 1 : 0, MEM ? M : 0,
+                     stats);
   return check_launch(who);
 }
 
-int np_w_x3_check(const char *who, int B, const uint16_t *W, int64_t ldw, int64_t plane) {
-  CDML_REQUIRE(W, CDML_E_BADARG, "%s: null pointer", who);
-  CDML_REQUIRE(plane >= B && ldw >= 2 * plane + B && (plane & 3) == 0 && (ldw & 3) == 0 &&
-                   (reinterpret_cast<uintptr_t>(W) & 7) == 0,
-               CDML_E_BADARG,
-               "%s: W needs an 8-B aligned base, plane >= B (%d) and ldw >= 2 plane + B, both multiples of 4 "
-               "(got plane %lld, ldw %lld)", who, B, (long long)plane, (long long)ldw);
-  return CDML_OK;
-}
-
-int np_w_f32_check(const char *who, int B, const float *W, int64_t ldw) {
-  CDML_REQUIRE(W, CDML_E_BADARG, "%s: null pointer", who);
-  CDML_REQUIRE(ldw >= B && (ldw & 3) == 0 && aligned16(W), CDML_E_BADARG,
-               "%s: W needs a 16-B aligned base and ldw >= B (%d), a multiple of 4 (got %lld)", who, B, (long long)ldw);
-  return CDML_OK;
-}
-
+// W's in-batch block: B columns from column 0
 template <int FMT, bool BIAS>
 int np_w_launch(const char *who, const float *S, int64_t lds, const int32_t *ids, int B, const float *bias, float temperature,
                 int symmetric, const float *lse, void *W, int64_t ldw, int64_t plane, cdml_stream_t stream) {
+  if (int rc = np_check(who, S, lds, B, temperature, lse)) return rc;
+  if (BIAS)
+    if (int rc = np_bias_check(who, "bias", bias)) return rc;
+  if (int rc = np_w_check(who, FMT, B, W, ldw, plane)) return rc;
   const dim3 grid((unsigned)B, (unsigned)((B + 4 * kNpThreads - 1) / (4 * kNpThreads)));
   hipLaunchKernelGGL((k_npair_w<FMT, BIAS>), grid, dim3(kNpThreads), 0, (hipStream_t)stream, S, lds, ids, B, 1.0f / temperature,
                      symmetric ? 1 : 0, lse, 1.0f / ((float)B * temperature), W, ldw, plane, bias);
+  return check_launch(who);
+}
+
+// W's memory block: M columns from column mem_col
+template <int FMT, bool BIAS>
+int npm_w_launch(const char *who, const float *S, int64_t lds, const int32_t *ids, int B, int64_t mem_col,
+                 const int32_t *mem_id, const float *mem_bias, int M, float temperature, int symmetric, const float *lse,
+                 void *W, int64_t ldw, int64_t plane, cdml_stream_t stream) {
+  if (int rc = npm_check(who, S, lds, B, mem_col, mem_id, M, temperature, lse)) return rc;
+  if (BIAS)
+    if (int rc = np_bias_check(who, "mem_bias", mem_bias)) return rc;
+  if (int rc = np_w_check(who, FMT, mem_col + M, W, ldw, plane)) return rc;
+  const dim3 grid((unsigned)B, (unsigned)((M + 4 * kNpThreads - 1) / (4 * kNpThreads)));
+  const float scale = (symmetric ? 0.5f : 1.0f) / ((float)B * temperature);
+  hipLaunchKernelGGL((k_npair_mem_w<FMT, BIAS>), grid, dim3(kNpThreads), 0, (hipStream_t)stream, S, lds, mem_col, ids, mem_id, M,
+                     1.0f / temperature, lse, scale, W, ldw, plane, mem_bias);
+  return check_launch(who);
+}
+
+template <int FMT>
+int np_push_launch(const char *who, const float *P, int64_t ldp, const int32_t *ids, int B, int D, uint64_t step,
+                   const uint64_t *step_dev, int64_t start, int M, float *mem, int64_t ldm, int32_t *mem_id, uint16_t *R,
+                   int64_t ldr, int64_t plane_r, uint16_t *T, int64_t ldt, int64_t plane_t, cdml_stream_t stream) {
+  const dim3 grid((unsigned)((D + kPushTile - 1) / kPushTile), (unsigned)((B + kPushTile - 1) / kPushTile));
+  hipLaunchKernelGGL(k_npair_mem_push<FMT>, grid, dim3(kNpThreads), 0, (hipStream_t)stream, P, ldp, ids, B, D, step, step_dev,
+                     start, M, mem, ldm, mem_id, reinterpret_cast<__bf16 *>(R), ldr, plane_r, reinterpret_cast<__bf16 *>(T), ldt,
+                     plane_t);
   return check_launch(who);
 }
 
@@ -536,15 +374,11 @@ extern "C" int cdml_npair_stats(const float *S, int64_t lds, const int32_t *ids,
 
 extern "C" int cdml_npair_grad_x3(const float *S, int64_t lds, const int32_t *ids, int B, float temperature, int symmetric,
                                   const float *lse, uint16_t *W, int64_t ldw, int64_t plane, cdml_stream_t stream) {
-  if (int rc = np_check("npair_grad_x3", S, lds, B, temperature, lse)) return rc;
-  if (int rc = np_w_x3_check("npair_grad_x3", B, W, ldw, plane)) return rc;
   return np_w_launch<kWX3, false>("npair_grad_x3", S, lds, ids, B, nullptr, temperature, symmetric, lse, W, ldw, plane, stream);
 }
 
 extern "C" int cdml_npair_grad_f32(const float *S, int64_t lds, const int32_t *ids, int B, float temperature, int symmetric,
                                    const float *lse, float *W, int64_t ldw, cdml_stream_t stream) {
-  if (int rc = np_check("npair_grad_f32", S, lds, B, temperature, lse)) return rc;
-  if (int rc = np_w_f32_check("npair_grad_f32", B, W, ldw)) return rc;
   return np_w_launch<kWF32, false>("npair_grad_f32", S, lds, ids, B, nullptr, temperature, symmetric, lse, W, ldw, 0, stream);
 }
 
@@ -554,7 +388,7 @@ extern "C" int cdml_npair_logq_stats(const float *S, int64_t lds, const int32_t 
                                      float temperature, int symmetric, float *lse, float *stats, void *workspace,
                                      size_t workspace_bytes, cdml_stream_t stream) {
   if (int rc = np_check("npair_logq_stats", S, lds, B, temperature, lse)) return rc;
-  if (int rc = np_bias_check("npair_logq_stats", bias)) return rc;
+  if (int rc = np_bias_check("npair_logq_stats", "bias", bias)) return rc;
   return np_stats_launch<false, true>("npair_logq_stats", S, lds, ids, B, bias, 0, nullptr, nullptr, 0, temperature, symmetric,
                                       lse, stats, workspace, workspace_bytes, stream);
 }
@@ -562,9 +396,6 @@ extern "C" int cdml_npair_logq_stats(const float *S, int64_t lds, const int32_t 
 extern "C" int cdml_npair_logq_grad_x3(const float *S, int64_t lds, const int32_t *ids, int B, const float *bias,
                                        float temperature, int symmetric, const float *lse, uint16_t *W, int64_t ldw,
                                        int64_t plane, cdml_stream_t stream) {
-  if (int rc = np_check("npair_logq_grad_x3", S, lds, B, temperature, lse)) return rc;
-  if (int rc = np_bias_check("npair_logq_grad_x3", bias)) return rc;
-  if (int rc = np_w_x3_check("npair_logq_grad_x3", B, W, ldw, plane)) return rc;
   return np_w_launch<kWX3, true>("npair_logq_grad_x3", S, lds, ids, B, bias, temperature, symmetric, lse, W, ldw, plane,
                                  stream);
 }
@@ -572,68 +403,10 @@ extern "C" int cdml_npair_logq_grad_x3(const float *S, int64_t lds, const int32_
 extern "C" int cdml_npair_logq_grad_f32(const float *S, int64_t lds, const int32_t *ids, int B, const float *bias,
                                         float temperature, int symmetric, const float *lse, float *W, int64_t ldw,
                                         cdml_stream_t stream) {
-  if (int rc = np_check("npair_logq_grad_f32", S, lds, B, temperature, lse)) return rc;
-  if (int rc = np_bias_check("npair_logq_grad_f32", bias)) return rc;
-  if (int rc = np_w_f32_check("npair_logq_grad_f32", B, W, ldw)) return rc;
   return np_w_launch<kWF32, true>("npair_logq_grad_f32", S, lds, ids, B, bias, temperature, symmetric, lse, W, ldw, 0, stream);
 }
 
 // ---- cross-batch memory (XBM, Wang et al. 2020): a ring of M earlier positives as extra row-term columns of S ----------
-
-namespace cdml {
-namespace {
-
-int npm_check(const char *who, const float *S, int64_t lds, int B, int64_t mem_col, const int32_t *mem_id, int M,
-              float temperature, const float *lse) {
-  CDML_REQUIRE(S && lse && mem_id, CDML_E_BADARG, "%s: null pointer", who);
-  CDML_REQUIRE(B >= 1, CDML_E_BADARG, "%s: B must be >= 1, got %d", who, B);
-  CDML_REQUIRE(M >= 4 && (M & 3) == 0, CDML_E_BADARG, "%s: the memory size M must be a positive multiple of 4, got %d", who, M);
-  CDML_REQUIRE(isfinite(temperature) && temperature > 0.f, CDML_E_BADARG, "%s: temperature must be finite and > 0, got %g",
-               who, (double)temperature);
-  CDML_REQUIRE(mem_col >= B && (mem_col & 3) == 0 && lds >= mem_col + M && (lds & 3) == 0 && aligned16(S) && aligned16(mem_id),
-               CDML_E_BADARG,
-               "%s: S and mem_id need 16-B aligned bases, mem_col >= B (%d) and lds >= mem_col + M (%d), multiples of 4 "
-               "(got mem_col %lld, lds %lld)", who, B, M, (long long)mem_col, (long long)lds);
-  return CDML_OK;
-}
-
-int npm_mem_bias_check(const char *who, const float *mem_bias) {
-  CDML_REQUIRE(mem_bias, CDML_E_BADARG, "%s: null pointer (mem_bias)", who);
-  CDML_REQUIRE(aligned16(mem_bias), CDML_E_BADARG, "%s: mem_bias needs a 16-B aligned base", who);
-  return CDML_OK;
-}
-
-int npm_w_x3_check(const char *who, int64_t mem_col, int M, const uint16_t *W, int64_t ldw, int64_t plane) {
-  CDML_REQUIRE(W, CDML_E_BADARG, "%s: null pointer", who);
-  CDML_REQUIRE(plane >= mem_col + M && ldw >= 2 * plane + mem_col + M && (plane & 3) == 0 && (ldw & 3) == 0 &&
-                   (reinterpret_cast<uintptr_t>(W) & 7) == 0,
-               CDML_E_BADARG,
-               "%s: W needs an 8-B aligned base, plane >= mem_col + M (%lld) and ldw >= 2 plane + mem_col + M, "
-               "both multiples of 4 (got plane %lld, ldw %lld)", who, (long long)(mem_col + M), (long long)plane, (long long)ldw);
-  return CDML_OK;
-}
-
-int npm_w_f32_check(const char *who, int64_t mem_col, int M, const float *W, int64_t ldw) {
-  CDML_REQUIRE(W, CDML_E_BADARG, "%s: null pointer", who);
-  CDML_REQUIRE(ldw >= mem_col + M && (ldw & 3) == 0 && aligned16(W), CDML_E_BADARG,
-               "%s: W needs a 16-B aligned base and ldw >= mem_col + M (%lld), a multiple of 4 (got %lld)", who,
-               (long long)(mem_col + M), (long long)ldw);
-  return CDML_OK;
-}
-
-template <int FMT, bool BIAS>
-int npm_w_launch(const char *who, const float *S, int64_t lds, const int32_t *ids, int B, int64_t mem_col,
-                 const int32_t *mem_id, const float *mem_bias, int M, float temperature, int symmetric, const float *lse,
-                 void *W, int64_t ldw, int64_t plane, cdml_stream_t stream) {
-  const dim3 grid((unsigned)B, (unsigned)((M + 4 * kNpThreads - 1) / (4 * kNpThreads)));
-  const float scale = (symmetric ? 0.5f : 1.0f) / ((float)B * temperature);
-  hipLaunchKernelGGL((k_npair_mem_w<FMT, BIAS>), grid, dim3(kNpThreads), 0, (hipStream_t)stream, S, lds, mem_col, ids, mem_id, M,
-                     1.0f / temperature, lse, scale, W, ldw, plane, mem_bias);
-  return check_launch(who);
-}
-
-}  // namespace
-}  // namespace cdml
 
 extern "C" size_t cdml_npair_memory_workspace(int B, int M) { return M >= 0 ? np_ws_bytes(B) : 0; }
 
@@ -648,8 +421,6 @@ extern "C" int cdml_npair_memory_stats(const float *S, int64_t lds, const int32_
 extern "C" int cdml_npair_memory_grad_x3(const float *S, int64_t lds, const int32_t *ids, int B, int64_t mem_col,
                                          const int32_t *mem_id, int M, float temperature, int symmetric, const float *lse,
                                          uint16_t *W, int64_t ldw, int64_t plane, cdml_stream_t stream) {
-  if (int rc = npm_check("npair_memory_grad_x3", S, lds, B, mem_col, mem_id, M, temperature, lse)) return rc;
-  if (int rc = npm_w_x3_check("npair_memory_grad_x3", mem_col, M, W, ldw, plane)) return rc;
   return npm_w_launch<kWX3, false>("npair_memory_grad_x3", S, lds, ids, B, mem_col, mem_id, nullptr, M, temperature, symmetric,
                                    lse, W, ldw, plane, stream);
 }
@@ -657,8 +428,6 @@ extern "C" int cdml_npair_memory_grad_x3(const float *S, int64_t lds, const int3
 extern "C" int cdml_npair_memory_grad_f32(const float *S, int64_t lds, const int32_t *ids, int B, int64_t mem_col,
                                           const int32_t *mem_id, int M, float temperature, int symmetric, const float *lse,
                                           float *W, int64_t ldw, cdml_stream_t stream) {
-  if (int rc = npm_check("npair_memory_grad_f32", S, lds, B, mem_col, mem_id, M, temperature, lse)) return rc;
-  if (int rc = npm_w_f32_check("npair_memory_grad_f32", mem_col, M, W, ldw)) return rc;
   return npm_w_launch<kWF32, false>("npair_memory_grad_f32", S, lds, ids, B, mem_col, mem_id, nullptr, M, temperature,
                                     symmetric, lse, W, ldw, 0, stream);
 }
@@ -668,8 +437,8 @@ extern "C" int cdml_npair_memory_logq_stats(const float *S, int64_t lds, const i
                                             float temperature, int symmetric, float *lse, float *stats, void *workspace,
                                             size_t workspace_bytes, cdml_stream_t stream) {
   if (int rc = npm_check("npair_memory_logq_stats", S, lds, B, mem_col, mem_id, M, temperature, lse)) return rc;
-  if (int rc = np_bias_check("npair_memory_logq_stats", bias)) return rc;
-  if (int rc = npm_mem_bias_check("npair_memory_logq_stats", mem_bias)) return rc;
+  if (int rc = np_bias_check("npair_memory_logq_stats", "bias", bias)) return rc;
+  if (int rc = np_bias_check("npair_memory_logq_stats", "mem_bias", mem_bias)) return rc;
   return np_stats_launch<true, true>("npair_memory_logq_stats", S, lds, ids, B, bias, mem_col, mem_id, mem_bias, M, temperature,
                                      symmetric, lse, stats, workspace, workspace_bytes, stream);
 }
@@ -678,9 +447,6 @@ extern "C" int cdml_npair_memory_logq_grad_x3(const float *S, int64_t lds, const
                                               const int32_t *mem_id, const float *mem_bias, int M, float temperature,
                                               int symmetric, const float *lse, uint16_t *W, int64_t ldw, int64_t plane,
                                               cdml_stream_t stream) {
-  if (int rc = npm_check("npair_memory_logq_grad_x3", S, lds, B, mem_col, mem_id, M, temperature, lse)) return rc;
-  if (int rc = npm_mem_bias_check("npair_memory_logq_grad_x3", mem_bias)) return rc;
-  if (int rc = npm_w_x3_check("npair_memory_logq_grad_x3", mem_col, M, W, ldw, plane)) return rc;
   return npm_w_launch<kWX3, true>("npair_memory_logq_grad_x3", S, lds, ids, B, mem_col, mem_id, mem_bias, M, temperature,
                                   symmetric, lse, W, ldw, plane, stream);
 }
@@ -688,17 +454,16 @@ extern "C" int cdml_npair_memory_logq_grad_x3(const float *S, int64_t lds, const
 extern "C" int cdml_npair_memory_logq_grad_f32(const float *S, int64_t lds, const int32_t *ids, int B, int64_t mem_col,
                                                const int32_t *mem_id, const float *mem_bias, int M, float temperature,
                                                int symmetric, const float *lse, float *W, int64_t ldw, cdml_stream_t stream) {
-  if (int rc = npm_check("npair_memory_logq_grad_f32", S, lds, B, mem_col, mem_id, M, temperature, lse)) return rc;
-  if (int rc = npm_mem_bias_check("npair_memory_logq_grad_f32", mem_bias)) return rc;
-  if (int rc = npm_w_f32_check("npair_memory_logq_grad_f32", mem_col, M, W, ldw)) return rc;
   return npm_w_launch<kWF32, true>("npair_memory_logq_grad_f32", S, lds, ids, B, mem_col, mem_id, mem_bias, M, temperature,
                                    symmetric, lse, W, ldw, 0, stream);
 }
 
+// the ring push: rows + ids, with the slots' three-plane images when R3 / T3 are given (precision f32x3)
 extern "C" int cdml_npair_memory_push(const float *P, int64_t ldp, const int32_t *ids, int B, int D, uint64_t step,
                                       const uint64_t *step_dev, int64_t start, int M, float *mem, int64_t ldm,
                                       int32_t *mem_id, uint16_t *R3, int64_t ldr, int64_t plane_r, uint16_t *T3,
                                       int64_t ldt, int64_t plane_t, cdml_stream_t stream) {
+  const char *who = "npair_memory_push";
   CDML_REQUIRE(P && ids && mem && mem_id, CDML_E_BADARG, "npair_memory_push: null pointer");
   CDML_REQUIRE(B >= 1 && D >= 1 && M >= B && M % B == 0, CDML_E_BADARG,
                "npair_memory_push: needs B >= 1, D >= 1 and M a multiple of B (got B %d, D %d, M %d)", B, D, M);
@@ -709,56 +474,31 @@ extern "C" int cdml_npair_memory_push(const float *P, int64_t ldp, const int32_t
   CDML_REQUIRE(!R3 || (plane_r >= D && ldr >= 2 * plane_r + D && plane_t >= M && ldt >= 2 * plane_t + M), CDML_E_BADARG,
                "npair_memory_push: plane images need plane_r >= D, ldr >= 2 plane_r + D, plane_t >= M and ldt >= 2 plane_t + M "
                "(got %lld, %lld, %lld, %lld)", (long long)plane_r, (long long)ldr, (long long)plane_t, (long long)ldt);
-  const dim3 grid((unsigned)((D + kPushTile - 1) / kPushTile), (unsigned)((B + kPushTile - 1) / kPushTile));
-  hipStream_t st = (hipStream_t)stream;
   if (R3)
-    hipLaunchKernelGGL(k_npair_mem_push<true>, grid, dim3(kNpThreads), 0, st, P, ldp, ids, B, D, step, step_dev, start, M, mem,
-                       ldm, mem_id, reinterpret_cast<__bf16 *>(R3), ldr, plane_r, reinterpret_cast<__bf16 *>(T3), ldt, plane_t);
-  else
-    hipLaunchKernelGGL(k_npair_mem_push<false>, grid, dim3(kNpThreads), 0, st, P, ldp, ids, B, D, step, step_dev, start, M, mem,
-                       ldm, mem_id, (__bf16 *)nullptr, (int64_t)0, (int64_t)0, (__bf16 *)nullptr, (int64_t)0, (int64_t)0);
-  return check_launch("npair_memory_push");
+    return np_push_launch<kWX3>(who, P, ldp, ids, B, D, step, step_dev, start, M, mem, ldm, mem_id, R3, ldr, plane_r, T3, ldt,
+                                plane_t, stream);
+  return np_push_launch<kWF32>(who, P, ldp, ids, B, D, step, step_dev, start, M, mem, ldm, mem_id, nullptr, 0, 0, nullptr, 0, 0,
+                               stream);
 }
 
 // ---- precision "bf16" (include/cdml_npair_bf16.h): W as ONE bf16 plane, the round-to-nearest-even of the fp32 value the
-// _f32 entry points write -- the kWBf16 format of k_npair_w / k_npair_mem_w.  (The operand images and the ring push of that
-// precision are csrc/npair_bf16.hip.) ----------------------------------------------------------------------------------
-
-namespace cdml {
-namespace {
-
-int np_w_bf16_check(const char *who, int64_t span, const uint16_t *W, int64_t ldw) {
-  CDML_REQUIRE(W, CDML_E_BADARG, "%s: null pointer", who);
-  CDML_REQUIRE(ldw >= span && (ldw & 3) == 0 && (reinterpret_cast<uintptr_t>(W) & 7) == 0, CDML_E_BADARG,
-               "%s: W needs an 8-B aligned base and ldw >= %lld, a multiple of 4 (got %lld)", who, (long long)span,
-               (long long)ldw);
-  return CDML_OK;
-}
-
-}  // namespace
-}  // namespace cdml
+// _f32 entry points write -- the kWBf16 format of store_w4 -- and the ring push with one-plane slot images.  (The operand
+// images of that precision are csrc/npair_bf16.hip.) ----------------------------------------------------------------------
 
 extern "C" int cdml_npair_grad_bf16(const float *S, int64_t lds, const int32_t *ids, int B, float temperature, int symmetric,
                                     const float *lse, uint16_t *W, int64_t ldw, cdml_stream_t stream) {
-  if (int rc = np_check("npair_grad_bf16", S, lds, B, temperature, lse)) return rc;
-  if (int rc = np_w_bf16_check("npair_grad_bf16", B, W, ldw)) return rc;
   return np_w_launch<kWBf16, false>("npair_grad_bf16", S, lds, ids, B, nullptr, temperature, symmetric, lse, W, ldw, 0, stream);
 }
 
 extern "C" int cdml_npair_logq_grad_bf16(const float *S, int64_t lds, const int32_t *ids, int B, const float *bias,
                                          float temperature, int symmetric, const float *lse, uint16_t *W, int64_t ldw,
                                          cdml_stream_t stream) {
-  if (int rc = np_check("npair_logq_grad_bf16", S, lds, B, temperature, lse)) return rc;
-  if (int rc = np_bias_check("npair_logq_grad_bf16", bias)) return rc;
-  if (int rc = np_w_bf16_check("npair_logq_grad_bf16", B, W, ldw)) return rc;
   return np_w_launch<kWBf16, true>("npair_logq_grad_bf16", S, lds, ids, B, bias, temperature, symmetric, lse, W, ldw, 0, stream);
 }
 
 extern "C" int cdml_npair_memory_grad_bf16(const float *S, int64_t lds, const int32_t *ids, int B, int64_t mem_col,
                                            const int32_t *mem_id, int M, float temperature, int symmetric, const float *lse,
                                            uint16_t *W, int64_t ldw, cdml_stream_t stream) {
-  if (int rc = npm_check("npair_memory_grad_bf16", S, lds, B, mem_col, mem_id, M, temperature, lse)) return rc;
-  if (int rc = np_w_bf16_check("npair_memory_grad_bf16", mem_col + M, W, ldw)) return rc;
   return npm_w_launch<kWBf16, false>("npair_memory_grad_bf16", S, lds, ids, B, mem_col, mem_id, nullptr, M, temperature,
                                      symmetric, lse, W, ldw, 0, stream);
 }
@@ -767,9 +507,21 @@ extern "C" int cdml_npair_memory_logq_grad_bf16(const float *S, int64_t lds, con
                                                 const int32_t *mem_id, const float *mem_bias, int M, float temperature,
                                                 int symmetric, const float *lse, uint16_t *W, int64_t ldw,
                                                 cdml_stream_t stream) {
-  if (int rc = npm_check("npair_memory_logq_grad_bf16", S, lds, B, mem_col, mem_id, M, temperature, lse)) return rc;
-  if (int rc = npm_mem_bias_check("npair_memory_logq_grad_bf16", mem_bias)) return rc;
-  if (int rc = np_w_bf16_check("npair_memory_logq_grad_bf16", mem_col + M, W, ldw)) return rc;
   return npm_w_launch<kWBf16, true>("npair_memory_logq_grad_bf16", S, lds, ids, B, mem_col, mem_id, mem_bias, M, temperature,
                                     symmetric, lse, W, ldw, 0, stream);
+}
+
+extern "C" int cdml_npair_memory_push_bf16(const float *P, int64_t ldp, const int32_t *ids, int B, int D, uint64_t step,
+                                           const uint64_t *step_dev, int64_t start, int M, float *mem, int64_t ldm,
+                                           int32_t *mem_id, uint16_t *R, int64_t ldr, uint16_t *T, int64_t ldt,
+                                           cdml_stream_t stream) {
+  CDML_REQUIRE(P && ids && mem && mem_id && R && T, CDML_E_BADARG, "npair_memory_push_bf16: null pointer");
+  CDML_REQUIRE(B >= 1 && D >= 1 && M >= B && M % B == 0, CDML_E_BADARG,
+               "npair_memory_push_bf16: needs B >= 1, D >= 1 and M a multiple of B (got B %d, D %d, M %d)", B, D, M);
+  CDML_REQUIRE(ldp >= D && ldm >= D && ldr >= D && ldt >= M && start >= 0, CDML_E_BADARG,
+               "npair_memory_push_bf16: ldp, ldm and ldr must be >= D (%d), ldt >= M (%d) and start >= 0 (got ldp %lld, ldm "
+               "%lld, ldr %lld, ldt %lld, start %lld)", D, M, (long long)ldp, (long long)ldm, (long long)ldr, (long long)ldt,
+               (long long)start);
+  return np_push_launch<kWBf16>("npair_memory_push_bf16", P, ldp, ids, B, D, step, step_dev, start, M, mem, ldm, mem_id, R, ldr,
+                                0, T, ldt, 0, stream);
 }

@@ -13,11 +13,12 @@
 //                     same bits on every rank (lse_merge never forms -inf - -inf)
 //   k_npdp_stats      one block: this rank's step scalars in a fixed order; the column term of the columns it owns reads
 //                     its own row diagonals
-//   k_npdp_w<X3>      W_r [B][G], four columns per lane, as three exact bf16 planes or fp32; scale 1 / (B t): the LOCAL mean,
+//   k_npdp_w<FMT>     W_r [B][G], four columns per lane, as three exact bf16 planes or fp32; scale 1 / (B t): the LOCAL mean,
 //                     the gradient average over the ranks makes it the global one
 //   k_npdp_pos_fold   de[2i + 1] = the received partial positive gradients summed in rank order
-// All enqueue-only, no atomics, every sum in a fixed order.
-#include "common.h"
+// All enqueue-only, no atomics, every sum in a fixed order; the log-sum-exp pair, the row pass's tail (row_fold), the step
+// scalars (step_scalars), the W store (store_w4) and the common host checks are csrc/npair_common.h.
+#include "npair_common.h"
 #include "../../include/cdml_npair_dp.h"
 #include <math.h>
 
@@ -26,23 +27,6 @@ namespace {
 
 constexpr int kDpThreads = 256;
 constexpr int kDpChunk = 256;          // rows per block of the column pass
-
-// (m, s) <- the pair for the values summarised by (m, s) and by (m2, s2); an empty pair is (-inf, 0)
-__device__ __forceinline__ void dp_merge(float &m, float &s, float m2, float s2) {
-  const float mx = fmaxf(m, m2);
-  if (mx == -INFINITY) return;
-  s = s * expf(m - mx) + s2 * expf(m2 - mx);
-  m = mx;
-}
-
-__device__ __forceinline__ void dp_add(float &m, float &s, float x) {
-  if (x > m) {
-    s = s * expf(m - x) + 1.f;
-    m = x;
-  } else {
-    s += expf(x - m);
-  }
-}
 
 // column j (positive id q) counts for the row of global pair g (ids ida, idp)
 __device__ __forceinline__ bool dp_row_counts(bool ids, int g, int j, int q, int ida, int idp) {
@@ -57,7 +41,7 @@ __device__ __forceinline__ bool dp_col_counts(bool ids, int g, int j, int ida, i
 __device__ __forceinline__ void dp_row_add(bool ids, int g, int j, float v, int q, int ida, int idp, float inv_t, float &m,
                                            float &s, float &nsum, float &ncnt) {
   if (!dp_row_counts(ids, g, j, q, ida, idp)) return;
-  dp_add(m, s, v * inv_t);
+  lse_add(m, s, v * inv_t);
   if (j != g) {
     nsum += 2.f - 2.f * v;
     ncnt += 1.f;
@@ -69,7 +53,6 @@ __device__ __forceinline__ void dp_row_add(bool ids, int g, int j, float v, int 
 __global__ void __launch_bounds__(kDpThreads)
 k_npdp_rows(const float *__restrict__ S, int64_t lds, const int32_t *__restrict__ ids, int G, int col0, float inv_t,
             float *__restrict__ lse, float *__restrict__ part) {
-  __shared__ float sm[kDpThreads / kWave][4];
   const int i = blockIdx.x, g = col0 + i;
   const float *row = S + (int64_t)i * lds;
   const bool has = ids != nullptr;
@@ -87,33 +70,10 @@ k_npdp_rows(const float *__restrict__ S, int64_t lds, const int32_t *__restrict_
     dp_row_add(has, g, j + 2, v.z, q1.y, ida, idp, inv_t, m, s, nsum, ncnt);
     dp_row_add(has, g, j + 3, v.w, q1.w, ida, idp, inv_t, m, s, nsum, ncnt);
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const float m2 = __shfl_xor(m, off, 64), s2 = __shfl_xor(s, off, 64);
-    dp_merge(m, s, m2, s2);
-  }
-  nsum = wave_sum(nsum);
-  ncnt = wave_sum(ncnt);
-  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-  if (lane == 0) {
-    sm[wave][0] = m;
-    sm[wave][1] = s;
-    sm[wave][2] = nsum;
-    sm[wave][3] = ncnt;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float M = sm[0][0], Sx = sm[0][1], ns = sm[0][2], nc = sm[0][3];
-    for (int w = 1; w < kDpThreads / kWave; ++w) {
-      dp_merge(M, Sx, sm[w][0], sm[w][1]);
-      ns += sm[w][2];
-      nc += sm[w][3];
-    }
-    const float sii = row[g];
-    const float l = M + logf(Sx);
-    lse[i] = l;
-    *reinterpret_cast<float4 *>(part + 4 * (int64_t)i) = make_float4(l - sii * inv_t, 2.f - 2.f * sii, ns, nc);
-  }
+  float M, Sx, ns, nc;
+  if (!row_fold<kDpThreads>(m, s, nsum, ncnt, M, Sx, ns, nc)) return;
+  const float sii = row[g];
+  row_store(M, Sx, ns, nc, sii, sii * inv_t, i, lse, part);
 }
 
 // cm / cs [chunk][G]: the (max, sum-exp) of column j over the local rows chunk * kDpChunk .. + kDpChunk - 1 that count
@@ -131,7 +91,7 @@ k_npdp_cols(const float *__restrict__ S, int64_t lds, const int32_t *__restrict_
   for (int i = i0; i < i1; ++i) {
     const int g = col0 + i;
     if (!dp_col_counts(has, g, j, has ? ids[2 * g] : 0, idaj, idpj)) continue;
-    dp_add(m, s, S[(int64_t)i * lds + j] * inv_t);
+    lse_add(m, s, S[(int64_t)i * lds + j] * inv_t);
   }
   cm[(int64_t)c * G + j] = m;
   cs[(int64_t)c * G + j] = s;
@@ -143,7 +103,7 @@ k_npdp_colpart(const float *__restrict__ cm, const float *__restrict__ cs, int G
   const int j = blockIdx.x * kDpThreads + threadIdx.x;
   if (j >= G) return;
   float m = -INFINITY, s = 0.f;
-  for (int c = 0; c < chunks; ++c) dp_merge(m, s, cm[(int64_t)c * G + j], cs[(int64_t)c * G + j]);
+  for (int c = 0; c < chunks; ++c) lse_merge(m, s, cm[(int64_t)c * G + j], cs[(int64_t)c * G + j]);
   *reinterpret_cast<float2 *>(colpart + 2 * (int64_t)j) = make_float2(m, s);
 }
 
@@ -155,7 +115,7 @@ k_npdp_col_fold(const float *__restrict__ colpart_all, int world, int G, float *
   float m = -INFINITY, s = 0.f;
   for (int r = 0; r < world; ++r) {
     const float2 p = *reinterpret_cast<const float2 *>(colpart_all + 2 * ((int64_t)r * G + j));
-    dp_merge(m, s, p.x, p.y);
+    lse_merge(m, s, p.x, p.y);
   }
   lse_col[j] = m + logf(s);                            // (nobody counted: -inf + -inf = -inf, not a NaN)
 }
@@ -165,34 +125,8 @@ k_npdp_col_fold(const float *__restrict__ colpart_all, int world, int G, float *
 __global__ void __launch_bounds__(1024)
 k_npdp_stats(const float *__restrict__ S, int64_t lds, const float *__restrict__ part, const float *__restrict__ lse_col, int B,
              int G, int col0, float inv_t, int symmetric, float *__restrict__ stats) {
-  __shared__ float sm[5][1024 / kWave];
-  float acc[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-  for (int i = threadIdx.x; i < B; i += 1024) {
-    const float4 p = *reinterpret_cast<const float4 *>(part + 4 * (int64_t)i);
-    acc[0] += p.x;
-    acc[1] += p.y;
-    acc[2] += p.z;
-    acc[3] += p.w;
-    if (symmetric) acc[4] += lse_col[col0 + i] - S[(int64_t)i * lds + col0 + i] * inv_t;
-  }
-  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-#pragma unroll
-  for (int c = 0; c < 5; ++c) {
-    const float v = wave_sum(acc[c]);
-    if (lane == 0) sm[c][wave] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float t[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-    for (int w = 0; w < 1024 / kWave; ++w)
-      for (int c = 0; c < 5; ++c) t[c] += sm[c][w];
-    const float fb = (float)B;
-    stats[0] = symmetric ? 0.5f * (t[0] / fb + t[4] / fb) : t[0] / fb;
-    stats[1] = t[1] / fb;
-    stats[2] = t[3] > 0.f ? t[2] / t[3] : 0.f;
-    const float den = fb * (float)(G - 1);
-    stats[3] = den > 0.f ? t[3] / den : 0.f;
-  }
+  step_scalars<true>(part, B, symmetric, [&](int i) { return lse_col[col0 + i] - S[(int64_t)i * lds + col0 + i] * inv_t; },
+                     (float)B * (float)(G - 1), stats);
 }
 
 __device__ __forceinline__ float dp_w(bool ids, int g, int j, int ida, int idp, int idaj, int idpj, float v, float inv_t,
@@ -208,7 +142,7 @@ __device__ __forceinline__ float dp_w(bool ids, int g, int j, int ida, int idp, 
 }
 
 // local row i = blockIdx.x, columns 4 (blockIdx.y * kDpThreads + threadIdx.x) .. + 3 (G a multiple of 4)
-template <bool X3>
+template <int FMT>
 __global__ void __launch_bounds__(kDpThreads)
 k_npdp_w(const float *__restrict__ S, int64_t lds, const int32_t *__restrict__ ids, int G, int col0, float inv_t, int symmetric,
          const float *__restrict__ lse_row, const float *__restrict__ lse_col, float scale, void *__restrict__ Wout,
@@ -227,29 +161,11 @@ k_npdp_w(const float *__restrict__ S, int64_t lds, const int32_t *__restrict__ i
   }
   float4 lc = make_float4(0.f, 0.f, 0.f, 0.f);
   if (symmetric) lc = *reinterpret_cast<const float4 *>(lse_col + j0);
-  const float w0 = dp_w(has, g, j0, ida, idp, q0.x, q0.y, v.x, inv_t, lr, lc.x, symmetric, scale);
-  const float w1 = dp_w(has, g, j0 + 1, ida, idp, q0.z, q0.w, v.y, inv_t, lr, lc.y, symmetric, scale);
-  const float w2 = dp_w(has, g, j0 + 2, ida, idp, q1.x, q1.y, v.z, inv_t, lr, lc.z, symmetric, scale);
-  const float w3 = dp_w(has, g, j0 + 3, ida, idp, q1.z, q1.w, v.w, inv_t, lr, lc.w, symmetric, scale);
-  if (X3) {
-    using bf4 = __attribute__((ext_vector_type(4))) __bf16;
-    bf4 h, m, l;
-    __bf16 a, b, c;
-    split3_bf16(w0, a, b, c);
-    h[0] = a, m[0] = b, l[0] = c;
-    split3_bf16(w1, a, b, c);
-    h[1] = a, m[1] = b, l[1] = c;
-    split3_bf16(w2, a, b, c);
-    h[2] = a, m[2] = b, l[2] = c;
-    split3_bf16(w3, a, b, c);
-    h[3] = a, m[3] = b, l[3] = c;
-    __bf16 *dst = static_cast<__bf16 *>(Wout) + (int64_t)i * ldw + j0;
-    *reinterpret_cast<bf4 *>(dst) = h;
-    *reinterpret_cast<bf4 *>(dst + plane) = m;
-    *reinterpret_cast<bf4 *>(dst + 2 * plane) = l;
-  } else {
-    *reinterpret_cast<float4 *>(static_cast<float *>(Wout) + (int64_t)i * ldw + j0) = make_float4(w0, w1, w2, w3);
-  }
+  const float w[4] = {dp_w(has, g, j0, ida, idp, q0.x, q0.y, v.x, inv_t, lr, lc.x, symmetric, scale),
+                      dp_w(has, g, j0 + 1, ida, idp, q0.z, q0.w, v.y, inv_t, lr, lc.y, symmetric, scale),
+                      dp_w(has, g, j0 + 2, ida, idp, q1.x, q1.y, v.z, inv_t, lr, lc.z, symmetric, scale),
+                      dp_w(has, g, j0 + 3, ida, idp, q1.z, q1.w, v.w, inv_t, lr, lc.w, symmetric, scale)};
+  store_w4<FMT>(Wout, i, ldw, plane, j0, w, 4);
 }
 
 // one lane per four columns of one positive's row: recv[0][i] + recv[1][i] + ... in that order -> de[2i + 1]
@@ -284,19 +200,14 @@ int dp_check(const char *who, const float *S, int64_t lds, int B, int G, int col
                "%s: needs B >= 1 and G >= B, G a multiple of 4 (got B %d, G %d)", who, B, G);
   CDML_REQUIRE(col0 >= 0 && (col0 & 3) == 0 && (int64_t)col0 + B <= G, CDML_E_BADARG,
                "%s: col0 must be a multiple of 4 with 0 <= col0 and col0 + B <= G (got col0 %d, B %d, G %d)", who, col0, B, G);
-  CDML_REQUIRE(isfinite(temperature) && temperature > 0.f, CDML_E_BADARG, "%s: temperature must be finite and > 0, got %g",
-               who, (double)temperature);
+  if (int rc = np_temperature_check(who, temperature)) return rc;
   CDML_REQUIRE(lds >= G && (lds & 3) == 0 && aligned16(S), CDML_E_BADARG,
                "%s: S needs a 16-B aligned base and lds >= G (%d), a multiple of 4 (got %lld)", who, G, (long long)lds);
   return CDML_OK;
 }
 
 int dp_ws_check(const char *who, int B, int G, const void *workspace, size_t workspace_bytes) {
-  CDML_REQUIRE(workspace, CDML_E_BADARG, "%s: null pointer (workspace)", who);
-  CDML_REQUIRE(aligned16(workspace) && workspace_bytes >= dp_ws_bytes(B, G), CDML_E_BADARG,
-               "%s: the workspace must be 16-B aligned and hold cdml_npair_dp_workspace(%d, %d) = %zu bytes (got %zu)", who, B,
-               G, dp_ws_bytes(B, G), workspace_bytes);
-  return CDML_OK;
+  return np_ws_check(who, workspace, workspace_bytes, dp_ws_bytes(B, G), "cdml_npair_dp_workspace(B, G)");
 }
 
 int dp_grad_check(const char *who, const int32_t *ids_all, int symmetric, const float *lse_row, const float *lse_col) {
@@ -305,12 +216,15 @@ int dp_grad_check(const char *who, const int32_t *ids_all, int symmetric, const 
   return CDML_OK;
 }
 
-template <bool X3>
+template <int FMT>
 int dp_w_launch(const char *who, const float *S, int64_t lds, const int32_t *ids_all, int B, int G, int col0, float temperature,
                 int symmetric, const float *lse_row, const float *lse_col, void *W, int64_t ldw, int64_t plane,
                 cdml_stream_t stream) {
+  if (int rc = dp_check(who, S, lds, B, G, col0, temperature)) return rc;
+  if (int rc = dp_grad_check(who, ids_all, symmetric, lse_row, lse_col)) return rc;
+  if (int rc = np_w_check(who, FMT, G, W, ldw, plane)) return rc;
   const dim3 grid((unsigned)B, (unsigned)((G + 4 * kDpThreads - 1) / (4 * kDpThreads)));
-  hipLaunchKernelGGL(k_npdp_w<X3>, grid, dim3(kDpThreads), 0, (hipStream_t)stream, S, lds, ids_all, G, col0, 1.0f / temperature,
+  hipLaunchKernelGGL(k_npdp_w<FMT>, grid, dim3(kDpThreads), 0, (hipStream_t)stream, S, lds, ids_all, G, col0, 1.0f / temperature,
                      symmetric ? 1 : 0, lse_row, lse_col, 1.0f / ((float)B * temperature), W, ldw, plane);
   return check_launch(who);
 }
@@ -370,28 +284,15 @@ extern "C" int cdml_npair_dp_stats(const float *S, int64_t lds, int B, int G, in
 extern "C" int cdml_npair_dp_grad_x3(const float *S, int64_t lds, const int32_t *ids_all, int B, int G, int col0,
                                      float temperature, int symmetric, const float *lse_row, const float *lse_col, uint16_t *W,
                                      int64_t ldw, int64_t plane, cdml_stream_t stream) {
-  const char *who = "npair_dp_grad_x3";
-  if (int rc = dp_check(who, S, lds, B, G, col0, temperature)) return rc;
-  if (int rc = dp_grad_check(who, ids_all, symmetric, lse_row, lse_col)) return rc;
-  CDML_REQUIRE(W, CDML_E_BADARG, "%s: null pointer (W)", who);
-  CDML_REQUIRE(plane >= G && ldw >= 2 * plane + G && (plane & 3) == 0 && (ldw & 3) == 0 &&
-                   (reinterpret_cast<uintptr_t>(W) & 7) == 0,
-               CDML_E_BADARG,
-               "%s: W needs an 8-B aligned base, plane >= G (%d) and ldw >= 2 plane + G, both multiples of 4 "
-               "(got plane %lld, ldw %lld)", who, G, (long long)plane, (long long)ldw);
-  return dp_w_launch<true>(who, S, lds, ids_all, B, G, col0, temperature, symmetric, lse_row, lse_col, W, ldw, plane, stream);
+  return dp_w_launch<kWX3>("npair_dp_grad_x3", S, lds, ids_all, B, G, col0, temperature, symmetric, lse_row, lse_col, W, ldw,
+                           plane, stream);
 }
 
 extern "C" int cdml_npair_dp_grad_f32(const float *S, int64_t lds, const int32_t *ids_all, int B, int G, int col0,
                                       float temperature, int symmetric, const float *lse_row, const float *lse_col, float *W,
                                       int64_t ldw, cdml_stream_t stream) {
-  const char *who = "npair_dp_grad_f32";
-  if (int rc = dp_check(who, S, lds, B, G, col0, temperature)) return rc;
-  if (int rc = dp_grad_check(who, ids_all, symmetric, lse_row, lse_col)) return rc;
-  CDML_REQUIRE(W, CDML_E_BADARG, "%s: null pointer (W)", who);
-  CDML_REQUIRE(ldw >= G && (ldw & 3) == 0 && aligned16(W), CDML_E_BADARG,
-               "%s: W needs a 16-B aligned base and ldw >= G (%d), a multiple of 4 (got %lld)", who, G, (long long)ldw);
-  return dp_w_launch<false>(who, S, lds, ids_all, B, G, col0, temperature, symmetric, lse_row, lse_col, W, ldw, 0, stream);
+  return dp_w_launch<kWF32>("npair_dp_grad_f32", S, lds, ids_all, B, G, col0, temperature, symmetric, lse_row, lse_col, W, ldw, 0,
+                            stream);
 }
 
 extern "C" int cdml_npair_dp_pos_fold(const float *recv, int64_t ldr, int world, int B, int D, float *de, int64_t ldde,

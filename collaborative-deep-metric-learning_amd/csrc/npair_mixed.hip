@@ -9,13 +9,14 @@
 //                     GEMMs: A3, the row image [P; N; ..] and (through a 64 x 64 LDS tile) the transposed image
 //   k_mixed_rows      one block per anchor: one pass over S[i][:] -- the in-batch and the uniform block four columns per
 //                     lane from the same id loads, then the memory block -- with an online (max, sum-exp) per lane,
-//                     combined by a fixed butterfly and then wave by wave
-//   k_mixed_cols / k_mixed_col_fold   (symmetric) the column term over the in-batch block, as k_npair_cols / _fold
-//   k_mixed_stats     one block: the step scalars from the per-row partials in a fixed order
-//   k_mixed_w<X3>     W of all blocks in ONE launch, four columns per lane, as three bf16 planes or fp32
+//                     combined by a fixed butterfly and then wave by wave (row_fold of csrc/npair_common.h)
+//   k_npair_cols<BIAS, 3> / k_npair_col_fold   (npair_common.h; symmetric) the column term over the in-batch block: the
+//                     in-batch chain's column pass reading the ids three apart
+//   k_mixed_stats     one block: the step scalars from the per-row partials in a fixed order (step_scalars)
+//   k_mixed_w<FMT>    W of all blocks in ONE launch, four columns per lane, as three bf16 planes or fp32 (store_w4)
 // BIAS (template switch): the logQ correction -- in-batch logits less bias[2j + 1] (the [2B] layout of the logQ gather),
 // the uniform block's less the scalar lq_u, a slot's less mem_bias[k].  No atomics; every sum in a fixed order.
-#include "common.h"
+#include "npair_common.h"
 #include "../../include/cdml_npair_mixed.h"
 #include <math.h>
 
@@ -23,44 +24,7 @@ namespace cdml {
 namespace {
 
 constexpr int kMxThreads = 256;
-constexpr int kMxChunk = 256;          // rows per block of the column pass
 constexpr int kMxTile = 64;            // the split's tile
-
-using bf4 = __attribute__((ext_vector_type(4))) __bf16;
-
-__device__ __forceinline__ void mx_split3(float v, __bf16 &h, __bf16 &m, __bf16 &l) {
-  h = (__bf16)v;
-  const float r = v - (float)h;
-  m = (__bf16)r;
-  l = (__bf16)(r - (float)m);
-}
-
-__device__ __forceinline__ void mx_split4(const float (&w)[4], bf4 &h, bf4 &m, bf4 &l) {
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    __bf16 a, b, c;
-    mx_split3(w[q], a, b, c);
-    h[q] = a;
-    m[q] = b;
-    l[q] = c;
-  }
-}
-
-__device__ __forceinline__ void mx_merge(float &m, float &s, float m2, float s2) {
-  const float mx = fmaxf(m, m2);
-  if (mx == -INFINITY) return;
-  s = s * expf(m - mx) + s2 * expf(m2 - mx);
-  m = mx;
-}
-
-__device__ __forceinline__ void mx_add(float &m, float &s, float x) {
-  if (x > m) {
-    s = s * expf(m - x) + 1.f;
-    m = x;
-  } else {
-    s += expf(x - m);
-  }
-}
 
 // the ids of triplets j0 .. j0 + 3 (j0 a multiple of 4): twelve consecutive int32, three 16-B loads
 __device__ __forceinline__ void mx_ids4(const int32_t *ids, int j0, int (&a)[4], int (&p)[4], int (&n)[4]) {
@@ -81,7 +45,6 @@ k_mixed_rows(const float *__restrict__ S, int64_t lds, const int32_t *__restrict
              float *__restrict__ lse, float *__restrict__ part, int64_t neg_col, int64_t mem_col,
              const int32_t *__restrict__ mem_id, int n_mem, const float *__restrict__ bias, float lq_u,
              const float *__restrict__ mem_bias) {
-  __shared__ float sm[kMxThreads / kWave][4];
   const int i = blockIdx.x;
   const float *row = S + (int64_t)i * lds;
   const int ida = ids ? ids[3 * (int64_t)i] : 0, idp = ids ? ids[3 * (int64_t)i + 1] : 0;
@@ -103,9 +66,9 @@ k_mixed_rows(const float *__restrict__ S, int64_t lds, const int32_t *__restrict
       const int j = j0 + q;
       if (j != i && ids && !mx_other(p[q], ida, idp)) continue;
       if constexpr (BIAS)
-        mx_add(m, s, v[q] * inv_t - bp[q]);
+        lse_add(m, s, v[q] * inv_t - bp[q]);
       else
-        mx_add(m, s, v[q] * inv_t);
+        lse_add(m, s, v[q] * inv_t);
       if (j != i) {
         nsum += 2.f - 2.f * v[q];
         ncnt += 1.f;
@@ -115,9 +78,9 @@ k_mixed_rows(const float *__restrict__ S, int64_t lds, const int32_t *__restrict
     for (int q = 0; q < 4; ++q) {                        // the uniform block: no special diagonal
       if (ids && !mx_other(n[q], ida, idp)) continue;
       if constexpr (BIAS)
-        mx_add(m, s, u[q] * inv_t - lq_u);
+        lse_add(m, s, u[q] * inv_t - lq_u);
       else
-        mx_add(m, s, u[q] * inv_t);
+        lse_add(m, s, u[q] * inv_t);
       nsum += 2.f - 2.f * u[q];
       ncnt += 1.f;
     }
@@ -138,86 +101,23 @@ k_mixed_rows(const float *__restrict__ S, int64_t lds, const int32_t *__restrict
       for (int c = 0; c < 4; ++c) {
         if (q[c] < 0 || (ids && !mx_other(q[c], ida, idp))) continue;
         if constexpr (BIAS)
-          mx_add(m, s, v[c] * inv_t - b[c]);
+          lse_add(m, s, v[c] * inv_t - b[c]);
         else
-          mx_add(m, s, v[c] * inv_t);
+          lse_add(m, s, v[c] * inv_t);
         nsum += 2.f - 2.f * v[c];
         ncnt += 1.f;
       }
     }
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const float m2 = __shfl_xor(m, off, 64), s2 = __shfl_xor(s, off, 64);
-    mx_merge(m, s, m2, s2);
-  }
-  nsum = wave_sum(nsum);
-  ncnt = wave_sum(ncnt);
-  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-  if (lane == 0) {
-    sm[wave][0] = m;
-    sm[wave][1] = s;
-    sm[wave][2] = nsum;
-    sm[wave][3] = ncnt;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float M = sm[0][0], Sx = sm[0][1], ns = sm[0][2], nc = sm[0][3];
-    for (int w = 1; w < kMxThreads / kWave; ++w) {
-      mx_merge(M, Sx, sm[w][0], sm[w][1]);
-      ns += sm[w][2];
-      nc += sm[w][3];
-    }
-    const float sii = row[i];
-    const float l = M + logf(Sx);
-    lse[i] = l;
-    float d;
-    if constexpr (BIAS)
-      d = sii * inv_t - bias[2 * (int64_t)i + 1];
-    else
-      d = sii * inv_t;
-    *reinterpret_cast<float4 *>(part + 4 * (int64_t)i) = make_float4(l - d, 2.f - 2.f * sii, ns, nc);
-  }
-}
-
-// cm / cs [chunk][B]: the (max, sum-exp) of in-batch column j over rows chunk * kMxChunk .. + kMxChunk - 1
-// (row i counts for column j when i == j or id(a_i) is neither id(a_j) nor id(p_j); BIAS: row i's logit less bias[2i])
-template <bool BIAS>
-__global__ void __launch_bounds__(kMxThreads)
-k_mixed_cols(const float *__restrict__ S, int64_t lds, const int32_t *__restrict__ ids, int B, float inv_t,
-             float *__restrict__ cm, float *__restrict__ cs, const float *__restrict__ bias) {
-  const int j = blockIdx.x * kMxThreads + threadIdx.x;
-  const int c = blockIdx.y;
-  if (j >= B) return;
-  const int idaj = ids ? ids[3 * (int64_t)j] : 0, idpj = ids ? ids[3 * (int64_t)j + 1] : 0;
-  const int i0 = c * kMxChunk, i1 = min(B, i0 + kMxChunk);
-  float m = -INFINITY, s = 0.f;
-  for (int i = i0; i < i1; ++i) {
-    if (i != j && ids && !mx_other(ids[3 * (int64_t)i], idaj, idpj)) continue;
-    if constexpr (BIAS)
-      mx_add(m, s, S[(int64_t)i * lds + j] * inv_t - bias[2 * (int64_t)i]);
-    else
-      mx_add(m, s, S[(int64_t)i * lds + j] * inv_t);
-  }
-  cm[(int64_t)c * B + j] = m;
-  cs[(int64_t)c * B + j] = s;
-}
-
-template <bool BIAS>
-__global__ void __launch_bounds__(kMxThreads)
-k_mixed_col_fold(const float *__restrict__ S, int64_t lds, int B, int chunks, float inv_t, const float *__restrict__ cm,
-                 const float *__restrict__ cs, float *__restrict__ lse, float *__restrict__ closs,
-                 const float *__restrict__ bias) {
-  const int j = blockIdx.x * kMxThreads + threadIdx.x;
-  if (j >= B) return;
-  float m = -INFINITY, s = 0.f;
-  for (int c = 0; c < chunks; ++c) mx_merge(m, s, cm[(int64_t)c * B + j], cs[(int64_t)c * B + j]);
-  const float l = m + logf(s);
-  lse[B + j] = l;
+  float M, Sx, ns, nc;
+  if (!row_fold<kMxThreads>(m, s, nsum, ncnt, M, Sx, ns, nc)) return;
+  const float sii = row[i];
+  float d;
   if constexpr (BIAS)
-    closs[j] = l - (S[(int64_t)j * lds + j] * inv_t - bias[2 * (int64_t)j]);
+    d = sii * inv_t - bias[2 * (int64_t)i + 1];
   else
-    closs[j] = l - S[(int64_t)j * lds + j] * inv_t;
+    d = sii * inv_t;
+  row_store(M, Sx, ns, nc, sii, d, i, lse, part);
 }
 
 // stats[0] = loss, [1] = mean |a_i - p_i|^2, [2] = mean squared distance over the counted negatives of the three blocks,
@@ -225,40 +125,14 @@ k_mixed_col_fold(const float *__restrict__ S, int64_t lds, int B, int chunks, fl
 __global__ void __launch_bounds__(1024)
 k_mixed_stats(const float *__restrict__ part, const float *__restrict__ closs, int B, int symmetric, int M,
               float *__restrict__ stats) {
-  __shared__ float sm[5][1024 / kWave];
-  float acc[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-  for (int i = threadIdx.x; i < B; i += 1024) {
-    const float4 p = *reinterpret_cast<const float4 *>(part + 4 * (int64_t)i);
-    acc[0] += p.x;
-    acc[1] += p.y;
-    acc[2] += p.z;
-    acc[3] += p.w;
-    if (symmetric) acc[4] += closs[i];
-  }
-  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-#pragma unroll
-  for (int c = 0; c < 5; ++c) {
-    const float v = wave_sum(acc[c]);
-    if (lane == 0) sm[c][wave] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float t[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-    for (int w = 0; w < 1024 / kWave; ++w)
-      for (int c = 0; c < 5; ++c) t[c] += sm[c][w];
-    const float fb = (float)B;
-    stats[0] = symmetric ? 0.5f * (t[0] / fb + t[4] / fb) : t[0] / fb;
-    stats[1] = t[1] / fb;
-    stats[2] = t[3] > 0.f ? t[2] / t[3] : 0.f;
-    const float den = fb * (float)(B - 1) + fb * fb + fb * (float)M;
-    stats[3] = t[3] / den;
-  }
+  const float fb = (float)B;
+  step_scalars<false>(part, B, symmetric, [&](int i) { return closs[i]; }, fb * (float)(B - 1) + fb * fb + fb * (float)M, stats);
 }
 
 // Row i = blockIdx.x, columns c0 = 4 (blockIdx.y * kMxThreads + threadIdx.x) .. c0 + 3 of the span [0, mem_col + M) (without
 // a memory: [0, neg_col + B)).  Every block starts and ends on a multiple of 4, so the four columns lie in one block or in a
 // gap between two, which is not written.  scale = 1 / (B t); the uniform and the memory block halve it with `symmetric`.
-template <bool X3, bool MEM, bool BIAS>
+template <int FMT, bool MEM, bool BIAS>
 __global__ void __launch_bounds__(kMxThreads)
 k_mixed_w(const float *__restrict__ S, int64_t lds, const int32_t *__restrict__ ids, int B, int64_t neg_col, int64_t mem_col,
           const int32_t *__restrict__ mem_id, int M, float inv_t, int symmetric, const float *__restrict__ lse, float scale,
@@ -344,16 +218,7 @@ k_mixed_w(const float *__restrict__ S, int64_t lds, const int32_t *__restrict__ 
   } else {
     return;                                              // a gap between two blocks
   }
-  if (X3) {
-    bf4 h, m, l;
-    mx_split4(w, h, m, l);
-    __bf16 *dst = static_cast<__bf16 *>(Wout) + (int64_t)i * ldw + c0;
-    *reinterpret_cast<bf4 *>(dst) = h;
-    *reinterpret_cast<bf4 *>(dst + plane) = m;
-    *reinterpret_cast<bf4 *>(dst + 2 * plane) = l;
-  } else {
-    *reinterpret_cast<float4 *>(static_cast<float *>(Wout) + (int64_t)i * ldw + c0) = make_float4(w[0], w[1], w[2], w[3]);
-  }
+  store_w4<FMT>(Wout, i, ldw, plane, c0, w, 4);
 }
 
 // blockIdx.z = the role of the rows this block splits: 0 anchors (e[3r] -> A3[r]), 1 positives (e[3r + 1] -> R3[r] and
@@ -376,7 +241,7 @@ k_mixed_split(const float *__restrict__ e, int64_t lde, int B, int D, __bf16 *__
     const float4 v4 = *reinterpret_cast<const float4 *>(e + (3 * (int64_t)gr + role) * lde + gc);
     const float v[4] = {v4.x, v4.y, v4.z, v4.w};
     bf4 h, m, l;
-    mx_split4(v, h, m, l);
+    split4(v, h, m, l);
     __bf16 *dst = role == 0 ? A3 + (int64_t)gr * lda + gc : R3 + (base + gr) * ldr + gc;
     const int64_t pl = role == 0 ? plane_a : plane_r;
     *reinterpret_cast<bf4 *>(dst) = h;
@@ -396,24 +261,13 @@ k_mixed_split(const float *__restrict__ e, int64_t lde, int B, int D, __bf16 *__
     if (gc >= D || gr >= B) continue;
     const float v[4] = {tile[4 * g][c], tile[4 * g + 1][c], tile[4 * g + 2][c], tile[4 * g + 3][c]};
     bf4 h, m, l;
-    mx_split4(v, h, m, l);
+    split4(v, h, m, l);
     __bf16 *dst = T3 + (int64_t)gc * ldt + base + gr;
     *reinterpret_cast<bf4 *>(dst) = h;
     *reinterpret_cast<bf4 *>(dst + plane_t) = m;
     *reinterpret_cast<bf4 *>(dst + 2 * plane_t) = l;
   }
 }
-
-int mx_chunks(int B) { return (B + kMxChunk - 1) / kMxChunk; }
-
-// workspace floats: part [4B] | closs [B] | cm [chunks B] | cs [chunks B]
-size_t mx_ws_bytes(int B) {
-  if (B < 1) return 0;
-  const size_t f = (size_t)B * (5 + 2 * (size_t)mx_chunks(B));
-  return (f * sizeof(float) + 255) / 256 * 256;
-}
-
-bool mult4(int64_t v) { return (v & 3) == 0; }
 
 // the arguments the statistics and the W launches share
 int mx_check(const char *who, const float *S, int64_t lds, const int32_t *ids, int B, int64_t neg_col, int64_t mem_col,
@@ -423,8 +277,7 @@ int mx_check(const char *who, const float *S, int64_t lds, const int32_t *ids, i
   CDML_REQUIRE(B >= 4 && mult4(B), CDML_E_BADARG, "%s: B must be a positive multiple of 4, got %d", who, B);
   CDML_REQUIRE(M >= 0 && mult4(M), CDML_E_BADARG, "%s: the memory size M must be 0 or a positive multiple of 4, got %d", who, M);
   CDML_REQUIRE(!M || mem_id, CDML_E_BADARG, "%s: null pointer (M > 0 needs mem_id)", who);
-  CDML_REQUIRE(isfinite(temperature) && temperature > 0.f, CDML_E_BADARG, "%s: temperature must be finite and > 0, got %g",
-               who, (double)temperature);
+  if (int rc = np_temperature_check(who, temperature)) return rc;
   CDML_REQUIRE(neg_col >= B && mult4(neg_col), CDML_E_BADARG, "%s: neg_col must be >= B (%d) and a multiple of 4, got %lld", who,
                B, (long long)neg_col);
   CDML_REQUIRE(!M || (mem_col >= neg_col + B && mult4(mem_col)), CDML_E_BADARG,
@@ -448,36 +301,32 @@ int mx_stats_launch(const float *S, int64_t lds, const int32_t *ids, int B, int6
                     const int32_t *mem_id, int M, const float *bias, float lq_u, const float *mem_bias, float temperature,
                     int symmetric, float *lse, float *stats, void *workspace, cdml_stream_t stream) {
   const float inv_t = 1.0f / temperature;
-  const int chunks = mx_chunks(B);
-  float *part = static_cast<float *>(workspace), *closs = part + 4 * (size_t)B;
-  float *cm = closs + B, *cs = cm + (size_t)chunks * B;
+  float *part = static_cast<float *>(workspace);
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL((k_mixed_rows<MEM, BIAS>), dim3(B), dim3(kMxThreads), 0, st, S, lds, ids, B, inv_t, lse, part, neg_col,
                      mem_col, mem_id, M, bias, lq_u, mem_bias);
   if (int rc = check_launch("npair_mixed_stats rows")) return rc;
-  if (symmetric) {
-    const unsigned gx = (unsigned)((B + kMxThreads - 1) / kMxThreads);
-    hipLaunchKernelGGL(k_mixed_cols<BIAS>, dim3(gx, chunks), dim3(kMxThreads), 0, st, S, lds, ids, B, inv_t, cm, cs, bias);
-    if (int rc = check_launch("npair_mixed_stats columns")) return rc;
-    hipLaunchKernelGGL(k_mixed_col_fold<BIAS>, dim3(gx), dim3(kMxThreads), 0, st, S, lds, B, chunks, inv_t, cm, cs, lse, closs,
-                       bias);
-    if (int rc = check_launch("npair_mixed_stats column fold")) return rc;
-  }
-  hipLaunchKernelGGL(k_mixed_stats, dim3(1), dim3(1024), 0, st, part, closs, B, symmetric ? 1 : 0, M, stats);
+  if (symmetric)
+    if (int rc = np_cols_launch<BIAS, 3>("npair_mixed_stats columns", "npair_mixed_stats column fold", S, lds, ids, B, inv_t,
+                                         bias, lse, part, st))
+      return rc;
+  hipLaunchKernelGGL(k_mixed_stats, dim3(1), dim3(1024), 0, st, part, part + 4 * (size_t)B, B, symmetric ? 1 : 0, M, stats);
   return check_launch("npair_mixed_stats");
 }
 
-template <bool X3>
+template <int FMT>
 int mx_w_launch(const char *who, const float *S, int64_t lds, const int32_t *ids, int B, int64_t neg_col, int64_t mem_col,
                 const int32_t *mem_id, int M, const float *bias, float lq_u, const float *mem_bias, float temperature,
                 int symmetric, const float *lse, void *W, int64_t ldw, int64_t plane, cdml_stream_t stream) {
+  if (int rc = mx_check(who, S, lds, ids, B, neg_col, mem_col, mem_id, M, bias, lq_u, mem_bias, temperature, lse)) return rc;
   const int64_t span = M ? mem_col + M : neg_col + B;
+  if (int rc = np_w_check(who, FMT, span, W, ldw, plane)) return rc;
   const dim3 grid((unsigned)B, (unsigned)((span + 4 * kMxThreads - 1) / (4 * kMxThreads)));
   const float inv_t = 1.0f / temperature, scale = 1.0f / ((float)B * temperature);
   const int sym = symmetric ? 1 : 0;
   hipStream_t st = (hipStream_t)stream;
 #define CDML_MX_W(MEM, BIAS)                                                                                                   \
-  hipLaunchKernelGGL((k_mixed_w<X3, MEM, BIAS>), grid, dim3(kMxThreads), 0, st, S, lds, ids, B, neg_col, mem_col, mem_id, M,    \
+  hipLaunchKernelGGL((k_mixed_w<FMT, MEM, BIAS>), grid, dim3(kMxThreads), 0, st, S, lds, ids, B, neg_col, mem_col, mem_id, M,    \
                      inv_t, sym, lse, scale, W, ldw, plane, bias, lq_u, mem_bias)
   if (M && bias) {
     CDML_MX_W(true, true);
@@ -497,7 +346,7 @@ int mx_w_launch(const char *who, const float *S, int64_t lds, const int32_t *ids
 
 using namespace cdml;
 
-extern "C" size_t cdml_npair_mixed_workspace(int B, int M) { return M >= 0 ? mx_ws_bytes(B) : 0; }
+extern "C" size_t cdml_npair_mixed_workspace(int B, int M) { return M >= 0 ? np_ws_bytes(B) : 0; }
 
 extern "C" int cdml_npair_mixed_stats(const float *S, int64_t lds, const int32_t *ids, int B, int64_t neg_col, int64_t mem_col,
                                       const int32_t *mem_id, int M, const float *bias, float lq_u, const float *mem_bias,
@@ -505,10 +354,8 @@ extern "C" int cdml_npair_mixed_stats(const float *S, int64_t lds, const int32_t
                                       size_t workspace_bytes, cdml_stream_t stream) {
   const char *who = "npair_mixed_stats";
   if (int rc = mx_check(who, S, lds, ids, B, neg_col, mem_col, mem_id, M, bias, lq_u, mem_bias, temperature, lse)) return rc;
-  CDML_REQUIRE(stats && workspace, CDML_E_BADARG, "%s: null pointer", who);
-  CDML_REQUIRE(aligned16(workspace) && workspace_bytes >= mx_ws_bytes(B), CDML_E_BADARG,
-               "%s: the workspace must be 16-B aligned and hold cdml_npair_mixed_workspace(%d, %d) = %zu bytes (got %zu)", who, B,
-               M, mx_ws_bytes(B), workspace_bytes);
+  CDML_REQUIRE(stats, CDML_E_BADARG, "%s: null pointer (stats)", who);
+  if (int rc = np_ws_check(who, workspace, workspace_bytes, np_ws_bytes(B), "cdml_npair_mixed_workspace(B, M)")) return rc;
   if (M) {
     if (bias)
       return mx_stats_launch<true, true>(S, lds, ids, B, neg_col, mem_col, mem_id, M, bias, lq_u, mem_bias, temperature,
@@ -527,31 +374,16 @@ extern "C" int cdml_npair_mixed_grad_x3(const float *S, int64_t lds, const int32
                                         int64_t mem_col, const int32_t *mem_id, int M, const float *bias, float lq_u,
                                         const float *mem_bias, float temperature, int symmetric, const float *lse, uint16_t *W,
                                         int64_t ldw, int64_t plane, cdml_stream_t stream) {
-  const char *who = "npair_mixed_grad_x3";
-  if (int rc = mx_check(who, S, lds, ids, B, neg_col, mem_col, mem_id, M, bias, lq_u, mem_bias, temperature, lse)) return rc;
-  const int64_t span = M ? mem_col + M : neg_col + B;
-  CDML_REQUIRE(W, CDML_E_BADARG, "%s: null pointer", who);
-  CDML_REQUIRE(plane >= span && ldw >= 2 * plane + span && mult4(plane) && mult4(ldw) && (reinterpret_cast<uintptr_t>(W) & 7) == 0,
-               CDML_E_BADARG,
-               "%s: W needs an 8-B aligned base, plane >= the column span (%lld) and ldw >= 2 plane + span, both multiples "
-               "of 4 (got plane %lld, ldw %lld)", who, (long long)span, (long long)plane, (long long)ldw);
-  return mx_w_launch<true>(who, S, lds, ids, B, neg_col, mem_col, mem_id, M, bias, lq_u, mem_bias, temperature, symmetric, lse, W,
-                           ldw, plane, stream);
+  return mx_w_launch<kWX3>("npair_mixed_grad_x3", S, lds, ids, B, neg_col, mem_col, mem_id, M, bias, lq_u, mem_bias, temperature,
+                           symmetric, lse, W, ldw, plane, stream);
 }
 
 extern "C" int cdml_npair_mixed_grad_f32(const float *S, int64_t lds, const int32_t *ids, int B, int64_t neg_col,
                                          int64_t mem_col, const int32_t *mem_id, int M, const float *bias, float lq_u,
                                          const float *mem_bias, float temperature, int symmetric, const float *lse, float *W,
                                          int64_t ldw, cdml_stream_t stream) {
-  const char *who = "npair_mixed_grad_f32";
-  if (int rc = mx_check(who, S, lds, ids, B, neg_col, mem_col, mem_id, M, bias, lq_u, mem_bias, temperature, lse)) return rc;
-  const int64_t span = M ? mem_col + M : neg_col + B;
-  CDML_REQUIRE(W, CDML_E_BADARG, "%s: null pointer", who);
-  CDML_REQUIRE(ldw >= span && mult4(ldw) && aligned16(W), CDML_E_BADARG,
-               "%s: W needs a 16-B aligned base and ldw >= the column span (%lld), a multiple of 4 (got %lld)", who,
-               (long long)span, (long long)ldw);
-  return mx_w_launch<false>(who, S, lds, ids, B, neg_col, mem_col, mem_id, M, bias, lq_u, mem_bias, temperature, symmetric, lse,
-                            W, ldw, 0, stream);
+  return mx_w_launch<kWF32>("npair_mixed_grad_f32", S, lds, ids, B, neg_col, mem_col, mem_id, M, bias, lq_u, mem_bias,
+                            temperature, symmetric, lse, W, ldw, 0, stream);
 }
 
 extern "C" int cdml_npair_mixed_split_x3(const float *e, int64_t lde, int B, int D, uint16_t *A3, int64_t lda, int64_t plane_a,

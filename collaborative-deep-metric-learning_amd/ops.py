@@ -824,7 +824,7 @@ def npair_loss(e, rows, B, Dp, temperature=0.1, symmetric=True, precision="f32x3
     written into de[0::2] / de[1::2] (fp32 [2 Bp, Dp]; None: loss only).  Precision "f32x3": fp32 operands as three
     bf16 planes on the plane GEMMs; "f32": the fp32-MFMA GEMMs; "bf16": the config-4 precision -- the rows rounded to ONE
     bf16 plane, W in one bf16 plane, each product one pass of the bf16 GEMMs with fp32 accumulation (S, the statistics and
-    the gradient stay fp32; the same chain with a memory and with logQ: _npair_bf16_loss).  stats: fp32 [>= 4] (loss, mean positive distance,
+    the gradient stay fp32).  stats: fp32 [>= 4] (loss, mean positive distance,
     mean counted-negative distance, fraction of counted negatives).  ws: an NPairWorkspace (allocated here if None).
     memory: an NPairMemory (B == Bp, video ids given): its ring adds M negatives to every anchor's row term -- S = A [P;
     Mem]^T -> statistics -> W (the in-batch block + the memory block) -> dA = W [P; Mem] over K = Bp + M, dP = W^T A ->
@@ -855,194 +855,149 @@ def npair_loss(e, rows, B, Dp, temperature=0.1, symmetric=True, precision="f32x3
                 raise ValueError("a per-row logQ tensor needs 2B = %d entries, got %d" % (2 * B, logq.numel()))
         elif rows is None:
             raise ValueError("the logQ correction needs the rows' video ids")
-        if memory is None and precision != "bf16":
-            return _npair_logq_loss(e, rows, B, Dp, temperature, symmetric, precision, de, stats, ws, logq, step, step_dev)
+    return _npair_chain(e, rows, B, Dp, temperature, symmetric, precision, de, stats, ws, memory, step, step_dev, logq)
+
+
+def _npair_buffers(precision, ws, mem):
+    """(K, S, W, the row image of [P; Mem], its transposed image, the GEMM workspace): the in-batch chain's (K = Bp, from
+    the NPairWorkspace) or, with a memory, the concatenated ones it owns (K = Bp + M).  f32 has no images: None."""
+    if precision == "f32x3":
+        return (ws.Bp, ws.S, ws.W3, ws.P3, ws.PT3, ws.gemm_ws) if mem is None else \
+            (mem.K, mem.S, mem.W3, mem.PM3, mem.PMT3, mem.gemm_ws)
     if precision == "bf16":
-        return _npair_bf16_loss(e, rows, B, Dp, temperature, symmetric, de, stats, ws, memory, step, step_dev, logq)
-    if memory is not None:
-        return _npair_memory_loss(e, rows, B, Dp, temperature, symmetric, precision, de, stats, ws, memory, step, step_dev,
-                                  logq)
+        return (ws.Bp, ws.S, ws.W16, ws.P16, ws.PT16, ws.gemm_ws) if mem is None else \
+            (mem.K, mem.S, mem.W16, mem.PM16, mem.PMT16, mem.gemm_ws)
+    return (ws.Bp, ws.S, ws.Wf, None, None, None) if mem is None else (mem.K, mem.S, mem.Wf, mem.PM, None, None)
+
+
+def _npair_scores(precision, e, ws, K, S, PM, PMT, gws):
+    """The operands of the batch (the batch's part of both images of [P; Mem]) and S = A [P; Mem]^T.  Returns [P; Mem] as
+    the dA product reads it on f32 (fp32 rows)."""
+    Bp, Dp = ws.Bp, ws.Dp
     A, P = e[0::2, :Dp], e[1::2, :Dp]
-    lse = ws.lse
     if precision == "f32x3":
         Dq = ws.Dq
         split_f32_bf16x3(A, ws.A3, Dq)
-        split_f32_bf16x3(P, ws.P3, Dq)
-        split_f32_bf16x3(P, ws.PT3, Bp, transpose=True)
-        gemm_bf16x3_nt(BE_F32, ws.A3, Dq, ws.P3, Dq, ws.S, Bp, Bp, Dq, workspace=ws.gemm_ws)
+        split_f32_bf16x3(P, PM[:Bp], Dq)
+        split_f32_bf16x3(P, PMT, K, transpose=True)
+        gemm_bf16x3_nt(BE_F32, ws.A3, Dq, PM, Dq, S, Bp, K, Dq, workspace=gws)
+    elif precision == "bf16":
+        npair_operands_bf16(e, Bp, Dp, ws.A16, PM, PMT)
+        gemm_bf16_nt(BE_F32, ws.A16, PM, S, Bp, K, ws.Dq, workspace=gws)
     else:
-        fc_bwd_data(A, P, None, ws.S, Bp, Bp, Dp)              # S[i][j] = <a_i, p_j>
-    npair_stats(ws.S, rows, B, temperature, symmetric, lse, stats, ws.ws)
-    if de is None:
-        return stats, lse
-    dA, dP = de[0::2], de[1::2]
-    if precision == "f32x3":
-        npair_grad_x3(ws.S, rows, B, temperature, symmetric, lse, ws.W3, Bp)
-        oA = dA if ws.dA is None else ws.dA
-        oP = dP if ws.dP is None else ws.dP
-        gemm_bf16x3_nt(BE_F32, ws.W3, Bp, ws.PT3, Bp, oA, Bp, Dq, Bp, workspace=ws.gemm_ws)      # dA = W . P
-        gemm_bf16x3_tn(ws.W3, Bp, ws.A3, Dq, oP, Bp, Dq, Bp, workspace=ws.gemm_ws)               # dP = W^T . A
-        if ws.dA is not None:
-            dA.copy_(ws.dA[:, :Dp])
-            dP.copy_(ws.dP[:, :Dp])
-    else:
-        npair_grad_f32(ws.S, rows, B, temperature, symmetric, lse, ws.Wf)
-        fc_lrelu_fwd(ws.Wf, P, ws.zero_bias, dA, Bp, Bp, Dp, alpha=1.0)      # dA = W . P (x W form, identity activation)
-        fc_bwd_weight(ws.Wf, A, dP, None, ws.bw, Bp, Bp, Dp)                 # dP = W^T . A (x^T dy form)
-    return stats, lse
+        if PM is None:
+            PM = P
+        else:
+            PM[:Bp].copy_(P)
+        fc_bwd_data(A, PM, None, S, Bp, K, Dp)                # S[i][j] = <a_i, [p; mem]_j>
+    return PM
 
 
-def _npair_bf16_loss(e, rows, B, Dp, temperature, symmetric, de, stats, ws, mem, step, step_dev, logq):
-    """npair_loss on precision "bf16", with or without a memory and a logQ correction -- the launches in the order of the
-    other precisions' chains: the logQ gather, the operand images (one launch), S = A [P; Mem]^T, the statistics (the fp32
-    launches as they are: S is the bf16 GEMM's fp32 output), W in one bf16 plane (the in-batch block, the memory block),
-    the estimator's update, dA = W [P; Mem] against the transposed image, dP = W^T A over the in-batch block, the ring push."""
-    Bp, Dq, lse = ws.Bp, ws.Dq, ws.lse
-    if mem is None:
-        K, P16, PT16, S, W16, gws = Bp, ws.P16, ws.PT16, ws.S, ws.W16, ws.gemm_ws
-    else:
-        if (mem.Bp, mem.Dp, mem.precision) != (Bp, Dp, "bf16"):
-            raise ValueError("NPairMemory is for %d pairs x %d columns on %s" % (mem.Bp, mem.Dp, mem.precision))
-        if B != Bp or rows is None:
-            raise ValueError("the cross-batch memory needs an unpadded batch (B == Bp) and the rows' video ids")
-        K, P16, PT16, S, W16, gws = mem.K, mem.PM16, mem.PMT16, mem.S, mem.W16, mem.gemm_ws
-    bias = mem_bias = None
-    if logq is not None:
-        bias = ws.bias
-        if isinstance(logq, torch.Tensor):
-            bias[:2 * B].copy_(logq.reshape(-1)[:2 * B])
-            logq = None
-        elif mem is None:
-            logq.gather(rows, B, None, bias, None)
-        else:                                                   # (the gather reads the ring's ids before this step's push)
-            mem_bias = mem.bias
-            logq.gather(rows, B, mem.ids, bias, mem_bias)
-    npair_operands_bf16(e, Bp, Dp, ws.A16, P16, PT16)            # [P; Mem]: the batch's part of both operand images
-    gemm_bf16_nt(BE_F32, ws.A16, P16, S, Bp, K, Dq, workspace=gws)
+def _npair_any_stats(S, rows, B, bias, mem, mem_bias, temperature, symmetric, lse, stats, workspace):
     if mem is None and bias is None:
-        npair_stats(S, rows, B, temperature, symmetric, lse, stats, ws.ws)
+        npair_stats(S, rows, B, temperature, symmetric, lse, stats, workspace)
     elif mem is None:
-        npair_logq_stats(S, rows, B, bias, temperature, symmetric, lse, stats, ws.ws)
+        npair_logq_stats(S, rows, B, bias, temperature, symmetric, lse, stats, workspace)
     elif bias is None:
-        npair_memory_stats(S, rows, B, Bp, mem.ids, temperature, symmetric, lse, stats, ws.ws)
+        npair_memory_stats(S, rows, B, mem.Bp, mem.ids, temperature, symmetric, lse, stats, workspace)
     else:
-        npair_memory_logq_stats(S, rows, B, bias, Bp, mem.ids, mem_bias, temperature, symmetric, lse, stats, ws.ws)
-    if de is None:
-        return stats, lse
+        npair_memory_logq_stats(S, rows, B, bias, mem.Bp, mem.ids, mem_bias, temperature, symmetric, lse, stats, workspace)
+
+
+def _npair_weights(precision, S, rows, B, bias, mem, mem_bias, temperature, symmetric, lse, W, K):
+    """W: the in-batch block, then the memory block."""
+    if precision == "bf16":
+        npair_grad_bf16(S, rows, B, temperature, symmetric, lse, W, bias=bias)
+        if mem is not None:
+            npair_memory_grad_bf16(S, rows, B, mem.Bp, mem.ids, temperature, symmetric, lse, W, mem_bias=mem_bias)
+        return
+    x3 = precision == "f32x3"
+    plane = (K,) if x3 else ()
+    if bias is None:
+        (npair_grad_x3 if x3 else npair_grad_f32)(S, rows, B, temperature, symmetric, lse, W, *plane)
+    else:
+        (npair_logq_grad_x3 if x3 else npair_logq_grad_f32)(S, rows, B, bias, temperature, symmetric, lse, W, *plane)
+    if mem is None:
+        return
+    if mem_bias is None:
+        (npair_memory_grad_x3 if x3 else npair_memory_grad_f32)(S, rows, B, mem.Bp, mem.ids, temperature, symmetric, lse, W,
+                                                                *plane)
+    else:
+        (npair_memory_logq_grad_x3 if x3 else npair_memory_logq_grad_f32)(S, rows, B, mem.Bp, mem.ids, mem_bias, temperature,
+                                                                          symmetric, lse, W, *plane)
+
+
+def _npair_products(precision, e, ws, K, W, PM, PMT, gws, de):
+    """dA = W [P; Mem] over K, dP = W^T A over the in-batch block of W, into de[0::2] / de[1::2]."""
+    Bp, Dp = ws.Bp, ws.Dp
     dA, dP = de[0::2], de[1::2]
-    npair_grad_bf16(S, rows, B, temperature, symmetric, lse, W16, bias=bias)
-    if mem is not None:
-        npair_memory_grad_bf16(S, rows, B, Bp, mem.ids, temperature, symmetric, lse, W16, mem_bias=mem_bias)
-    if logq is not None:
-        logq.update(rows, B, step, step_dev)
-    oA = dA if ws.dA is None else ws.dA
+    if precision == "f32":
+        fc_lrelu_fwd(W, PM, ws.zero_bias, dA, Bp, K, Dp, alpha=1.0)          # (x W form, identity activation)
+        fc_bwd_weight(W[:, :Bp], e[0::2, :Dp], dP, None, ws.bw, Bp, Bp, Dp)  # (x^T dy form)
+        return
+    Dq = ws.Dq
+    oA = dA if ws.dA is None else ws.dA                     # (rows narrower than the tile: the products land here first)
     oP = dP if ws.dP is None else ws.dP
-    gemm_bf16_nt(BE_F32, W16, PT16, oA, Bp, Dq, K, workspace=gws)          # dA = W . [P; Mem]
-    gemm_bf16_tn(W16, ws.A16, oP, Bp, Dq, Bp, workspace=gws)               # dP = W^T . A (the in-batch block of W)
+    if precision == "f32x3":
+        gemm_bf16x3_nt(BE_F32, W, K, PMT, K, oA, Bp, Dq, K, workspace=gws)
+        gemm_bf16x3_tn(W, K, ws.A3, Dq, oP, Bp, Dq, Bp, workspace=gws)
+    else:
+        gemm_bf16_nt(BE_F32, W, PMT, oA, Bp, Dq, K, workspace=gws)
+        gemm_bf16_tn(W, ws.A16, oP, Bp, Dq, Bp, workspace=gws)
     if ws.dA is not None:
         dA.copy_(ws.dA[:, :Dp])
         dP.copy_(ws.dP[:, :Dp])
-    if mem is not None:
-        npair_memory_push_bf16(e[1::2, :Dp], rows, Bp, Dp, step, step_dev, mem.start, mem.rows, mem.ids, mem.PM16[Bp:],
-                               mem.PMT16[:, Bp:])
-    return stats, lse
 
 
-def _npair_logq_loss(e, rows, B, Dp, temperature, symmetric, precision, de, stats, ws, logq, step, step_dev):
-    """npair_loss's in-batch chain with the logQ correction (the gather, the BIAS passes, the estimator's update)."""
-    Bp = ws.Bp
-    A, P = e[0::2, :Dp], e[1::2, :Dp]
-    lse, bias = ws.lse, ws.bias
-    if isinstance(logq, torch.Tensor):
-        bias[:2 * B].copy_(logq.reshape(-1)[:2 * B])
-        logq = None
-    else:
-        logq.gather(rows, B, None, bias, None)
+def _npair_push(precision, P, rows, ws, mem, step, step_dev):
+    """This step's positives into the ring, with the slots' part of the operand images the precision keeps."""
+    Bp, Dp = ws.Bp, ws.Dp
     if precision == "f32x3":
-        Dq = ws.Dq
-        split_f32_bf16x3(A, ws.A3, Dq)
-        split_f32_bf16x3(P, ws.P3, Dq)
-        split_f32_bf16x3(P, ws.PT3, Bp, transpose=True)
-        gemm_bf16x3_nt(BE_F32, ws.A3, Dq, ws.P3, Dq, ws.S, Bp, Bp, Dq, workspace=ws.gemm_ws)
-    else:
-        fc_bwd_data(A, P, None, ws.S, Bp, Bp, Dp)
-    npair_logq_stats(ws.S, rows, B, bias, temperature, symmetric, lse, stats, ws.ws)
-    if de is None:
-        return stats, lse
-    dA, dP = de[0::2], de[1::2]
-    if precision == "f32x3":
-        npair_logq_grad_x3(ws.S, rows, B, bias, temperature, symmetric, lse, ws.W3, Bp)
-        if logq is not None:
-            logq.update(rows, B, step, step_dev)
-        oA = dA if ws.dA is None else ws.dA
-        oP = dP if ws.dP is None else ws.dP
-        gemm_bf16x3_nt(BE_F32, ws.W3, Bp, ws.PT3, Bp, oA, Bp, Dq, Bp, workspace=ws.gemm_ws)
-        gemm_bf16x3_tn(ws.W3, Bp, ws.A3, Dq, oP, Bp, Dq, Bp, workspace=ws.gemm_ws)
-        if ws.dA is not None:
-            dA.copy_(ws.dA[:, :Dp])
-            dP.copy_(ws.dP[:, :Dp])
-    else:
-        npair_logq_grad_f32(ws.S, rows, B, bias, temperature, symmetric, lse, ws.Wf)
-        if logq is not None:
-            logq.update(rows, B, step, step_dev)
-        fc_lrelu_fwd(ws.Wf, P, ws.zero_bias, dA, Bp, Bp, Dp, alpha=1.0)
-        fc_bwd_weight(ws.Wf, A, dP, None, ws.bw, Bp, Bp, Dp)
-    return stats, lse
-
-
-def _npair_memory_loss(e, rows, B, Dp, temperature, symmetric, precision, de, stats, ws, mem, step, step_dev, logq=None):
-    Bp, M, K = ws.Bp, mem.M, mem.K
-    if (mem.Bp, mem.Dp, mem.precision) != (Bp, Dp, precision):
-        raise ValueError("NPairMemory is for %d pairs x %d columns on %s" % (mem.Bp, mem.Dp, mem.precision))
-    if B != Bp or rows is None:
-        raise ValueError("the cross-batch memory needs an unpadded batch (B == Bp) and the rows' video ids")
-    A, P = e[0::2, :Dp], e[1::2, :Dp]
-    lse = ws.lse
-    if precision == "f32x3":
-        Dq = ws.Dq
-        split_f32_bf16x3(A, ws.A3, Dq)
-        split_f32_bf16x3(P, mem.PM3[:Bp], Dq)                        # [P; Mem]: the batch's part of both operand images
-        split_f32_bf16x3(P, mem.PMT3, K, transpose=True)
-        gemm_bf16x3_nt(BE_F32, ws.A3, Dq, mem.PM3, Dq, mem.S, Bp, K, Dq, workspace=mem.gemm_ws)     # S = A [P; Mem]^T
-    else:
-        mem.PM[:Bp].copy_(P)
-        fc_bwd_data(A, mem.PM, None, mem.S, Bp, K, Dp)
-    if logq is None:
-        npair_memory_stats(mem.S, rows, B, Bp, mem.ids, temperature, symmetric, lse, stats, ws.ws)
-    else:                                                       # (the gather reads the ring's ids before this step's push)
-        logq.gather(rows, B, mem.ids, ws.bias, mem.bias)
-        npair_memory_logq_stats(mem.S, rows, B, ws.bias, Bp, mem.ids, mem.bias, temperature, symmetric, lse, stats, ws.ws)
-    if de is None:
-        return stats, lse
-    dA, dP = de[0::2], de[1::2]
-    if precision == "f32x3":
-        if logq is None:
-            npair_grad_x3(mem.S, rows, B, temperature, symmetric, lse, mem.W3, K)
-            npair_memory_grad_x3(mem.S, rows, B, Bp, mem.ids, temperature, symmetric, lse, mem.W3, K)
-        else:
-            npair_logq_grad_x3(mem.S, rows, B, ws.bias, temperature, symmetric, lse, mem.W3, K)
-            npair_memory_logq_grad_x3(mem.S, rows, B, Bp, mem.ids, mem.bias, temperature, symmetric, lse, mem.W3, K)
-            logq.update(rows, B, step, step_dev)
-        oA = dA if ws.dA is None else ws.dA
-        oP = dP if ws.dP is None else ws.dP
-        gemm_bf16x3_nt(BE_F32, mem.W3, K, mem.PMT3, K, oA, Bp, Dq, K, workspace=mem.gemm_ws)      # dA = W . [P; Mem]
-        gemm_bf16x3_tn(mem.W3, K, ws.A3, Dq, oP, Bp, Dq, Bp, workspace=mem.gemm_ws)               # dP = W^T . A
-        if ws.dA is not None:
-            dA.copy_(ws.dA[:, :Dp])
-            dP.copy_(ws.dP[:, :Dp])
-        npair_memory_push(P, rows, Bp, Dp, step, step_dev, mem.start, mem.rows, mem.ids, R3=mem.PM3[Bp:], plane_r=Dq,
-                          T3=mem.PMT3[:, Bp:], plane_t=K)
-    else:
-        if logq is None:
-            npair_grad_f32(mem.S, rows, B, temperature, symmetric, lse, mem.Wf)
-            npair_memory_grad_f32(mem.S, rows, B, Bp, mem.ids, temperature, symmetric, lse, mem.Wf)
-        else:
-            npair_logq_grad_f32(mem.S, rows, B, ws.bias, temperature, symmetric, lse, mem.Wf)
-            npair_memory_logq_grad_f32(mem.S, rows, B, Bp, mem.ids, mem.bias, temperature, symmetric, lse, mem.Wf)
-            logq.update(rows, B, step, step_dev)
-        fc_lrelu_fwd(mem.Wf, mem.PM, ws.zero_bias, dA, Bp, K, Dp, alpha=1.0)          # dA = W . [P; Mem]
-        fc_bwd_weight(mem.Wf[:, :Bp], A, dP, None, ws.bw, Bp, Bp, Dp)                 # dP = W^T . A
+        npair_memory_push(P, rows, Bp, Dp, step, step_dev, mem.start, mem.rows, mem.ids, R3=mem.PM3[Bp:], plane_r=ws.Dq,
+                          T3=mem.PMT3[:, Bp:], plane_t=mem.K)
+    elif precision == "bf16":
+        npair_memory_push_bf16(P, rows, Bp, Dp, step, step_dev, mem.start, mem.rows, mem.ids, mem.PM16[Bp:], mem.PMT16[:, Bp:])
+    else:                                                   # (the ring's rows ARE the last M rows of [P; Mem])
         npair_memory_push(P, rows, Bp, Dp, step, step_dev, mem.start, mem.rows, mem.ids)
+
+
+def _npair_chain(e, rows, B, Dp, temperature, symmetric, precision, de, stats, ws, mem, step, step_dev, logq):
+    """npair_loss's one chain, for every precision, with or without a memory and a logQ correction: the logQ gather, the
+    operands, S = A [P; Mem]^T, the statistics, W (the in-batch block, the memory block), the estimator's update, dA and dP,
+    the ring push -- in that order (the gather reads the ring's ids before this step's push; the update follows the
+    launches that read the bias)."""
+    Bp, lse = ws.Bp, ws.lse
+    if mem is not None:
+        if (mem.Bp, mem.Dp, mem.precision) != (Bp, Dp, precision):
+            raise ValueError("NPairMemory is for %d pairs x %d columns on %s" % (mem.Bp, mem.Dp, mem.precision))
+        if B != Bp or rows is None:
+            raise ValueError("the cross-batch memory needs an unpadded batch (B == Bp) and the rows' video ids")
+    K, S, W, PM, PMT, gws = _npair_buffers(precision, ws, mem)
+    bias = None if logq is None else ws.bias
+    mem_bias = None if logq is None or mem is None else mem.bias
+    # (the plane and fp32 chains with a memory gather after S, the others before the operands: the order they were built in)
+    late = mem is not None and precision != "bf16"
+
+    def gather():
+        if isinstance(logq, torch.Tensor):
+            bias[:2 * B].copy_(logq.reshape(-1)[:2 * B])
+        elif logq is not None:
+            logq.gather(rows, B, None if mem is None else mem.ids, bias, mem_bias)
+
+    if not late:
+        gather()
+    PM = _npair_scores(precision, e, ws, K, S, PM, PMT, gws)
+    if late:
+        gather()
+    _npair_any_stats(S, rows, B, bias, mem, mem_bias, temperature, symmetric, lse, stats, ws.ws)
+    if de is None:
+        return stats, lse
+    _npair_weights(precision, S, rows, B, bias, mem, mem_bias, temperature, symmetric, lse, W, K)
+    if logq is not None and not isinstance(logq, torch.Tensor):
+        logq.update(rows, B, step, step_dev)
+    _npair_products(precision, e, ws, K, W, PM, PMT, gws, de)
+    if mem is not None:
+        _npair_push(precision, e[1::2, :Dp], rows, ws, mem, step, step_dev)
     return stats, lse
 
 

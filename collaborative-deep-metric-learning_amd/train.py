@@ -92,7 +92,7 @@ class TrainStep:
         positive->anchor terms), both build-defined; the reference has no such loss.  One GPU; fp32 catalogue, precision
         "f32x3" (a batch that is a multiple of 256 pairs; what "auto" picks then) or "f32" (a multiple of 64), or an fp16
         catalogue on precision "bf16" (config 4; a multiple of 256 pairs; "auto" there): the rows and the gradient weights in
-        one bf16 plane each, every product one pass of the bf16 GEMMs (ops._npair_bf16_loss) -- with ``memory_size`` and
+        one bf16 plane each, every product one pass of the bf16 GEMMs (ops._npair_chain) -- with ``memory_size`` and
         ``logq``, not with ``uniform_negatives``, ``npair_sync`` or ``train_table``; the
         embeddings' gradient goes through the separate l2norm backward (no fused tail, so no ``variance`` summary).
         ``memory_size`` (mode "npair"; 0 = none): a cross-batch memory of the last ``memory_size`` positives (XBM, Wang et
@@ -223,7 +223,7 @@ class TrainStep:
                 raise ValueError("mode 'npair' runs on precision 'f32x3' or 'f32' (an fp32 catalogue) or 'bf16' (an fp16 "
                                  "catalogue), not %r" % (precision,))
             if precision == "bf16":
-                # the config-4 chain (ops._npair_bf16_loss) is the in-batch softmax with a memory and logQ; the mixed and
+                # the config-4 chain (ops._npair_chain) is the in-batch softmax with a memory and logQ; the mixed and
                 # the data-parallel chains have no one-plane form
                 for name, on in (("uniform_negatives", uniform_negatives), ("npair_sync", npair_sync is not None)):
                     if on:

@@ -84,6 +84,29 @@ def test_no_gemm_kernel_has_a_scratch_frame(built):
     g._check_no_scratch([f[:-8] + ".o" for f in rem])
 
 
+def test_no_npair_kernel_has_a_scratch_frame(built):
+    """The N-pair launches (k_npair_*, k_mixed_*, k_npdp_*) are bandwidth-bound passes sized for full occupancy with no
+    spill; build() refuses a scratch frame in any of them, and this test reads the compiler's resource remarks again."""
+    import glob
+    import re
+    import __graft_entry__ as g
+    rem = sorted(glob.glob(os.path.join(ROOT, "build", "obj", "npair*.remarks")))
+    assert len(rem) >= 4, "build() writes <object>.remarks for every source"
+    seen = 0
+    for f in rem:
+        name = None
+        for ln in open(f):
+            m = re.search(r"Function Name: (\S+)", ln)
+            if m:
+                name = m.group(1)
+            m = re.search(r"ScratchSize \[bytes/lane\]: (\d+)", ln)
+            if m and name and any(k in name for k in g.NPAIR_KERNELS):
+                seen += 1
+                assert int(m.group(1)) == 0, (name, ln)
+    assert seen >= 51                                  # every instantiation of the family's kernels reports
+    g._check_no_scratch([f[:-8] + ".o" for f in rem])
+
+
 def test_argument_errors_need_no_gpu(built):
     """Validation happens before any HIP call, so the status/message contract is
     testable on CPU: null pointers -> CDML_E_BADARG with a message."""
