@@ -8,6 +8,8 @@
   TowerWorkspace caller-owned activations / workspaces for a fixed row count
   tower_forward / tower_backward   the kernel sequence of VNet.create_model
                  (models.py:46-62) and of its autodiff (train.py:141)
+  EngineWorkspace / Engine / get_engine   the ONE interface of the four precisions and the one place
+                 that maps a precision name to it
 
 Padding: F -> Fp (x64), H -> Hp (x128), D -> Dp (x64).  Padded weights, biases
 and table columns are zero, every kernel keeps them zero (zero activations ->
@@ -32,9 +34,12 @@ class FeatureTable:
     [row0, row0+n_rows).  row_stride*4 is a multiple of 128 B so every row starts
     on a cache line and doubles as the GEMM's K padding."""
 
+    DTYPE, NP_DTYPE, KIND = torch.float32, np.float32, "fp32"      # (engine_bf16.FeatureTableF16: the fp16 catalogue)
+    _fill = staticmethod(ops.fill_uniform_table)
+
     def __init__(self, data, feature_size, row0=0, n_rows_global=None):
-        if not data.is_cuda or data.dtype != torch.float32 or data.dim() != 2:
-            raise ValueError("FeatureTable needs a 2-D fp32 device tensor")
+        if not data.is_cuda or data.dtype != self.DTYPE or data.dim() != 2:
+            raise ValueError("%s needs a 2-D %s device tensor" % (type(self).__name__, self.KIND))
         self.data = data
         self.feature_size = int(feature_size)
         self.row0 = int(row0)
@@ -48,9 +53,9 @@ class FeatureTable:
     @classmethod
     def from_numpy(cls, features, device, row0=0, n_rows_global=None):
         """features.npy contents (float32 [N,F], online_data.py:87-93) -> HBM."""
-        f = np.asarray(features, dtype=np.float32)
+        f = np.asarray(features, dtype=cls.NP_DTYPE)
         n, F = f.shape
-        data = torch.zeros((n, cls.padded_stride(F)), dtype=torch.float32, device=device)
+        data = torch.zeros((n, cls.padded_stride(F)), dtype=cls.DTYPE, device=device)
         data[:, :F] = torch.from_numpy(f).to(device)
         return cls(data, F, row0, n_rows_global)
 
@@ -58,9 +63,8 @@ class FeatureTable:
     def synthetic(cls, n_rows, feature_size, seed, device, row0=0, n_rows_global=None):
         """imitation_data.py-shaped U[0,1) table generated in HBM by the HIP fill
         kernel (a 6-60 GB table is not generated on the host)."""
-        data = torch.empty((n_rows, cls.padded_stride(feature_size)), dtype=torch.float32,
-                           device=device)
-        ops.fill_uniform_table(data, row0, feature_size, seed)
+        data = torch.empty((n_rows, cls.padded_stride(feature_size)), dtype=cls.DTYPE, device=device)
+        cls._fill(data, row0, feature_size, seed)
         return cls(data, feature_size, row0, n_rows_global)
 
     def rows(self, idx):
@@ -69,11 +73,10 @@ class FeatureTable:
 
 
 class TowerLayout:
-    def __init__(self, feature_size, hidden=5000, output_size=256):
+    def __init__(self, feature_size, hidden=5000, output_size=256, pad=(64, 128, 64)):
+        """``pad``: the multiples F, H and D are padded to (layout_bf16, layout_x3: their kernels' tiles)."""
         self.F, self.H, self.D = int(feature_size), int(hidden), int(output_size)
-        self.Fp = round_up(self.F, 64)
-        self.Hp = round_up(self.H, 128)
-        self.Dp = round_up(self.D, 64)
+        self.Fp, self.Hp, self.Dp = round_up(self.F, pad[0]), round_up(self.H, pad[1]), round_up(self.D, pad[2])
         self.sizes = (self.Fp * self.Hp, self.Hp, self.Hp * self.Dp, self.Dp)
         self.offsets = tuple(int(x) for x in np.cumsum((0,) + self.sizes[:-1]))
         self.numel = int(sum(self.sizes))
@@ -130,11 +133,58 @@ class VNetParams:
         return {n: t.detach().cpu().clone() for n, t in zip(self.NAMES, self.unpadded())}
 
 
-class TowerWorkspace:
+class EngineWorkspace:
+    """What every precision's workspace answers, the fp32 engine's answers as the defaults: an engine
+    overrides only what it has, and TrainStep, Prediction and FusionTower ask these and never which engine they hold."""
+    ROWS = 1                        # the row count must be a multiple of this
+    WIDTHS = 1                      # ... and the layout's padded widths of this (beyond TowerLayout's own)
+    MAX_ROWS = None                 # the most rows one forward pass takes (None: no limit below the 2 GiB operand range)
+    TABLE_DTYPE = torch.float32     # the catalogue this precision gathers from
+    INFERENCE = "f32"               # the precision catalogue inference runs on for a step of this one
+    EXCHANGE_PLANES = False         # the row exchange of a sharded catalogue writes x_hat in the gather's plane form
+    # state that the kernel sequences and the callers read whatever the engine
+    h1_bits = xk = W1n = scales = None
+    kint = tail_done = dz2_planes_done = False
+
+    def tail_operands(self, indexed=False):
+        """(keywords, planes_done): what ops.vnet_tail (``indexed``: ops.triplet_hinge_indexed) writes besides fp32 dz2 --
+        ``dz2_bf16``, ``plane_bf``, ``h2_scale`` -- and whether the backward pass reads that form as it is."""
+        return {}, False
+
+    def miner_operands(self):       # None, or (planes, dtype, h2_scale) of the semi-hard miner on the plane kernels
+        return None                 # (ops.semihard_mine_x3), whose prep launch may then normalise z itself
+
+    def optimizer_operands(self):   # None (the flat update), or (W1's, W2's) keywords of the two matrix launches: the
+        return None                 # operand copies written with the update -- wt, plane_t, wc, plane_c, h2_scale
+
+    def enable_row_gradient(self, p):                # a trainable catalogue: what row_gradient needs (the planes' W1n)
+        pass
+
+    def row_gradient(self, p, dxh):                  # dxh = dLoss/dx_hat = dz1 . W1^T for the workspace's rows
+        ops.fc_bwd_data(self.dz1, p.W1, None, dxh, self.R, self.layout.Fp, self.layout.Hp)
+
+    # the delayed-scale hooks of precision f16x2 (engine_f16x2.PlaneScales); nothing to do anywhere else
+    def scales_due(self, step=None):                 # a check step (``step`` None: the scales have never been calibrated)
+        return False
+
+    def observe_weights(self, p):                    # True: the weights' operand copies are dealt with too
+        return False
+
+    def observe_gradients(self, p):
+        pass
+
+    def scales_state(self):         # what a checkpoint keeps of them
+        return None
+
+    def load_scales(self, p, saved):                 # ``saved``: a checkpoint's scales_state or None.  True: the weights'
+        return False                                 # operand copies are dealt with (at those scales); False: refresh them
+
+
+class TowerWorkspace(EngineWorkspace):
     """Activations and scratch for R rows.  Allocated once by the caller; the
     step path allocates nothing (hipGraph-capturable)."""
 
-    def __init__(self, layout, n_rows, device, backward=True):
+    def __init__(self, layout, n_rows, device, backward=True, **plane_options):
         L = layout
         self.layout, self.R = layout, int(n_rows)
         z = lambda *s: torch.zeros(s, dtype=torch.float32, device=device)
@@ -142,6 +192,7 @@ class TowerWorkspace:
         self.h1 = z(n_rows, L.Hp)
         self.z = z(n_rows, L.Dp)
         self.e = z(n_rows, L.Dp)
+        self.sk_bytes = 0
         if backward:
             self.de = z(n_rows, L.Dp)
             self.dz2 = z(n_rows, L.Dp)
@@ -153,6 +204,10 @@ class TowerWorkspace:
                          # dW1 in two row blocks (data-parallel runs, tower_backward w1_chunks=2)
                          ops.fc_bwd_weight_workspace(n_rows, L.Fp // 2, L.Hp) if L.Fp % 256 == 0 else 0)
             self.bw = torch.empty(nbytes // 4, dtype=torch.float32, device=device)
+
+
+def refresh_weights(p, ws):
+    """The fp32 MFMA reads the master weights: no operand copies to refresh."""
 
 
 def tower_forward(p, ws, n_rows=None, normalize=True):
@@ -173,6 +228,22 @@ def tower_forward(p, ws, n_rows=None, normalize=True):
     return ws.e
 
 
+def dw1_in_blocks(p, dw1, w1_chunks, after_w1_chunk, can_split):
+    """dW1 through ``dw1(lo, hi, db)`` (rows lo .. hi of W1; db1 into ``db`` unless None): whole, or -- ``can_split(rows per
+    block)`` -- in ``w1_chunks`` row blocks with ``after_w1_chunk(flat-gradient range)`` after each.  Every engine's backward."""
+    L = p.layout
+    rows = L.Fp // w1_chunks if w1_chunks > 1 else 0
+    if after_w1_chunk is not None and w1_chunks > 1 and rows * w1_chunks == L.Fp and can_split(rows):
+        for c in range(w1_chunks):
+            last = c == w1_chunks - 1
+            dw1(c * rows, (c + 1) * rows, p.gb1 if last else None)
+            after_w1_chunk(c * rows * L.Hp, (c + 1) * rows * L.Hp + (L.Hp if last else 0))
+    else:
+        dw1(0, L.Fp, p.gb1)
+        if after_w1_chunk is not None:
+            after_w1_chunk(0, L.Fp * L.Hp + L.Hp)
+
+
 def tower_backward(p, ws, n_rows=None, after_w1=None, w1_chunks=1, after_w1_chunk=None):
     """ws.de (grad wrt e) -> p.grad (dW1, db1, dW2, db2).  No dX: the features are
     inputs, not variables (train.py:265).  The first layer's gradient (85 % of the
@@ -185,28 +256,52 @@ def tower_backward(p, ws, n_rows=None, after_w1=None, w1_chunks=1, after_w1_chun
     c+1 and only the last, smaller one is left for the dW2 GEMM to cover."""
     L = p.layout
     R = ws.R if n_rows is None else n_rows
-    if not getattr(ws, "tail_done", False):          # the fused tail has already produced dz2
+    if not ws.tail_done:                             # the fused tail has already produced dz2
         ops.l2norm_bwd(ws.z[:R], ws.de[:R], L.Dp, ws.dz2, lrelu_alpha=ops.LRELU_ALPHA)
     ops.fc_bwd_data(ws.dz2, p.W2, ws.h1, ws.dz1, R, L.Hp, L.Dp)
-    rows = L.Fp // w1_chunks if w1_chunks > 1 else 0
-    if (after_w1 is None and after_w1_chunk is None and getattr(ws, "sk_bytes", 0) and R == ws.R
+    if (after_w1 is None and after_w1_chunk is None and ws.sk_bytes and R == ws.R
             and not os.environ.get("CDML_NO_STREAMK")):
         # single GPU: nothing waits for dW1 alone, so both products share one stream-K launch
         ops.fc_bwd_weight2(ws.x_hat, ws.dz1, p.gW1, p.gb1, L.Fp, L.Hp, ws.h1, ws.dz2, p.gW2, p.gb2, L.Hp, L.Dp,
                            R, ws.bw)
         return p.grad
-    if after_w1_chunk is not None and w1_chunks > 1 and rows % 128 == 0 and rows * w1_chunks == L.Fp:
-        for c in range(w1_chunks):
-            lo, hi = c * rows, (c + 1) * rows
-            last = c == w1_chunks - 1
-            ops.fc_bwd_weight(ws.x_hat[:, lo:hi], ws.dz1, p.gW1[lo:hi], p.gb1 if last else None, ws.bw,
-                              R, rows, L.Hp)
-            after_w1_chunk(lo * L.Hp, hi * L.Hp + (L.Hp if last else 0))
-    else:
-        ops.fc_bwd_weight(ws.x_hat, ws.dz1, p.gW1, p.gb1, ws.bw, R, L.Fp, L.Hp)
-        if after_w1_chunk is not None:
-            after_w1_chunk(0, L.Fp * L.Hp + L.Hp)
+    dw1_in_blocks(p, lambda lo, hi, db: ops.fc_bwd_weight(ws.x_hat[:, lo:hi], ws.dz1, p.gW1[lo:hi], db, ws.bw, R, hi - lo, L.Hp),
+                  w1_chunks, after_w1_chunk, lambda rows: rows % 128 == 0)
     if after_w1 is not None:
         after_w1()
     ops.fc_bwd_weight(ws.h1, ws.dz2, p.gW2, p.gb2, ws.bw, R, L.Hp, L.Dp)
     return p.grad
+
+
+class Engine:
+    """One precision: layout function, workspace constructor and the kernel sequences refresh_weights(p, ws), tower_forward(p,
+    ws, normalize=True) (fp32 also takes n_rows=) and tower_backward(p, ws, after_w1=None, w1_chunks=1, after_w1_chunk=None)."""
+
+    def __init__(self, name, module, layout, Workspace, **ws_args):
+        self.name, self.layout, self.Workspace, self.ws_args = name, layout, Workspace, ws_args
+        self.rows, self.table_dtype = self.Workspace.ROWS, self.Workspace.TABLE_DTYPE
+        self.refresh_weights, self.tower_forward, self.tower_backward = (
+            module.refresh_weights, module.tower_forward, module.tower_backward)
+
+    def workspace(self, layout, n_rows, device, backward=True, **options):
+        """``options``: planes_in, kint, fc2_single_pass -- an engine's constructor ignores the ones it does not have."""
+        return self.Workspace(layout, n_rows, device, backward=backward, **dict(self.ws_args, **options))
+
+
+def get_engine(precision):
+    """The engine of a precision name (TrainStep's; "auto" first goes through auto_precision)."""
+    import sys
+    from . import engine_bf16 as b, engine_f16x2 as h, engine_x3 as x
+    engines = {"f32": (sys.modules[__name__], TowerLayout, TowerWorkspace, {}),
+               "bf16": (b, b.layout_bf16, b.TowerWorkspaceBF16, {}), "f16x2": (h, x.layout_x3, h.TowerWorkspaceH2, {}),
+               "f32x3": (x, x.layout_x3, x.TowerWorkspaceX3, {"products": 6}),
+               "f32x3-3": (x, x.layout_x3, x.TowerWorkspaceX3, {"products": 3})}
+    if precision not in engines:
+        raise ValueError("precision must be 'auto', 'f32', 'f32x3', 'f16x2' or 'bf16'")
+    return Engine(precision, *engines[precision][:3], **engines[precision][3])
+
+
+def auto_precision(table_dtype, rows, tile=128):
+    """precision "auto": "bf16" for an fp16 catalogue (config 4), else "f32x3" (what bench.py times) when ``rows`` -- the step's
+    rows, or an N-pair batch against its loss chain's ``tile`` -- is a multiple of ``tile``, else "f32" (the fp32 MFMA)."""
+    return "bf16" if table_dtype == torch.float16 else "f32x3" if rows % tile == 0 else "f32"

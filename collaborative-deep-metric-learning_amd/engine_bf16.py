@@ -11,56 +11,28 @@ unit-norm embeddings, 2e-2 on the loss.
 """
 import os
 
+import numpy as np
 import torch
 
 from . import ops
-from .engine import FeatureTable, TowerLayout, round_up
+from .engine import EngineWorkspace, FeatureTable, TowerLayout, dw1_in_blocks
 
 
 class FeatureTableF16(FeatureTable):
     """fp16 catalogue shard [n_rows, row_stride] (3 KB rows at F=1500)."""
-
-    def __init__(self, data, feature_size, row0=0, n_rows_global=None):
-        if not data.is_cuda or data.dtype != torch.float16 or data.dim() != 2:
-            raise ValueError("FeatureTableF16 needs a 2-D fp16 device tensor")
-        self.data = data
-        self.feature_size = int(feature_size)
-        self.row0 = int(row0)
-        self.n_rows = data.shape[0]
-        self.n_rows_global = self.n_rows if n_rows_global is None else int(n_rows_global)
-
-    @classmethod
-    def from_numpy(cls, features, device, row0=0, n_rows_global=None):
-        import numpy as np
-        f = np.asarray(features, dtype=np.float16)
-        n, F = f.shape
-        data = torch.zeros((n, cls.padded_stride(F)), dtype=torch.float16, device=device)
-        data[:, :F] = torch.from_numpy(f).to(device)
-        return cls(data, F, row0, n_rows_global)
-
-    @classmethod
-    def synthetic(cls, n_rows, feature_size, seed, device, row0=0, n_rows_global=None):
-        data = torch.empty((n_rows, cls.padded_stride(feature_size)), dtype=torch.float16, device=device)
-        ops.fill_uniform_table_f16(data, row0, feature_size, seed)
-        return cls(data, feature_size, row0, n_rows_global)
+    DTYPE, NP_DTYPE, KIND = torch.float16, np.float16, "fp16"
+    _fill = staticmethod(ops.fill_uniform_table_f16)
 
 
 def layout_bf16(feature_size, hidden=5000, output_size=256):
     """TowerLayout whose padded sizes satisfy the bf16 GEMM (N % 128, K % 64)."""
-    L = TowerLayout(feature_size, hidden, output_size)
-    if L.Dp % 128:
-        L.Dp = round_up(L.D, 128)
-        L.sizes = (L.Fp * L.Hp, L.Hp, L.Hp * L.Dp, L.Dp)
-        off = [0]
-        for n in L.sizes[:-1]:
-            off.append(off[-1] + n)
-        L.offsets = tuple(off)
-        L.numel = int(sum(L.sizes))
-    return L
+    return TowerLayout(feature_size, hidden, output_size, pad=(64, 128, 128))
 
 
-class TowerWorkspaceBF16:
-    def __init__(self, layout, n_rows, device, backward=True):
+class TowerWorkspaceBF16(EngineWorkspace):
+    ROWS, TABLE_DTYPE, INFERENCE = 64, torch.float16, "bf16"
+
+    def __init__(self, layout, n_rows, device, backward=True, **plane_options):
         L, R = layout, int(n_rows)
         if R % 64:
             raise ValueError("the bf16 path needs a row count that is a multiple of 64 (got %d)" % R)
@@ -105,6 +77,12 @@ class TowerWorkspaceBF16:
         self.gemm_ws = torch.empty(nb // 4, dtype=torch.float32, device=device)
         self.colsum_ws = f32(max(ops.colsum_workspace_floats(R, L.Hp), ops.colsum_workspace_floats(R, L.Dp)))
 
+    def tail_operands(self, indexed=False):
+        return {"dz2_bf16": self.dz2_bf}, False            # (the bf16 copy of dz2: both tails write it)
+
+    def optimizer_operands(self):
+        return {"wt": self.W1T}, {"wt": self.W2T, "wc": self.W2}
+
 
 def refresh_weights(p, ws):
     """bf16 operand copies of the fp32 master weights (after every optimizer step)."""
@@ -118,7 +96,7 @@ def tower_forward(p, ws, normalize=True):
     """x_hat (bf16, l2-normalised) -> h1 (bf16) -> z (fp32) -> e (fp32).  models.py:59-61.
     ``normalize=False``: stop at z (the fused tail of the training step takes over)."""
     L, R = p.layout, ws.R
-    bits = getattr(ws, "h1_bits", None)
+    bits = ws.h1_bits
     if bits is not None:
         ops.gemm_bf16_nt(ops.BE_BIAS_LRELU_BF16_BITS, ws.x_hat, ws.W1T, ws.h1, R, L.Hp, L.Fp, bias=p.b1, aux=bits)
     else:
@@ -140,7 +118,7 @@ def tower_backward(p, ws, after_w1=None, w1_chunks=1, after_w1_chunk=None):
     that follows both stream h1 (252 MB at the config-4 shape), and back to back the second pass
     finds part of it in the Infinity Cache (1.087 -> 1.070 ms per step, measured)."""
     L, R = p.layout, ws.R
-    if not getattr(ws, "tail_done", False):          # the fused tail writes dz2 and its bf16 copy
+    if not ws.tail_done:                             # the fused tail writes dz2 and its bf16 copy
         ops.l2norm_bwd(ws.z, ws.de, L.Dp, ws.dz2, lrelu_alpha=ops.LRELU_ALPHA)
         ops.cast_f32_bf16(ws.dz2, ws.dz2_bf, R, L.Dp)
     single = after_w1 is None and after_w1_chunk is None
@@ -167,26 +145,16 @@ def tower_backward(p, ws, after_w1=None, w1_chunks=1, after_w1_chunk=None):
         ops.gemm_bf16_nt(ops.BE_MASKBITS_BF16, ws.dz2_bf, ws.W2, ws.dz1, R, L.Hp, L.Dp, aux=ws.h1_bits)
     else:
         ops.gemm_bf16_nt(ops.BE_MASK_BF16, ws.dz2_bf, ws.W2, ws.dz1, R, L.Hp, L.Dp, aux=ws.h1)
-    rows = L.Fp // w1_chunks if w1_chunks > 1 else 0
-    chunked = (after_w1_chunk is not None and w1_chunks > 1 and rows * w1_chunks == L.Fp and ws.tn1
-               and ops.gemm_bf16_tn_supported(rows, L.Hp, R, L.Fp, L.Hp))
-    if chunked:
-        for c in range(w1_chunks):
-            lo, hi = c * rows, (c + 1) * rows
-            last = c == w1_chunks - 1
-            ops.gemm_bf16_tn(ws.x_hat[:, lo:hi], ws.dz1, p.gW1[lo:hi], rows, L.Hp, R, workspace=ws.gemm_ws,
-                             colsum=p.gb1 if last else None)
-            after_w1_chunk(lo * L.Hp, hi * L.Hp + (L.Hp if last else 0))
-    else:
+    def dw1(lo, hi, db):
         if ws.tn1:   # db1 = column sums of dz1, taken from the LDS tiles of the same GEMM
-            ops.gemm_bf16_tn(ws.x_hat, ws.dz1, p.gW1, L.Fp, L.Hp, R, workspace=ws.gemm_ws, colsum=p.gb1)
-        else:
+            ops.gemm_bf16_tn(ws.x_hat[:, lo:hi], ws.dz1, p.gW1[lo:hi], hi - lo, L.Hp, R, workspace=ws.gemm_ws, colsum=db)
+        else:        # (whole only: the row blocks need the k-strided form)
             ops.colsum(ws.dz1, R, L.Hp, p.gb1, ws.colsum_ws)
             ops.transpose_to_bf16(ws.dz1, ws.dz1T, R, L.Hp)
             ops.transpose_to_bf16(ws.x_hat, ws.xT, R, L.Fp)
             ops.gemm_bf16_nt(ops.BE_F32, ws.xT, ws.dz1T, p.gW1, L.Fp, L.Hp, R, workspace=ws.gemm_ws)
-        if after_w1_chunk is not None:
-            after_w1_chunk(0, L.Fp * L.Hp + L.Hp)
+    dw1_in_blocks(p, dw1, w1_chunks, after_w1_chunk,
+                  lambda rows: ws.tn1 and ops.gemm_bf16_tn_supported(rows, L.Hp, R, L.Fp, L.Hp))
     if after_w1 is not None:
         after_w1()
     if w2_first:

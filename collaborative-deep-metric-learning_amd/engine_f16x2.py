@@ -33,7 +33,8 @@ import math
 import torch
 
 from . import ops
-from .engine_x3 import layout_x3                     # the same padded widths: multiples of 256
+from .engine import EngineWorkspace, dw1_in_blocks
+from .engine_x3 import layout_x3, plane_operands     # the same padded widths: multiples of 256
 
 X_SCALE = 2.0 ** 14                                  # include/cdml.h CDML_F16X2_X_SCALE: the gather's constant
 
@@ -83,8 +84,10 @@ class PlaneScales:
         return {k: getattr(self, k) for k in ("x", "w1", "w2", "h1", "dz2", "dz1")}
 
 
-class TowerWorkspaceH2:
-    def __init__(self, layout, n_rows, device, planes_in=True, backward=True, check_every=64):
+class TowerWorkspaceH2(EngineWorkspace):
+    ROWS, WIDTHS, MAX_ROWS = 128, 256, 65536
+
+    def __init__(self, layout, n_rows, device, planes_in=True, backward=True, check_every=64, **x3_options):
         """planes_in: ``x_hat`` IS the plane buffer (the fused sampler + gather writes the fp16 planes); False: ``x_hat``
         is fp32 and the forward pass splits it."""
         L, R = layout, int(n_rows)
@@ -114,6 +117,51 @@ class TowerWorkspaceH2:
         self.tail_done = False
         self.dz2_planes_done = False
 
+    def tail_operands(self, indexed=False):
+        if indexed:                  # (the indexed tail has no fp16-plane form: the backward pass splits dz2 itself)
+            return {}, False
+        return {"dz2_bf16": self.dz2_2, "plane_bf": self.layout.Dp, "h2_scale": self.scales.dz2}, True
+
+    def miner_operands(self):        # (the score product on two fp16 planes of the unit rows times 2^14: no range to manage)
+        return 2, torch.float16, X_SCALE
+
+    def optimizer_operands(self):
+        w1, w2 = plane_operands(self)     # at the scales as of this step (observe_weights re-splits itself when it moves one)
+        return dict(w1, h2_scale=self.scales.w1), dict(w2, h2_scale=self.scales.w2)
+
+    def enable_row_gradient(self, p):      # the same sixth product on the fp16 planes: W1 [F][hi H | lo H] at the weights' scale
+        L = self.layout
+        self.W1n = torch.zeros((L.Fp, 2 * L.Hp), dtype=torch.float16, device=self.z.device)
+
+    def row_gradient(self, p, dxh):
+        L, sc = self.layout, self.scales
+        ops.gemm_f16x2_nt(ops.BE_F32, self.dz1, L.Hp, self.W1n, L.Hp, dxh, self.R, L.Fp, L.Hp, 1.0 / (sc.dz1 * sc.w1))
+
+    def scales_due(self, step=None):
+        return not self.scales.calibrated if step is None else self.scales.due(step)
+
+    def observe_weights(self, p):
+        observe_weights(p, self)
+        return True
+
+    def observe_gradients(self, p):
+        observe_gradients(p, self)
+
+    def scales_state(self):
+        sc = self.scales
+        return dict(sc.state(), calibrated=sc.calibrated, changes=sc.changes, last=dict(sc.last))
+
+    def load_scales(self, p, saved):
+        sc = self.scales
+        if saved:                                    # the checkpointed run's scales, and the weights' planes at them
+            for k in ("w1", "w2", "h1", "dz2", "dz1"):
+                setattr(sc, k, float(saved[k]))
+            sc.calibrated, sc.changes, sc.last = bool(saved["calibrated"]), int(saved["changes"]), dict(saved["last"])
+            refresh_weights(p, self)
+        else:
+            sc.calibrated = False                    # (a checkpoint of another precision: the next step calibrates)
+        return True
+
     def _value(self, t, width, scale):
         return (t[:, :width].float() + t[:, width:2 * width].float()) / scale
 
@@ -134,7 +182,7 @@ def refresh_weights(p, ws):
     ops.split_f32_f16x2(p.W1, ws.W1T, L.Fp, s.w1, transpose=True)        # [Hp][2 Fp]
     ops.split_f32_f16x2(p.W2, ws.W2T, L.Hp, s.w2, transpose=True)        # [Dp][2 Hp]
     ops.split_f32_f16x2(p.W2, ws.W2, L.Dp, s.w2)                         # [Hp][2 Dp]
-    if getattr(ws, "W1n", None) is not None:                              # trainable catalogue: dx_hat = dz1 . W1^T reads W1 as it is
+    if ws.W1n is not None:                                                # trainable catalogue: dx_hat = dz1 . W1^T reads W1 as it is
         ops.split_f32_f16x2(p.W1, ws.W1n, L.Hp, s.w1)                     # [Fp][2 Hp]
 
 
@@ -227,16 +275,7 @@ def tower_backward(p, ws, after_w1=None, w1_chunks=1, after_w1_chunk=None):
     def dw1(lo, hi, db):      # columns lo .. hi of both planes of x_hat: the same plane stride, the base moved by lo
         ops.gemm_f16x2_tn(ws.x2[:, lo:], L.Fp, ws.dz1, L.Hp, p.gW1[lo:hi], hi - lo, L.Hp, R, 1.0 / (s.x * s.dz1), workspace=ws.gemm_ws,
                           colsum=db, colsum_scale=1.0 / s.dz1)
-    rows = L.Fp // w1_chunks if w1_chunks > 1 else 0
-    if after_w1_chunk is not None and w1_chunks > 1 and rows * w1_chunks == L.Fp and rows % 256 == 0:
-        for c in range(w1_chunks):
-            last = c == w1_chunks - 1
-            dw1(c * rows, (c + 1) * rows, p.gb1 if last else None)
-            after_w1_chunk(c * rows * L.Hp, (c + 1) * rows * L.Hp + (L.Hp if last else 0))
-    else:
-        dw1(0, L.Fp, p.gb1)
-        if after_w1_chunk is not None:
-            after_w1_chunk(0, L.Fp * L.Hp + L.Hp)
+    dw1_in_blocks(p, dw1, w1_chunks, after_w1_chunk, lambda rows: rows % 256 == 0)
     if after_w1 is not None:
         after_w1()
     if not single:

@@ -17,24 +17,18 @@ import os
 import torch
 
 from . import ops
-from .engine import TowerLayout, round_up
+from .engine import EngineWorkspace, TowerLayout, dw1_in_blocks
 
 
 def layout_x3(feature_size, hidden=5000, output_size=256):
     """TowerLayout whose padded widths are multiples of 256 (the plane GEMMs' tile; 1536 / 5120 / 256 at the
     production sizes, as on the other paths).  Padding rows and columns of the weights are zero and stay zero."""
-    L = TowerLayout(feature_size, hidden, output_size)
-    L.Fp, L.Hp, L.Dp = round_up(L.F, 256), round_up(L.H, 256), round_up(L.D, 256)
-    L.sizes = (L.Fp * L.Hp, L.Hp, L.Hp * L.Dp, L.Dp)
-    off = [0]
-    for n in L.sizes[:-1]:
-        off.append(off[-1] + n)
-    L.offsets = tuple(off)
-    L.numel = int(sum(L.sizes))
-    return L
+    return TowerLayout(feature_size, hidden, output_size, pad=(256, 256, 256))
 
 
-class TowerWorkspaceX3:
+class TowerWorkspaceX3(EngineWorkspace):
+    ROWS, WIDTHS, MAX_ROWS, INFERENCE, EXCHANGE_PLANES = 128, 256, 65536, "f32x3", True
+
     def __init__(self, layout, n_rows, device, products=6, planes_in=True, backward=True, transposed=None,
                  fc2_single_pass=False, kint=None):
         """planes_in: ``x_hat`` IS the plane buffer (the fused sampler + gather writes planes); False: ``x_hat`` is
@@ -126,6 +120,29 @@ class TowerWorkspaceX3:
         self.gemm_ws = torch.empty(nb // 4, dtype=torch.float32, device=device)
         self.tail_done = False
 
+    def tail_operands(self, indexed=False):
+        return {"dz2_bf16": self.dz2_3, "plane_bf": self.layout.Dp}, True      # dz2's three planes, from either tail
+
+    def miner_operands(self):
+        return (3, torch.bfloat16, 0.0) if self.products == 6 else None
+
+    def optimizer_operands(self):
+        return plane_operands(self)
+
+    def enable_row_gradient(self, p):
+        # the row gradient dLoss/dx_hat = dz1 . W1^T is one more fp32 product on the plane kernels (k-contiguous form:
+        # dz1's planes as they are, W1 in its NATURAL orientation [F][hi H | mid H | lo H] -- a third plane copy of W1
+        # that the Adam launch writes with the update, as it does W2's two)
+        L = self.layout
+        if self.transposed or self.dz1 is None:
+            raise ValueError("train_table needs the row-major activation layout of the f32x3 path")
+        self.W1n = torch.zeros((L.Fp, 3 * L.Hp), dtype=torch.bfloat16, device=self.z.device)
+        refresh_weights(p, self)
+
+    def row_gradient(self, p, dxh):
+        L = self.layout
+        ops.gemm_bf16x3_nt(ops.BE_F32, self.dz1, L.Hp, self.W1n, L.Hp, dxh, self.R, L.Fp, L.Hp, products=self.products)
+
     def _sum_planes(self, t, width):
         return t[:, :width].float() + t[:, width:2 * width].float() + t[:, 2 * width:3 * width].float()
 
@@ -145,9 +162,16 @@ class TowerWorkspaceX3:
     def h1_f32(self):
         """the hidden activations as one fp32 tensor (tests, debugging): the planes summed"""
         H, R = self.layout.Hp, self.R
-        if self.transposed:
-            return (self.h1[:, :R].float() + self.h1[:, R:2 * R].float() + self.h1[:, 2 * R:].float()).t().contiguous()
-        return self.h1[:, :H].float() + self.h1[:, H:2 * H].float() + self.h1[:, 2 * H:].float()
+        return self._sum_planes(self.h1, R).t().contiguous() if self.transposed else self._sum_planes(self.h1, H)
+
+
+def plane_operands(ws):
+    """optimizer_operands of a plane workspace (bf16 x 3, fp16 x 2): W1^T; W2^T and W2; a trainable catalogue's natural W1"""
+    L = ws.layout
+    w1 = {"wt": ws.W1T, "plane_t": L.Fp}
+    if ws.W1n is not None:
+        w1.update(wc=ws.W1n, plane_c=L.Hp)
+    return w1, {"wt": ws.W2T, "plane_t": L.Hp, "wc": ws.W2, "plane_c": L.Dp}
 
 
 def refresh_weights(p, ws):
@@ -156,7 +180,7 @@ def refresh_weights(p, ws):
     ops.split_f32_bf16x3(p.W1, ws.W1T, L.Fp, transpose=True)        # [Hp][3 Fp]
     ops.split_f32_bf16x3(p.W2, ws.W2T, L.Hp, transpose=True)        # [Dp][3 Hp]
     ops.split_f32_bf16x3(p.W2, ws.W2, L.Dp)                         # [Hp][3 Dp]
-    if getattr(ws, "W1n", None) is not None:                        # trainable catalogue: dx_hat = dz1 . W1^T reads W1 as it is
+    if ws.W1n is not None:                                          # trainable catalogue: dx_hat = dz1 . W1^T reads W1 as it is
         ops.split_f32_bf16x3(p.W1, ws.W1n, L.Hp)                    # [Fp][3 Hp]
 
 
@@ -173,15 +197,15 @@ def tower_forward(p, ws, normalize=True):
                            plane_c=R, bias=p.b1)
         ops.gemm_bf16x3_tn(ws.h1, R, ws.W2, L.Dp, ws.z, R, L.Dp, L.Hp, products=q, workspace=ws.gemm_ws, bias=p.b2)
     else:
-        if getattr(ws, "h1_bits", None) is not None:
+        if ws.h1_bits is not None:
             ops.gemm_bf16x3_nt(ops.BE_BIAS_LRELU_X3_BITS, ws.x3, L.Fp, ws.W1T, L.Fp, ws.h1, R, L.Hp, L.Fp, products=q,
                                plane_c=L.Hp, bias=p.b1, aux=ws.h1_bits)
         else:
             ops.gemm_bf16x3_nt(ops.BE_BIAS_LRELU_X3, ws.x3, L.Fp, ws.W1T, L.Fp, ws.h1, R, L.Hp, L.Fp, products=q,
                                plane_c=L.Hp, bias=p.b1)
         ops.gemm_bf16x3_nt(ops.BE_BIAS_LRELU_F32, ws.h1, L.Hp, ws.W2T, L.Hp, ws.z, R, L.Dp, L.Hp, products=q,
-                           bias=p.b2, workspace=None if getattr(ws, "fc2_single_pass", False) else ws.gemm_ws,
-                           slab_steps=getattr(ws, "slab_steps", None))
+                           bias=p.b2, workspace=None if ws.fc2_single_pass else ws.gemm_ws,
+                           slab_steps=ws.slab_steps)
     ws.tail_done = False
     ws.dz2_planes_done = False
     if normalize:
@@ -198,7 +222,7 @@ def tower_backward(p, ws, after_w1=None, w1_chunks=1, after_w1_chunk=None):
     L, R, q = p.layout, ws.R, ws.products
     if not ws.tail_done:
         ops.l2norm_bwd(ws.z, ws.de, L.Dp, ws.dz2, lrelu_alpha=ops.LRELU_ALPHA)
-    if not (ws.tail_done and getattr(ws, "dz2_planes_done", False)):      # the fused tail writes the planes itself
+    if not (ws.tail_done and ws.dz2_planes_done):      # the fused tail writes the planes itself
         ops.split_f32_bf16x3(ws.dz2, ws.dz2_3, L.Dp)
     T = ws.transposed
     if T:
@@ -219,39 +243,30 @@ def tower_backward(p, ws, after_w1=None, w1_chunks=1, after_w1_chunk=None):
         for pl in range(3):                                                       # the gathered planes, transposed
             ops.transpose_to_bf16(ws.x3[:, pl * L.Fp:(pl + 1) * L.Fp], ws.xT[:, pl * R:(pl + 1) * R], R, L.Fp)
     else:
-        kint = getattr(ws, "kint", False) and ws.xk is not None and getattr(ws, "h1_bits", None) is not None
-        if getattr(ws, "kint", False) and not kint:
+        kint = ws.kint and ws.xk is not None and ws.h1_bits is not None
+        if ws.kint and not kint:
             raise RuntimeError("this workspace holds dz1 k8-interleaved only: it needs the gather's interleaved x_hat (ws.xk) and "
                                "the sign bitmask of h1 (CDML_X3_MASKBITS); build it with kint=False otherwise")
         if kint:      # dz1 written k8-interleaved by the epilogue: the only form the first layer's weight gradient reads
             ops.gemm_bf16x3_nt(ops.BE_MASKBITS_X3_KI, ws.dz2_3, L.Dp, ws.W2, L.Dp, ws.dz1k, R, L.Hp, L.Dp, products=q,
                                plane_c=R * L.Hp, aux=ws.h1_bits, ldc=L.Hp)
-        elif getattr(ws, "h1_bits", None) is not None:
+        elif ws.h1_bits is not None:
             ops.gemm_bf16x3_nt(ops.BE_MASKBITS_X3, ws.dz2_3, L.Dp, ws.W2, L.Dp, ws.dz1, R, L.Hp, L.Dp, products=q,
                                plane_c=L.Hp, aux=ws.h1_bits)
         else:
             ops.gemm_bf16x3_nt(ops.BE_MASK_X3, ws.dz2_3, L.Dp, ws.W2, L.Dp, ws.dz1, R, L.Hp, L.Dp, products=q, plane_c=L.Hp,
                                aux=ws.h1)
-    rows = L.Fp // w1_chunks if w1_chunks > 1 else 0
 
     def dw1(lo, hi, db):
         if T:      # rows lo .. hi of x^T against all of dz1^T; db1 = the row sums of dz1^T
             ops.gemm_bf16x3_nt(ops.BE_F32, ws.xT[lo:hi], R, ws.dz1, R, p.gW1[lo:hi], hi - lo, L.Hp, R, products=q,
                                workspace=ws.gemm_ws, colsum=db)
-        elif getattr(ws, "kint", False):      # k8-interleaved operands: one 16-B LDS read per fragment (columns lo .. hi of x_hat)
+        elif ws.kint:      # k8-interleaved operands: one 16-B LDS read per fragment (columns lo .. hi of x_hat)
             ops.gemm_bf16x3_tnk(ws.xk, L.Fp, lo, ws.dz1k, L.Hp, 0, p.gW1[lo:hi], hi - lo, L.Hp, R, workspace=ws.gemm_ws, colsum=db)
         else:      # columns lo .. hi of every plane of x_hat: the same plane stride, the base moved by lo
             ops.gemm_bf16x3_tn(ws.x3[:, lo:], L.Fp, ws.dz1, L.Hp, p.gW1[lo:hi], hi - lo, L.Hp, R, products=q,
                                workspace=ws.gemm_ws, colsum=db)
-    if after_w1_chunk is not None and w1_chunks > 1 and rows * w1_chunks == L.Fp and rows % 256 == 0:
-        for c in range(w1_chunks):
-            last = c == w1_chunks - 1
-            dw1(c * rows, (c + 1) * rows, p.gb1 if last else None)
-            after_w1_chunk(c * rows * L.Hp, (c + 1) * rows * L.Hp + (L.Hp if last else 0))
-    else:
-        dw1(0, L.Fp, p.gb1)
-        if after_w1_chunk is not None:
-            after_w1_chunk(0, L.Fp * L.Hp + L.Hp)
+    dw1_in_blocks(p, dw1, w1_chunks, after_w1_chunk, lambda rows: rows % 256 == 0)
     if after_w1 is not None:
         after_w1()
     if not single:

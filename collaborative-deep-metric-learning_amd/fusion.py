@@ -18,8 +18,9 @@ import math
 import numpy as np
 import torch
 
-from . import engine_f16x2, engine_x3, ops
-from .engine import round_up
+from . import ops
+from .engine import get_engine, round_up
+from .engine_x3 import layout_x3
 
 NETS = ("MultiplyNet", "MlpNet", "ResNet", "ResNetV2")
 VISUAL = 1500                       # models.py:80,107,138: model_input[:, :1500]
@@ -110,12 +111,12 @@ class FusionParams:
 
 class _VisualAsVNet:
     """The visual branch of a fusion tower IS VNet's two layers (models.py:82-83 against :59-60): this view hands its
-    weights, biases and gradients -- slices of the fusion tower's flat buffers -- to engine_x3's forward / backward under
-    the names they use."""
+    weights, biases and gradients -- slices of the fusion tower's flat buffers -- to a plane engine's forward / backward
+    (engine.get_engine: "f32x3" or "f16x2") under the names they use."""
 
     def __init__(self, fp, n1, n2):
         L1, L2 = fp.layers[n1], fp.layers[n2]
-        self.layout = engine_x3.layout_x3(L1.K, L1.N, L2.N)
+        self.layout = layout_x3(L1.K, L1.N, L2.N)
         self.W1, self.b1, self.W2, self.b2 = fp.W(n1), fp.b(n1), fp.W(n2), fp.b(n2)
         self.gW1, self.gb1, self.gW2, self.gb2 = fp.gW(n1), fp.gb(n1), fp.gW(n2), fp.gb(n2)
         self.grad = fp.grad
@@ -123,7 +124,7 @@ class _VisualAsVNet:
     @staticmethod
     def fits(fp, n1, n2, n_rows):
         L1, L2 = fp.layers[n1], fp.layers[n2]
-        L = engine_x3.layout_x3(L1.K, L1.N, L2.N)
+        L = layout_x3(L1.K, L1.N, L2.N)
         return (L.Fp, L.Hp, L.Dp) == (L1.Kp, L1.Np, L2.Np) and L2.Kp == L1.Np and n_rows % 128 == 0
 
 
@@ -165,20 +166,20 @@ class FusionTower:
             self.sk_bytes = ops.fc_bwd_weight2_workspace(R, v1.Kp, v1.Np, v2.Kp, v2.Np)
         self.bw = torch.empty(max(nb, self.sk_bytes, 16) // 4, dtype=torch.float32, device=dev)
         # the visual branch on the plane kernels
-        self.vx3 = self.vp3 = None
-        self.vh2, self._h2_check = False, False
+        self.vx3 = self.vp3 = self.engine = None
+        self.vh2, self._scale_check = False, False
         if precision != "f32" and "layer_visual_1" in Ls:
             if _VisualAsVNet.fits(p, "layer_visual_1", "layer_visual_2", R):
                 self.vp3 = _VisualAsVNet(p, "layer_visual_1", "layer_visual_2")
-                self.vh2 = precision == "f16x2"
-                ws = (engine_f16x2.TowerWorkspaceH2(self.vp3.layout, R, dev, planes_in=False) if self.vh2 else
-                      engine_x3.TowerWorkspaceX3(self.vp3.layout, R, dev, planes_in=False, kint=False))
+                self.vh2 = precision == "f16x2"                          # (for outside readers)
+                self.engine = get_engine("f16x2" if precision == "f16x2" else "f32x3")
+                ws = self.engine.workspace(self.vp3.layout, R, dev, planes_in=False, kint=False)
                 ws.x_hat = self.xv                                       # the l2-normalised visual rows (fp32: split in the forward pass)
                 self.act["layer_visual_2"] = ws.z                        # the branch's output, where the fusion reads it
                 self.dpre["layer_visual_2"] = ws.dz2                     # ... and where its gradient arrives
                 self.vx3 = ws
-                if not self.vh2:
-                    engine_x3.refresh_weights(self.vp3, ws)
+                if not ws.scales_due():                                  # (due: the first pass calibrates, then splits)
+                    self.engine.refresh_weights(self.vp3, ws)
             elif precision in ("f32x3", "f16x2"):
                 raise ValueError("precision '%s' needs the visual branch's padded widths to be multiples of 256 and the "
                                  "rows a multiple of 128" % precision)
@@ -189,14 +190,10 @@ class FusionTower:
         scales are re-derived first, and backward() re-derives the gradients' once the fusion layers have produced them."""
         if self.vx3 is None:
             return
-        if self.vh2:
-            sc = self.vx3.scales
-            self._h2_check = step is None or sc.due(step)
-            if self._h2_check:
-                engine_f16x2.observe_weights(self.vp3, self.vx3)
-            engine_f16x2.refresh_weights(self.vp3, self.vx3)
-        else:
-            engine_x3.refresh_weights(self.vp3, self.vx3)
+        self._scale_check = step is None or self.vx3.scales_due(step)
+        if self._scale_check:
+            self.vx3.observe_weights(self.vp3)
+        self.engine.refresh_weights(self.vp3, self.vx3)
 
     def _fc(self, n, x):
         L = self.p.layers[n]
@@ -222,12 +219,9 @@ class FusionTower:
             ops.l2norm_fwd(self.pre, D, self.e)
             return self.e
         if self.vx3 is not None:
-            if self.vh2:
-                if not (self.vx3.scales.calibrated or self._h2_check):
-                    self.refresh_planes()                                        # a first pass nobody prepared: calibrate
-                engine_f16x2.tower_forward(self.vp3, self.vx3, normalize=False)
-            else:
-                engine_x3.tower_forward(self.vp3, self.vx3, normalize=False)     # h1 as planes + sign bits, v2 = vx3.z (fp32)
+            if self.vx3.scales_due() and not self._scale_check:
+                self.refresh_planes()                                            # (f16x2) a first pass nobody prepared: calibrate
+            self.engine.tower_forward(self.vp3, self.vx3, normalize=False)       # h1 as planes + sign bits, v2 = vx3.z (fp32)
             v2 = self.vx3.z
         else:
             v2 = self._fc("layer_visual_2", self._fc("layer_visual_1", self.xv))
@@ -297,13 +291,10 @@ class FusionTower:
             # dp["layer_visual_2"] IS vx3.dz2 (the gradient of the branch's output pre-activation): planes, data gradient,
             # both weight gradients + bias gradients on the plane kernels
             self.vx3.tail_done, self.vx3.dz2_planes_done = True, False
-            if self.vh2:
-                if self._h2_check:                                               # the gradients' scales, from dz2 as it stands
-                    engine_f16x2.observe_gradients(self.vp3, self.vx3)
-                    self._h2_check = False
-                engine_f16x2.tower_backward(self.vp3, self.vx3)
-            else:
-                engine_x3.tower_backward(self.vp3, self.vx3)
+            if self._scale_check:                                        # (f16x2) the gradients' scales, from dz2 as it stands
+                self.vx3.observe_gradients(self.vp3)
+                self._scale_check = False
+            self.engine.tower_backward(self.vp3, self.vx3)
         elif self.sk_bytes and joint_visual:
             v1, v2 = p.layers["layer_visual_1"], p.layers["layer_visual_2"]
             ops.fc_bwd_data(dp["layer_visual_2"], p.W("layer_visual_2"), A["layer_visual_1"], dp["layer_visual_1"],
@@ -339,8 +330,7 @@ class FusionTrainStep:
         doc = table.feature_size - dims.get("visual_size", VISUAL)
         self.params = FusionParams(net, device, doc_size=doc, seed=weight_seed, **dims)
         self.tower = FusionTower(self.params, 3 * self.B, precision=precision)
-        self.precision = ("f32" if self.tower.vx3 is None else
-                          "f16x2 (visual branch) + f32" if self.tower.vh2 else "f32x3 (visual branch) + f32")
+        self.precision = "f32" if self.tower.vx3 is None else "%s (visual branch) + f32" % self.tower.engine.name
         dev, f32 = self.device, torch.float32
         self.idx = torch.zeros((self.B, 3), dtype=torch.int32, device=dev)
         self.x = torch.zeros((3 * self.B, table.data.shape[1]), dtype=f32, device=dev)

@@ -17,10 +17,11 @@ correction.  ``Trainer`` mirrors the reference's loop (train.py:260-336).
 import logging
 import os
 import time
+from types import SimpleNamespace
 
 import torch
 
-from . import engine, engine_bf16, engine_f16x2, engine_x3, ops
+from . import engine, ops
 from .inputs import MODE_INBATCH, MODE_UNIFORM
 
 # sampler mode per negative policy: "semihard" samples like "inbatch" (rows a_i, p_i)
@@ -35,6 +36,130 @@ def exponential_decay(base_lr, global_step, decay_steps, decay_rate, staircase=T
     if staircase:
         p = float(int(p))
     return base_lr * (decay_rate ** p)
+
+
+def validate_args(table, batch_size, mode="uniform", optimizer="adam", exchange=None, grad_sync=None, slot0=0,
+                  batch_global=None, precision="auto", train_table=False, temperature=0.1, memory_size=0, memory_start=0,
+                  logq=None, logq_alpha=0.01, logq_init_gap=None, uniform_negatives=False, uniform_logq=None,
+                  npair_sync=None, negative_lists=None, hard_fraction=1.0):
+    """The refusals of TrainStep's arguments that come before its device and pair-id checks, in its order; returns the values
+    normalised on the way (``memory_size``, ``logq``, ``uniform_logq``, ...; ``precision``: resolved for mode "npair", else as
+    given -- resolve_precision).  ``table``: anything with ``n_rows_global`` and a ``data`` of the catalogue's dtype."""
+    if negative_lists is not None:
+        for name, on in (("exchange", exchange is not None), ("grad_sync", grad_sync is not None),
+                         ("npair_sync", npair_sync is not None), ("train_table", bool(train_table))):
+            if on:
+                raise ValueError("negative_lists does not go with %s yet: listed negatives run on one GPU over a frozen "
+                                 "catalogue" % name)
+        if precision == "f16x2":
+            raise ValueError("negative_lists does not go with precision 'f16x2' (its gather has no listed form): use "
+                             "'f32x3', 'f32' or 'bf16'")
+        if not (mode == "uniform" or (mode == "npair" and uniform_negatives)):
+            raise ValueError("negative_lists goes with a mode that draws a negative (mode 'uniform', or mode 'npair' with "
+                             "uniform_negatives=True), not mode %r" % (mode,))
+        hard_fraction = float(hard_fraction)
+        if not 0.0 <= hard_fraction <= 1.0:
+            raise ValueError("hard_fraction must be in [0, 1], got %r" % (hard_fraction,))
+        negative_lists = torch.as_tensor(negative_lists)
+        if (negative_lists.dim() != 2 or negative_lists.dtype != torch.int32
+                or negative_lists.shape[0] != table.n_rows_global or not 1 <= negative_lists.shape[1] <= 1024):
+            raise ValueError("negative_lists must be an int32 [n_rows = %d, L in [1, 1024]] tensor, got %s %s"
+                             % (table.n_rows_global, negative_lists.dtype, tuple(negative_lists.shape)))
+    if mode not in _MODES:
+        raise ValueError("mode must be 'uniform', 'inbatch', 'semihard' or 'npair'")
+    if npair_sync is not None:
+        if mode != "npair":
+            raise ValueError("npair_sync goes with mode 'npair' (it carries the positives of its softmax between the ranks), "
+                             "not %r" % (mode,))
+        for name, on in (("memory_size", int(memory_size) != 0), ("logq", logq is not None),
+                         ("uniform_negatives", bool(uniform_negatives)), ("train_table", bool(train_table))):
+            if on:
+                raise ValueError("npair_sync does not go with %s yet: the data-parallel N-pair loss is the plain in-batch "
+                                 "softmax over every rank's positives" % name)
+        bg = int(batch_size) if batch_global is None else int(batch_global)
+        if bg != int(batch_size) * npair_sync.world or int(slot0) != npair_sync.rank * int(batch_size):
+            raise ValueError("npair_sync over %d ranks needs batch_global = world x batch = %d and slot0 = rank x batch = %d "
+                             "(got %d and %d)" % (npair_sync.world, int(batch_size) * npair_sync.world,
+                                                  npair_sync.rank * int(batch_size), bg, int(slot0)))
+    memory_size, memory_start = int(memory_size), int(memory_start)
+    if memory_size and mode != "npair":
+        raise ValueError("memory_size > 0 goes with mode 'npair' (the cross-batch memory of its softmax), not %r" % (mode,))
+    if memory_size < 0 or memory_start < 0:
+        raise ValueError("memory_size and memory_start must be >= 0, got %d and %d" % (memory_size, memory_start))
+    logq_stream = isinstance(logq, str)
+    if logq is not None:
+        if mode != "npair":
+            raise ValueError("logq goes with mode 'npair' (the sampling-bias correction of its softmax), not %r" % (mode,))
+        if logq_stream and logq != "stream":
+            raise ValueError("logq must be None, 'stream' or a tensor of one log-probability per video, not %r" % (logq,))
+        logq_alpha = float(logq_alpha)
+        if not 0.0 < logq_alpha <= 1.0:
+            raise ValueError("logq_alpha must be in (0, 1], got %r" % (logq_alpha,))
+        if logq_init_gap is not None and not 1.0 <= float(logq_init_gap) < float("inf"):
+            raise ValueError("logq_init_gap must be finite and >= 1, got %r" % (logq_init_gap,))
+        if not logq_stream:
+            logq = torch.as_tensor(logq)
+            if logq.dim() != 1 or logq.numel() != table.n_rows_global:
+                raise ValueError("a logq table needs one entry per catalogue row (%d), got shape %s"
+                                 % (table.n_rows_global, tuple(logq.shape)))
+            if not logq.is_floating_point() or not bool(torch.isfinite(logq).all()):
+                raise ValueError("every entry of the logq table must be a finite float")
+    uniform_negatives = bool(uniform_negatives)
+    if uniform_negatives and mode != "npair":
+        raise ValueError("uniform_negatives goes with mode 'npair' (mixed negative sampling of its softmax), not %r" % (mode,))
+    if uniform_logq is not None:
+        if not uniform_negatives:
+            raise ValueError("uniform_logq goes with uniform_negatives=True (the uniform block's log sampling probability)")
+        if logq is None:
+            raise ValueError("uniform_logq goes with a logQ correction (logq=...): without one no logit is corrected")
+        uniform_logq = float(uniform_logq)
+        if not (float("-inf") < uniform_logq < float("inf")):
+            raise ValueError("uniform_logq must be a finite float, got %r" % (uniform_logq,))
+    if mode == "npair":
+        if (exchange is not None or grad_sync is not None) and npair_sync is None:
+            raise ValueError("mode 'npair' runs on one GPU unless npair_sync (dist.NPairSync) carries its positives between "
+                             "the ranks")
+        if train_table:
+            raise ValueError("mode 'npair' does not train the catalogue (train_table=True is not supported)")
+        if precision in ("auto", None):
+            precision = engine.auto_precision(table.data.dtype, int(batch_size), ops.NPAIR_TILE["f32x3"])
+        if precision not in ops.NPAIR_PRECISIONS:
+            raise ValueError("mode 'npair' runs on precision 'f32x3' or 'f32' (an fp32 catalogue) or 'bf16' (an fp16 "
+                             "catalogue), not %r" % (precision,))
+        if precision == "bf16":
+            for name, on in (("uniform_negatives", uniform_negatives), ("npair_sync", npair_sync is not None)):
+                if on:
+                    raise ValueError("mode 'npair' on precision 'bf16' does not take %s (precision 'f32x3' or 'f32' does)"
+                                     % name)
+        tile = ops.NPAIR_TILE[precision]
+        if int(batch_size) % tile:
+            raise ValueError("mode 'npair' on precision %r needs a batch that is a multiple of %d pairs (got %d)"
+                             % (precision, tile, int(batch_size)))
+        temperature = float(temperature)
+        if not (0.0 < temperature < float("inf")):
+            raise ValueError("temperature must be finite and > 0, got %r" % (temperature,))
+        if memory_size % int(batch_size) or memory_size % tile:
+            raise ValueError("memory_size must be a multiple of the batch (%d pairs) and of %d on precision %r (got %d)"
+                             % (int(batch_size), tile, precision, memory_size))
+    if optimizer not in ("adam", "lars", "momentum"):
+        raise ValueError("optimizer must be 'adam', 'lars' or 'momentum'")
+    return SimpleNamespace(precision=precision, temperature=temperature, memory_size=memory_size, memory_start=memory_start,
+                           logq=logq, logq_stream=logq_stream, logq_alpha=logq_alpha, logq_init_gap=logq_init_gap,
+                           uniform_negatives=uniform_negatives, uniform_logq=uniform_logq, negative_lists=negative_lists,
+                           hard_fraction=hard_fraction)
+
+
+def resolve_precision(table, rows, precision, use_graph=False, exchange=None, grad_sync=None):
+    """The precision of a step of ``rows`` rows ("auto" resolved: round 6, VERDICT r5 #14 -- the default is the path bench.py
+    times), or the refusal of one that does not go with the table's dtype or the way the step is to replay."""
+    if precision in ("auto", None):
+        precision = engine.auto_precision(table.data.dtype, rows)
+    if engine.get_engine(precision).table_dtype != table.data.dtype:
+        raise ValueError("precision 'bf16' goes with an fp16 FeatureTableF16, 'f32' / 'f32x3' with an fp32 table")
+    if precision == "f16x2" and use_graph and (use_graph == "split" or exchange is not None or grad_sync is not None):
+        raise ValueError("precision 'f16x2' replays from a hipGraph on one GPU only (its plane scales are kernel arguments "
+                         "baked into a capture: the check steps run eagerly and a moved scale re-captures, engine_f16x2.py)")
+    return precision
 
 
 class TrainStep:
@@ -137,110 +262,12 @@ class TrainStep:
         them from the current weights, ``hard_share()`` is the last step's share of listed negatives; the lists and
         ``hard_fraction`` are part of ``state_dict``.  ``gather_ahead`` is 1 while lists are set: a refresh must not race
         rows fetched ahead."""
-        if negative_lists is not None:
-            # hard negatives, first form: one GPU, a frozen catalogue, a sampler that draws a negative
-            for name, on in (("exchange", exchange is not None), ("grad_sync", grad_sync is not None),
-                             ("npair_sync", npair_sync is not None), ("train_table", bool(train_table))):
-                if on:
-                    raise ValueError("negative_lists does not go with %s yet: listed negatives run on one GPU over a frozen "
-                                     "catalogue" % name)
-            if precision == "f16x2":
-                raise ValueError("negative_lists does not go with precision 'f16x2' (its gather has no listed form): use "
-                                 "'f32x3', 'f32' or 'bf16'")
-            if not (mode == "uniform" or (mode == "npair" and uniform_negatives)):
-                raise ValueError("negative_lists goes with a mode that draws a negative (mode 'uniform', or mode 'npair' with "
-                                 "uniform_negatives=True), not mode %r" % (mode,))
-            hard_fraction = float(hard_fraction)
-            if not 0.0 <= hard_fraction <= 1.0:
-                raise ValueError("hard_fraction must be in [0, 1], got %r" % (hard_fraction,))
-            negative_lists = torch.as_tensor(negative_lists)
-            if (negative_lists.dim() != 2 or negative_lists.dtype != torch.int32
-                    or negative_lists.shape[0] != table.n_rows_global or not 1 <= negative_lists.shape[1] <= 1024):
-                raise ValueError("negative_lists must be an int32 [n_rows = %d, L in [1, 1024]] tensor, got %s %s"
-                                 % (table.n_rows_global, negative_lists.dtype, tuple(negative_lists.shape)))
-        if mode not in _MODES:
-            raise ValueError("mode must be 'uniform', 'inbatch', 'semihard' or 'npair'")
-        if npair_sync is not None:
-            if mode != "npair":
-                raise ValueError("npair_sync goes with mode 'npair' (it carries the positives of its softmax between the ranks), "
-                                 "not %r" % (mode,))
-            for name, on in (("memory_size", int(memory_size) != 0), ("logq", logq is not None),
-                             ("uniform_negatives", bool(uniform_negatives)), ("train_table", bool(train_table))):
-                if on:
-                    raise ValueError("npair_sync does not go with %s yet: the data-parallel N-pair loss is the plain in-batch "
-                                     "softmax over every rank's positives" % name)
-            bg = int(batch_size) if batch_global is None else int(batch_global)
-            if bg != int(batch_size) * npair_sync.world or int(slot0) != npair_sync.rank * int(batch_size):
-                raise ValueError("npair_sync over %d ranks needs batch_global = world x batch = %d and slot0 = rank x batch = %d "
-                                 "(got %d and %d)" % (npair_sync.world, int(batch_size) * npair_sync.world,
-                                                      npair_sync.rank * int(batch_size), bg, int(slot0)))
-        memory_size, memory_start = int(memory_size), int(memory_start)
-        if memory_size and mode != "npair":
-            raise ValueError("memory_size > 0 goes with mode 'npair' (the cross-batch memory of its softmax), not %r" % (mode,))
-        if memory_size < 0 or memory_start < 0:
-            raise ValueError("memory_size and memory_start must be >= 0, got %d and %d" % (memory_size, memory_start))
-        logq_stream = isinstance(logq, str)
-        if logq is not None:
-            if mode != "npair":
-                raise ValueError("logq goes with mode 'npair' (the sampling-bias correction of its softmax), not %r" % (mode,))
-            if logq_stream and logq != "stream":
-                raise ValueError("logq must be None, 'stream' or a tensor of one log-probability per video, not %r" % (logq,))
-            logq_alpha = float(logq_alpha)
-            if not 0.0 < logq_alpha <= 1.0:
-                raise ValueError("logq_alpha must be in (0, 1], got %r" % (logq_alpha,))
-            if logq_init_gap is not None and not 1.0 <= float(logq_init_gap) < float("inf"):
-                raise ValueError("logq_init_gap must be finite and >= 1, got %r" % (logq_init_gap,))
-            if not logq_stream:
-                logq = torch.as_tensor(logq)
-                if logq.dim() != 1 or logq.numel() != table.n_rows_global:
-                    raise ValueError("a logq table needs one entry per catalogue row (%d), got shape %s"
-                                     % (table.n_rows_global, tuple(logq.shape)))
-                if not logq.is_floating_point() or not bool(torch.isfinite(logq).all()):
-                    raise ValueError("every entry of the logq table must be a finite float")
-        uniform_negatives = bool(uniform_negatives)
-        if uniform_negatives and mode != "npair":
-            raise ValueError("uniform_negatives goes with mode 'npair' (mixed negative sampling of its softmax), not %r" % (mode,))
-        if uniform_logq is not None:
-            if not uniform_negatives:
-                raise ValueError("uniform_logq goes with uniform_negatives=True (the uniform block's log sampling probability)")
-            if logq is None:
-                raise ValueError("uniform_logq goes with a logQ correction (logq=...): without one no logit is corrected")
-            uniform_logq = float(uniform_logq)
-            if not (float("-inf") < uniform_logq < float("inf")):
-                raise ValueError("uniform_logq must be a finite float, got %r" % (uniform_logq,))
-        if mode == "npair":
-            if (exchange is not None or grad_sync is not None) and npair_sync is None:
-                raise ValueError("mode 'npair' runs on one GPU unless npair_sync (dist.NPairSync) carries its positives between "
-                                 "the ranks")
-            if train_table:
-                raise ValueError("mode 'npair' does not train the catalogue (train_table=True is not supported)")
-            if precision in ("auto", None):
-                if table.data.dtype == torch.float16:
-                    precision = "bf16"
-                else:
-                    precision = "f32x3" if int(batch_size) % ops.NPAIR_TILE["f32x3"] == 0 else "f32"
-            if precision not in ops.NPAIR_PRECISIONS:
-                raise ValueError("mode 'npair' runs on precision 'f32x3' or 'f32' (an fp32 catalogue) or 'bf16' (an fp16 "
-                                 "catalogue), not %r" % (precision,))
-            if precision == "bf16":
-                # the config-4 chain (ops._npair_chain) is the in-batch softmax with a memory and logQ; the mixed and
-                # the data-parallel chains have no one-plane form
-                for name, on in (("uniform_negatives", uniform_negatives), ("npair_sync", npair_sync is not None)):
-                    if on:
-                        raise ValueError("mode 'npair' on precision 'bf16' does not take %s (precision 'f32x3' or 'f32' does)"
-                                         % name)
-            tile = ops.NPAIR_TILE[precision]
-            if int(batch_size) % tile:
-                raise ValueError("mode 'npair' on precision %r needs a batch that is a multiple of %d pairs (got %d)"
-                                 % (precision, tile, int(batch_size)))
-            temperature = float(temperature)
-            if not (0.0 < temperature < float("inf")):
-                raise ValueError("temperature must be finite and > 0, got %r" % (temperature,))
-            if memory_size % int(batch_size) or memory_size % tile:
-                raise ValueError("memory_size must be a multiple of the batch (%d pairs) and of %d on precision %r (got %d)"
-                                 % (int(batch_size), tile, precision, memory_size))
-        if optimizer not in ("adam", "lars", "momentum"):
-            raise ValueError("optimizer must be 'adam', 'lars' or 'momentum'")
+        a = validate_args(table, batch_size, mode=mode, optimizer=optimizer, exchange=exchange, grad_sync=grad_sync,
+                          slot0=slot0, batch_global=batch_global, precision=precision, train_table=train_table,
+                          temperature=temperature, memory_size=memory_size, memory_start=memory_start, logq=logq,
+                          logq_alpha=logq_alpha, logq_init_gap=logq_init_gap, uniform_negatives=uniform_negatives,
+                          uniform_logq=uniform_logq, npair_sync=npair_sync, negative_lists=negative_lists,
+                          hard_fraction=hard_fraction)
         self.device = torch.device(device)
         if self.device.type == "cuda" and self.device.index is not None \
                 and torch.cuda.current_device() != self.device.index:
@@ -248,7 +275,6 @@ class TrainStep:
             # would run its kernels on the wrong stream with that device's pointers
             raise ValueError("TrainStep(device=%s) needs torch.cuda.set_device(%d) first (current device %d)"
                              % (self.device, self.device.index, torch.cuda.current_device()))
-        self.table, self.pairs = table, pairs
         # the reference raises IndexError on an id outside the table (inputs.py:158); the fused
         # kernel clamps, so the ids are checked once here instead of per step
         if pairs.numel():
@@ -256,78 +282,58 @@ class TrainStep:
             if lo < 0 or hi >= table.n_rows_global:
                 raise IndexError("co-watch pair ids span [%d, %d] but the catalogue has %d rows"
                                  % (lo, hi, table.n_rows_global))
+        if grad_sync_mode not in self.GRAD_SYNC_MODES:
+            raise ValueError("grad_sync_mode must be one of %s" % (self.GRAD_SYNC_MODES,))
+        self.table, self.pairs = table, pairs
         self.B = int(batch_size)
         self.mode = mode
-        self.uniform_negatives = uniform_negatives
+        self.uniform_negatives = a.uniform_negatives
         # (mode "npair" with uniform negatives samples like mode "uniform": a, p and a uniform catalogue negative)
-        self.sampler_mode = MODE_UNIFORM if uniform_negatives else _MODES[mode]
+        self.sampler_mode = MODE_UNIFORM if a.uniform_negatives else _MODES[mode]
         self.rows_per_triplet = 3 if self.sampler_mode == MODE_UNIFORM else 2
         self.R = self.B * self.rows_per_triplet
         self.margin = float(margin)
-        self.temperature, self.symmetric = float(temperature), bool(symmetric)
+        self.temperature, self.symmetric = float(a.temperature), bool(symmetric)
         self.seed = int(seed)
         self.optimizer = optimizer
         self.base_lr = float(base_learning_rate)
         self.decay_steps = learning_rate_decay_examples
         self.decay_rate = learning_rate_decay
         self.exchange, self.grad_sync = exchange, grad_sync
-        if grad_sync_mode not in self.GRAD_SYNC_MODES:
-            raise ValueError("grad_sync_mode must be one of %s" % (self.GRAD_SYNC_MODES,))
         self._grad_sync_mode = grad_sync_mode
         self.slot0 = int(slot0)
         self.batch_global = self.B if batch_global is None else int(batch_global)
-        F = table.feature_size if feature_size is None else feature_size
-        if precision in ("auto", None):
-            # round 6: the default is the path bench.py times.  An fp16 catalogue is config 4's path; an fp32
-            # catalogue takes the split-fp32 products on the bf16 MFMA ("f32x3": fp32 results, 1.7 x the fp32 MFMA's rate)
-            # whenever the step's row count allows it (a multiple of 128: the plane kernels' row tiles), else the fp32 MFMA.
-            # Say precision="f32" / "f32x3" to pin one.
-            if table.data.dtype == torch.float16:
-                precision = "bf16"
-            else:
-                precision = "f32x3" if (self.B * self.rows_per_triplet) % 128 == 0 else "f32"
-        if precision not in ("f32", "bf16", "f32x3", "f32x3-3", "f16x2"):
-            raise ValueError("precision must be 'auto', 'f32', 'f32x3', 'f16x2' or 'bf16'")
+        self._build_tower(resolve_precision(table, self.R, a.precision, use_graph, exchange, grad_sync),
+                          table.feature_size if feature_size is None else feature_size, hidden_size, output_size, weight_seed,
+                          train_table)
+        self._build_loss_buffers(a, npair_sync)
+        self._build_optimizer_state(clip_gradient_norm, regularization_penalty, l2_penalty)
+        self._build_trainable_table(train_table)
+        self._build_gather_ahead(gather_ahead)
+        # (a trainable table: a prefetched batch would read rows from before this step's update)
+        self._decide_graph_and_prefetch(use_graph, prefetch and not self.train_table)
+
+    def _build_tower(self, precision, F, hidden_size, output_size, weight_seed, train_table):
+        """Layout, parameters and workspace of the precision's engine (engine.get_engine: the one place that knows the four)."""
+        E = self.engine = engine.get_engine(precision)
         self.precision = precision
-        self.bf16 = precision == "bf16"          # BASELINE config 4: fp16 table + bf16 MFMA
-        # fp32 products on the bf16 MFMA: operands as three exact bf16 planes, six plane products (engine_x3;
-        # "f32x3-3": the three leading products only -- 16-bit operands, not an fp32 equivalent)
-        self.x3 = precision.startswith("f32x3")
-        # fp32 products on the fp16 MFMA: operands as two fp16 planes under per-tensor scales, three plane products (engine_f16x2)
-        self.h2 = precision == "f16x2"
-        if self.bf16 != (table.data.dtype == torch.float16):
-            raise ValueError("precision 'bf16' goes with an fp16 FeatureTableF16, 'f32' / 'f32x3' with an fp32 table")
-        if self.h2:
-            if use_graph and (use_graph == "split" or exchange is not None or grad_sync is not None):
-                raise ValueError("precision 'f16x2' replays from a hipGraph on one GPU only (its plane scales are kernel arguments "
-                                 "baked into a capture: the check steps run eagerly and a moved scale re-captures, engine_f16x2.py)")
-            self._h2_sig = None                          # the scales the captured graphs were recorded with
-            self.layout = engine_x3.layout_x3(F, hidden_size, output_size)
-            self.params = engine.VNetParams(self.layout, self.device, weight_seed)
-            # one GPU: the fused sampler + gather writes the fp16 planes; sharded catalogue: the rows arrive in fp32 through the
-            # exchange and the forward pass splits them
-            self.ws = engine_f16x2.TowerWorkspaceH2(self.layout, self.R, self.device, planes_in=exchange is None)
-        elif self.x3:
-            self.layout = engine_x3.layout_x3(F, hidden_size, output_size)
-            self.params = engine.VNetParams(self.layout, self.device, weight_seed)
-            self.ws = engine_x3.TowerWorkspaceX3(self.layout, self.R, self.device, products=3 if precision.endswith("-3") else 6,
-                                                 # the plane buffer IS x_hat on both paths: the fused gather writes planes, and so
-                                                 # does the un-permute pass of the row exchange (round 5; a caller's fp32 rows:
-                                                 # TowerWorkspaceX3(planes_in=False) splits them in the forward pass)
-                                                 planes_in=True,
-                                                 # the interleaved copy of x_hat comes from the fused sampler + gather (one GPU)
-                                                 kint=None if (exchange is None and not train_table) else False)
-            engine_x3.refresh_weights(self.params, self.ws)
-        elif self.bf16:
-            self.layout = engine_bf16.layout_bf16(F, hidden_size, output_size)
-            self.params = engine.VNetParams(self.layout, self.device, weight_seed)
-            self.ws = engine_bf16.TowerWorkspaceBF16(self.layout, self.R, self.device)
-            engine_bf16.refresh_weights(self.params, self.ws)
-        else:
-            self.layout = engine.TowerLayout(F, hidden_size, output_size)
-            self.params = engine.VNetParams(self.layout, self.device, weight_seed)
-            self.ws = engine.TowerWorkspace(self.layout, self.R, self.device)
-        dev, i32, f32 = self.device, torch.int32, torch.float32
+        # (for outside readers: nothing in the package branches on them)
+        self.bf16, self.x3, self.h2 = precision == "bf16", precision.startswith("f32x3"), precision == "f16x2"
+        self._scale_sig = None                           # the plane scales the captured graphs were recorded with (f16x2)
+        self.layout = E.layout(F, hidden_size, output_size)
+        self.params = engine.VNetParams(self.layout, self.device, weight_seed)
+        sharded = self.exchange is not None
+        # planes_in: the fused sampler + gather writes planes (the plane buffer IS x_hat), and so does the row exchange's
+        # un-permute pass on f32x3 (on f16x2 its rows arrive in fp32); kint: the gather's interleaved copy (one GPU)
+        self.ws = E.workspace(self.layout, self.R, self.device, planes_in=not sharded or E.Workspace.EXCHANGE_PLANES,
+                              kint=None if (not sharded and not train_table) else False)
+        if not self.ws.scales_due():                     # (due: the first step's check splits the weights at the scales it finds)
+            E.refresh_weights(self.params, self.ws)
+
+    def _build_loss_buffers(self, a, npair_sync):
+        """Index / loss / statistics buffers and what the mode's loss needs: miner, N-pair family, logQ source, negative lists."""
+        dev, i32, f32, precision, mode = self.device, torch.int32, torch.float32, self.precision, self.mode
+        memory_size, memory_start = a.memory_size, a.memory_start
         self.idx = torch.zeros(self.R, dtype=i32, device=dev)       # [B,3] or [2B] video ids
         self.shift = torch.zeros(1, dtype=i32, device=dev)
         self.pos = torch.zeros(self.B, dtype=f32, device=dev)
@@ -338,20 +344,20 @@ class TrainStep:
         self.oob = torch.zeros(1, dtype=i32, device=dev)     # fused sampler+gather: a pair id outside the table
         self.adam_tickets = ops.new_tickets(dev)             # Adam: last block advances the step counter
         self.var_ws = None                                   # set by enable_variance()
+        self.mine_fused = False
         if mode == "semihard":
             if self.B % 32:
                 raise ValueError("semi-hard mining needs a batch that is a multiple of 32")
-            # precision f32x3: the score product on the plane kernels with the selection as its epilogue -- no B x 2B
-            # score matrix (537 MB at B = 8192) is written or scanned (csrc/gemm_bf16x3.hip; CDML_MINE_FUSED=0: the
+            # the plane engines (f32x3, f16x2): the score product on the plane kernels with the selection as its epilogue -- no
+            # B x 2B score matrix (537 MB at B = 8192) is written or scanned (csrc/gemm_bf16x3.hip; CDML_MINE_FUSED=0: the
             # round-2 form, for A/B runs); the fp32-MFMA and bf16 paths keep the score matrix
             # (precision f16x2: the same epilogue on the fp16 build of the kernel, cdml_semihard_mine_h2)
-            self.mine_fused = ((precision == "f32x3" or self.h2) and (2 * self.B) % 256 == 0 and self.layout.Dp % 64 == 0
+            miner = self.ws.miner_operands()
+            self.mine_fused = (miner is not None and (2 * self.B) % 256 == 0 and self.layout.Dp % 64 == 0
                                and os.environ.get("CDML_MINE_FUSED", "1") != "0")
             if self.mine_fused:
-                Dp = self.layout.Dp
-                # (f16x2: the miner's score product on two fp16 planes of the unit rows times 2^14 -- no range to manage)
-                self.e3 = (torch.zeros((2 * self.B, 2 * Dp), dtype=torch.float16, device=dev) if self.h2
-                           else torch.zeros((2 * self.B, 3 * Dp), dtype=torch.bfloat16, device=dev))
+                planes, dtype, self.mine_scale = miner
+                self.e3 = torch.zeros((2 * self.B, planes * self.layout.Dp), dtype=dtype, device=dev)
                 self.dp = torch.zeros(self.B, dtype=f32, device=dev)
                 self.mine_ws = torch.zeros(ops.semihard_mine_x3_workspace(self.B) // 4, dtype=f32, device=dev)
             else:
@@ -363,7 +369,7 @@ class TrainStep:
         self.npair_sync, self.npair_dp = npair_sync, None
         self.npair_memory = None
         self.npair_mixed = None
-        if uniform_negatives:                                # the mixed chain's S, W and [P; N; Mem] operands (and the ring)
+        if a.uniform_negatives:                              # the mixed chain's S, W and [P; N; Mem] operands (and the ring)
             self.npair_mixed = ops.NPairMixed(self.B, self.layout.Dp, precision, dev, memory_size, memory_start)
             self.npair_memory = self.npair_mixed.ring
         elif mode == "npair" and npair_sync is not None:     # the data-parallel chain: this rank's rows x every rank's positives
@@ -374,22 +380,26 @@ class TrainStep:
             if memory_size:
                 self.npair_memory = ops.NPairMemory(memory_size, self.B, self.layout.Dp, precision, dev, start=memory_start)
         self.npair_logq = None                               # the sampling-bias correction's source (ops.LogQ*)
-        if logq is not None:
-            self.npair_logq = (ops.LogQEstimator(table.n_rows_global, self.B, logq_alpha, logq_init_gap, dev) if logq_stream
-                               else ops.LogQTable(logq, dev))
-        self.uniform_lq = ops.uniform_logq(self.npair_logq, uniform_logq) if uniform_negatives else 0.0
+        if a.logq is not None:
+            self.npair_logq = (ops.LogQEstimator(self.table.n_rows_global, self.B, a.logq_alpha, a.logq_init_gap, dev)
+                               if a.logq_stream else ops.LogQTable(a.logq, dev))
+        self.uniform_lq = ops.uniform_logq(self.npair_logq, a.uniform_logq) if a.uniform_negatives else 0.0
         # hard negatives: ONE device copy of the lists (set_negative_lists copies into it) and the last step's kinds
         self.neg_lists = None
-        self.hard_fraction = float(hard_fraction)
-        if negative_lists is not None:
-            self.neg_lists = negative_lists.to(dev).contiguous().clone()
+        self.hard_fraction = float(a.hard_fraction)
+        if a.negative_lists is not None:
+            self.neg_lists = a.negative_lists.to(dev).contiguous().clone()
             self.kind = torch.zeros(self.B, dtype=i32, device=dev)
+
+    def _build_optimizer_state(self, clip_gradient_norm, regularization_penalty, l2_penalty):
+        """Step counter and learning rate on the device, the optimizer's slots, the clipping / regulariser scratch."""
+        dev, f32 = self.device, torch.float32
         self.step_dev = torch.zeros(1, dtype=torch.int64, device=dev)
         self.lr_dev = torch.full((1,), self.base_lr, dtype=f32, device=dev)
         self._lr_host = self.base_lr
         self.global_step = 0
         n = self.layout.numel
-        if optimizer == "adam":
+        if self.optimizer == "adam":
             self.m = torch.zeros(n, dtype=f32, device=dev)
             self.v = torch.zeros(n, dtype=f32, device=dev)
         else:
@@ -400,39 +410,34 @@ class TrainStep:
         self.reg_scale = float(regularization_penalty) * float(l2_penalty)
         self.l2_penalty = float(l2_penalty)
         self.grad_norms = torch.zeros((4, 2), dtype=f32, device=dev)   # per variable: |g|, |w|^2
+
+    def _build_trainable_table(self, train_table):
+        """Lazy-Adam state of the catalogue rows and the row gradient's buffers."""
+        dev, table = self.device, self.table
         self.train_table = bool(train_table)
         if self.train_table:
-            if self.bf16 or optimizer != "adam" or precision == "f32x3-3":
+            if self.engine.table_dtype == torch.float16 or self.optimizer != "adam" or self.precision == "f32x3-3":
                 # (config 4's catalogue is fp16: it has no fp32 master rows for Adam to move by 1e-2 * 2^-11 of a value)
                 raise ValueError("train_table goes with an fp32 catalogue (precision 'f32x3' or 'f32') and the Adam optimizer")
-            if self.x3:
-                # the row gradient dLoss/dx_hat = dz1 . W1^T is one more fp32 product on the plane kernels (k-contiguous
-                # form: dz1's planes as they are, W1 in its NATURAL orientation [F][hi H | mid H | lo H] -- a third plane
-                # copy of W1 that the Adam launch writes with the update, as it does W2's two)
-                if getattr(self.ws, "transposed", False) or self.ws.dz1 is None:
-                    raise ValueError("train_table needs the row-major activation layout of the f32x3 path")
-                self.ws.W1n = torch.zeros((self.layout.Fp, 3 * self.layout.Hp), dtype=torch.bfloat16, device=dev)
-                engine_x3.refresh_weights(self.params, self.ws)
-            elif self.h2:      # the same sixth product on the fp16 planes: W1 [F][hi H | lo H] at the weights' scale
-                self.ws.W1n = torch.zeros((self.layout.Fp, 2 * self.layout.Hp), dtype=torch.float16, device=dev)
+            self.ws.enable_row_gradient(self.params)         # (the plane engines: W1's planes in their natural orientation)
             self.tab_m = torch.zeros_like(table.data)
             self.tab_v = torch.zeros_like(table.data)
-            self.tab_head = torch.full((table.n_rows,), -1, dtype=i32, device=dev)
-            self.tab_next = torch.zeros(self.R, dtype=i32, device=dev)
-            self.dxh = torch.zeros((self.R, self.layout.Fp), dtype=f32, device=dev)
-            prefetch = False      # a prefetched batch would read rows from before this step's update
-            if grad_sync is not None and exchange is None:
+            self.tab_head = torch.full((table.n_rows,), -1, dtype=torch.int32, device=dev)
+            self.tab_next = torch.zeros(self.R, dtype=torch.int32, device=dev)
+            self.dxh = torch.zeros((self.R, self.layout.Fp), dtype=torch.float32, device=dev)
+            if self.grad_sync is not None and self.exchange is None:
                 raise ValueError("train_table with grad_sync needs a row-sharded table (exchange): "
                                  "replicated trainable tables would diverge between ranks")
-        # several steps' rows per gather launch (the frozen catalogue cannot change in between;
-        # a trainable one can, and the sharded path has its own prefetcher)
-        kint = self.x3 and getattr(self.ws, "kint", False)
+
+    def _build_gather_ahead(self, gather_ahead):
+        """Several steps' rows per gather launch (a frozen, unsharded catalogue: it cannot change in between)."""
+        dev, kint = self.device, self.ws.kint
         if gather_ahead in ("auto", None, 0):
             row_bytes = self.ws.x_hat.shape[-1] * self.ws.x_hat.element_size() * (2 if kint else 1)   # what one gathered row writes
-            target = 230e6 if self.bf16 else 300e6                                  # (fp16 -> bf16 rows: half the bytes read per byte written)
+            target = 230e6 if self.engine.table_dtype == torch.float16 else 300e6      # (fp16 -> bf16 rows: half the bytes read)
             gather_ahead = min(4, max(1, int(round(target / (self.R * row_bytes)))))
         self.gather_ahead = max(1, int(gather_ahead))
-        if exchange is not None or self.train_table or self.neg_lists is not None:
+        if self.exchange is not None or self.train_table or self.neg_lists is not None:
             self.gather_ahead = 1                            # (lists: a refresh must not race rows fetched ahead)
         self._ahead_base = None
         if self.gather_ahead > 1:
@@ -441,25 +446,28 @@ class TrainStep:
             K = self.gather_ahead
             self._xa = torch.zeros((K,) + tuple(self.ws.x_hat.shape), dtype=self.ws.x_hat.dtype, device=dev)
             self._xka = torch.zeros((K, 3 * self.R * self.layout.Fp), dtype=torch.bfloat16, device=dev) if kint else None
-            self._idxa = torch.zeros((K, self.R), dtype=i32, device=dev)
-            self._shifta = torch.zeros(K, dtype=i32, device=dev)
+            self._idxa = torch.zeros((K, self.R), dtype=torch.int32, device=dev)
+            self._shifta = torch.zeros(K, dtype=torch.int32, device=dev)
             self._select_ahead(0)
         elif kint:
             self._xka = None
             self.ws.xk = torch.zeros(3 * self.R * self.layout.Fp, dtype=torch.bfloat16, device=dev)
+
+    def _decide_graph_and_prefetch(self, use_graph, prefetch):
+        """Whether the step replays from hipGraphs (with capture-only process groups); a sharded catalogue's row prefetcher."""
+        exchange, grad_sync, warn = self.exchange, self.grad_sync, logging.getLogger("cdml.train").warning
         self._graphs = {}
         self._warmed = False
         self._replayed = False                           # the previous step was a graph replay
         # the data-parallel step is enqueue-only too (fixed-capacity exchange, no host counts), so
         # it captures like the single-GPU one: one graph per prefetch buffer
         self.use_graph = "split" if use_graph == "split" else bool(use_graph)
-        if self.use_graph and npair_sync is not None:
+        if self.use_graph and self.npair_sync is not None:
             self.use_graph = False                       # its three collectives are not captured
-            logging.getLogger("cdml.train").warning(
-                "use_graph ignored: the data-parallel N-pair loss (npair_sync) steps eagerly")
+            warn("use_graph ignored: the data-parallel N-pair loss (npair_sync) steps eagerly")
         if self.use_graph and self.train_table and exchange is not None:
             self.use_graph = False                       # scatter_back sizes its scratch on the fly
-            logging.getLogger("cdml.train").warning("use_graph ignored: trainable sharded table runs eagerly")
+            warn("use_graph ignored: trainable sharded table runs eagerly")
         # (with RCCL inside: under capture the exchange is recorded on the capturing stream, see
         # dist.Prefetcher; verified over RCCL at world size 1, tests/test_gpu_dist.py)
         if self.use_graph and (exchange is not None or grad_sync is not None):
@@ -468,14 +476,12 @@ class TrainStep:
                       and _cdist._host_staged(h.group)]
             if staged:                                   # gloo rehearsal: collectives go through host memory
                 self.use_graph = False
-                logging.getLogger("cdml.train").warning(
-                    "use_graph ignored: host-staged (gloo) collectives cannot be captured; RCCL ones can")
+                warn("use_graph ignored: host-staged (gloo) collectives cannot be captured; RCCL ones can")
             elif self._needs_capture_groups() and _cdist.capture_groups_supported() is None:
                 # the capture-only groups need a default group bound to its device (dist.new_capture_group); a caller
                 # that initialised torch.distributed without device_id= (what worked through round 3) steps eagerly
                 self.use_graph = False
-                logging.getLogger("cdml.train").warning(
-                    "use_graph ignored: capturing RCCL collectives needs init_process_group(..., device_id=...); stepping eagerly")
+                warn("use_graph ignored: capturing RCCL collectives needs init_process_group(..., device_id=...); stepping eagerly")
             else:
                 self._ensure_capture_groups()
         # row-sharded catalogue: the exchange of step t+1 runs ahead on a side stream
@@ -492,16 +498,11 @@ class TrainStep:
             self.use_graph = True                        # nothing to overlap: one graph per step
 
     def _needs_capture_groups(self):
-        """True when a captured step of this job would issue an RCCL collective (a hook over the nccl backend that is
-        not skipped at world size 1)."""
-        for h in (self.exchange, self.grad_sync):
-            if h is None or not (torch.distributed.is_available() and torch.distributed.is_initialized()):
-                continue
-            if torch.distributed.get_backend(h.group) != "nccl":
-                continue
-            if h.world > 1 or not getattr(h, "skip_self", True) or getattr(h, "active", False):
-                return True
-        return False
+        """The hooks through which a captured step would issue an RCCL collective (nccl backend, not skipped at world size 1)."""
+        td = torch.distributed
+        return [h for h in (self.exchange, self.grad_sync)
+                if h is not None and td.is_available() and td.is_initialized() and td.get_backend(h.group) == "nccl"
+                and (h.world > 1 or not getattr(h, "skip_self", True) or getattr(h, "active", False))]
 
     def _ensure_capture_groups(self):
         """Captured collectives go through process groups of their own, which never carry an eager one: the RCCL watchdog's
@@ -510,14 +511,8 @@ class TrainStep:
         graphs, and again checked right before any capture (a step switched to graph replay later): a collective call,
         reached by every rank at the same point in the same order."""
         from . import dist as _cdist
-        for h in (self.exchange, self.grad_sync):
-            if h is None or getattr(h, "capture_group", None) is not None:
-                continue
-            if not (torch.distributed.is_available() and torch.distributed.is_initialized()):
-                continue
-            if torch.distributed.get_backend(h.group) != "nccl":
-                continue
-            if h.world > 1 or not getattr(h, "skip_self", True) or getattr(h, "active", False):
+        for h in self._needs_capture_groups():
+            if getattr(h, "capture_group", None) is None:
                 h.capture_group = _cdist.new_capture_group(h.group)
 
     @property
@@ -542,13 +537,16 @@ class TrainStep:
         sd = None
         if self.device.type == "cuda" and torch.cuda.is_current_stream_capturing():
             step, sd = 1, self.step_dev
-        if self.sampler_mode == MODE_UNIFORM:
-            ops.sample_uniform(self.pairs, self.table.n_rows_global, self.seed, step, self.B,
-                               self._idx[b], slot0=self.slot0, batch_global=self.batch_global, step_dev=sd)
-        else:
-            ops.sample_inbatch(self.pairs, self.seed, step, self.B, self._idx[b], self._shift[b],
-                               slot0=self.slot0, batch_global=self.batch_global, step_dev=sd)
+        self._sample(step, sd, self._idx[b], self._shift[b])
         self.exchange.gather(self.table, self._idx[b], self._x[b])
+
+    def _sample(self, step, step_dev, idx, shift):      # the sampler alone (a sharded catalogue: the exchange brings the rows)
+        if self.sampler_mode == MODE_UNIFORM:
+            ops.sample_uniform(self.pairs, self.table.n_rows_global, self.seed, step, self.B, idx,
+                               slot0=self.slot0, batch_global=self.batch_global, step_dev=step_dev)
+        else:
+            ops.sample_inbatch(self.pairs, self.seed, step, self.B, idx, shift,
+                               slot0=self.slot0, batch_global=self.batch_global, step_dev=step_dev)
 
     def _ahead_offset(self):
         """Position of the current step inside the block of steps the last gather launch
@@ -594,22 +592,15 @@ class TrainStep:
                                      self.neg_lists, self.hard_fraction, self.idx, self.ws.x_hat, kind_out=self.kind,
                                      slot0=self.slot0, batch_global=self.batch_global, step_dev=self.step_dev,
                                      oob_flag=self.oob,
-                                     x_ki=self.ws.xk if (self.x3 and getattr(self.ws, "kint", False)) else None)
+                                     x_ki=self.ws.xk if self.ws.kint else None)
         elif self.exchange is None:
             ops.sample_gather(m, self.pairs, self.seed, None, self.B, self.table.data,
                               self.table.feature_size, self.idx, self.ws.x_hat,
                               shift_out=self.shift, slot0=self.slot0,
                               batch_global=self.batch_global, step_dev=self.step_dev, oob_flag=self.oob,
-                              x_ki=self.ws.xk if (self.x3 and getattr(self.ws, "kint", False)) else None)
+                              x_ki=self.ws.xk if self.ws.kint else None)
         else:
-            if m == MODE_UNIFORM:
-                ops.sample_uniform(self.pairs, self.table.n_rows_global, self.seed, None, self.B,
-                                   self.idx, slot0=self.slot0, batch_global=self.batch_global,
-                                   step_dev=self.step_dev)
-            else:
-                ops.sample_inbatch(self.pairs, self.seed, None, self.B, self.idx, self.shift,
-                                   slot0=self.slot0, batch_global=self.batch_global,
-                                   step_dev=self.step_dev)
+            self._sample(None, self.step_dev, self.idx, self.shift)
             self.exchange.gather(self.table, self.idx, self.ws.x_hat)
 
     # ------------------------------------------------------- hard negatives --
@@ -643,7 +634,7 @@ class TrainStep:
             raise ValueError("k = %d gives lists of width %d, this step holds lists of width %d"
                              % (k, hardneg.list_width(k), self.neg_lists.shape[1]))
         if getattr(self, "_list_predictor", None) is None:
-            self._list_predictor = Prediction(params=self.params, precision="bf16" if self.bf16 else "f32x3" if self.x3 else "f32")
+            self._list_predictor = Prediction(params=self.params, precision=self.ws.INFERENCE)
         emb = self._list_predictor.embed_table(self.table, 16384)
         lists = hardneg.mine_lists(emb, k, skip_top=skip_top, pairs=self.pairs if drop_partners else None, device=self.device)
         self.set_negative_lists(lists)
@@ -669,37 +660,27 @@ class TrainStep:
         # precision f16x2: on its check steps (0, 1, 2, 4 .. 64, then every 64th) the plane scales are re-derived -- the weights'
         # and the hidden layer's before the forward pass, the gradients' once the loss tail has written dz2 (two small
         # device-to-host copies; engine_f16x2.PlaneScales)
-        due = self.h2 and self.ws.scales.due(self.global_step)
+        due = self.ws.scales_due(self.global_step)
         if due:
-            engine_f16x2.observe_weights(self.params, self.ws)
+            self.ws.observe_weights(self.params)
         self._forward_loss(with_grad)
         if due and with_grad:
-            engine_f16x2.observe_gradients(self.params, self.ws)
+            self.ws.observe_gradients(self.params)
 
     def _forward_loss(self, with_grad=True):
         # uniform / in-batch negatives: one launch normalises z, takes the loss and starts the
         # backward pass (semi-hard mining needs every embedded row first: separate kernels)
         fused = with_grad and self.mode not in ("semihard", "npair")
         # (semi-hard mining on the plane kernels: the miner's prep launch normalises z itself -- round 6)
-        mine_norm = (self.mode == "semihard" and getattr(self, "mine_fused", False)
-                     and os.environ.get("CDML_MINE_NORM", "1") != "0")
-        if self.h2:
-            engine_f16x2.tower_forward(self.params, self.ws, normalize=not (fused or mine_norm))
-        elif self.x3:
-            engine_x3.tower_forward(self.params, self.ws, normalize=not (fused or mine_norm))
-        elif self.bf16:
-            engine_bf16.tower_forward(self.params, self.ws, normalize=not fused)
-        else:
-            engine.tower_forward(self.params, self.ws, normalize=not fused)
+        mine_norm = self.mode == "semihard" and self.mine_fused and os.environ.get("CDML_MINE_NORM", "1") != "0"
+        self.engine.tower_forward(self.params, self.ws, normalize=not (fused or mine_norm))
         L = self.layout
         if fused:
+            planes, planes_done = self.ws.tail_operands()
             ops.vnet_tail(0 if self.mode == "uniform" else 1, self.ws.z, self.idx, self.shift, self.B, L.Dp,
                           self.margin, self.ws.e, self.pos, self.neg, self.hinge, self.ws.dz2, valid=self.valid,
-                          stats=self.stats, var_ws=self.var_ws,
-                          dz2_bf16=self.ws.dz2_bf if self.bf16 else self.ws.dz2_3 if self.x3 else self.ws.dz2_2 if self.h2 else None,
-                          plane_bf=L.Dp if (self.x3 or self.h2) else 0, h2_scale=self.ws.scales.dz2 if self.h2 else 0.0)
-            self.ws.tail_done = True
-            self.ws.dz2_planes_done = self.x3 or self.h2
+                          stats=self.stats, var_ws=self.var_ws, **planes)
+            self.ws.tail_done, self.ws.dz2_planes_done = True, planes_done
             return
         de = self.ws.de if with_grad else None
         if self.npair_mixed is not None:
@@ -730,7 +711,7 @@ class TrainStep:
             e = self.ws.e
             if self.mine_fused:
                 ops.semihard_mine_x3(e, self.idx, self.B, L.Dp, self.e3, L.Dp, self.sqn, self.dp, self.mine_ws, self.neg_row,
-                                     z=self.ws.z if mine_norm else None, h2_scale=engine_f16x2.X_SCALE if self.h2 else 0.0)
+                                     z=self.ws.z if mine_norm else None, h2_scale=self.mine_scale)
             else:
                 # S[i][c] = <anchor_i, row_c>: the data-gradient GEMM (x @ W^T) with no mask
                 ops.fc_bwd_data(e[0::2], e, None, self.S, self.B, 2 * self.B, L.Dp)
@@ -739,12 +720,10 @@ class TrainStep:
                 # round 6: the rest of the tail rides in the gradient launch -- every finished row gradient goes through the
                 # l2norm backward (+ leaky-relu') into dz2 and its operand copy (bf16 / three planes) on the spot: two
                 # launches fewer per step, bit-identical (CDML_INDEXED_TAIL=0: the separate launches, for A/B runs)
+                planes, planes_done = self.ws.tail_operands(indexed=True)
                 ops.triplet_hinge_indexed(e, self.neg_row, self.B, L.Dp, self.margin, self.pos, self.neg, self.hinge,
-                                          self.scale, self.stats, de, z=self.ws.z, dz2=self.ws.dz2,
-                                          dz2_bf16=self.ws.dz2_bf if self.bf16 else self.ws.dz2_3 if self.x3 else None,
-                                          plane_bf=L.Dp if self.x3 else 0)
-                self.ws.tail_done = True
-                self.ws.dz2_planes_done = self.x3
+                                          self.scale, self.stats, de, z=self.ws.z, dz2=self.ws.dz2, **planes)
+                self.ws.tail_done, self.ws.dz2_planes_done = True, planes_done
             else:
                 ops.triplet_hinge_indexed(e, self.neg_row, self.B, L.Dp, self.margin, self.pos, self.neg,
                                           self.hinge, self.scale, self.stats, de)
@@ -753,29 +732,14 @@ class TrainStep:
                                       self.pos, self.neg, self.hinge, self.valid, self.stats, de)
 
     def backward(self, after_w1=None):
-        if self.h2:
-            engine_f16x2.tower_backward(self.params, self.ws, after_w1=after_w1)
-        elif self.x3:
-            engine_x3.tower_backward(self.params, self.ws, after_w1=after_w1)
-        elif self.bf16:
-            engine_bf16.tower_backward(self.params, self.ws, after_w1=after_w1)
-        else:
-            engine.tower_backward(self.params, self.ws, after_w1=after_w1)
+        self.engine.tower_backward(self.params, self.ws, after_w1=after_w1)
 
     def update_table(self):
         """dLoss/d x_hat = dz1 . W1^T for the gathered rows, then the lazy-Adam update of the
         catalogue rows they came from (on their owners when the table is sharded).  Runs
         before the dense update: it needs this step's W1 and step counter."""
         L, p, t = self.layout, self.params, self.table
-        if self.h2:
-            sc = self.ws.scales
-            ops.gemm_f16x2_nt(ops.BE_F32, self.ws.dz1, L.Hp, self.ws.W1n, L.Hp, self.dxh, self.R, L.Fp, L.Hp,
-                              1.0 / (sc.dz1 * sc.w1))
-        elif self.x3:
-            ops.gemm_bf16x3_nt(ops.BE_F32, self.ws.dz1, L.Hp, self.ws.W1n, L.Hp, self.dxh, self.R, L.Fp, L.Hp,
-                               products=self.ws.products)
-        else:
-            ops.fc_bwd_data(self.ws.dz1, p.W1, None, self.dxh, self.R, L.Fp, L.Hp)
+        self.ws.row_gradient(p, self.dxh)
         idx, rows = self.idx, self.dxh
         if self.exchange is not None:
             idx, rows = self.exchange.scatter_back(self.dxh)
@@ -822,86 +786,46 @@ class TrainStep:
             for i, (off, n) in enumerate(p.segments()):    # W1, b1, W2, b2: weights carry the regulariser
                 ops.grad_prepare(p.grad[off:off + n], p.flat[off:off + n], self.reg_scale if i % 2 == 0 else 0.0,
                                  self.clip_gradient_norm, self.lars_scratch, self.grad_norms[i])
-        if self.optimizer == "adam" and self.h2:
-            # two fp16 planes: the same two launches, the copies written as the planes of W * its scale (the scales as of
-            # this step: engine_f16x2.observe_weights re-splits the weights itself when it moves one)
-            L, o, ws = self.layout, self.layout.offsets, self.ws
-            mat = lambda t, i, r, c: t[o[i]:o[i] + r * c].view(r, c)
-            kw = dict(lr_dev=self.lr_dev, t_dev=self.step_dev)
-            b1, b2 = slice(o[1], o[1] + L.Hp), slice(o[3], o[3] + L.Dp)
-            vec = lambda sl: (p.flat[sl], p.grad[sl], self.m[sl], self.v[sl])
-            w1n = getattr(ws, "W1n", None)                 # trainable table: W1's planes in their natural orientation too
-            ops.adam_matrix_bf16(p.W1, mat(p.grad, 0, L.Fp, L.Hp), mat(self.m, 0, L.Fp, L.Hp),
-                                 mat(self.v, 0, L.Fp, L.Hp), 0.0, 1, wt=ws.W1T, plane_t=L.Fp, bias=vec(b1),
-                                 h2_scale=ws.scales.w1, **(dict(kw, wc=w1n, plane_c=L.Hp) if w1n is not None else kw))
-            ops.adam_matrix_bf16(p.W2, mat(p.grad, 2, L.Hp, L.Dp), mat(self.m, 2, L.Hp, L.Dp),
-                                 mat(self.v, 2, L.Hp, L.Dp), 0.0, 1, wt=ws.W2T, plane_t=L.Hp, wc=ws.W2, plane_c=L.Dp,
-                                 bias=vec(b2), advance_tickets=self.adam_tickets, h2_scale=ws.scales.w2, **kw)
-        elif self.optimizer == "adam" and self.x3:
-            # split-fp32 precision: as on the config-4 path two launches, each weight matrix with its bias vector;
-            # the update writes the plane copies the GEMMs read (W1^T; W2^T and W2)
-            L, o, ws = self.layout, self.layout.offsets, self.ws
-            mat = lambda t, i, r, c: t[o[i]:o[i] + r * c].view(r, c)
-            kw = dict(lr_dev=self.lr_dev, t_dev=self.step_dev)
-            b1, b2 = slice(o[1], o[1] + L.Hp), slice(o[3], o[3] + L.Dp)
-            vec = lambda sl: (p.flat[sl], p.grad[sl], self.m[sl], self.v[sl])
-            w1n = getattr(ws, "W1n", None)                 # trainable table: W1's planes in their natural orientation too
-            ops.adam_matrix_bf16(p.W1, mat(p.grad, 0, L.Fp, L.Hp), mat(self.m, 0, L.Fp, L.Hp),
-                                 mat(self.v, 0, L.Fp, L.Hp), 0.0, 1, wt=ws.W1T, plane_t=L.Fp, bias=vec(b1),
-                                 **(dict(kw, wc=w1n, plane_c=L.Hp) if w1n is not None else kw))
-            ops.adam_matrix_bf16(p.W2, mat(p.grad, 2, L.Hp, L.Dp), mat(self.m, 2, L.Hp, L.Dp),
-                                 mat(self.v, 2, L.Hp, L.Dp), 0.0, 1, wt=ws.W2T, plane_t=L.Hp, wc=ws.W2, plane_c=L.Dp,
-                                 bias=vec(b2), advance_tickets=self.adam_tickets, **kw)
-        elif self.optimizer == "adam" and self.bf16:
-            # config-4 precision: two launches -- each weight matrix with its bias vector; the update
-            # also writes the bf16 operand copies the GEMMs read (no separate transposes / cast), and
-            # the last block of the second launch advances the step counter
-            L, o, ws = self.layout, self.layout.offsets, self.ws
-            mat = lambda t, i, r, c: t[o[i]:o[i] + r * c].view(r, c)
-            kw = dict(lr_dev=self.lr_dev, t_dev=self.step_dev)
-            b1, b2 = slice(o[1], o[1] + L.Hp), slice(o[3], o[3] + L.Dp)
-            vec = lambda sl: (p.flat[sl], p.grad[sl], self.m[sl], self.v[sl])
-            ops.adam_matrix_bf16(p.W1, mat(p.grad, 0, L.Fp, L.Hp), mat(self.m, 0, L.Fp, L.Hp),
-                                 mat(self.v, 0, L.Fp, L.Hp), 0.0, 1, wt=ws.W1T, bias=vec(b1), **kw)
-            ops.adam_matrix_bf16(p.W2, mat(p.grad, 2, L.Hp, L.Dp), mat(self.m, 2, L.Hp, L.Dp),
-                                 mat(self.v, 2, L.Hp, L.Dp), 0.0, 1, wt=ws.W2T, wc=ws.W2, bias=vec(b2),
-                                 advance_tickets=self.adam_tickets, **kw)
-        elif self.optimizer == "adam":
-            # the step counter advances inside the same launch
-            ops.adam_step(p.flat, p.grad, self.m, self.v, 0.0, 1, lr_dev=self.lr_dev,
-                          t_dev=self.step_dev, advance_tickets=self.adam_tickets)
-        elif self.x3 or self.bf16 or self.h2:
-            # LARS / momentum on the plane (f32x3, f16x2) or bf16 (config 4) paths: two matrix launches, each weight matrix with
-            # its bias vector, writing the operand copies the GEMMs read with the update (as the Adam launches above do --
-            # round 3 ran separate split / transpose launches after the optimizer); the last one advances the step counter
-            L, o, ws = self.layout, self.layout.offsets, self.ws
-            pt1, pt2, pc2 = (L.Fp, L.Hp, L.Dp) if (self.x3 or self.h2) else (0, 0, 0)
-            s1, s2 = (ws.scales.w1, ws.scales.w2) if self.h2 else (0.0, 0.0)     # (f16x2: fp16 planes of W * its scale)
-            if self.optimizer == "lars":
-                segs = p.segments()
-                ops.lars_multi_norms(p.flat, p.grad, segs, self.lars_scratch)
-                kw = dict(lr_dev=self.lr_dev)
-                ops.lars_matrix(p.flat, p.grad, self.acc, segs, 0, 1, L.Fp, L.Hp, 0.0, self.lars_scratch, wt=ws.W1T,
-                                plane_t=pt1, h2_scale=s1, **kw)
-                ops.lars_matrix(p.flat, p.grad, self.acc, segs, 2, 3, L.Hp, L.Dp, 0.0, self.lars_scratch, wt=ws.W2T, wc=ws.W2,
-                                plane_t=pt2, plane_c=pc2, step_dev=self.step_dev, tickets=self.adam_tickets, h2_scale=s2, **kw)
+        copies = self.ws.optimizer_operands()
+        if copies is None:                                 # fp32 MFMA: the masters are the operands, one flat update
+            if self.optimizer == "adam":
+                # the step counter advances inside the same launch
+                ops.adam_step(p.flat, p.grad, self.m, self.v, 0.0, 1, lr_dev=self.lr_dev,
+                              t_dev=self.step_dev, advance_tickets=self.adam_tickets)
+            elif self.optimizer == "momentum":
+                ops.momentum_step(p.flat, p.grad, self.acc, 0.0, 0.9, True, lr_dev=self.lr_dev)
+                ops.step_advance(self.step_dev)
             else:
-                mat = lambda t, i, r, c: t[o[i]:o[i] + r * c].view(r, c)
-                b1, b2 = slice(o[1], o[1] + L.Hp), slice(o[3], o[3] + L.Dp)
-                vec = lambda sl: (p.flat[sl], p.grad[sl], self.acc[sl])
-                ops.momentum_matrix(p.W1, mat(p.grad, 0, L.Fp, L.Hp), mat(self.acc, 0, L.Fp, L.Hp), 0.0, wt=ws.W1T,
-                                    plane_t=pt1, lr_dev=self.lr_dev, bias=vec(b1), h2_scale=s1)
-                ops.momentum_matrix(p.W2, mat(p.grad, 2, L.Hp, L.Dp), mat(self.acc, 2, L.Hp, L.Dp), 0.0, wt=ws.W2T, wc=ws.W2,
-                                    plane_t=pt2, plane_c=pc2, lr_dev=self.lr_dev, bias=vec(b2), step_dev=self.step_dev,
-                                    tickets=self.adam_tickets, h2_scale=s2)
-        elif self.optimizer == "momentum":
-            ops.momentum_step(p.flat, p.grad, self.acc, 0.0, 0.9, True, lr_dev=self.lr_dev)
-            ops.step_advance(self.step_dev)
+                # LARS: one trust ratio per variable, all four variables in two launches; the second
+                # also advances the step counter
+                ops.lars_multi(p.flat, p.grad, self.acc, p.segments(), 0.0, self.lars_scratch, lr_dev=self.lr_dev,
+                               step_dev=self.step_dev, tickets=self.adam_tickets)
+            return
+        # the bf16 (config 4) and plane (f32x3, f16x2) engines: two matrix launches, each weight matrix with its bias vector,
+        # writing the operand copies the GEMMs read with the update; the last block of the second advances the step counter
+        L, o = self.layout, self.layout.offsets
+        c1, c2 = copies
+        mat = lambda t, i, r, c: t[o[i]:o[i] + r * c].view(r, c)
+        b1, b2 = slice(o[1], o[1] + L.Hp), slice(o[3], o[3] + L.Dp)
+        if self.optimizer == "adam":
+            kw = dict(lr_dev=self.lr_dev, t_dev=self.step_dev)
+            vec = lambda sl: (p.flat[sl], p.grad[sl], self.m[sl], self.v[sl])
+            ops.adam_matrix_bf16(p.W1, mat(p.grad, 0, L.Fp, L.Hp), mat(self.m, 0, L.Fp, L.Hp),
+                                 mat(self.v, 0, L.Fp, L.Hp), 0.0, 1, bias=vec(b1), **c1, **kw)
+            ops.adam_matrix_bf16(p.W2, mat(p.grad, 2, L.Hp, L.Dp), mat(self.m, 2, L.Hp, L.Dp),
+                                 mat(self.v, 2, L.Hp, L.Dp), 0.0, 1, bias=vec(b2), advance_tickets=self.adam_tickets, **c2, **kw)
+        elif self.optimizer == "lars":
+            segs = p.segments()
+            ops.lars_multi_norms(p.flat, p.grad, segs, self.lars_scratch)
+            ops.lars_matrix(p.flat, p.grad, self.acc, segs, 0, 1, L.Fp, L.Hp, 0.0, self.lars_scratch, lr_dev=self.lr_dev, **c1)
+            ops.lars_matrix(p.flat, p.grad, self.acc, segs, 2, 3, L.Hp, L.Dp, 0.0, self.lars_scratch, lr_dev=self.lr_dev,
+                            step_dev=self.step_dev, tickets=self.adam_tickets, **c2)
         else:
-            # LARS: one trust ratio per variable, all four variables in two launches; the second
-            # also advances the step counter
-            ops.lars_multi(p.flat, p.grad, self.acc, p.segments(), 0.0, self.lars_scratch, lr_dev=self.lr_dev,
-                           step_dev=self.step_dev, tickets=self.adam_tickets)
+            vec = lambda sl: (p.flat[sl], p.grad[sl], self.acc[sl])
+            ops.momentum_matrix(p.W1, mat(p.grad, 0, L.Fp, L.Hp), mat(self.acc, 0, L.Fp, L.Hp), 0.0, lr_dev=self.lr_dev,
+                                bias=vec(b1), **c1)
+            ops.momentum_matrix(p.W2, mat(p.grad, 2, L.Hp, L.Dp), mat(self.acc, 2, L.Hp, L.Dp), 0.0, lr_dev=self.lr_dev,
+                                bias=vec(b2), step_dev=self.step_dev, tickets=self.adam_tickets, **c2)
 
     def _enqueue(self):
         self.fetch()
@@ -933,7 +857,7 @@ class TrainStep:
                 self.prefetch.wait_ready(1 - b)
             n1 = self.layout.offsets[2]
             handles = []
-            (engine_f16x2 if self.h2 else engine_x3 if self.x3 else engine_bf16 if self.bf16 else engine).tower_backward(
+            self.engine.tower_backward(
                 self.params, self.ws, after_w1=lambda: handles.append(self.grad_sync.start(self.params.grad, 0, n1)))
             handles.append(self.grad_sync.start(self.params.grad, n1, self.layout.numel))
             self.grad_sync.finish(handles)
@@ -945,7 +869,7 @@ class TrainStep:
             # GEMM -- and [dW2|db2] right after its GEMM; the optimizer waits for all of them
             n1 = self.layout.offsets[2]
             handles = []
-            (engine_f16x2 if self.h2 else engine_x3 if self.x3 else engine_bf16 if self.bf16 else engine).tower_backward(
+            self.engine.tower_backward(
                 self.params, self.ws, w1_chunks=2,
                 after_w1_chunk=lambda lo, hi: handles.append(self.grad_sync.start(self.params.grad, lo, hi)))
             handles.append(self.grad_sync.start(self.params.grad, n1, self.layout.numel))
@@ -966,11 +890,11 @@ class TrainStep:
             self._lr_host = lr
         # precision f16x2 under use_graph: a check step of the plane scales (host reads) runs eagerly, and graphs recorded with
         # scales that have moved since are dropped (re-captured on the next replay step)
-        h2_eager = self.h2 and bool(self.use_graph) and self.ws.scales.due(self.global_step)
+        scales_eager = bool(self.use_graph) and self.ws.scales_due(self.global_step)
         if self.use_graph == "split" and self._warmed and self.prefetch is not None:
             self._step_split(self.global_step)
             self._replayed = True
-        elif self.use_graph and self._warmed and not h2_eager:   # the first step of a process runs eagerly
+        elif self.use_graph and self._warmed and not scales_eager:   # the first step of a process runs eagerly
             t = self.global_step                         # (it loads the kernels), also after a resume
             if self.prefetch is not None:
                 # one graph per prefetch buffer; the rows of step t were fetched by step t-1 (an
@@ -1000,10 +924,10 @@ class TrainStep:
             self._replayed = False
             self._enqueue()
             self._warmed = True
-            if self.h2 and self.use_graph:
-                sig = tuple(sorted(self.ws.scales.state().items()))
-                if sig != self._h2_sig:
-                    self._graphs, self._h2_sig = {}, sig
+            if self.use_graph:
+                sig = self.ws.scales and tuple(sorted(self.ws.scales.state().items()))      # (f16x2: baked into a capture)
+                if sig != self._scale_sig:
+                    self._graphs, self._scale_sig = {}, sig
         self.global_step += 1
 
     def _capture(self, fn=None, origin=None):
@@ -1138,9 +1062,9 @@ class TrainStep:
         if self.train_table:                             # this rank's shard and its Adam states
             state["table"] = {"row0": self.table.row0, "rows": self.table.data.detach().cpu().clone(),
                               "m": self.tab_m.detach().cpu().clone(), "v": self.tab_v.detach().cpu().clone()}
-        if self.h2:                                      # precision f16x2: the plane scales are state (a resumed run keeps the
-            sc = self.ws.scales                          # straight run's bits only with the scales that run would hold)
-            state["plane_scales"] = dict(sc.state(), calibrated=sc.calibrated, changes=sc.changes, last=dict(sc.last))
+        scales = self.ws.scales_state()                  # precision f16x2: the plane scales are state (a resumed run keeps the
+        if scales is not None:                           # straight run's bits only with the scales that run would hold)
+            state["plane_scales"] = scales
         if self.npair_memory is not None:                # the ring as fp32 rows + ids (the planes are re-derived on load)
             state["npair_memory"] = self.npair_memory.state_dict()
         if isinstance(self.npair_logq, ops.LogQEstimator):   # (a fixed logQ table is an argument, not state)
@@ -1164,19 +1088,9 @@ class TrainStep:
             self.table.data.copy_(state["table"]["rows"].to(self.device))
             self.tab_m.copy_(state["table"]["m"].to(self.device))
             self.tab_v.copy_(state["table"]["v"].to(self.device))
-        if self.bf16:                                    # the GEMMs read the bf16 copies, not the masters
-            engine_bf16.refresh_weights(self.params, self.ws)
-        if self.h2:
-            sc, saved = self.ws.scales, state.get("plane_scales")
-            if saved:                                    # the checkpointed run's scales, and the weights' planes at them
-                for k in ("w1", "w2", "h1", "dz2", "dz1"):
-                    setattr(sc, k, float(saved[k]))
-                sc.calibrated, sc.changes, sc.last = bool(saved["calibrated"]), int(saved["changes"]), dict(saved["last"])
-                engine_f16x2.refresh_weights(self.params, self.ws)
-            else:
-                sc.calibrated = False                    # (a checkpoint of another precision: the next step calibrates)
-        if self.x3:
-            engine_x3.refresh_weights(self.params, self.ws)
+        # the GEMMs read the operand copies, not the masters (f16x2: at the checkpoint's scales, or the next step calibrates)
+        if not self.ws.load_scales(self.params, state.get("plane_scales")):
+            self.engine.refresh_weights(self.params, self.ws)
         ring = state.get("npair_memory")
         if ring is not None and int(ring["size"]) != self.memory_size:
             raise ValueError("the checkpoint holds a cross-batch memory of %d rows, this step one of %d"
