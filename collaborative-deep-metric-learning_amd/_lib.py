@@ -245,6 +245,11 @@ SIGNATURES_HARDNEG = {
                                            _p, _p, _p, _i64, _i, _i64, _i64, _i64, _p, _p]),
 }
 
+# name -> (restype, argtypes); must list every symbol include/cdml_x3_wide.h declares (dW1 with dz1 k8-interleaved)
+SIGNATURES_WIDE = {
+    "cdml_gemm_bf16x3_tn_kb": (_i, [_p, _i64, _i64, _p, _i, _i, _i, _i, _i, _p, _i64, _p, _p, _sz, _p]),
+}
+
 _lib = None
 
 
@@ -264,7 +269,7 @@ def load_library():
     import torch  # noqa: F401
     lib = C.CDLL(path)
     for name, (res, args) in (list(SIGNATURES.items()) + list(SIGNATURES_MIXED.items()) + list(SIGNATURES_DP.items())
-                               + list(SIGNATURES_BF16.items()) + list(SIGNATURES_HARDNEG.items())):
+                               + list(SIGNATURES_BF16.items()) + list(SIGNATURES_HARDNEG.items()) + list(SIGNATURES_WIDE.items())):
         fn = getattr(lib, name)          # AttributeError if the ABI lost a symbol
         fn.restype = res
         fn.argtypes = args

@@ -117,6 +117,9 @@ int launch_gemm_f16x2_rank(const BArgs &g, hipStream_t stream);
 // the k-strided product on k8-INTERLEAVED operands ([plane][k / 8][column][8 k]; g.lda / g.ldb = elements per k-group,
 // g.x3_plane_* = elements per plane): the resident-plane walk with one 16-B LDS read per fragment
 int launch_gemm_x3_tnk(const BArgs &g, int splits, hipStream_t stream);
+// the same walk with ONLY g.B k8-interleaved (g.A row-major k-strided, as launch_gemm_bf16_256_x3's k-strided form reads
+// it) and the waves tiled 4 row groups x 2 column strips: g.B is the wide operand of a wave's 64 x 128 tile
+int launch_gemm_x3_tnkb(const BArgs &g, int splits, hipStream_t stream);
 
 // streaming kernel for the mask / plain-bf16 epilogue (BE_MASK_BF16) at K == 256: N % 256 == 0,
 // lda / ldb / ldc / ldaux multiples of 8, A inside the 2 GiB buffer-descriptor window

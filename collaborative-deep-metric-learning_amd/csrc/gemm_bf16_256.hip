@@ -165,7 +165,7 @@ __device__ __forceinline__ i32x4 make_srd(const void *base, int64_t bytes) {
 // [8 k-groups][128 columns][16 B] is filled by 1-KiB pieces that are contiguous in memory.  Same images, slots, DMA schedule,
 // accumulation order and results as the k-strided form (test_gemm_x3_tnk_equals_tn: bit for bit).
 template <bool TN, int EPI, bool S16, bool X3 = false, bool F6 = false, bool NTCS = false, bool R6 = false, bool NARROW = false,
-          bool KI = false>
+          bool KI = false, bool WIDEB = false>
 __device__ __forceinline__ void run_tile(const BArgs &g, const int tm, const int m0, const int n0, const int k_begin,
                                          const int n_ktiles, void *c_base, const int64_t c_ld, const int c_row0,
                                          const int c_col0, float *cs_row, const int64_t cs_grp_stride,
@@ -178,6 +178,9 @@ __device__ __forceinline__ void run_tile(const BArgs &g, const int tm, const int
   static_assert((EPI != BE_MINE_X3 && EPI != BE_KNN_X3 && EPI != BE_RANK_X3) || (X3 && S16 && R6 && !TN && !NARROW),
                 "the mining / kNN-filter / rank-count epilogues ride on the resident-plane walk");
   static_assert(!KI || (TN && X3 && S16 && R6), "the k8-interleaved operands exist for the k-strided resident-plane walk");
+  static_assert(!WIDEB || (TN && X3 && S16 && R6 && !KI && !kF16 && !NARROW && EPI == BE_F32),
+                "the wide column operand exists for the bf16 k-strided resident-plane walk");
+  constexpr bool KIA = KI, KIB = KI || WIDEB;                  // which operand is stored k8-interleaved
   const int t = threadIdx.x;
   const int lane = t & 63;
   const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
@@ -196,8 +199,8 @@ __device__ __forceinline__ void run_tile(const BArgs &g, const int tm, const int
   constexpr bool kSwap = EPI == BE_MINE_X3 || EPI == BE_KNN_X3 || EPI == BE_RANK_X3;
 
   const int k_rows = X3 ? g.x3_tpp * kTileK : g.K;              // k-strided form: rows of the operands in memory
-  const i32x4 srd_a = make_srd(g.A, KI ? 3 * g.x3_plane_a * 2 : (int64_t)(TN ? k_rows : g.M) * g.lda * 2);
-  const i32x4 srd_b = make_srd(g.B, KI ? 3 * g.x3_plane_b * 2 : (int64_t)(TN ? k_rows : g.N) * g.ldb * 2);
+  const i32x4 srd_a = make_srd(g.A, KIA ? 3 * g.x3_plane_a * 2 : (int64_t)(TN ? k_rows : g.M) * g.lda * 2);
+  const i32x4 srd_b = make_srd(g.B, KIB ? 3 * g.x3_plane_b * 2 : (int64_t)(TN ? k_rows : g.N) * g.ldb * 2);
 
   // ---- DMA lane constants.  NT: piece pc = wave*2+i covers image rows pc*8 .. pc*8+7
   //      (128-B rows); TN: k-rows pc*4 .. pc*4+3 (256-B rows) ----
@@ -211,16 +214,16 @@ __device__ __forceinline__ void run_tile(const BArgs &g, const int tm, const int
       const int col_b = (r >> 5) * 64 + (r & 31);            // B-h0 (B-h1: + 32 columns)
       va[i] = (uint32_t)(((int64_t)(m0 + row_a) * g.lda + sc * 8) * 2);
       vb[i] = (uint32_t)(((int64_t)(n0 + col_b) * g.ldb + sc * 8) * 2);
-    } else if constexpr (KI) {
-      // piece pc = k-group pc >> 1, columns (pc & 1) * 64 + lane of the half image: 64 x 16 B contiguous in memory
-      const int pc = wave * 2 + i;
-      va[i] = (uint32_t)(((int64_t)(pc >> 1) * g.lda + (int64_t)(m0 + (pc & 1) * 64 + lane) * 8) * 2);   // A-h1: + 128 columns
-      vb[i] = (uint32_t)(((int64_t)(pc >> 1) * g.ldb + (int64_t)(n0 + (pc & 1) * 64 + lane) * 8) * 2);
     } else {
-      const int r = (wave * 2 + i) * 4 + (lane >> 4);
+      // interleaved: piece pc = k-group pc >> 1, columns (pc & 1) * 64 + lane of the half image: 64 x 16 B contiguous in memory;
+      // row-major: k-rows pc * 4 .. + 3, chunk-swizzled (A-h1 / B-h1: + 128 columns)
+      const int pc = wave * 2 + i;
+      const int r = pc * 4 + (lane >> 4);
       const int sc = (lane & 15) ^ (((r & 3) << 2) | ((r >> 2) & 3));
-      va[i] = (uint32_t)(((int64_t)r * g.lda + m0 + sc * 8) * 2);   // A-h1: + 128 columns
-      vb[i] = (uint32_t)(((int64_t)r * g.ldb + n0 + sc * 8) * 2);
+      if constexpr (KIA) va[i] = (uint32_t)(((int64_t)(pc >> 1) * g.lda + (int64_t)(m0 + (pc & 1) * 64 + lane) * 8) * 2);
+      else va[i] = (uint32_t)(((int64_t)r * g.lda + m0 + sc * 8) * 2);
+      if constexpr (KIB) vb[i] = (uint32_t)(((int64_t)(pc >> 1) * g.ldb + (int64_t)(n0 + (pc & 1) * 64 + lane) * 8) * 2);
+      else vb[i] = (uint32_t)(((int64_t)r * g.ldb + n0 + sc * 8) * 2);
     }
   }
   const uint32_t d_a = TN ? 256u : (uint32_t)(64 * g.lda * 2), d_b = TN ? 256u : (uint32_t)(32 * g.ldb * 2);
@@ -345,7 +348,7 @@ __device__ __forceinline__ void run_tile(const BArgs &g, const int tm, const int
 #pragma unroll
   for (int sh = 0; sh < 2; ++sh) {
 #pragma unroll
-    for (int rb = 0; rb < 4; ++rb) ta16[rb][sh] = tr_off16(grp * 8 + 2 * rb, sh);
+    for (int rb = 0; rb < 4; ++rb) ta16[rb][sh] = tr_off16((WIDEB ? (grp * 2 + (wc >> 1)) * 4 : grp * 8) + 2 * rb, sh);   // (WIDEB: rb 0, 1 only)
 #pragma unroll
     for (int cb = 0; cb < 2; ++cb) tb16[cb][sh] = tr_off16(wc * 4 + 2 * cb, sh);
   }
@@ -374,6 +377,18 @@ __device__ __forceinline__ void run_tile(const BArgs &g, const int tm, const int
   for (int i = 0; i < (S16 ? 8 : 1); ++i)
 #pragma unroll
     for (int j = 0; j < (S16 ? 4 : 1); ++j) acc16[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  // WIDEB (the wide column operand; k-strided resident-plane walk, B k8-interleaved, A row-major): the eight waves tile the
+  // 256 x 256 block as 4 row groups x 2 column strips -- a wave's tile is 64 x 128 instead of 128 x 64 -- so that the operand
+  // whose fragments are ONE 16-B LDS read each supplies two thirds of them.  Ping-pong set `grp` = wave >> 2 as before; inside
+  // a set, row sub-group wc >> 1 and strip wc & 1: the wave owns rows (2 grp + (wc >> 1)) * 32 .. + 31 of each A half image
+  // and columns (wc & 1) * 64 .. + 63 of each B half image.  Images, slots, DMA schedule, counted waits and the order in
+  // which an output element meets its K-tiles and plane products are those of the row-major form: the same bits.
+  // fbx[hh * 8 + cb * 2 + ks2] = column block cb (0 .. 3) of B half hh; fa[ks2][rb], rb = 0, 1; accumulator block
+  // acc16[4 HALF + 2 hh + rb][cb] = rows HALF 128 + (2 grp + (wc >> 1)) 32 + rb 16 .., columns hh 128 + (wc & 1) 64 + cb 16 ..
+  bf16x8 fbx[WIDEB ? 16 : 1];
+  float csw[WIDEB ? 8 : 1];
+#pragma unroll
+  for (int i = 0; i < (WIDEB ? 8 : 1); ++i) csw[i] = 0.f;
   bf16x8 fa[2][4], fb0[4], fb1[4];     // 32x32x16: [mi][ks], [ks];  16x16x32: fa[ks2][rb], fb0 = [cb of half 0..1][ks2] ...
 
   // Bias gradient riding along (k-strided form): db[n] = sum_k B[k][n].  The tiles_m blocks and
@@ -680,8 +695,8 @@ __device__ __forceinline__ void run_tile(const BArgs &g, const int tm, const int
     const int n_per = n_ktiles / kPer;                     // whole periods (host)
     if (n_per > 0) {                                       // (an empty split writes zeros)
       const int w_first = x3_t0 / kPer, w_last = w_first + n_per - 1;
-      const uint32_t ws_a = KI ? (uint32_t)(8 * g.lda * 2) : TN ? (uint32_t)(kTileK * g.lda * 2) : (uint32_t)(kTileK * 2);   // bytes per K-tile of a plane
-      const uint32_t ws_b = KI ? (uint32_t)(8 * g.ldb * 2) : TN ? (uint32_t)(kTileK * g.ldb * 2) : (uint32_t)(kTileK * 2);
+      const uint32_t ws_a = KIA ? (uint32_t)(8 * g.lda * 2) : TN ? (uint32_t)(kTileK * g.lda * 2) : (uint32_t)(kTileK * 2);   // bytes per K-tile of a plane
+      const uint32_t ws_b = KIB ? (uint32_t)(8 * g.ldb * 2) : TN ? (uint32_t)(kTileK * g.ldb * 2) : (uint32_t)(kTileK * 2);
       const uint32_t ps_a = (uint32_t)(g.x3_plane_a * 2), ps_b = (uint32_t)(g.x3_plane_b * 2);
       const unsigned char *b16r = smem + 6 * IMG + (wc * 32 + l15) * 128;
       // k-strided form: the transposed reads address LDS as (lane offset register) + (16-bit immediate).  160 KiB need
@@ -689,28 +704,31 @@ __device__ __forceinline__ void run_tile(const BArgs &g, const int tm, const int
       // by 64 / 96 KiB -- made opaque to the optimizer, which otherwise forms one hoisted register per DISTINCT large
       // constant (dozens over the 24 unrolled phases: 61 spilled VGPRs, measured)
       int ta_w2[4][2], tb_w[2][2];
-      if constexpr (TN && !KI) {
+      if constexpr (TN && !KIA) {
 #pragma unroll
-        for (int sh = 0; sh < 2; ++sh) {
+        for (int sh = 0; sh < 2; ++sh)
 #pragma unroll
-          for (int rb = 0; rb < 4; ++rb) {
+          for (int rb = 0; rb < (WIDEB ? 2 : 4); ++rb) {
             ta_w2[rb][sh] = ta16[rb][sh] + 4 * IMG;
             asm volatile("" : "+v"(ta_w2[rb][sh]));
           }
+      }
+      if constexpr (TN && !KIB) {
+#pragma unroll
+        for (int sh = 0; sh < 2; ++sh)
 #pragma unroll
           for (int cb = 0; cb < 2; ++cb) {
             tb_w[cb][sh] = tb16[cb][sh] + 6 * IMG;
             asm volatile("" : "+v"(tb_w[cb][sh]));
           }
-        }
       }
       // k8-interleaved images [8 k-groups][128 columns][16 B]: lane (l15, q) reads k-group 4 ks2 + q of its column
       const unsigned char *ka_rd = smem + (q16 * 128 + grp * 64 + l15) * 16;
-      const unsigned char *kb_rd = smem + 6 * IMG + (q16 * 128 + wc * 32 + l15) * 16;
+      const unsigned char *kb_rd = smem + 6 * IMG + (q16 * 128 + (WIDEB ? (wc & 1) * 64 : wc * 32) + l15) * 16;   // (WIDEB: cb 0 .. 3)
       auto rd_a = [&](int slot, int hh, int rb, int ks2) {
         if constexpr (!TN)
           return *reinterpret_cast<const bf16x8 *>(a16_rd + slot * 2 * IMG + hh * IMG + rb * 2048 + sw16[ks2]);
-        else if constexpr (KI)
+        else if constexpr (KIA)
           return *reinterpret_cast<const bf16x8 *>(ka_rd + slot * 2 * IMG + hh * IMG + ks2 * 8192 + rb * 256);
         else if (slot < 2)
           return tr_read(smem + slot * 2 * IMG + hh * IMG + ks2 * 8192, ta16[rb][0], ta16[rb][1]);
@@ -720,7 +738,7 @@ __device__ __forceinline__ void run_tile(const BArgs &g, const int tm, const int
       auto rd_b = [&](int slot, int hh, int cb, int ks2) {
         if constexpr (!TN)
           return *reinterpret_cast<const bf16x8 *>(b16r + slot * 2 * IMG + hh * IMG + cb * 2048 + sw16[ks2]);
-        else if constexpr (KI)
+        else if constexpr (KIB)
           return *reinterpret_cast<const bf16x8 *>(kb_rd + slot * 2 * IMG + hh * IMG + ks2 * 8192 + cb * 256);
         else
           return tr_read(smem + slot * 2 * IMG + hh * IMG + ks2 * 8192, tb_w[cb][0], tb_w[cb][1]);
@@ -732,7 +750,7 @@ __device__ __forceinline__ void run_tile(const BArgs &g, const int tm, const int
       // (whether the check also sees the scalar offset is not something to depend on)
       uint32_t va_h1[2] = {va[0] + d_a, va[1] + d_a}, vb_h1[2] = {vb[0] + d_b, vb[1] + d_b};
       auto issue = [&](int img, int pl, int hh, int slot, uint32_t kw) {
-        const uint32_t so = (img == 0 ? pl * ps_a : pl * ps_b) + kw + (KI ? hh * 2048u : TN ? hh * 256u : 0u);
+        const uint32_t so = (img == 0 ? pl * ps_a : pl * ps_b) + kw + ((img == 0 ? KIA : KIB) ? hh * 2048u : TN ? hh * 256u : 0u);
         const uint32_t dst = lds_piece + (img == 0 ? 0 : 6 * IMG) + slot * 2 * IMG + hh * IMG;
         const bool h1 = !TN && hh == 1;
         dma_s(img == 0 ? srd_a : srd_b, img == 0 ? (h1 ? va_h1[0] : va[0]) : (h1 ? vb_h1[0] : vb[0]), so, dst);
@@ -872,6 +890,14 @@ __device__ __forceinline__ void run_tile(const BArgs &g, const int tm, const int
         constexpr bool rdB = HALF == 0 && (S == 0 || S == 3 || S == 5);
         if constexpr (rdB) {
           constexpr int sb = (PB[S] & 1) ^ PAR;
+          if constexpr (WIDEB) {
+#pragma unroll
+            for (int hh = 0; hh < 2; ++hh)
+#pragma unroll
+              for (int cb = 0; cb < 4; ++cb)
+#pragma unroll
+                for (int ks2 = 0; ks2 < 2; ++ks2) fbx[hh * 8 + cb * 2 + ks2] = rd_b(sb, hh, cb, ks2);
+          } else {
 #pragma unroll
           for (int cb = 0; cb < 2; ++cb)
 #pragma unroll
@@ -879,11 +905,12 @@ __device__ __forceinline__ void run_tile(const BArgs &g, const int tm, const int
               fb0[2 * cb + ks2] = rd_b(sb, 0, cb, ks2);
               fb1[2 * cb + ks2] = rd_b(sb, 1, cb, ks2);
             }
+          }
         }
 #pragma unroll
         for (int ks2 = 0; ks2 < 2; ++ks2)
 #pragma unroll
-          for (int rb = 0; rb < 4; ++rb) fa[ks2][rb] = rd_a(sa, HALF, rb, ks2);
+          for (int rb = 0; rb < (WIDEB ? 2 : 4); ++rb) fa[ks2][rb] = rd_a(sa, HALF, rb, ks2);
         if constexpr (PH == 0) issue(0, 2, 1, SLOT_A[PAR][2], kwa_c);
         if constexpr (PH == 1) issue(1, 1, 0, 1 ^ PAR, kwb_c);
         if constexpr (PH == 2) issue(1, 1, 1, 1 ^ PAR, kwb_c);
@@ -898,6 +925,36 @@ __device__ __forceinline__ void run_tile(const BArgs &g, const int tm, const int
         if constexpr (PH == 11) issue(0, 2, 0, SLOT_A[PAR ^ 1][2], kwa_n);
         constexpr int VM[12] = {8, 8, 8, 8, 8, 6, 8, 10, 12, 10, 12, 6};
         asm volatile("s_waitcnt vmcnt(%0)" :: "n"(VM[PH]) : "memory");
+        if constexpr (WIDEB) {
+          if constexpr (rdB)
+            asm volatile("" : "+v"(fbx[0]), "+v"(fbx[1]), "+v"(fbx[2]), "+v"(fbx[3]), "+v"(fbx[4]), "+v"(fbx[5]), "+v"(fbx[6]), "+v"(fbx[7]),
+                              "+v"(fbx[8]), "+v"(fbx[9]), "+v"(fbx[10]), "+v"(fbx[11]), "+v"(fbx[12]), "+v"(fbx[13]), "+v"(fbx[14]), "+v"(fbx[15]));
+          asm volatile("" : "+v"(fa[0][0]), "+v"(fa[0][1]), "+v"(fa[1][0]), "+v"(fa[1][1]));
+          if constexpr (rdB) {
+            // bias gradient: the K-tile's owner (tile, set) as in the row-major form; of the two waves of a set that hold
+            // the same B fragments, row sub-group 0 sums them -- per column the same values in the same order
+            if (own && (wc >> 1) == 0) {
+#pragma unroll
+              for (int hc = 0; hc < 8; ++hc)
+#pragma unroll
+                for (int ks2 = 0; ks2 < 2; ++ks2) csw[hc] = dot_sum(fbx[hc * 2 + ks2], csw[hc]);
+            }
+          }
+          CDML_BARRIER();
+          __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+          for (int ks2 = 0; ks2 < 2; ++ks2)
+#pragma unroll
+            for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+              for (int hh = 0; hh < 2; ++hh)
+#pragma unroll
+                for (int cb = 0; cb < 4; ++cb)
+                  acc16[4 * HALF + 2 * hh + rb][cb] = CDML_MFMA16(fa[ks2][rb], fbx[hh * 8 + cb * 2 + ks2], acc16[4 * HALF + 2 * hh + rb][cb]);
+          __builtin_amdgcn_s_setprio(0);
+          CDML_BARRIER();
+          return;
+        }
         if constexpr (rdB) pin_b();
         pin_a();
         if constexpr (rdB) {
@@ -1138,7 +1195,17 @@ __device__ __forceinline__ void run_tile(const BArgs &g, const int tm, const int
       if (q16 == 0) cs_row[grp * cs_grp_stride + wc * 64 + (cbt >> 1) * 32 + (cbt & 1) * 16 + l15] = v;
     }
   }
-  if (TN && cs_on && S16) {    // the four 16-lane groups hold the four k-quarters of column l15
+  if (WIDEB && cs_on) {           // the same, for the 64 columns of each B half that the strip (wc & 1) holds
+    if ((wc >> 1) == 0) {
+#pragma unroll
+      for (int hc = 0; hc < 8; ++hc) {
+        float v = csw[hc] + __shfl_xor(csw[hc], 16, 64);
+        v += __shfl_xor(v, 32, 64);
+        if (q16 == 0) cs_row[grp * cs_grp_stride + (hc >> 2) * 128 + (wc & 1) * 64 + (hc & 3) * 16 + l15] = v;
+      }
+    }
+  }
+  if (TN && !WIDEB && cs_on && S16) {    // the four 16-lane groups hold the four k-quarters of column l15
 #pragma unroll
     for (int cbt = 0; cbt < 4; ++cbt) {
       float v = cs16[cbt] + __shfl_xor(cs16[cbt], 16, 64);
@@ -1371,6 +1438,35 @@ __device__ __forceinline__ void run_tile(const BArgs &g, const int tm, const int
       n += __shfl_xor(n, 32, 64);
       const int i = row_base + rbb * 16;
       if (q16 == 0 && i < g.M && n) atomicAdd(g.rank_cnt + i, n);
+    }
+    return;
+  }
+
+  // ---- WIDEB epilogue: the wave's 64 x 128 tile as four 32 x 64 strips (row half x column half) through its 16 KiB of LDS: a
+  // store instruction writes four rows x 256 B ----
+  if constexpr (WIDEB) {
+    float *const sW = reinterpret_cast<float *>(smem + wave * 16384);
+    const int c4w = lane & 15;
+    float *const cw = static_cast<float *>(c_base) + (int64_t)(c_row0 + (grp * 2 + (wc >> 1)) * 32 + (lane >> 4)) * c_ld + c_col0 +
+                      (wc & 1) * 64 + c4w * 4;
+#pragma unroll
+    for (int rt = 0; rt < 4; ++rt) {                        // rt = 2 HALF + hh
+      float *strip = sW + (rt & 1) * 2048;
+#pragma unroll
+      for (int rbb = 0; rbb < 2; ++rbb)
+#pragma unroll
+        for (int cb = 0; cb < 4; ++cb)
+#pragma unroll
+          for (int r = 0; r < 4; ++r)
+            strip[(rbb * 16 + q16 * 4 + r) * 64 + ((cb * 16 + l15) ^ ((q16 & 1) << 4))] = acc16[2 * rt + rbb][cb][r];
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+#pragma unroll
+      for (int p = 0; p < 8; ++p) {
+        const int lr = p * 4 + (lane >> 4);
+        const f32x4 v = *reinterpret_cast<const f32x4 *>(strip + lr * 64 + ((c4w * 4) ^ (((lr >> 2) & 1) << 4)));
+        *reinterpret_cast<f32x4 *>(cw + (int64_t)((rt >> 1) * 128 + p * 4) * c_ld + (rt & 1) * 128) = v;
+      }
     }
     return;
   }
@@ -1696,7 +1792,7 @@ __device__ __forceinline__ void run_tile(const BArgs &g, const int tm, const int
 }
 
 // one block of a launch: block index `bid` of this launch -> (half) tile -> run_tile
-template <bool TN, int EPI, bool S16, bool X3, bool F6, bool NTCS, bool R6, bool NARROW, bool KI = false>
+template <bool TN, int EPI, bool S16, bool X3, bool F6, bool NTCS, bool R6, bool NARROW, bool KI = false, bool WIDEB = false>
 __device__ __forceinline__ void block_of_launch(const BArgs &g, int bid, unsigned char *smem) {
   int tm, tn;
   // the block -> tile map of the WHOLE tile grid, of which this launch may cover the first blocks only (grid_tiles) or,
@@ -1726,18 +1822,18 @@ __device__ __forceinline__ void block_of_launch(const BArgs &g, int bid, unsigne
   const int n_ktiles = k_end > k_begin ? (k_end - k_begin) / kTileK : 0;   // even (host)
   void *c_base = EPI == BE_F32 ? static_cast<void *>(static_cast<float *>(g.C) + (int64_t)split * g.slab_stride) : g.C;
   float *cs_row = ((TN || NTCS) && g.colsum_partial) ? g.colsum_partial + (int64_t)((split * g.tiles_m + tm) * 2) * g.N + n0 : nullptr;
-  run_tile<TN, EPI, S16, X3, F6, NTCS, R6, NARROW, KI>(g, tm, m0, n0, k_begin, n_ktiles, c_base, g.ldc, m0, n0, cs_row, g.N, smem);
+  run_tile<TN, EPI, S16, X3, F6, NTCS, R6, NARROW, KI, WIDEB>(g, tm, m0, n0, k_begin, n_ktiles, c_base, g.ldc, m0, n0, cs_row, g.N, smem);
 }
 
 template <bool TN, int EPI, bool S16, bool X3 = false, bool F6 = false, bool NTCS = false, bool R6 = false, bool NARROW = false,
-          bool KI = false>
+          bool KI = false, bool WIDEB = false>
 __global__ void __launch_bounds__(kT, 1) k_gemm_bf16_256(BArgs g) {
   extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];
   // (round 5: ONE resident block per CU walking the launch's tiles -- no block dispatch between a CU's tiles -- was built
   // and measured: miner 0.437-0.442 against 0.429-0.430 ms, headline step 2.629-2.633 against 2.621-2.623 ms,
   // profiles/r05_persistent_tiles_ab.txt; the loop around run_tile also cost the k-strided kernel its last free VGPRs --
   // 72 B of scratch.  Removed.)
-  block_of_launch<TN, EPI, S16, X3, F6, NTCS, R6, NARROW, KI>(g, blockIdx.x, smem);
+  block_of_launch<TN, EPI, S16, X3, F6, NTCS, R6, NARROW, KI, WIDEB>(g, blockIdx.x, smem);
 }
 
 // full tiles and the last round's half tiles in ONE launch (blocks [0, narrow_first): full tiles; the rest: half tiles):
@@ -2044,6 +2140,20 @@ int launch_gemm_x3_tnk(const BArgs &g, int splits, hipStream_t s) {
   hipLaunchKernelGGL((k_gemm_bf16_256<true, BE_F32, true, true, false, false, true, false, true>), dim3(g.tiles_m * g.tiles_n, splits),
                      dim3(kT), SMEM_R6, s, g);
   return check_launch("gemm_bf16x3_tnk");
+}
+
+// the k-strided product with ONLY B k8-interleaved, B as the wide operand of a wave's tile (64 x 128: run_tile's WIDEB)
+int launch_gemm_x3_tnkb(const BArgs &g, int splits, hipStream_t s) {
+  static bool configured = false;
+  if (!configured) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_gemm_bf16_256<true, BE_F32, true, true, false, false, true, false, false, true>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_R6);
+    if (e != hipSuccess) return fail(CDML_E_HIP, "gemm_bf16x3_tn_kb: cannot reserve %d B of LDS: %s", SMEM_R6, hipGetErrorString(e));
+    configured = true;
+  }
+  hipLaunchKernelGGL((k_gemm_bf16_256<true, BE_F32, true, true, false, false, true, false, false, true>), dim3(g.tiles_m * g.tiles_n, splits),
+                     dim3(kT), SMEM_R6, s, g);
+  return check_launch("gemm_bf16x3_tn_kb");
 }
 
 int launch_gemm_x3_mine(const BArgs &g, hipStream_t s) {

@@ -16,6 +16,7 @@
 // (BArgs::x3_*); epilogues 6 / 7 write their result as planes again, so the chain FC1 -> FC2 / dH1 -> dW1 never
 // holds an activation in fp32.  Replaces the same reference lines as gemm_f32.hip (models.py:59-60, train.py:141).
 #include "gemm_bf16.h"
+#include "../../include/cdml_x3_wide.h"
 #include <stdlib.h>
 
 namespace cdml {
@@ -817,6 +818,56 @@ extern "C" int cdml_gemm_bf16x3_tnk(const uint16_t *A, int ma, int a_col0, const
     hipLaunchKernelGGL(k_x3_sum_slabs, dim3(sb + cb), dim3(kThreads), 0, s, static_cast<const float *>(workspace), g.slab_stride,
                        splits, M, N, static_cast<const float *>(nullptr), 0.f, C, ldc, sb, g.colsum_partial, (int)cs_rows, colsum, 1.0f);
     rc = check_launch("gemm_bf16x3_tnk combine");
+  }
+  return rc;
+}
+
+// C[M][N] (fp32) = sum_k A[k][M] B[k][N] like cdml_gemm_bf16x3_tn with ONLY B k8-interleaved: A = row-major planes [K][lda]
+// (plane_a apart; a column window is a moved base), B = bf16 [3][K / 8][nb][8], columns [b_col0, b_col0 + N).  The kernel's
+// waves are tiled so that B supplies two thirds of the fragment reads (gemm_bf16_256.hip, WB); colsum[n] = sum_k B[k][n].
+// Six products; M, N % 256 == 0, K % 128 == 0; the split rule, slab combine, colsum partition and workspace of the
+// row-major form (cdml_gemm_bf16x3_workspace(1, M, N, K, 6)); C and colsum bit-identical to it.
+extern "C" int cdml_gemm_bf16x3_tn_kb(const uint16_t *A, int64_t lda, int64_t plane_a, const uint16_t *B, int nb, int b_col0, int M,
+                                      int N, int K, float *C, int64_t ldc, float *colsum, void *workspace, size_t workspace_bytes,
+                                      cdml_stream_t stream) {
+  CDML_REQUIRE(A && B && C && M > 0 && N > 0 && K > 0, CDML_E_BADARG, "gemm_bf16x3_tn_kb: bad argument");
+  CDML_REQUIRE(M % 256 == 0 && N % 256 == 0 && K % 128 == 0, CDML_E_UNSUPPORTED,
+               "gemm_bf16x3_tn_kb: M, N must be multiples of 256 and K of 128, got M=%d N=%d K=%d", M, N, K);
+  CDML_REQUIRE(aligned16(A) && aligned16(B) && aligned16(C) && !(lda & 7) && !(plane_a & 7) && !(ldc & 3) && plane_a >= M &&
+                   lda >= 2 * plane_a + M && ldc >= N && b_col0 >= 0 && b_col0 + N <= nb && !(nb & 7),
+               CDML_E_ALIGN, "gemm_bf16x3_tn_kb: 16-B aligned bases, strides multiples of 8, lda >= 2 plane + columns, B's window inside it");
+  CDML_REQUIRE((int64_t)K * lda * 2 < ((int64_t)1 << 31) && (int64_t)3 * (K / 8) * nb * 16 < ((int64_t)1 << 31), CDML_E_UNSUPPORTED,
+               "gemm_bf16x3_tn_kb: an operand exceeds the 2 GiB buffer-descriptor range");
+  BArgs g{};
+  g.A = reinterpret_cast<const bf16 *>(A); g.lda = lda;
+  g.B = reinterpret_cast<const bf16 *>(B) + (int64_t)b_col0 * 8; g.ldb = (int64_t)nb * 8;
+  g.M = M; g.N = N;
+  g.x3_tpp = K / 64; g.x3_plane_a = plane_a; g.x3_plane_b = (int64_t)(K / 8) * nb * 8;
+  g.x3_products = 6;
+  const int ktiles = 6 * g.x3_tpp;
+  g.K = ktiles * 64;
+  g.tiles_m = M / 256; g.tiles_n = N / 256;
+  int splits = gemm_bf16_256_splits(M, N, g.K), per = 0;
+  x3_split_geometry(ktiles, splits, 6, per, splits);
+  const bool slabs = splits > 1;
+  const size_t slab_bytes = slabs ? (size_t)splits * M * N * sizeof(float) : 0;
+  const size_t cs_rows = (size_t)splits * g.tiles_m * 2;
+  const size_t need = slab_bytes + (colsum ? cs_rows * N * sizeof(float) : 0);
+  CDML_REQUIRE(need == 0 || (workspace && workspace_bytes >= need && aligned16(workspace)), CDML_E_BADARG,
+               "gemm_bf16x3_tn_kb: workspace of %zu bytes required (cdml_gemm_bf16x3_workspace)", need);
+  hipStream_t s = (hipStream_t)stream;
+  g.k_per_split = per * 64;
+  g.slab_stride = (int64_t)M * N;
+  g.C = slabs ? workspace : static_cast<void *>(C);
+  g.ldc = slabs ? N : ldc;
+  g.colsum_partial = colsum ? reinterpret_cast<float *>(static_cast<char *>(workspace) + slab_bytes) : nullptr;
+  int rc = launch_gemm_x3_tnkb(g, splits, s);
+  if (rc) return rc;
+  if (slabs || colsum) {
+    const int sb = slabs ? grid1d((int64_t)M * N / 4) : 0, cb = colsum ? (N + 15) / 16 : 0;
+    hipLaunchKernelGGL(k_x3_sum_slabs, dim3(sb + cb), dim3(kThreads), 0, s, static_cast<const float *>(workspace), g.slab_stride,
+                       splits, M, N, static_cast<const float *>(nullptr), 0.f, C, ldc, sb, g.colsum_partial, (int)cs_rows, colsum, 1.0f);
+    rc = check_launch("gemm_bf16x3_tn_kb combine");
   }
   return rc;
 }

@@ -144,7 +144,7 @@ class EngineWorkspace:
     EXCHANGE_PLANES = False         # the row exchange of a sharded catalogue writes x_hat in the gather's plane form
     # state that the kernel sequences and the callers read whatever the engine
     h1_bits = xk = W1n = scales = None
-    kint = tail_done = dz2_planes_done = False
+    kint = wide_dz1 = tail_done = dz2_planes_done = False
 
     def tail_operands(self, indexed=False):
         """(keywords, planes_done): what ops.vnet_tail (``indexed``: ops.triplet_hinge_indexed) writes besides fp32 dz2 --
@@ -284,7 +284,7 @@ class Engine:
             module.refresh_weights, module.tower_forward, module.tower_backward)
 
     def workspace(self, layout, n_rows, device, backward=True, **options):
-        """``options``: planes_in, kint, fc2_single_pass -- an engine's constructor ignores the ones it does not have."""
+        """``options``: planes_in, kint, wide_dz1, fc2_single_pass -- an engine's constructor ignores the ones it does not have."""
         return self.Workspace(layout, n_rows, device, backward=backward, **dict(self.ws_args, **options))
 
 

@@ -30,7 +30,7 @@ class TowerWorkspaceX3(EngineWorkspace):
     ROWS, WIDTHS, MAX_ROWS, INFERENCE, EXCHANGE_PLANES = 128, 256, 65536, "f32x3", True
 
     def __init__(self, layout, n_rows, device, products=6, planes_in=True, backward=True, transposed=None,
-                 fc2_single_pass=False, kint=None):
+                 fc2_single_pass=False, kint=None, wide_dz1=None):
         """planes_in: ``x_hat`` IS the plane buffer (the fused sampler + gather writes planes); False: ``x_hat`` is
         fp32 (rows arriving through the exchange) and the forward pass splits it.
         fc2_single_pass: the narrow second layer normally splits its contraction into slabs whose partition depends on
@@ -49,7 +49,13 @@ class TowerWorkspaceX3(EngineWorkspace):
         (0.59 -> 0.655 of the peak at 16 384 rows); IN THE STEP 4 % (999 -> 959 us: the chip answers the higher matrix-pipe
         duty with a lower clock), the gather's second copy costs + 48 us a step (151 MB more to write and a launch per step
         instead of per two), the epilogue's second LDS pass + 5 us: the step comes out EVEN (2.7309 against 2.7321 ms).  Kept,
-        with its tests, as the measured alternative; off by default."""
+        with its tests, as the measured alternative; off by default.
+        wide_dz1 (training, six products; None = on wherever it applies): dz1 ALONE is held k8-interleaved (``dz1k``, written
+        by the data gradient's epilogue 12 as with kint) and dW1 runs on cdml_gemm_bf16x3_tn_kb, whose waves are tiled 64 x 128
+        instead of 128 x 64: the interleaved operand then supplies two thirds of the fragment reads (one 16-B LDS read each),
+        and x_hat stays exactly what the gather writes -- no second copy.  Same images, DMA schedule, product order and K
+        partition: gW1 and gb1 have the row-major path's bits (tests/test_gpu_x3_wide_dz1.py).  Needs the sign bitmask,
+        R % 8 == 0 and the row-major layout; False for a trainable catalogue (its row gradient reads row-major dz1)."""
         L, R = layout, int(n_rows)
         if R % 128:
             raise ValueError("precision 'f32x3' needs a row count that is a multiple of 128 (got %d)" % R)
@@ -78,6 +84,7 @@ class TowerWorkspaceX3(EngineWorkspace):
         if kint is None:
             kint = os.environ.get("CDML_X3_KI", "0") == "1" and planes_in
         self.kint = bool(kint) and maskbits and products == 6 and R % 8 == 0
+        self.wide_dz1 = (wide_dz1 is None or bool(wide_dz1)) and maskbits and products == 6 and R % 8 == 0 and not self.kint
         self.xk = None                                       # [3 * R * Fp] bf16, k8-interleaved x_hat (the gather's second output)
         self.x3 = bf(R, 3 * L.Fp)
         self.x_hat = self.x3 if planes_in else f32(R, L.Fp)    # the gather's output (l2-normalised rows)
@@ -103,8 +110,9 @@ class TowerWorkspaceX3(EngineWorkspace):
         if maskbits:
             self.h1_bits = torch.zeros((R, L.Hp // 8), dtype=torch.uint8, device=device)
         if backward:                                       # (catalogue inference: forward buffers only)
-            self.dz1 = bf(L.Hp, 3 * R) if self.transposed else (None if self.kint else bf(R, 3 * L.Hp))
-            self.dz1k = torch.zeros(3 * R * L.Hp, dtype=torch.bfloat16, device=device) if self.kint else None
+            ki = self.kint or self.wide_dz1
+            self.dz1 = bf(L.Hp, 3 * R) if self.transposed else (None if ki else bf(R, 3 * L.Hp))
+            self.dz1k = torch.zeros(3 * R * L.Hp, dtype=torch.bfloat16, device=device) if ki else None
             self.de, self.dz2 = f32(R, L.Dp), f32(R, L.Dp)
             self.dz2_3 = bf(R, 3 * L.Dp)
             nb = max(nb, ops.gemm_bf16x3_workspace(True, L.Fp, L.Hp, R, q), ops.gemm_bf16x3_workspace(True, L.Hp, L.Dp, R, q))
@@ -135,7 +143,7 @@ class TowerWorkspaceX3(EngineWorkspace):
         # that the Adam launch writes with the update, as it does W2's two)
         L = self.layout
         if self.transposed or self.dz1 is None:
-            raise ValueError("train_table needs the row-major activation layout of the f32x3 path")
+            raise ValueError("train_table needs the row-major activation layout of the f32x3 path and dz1 in it (kint=False, wide_dz1=False)")
         self.W1n = torch.zeros((L.Fp, 3 * L.Hp), dtype=torch.bfloat16, device=self.z.device)
         refresh_weights(p, self)
 
@@ -247,7 +255,7 @@ def tower_backward(p, ws, after_w1=None, w1_chunks=1, after_w1_chunk=None):
         if ws.kint and not kint:
             raise RuntimeError("this workspace holds dz1 k8-interleaved only: it needs the gather's interleaved x_hat (ws.xk) and "
                                "the sign bitmask of h1 (CDML_X3_MASKBITS); build it with kint=False otherwise")
-        if kint:      # dz1 written k8-interleaved by the epilogue: the only form the first layer's weight gradient reads
+        if kint or ws.wide_dz1:      # dz1 written k8-interleaved by the epilogue: the only form the first layer's weight gradient reads
             ops.gemm_bf16x3_nt(ops.BE_MASKBITS_X3_KI, ws.dz2_3, L.Dp, ws.W2, L.Dp, ws.dz1k, R, L.Hp, L.Dp, products=q,
                                plane_c=R * L.Hp, aux=ws.h1_bits, ldc=L.Hp)
         elif ws.h1_bits is not None:
@@ -263,6 +271,9 @@ def tower_backward(p, ws, after_w1=None, w1_chunks=1, after_w1_chunk=None):
                                workspace=ws.gemm_ws, colsum=db)
         elif ws.kint:      # k8-interleaved operands: one 16-B LDS read per fragment (columns lo .. hi of x_hat)
             ops.gemm_bf16x3_tnk(ws.xk, L.Fp, lo, ws.dz1k, L.Hp, 0, p.gW1[lo:hi], hi - lo, L.Hp, R, workspace=ws.gemm_ws, colsum=db)
+        elif ws.wide_dz1:      # dz1 (interleaved) as the wide operand of a wave's tile, x_hat as the gather wrote it
+            ops.gemm_bf16x3_tn(ws.x3[:, lo:], L.Fp, ws.dz1k, L.Hp, p.gW1[lo:hi], hi - lo, L.Hp, R, products=q,
+                               workspace=ws.gemm_ws, colsum=db, b_kint=(L.Hp, 0))
         else:      # columns lo .. hi of every plane of x_hat: the same plane stride, the base moved by lo
             ops.gemm_bf16x3_tn(ws.x3[:, lo:], L.Fp, ws.dz1, L.Hp, p.gW1[lo:hi], hi - lo, L.Hp, R, products=q,
                                workspace=ws.gemm_ws, colsum=db)

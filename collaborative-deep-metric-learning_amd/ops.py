@@ -1778,10 +1778,26 @@ def gemm_bf16x3_tnk(A, ma, a_col0, B, nb, b_col0, out, M, N, K, workspace=None, 
     return out
 
 
+def gemm_bf16x3_tn_kb(A, plane_a, B, nb, b_col0, out, M, N, K, workspace=None, colsum=None):
+    """out[M][N] f32 = sum_k A[k][m] B[k][b_col0 + n]: A row-major planes [K][hi | mid | lo], B k8-interleaved [3, K / 8, nb, 8]
+    (six products; out and colsum bit-identical to gemm_bf16x3_tn)."""
+    ap, ald = _mat16(A)
+    cp, cld = _mat(out)
+    ws, wb = (C.c_void_p(0), 0) if workspace is None else (C.c_void_p(workspace.data_ptr()), workspace.numel() * workspace.element_size())
+    call("cdml_gemm_bf16x3_tn_kb", ap, ald, plane_a, C.c_void_p(B.data_ptr()), nb, b_col0, M, N, K, cp, cld,
+         _p(colsum, torch.float32), ws, wb, _stream())
+    return out
+
+
 def gemm_bf16x3_tn(A, plane_a, B, plane_b, C, M, N, K, products=6, workspace=None, colsum=None, bias=None,
-                   alpha=LRELU_ALPHA):
+                   alpha=LRELU_ALPHA, b_kint=None):
     """C[M][N] f32 = sum_k A[k][M] B[k][N] for fp32 operands given as bf16 planes [K][hi | mid | lo]
-    (bias given: C = lrelu(. + bias))."""
+    (bias given: C = lrelu(. + bias)).  b_kint = (nb, b_col0): B is the k8-interleaved buffer of gemm_bf16x3_tn_kb instead
+    (plane_b unused; six products, no bias)."""
+    if b_kint is not None:
+        if products != 6 or bias is not None:
+            raise ValueError("gemm_bf16x3_tn: the interleaved B operand takes six products and no bias")
+        return gemm_bf16x3_tn_kb(A, plane_a, B, b_kint[0], b_kint[1], C, M, N, K, workspace=workspace, colsum=colsum)
     ap, ald = _mat16(A)
     bp, bld = _mat16(B)
     cp, cld = _mat(C)

@@ -326,7 +326,8 @@ class TrainStep:
         # planes_in: the fused sampler + gather writes planes (the plane buffer IS x_hat), and so does the row exchange's
         # un-permute pass on f32x3 (on f16x2 its rows arrive in fp32); kint: the gather's interleaved copy (one GPU)
         self.ws = E.workspace(self.layout, self.R, self.device, planes_in=not sharded or E.Workspace.EXCHANGE_PLANES,
-                              kint=None if (not sharded and not train_table) else False)
+                              kint=None if (not sharded and not train_table) else False,
+                              wide_dz1=None if not train_table else False)
         if not self.ws.scales_due():                     # (due: the first step's check splits the weights at the scales it finds)
             E.refresh_weights(self.params, self.ws)
 
