@@ -36,8 +36,7 @@
 //   phase B(T) waits vmcnt(6): B-h0, B-h1, A-h0 of T+1 have landed, read in phase A(T+1).
 //   A wave waits for its OWN pieces before a barrier; the read of the image comes two barriers
 //   later, after every wave of both groups has passed its wait.
-#include "gemm_bf16.h"
-#include <type_traits>
+#include "gemm_tile.h"   // the tile's types and constants, the LDS-DMA and packing helpers, unroll, the Variant traits
 #include <stdlib.h>
 
 #ifndef CDML_BF16_MFMA_DEFAULT
@@ -46,94 +45,6 @@
 
 namespace cdml {
 namespace {
-
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-using bf16x4 = __attribute__((ext_vector_type(4))) __bf16;
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-using f32x2 = __attribute__((ext_vector_type(2))) float;
-using i32x4 = __attribute__((ext_vector_type(4))) int;
-
-constexpr int kT = 512;
-constexpr int kTileM = 256, kTileN = 256, kTileK = 64;
-constexpr int IMG = 16384;       // one half image: 128 rows x 128 B
-constexpr int BUF = 4 * IMG;     // one K-tile: A-h0, A-h1, B-h0, B-h1
-// LDS by OPERAND: [A: buf0 h0 | buf0 h1 | buf1 h0 | buf1 h1][B: likewise] (round 4; rounds 1-3 laid it out by buffer).  Every
-// fragment read of an operand is then within 64 KiB of ONE lane base, i.e. inside the 16-bit offset immediate of a ds_read:
-// the second buffer costs no v_add per read (k-strided form: 24 fewer VALU per K-tile, -2 % measured) and no second set
-// of base registers (k-contiguous forms: 229-240 -> 205-226 VGPRs).
-constexpr int SMEM = 2 * BUF;    // 128 KiB
-constexpr int SMEM_R6 = 10 * IMG;  // 160 KiB (the whole LDS of a CU): the resident-plane walk's 3 A slots + 2 B slots
-
-__device__ __forceinline__ uint32_t lds_off(const void *p) {
-  return (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const void *)p;
-}
-// 64 lanes x 16 B through a buffer descriptor into LDS at m0 + lane*16; lanes whose
-// offset is outside the descriptor's range deliver zeros.  Inline asm: invisible to
-// hipcc's wait-count pass, the kernel counts these loads itself.
-__device__ __forceinline__ void dma(i32x4 srd, uint32_t voff, uint32_t lds_base) {
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds"
-               :: "s"(lds_base), "v"(voff), "s"(srd) : "memory", "m0");
-}
-// the same with the wave-uniform part of the source offset in an SGPR (the instruction's soffset field): the per-lane
-// offset register is then loop-invariant -- no v_add per piece, and nothing for the compiler to hoist into extra VGPRs
-// when a loop is unrolled over many (plane, half, K-tile) combinations
-__device__ __forceinline__ void dma_s(i32x4 srd, uint32_t voff, uint32_t soff, uint32_t lds_base) {
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds"
-               :: "s"(lds_base), "v"(voff), "s"(srd), "s"(soff) : "memory", "m0");
-}
-using u32x4 = __attribute__((ext_vector_type(4))) uint32_t;
-using bf16x2 = __attribute__((ext_vector_type(2))) __bf16;
-// CDML_F16X2 (gemm_f16x2_256.hip compiles THIS file with it): the 16-bit operands are fp16 -- v_mfma_f32_16x16x32_f16 -- and
-// the plane-output epilogues write TWO fp16 planes hi | lo of (value * BArgs::c_scale) instead of three bf16 planes.  The
-// tile, images, DMA schedule, fragment layouts and phases are those of the bf16 form (both types are 16 bits wide; a
-// fragment is eight of them in four registers either way).  Only the split-fp32 (X3) launchers are exported from that build.
-#ifdef CDML_F16X2
-constexpr bool kF16 = true;
-using half8 = __attribute__((ext_vector_type(8))) _Float16;
-using half2v = __attribute__((ext_vector_type(2))) _Float16;
-#define CDML_MFMA16(a, b, c) \
-  __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, a), __builtin_bit_cast(half8, b), c, 0, 0, 0)
-// two fp32 -> one dword of two fp16 (round to nearest even; element 0 in the low half), and the halves back as fp32
-__device__ __forceinline__ uint32_t pack2(float a, float b) {
-  uint32_t w = __builtin_bit_cast(uint32_t, half2v{(_Float16)a, (_Float16)b});
-  asm("" : "+v"(w));
-  return w;
-}
-__device__ __forceinline__ float lo_of(uint32_t w) { return (float)__builtin_bit_cast(half2v, w)[0]; }
-__device__ __forceinline__ float hi_of(uint32_t w) { return (float)__builtin_bit_cast(half2v, w)[1]; }
-#else
-constexpr bool kF16 = false;
-#define CDML_MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0)
-// two fp32 -> one dword of two bf16 (round to nearest even; element 0 in the low half), and the halves back as fp32
-// (the dword is made opaque: hipcc otherwise sees through `pack << 16` and converts the low element a second time on its own)
-__device__ __forceinline__ uint32_t pack2(float a, float b) {
-  uint32_t w = __builtin_bit_cast(uint32_t, bf16x2{(__bf16)a, (__bf16)b});
-  asm("" : "+v"(w));
-  return w;
-}
-__device__ __forceinline__ float lo_of(uint32_t w) { return __builtin_bit_cast(float, w << 16); }
-__device__ __forceinline__ float hi_of(uint32_t w) { return __builtin_bit_cast(float, w & 0xffff0000u); }
-#endif
-constexpr int kPlanesOut = kF16 ? 2 : 3;             // planes a plane-output epilogue writes
-__device__ __forceinline__ i32x4 make_srd(const void *base, int64_t bytes) {
-  const uint64_t a = (uint64_t)(uintptr_t)base;
-  i32x4 r;
-  r.x = __builtin_amdgcn_readfirstlane((int)(uint32_t)a);
-  r.y = __builtin_amdgcn_readfirstlane((int)(uint32_t)((a >> 32) & 0xffff));  // stride 0
-  r.z = __builtin_amdgcn_readfirstlane((int)(bytes > 0 ? bytes : 0));
-  r.w = 0x00020000;
-  return r;
-}
-
-// Every half image is waited for one phase before the phase that reads it, which
-// always leaves the five newest images (10 wave-instructions) in flight.
-#define CDML_BARRIER()                         \
-  do {                                         \
-    __builtin_amdgcn_sched_barrier(0);         \
-    asm volatile("s_barrier" ::: "memory");    \
-    __builtin_amdgcn_sched_barrier(0);         \
-  } while (0)
 
 // TN = false: A[M][K], B[N][K] (k-contiguous rows; fragments by ds_read_b128).
 // TN = true : A[K][M], B[K][N] (the weight gradients x^T.dy: the contraction runs over
@@ -164,23 +75,15 @@ __device__ __forceinline__ i32x4 make_srd(const void *base, int64_t bytes) {
 // consecutive k of one column) is ONE aligned 16-B LDS read instead of two transposed 8-B reads, and a half image
 // [8 k-groups][128 columns][16 B] is filled by 1-KiB pieces that are contiguous in memory.  Same images, slots, DMA schedule,
 // accumulation order and results as the k-strided form (test_gemm_x3_tnk_equals_tn: bit for bit).
-template <bool TN, int EPI, bool S16, bool X3 = false, bool F6 = false, bool NTCS = false, bool R6 = false, bool NARROW = false,
-          bool KI = false, bool WIDEB = false>
+template <class V>
 __device__ __forceinline__ void run_tile(const BArgs &g, const int tm, const int m0, const int n0, const int k_begin,
                                          const int n_ktiles, void *c_base, const int64_t c_ld, const int c_row0,
                                          const int c_col0, float *cs_row, const int64_t cs_grp_stride,
                                          unsigned char *smem) {
-  static_assert(!TN || EPI == BE_F32, "the k-strided form only serves the weight gradients");
-  static_assert(!NARROW || (X3 && S16 && R6 && !TN && (EPI == BE_BIAS_LRELU_X3 || EPI == BE_MASK_X3 || EPI == BE_ROWBIAS_LRELU_X3 || EPI == BE_F32)),
-                "the 128 x 256 half tile exists for the plane-output products of the resident-plane walk and for the fp32 slabs of the narrow layer");
-  static_assert(X3 || (EPI != BE_BIAS_LRELU_X3 && EPI != BE_MASK_X3 && EPI != BE_ROWBIAS_LRELU_X3),
-                "plane outputs belong to the split-fp32 form");
-  static_assert((EPI != BE_MINE_X3 && EPI != BE_KNN_X3 && EPI != BE_RANK_X3) || (X3 && S16 && R6 && !TN && !NARROW),
-                "the mining / kNN-filter / rank-count epilogues ride on the resident-plane walk");
-  static_assert(!KI || (TN && X3 && S16 && R6), "the k8-interleaved operands exist for the k-strided resident-plane walk");
-  static_assert(!WIDEB || (TN && X3 && S16 && R6 && !KI && !kF16 && !NARROW && EPI == BE_F32),
-                "the wide column operand exists for the bf16 k-strided resident-plane walk");
-  constexpr bool KIA = KI, KIB = KI || WIDEB;                  // which operand is stored k8-interleaved
+  constexpr bool TN = V::TN, S16 = V::S16, X3 = V::X3, F6 = V::F6, NTCS = V::NTCS, NARROW = V::NARROW, WIDEB = V::WIDEB;
+  constexpr int EPI = V::EPI;
+  constexpr bool KIA = V::KIA, KIB = V::KIB, kSwap = V::kSwap, kR6 = V::kR6, kFast6 = V::kFast6;
+  constexpr bool kRowBias = V::kRowBias, kBiasEpi = V::kBiasEpi, kMaskEpi = V::kMaskEpi, kPlanes = V::kPlanes;
   const int t = threadIdx.x;
   const int lane = t & 63;
   const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
@@ -195,8 +98,8 @@ __device__ __forceinline__ void run_tile(const BArgs &g, const int tm, const int
   // (The plane-output epilogues were built in this layout too -- one 8-B store per plane straight from the accumulators, no
   // strip, no barrier -- and measured SLOWER: FC1 + 4 %, the data gradient + 30 %, profiles/r06_swapped_plane_epilogue_ab.txt.
   // A store instruction then writes 16 rows x 32 B and a 128-B line is assembled from four of them; the LDS transpose of
-  // tail16 below is what makes every store a whole line.  The swapped layout stays where nothing of the tile is stored.)
-  constexpr bool kSwap = EPI == BE_MINE_X3 || EPI == BE_KNN_X3 || EPI == BE_RANK_X3;
+  // tail16 below is what makes every store a whole line.  The swapped layout stays where nothing of the tile is stored:
+  // Variant::kSwap.)
 
   const int k_rows = X3 ? g.x3_tpp * kTileK : g.K;              // k-strided form: rows of the operands in memory
   const i32x4 srd_a = make_srd(g.A, KIA ? 3 * g.x3_plane_a * 2 : (int64_t)(TN ? k_rows : g.M) * g.lda * 2);
@@ -446,27 +349,103 @@ __device__ __forceinline__ void run_tile(const BArgs &g, const int tm, const int
   // so the LDS reads are waited for BEFORE the barrier that follows (it would otherwise sink
   // the waits into the MFMA part, and the images are refilled one barrier after their reads).
   auto pin_a = [&]() {
-    asm volatile("" : "+v"(fa[0][0]), "+v"(fa[0][1]), "+v"(fa[0][2]), "+v"(fa[0][3]),
-                      "+v"(fa[1][0]), "+v"(fa[1][1]), "+v"(fa[1][2]), "+v"(fa[1][3]));
+    if constexpr (WIDEB)
+      asm volatile("" : "+v"(fa[0][0]), "+v"(fa[0][1]), "+v"(fa[1][0]), "+v"(fa[1][1]));
+    else
+      asm volatile("" : "+v"(fa[0][0]), "+v"(fa[0][1]), "+v"(fa[0][2]), "+v"(fa[0][3]),
+                        "+v"(fa[1][0]), "+v"(fa[1][1]), "+v"(fa[1][2]), "+v"(fa[1][3]));
   };
   auto pin_b = [&]() {
-    asm volatile("" : "+v"(fb0[0]), "+v"(fb0[1]), "+v"(fb0[2]), "+v"(fb0[3]),
-                      "+v"(fb1[0]), "+v"(fb1[1]), "+v"(fb1[2]), "+v"(fb1[3]));
+    if constexpr (WIDEB)
+      asm volatile("" : "+v"(fbx[0]), "+v"(fbx[1]), "+v"(fbx[2]), "+v"(fbx[3]), "+v"(fbx[4]), "+v"(fbx[5]), "+v"(fbx[6]), "+v"(fbx[7]),
+                        "+v"(fbx[8]), "+v"(fbx[9]), "+v"(fbx[10]), "+v"(fbx[11]), "+v"(fbx[12]), "+v"(fbx[13]), "+v"(fbx[14]), "+v"(fbx[15]));
+    else
+      asm volatile("" : "+v"(fb0[0]), "+v"(fb0[1]), "+v"(fb0[2]), "+v"(fb0[3]),
+                        "+v"(fb1[0]), "+v"(fb1[1]), "+v"(fb1[2]), "+v"(fb1[3]));
   };
-  // 16x16x32 form of the K-tile: fb0[2*cb + ks2] = column block cb (0, 1) of B-h0, fb1 likewise of B-h1,
-  // fa[ks2][rb] = row block rb (0..3) of the phase's A half image
-  auto do_tile2_s16 = [&](const int buf, const int tile) {
+  // ---- the parts a phase of the 16x16x32 form is made of, ONE copy each: the five phase bodies below (general loop, six-step
+  // period, three-product / six-product / half-tile resident walks) differ in where they read from, what they issue and what
+  // they wait for, not in these.  fb0[2*cb + ks2] = column block cb (0, 1) of B-h0, fb1 likewise of B-h1, fa[ks2][rb] = row
+  // block rb (0..3) of the phase's A half image (WIDEB: fbx / rb 0, 1 -- the layout described at their declaration)
+  // the B fragments of both halves, through rd(hh, cb, ks2)
+  auto load_b16 = [&](auto rd) {
+    if constexpr (WIDEB) {
 #pragma unroll
-    for (int cb = 0; cb < 2; ++cb)
+      for (int hh = 0; hh < 2; ++hh)
 #pragma unroll
-      for (int ks2 = 0; ks2 < 2; ++ks2) {
-        fb0[2 * cb + ks2] = read_b16(buf, 0, cb, ks2);
-        fb1[2 * cb + ks2] = read_b16(buf, 1, cb, ks2);
-      }
+        for (int cb = 0; cb < 4; ++cb)
+#pragma unroll
+          for (int ks2 = 0; ks2 < 2; ++ks2) fbx[hh * 8 + cb * 2 + ks2] = rd(hh, cb, ks2);
+    } else {
+#pragma unroll
+      for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+        for (int ks2 = 0; ks2 < 2; ++ks2) {
+          fb0[2 * cb + ks2] = rd(0, cb, ks2);
+          fb1[2 * cb + ks2] = rd(1, cb, ks2);
+        }
+    }
+  };
+  // the A fragments of one half image, through rd(rb, ks2)
+  auto load_a16 = [&](auto rd) {
 #pragma unroll
     for (int ks2 = 0; ks2 < 2; ++ks2)
 #pragma unroll
-      for (int rb = 0; rb < 4; ++rb) fa[ks2][rb] = read_a16(buf, 0, rb, ks2);
+      for (int rb = 0; rb < (WIDEB ? 2 : 4); ++rb) fa[ks2][rb] = rd(rb, ks2);
+  };
+  // the owner's column sums: every B fragment just read goes into its column block's sum, sum = add(fragment, sum)
+  auto sum_b16 = [&](auto add) {
+    if constexpr (WIDEB) {
+#pragma unroll
+      for (int hc = 0; hc < 8; ++hc)
+#pragma unroll
+        for (int ks2 = 0; ks2 < 2; ++ks2) csw[hc] = add(fbx[hc * 2 + ks2], csw[hc]);
+    } else {
+#pragma unroll
+      for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+        for (int ks2 = 0; ks2 < 2; ++ks2) {
+          cs16[cb] = add(fb0[2 * cb + ks2], cs16[cb]);
+          cs16[2 + cb] = add(fb1[2 * cb + ks2], cs16[2 + cb]);
+        }
+    }
+  };
+  // the phase's 32 MFMAs into the accumulator blocks of its row half (r0 = 0 / 4); kSwap: the transposed block (the miner /
+  // kNN filter / rank count: a row's columns per lane)
+  auto mfma16 = [&](const int r0) {
+    __builtin_amdgcn_s_setprio(1);
+    if constexpr (WIDEB) {
+#pragma unroll
+      for (int ks2 = 0; ks2 < 2; ++ks2)
+#pragma unroll
+        for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+          for (int hh = 0; hh < 2; ++hh)
+#pragma unroll
+            for (int cb = 0; cb < 4; ++cb)
+              acc16[r0 + 2 * hh + rb][cb] = CDML_MFMA16(fa[ks2][rb], fbx[hh * 8 + cb * 2 + ks2], acc16[r0 + 2 * hh + rb][cb]);
+    } else {
+#pragma unroll
+      for (int ks2 = 0; ks2 < 2; ++ks2)
+#pragma unroll
+        for (int rb = 0; rb < 4; ++rb)
+#pragma unroll
+          for (int cb = 0; cb < 2; ++cb) {
+            if constexpr (kSwap) {
+              acc16[r0 + rb][cb] = CDML_MFMA16(fb0[2 * cb + ks2], fa[ks2][rb], acc16[r0 + rb][cb]);
+              acc16[r0 + rb][2 + cb] = CDML_MFMA16(fb1[2 * cb + ks2], fa[ks2][rb], acc16[r0 + rb][2 + cb]);
+            } else {
+              acc16[r0 + rb][cb] = CDML_MFMA16(fa[ks2][rb], fb0[2 * cb + ks2], acc16[r0 + rb][cb]);
+              acc16[r0 + rb][2 + cb] = CDML_MFMA16(fa[ks2][rb], fb1[2 * cb + ks2], acc16[r0 + rb][2 + cb]);
+            }
+          }
+    }
+    __builtin_amdgcn_s_setprio(0);
+  };
+  // 16x16x32 form of the K-tile
+  auto do_tile2_s16 = [&](const int buf, const int tile) {
+    load_b16([&](int hh, int cb, int ks2) { return read_b16(buf, hh, cb, ks2); });
+    load_a16([&](int rb, int ks2) { return read_a16(buf, 0, rb, ks2); });
     if (X3 && x3_run) {
       const int pl = (0x120100 >> (4 * (xp_a & 7))) & 3;
       stage_pw(0, 0, pl, xp_a >> 3, tile + 1, buf ^ 1);
@@ -481,32 +460,11 @@ __device__ __forceinline__ void run_tile(const BArgs &g, const int tm, const int
     // (the owner test as a countdown in an SGPR: `tile % cs_period` was a dozen scalar instructions per K-tile)
     const bool cs_mine = cs_left == 0;
     cs_left = cs_mine ? cs_period - 1 : cs_left - 1;
-    if (cs_mine && (!X3 || ((0xB >> (x3_run ? (xp_c & 7) : x3_segment(x3_t0 + tile))) & 1))) {
-#pragma unroll
-      for (int cb = 0; cb < 2; ++cb)
-#pragma unroll
-        for (int ks2 = 0; ks2 < 2; ++ks2) {
-          cs16[cb] = dot_sum(fb0[2 * cb + ks2], cs16[cb]);
-          cs16[2 + cb] = dot_sum(fb1[2 * cb + ks2], cs16[2 + cb]);
-        }
-    }
+    if (cs_mine && (!X3 || ((0xB >> (x3_run ? (xp_c & 7) : x3_segment(x3_t0 + tile))) & 1))) sum_b16(dot_sum);
     CDML_BARRIER();
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int ks2 = 0; ks2 < 2; ++ks2)
-#pragma unroll
-      for (int rb = 0; rb < 4; ++rb)
-#pragma unroll
-        for (int cb = 0; cb < 2; ++cb) {
-          acc16[rb][cb] = CDML_MFMA16(fa[ks2][rb], fb0[2 * cb + ks2], acc16[rb][cb]);
-          acc16[rb][2 + cb] = CDML_MFMA16(fa[ks2][rb], fb1[2 * cb + ks2], acc16[rb][2 + cb]);
-        }
-    __builtin_amdgcn_s_setprio(0);
+    mfma16(0);
     CDML_BARRIER();
-#pragma unroll
-    for (int ks2 = 0; ks2 < 2; ++ks2)
-#pragma unroll
-      for (int rb = 0; rb < 4; ++rb) fa[ks2][rb] = read_a16(buf, 1, rb, ks2);
+    load_a16([&](int rb, int ks2) { return read_a16(buf, 1, rb, ks2); });
     if (X3 && x3_run) {
       const int pl = (0x102010 >> (4 * (xp_b & 7))) & 3;
       stage_pw(1, 0, pl, xp_b >> 3, tile + 2, buf);
@@ -518,17 +476,7 @@ __device__ __forceinline__ void run_tile(const BArgs &g, const int tm, const int
     asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
     pin_a();
     CDML_BARRIER();
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int ks2 = 0; ks2 < 2; ++ks2)
-#pragma unroll
-      for (int rb = 0; rb < 4; ++rb)
-#pragma unroll
-        for (int cb = 0; cb < 2; ++cb) {
-          acc16[4 + rb][cb] = CDML_MFMA16(fa[ks2][rb], fb0[2 * cb + ks2], acc16[4 + rb][cb]);
-          acc16[4 + rb][2 + cb] = CDML_MFMA16(fa[ks2][rb], fb1[2 * cb + ks2], acc16[4 + rb][2 + cb]);
-        }
-    __builtin_amdgcn_s_setprio(0);
+    mfma16(4);
     CDML_BARRIER();
     if (X3 && x3_run) { xp_c = x3_step(xp_c); xp_a = x3_step(xp_a); xp_b = x3_step(xp_b); }
   };
@@ -545,17 +493,8 @@ __device__ __forceinline__ void run_tile(const BArgs &g, const int tm, const int
     constexpr bool skip_b = (S <= 3) && PB[(S + 2) % 6] == PB[S];                       // B of step + 2 == B of this step
     constexpr int SP = (S + 5) % 6;                                                      // the previous step
     constexpr bool b_next_issued = !((SP <= 3) && PB[(SP + 2) % 6] == PB[SP]);           // B of step + 1: staged by it?
-#pragma unroll
-    for (int cb = 0; cb < 2; ++cb)
-#pragma unroll
-      for (int ks2 = 0; ks2 < 2; ++ks2) {
-        fb0[2 * cb + ks2] = read_b16(buf, 0, cb, ks2);
-        fb1[2 * cb + ks2] = read_b16(buf, 1, cb, ks2);
-      }
-#pragma unroll
-    for (int ks2 = 0; ks2 < 2; ++ks2)
-#pragma unroll
-      for (int rb = 0; rb < 4; ++rb) fa[ks2][rb] = read_a16(buf, 0, rb, ks2);
+    load_b16([&](int hh, int cb, int ks2) { return read_b16(buf, hh, cb, ks2); });
+    load_a16([&](int rb, int ks2) { return read_a16(buf, 0, rb, ks2); });
     if constexpr (!skip_a) {
       stage_pw(0, 0, PA[(S + 1) % 6], w + (S == 5 ? 1 : 0), tile + 1, buf ^ 1);
       stage_pw(0, 1, PA[(S + 1) % 6], w + (S == 5 ? 1 : 0), tile + 1, buf ^ 1);
@@ -564,32 +503,12 @@ __device__ __forceinline__ void run_tile(const BArgs &g, const int tm, const int
     asm volatile("s_waitcnt vmcnt(%0)" :: "n"(4 * (int)b_next_issued + 4 * (int)!skip_a) : "memory");
     pin_b();
     pin_a();
-    if (cs_on && ((0xB >> S) & 1) && (tile % cs_period) == cs_owner) {
-#pragma unroll
-      for (int cb = 0; cb < 2; ++cb)
-#pragma unroll
-        for (int ks2 = 0; ks2 < 2; ++ks2) {
-          cs16[cb] += frag_sum(fb0[2 * cb + ks2]);
-          cs16[2 + cb] += frag_sum(fb1[2 * cb + ks2]);
-        }
-    }
+    if (cs_on && ((0xB >> S) & 1) && (tile % cs_period) == cs_owner)
+      sum_b16([&](const bf16x8 &f, float sum) { return sum + frag_sum(f); });
     CDML_BARRIER();
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int ks2 = 0; ks2 < 2; ++ks2)
-#pragma unroll
-      for (int rb = 0; rb < 4; ++rb)
-#pragma unroll
-        for (int cb = 0; cb < 2; ++cb) {
-          acc16[rb][cb] = CDML_MFMA16(fa[ks2][rb], fb0[2 * cb + ks2], acc16[rb][cb]);
-          acc16[rb][2 + cb] = CDML_MFMA16(fa[ks2][rb], fb1[2 * cb + ks2], acc16[rb][2 + cb]);
-        }
-    __builtin_amdgcn_s_setprio(0);
+    mfma16(0);
     CDML_BARRIER();
-#pragma unroll
-    for (int ks2 = 0; ks2 < 2; ++ks2)
-#pragma unroll
-      for (int rb = 0; rb < 4; ++rb) fa[ks2][rb] = read_a16(buf, 1, rb, ks2);
+    load_a16([&](int rb, int ks2) { return read_a16(buf, 1, rb, ks2); });
     if constexpr (!skip_b) {
       stage_pw(1, 0, PB[(S + 2) % 6], w + (S >= 4 ? 1 : 0), tile + 2, buf);
       stage_pw(1, 1, PB[(S + 2) % 6], w + (S >= 4 ? 1 : 0), tile + 2, buf);
@@ -598,17 +517,7 @@ __device__ __forceinline__ void run_tile(const BArgs &g, const int tm, const int
     asm volatile("s_waitcnt vmcnt(%0)" :: "n"(2 * (int)!skip_a + 4 * (int)!skip_b) : "memory");
     pin_a();
     CDML_BARRIER();
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int ks2 = 0; ks2 < 2; ++ks2)
-#pragma unroll
-      for (int rb = 0; rb < 4; ++rb)
-#pragma unroll
-        for (int cb = 0; cb < 2; ++cb) {
-          acc16[4 + rb][cb] = CDML_MFMA16(fa[ks2][rb], fb0[2 * cb + ks2], acc16[4 + rb][cb]);
-          acc16[4 + rb][2 + cb] = CDML_MFMA16(fa[ks2][rb], fb1[2 * cb + ks2], acc16[4 + rb][2 + cb]);
-        }
-    __builtin_amdgcn_s_setprio(0);
+    mfma16(4);
     CDML_BARRIER();
   };
   auto do_tile2 = [&](const int buf, const int tile) {
@@ -689,7 +598,6 @@ __device__ __forceinline__ void run_tile(const BArgs &g, const int tm, const int
   //   alternate between the two B slots.  Every overwrite is issued at least one phase after the last read of what it
   //   replaces (reads are retired before a phase's first barrier, the lagging group is one barrier behind: the rule of
   //   the schedule at the top of this file), every image is waited for one phase before its first read.
-  constexpr bool kR6 = X3 && S16 && R6;
   if constexpr (kR6) {
     constexpr int kPer = kF16 ? 3 : 6;                     // steps per K-tile: the plane products
     const int n_per = n_ktiles / kPer;                     // whole periods (host)
@@ -772,7 +680,6 @@ __device__ __forceinline__ void run_tile(const BArgs &g, const int tm, const int
       //   before; A0' into the slot A0 of the K-tile BEFORE left at phases 4 / 5; B0' after phase 0; A1' halves after phases
       //   2 / 3), every image is waited for one phase before its first read (replayed from this source by
       //   tests/test_r6_schedule.py).
-      static_assert(!NARROW && !KI, "the fp16 form has the full tile on row-major operands only");
       auto phase3 = [&](auto phc, auto parc, const uint32_t kwb_c, const uint32_t kwa_n, const uint32_t kwb_n, const bool own) {
         constexpr int PH = decltype(phc)::value, PAR = decltype(parc)::value;
         constexpr int S = PH >> 1, HALF = PH & 1;
@@ -782,18 +689,9 @@ __device__ __forceinline__ void run_tile(const BArgs &g, const int tm, const int
         constexpr bool rdB = HALF == 0 && (S == 0 || S == 2);
         if constexpr (rdB) {
           constexpr int sb = PB3[S];
-#pragma unroll
-          for (int cb = 0; cb < 2; ++cb)
-#pragma unroll
-            for (int ks2 = 0; ks2 < 2; ++ks2) {
-              fb0[2 * cb + ks2] = rd_b(sb, 0, cb, ks2);
-              fb1[2 * cb + ks2] = rd_b(sb, 1, cb, ks2);
-            }
+          load_b16([&](int hh, int cb, int ks2) { return rd_b(sb, hh, cb, ks2); });
         }
-#pragma unroll
-        for (int ks2 = 0; ks2 < 2; ++ks2)
-#pragma unroll
-          for (int rb = 0; rb < 4; ++rb) fa[ks2][rb] = rd_a(sa, HALF, rb, ks2);
+        load_a16([&](int rb, int ks2) { return rd_a(sa, HALF, rb, ks2); });
         // Two placements of the period's eight loads (SCH).  0: the table above.  1: one load in each of the fragment-heavy
         // phases 0 / 4 (they also read the B fragments) and two in phases 1 / 3 -- B1.h0 | B1.h1 A0'.h0 | A0'.h1 | B0'.h0 B0'.h1 |
         // A1'.h0 | A1'.h1, waits 6 8 8 8 10 4: FC1 554.7 against 560.7 us, the other k-contiguous products even
@@ -817,44 +715,16 @@ __device__ __forceinline__ void run_tile(const BArgs &g, const int tm, const int
         if constexpr (rdB) pin_b();
         pin_a();
         if constexpr (rdB) {
-          if (own) {                                       // bias gradient: this (tile, row group) owns the K-tile
-#pragma unroll
-            for (int cb = 0; cb < 2; ++cb)
-#pragma unroll
-              for (int ks2 = 0; ks2 < 2; ++ks2) {
-                cs16[cb] = dot_sum(fb0[2 * cb + ks2], cs16[cb]);
-                cs16[2 + cb] = dot_sum(fb1[2 * cb + ks2], cs16[2 + cb]);
-              }
-          }
+          if (own) sum_b16(dot_sum);                       // bias gradient: this (tile, row group) owns the K-tile
         }
         CDML_BARRIER();
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int ks2 = 0; ks2 < 2; ++ks2)
-#pragma unroll
-          for (int rb = 0; rb < 4; ++rb)
-#pragma unroll
-            for (int cb = 0; cb < 2; ++cb) {
-              if constexpr (kSwap) {                       // (the miner / kNN filter: the transposed block, a row's columns per lane)
-                acc16[4 * HALF + rb][cb] = CDML_MFMA16(fb0[2 * cb + ks2], fa[ks2][rb], acc16[4 * HALF + rb][cb]);
-                acc16[4 * HALF + rb][2 + cb] = CDML_MFMA16(fb1[2 * cb + ks2], fa[ks2][rb], acc16[4 * HALF + rb][2 + cb]);
-              } else {
-                acc16[4 * HALF + rb][cb] = CDML_MFMA16(fa[ks2][rb], fb0[2 * cb + ks2], acc16[4 * HALF + rb][cb]);
-                acc16[4 * HALF + rb][2 + cb] = CDML_MFMA16(fa[ks2][rb], fb1[2 * cb + ks2], acc16[4 * HALF + rb][2 + cb]);
-              }
-            }
-        __builtin_amdgcn_s_setprio(0);
+        mfma16(4 * HALF);
         CDML_BARRIER();
       };
       auto period3 = [&](auto parc, const int w, const bool own) {
         const int wn = min(w + 1, w_last);                 // past the end: a valid K-tile again (its images are never read)
         const uint32_t kwb_c = (uint32_t)w * ws_b, kwa_n = (uint32_t)wn * ws_a, kwb_n = (uint32_t)wn * ws_b;
-        phase3(std::integral_constant<int, 0>{}, parc, kwb_c, kwa_n, kwb_n, own);
-        phase3(std::integral_constant<int, 1>{}, parc, kwb_c, kwa_n, kwb_n, own);
-        phase3(std::integral_constant<int, 2>{}, parc, kwb_c, kwa_n, kwb_n, own);
-        phase3(std::integral_constant<int, 3>{}, parc, kwb_c, kwa_n, kwb_n, own);
-        phase3(std::integral_constant<int, 4>{}, parc, kwb_c, kwa_n, kwb_n, own);
-        phase3(std::integral_constant<int, 5>{}, parc, kwb_c, kwa_n, kwb_n, own);
+        unroll<6>([&](auto phc) { phase3(phc, parc, kwb_c, kwa_n, kwb_n, own); });
       };
       // R3 prologue: the steady state at phase 0 of the first K-tile (parity 0): what phases 1 .. 5 of a previous period
       // would have issued, in their order, then the wait of its phase 5
@@ -890,27 +760,9 @@ __device__ __forceinline__ void run_tile(const BArgs &g, const int tm, const int
         constexpr bool rdB = HALF == 0 && (S == 0 || S == 3 || S == 5);
         if constexpr (rdB) {
           constexpr int sb = (PB[S] & 1) ^ PAR;
-          if constexpr (WIDEB) {
-#pragma unroll
-            for (int hh = 0; hh < 2; ++hh)
-#pragma unroll
-              for (int cb = 0; cb < 4; ++cb)
-#pragma unroll
-                for (int ks2 = 0; ks2 < 2; ++ks2) fbx[hh * 8 + cb * 2 + ks2] = rd_b(sb, hh, cb, ks2);
-          } else {
-#pragma unroll
-          for (int cb = 0; cb < 2; ++cb)
-#pragma unroll
-            for (int ks2 = 0; ks2 < 2; ++ks2) {
-              fb0[2 * cb + ks2] = rd_b(sb, 0, cb, ks2);
-              fb1[2 * cb + ks2] = rd_b(sb, 1, cb, ks2);
-            }
-          }
+          load_b16([&](int hh, int cb, int ks2) { return rd_b(sb, hh, cb, ks2); });
         }
-#pragma unroll
-        for (int ks2 = 0; ks2 < 2; ++ks2)
-#pragma unroll
-          for (int rb = 0; rb < (WIDEB ? 2 : 4); ++rb) fa[ks2][rb] = rd_a(sa, HALF, rb, ks2);
+        load_a16([&](int rb, int ks2) { return rd_a(sa, HALF, rb, ks2); });
         if constexpr (PH == 0) issue(0, 2, 1, SLOT_A[PAR][2], kwa_c);
         if constexpr (PH == 1) issue(1, 1, 0, 1 ^ PAR, kwb_c);
         if constexpr (PH == 2) issue(1, 1, 1, 1 ^ PAR, kwb_c);
@@ -925,70 +777,20 @@ __device__ __forceinline__ void run_tile(const BArgs &g, const int tm, const int
         if constexpr (PH == 11) issue(0, 2, 0, SLOT_A[PAR ^ 1][2], kwa_n);
         constexpr int VM[12] = {8, 8, 8, 8, 8, 6, 8, 10, 12, 10, 12, 6};
         asm volatile("s_waitcnt vmcnt(%0)" :: "n"(VM[PH]) : "memory");
-        if constexpr (WIDEB) {
-          if constexpr (rdB)
-            asm volatile("" : "+v"(fbx[0]), "+v"(fbx[1]), "+v"(fbx[2]), "+v"(fbx[3]), "+v"(fbx[4]), "+v"(fbx[5]), "+v"(fbx[6]), "+v"(fbx[7]),
-                              "+v"(fbx[8]), "+v"(fbx[9]), "+v"(fbx[10]), "+v"(fbx[11]), "+v"(fbx[12]), "+v"(fbx[13]), "+v"(fbx[14]), "+v"(fbx[15]));
-          asm volatile("" : "+v"(fa[0][0]), "+v"(fa[0][1]), "+v"(fa[1][0]), "+v"(fa[1][1]));
-          if constexpr (rdB) {
-            // bias gradient: the K-tile's owner (tile, set) as in the row-major form; of the two waves of a set that hold
-            // the same B fragments, row sub-group 0 sums them -- per column the same values in the same order
-            if (own && (wc >> 1) == 0) {
-#pragma unroll
-              for (int hc = 0; hc < 8; ++hc)
-#pragma unroll
-                for (int ks2 = 0; ks2 < 2; ++ks2) csw[hc] = dot_sum(fbx[hc * 2 + ks2], csw[hc]);
-            }
-          }
-          CDML_BARRIER();
-          __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-          for (int ks2 = 0; ks2 < 2; ++ks2)
-#pragma unroll
-            for (int rb = 0; rb < 2; ++rb)
-#pragma unroll
-              for (int hh = 0; hh < 2; ++hh)
-#pragma unroll
-                for (int cb = 0; cb < 4; ++cb)
-                  acc16[4 * HALF + 2 * hh + rb][cb] = CDML_MFMA16(fa[ks2][rb], fbx[hh * 8 + cb * 2 + ks2], acc16[4 * HALF + 2 * hh + rb][cb]);
-          __builtin_amdgcn_s_setprio(0);
-          CDML_BARRIER();
-          return;
-        }
         if constexpr (rdB) pin_b();
         pin_a();
         if constexpr (rdB) {
-          if (own) {                                       // bias gradient: this (tile, row group) owns the K-tile
-#pragma unroll
-            for (int cb = 0; cb < 2; ++cb)
-#pragma unroll
-              for (int ks2 = 0; ks2 < 2; ++ks2) {
-                cs16[cb] = dot_sum(fb0[2 * cb + ks2], cs16[cb]);
-                cs16[2 + cb] = dot_sum(fb1[2 * cb + ks2], cs16[2 + cb]);
-              }
+          // bias gradient: this (tile, row group) owns the K-tile.  WIDEB: the K-tile's owner (tile, set) as in the row-major
+          // form; of the two waves of a set that hold the same B fragments, row sub-group 0 sums them -- per column the same
+          // values in the same order
+          if constexpr (WIDEB) {
+            if (own && (wc >> 1) == 0) sum_b16(dot_sum);
+          } else {
+            if (own) sum_b16(dot_sum);
           }
         }
         CDML_BARRIER();
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int ks2 = 0; ks2 < 2; ++ks2)
-#pragma unroll
-          for (int rb = 0; rb < 4; ++rb)
-#pragma unroll
-            for (int cb = 0; cb < 2; ++cb) {
-              if constexpr (kSwap) {
-                acc16[4 * HALF + rb][cb] =
-                    CDML_MFMA16(fb0[2 * cb + ks2], fa[ks2][rb], acc16[4 * HALF + rb][cb]);
-                acc16[4 * HALF + rb][2 + cb] =
-                    CDML_MFMA16(fb1[2 * cb + ks2], fa[ks2][rb], acc16[4 * HALF + rb][2 + cb]);
-              } else {
-              acc16[4 * HALF + rb][cb] =
-                  CDML_MFMA16(fa[ks2][rb], fb0[2 * cb + ks2], acc16[4 * HALF + rb][cb]);
-              acc16[4 * HALF + rb][2 + cb] =
-                  CDML_MFMA16(fa[ks2][rb], fb1[2 * cb + ks2], acc16[4 * HALF + rb][2 + cb]);
-              }
-            }
-        __builtin_amdgcn_s_setprio(0);
+        mfma16(4 * HALF);
         CDML_BARRIER();
       };
       // (round 6 pointed the last period's run-ahead loads -- seven half images "for the next K-tile" that nobody reads -- at the
@@ -999,18 +801,7 @@ __device__ __forceinline__ void run_tile(const BArgs &g, const int tm, const int
         const int wn = min(w + 1, w_last);                 // past the end: a valid K-tile again (its images are never read)
         const uint32_t kwa_c = (uint32_t)w * ws_a, kwb_c = (uint32_t)w * ws_b;
         const uint32_t kwa_n = (uint32_t)wn * ws_a, kwb_n = (uint32_t)wn * ws_b;
-        phase(std::integral_constant<int, 0>{}, parc, kwa_c, kwb_c, kwa_n, kwb_n, own);
-        phase(std::integral_constant<int, 1>{}, parc, kwa_c, kwb_c, kwa_n, kwb_n, own);
-        phase(std::integral_constant<int, 2>{}, parc, kwa_c, kwb_c, kwa_n, kwb_n, own);
-        phase(std::integral_constant<int, 3>{}, parc, kwa_c, kwb_c, kwa_n, kwb_n, own);
-        phase(std::integral_constant<int, 4>{}, parc, kwa_c, kwb_c, kwa_n, kwb_n, own);
-        phase(std::integral_constant<int, 5>{}, parc, kwa_c, kwb_c, kwa_n, kwb_n, own);
-        phase(std::integral_constant<int, 6>{}, parc, kwa_c, kwb_c, kwa_n, kwb_n, own);
-        phase(std::integral_constant<int, 7>{}, parc, kwa_c, kwb_c, kwa_n, kwb_n, own);
-        phase(std::integral_constant<int, 8>{}, parc, kwa_c, kwb_c, kwa_n, kwb_n, own);
-        phase(std::integral_constant<int, 9>{}, parc, kwa_c, kwb_c, kwa_n, kwb_n, own);
-        phase(std::integral_constant<int, 10>{}, parc, kwa_c, kwb_c, kwa_n, kwb_n, own);
-        phase(std::integral_constant<int, 11>{}, parc, kwa_c, kwb_c, kwa_n, kwb_n, own);
+        unroll<12>([&](auto phc) { phase(phc, parc, kwa_c, kwb_c, kwa_n, kwb_n, own); });
       };
       // prologue: the steady state at phase 0 of the first K-tile (parity 0): what phases 5 .. 11 of a previous period
       // would have issued, in their order, then the wait of its phase 11
@@ -1072,19 +863,8 @@ __device__ __forceinline__ void run_tile(const BArgs &g, const int tm, const int
         constexpr int PA[6] = {0, 1, 2, 0, 1, 0}, PB[6] = {0, 0, 0, 1, 1, 2};
         constexpr int NSLOT_A[2][3] = {{0, 1, 2}, {3, 2, 1}};    // [parity][plane]
         constexpr bool rdB = S == 0 || S == 3 || S == 5;
-        if constexpr (rdB) {
-#pragma unroll
-          for (int cb = 0; cb < 2; ++cb)
-#pragma unroll
-            for (int ks2 = 0; ks2 < 2; ++ks2) {
-              fb0[2 * cb + ks2] = rd_bn(PB[S], 0, cb, ks2);
-              fb1[2 * cb + ks2] = rd_bn(PB[S], 1, cb, ks2);
-            }
-        }
-#pragma unroll
-        for (int ks2 = 0; ks2 < 2; ++ks2)
-#pragma unroll
-          for (int rb = 0; rb < 4; ++rb) fa[ks2][rb] = rd_an(NSLOT_A[PAR][PA[S]], rb, ks2);
+        if constexpr (rdB) load_b16([&](int hh, int cb, int ks2) { return rd_bn(PB[S], hh, cb, ks2); });
+        load_a16([&](int rb, int ks2) { return rd_an(NSLOT_A[PAR][PA[S]], rb, ks2); });
         if constexpr (S == 0) { issue_n(1, 2, 0, 2, kwb_c); issue_n(1, 2, 1, 2, kwb_c); }
         if constexpr (S == 1) { issue_n(1, 0, 0, 0, kwb_n); issue_n(0, 0, 0, NSLOT_A[PAR ^ 1][0], kwa_n); }
         if constexpr (S == 2) { issue_n(1, 0, 1, 0, kwb_n); }
@@ -1096,28 +876,13 @@ __device__ __forceinline__ void run_tile(const BArgs &g, const int tm, const int
         if constexpr (rdB) pin_b();
         pin_a();
         CDML_BARRIER();
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int ks2 = 0; ks2 < 2; ++ks2)
-#pragma unroll
-          for (int rb = 0; rb < 4; ++rb)
-#pragma unroll
-            for (int cb = 0; cb < 2; ++cb) {
-              acc16[rb][cb] = CDML_MFMA16(fa[ks2][rb], fb0[2 * cb + ks2], acc16[rb][cb]);
-              acc16[rb][2 + cb] = CDML_MFMA16(fa[ks2][rb], fb1[2 * cb + ks2], acc16[rb][2 + cb]);
-            }
-        __builtin_amdgcn_s_setprio(0);
+        mfma16(0);
         CDML_BARRIER();
       };
       auto period_n = [&](auto parc, const int w) {
         const int wn = min(w + 1, w_last);                 // past the end: a valid K-tile again (its images are never read)
         const uint32_t kwb_c = (uint32_t)w * ws_b, kwa_n = (uint32_t)wn * ws_a, kwb_n = (uint32_t)wn * ws_b;
-        phase_n(std::integral_constant<int, 0>{}, parc, kwb_c, kwa_n, kwb_n);
-        phase_n(std::integral_constant<int, 1>{}, parc, kwb_c, kwa_n, kwb_n);
-        phase_n(std::integral_constant<int, 2>{}, parc, kwb_c, kwa_n, kwb_n);
-        phase_n(std::integral_constant<int, 3>{}, parc, kwb_c, kwa_n, kwb_n);
-        phase_n(std::integral_constant<int, 4>{}, parc, kwb_c, kwa_n, kwb_n);
-        phase_n(std::integral_constant<int, 5>{}, parc, kwb_c, kwa_n, kwb_n);
+        unroll<6>([&](auto sc) { phase_n(sc, parc, kwb_c, kwa_n, kwb_n); });
       };
       // narrow prologue: the steady state at step 0 of the first K-tile (parity 0): what steps 1 .. 5 of a previous
       // period would have issued, in their order, then the wait of its step 5
@@ -1150,7 +915,6 @@ __device__ __forceinline__ void run_tile(const BArgs &g, const int tm, const int
   asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
   CDML_BARRIER();
   if (grp == 1) CDML_BARRIER();                          // group 1 runs one barrier behind
-  constexpr bool kFast6 = X3 && S16 && F6;
   if constexpr (kFast6) {
     {
       int w = x3_t0 / 6;
@@ -1486,10 +1250,6 @@ __device__ __forceinline__ void run_tile(const BArgs &g, const int tm, const int
     const int lr = p * 4 + (lane >> 4);
     return TN ? m0 + (rt >> 1) * 128 + grp * 64 + (rt & 1) * 32 + lr : m0 + grp * GRg + rt * 32 + lr;
   };
-  constexpr bool kRowBias = EPI == BE_ROWBIAS_LRELU_X3;
-  constexpr bool kBiasEpi = EPI == BE_BIAS_LRELU_BF16 || EPI == BE_BIAS_LRELU_X3 || kRowBias;
-  constexpr bool kMaskEpi = EPI == BE_MASK_BF16 || EPI == BE_MASK_X3;
-  constexpr bool kPlanes = EPI == BE_BIAS_LRELU_X3 || EPI == BE_MASK_X3 || kRowBias;
   if constexpr (!TN && (kBiasEpi || kMaskEpi)) {
     // bf16 outputs of the k-contiguous form: 16 B per lane and store (8 rows x 128 B per instruction) instead of
     // 8 B -- half the store instructions of the tile's tail (cdna guide T21: such a tail is issue-bound)
@@ -1792,8 +1552,10 @@ __device__ __forceinline__ void run_tile(const BArgs &g, const int tm, const int
 }
 
 // one block of a launch: block index `bid` of this launch -> (half) tile -> run_tile
-template <bool TN, int EPI, bool S16, bool X3, bool F6, bool NTCS, bool R6, bool NARROW, bool KI = false, bool WIDEB = false>
+template <class V>
 __device__ __forceinline__ void block_of_launch(const BArgs &g, int bid, unsigned char *smem) {
+  constexpr bool TN = V::TN, X3 = V::X3, NTCS = V::NTCS, NARROW = V::NARROW;
+  constexpr int EPI = V::EPI;
   int tm, tn;
   // the block -> tile map of the WHOLE tile grid, of which this launch may cover the first blocks only (grid_tiles) or,
   // NARROW, the rest as two half tiles each: block (xcd, local) -> half local / per of the tile of block (narrow_first / 8
@@ -1822,18 +1584,17 @@ __device__ __forceinline__ void block_of_launch(const BArgs &g, int bid, unsigne
   const int n_ktiles = k_end > k_begin ? (k_end - k_begin) / kTileK : 0;   // even (host)
   void *c_base = EPI == BE_F32 ? static_cast<void *>(static_cast<float *>(g.C) + (int64_t)split * g.slab_stride) : g.C;
   float *cs_row = ((TN || NTCS) && g.colsum_partial) ? g.colsum_partial + (int64_t)((split * g.tiles_m + tm) * 2) * g.N + n0 : nullptr;
-  run_tile<TN, EPI, S16, X3, F6, NTCS, R6, NARROW, KI, WIDEB>(g, tm, m0, n0, k_begin, n_ktiles, c_base, g.ldc, m0, n0, cs_row, g.N, smem);
+  run_tile<V>(g, tm, m0, n0, k_begin, n_ktiles, c_base, g.ldc, m0, n0, cs_row, g.N, smem);
 }
 
-template <bool TN, int EPI, bool S16, bool X3 = false, bool F6 = false, bool NTCS = false, bool R6 = false, bool NARROW = false,
-          bool KI = false, bool WIDEB = false>
+template <class V>
 __global__ void __launch_bounds__(kT, 1) k_gemm_bf16_256(BArgs g) {
   extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];
   // (round 5: ONE resident block per CU walking the launch's tiles -- no block dispatch between a CU's tiles -- was built
   // and measured: miner 0.437-0.442 against 0.429-0.430 ms, headline step 2.629-2.633 against 2.621-2.623 ms,
   // profiles/r05_persistent_tiles_ab.txt; the loop around run_tile also cost the k-strided kernel its last free VGPRs --
   // 72 B of scratch.  Removed.)
-  block_of_launch<TN, EPI, S16, X3, F6, NTCS, R6, NARROW, KI, WIDEB>(g, blockIdx.x, smem);
+  block_of_launch<V>(g, blockIdx.x, smem);
 }
 
 // full tiles and the last round's half tiles in ONE launch (blocks [0, narrow_first): full tiles; the rest: half tiles):
@@ -1843,8 +1604,8 @@ __global__ void __launch_bounds__(kT, 1) k_gemm_x3_rounds(BArgs g) {
   extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];
   // dispatch order (blocks start in index order): [stagger_lead half-tile blocks][the full tiles][the other half-tile blocks]
   const int b = blockIdx.x, lead = g.stagger_lead;
-  if (b >= lead && b < lead + g.narrow_first) block_of_launch<false, EPI, true, true, false, false, true, false>(g, b - lead, smem);
-  else block_of_launch<false, EPI, true, true, false, false, true, true>(g, b < lead ? b : b - g.narrow_first, smem);
+  if (b >= lead && b < lead + g.narrow_first) block_of_launch<X3Resident<false, EPI>>(g, b - lead, smem);
+  else block_of_launch<X3ResidentHalf<EPI>>(g, b < lead ? b : b - g.narrow_first, smem);
 }
 
 // ---- both weight gradients of the tower in ONE launch (k-strided form; dW1 = x_hat^T dz1, dW2 = h1^T dz2) ----
@@ -1888,7 +1649,7 @@ __global__ void __launch_bounds__(kT, 1) k_gemm_bf16_sk(SKArgs a) {
     const int slot = sk_slot(a, u);
     if (!first) CDML_BARRIER();                      // the previous segment's epilogue strips are LDS images again
     first = false;
-    run_tile<true, BE_F32, S16>(g, tm, tm * kTileM, tn * kTileN, ku * 2 * kTileK, len * 2,
+    run_tile<PlainLoop<true, BE_F32, S16>>(g, tm, tm * kTileM, tn * kTileN, ku * 2 * kTileK, len * 2,
                                 a.partials + (int64_t)slot * (kTileM * kTileN), kTileN, 0, 0,
                                 a.cs_partials ? a.cs_partials + (int64_t)slot * (2 * kTileN) : nullptr, kTileN, smem);
     u += len;
@@ -1941,18 +1702,23 @@ __global__ void __launch_bounds__(256) k_sk_fixup_tn(SKArgs a, float *db0, float
   db[tn * kTileN + threadIdx.x] = acc;
 }
 
-template <bool TN, int EPI, bool S16>
-int launch1(const BArgs &g, int splits, hipStream_t s) {
-  static bool configured = false;   // raising the dynamic-LDS limit is idempotent; a race only repeats it
+// One launch of kernel Fn (512 threads, `smem` bytes of dynamic LDS), checked; the kernel's LDS limit is raised before its
+// first launch (idempotent; a race only repeats it).  `what` names the launcher in error messages.
+template <auto Fn, class Arg>
+int launch_kernel(dim3 grid, int smem, hipStream_t s, const Arg &arg, const char *what) {
+  static bool configured = false;
   if (!configured) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_gemm_bf16_256<TN, EPI, S16>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-    if (e != hipSuccess) return fail(CDML_E_HIP, "gemm_bf16_256: cannot reserve %d B of LDS: %s", SMEM,
-                                     hipGetErrorString(e));
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(Fn), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
+    if (e != hipSuccess) return fail(CDML_E_HIP, "%s: cannot reserve %d B of LDS: %s", what, smem, hipGetErrorString(e));
     configured = true;
   }
-  hipLaunchKernelGGL((k_gemm_bf16_256<TN, EPI, S16>), dim3(g.tiles_m * g.tiles_n, splits), dim3(kT), SMEM, s, g);
-  return check_launch("gemm_bf16_256");
+  hipLaunchKernelGGL(Fn, grid, dim3(kT), smem, s, arg);
+  return check_launch(what);
+}
+// a whole tile grid of variant V
+template <class V>
+int launch_tiles(const BArgs &g, int blocks, int splits, hipStream_t s, const char *what) {
+  return launch_kernel<&k_gemm_bf16_256<V>>(dim3(blocks, splits), V::kSmem, s, g, what);
 }
 
 // MFMA shape: CDML_BF16_MFMA = "32" (v_mfma_f32_32x32x16_bf16) or "16"
@@ -1964,8 +1730,8 @@ static bool shape16() {
 
 template <bool TN, int EPI>
 int launch(const BArgs &g, int splits, hipStream_t s) {
-  if (shape16()) return launch1<TN, EPI, true>(g, splits, s);
-  return launch1<TN, EPI, false>(g, splits, s);
+  if (shape16()) return launch_tiles<PlainLoop<TN, EPI, true>>(g, g.tiles_m * g.tiles_n, splits, s, "gemm_bf16_256");
+  return launch_tiles<PlainLoop<TN, EPI, false>>(g, g.tiles_m * g.tiles_n, splits, s, "gemm_bf16_256");
 }
 
 }  // namespace
@@ -2003,33 +1769,22 @@ int launch_gemm_bf16_256(const BArgs &g, int epilogue, int splits, hipStream_t s
 #endif
 
 namespace {
-template <bool TN, int EPI, bool F6, bool NTCS = false, bool R6 = false, bool NARROW = false>
+template <class V>
 int launch_x3_1(const BArgs &g, int blocks, int splits, hipStream_t s) {
-  static bool configured = false;
-  constexpr int smem = R6 ? SMEM_R6 : SMEM;
-  if (!configured) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_gemm_bf16_256<TN, EPI, true, true, F6, NTCS, R6, NARROW>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    if (e != hipSuccess) return fail(CDML_E_HIP, "gemm_bf16x3: cannot reserve %d B of LDS: %s", smem, hipGetErrorString(e));
-    configured = true;
-  }
-  hipLaunchKernelGGL((k_gemm_bf16_256<TN, EPI, true, true, F6, NTCS, R6, NARROW>), dim3(blocks, splits), dim3(kT), smem, s, g);
-  return check_launch("gemm_bf16x3");
+  return launch_tiles<V>(g, blocks, splits, s, "gemm_bf16x3");
 }
 // The last round of a plane-output product in HALF TILES: a launch of T tiles runs T / 256 full rounds of the 256 CUs and
 // then a round with T % 256 of them busy (FC1 and the data gradient at config 1: 640 tiles, the third round on half the
 // chip).  When that remainder fits the chip twice, its tiles are computed by a second launch as two 128 x 256 halves
 // each -- same operands, same K order per output element (bit-identical results), twice the CUs at a little over half a
-// tile's time each.  CDML_X3_HALFTILES=0 turns it off (A/B timing); read per call.
-bool x3_half_tiles() {
+// tile's time each.  CDML_X3_HALFTILES=0 turns it off, =2 runs the half tiles as a launch of their own behind the full
+// tiles' (A/B timing); read per call.
+int x3_half_tiles_mode() {
   const char *e = getenv("CDML_X3_HALFTILES");
-  return !e || atoi(e) != 0;
+  return e ? atoi(e) : 1;
 }
-// CDML_X3_HALFTILES=2: the half tiles as a launch of their own behind the full tiles' (A/B timing)
-bool x3_one_launch() {
-  const char *e = getenv("CDML_X3_HALFTILES");
-  return !e || atoi(e) != 2;
-}
+bool x3_half_tiles() { return x3_half_tiles_mode() != 0; }
+bool x3_one_launch() { return x3_half_tiles_mode() != 2; }
 // which K loop walks the six plane products: CDML_X3_WALK = "r6" (default: the resident-plane walk, both forms),
 // "f6" (round 3's unrolled six-step period with DMA skipping; k-contiguous form only), "general" (round 3's general loop);
 // read per call so that one process can time them against each other
@@ -2045,15 +1800,15 @@ int launch_x3(const BArgs &g, int splits, hipStream_t s) {
   // CDML_X3_WALK=general: the general K-major loop (A/B runs; read per call)
   const int kt3 = g.K / kTileK, per3 = g.k_per_split / kTileK;
   const bool whole3 = g.x3_products == 3 && kt3 % 3 == 0 && per3 % 3 == 0 && per3 > 0;
-  if (whole3 && x3_walk() == 2) return launch_x3_1<TN, EPI, false, false, true>(g, g.tiles_m * g.tiles_n, splits, s);
-  return launch_x3_1<TN, EPI, false>(g, g.tiles_m * g.tiles_n, splits, s);
+  if (whole3 && x3_walk() == 2) return launch_x3_1<X3Resident<TN, EPI>>(g, g.tiles_m * g.tiles_n, splits, s);
+  return launch_x3_1<X3General<TN, EPI>>(g, g.tiles_m * g.tiles_n, splits, s);
 #else
   const int kt = g.K / kTileK, per = g.k_per_split / kTileK;
   const bool whole = g.x3_products == 6 && kt % 6 == 0 && per % 6 == 0 && per > 0;
   const int walk = whole ? x3_walk() : 0;
   if constexpr (!TN && EPI == BE_F32) {   // the weight gradients of the transposed activation layout: with the column sums
     // (the general loop: round 3's unrolled period plus the sums was 14 VGPRs over the budget)
-    if (g.colsum_partial) return launch_x3_1<TN, EPI, false, true>(g, g.tiles_m * g.tiles_n, splits, s);
+    if (g.colsum_partial) return launch_x3_1<X3GeneralColsum<EPI>>(g, g.tiles_m * g.tiles_n, splits, s);
   }
   const int tiles = g.tiles_m * g.tiles_n;
   // (round 6: the unsplit fp32-output product too -- the trainable table's row gradient dz1 . W1^T is 384 tiles at 16 384 rows:
@@ -2068,21 +1823,13 @@ int launch_x3(const BArgs &g, int splits, hipStream_t s) {
         // CDML_X3_STAGGER=1 (A/B, read per call): half of the half-tile blocks go first
         const char *st = getenv("CDML_X3_STAGGER");
         if (st && atoi(st) != 0 && full + rem >= kNumCU && rem % 8 == 0) h.stagger_lead = rem;
-        static bool configured = false;
-        if (!configured) {
-          hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_gemm_x3_rounds<EPI>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_R6);
-          if (e != hipSuccess) return fail(CDML_E_HIP, "gemm_bf16x3: cannot reserve %d B of LDS: %s", SMEM_R6, hipGetErrorString(e));
-          configured = true;
-        }
-        hipLaunchKernelGGL((k_gemm_x3_rounds<EPI>), dim3(full + 2 * rem), dim3(kT), SMEM_R6, s, h);
-        return check_launch("gemm_bf16x3");
+        return launch_kernel<&k_gemm_x3_rounds<EPI>>(dim3(full + 2 * rem), SMEM_R6, s, h, "gemm_bf16x3");
       }
       if (full > 0) {
-        const int rc = launch_x3_1<TN, EPI, false, false, true>(h, full, 1, s);
+        const int rc = launch_x3_1<X3Resident<TN, EPI>>(h, full, 1, s);
         if (rc) return rc;
       }
-      return launch_x3_1<TN, EPI, false, false, true, true>(h, 2 * rem, 1, s);
+      return launch_x3_1<X3ResidentHalf<EPI>>(h, 2 * rem, 1, s);
     }
   }
   if constexpr (!TN && EPI == BE_F32) {
@@ -2093,15 +1840,15 @@ int launch_x3(const BArgs &g, int splits, hipStream_t s) {
       BArgs h = g;
       h.grid_tiles = tiles;
       h.narrow_first = 0;
-      return launch_x3_1<TN, EPI, false, false, true, true>(h, 2 * tiles, splits, s);
+      return launch_x3_1<X3ResidentHalf<EPI>>(h, 2 * tiles, splits, s);
     }
   }
-  if (walk == 2) return launch_x3_1<TN, EPI, false, false, true>(g, tiles, splits, s);
+  if (walk == 2) return launch_x3_1<X3Resident<TN, EPI>>(g, tiles, splits, s);
   if constexpr (!TN) {
     // (round 3: the k-strided form did not fit the F6 period into 256 VGPRs -- 58 spilled, 2.4 x slower)
-    if (walk == 1) return launch_x3_1<TN, EPI, true>(g, tiles, splits, s);
+    if (walk == 1) return launch_x3_1<X3SixStep<EPI>>(g, tiles, splits, s);
   }
-  return launch_x3_1<TN, EPI, false>(g, tiles, splits, s);
+  return launch_x3_1<X3General<TN, EPI>>(g, tiles, splits, s);
 #endif
 }
 }  // namespace
@@ -2110,13 +1857,13 @@ int launch_x3(const BArgs &g, int splits, hipStream_t s) {
 // the score products whose epilogue is the selection (semi-hard mining) / the threshold filter (kNN export), on fp16 planes:
 // three products, the three-step resident-plane walk (K = D: whole periods always)
 int launch_gemm_f16x2_mine(const BArgs &g, hipStream_t s) {
-  return launch_x3_1<false, BE_MINE_X3, false, false, true>(g, g.tiles_m * g.tiles_n, 1, s);
+  return launch_x3_1<X3Mine>(g, g.tiles_m * g.tiles_n, 1, s);
 }
 int launch_gemm_f16x2_knn(const BArgs &g, hipStream_t s) {
-  return launch_x3_1<false, BE_KNN_X3, false, false, true>(g, g.tiles_m * g.tiles_n, 1, s);
+  return launch_x3_1<X3Knn>(g, g.tiles_m * g.tiles_n, 1, s);
 }
 int launch_gemm_f16x2_rank(const BArgs &g, hipStream_t s) {
-  return launch_x3_1<false, BE_RANK_X3, false, false, true>(g, g.tiles_m * g.tiles_n, 1, s);
+  return launch_x3_1<X3Rank>(g, g.tiles_m * g.tiles_n, 1, s);
 }
 int launch_gemm_f16x2_256(const BArgs &g, bool tn, int epilogue, int splits, hipStream_t s) {
   if (tn) return launch_x3<true, BE_F32>(g, splits, s);
@@ -2130,42 +1877,24 @@ int launch_gemm_f16x2_256(const BArgs &g, bool tn, int epilogue, int splits, hip
 #else
 // the k-strided product on k8-interleaved operands (resident-plane walk, six products, whole periods per split)
 int launch_gemm_x3_tnk(const BArgs &g, int splits, hipStream_t s) {
-  static bool configured = false;
-  if (!configured) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_gemm_bf16_256<true, BE_F32, true, true, false, false, true, false, true>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_R6);
-    if (e != hipSuccess) return fail(CDML_E_HIP, "gemm_bf16x3_tnk: cannot reserve %d B of LDS: %s", SMEM_R6, hipGetErrorString(e));
-    configured = true;
-  }
-  hipLaunchKernelGGL((k_gemm_bf16_256<true, BE_F32, true, true, false, false, true, false, true>), dim3(g.tiles_m * g.tiles_n, splits),
-                     dim3(kT), SMEM_R6, s, g);
-  return check_launch("gemm_bf16x3_tnk");
+  return launch_tiles<X3ResidentK8>(g, g.tiles_m * g.tiles_n, splits, s, "gemm_bf16x3_tnk");
 }
 
 // the k-strided product with ONLY B k8-interleaved, B as the wide operand of a wave's tile (64 x 128: run_tile's WIDEB)
 int launch_gemm_x3_tnkb(const BArgs &g, int splits, hipStream_t s) {
-  static bool configured = false;
-  if (!configured) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_gemm_bf16_256<true, BE_F32, true, true, false, false, true, false, false, true>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_R6);
-    if (e != hipSuccess) return fail(CDML_E_HIP, "gemm_bf16x3_tn_kb: cannot reserve %d B of LDS: %s", SMEM_R6, hipGetErrorString(e));
-    configured = true;
-  }
-  hipLaunchKernelGGL((k_gemm_bf16_256<true, BE_F32, true, true, false, false, true, false, false, true>), dim3(g.tiles_m * g.tiles_n, splits),
-                     dim3(kT), SMEM_R6, s, g);
-  return check_launch("gemm_bf16x3_tn_kb");
+  return launch_tiles<X3ResidentWideB>(g, g.tiles_m * g.tiles_n, splits, s, "gemm_bf16x3_tn_kb");
 }
 
 int launch_gemm_x3_mine(const BArgs &g, hipStream_t s) {
-  return launch_x3_1<false, BE_MINE_X3, false, false, true>(g, g.tiles_m * g.tiles_n, 1, s);
+  return launch_x3_1<X3Mine>(g, g.tiles_m * g.tiles_n, 1, s);
 }
 
 int launch_gemm_x3_knn(const BArgs &g, hipStream_t s) {
-  return launch_x3_1<false, BE_KNN_X3, false, false, true>(g, g.tiles_m * g.tiles_n, 1, s);
+  return launch_x3_1<X3Knn>(g, g.tiles_m * g.tiles_n, 1, s);
 }
 
 int launch_gemm_x3_rank(const BArgs &g, hipStream_t s) {
-  return launch_x3_1<false, BE_RANK_X3, false, false, true>(g, g.tiles_m * g.tiles_n, 1, s);
+  return launch_x3_1<X3Rank>(g, g.tiles_m * g.tiles_n, 1, s);
 }
 
 int launch_gemm_bf16_256_x3(const BArgs &g, bool tn, int epilogue, int splits, hipStream_t s) {
@@ -2227,18 +1956,9 @@ int launch_gemm_bf16_tn2(const BArgs &g1, const BArgs &g2, float *db1, float *db
   a.tiles0 = q.tiles0; a.upt = q.upt; a.total_units = q.total; a.units_per_block = q.U; a.lcm_units = q.lcm;
   a.partials = static_cast<float *>(workspace);
   a.cs_partials = (db1 || db2) ? a.partials + (size_t)q.slots * (kTileM * kTileN) : nullptr;
-  const bool s16 = shape16();
-  static bool configured[2] = {false, false};
-  if (!configured[s16]) {
-    const void *fn = s16 ? reinterpret_cast<const void *>(&k_gemm_bf16_sk<true>) : reinterpret_cast<const void *>(&k_gemm_bf16_sk<false>);
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-    if (e != hipSuccess) return fail(CDML_E_HIP, "gemm_bf16_tn2: cannot reserve %d B of LDS: %s", SMEM, hipGetErrorString(e));
-    configured[s16] = true;
-  }
   const int blocks = (q.total + q.U - 1) / q.U;
-  if (s16) hipLaunchKernelGGL((k_gemm_bf16_sk<true>), dim3(blocks), dim3(kT), SMEM, s, a);
-  else hipLaunchKernelGGL((k_gemm_bf16_sk<false>), dim3(blocks), dim3(kT), SMEM, s, a);
-  int rc = check_launch("gemm_bf16_tn2");
+  int rc = shape16() ? launch_kernel<&k_gemm_bf16_sk<true>>(dim3(blocks), SMEM, s, a, "gemm_bf16_tn2")
+                     : launch_kernel<&k_gemm_bf16_sk<false>>(dim3(blocks), SMEM, s, a, "gemm_bf16_tn2");
   if (rc) return rc;
   const int n_tiles = q.tiles0 + q.tiles1;
   const int cs_blocks = a.cs_partials ? a.p[0].tiles_n + a.p[1].tiles_n : 0;

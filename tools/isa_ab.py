@@ -1,0 +1,146 @@
+#!/usr/bin/env python3
+"""Proof that a source-only change of the tile GEMM kernels is only a change of the source: compile csrc/gemm_bf16_256.hip
+and csrc/gemm_f16x2_256.hip of two trees to gfx950 assembly with build()'s flags and compare the kernels' machine code.
+
+    python tools/isa_ab.py                 # the parent commit (a temporary git worktree of HEAD~) against the working tree
+    python tools/isa_ab.py --rev HEAD      # the last commit against uncommitted edits
+    python tools/isa_ab.py --a DIR --b DIR # two checked-out trees
+
+A kernel is its instructions plus its .amdhsa_kernel descriptor block (registers, LDS, scratch).  What may differ without
+the code differing is canonicalised: the kernel's own mangled name, the __hip_cuid_* symbol, comments, and the function
+number inside .LBB<n>_<m> / .Lfunc_end<n> labels.  The two trees are compared as MULTISETS of kernel bodies -- a refactor
+may rename template arguments, so names are reported and not matched.  Host tool: no GPU.  Exit status 0 = every kernel
+identical and the counts equal."""
+import argparse
+import collections
+import difflib
+import hashlib
+import os
+import re
+import subprocess
+import sys
+import tempfile
+from concurrent.futures import ThreadPoolExecutor
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = "collaborative-deep-metric-learning_amd"
+SOURCES = ("gemm_bf16_256.hip", "gemm_f16x2_256.hip")
+
+Kernel = collections.namedtuple("Kernel", "name body n_instr")
+
+
+def canonical(lines, name):
+    """The lines of one kernel with everything that may legitimately differ taken out."""
+    out = []
+    for ln in lines:
+        ln = ln.split(";", 1)[0].replace(name, "@KERNEL")
+        ln = re.sub(r"__hip_cuid_\w+", "__hip_cuid", ln)
+        ln = re.sub(r"\.(LBB|Lfunc_end|Lfunc_begin|LJTI)\d+", r".\1", ln)
+        ln = " ".join(ln.split())
+        if ln:
+            out.append(ln)
+    return out
+
+
+def kernels(asm):
+    """Cut a device assembly file into kernels: from the kernel's label to the end of its descriptor block."""
+    lines = asm.splitlines()
+    found = []
+    for i, ln in enumerate(lines):
+        m = re.match(r"\s*\.amdhsa_kernel\s+(\S+)", ln)
+        if not m:
+            continue
+        name = m.group(1)
+        start = max(j for j in range(i) if lines[j].split(";", 1)[0].strip() == name + ":")
+        end = next(j for j in range(i, len(lines)) if lines[j].strip() == ".end_amdhsa_kernel")
+        body = canonical(lines[start:end + 1], name)
+        code = body[:body.index(".amdhsa_kernel @KERNEL")]
+        n_instr = sum(1 for c in code if not c.startswith(".") and not c.endswith(":"))
+        found.append(Kernel(name, "\n".join(body), n_instr))
+    return found
+
+
+def compare(a, b):
+    """(report lines, ok) for two lists of Kernel compared as multisets of bodies."""
+    rest = collections.defaultdict(list)
+    for k in b:
+        rest[k.body].append(k)
+    report, ok = [], len(a) == len(b)
+    unmatched = []
+    for k in a:
+        if rest[k.body]:
+            o = rest[k.body].pop(0)
+            report.append("identical  %6d instr  %s  ==  %s" % (k.n_instr, k.name, o.name))
+        else:
+            unmatched.append(k)
+    left = [o for ks in rest.values() for o in ks]
+    for k in unmatched:                                    # pair the leftovers for the report by the likeness of their names
+        o = max(left, key=lambda x: difflib.SequenceMatcher(None, k.name, x.name).ratio(), default=None)
+        if o is not None:
+            left.remove(o)
+        report.append("DIFFERS    %6d instr  %s  !=  %s" % (k.n_instr, k.name, "%s (%d instr)" % (o.name, o.n_instr) if o else "(missing)"))
+        ok = False
+    for o in left:
+        report.append("DIFFERS    %6d instr  (missing)  !=  %s" % (o.n_instr, o.name))
+        ok = False
+    if len(a) != len(b):
+        report.append("kernel counts differ: %d against %d" % (len(a), len(b)))
+    return report, ok
+
+
+def build_flags():
+    sys.path.insert(0, ROOT)
+    import __graft_entry__
+    return list(__graft_entry__.HIPCC_FLAGS)
+
+
+def assemble(tree, src, flags, out):
+    csrc = os.path.join(tree, PKG, "csrc")
+    cmd = [os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")] + flags + ["-I" + csrc, "--cuda-device-only", "-S", "-o", out, src]
+    r = subprocess.run(cmd, cwd=csrc, stderr=subprocess.PIPE, text=True)
+    if r.returncode:
+        sys.stderr.write("\n".join(ln for ln in r.stderr.splitlines() if "error" in ln)[-4000:] + "\n")
+        raise RuntimeError("hipcc failed: " + " ".join(cmd))
+    return open(out).read()
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--rev", default="HEAD~", help="revision checked out as tree A when --a is not given")
+    ap.add_argument("--a", help="tree A (a checkout of the repository)")
+    ap.add_argument("--b", default=ROOT, help="tree B (default: the working tree)")
+    args = ap.parse_args()
+    flags = build_flags()
+    ok = True
+    with tempfile.TemporaryDirectory() as tmp:
+        a = args.a
+        if a is None:
+            a = os.path.join(tmp, "a")
+            subprocess.run(["git", "-C", ROOT, "worktree", "add", "--detach", "--force", a, args.rev], check=True,
+                           stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+        try:
+            jobs = [(side, tree, src) for src in SOURCES for side, tree in (("a", a), ("b", args.b))]
+            with ThreadPoolExecutor(max_workers=len(jobs)) as ex:
+                asm = dict(zip([(j[0], j[2]) for j in jobs],
+                               ex.map(lambda j: assemble(j[1], j[2], flags, os.path.join(tmp, j[0] + "_" + j[2] + ".s")), jobs)))
+        finally:
+            if args.a is None:
+                subprocess.run(["git", "-C", ROOT, "worktree", "remove", "--force", a], check=False)
+    print("A = %s, B = %s; flags: %s" % (args.a or args.rev, os.path.relpath(args.b, ROOT) if args.b != ROOT else "working tree",
+                                         " ".join(flags)))
+    for src in SOURCES:
+        ka, kb = kernels(asm[("a", src)]), kernels(asm[("b", src)])
+        report, same = compare(ka, kb)
+        ok = ok and same
+        print("%s: %d kernels against %d, %d instructions against %d, sha256 of the canonical bodies %s / %s" % (
+            src, len(ka), len(kb), sum(k.n_instr for k in ka), sum(k.n_instr for k in kb),
+            hashlib.sha256("\n".join(sorted(k.body for k in ka)).encode()).hexdigest()[:16],
+            hashlib.sha256("\n".join(sorted(k.body for k in kb)).encode()).hexdigest()[:16]))
+        for ln in report:
+            print("  " + ln)
+    print("RESULT: %s" % ("every kernel identical" if ok else "DIFFERENCES"))
+    return 0 if ok else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())
