@@ -5,6 +5,7 @@
 #include <stdio.h>
 #include <stdarg.h>
 #include "../../include/cdml.h"
+#include "gemm_plan.h"
 
 namespace cdml {
 
@@ -28,6 +29,7 @@ inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 
 
 constexpr int kWave = 64;
 constexpr int kNumCU = 256;
+static_assert(kPlanNumCU == kNumCU, "gemm_plan.h plans for this chip's CU count");
 
 // ---- device helpers -----------------------------------------------------------
 // Sum of squares of one 16-B chunk (8 halfs) of an fp16 catalogue row, elements at or past F zeroed IN the chunk (the pad is

@@ -97,7 +97,7 @@ struct BArgs {
 // 256x256x64 kernel: true if the shape can use it (N % 256 == 0, K per split a
 // multiple of 128, operands inside the 2 GiB buffer-descriptor window).
 bool gemm_bf16_256_usable(int M, int N, int K, int64_t lda, int64_t ldb);
-int gemm_bf16_256_splits(int M, int N, int K);
+// (its split-K rule, gemm_bf16_256_splits, and every entry's K-split plan: gemm_plan.h)
 // g.tiles_m / g.tiles_n / g.k_per_split / g.C (slabs when splits > 1) set by the caller
 int launch_gemm_bf16_256(const BArgs &g, int epilogue, int splits, hipStream_t stream);
 // the split-fp32 forms (g.x3_* set; epilogues 1, 3, 6, 7 k-contiguous, 3 k-strided)

@@ -543,10 +543,7 @@ extern "C" int cdml_gemm_bf16_tn_supported(int M, int N, int K, int64_t lda, int
 
 extern "C" size_t cdml_gemm_bf16_tn_workspace(int M, int N, int K) {
   if (M <= 0 || N <= 0 || K <= 0) return 0;
-  const int splits = gemm_bf16_256_splits(M, N, K);
-  const size_t slabs = splits > 1 ? (size_t)splits * M * N : 0;
-  const size_t partials = (size_t)splits * ((M + 255) / 256) * 2 * N;    // column sums of B
-  return (slabs + partials) * sizeof(float);
+  return bf16_tn_plan(M, N, K, true).need;                  // slabs + the column sums of B
 }
 
 extern "C" int cdml_gemm_bf16_tn(const uint16_t *A, int64_t lda, const uint16_t *B, int64_t ldb, int M,
@@ -565,26 +562,23 @@ extern "C" int cdml_gemm_bf16_tn(const uint16_t *A, int64_t lda, const uint16_t 
   g.C = C; g.ldc = ldc;
   g.M = M; g.N = N; g.K = K; g.k_per_split = K;
   g.tiles_m = M / 256; g.tiles_n = N / 256;
-  const int splits = gemm_bf16_256_splits(M, N, K);
+  const KSplitPlan p = bf16_tn_plan(M, N, K, colsum != nullptr);
+  const int chunks = (int)p.cs_rows;
   hipStream_t s = (hipStream_t)stream;
-  const size_t slab_floats = splits > 1 ? (size_t)splits * M * N : 0;
-  const int chunks = splits * g.tiles_m * 2;
-  const size_t need = (slab_floats + (colsum ? (size_t)chunks * N : 0)) * sizeof(float);
-  CDML_REQUIRE(need == 0 || (workspace && workspace_bytes >= need && aligned16(workspace)), CDML_E_BADARG,
-               "gemm_bf16_tn: workspace of %zu bytes required", need);
-  if (splits > 1) {
-    const int kps = (K + splits - 1) / splits;
-    g.k_per_split = (kps + 127) / 128 * 128;
+  CDML_REQUIRE(p.need == 0 || (workspace && workspace_bytes >= p.need && aligned16(workspace)), CDML_E_BADARG,
+               "gemm_bf16_tn: workspace of %zu bytes required", p.need);
+  if (p.slabs) {
+    g.k_per_split = p.per * 64;
     g.slab_stride = (int64_t)M * N;
     g.C = workspace; g.ldc = N;
   }
-  if (colsum) g.colsum_partial = static_cast<float *>(workspace) + slab_floats;
-  int rc = launch_gemm_bf16_tn(g, splits, s);
+  if (colsum) g.colsum_partial = reinterpret_cast<float *>(static_cast<char *>(workspace) + p.slab_bytes);
+  int rc = launch_gemm_bf16_tn(g, p.splits, s);
   if (rc) return rc;
-  if (splits > 1) {                                        // the slab sum and, in extra blocks, the bias gradient's final sums
+  if (p.slabs) {                                           // the slab sum and, in extra blocks, the bias gradient's final sums
     const int sb = grid1d((int64_t)M * N / 4, 1), cb = colsum ? colsum_final_blocks(chunks, N) : 0;
     hipLaunchKernelGGL(k_sum_slabs_f32, dim3(sb + cb), dim3(kThreads), 0, s, static_cast<const float *>(workspace), g.slab_stride,
-                       splits, M, N, C, ldc, sb, g.colsum_partial, chunks, colsum, (cb * 32 >= N) ? 1 : 0);
+                       p.splits, M, N, C, ldc, sb, g.colsum_partial, chunks, colsum, (cb * 32 >= N) ? 1 : 0);
     return check_launch("gemm_bf16_tn combine");
   }
   if (colsum) {

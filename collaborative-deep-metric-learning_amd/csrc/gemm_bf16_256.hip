@@ -1743,21 +1743,6 @@ bool gemm_bf16_256_usable(int M, int N, int K, int64_t lda, int64_t ldb) {
   return ((int64_t)M + kTileM) * lda * 2 < lim && (int64_t)N * ldb * 2 < lim;
 }
 
-// split-K for the skinny weight gradients: fill one round of 256 CUs as evenly as
-// possible with the fewest slabs
-int gemm_bf16_256_splits(int M, int N, int K) {
-  const int64_t tiles = (int64_t)((M + kTileM - 1) / kTileM) * (N / kTileN);
-  const int max_by_k = K / 1024 > 0 ? K / 1024 : 1;
-  int best = 1;
-  double best_eff = 0.0;
-  for (int s = 1; s <= 16 && s <= max_by_k; ++s) {
-    const int64_t blocks = tiles * s;
-    const double eff = (double)blocks / (double)(((blocks + kNumCU - 1) / kNumCU) * kNumCU);
-    if (eff > best_eff + 0.02) { best_eff = eff; best = s; }
-  }
-  return best;
-}
-
 int launch_gemm_bf16_256(const BArgs &g, int epilogue, int splits, hipStream_t s) {
   switch (epilogue) {
     case BE_BIAS_LRELU_BF16: return launch<false, BE_BIAS_LRELU_BF16>(g, splits, s);

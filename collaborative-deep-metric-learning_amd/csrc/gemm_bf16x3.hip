@@ -145,50 +145,12 @@ bool x3_kmajor() {
   return !(e && e[0] == 'p');
 }
 
-// split-K for the k-contiguous forms whose output is ONE tile column wide (N = 256: the narrow forward layer, whose
-// M / 256 tiles alone would leave most of the chip idle; fp32 slab output only).  The K partition is a function of K
-// ALONE -- slabs of twenty six-step periods (120 K-tile steps), at most 16 of them, summed in slab order by k_x3_sum_slabs
-// -- so the result does not depend on how many rows the call carries: a batch computed whole and the same batch computed
-// in row blocks (two ranks against one) give the same bits.  (Round 3 chose the slab count from the tile count: 8
-// slabs at 8 192 rows, none at 49 152, and leaky-relu' flips near zero then loosened the two-rank gradient bound.)
-// Round 5: 120 steps instead of 60 -- four slabs at K = 5 120 -- which halves the slab round trip (the forward layer at
-// 16 384 rows: 64 tiles x 4 slabs = one round of the chip instead of two rounds of half-length blocks); where four slabs
-// leave the chip under-filled (8 192 rows: 128 blocks) the SAME slabs run as 128 x 256 half tiles (gemm_bf16_256.hip),
-// so the partition stays a function of K alone.
-// Wider outputs are never split: their tiles fill the chip at every batch size the step uses.
-// Round 6: the slab length is a function of K and of the ROW-TILE CLASS.  The 120-step slabs were chosen for BASELINE's
-// batches; the reference's own recipe (B = 1 024: 3 072 rows = 12 row tiles) fills 96 half-tile blocks with them and ran
-// 0.622 against 0.643 ms/step with 60-step slabs (profiles/r05_reference_recipe_slab_steps_ab.txt).  Rule: where the
-// 120-step slabs give at most 64 full tiles (128 half-tile blocks: half the chip) the slabs are 60 steps long -- twice the
-// blocks -- else 120.  Within a class the partition is still a function of K alone (a batch whole or in row blocks of the
-// same class: the same bits); ACROSS the class boundary the last bits of z differ.  A caller that needs one partition for
-// every call size pins it: cdml_x3_slab_steps(120) (thread-local; catalogue inference does, so an embedding has the same
-// bits in 4 096- and 49 152-row chunks: test_embedding_bits_do_not_depend_on_the_chunk).
-thread_local int tl_slab_steps = 0;                        // 0 = by class
-// (half_steps: the two-plane fp16 form walks THREE steps per K-tile where the bf16 form walks six -- its slabs are half as
-// many steps long, so that the partition of K itself is the same: 20 or 10 K-tiles of every plane per slab)
-int x3_nt_splits(int N, int ktiles, int tiles_m, bool half_steps = false) {
-  if (N / 256 != 1) return 1;
-  if (half_steps) ktiles *= 2;
-  const char *e = getenv("CDML_X3_SLAB_STEPS");            // (A/B runs: one length for everything)
-  int steps = e && atoi(e) >= 12 ? atoi(e) / 6 * 6 : tl_slab_steps;
-  if (steps < 12) {
-    int s120 = ktiles / 120;
-    s120 = s120 < 1 ? 1 : (s120 > 16 ? 16 : s120);
-    steps = tiles_m * s120 <= 64 ? 60 : 120;
-  }
-  const int s = ktiles / steps;
-  return s < 1 ? 1 : (s > 16 ? 16 : s);
-}
-
-// K-tile steps per split, rounded up to whole walk periods (`period` = 6 for the six-product K-major walk, else 2), and
-// the number of splits that then actually carry K-tiles: rounding `per` up can leave the last of the requested splits
-// empty (ktiles = 288 in 11 splits: per = 30, ten splits cover it) -- an empty split would still launch its blocks, write
-// a zero slab and be read back by the combine pass
-void x3_split_geometry(int ktiles, int requested, int period, int &per, int &splits) {
-  per = (ktiles + requested - 1) / requested;
-  per = (per + period - 1) / period * period;
-  splits = (ktiles + per - 1) / per;
+// the K-slab length of the narrow k-contiguous layer (gemm_plan.h, x3_nt_splits): CDML_X3_SLAB_STEPS (A/B runs: one length
+// for everything; read per call), else the thread's pin (cdml_x3_slab_steps), else 0 = by row-tile class
+thread_local int tl_slab_steps = 0;
+int x3_slab_steps() {
+  const char *e = getenv("CDML_X3_SLAB_STEPS");
+  return e && atoi(e) >= 12 ? atoi(e) / 6 * 6 : tl_slab_steps;
 }
 
 }  // namespace
@@ -244,21 +206,9 @@ extern "C" int cdml_x3_slab_steps(int steps) {
   return prev;
 }
 
+// (k-contiguous form: a workspace serves any pin of cdml_x3_slab_steps -- and the one in force)
 extern "C" size_t cdml_gemm_bf16x3_workspace(int tn, int M, int N, int K, int products) {
-  if (M <= 0 || N <= 0 || K <= 0 || (products != 3 && products != 6) || K % 64) return 0;
-  const int ktiles = products * (K / 64);
-  // (k-contiguous form: the larger of the two slab lengths' counts -- a workspace serves any pin of cdml_x3_slab_steps)
-  int requested = tn ? gemm_bf16_256_splits(M, N, ktiles * 64) : x3_nt_splits(N, ktiles, (M + 255) / 256);
-  if (!tn && N / 256 == 1) {
-    const int s60 = ktiles / 60 < 1 ? 1 : (ktiles / 60 > 16 ? 16 : ktiles / 60);
-    if (s60 > requested) requested = s60;
-  }
-  int splits = requested, per = 0, s2 = requested;
-  x3_split_geometry(ktiles, requested, products == 6 ? 6 : 2, per, splits);
-  x3_split_geometry(ktiles, requested, 2, per, s2);          // (the product-major A/B walk rounds to pairs: never fewer slabs)
-  if (s2 > splits) splits = s2;
-  const size_t cs = (size_t)splits * ((M + 255) / 256) * 2 * N * sizeof(float) + (size_t)N * sizeof(float);   // bias-gradient partials
-  return (size_t)splits * M * N * sizeof(float) + cs;       // (a slab even unsplit: the k-strided form's bias pass reads one)
+  return x3_workspace_bytes(tn, M, N, K, products, tn ? 0 : x3_slab_steps());
 }
 
 // workspace of cdml_gemm_f16x2_nt / _tn: its slabs partition K as the six-product form's do (k-contiguous form) or as the
@@ -323,6 +273,36 @@ k_x3_sum_slabs(const float *__restrict__ slabs, int64_t slab_stride, int splits,
     reinterpret_cast<f32x4 *>(out + r * ldo)[c] = s;
   }
 }
+
+// THE launch of k_x3_sum_slabs for a planned product (g.M / N / slab_stride / colsum_partial set): `slabs` != null: the plan's
+// slabs summed (+ bias, leaky-relu when bias != null) into C; colsum != null: cs_scale times the column sums, in extra blocks
+int x3_sum_slabs(const char *entry, const char *stage, const BArgs &g, const KSplitPlan &p, const void *slabs, const float *bias,
+                 float alpha, float *C, int64_t ldc, float *colsum, float cs_scale, hipStream_t s) {
+  const int sb = slabs ? grid1d((int64_t)g.M * g.N / 4) : 0, cb = colsum ? (g.N + 15) / 16 : 0;
+  hipLaunchKernelGGL(k_x3_sum_slabs, dim3(sb + cb), dim3(kThreads), 0, s, static_cast<const float *>(slabs), g.slab_stride,
+                     p.splits, g.M, g.N, bias, alpha, C, ldc, sb, g.colsum_partial, (int)p.cs_rows, colsum, cs_scale);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? CDML_OK : fail(CDML_E_HIP, "%s %s: %s", entry, stage, hipGetErrorString(e));
+}
+
+// A k-strided product from its plan: g holds the operands (A, B, M, N, x3_*, scales); the workspace check, the slab / colsum
+// fields of g, `launch` (the kernel family of the entry) and the combine pass are the same for every entry -- which is what
+// makes cdml_gemm_bf16x3_tn, _tnk and _tn_kb bit-identical
+int x3_run_tn(const char *entry, BArgs &g, const KSplitPlan &p, int (*launch)(const BArgs &, int, hipStream_t), float *C, int64_t ldc,
+              const float *bias, float alpha, float *colsum, float cs_scale, void *workspace, size_t workspace_bytes, hipStream_t s) {
+  CDML_REQUIRE(p.need == 0 || (workspace && workspace_bytes >= p.need && aligned16(workspace)), CDML_E_BADARG,
+               "%s: workspace of %zu bytes required (cdml_gemm_bf16x3_workspace)", entry, p.need);
+  g.K = p.ktiles * 64;
+  g.tiles_m = g.M / 256; g.tiles_n = g.N / 256;
+  g.k_per_split = p.per * 64;
+  g.slab_stride = (int64_t)g.M * g.N;
+  g.C = p.slabs ? workspace : static_cast<void *>(C);
+  g.ldc = p.slabs ? g.N : ldc;
+  g.colsum_partial = colsum ? reinterpret_cast<float *>(static_cast<char *>(workspace) + p.slab_bytes) : nullptr;
+  const int rc = launch(g, p.splits, s);
+  if (rc || !(p.slabs || colsum)) return rc;
+  return x3_sum_slabs(entry, "combine", g, p, p.slabs ? workspace : nullptr, bias, alpha, C, ldc, colsum, cs_scale, s);
+}
 }  // namespace
 }  // namespace cdml
 
@@ -383,58 +363,37 @@ static int gemm_x3_nt_impl(bool f16, float out_scale, float c_scale, int epilogu
   g.x3_tpp = K / 64; g.x3_plane_a = plane_a; g.x3_plane_b = plane_b; g.x3_plane_c = plane_c;
   g.x3_products = (f16 || x3_kmajor()) ? products : 0;
   g.out_scale = out_scale; g.c_scale = c_scale;
-  const int ktiles = products * g.x3_tpp;
-  CDML_REQUIRE(ktiles % 2 == 0, CDML_E_UNSUPPORTED, "gemm_bf16x3_nt: products * K / 64 must be even");
-  g.K = ktiles * 64; g.k_per_split = g.K;
+  CDML_REQUIRE(products * g.x3_tpp % 2 == 0, CDML_E_UNSUPPORTED, "gemm_bf16x3_nt: products * K / 64 must be even");
+  // whole six-step periods of the K-major walk (and an even count; fp16 form: two K-tiles); no workspace: ONE pass over K
+  const KSplitPlan p = x3_plan_nt(M, N, K, products, f16, planes_out, colsum != nullptr, planes_out ? 0 : x3_slab_steps(), 6,
+                                  workspace != nullptr);
+  g.K = p.ktiles * 64; g.k_per_split = g.K;
   g.tiles_m = (M + 255) / 256; g.tiles_n = N / 256;
   hipStream_t s = (hipStream_t)stream;
   auto launch = [&](int epi, int n_splits) {
     return f16 ? launch_gemm_f16x2_256(g, false, epi, n_splits, s) : launch_gemm_bf16_256_x3(g, false, epi, n_splits, s);
   };
-  int splits = planes_out ? 1 : x3_nt_splits(N, ktiles, g.tiles_m, f16), per = ktiles;
-  if (splits > 1) x3_split_geometry(ktiles, splits, 6, per, splits);   // whole six-step periods of the K-major walk (and an even count; fp16 form: two K-tiles)
-  if (splits > 1) {
-    // The slab form needs the workspace.  workspace == NULL is the caller's explicit choice of ONE pass over K (fewer,
-    // longer blocks; no slab round trip) -- its sums are associated differently, so the result's last bits differ from
-    // the slab form's and the "same bits whole or in row blocks" property holds only among calls that all pass a workspace.
-    // A workspace that is given but too small is an error, not a silent change of arithmetic.
-    if (!workspace) {
-      splits = 1;
-    } else {
-      const size_t need = (size_t)splits * M * N * sizeof(float) + (colsum ? (size_t)splits * g.tiles_m * 2 * N * sizeof(float) : 0);
-      CDML_REQUIRE(workspace_bytes >= need && aligned16(workspace), CDML_E_BADARG,
-                   "gemm_bf16x3_nt: the slab form needs a 16-B aligned workspace of %zu bytes (cdml_gemm_bf16x3_workspace); pass "
-                   "NULL for the single-pass form", need);
-    }
-  }
-  const size_t slab_bytes = splits > 1 ? (size_t)splits * M * N * sizeof(float) : 0;
-  const size_t cs_rows = (size_t)splits * g.tiles_m * 2;
+  // A workspace that is given but too small is an error, not a silent change of arithmetic.
+  CDML_REQUIRE(!p.slabs || (workspace_bytes >= p.need && aligned16(workspace)), CDML_E_BADARG,
+               "gemm_bf16x3_nt: the slab form needs a 16-B aligned workspace of %zu bytes (cdml_gemm_bf16x3_workspace); pass "
+               "NULL for the single-pass form", p.need);
   if (colsum) {      // colsum[n] = sum_k B[n][k] (the bias gradient when B holds a transposed activation gradient)
-    CDML_REQUIRE(workspace && aligned16(workspace) && workspace_bytes >= slab_bytes + cs_rows * N * sizeof(float), CDML_E_BADARG,
+    CDML_REQUIRE(workspace && aligned16(workspace) && workspace_bytes >= p.need, CDML_E_BADARG,
                  "gemm_bf16x3_nt: colsum needs a workspace (cdml_gemm_bf16x3_workspace)");
-    g.colsum_partial = reinterpret_cast<float *>(static_cast<char *>(workspace) + slab_bytes);
+    g.colsum_partial = reinterpret_cast<float *>(static_cast<char *>(workspace) + p.slab_bytes);
   }
-  int rc;
-  if (splits == 1) {
-    rc = launch(epilogue, 1);
-  } else {
-    g.k_per_split = per * 64;
-    g.slab_stride = (int64_t)M * N;
-    g.C = workspace; g.ldc = N;
-    rc = launch(BE_F32, splits);                            // (fp16 form: the slabs are written times out_scale already)
-    if (rc) return rc;
-    const int sb = grid1d((int64_t)M * N / 4), cb = colsum ? (N + 15) / 16 : 0;
-    hipLaunchKernelGGL(k_x3_sum_slabs, dim3(sb + cb), dim3(kThreads), 0, s,
-                       static_cast<const float *>(workspace), g.slab_stride, splits, M, N,
-                       epilogue == BE_BIAS_LRELU_F32 ? bias : nullptr, alpha, static_cast<float *>(C), ldc, sb,
-                       g.colsum_partial, (int)cs_rows, colsum, 1.0f);
-    return check_launch("gemm_bf16x3_nt combine");
+  if (!p.slabs) {
+    const int rc = launch(epilogue, 1);
+    if (rc || !colsum) return rc;
+    return x3_sum_slabs("gemm_bf16x3_nt", "bias gradient", g, p, nullptr, nullptr, 0.f, nullptr, 0, colsum, 1.0f, s);
   }
-  if (rc || !colsum) return rc;
-  hipLaunchKernelGGL(k_x3_sum_slabs, dim3((N + 15) / 16), dim3(kThreads), 0, s, static_cast<const float *>(nullptr), (int64_t)0, 0, 0,
-                     N, static_cast<const float *>(nullptr), 0.f, static_cast<float *>(nullptr), (int64_t)0, 0, g.colsum_partial,
-                     (int)cs_rows, colsum, 1.0f);
-  return check_launch("gemm_bf16x3_nt bias gradient");
+  g.k_per_split = p.per * 64;
+  g.slab_stride = (int64_t)M * N;
+  g.C = workspace; g.ldc = N;
+  const int rc = launch(BE_F32, p.splits);                  // (fp16 form: the slabs are written times out_scale already)
+  if (rc) return rc;
+  return x3_sum_slabs("gemm_bf16x3_nt", "combine", g, p, workspace, epilogue == BE_BIAS_LRELU_F32 ? bias : nullptr, alpha,
+                      static_cast<float *>(C), ldc, colsum, 1.0f, s);
 }
 
 extern "C" int cdml_gemm_bf16x3_nt(int epilogue, const uint16_t *A, int64_t lda, int64_t plane_a, const uint16_t *B,
@@ -483,34 +442,10 @@ static int gemm_x3_tn_impl(bool f16, float out_scale, float cs_scale, const uint
   g.x3_tpp = K / 64; g.x3_plane_a = plane_a; g.x3_plane_b = plane_b;
   g.x3_products = (f16 || x3_kmajor()) ? products : 0;
   g.out_scale = out_scale; g.c_scale = 1.0f;
-  const int ktiles = products * g.x3_tpp;
-  g.K = ktiles * 64;
-  g.tiles_m = M / 256; g.tiles_n = N / 256;
-  int splits = gemm_bf16_256_splits(M, N, g.K), per = 0;
-  // whole six-step periods of the K-major walk per block (the unrolled loops need them); three products: an even count
-  // (the fp16 form: whole three-step periods, an even count for the general loop)
-  x3_split_geometry(ktiles, splits, ((products == 6 && g.x3_products == 6) || f16) ? 6 : 2, per, splits);
-  const bool slabs = splits > 1 || bias != nullptr;       // (bias + leaky-relu are applied by the combine pass)
-  const size_t slab_bytes = slabs ? (size_t)splits * M * N * sizeof(float) : 0;
-  const size_t cs_rows = (size_t)splits * g.tiles_m * 2;
-  const size_t need = slab_bytes + (colsum ? cs_rows * N * sizeof(float) : 0);
-  CDML_REQUIRE(need == 0 || (workspace && workspace_bytes >= need && aligned16(workspace)), CDML_E_BADARG,
-               "gemm_bf16x3_tn: workspace of %zu bytes required (cdml_gemm_bf16x3_workspace)", need);
-  hipStream_t s = (hipStream_t)stream;
-  g.k_per_split = per * 64;
-  g.slab_stride = (int64_t)M * N;
-  g.C = slabs ? workspace : static_cast<void *>(C);
-  g.ldc = slabs ? N : ldc;
-  g.colsum_partial = colsum ? reinterpret_cast<float *>(static_cast<char *>(workspace) + slab_bytes) : nullptr;
-  int rc = f16 ? launch_gemm_f16x2_256(g, true, BE_F32, splits, s) : launch_gemm_bf16_256_x3(g, true, BE_F32, splits, s);
-  if (rc) return rc;
-  if (slabs || colsum) {                                   // one launch: the slab sum and, in extra blocks, the bias gradient
-    const int sb = slabs ? grid1d((int64_t)M * N / 4) : 0, cb = colsum ? (N + 15) / 16 : 0;
-    hipLaunchKernelGGL(k_x3_sum_slabs, dim3(sb + cb), dim3(kThreads), 0, s, static_cast<const float *>(workspace), g.slab_stride,
-                       splits, M, N, bias, alpha, C, ldc, sb, g.colsum_partial, (int)cs_rows, colsum, cs_scale);
-    rc = check_launch("gemm_bf16x3_tn combine");
-  }
-  return rc;
+  const KSplitPlan p = x3_plan_tn(M, N, K, products, x3_tn_period(products, g.x3_products != 0, f16), bias != nullptr, colsum != nullptr);
+  const auto launch = f16 ? +[](const BArgs &a, int splits, hipStream_t s) { return launch_gemm_f16x2_256(a, true, BE_F32, splits, s); }
+                          : +[](const BArgs &a, int splits, hipStream_t s) { return launch_gemm_bf16_256_x3(a, true, BE_F32, splits, s); };
+  return x3_run_tn("gemm_bf16x3_tn", g, p, launch, C, ldc, bias, alpha, colsum, cs_scale, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 extern "C" int cdml_gemm_bf16x3_tn(const uint16_t *A, int64_t lda, int64_t plane_a, const uint16_t *B, int64_t ldb,
@@ -794,32 +729,8 @@ extern "C" int cdml_gemm_bf16x3_tnk(const uint16_t *A, int ma, int a_col0, const
   g.M = M; g.N = N;
   g.x3_tpp = K / 64; g.x3_plane_a = (int64_t)(K / 8) * ma * 8; g.x3_plane_b = (int64_t)(K / 8) * nb * 8;
   g.x3_products = 6;
-  const int ktiles = 6 * g.x3_tpp;
-  g.K = ktiles * 64;
-  g.tiles_m = M / 256; g.tiles_n = N / 256;
-  int splits = gemm_bf16_256_splits(M, N, g.K), per = 0;
-  x3_split_geometry(ktiles, splits, 6, per, splits);
-  const bool slabs = splits > 1;
-  const size_t slab_bytes = slabs ? (size_t)splits * M * N * sizeof(float) : 0;
-  const size_t cs_rows = (size_t)splits * g.tiles_m * 2;
-  const size_t need = slab_bytes + (colsum ? cs_rows * N * sizeof(float) : 0);
-  CDML_REQUIRE(need == 0 || (workspace && workspace_bytes >= need && aligned16(workspace)), CDML_E_BADARG,
-               "gemm_bf16x3_tnk: workspace of %zu bytes required (cdml_gemm_bf16x3_workspace)", need);
-  hipStream_t s = (hipStream_t)stream;
-  g.k_per_split = per * 64;
-  g.slab_stride = (int64_t)M * N;
-  g.C = slabs ? workspace : static_cast<void *>(C);
-  g.ldc = slabs ? N : ldc;
-  g.colsum_partial = colsum ? reinterpret_cast<float *>(static_cast<char *>(workspace) + slab_bytes) : nullptr;
-  int rc = launch_gemm_x3_tnk(g, splits, s);
-  if (rc) return rc;
-  if (slabs || colsum) {
-    const int sb = slabs ? grid1d((int64_t)M * N / 4) : 0, cb = colsum ? (N + 15) / 16 : 0;
-    hipLaunchKernelGGL(k_x3_sum_slabs, dim3(sb + cb), dim3(kThreads), 0, s, static_cast<const float *>(workspace), g.slab_stride,
-                       splits, M, N, static_cast<const float *>(nullptr), 0.f, C, ldc, sb, g.colsum_partial, (int)cs_rows, colsum, 1.0f);
-    rc = check_launch("gemm_bf16x3_tnk combine");
-  }
-  return rc;
+  const KSplitPlan p = x3_plan_tn(M, N, K, 6, x3_tn_period(6, true, false), false, colsum != nullptr);
+  return x3_run_tn("gemm_bf16x3_tnk", g, p, launch_gemm_x3_tnk, C, ldc, nullptr, 0.f, colsum, 1.0f, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 // C[M][N] (fp32) = sum_k A[k][M] B[k][N] like cdml_gemm_bf16x3_tn with ONLY B k8-interleaved: A = row-major planes [K][lda]
@@ -844,30 +755,6 @@ extern "C" int cdml_gemm_bf16x3_tn_kb(const uint16_t *A, int64_t lda, int64_t pl
   g.M = M; g.N = N;
   g.x3_tpp = K / 64; g.x3_plane_a = plane_a; g.x3_plane_b = (int64_t)(K / 8) * nb * 8;
   g.x3_products = 6;
-  const int ktiles = 6 * g.x3_tpp;
-  g.K = ktiles * 64;
-  g.tiles_m = M / 256; g.tiles_n = N / 256;
-  int splits = gemm_bf16_256_splits(M, N, g.K), per = 0;
-  x3_split_geometry(ktiles, splits, 6, per, splits);
-  const bool slabs = splits > 1;
-  const size_t slab_bytes = slabs ? (size_t)splits * M * N * sizeof(float) : 0;
-  const size_t cs_rows = (size_t)splits * g.tiles_m * 2;
-  const size_t need = slab_bytes + (colsum ? cs_rows * N * sizeof(float) : 0);
-  CDML_REQUIRE(need == 0 || (workspace && workspace_bytes >= need && aligned16(workspace)), CDML_E_BADARG,
-               "gemm_bf16x3_tn_kb: workspace of %zu bytes required (cdml_gemm_bf16x3_workspace)", need);
-  hipStream_t s = (hipStream_t)stream;
-  g.k_per_split = per * 64;
-  g.slab_stride = (int64_t)M * N;
-  g.C = slabs ? workspace : static_cast<void *>(C);
-  g.ldc = slabs ? N : ldc;
-  g.colsum_partial = colsum ? reinterpret_cast<float *>(static_cast<char *>(workspace) + slab_bytes) : nullptr;
-  int rc = launch_gemm_x3_tnkb(g, splits, s);
-  if (rc) return rc;
-  if (slabs || colsum) {
-    const int sb = slabs ? grid1d((int64_t)M * N / 4) : 0, cb = colsum ? (N + 15) / 16 : 0;
-    hipLaunchKernelGGL(k_x3_sum_slabs, dim3(sb + cb), dim3(kThreads), 0, s, static_cast<const float *>(workspace), g.slab_stride,
-                       splits, M, N, static_cast<const float *>(nullptr), 0.f, C, ldc, sb, g.colsum_partial, (int)cs_rows, colsum, 1.0f);
-    rc = check_launch("gemm_bf16x3_tn_kb combine");
-  }
-  return rc;
+  const KSplitPlan p = x3_plan_tn(M, N, K, 6, x3_tn_period(6, true, false), false, colsum != nullptr);
+  return x3_run_tn("gemm_bf16x3_tn_kb", g, p, launch_gemm_x3_tnkb, C, ldc, nullptr, 0.f, colsum, 1.0f, workspace, workspace_bytes, (hipStream_t)stream);
 }

@@ -5,6 +5,7 @@ and csrc/gemm_f16x2_256.hip of two trees to gfx950 assembly with build()'s flags
     python tools/isa_ab.py                 # the parent commit (a temporary git worktree of HEAD~) against the working tree
     python tools/isa_ab.py --rev HEAD      # the last commit against uncommitted edits
     python tools/isa_ab.py --a DIR --b DIR # two checked-out trees
+    python tools/isa_ab.py --sources gemm_bf16x3.hip gemm_bf16.hip   # other translation units of csrc/
 
 A kernel is its instructions plus its .amdhsa_kernel descriptor block (registers, LDS, scratch).  What may differ without
 the code differing is canonicalised: the kernel's own mangled name, the __hip_cuid_* symbol, comments, and the function
@@ -109,7 +110,10 @@ def main():
     ap.add_argument("--rev", default="HEAD~", help="revision checked out as tree A when --a is not given")
     ap.add_argument("--a", help="tree A (a checkout of the repository)")
     ap.add_argument("--b", default=ROOT, help="tree B (default: the working tree)")
+    ap.add_argument("--sources", nargs="+", default=list(SOURCES), metavar="FILE.hip",
+                    help="the translation units of csrc/ to compare (default: the two of the tile GEMM)")
     args = ap.parse_args()
+    sources = tuple(args.sources)
     flags = build_flags()
     ok = True
     with tempfile.TemporaryDirectory() as tmp:
@@ -119,7 +123,7 @@ def main():
             subprocess.run(["git", "-C", ROOT, "worktree", "add", "--detach", "--force", a, args.rev], check=True,
                            stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
         try:
-            jobs = [(side, tree, src) for src in SOURCES for side, tree in (("a", a), ("b", args.b))]
+            jobs = [(side, tree, src) for src in sources for side, tree in (("a", a), ("b", args.b))]
             with ThreadPoolExecutor(max_workers=len(jobs)) as ex:
                 asm = dict(zip([(j[0], j[2]) for j in jobs],
                                ex.map(lambda j: assemble(j[1], j[2], flags, os.path.join(tmp, j[0] + "_" + j[2] + ".s")), jobs)))
@@ -128,7 +132,7 @@ def main():
                 subprocess.run(["git", "-C", ROOT, "worktree", "remove", "--force", a], check=False)
     print("A = %s, B = %s; flags: %s" % (args.a or args.rev, os.path.relpath(args.b, ROOT) if args.b != ROOT else "working tree",
                                          " ".join(flags)))
-    for src in SOURCES:
+    for src in sources:
         ka, kb = kernels(asm[("a", src)]), kernels(asm[("b", src)])
         report, same = compare(ka, kb)
         ok = ok and same
