@@ -1113,7 +1113,8 @@ __device__ __forceinline__ void run_tile(const BArgs &g, const int tm, const int
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int id = g.knn_col0 + cbase + cb * 16 + r;
-          const float d = fmaxf((qs + bsv[cb][r]) - (kF16 ? 2.0f * g.out_scale : 2.0f) * acc16[rbb][cb][r], 0.f);
+          const float dr = (qs + bsv[cb][r]) - (kF16 ? 2.0f * g.out_scale : 2.0f) * acc16[rbb][cb][r];
+          const float d = dr < 0.f ? 0.f : dr;               // (a clamp that keeps NaN: a non-finite row is nobody's candidate)
           if (d <= tau && id < g.knn_n_valid && i < g.M) {   // rare
             const int pos = atomicAdd(g.knn_cnt + i, 1);
             if (pos < g.knn_cap) g.knn_cand[(int64_t)i * g.knn_cap + pos] = make_uint2(__float_as_uint(d), (uint32_t)id);
@@ -1194,7 +1195,8 @@ __device__ __forceinline__ void run_tile(const BArgs &g, const int tm, const int
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             const int id = id0 + cb * 16 + r;
-            const float d = fmaxf(__builtin_fmaf(m2s, acc16[rbb][cb][r], qs + bsv[cb][r]), 0.f);
+            const float dr = __builtin_fmaf(m2s, acc16[rbb][cb][r], qs + bsv[cb][r]);
+            const float d = dr < 0.f ? 0.f : dr;             // keeps NaN, as the fast path's d < tau does: a non-finite row is never counted
             n += (id < g.knn_n_valid && id != sid && id != pid && (d < tau || (d == tau && id < pid))) ? 1 : 0;
           }
       }

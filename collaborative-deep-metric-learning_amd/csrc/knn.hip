@@ -118,7 +118,8 @@ k_knn_merge(const float *scores, int64_t lds, int nq, int nb, int col0, int n_va
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const int id = col0 + c + e;
-      const float d = fmaxf((qs + bs[e]) - 2.f * s[e], 0.f);
+      const float dr = (qs + bs[e]) - 2.f * s[e];
+      const float d = dr < 0.f ? 0.f : dr;     // the clamp keeps a NaN (fmaxf would make it 0: a non-finite row everyone's nearest neighbour); NaN never passes
       const bool pass = (c + e < nb) && (id < n_valid) && key_less(d, id, tau_d, tau_i);
       const unsigned long long m = __ballot(pass);
       if (m == 0ull) continue;

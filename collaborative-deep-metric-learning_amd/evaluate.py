@@ -193,7 +193,8 @@ class Evaluation():
         ``vectors`` [N, D] by squared L2 -- #{j != a, p: d(a,j) < d(a,p), or d(a,j) == d(a,p) and j < p}.  Distances on the
         vectors as given (``l2_norm``: normalised first, as calc_knn does).  ``precision``: "f32x3" (three bf16 planes per
         fp32 value, six products) or "f16x2" (two fp16 planes, three products).  ``q_chunk`` queries x ``c_chunk``
-        catalogue rows per launch (the counts are integers: the same for any chunking)."""
+        catalogue rows per launch (the counts are integers: the same for any chunking).  A catalogue row with a non-finite
+        coordinate is never counted ahead of a partner."""
         queries, pos, _ = self._ranks(vectors, cowatches, symmetric, precision, l2_norm, q_chunk, c_chunk)
         return queries, pos
 

@@ -67,7 +67,13 @@ def knn_search(base, queries, k, l2_norm=True, device="cuda:0", q_block=Q_BLOCK,
     ``fused`` (precision "f32x3", catalogues of more than two first blocks): everything after the first ``first_block``
     catalogue rows through the filter epilogue instead of score blocks (False: score blocks throughout, the round-5 form);
     ``q_chunk`` queries x ``c_chunk`` catalogue rows per filter launch (operands inside a descriptor's 2 GiB window, candidate
-    buffer q_chunk x list capacity x 8 B), the lists merged -- and every query's threshold tightened -- after each."""
+    buffer q_chunk x list capacity x 8 B), the lists merged -- and every query's threshold tightened -- after each.
+    Non-finite input: a catalogue row with a NaN coordinate is nobody's neighbour (its distances are NaN, the kernels' clamp
+    at 0 keeps a NaN, and a NaN passes no compare); a row with an infinite coordinate has distance NaN or +inf, so it is
+    nobody's neighbour either wherever at least k finite rows exist (+inf can still fill a list that would otherwise be
+    short).  A non-finite query gets I = -1, D = +inf throughout.  The other results are those of the finite rows alone --
+    bit for bit on "f32x3" and "f32"; on "f16x2" the tensor's maximum is then not finite and the planes are split at scale 1
+    instead (_planes_h2), which loses precision for rows far below fp16's range."""
     if precision not in ("f32x3", "f32", "f16x2"):
         raise ValueError("precision must be 'f32x3', 'f16x2' or 'f32'")
     h2 = precision == "f16x2"

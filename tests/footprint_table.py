@@ -77,7 +77,7 @@ ENTRIES = [
     E("triplet_hinge_indexed_tail", "cdml_triplet_hinge_indexed_tail", "as triplet_hinge_indexed + in z; out dz2 dz2 planes (plane_bf > D)",
       "fp64 hinge + l2norm backward + lrelu' in torch", "1e-6: test_gpu_parity indexed hinge tests; planes == split of dz2"),
     E("semihard_mine_x3", "cdml_semihard_mine_x3", "in e[2B][D] rows[2B]; out e_planes sqn dp neg_row; ws",
-      "fp64 distances, the semi-hard rule", "2e-6 on the distances: test_gpu_parity / test_gpu_f32x3 semi-hard checks"),
+      "fp64 distances, the semi-hard rule", "2e-6 on the distances: test_gpu_parity / test_gpu_f32x3 semi-hard checks; bit for bit, ties included: tests/test_gpu_exact_select.py"),
     E("l2norm_fwd", "cdml_l2norm_fwd", "in x[M][N] (ldx > N); out y[M][N] (ldy > N) inv[M]", "fp64 x rsqrt(max(sum x^2, 1e-12))", "1e-6: test_gpu_parity l2norm"),
     E("l2norm_bwd", "cdml_l2norm_bwd", "in z g; out dz (ld > N)", "fp64 l2norm backward (+ lrelu')", "1e-6: test_gpu_parity l2norm"),
     # ---- N-pair family ---------------------------------------------------------------------------------------------------------
@@ -111,12 +111,12 @@ ENTRIES = [
     # ---- export and eval ----------------------------------------------------------------------------------------------------------
     E("row_sqnorm", "cdml_row_sqnorm", "in x[n][D] (ldx > D); out out[n]", "fp64 sum of squares", "1e-6 rel"),
     E("knn_merge", "cdml_knn_merge", "in scores[nq][nb] (lds > nb) q_sq b_sq; out best_d best_i [nq][128] (first = 1 starts the lists: all 128 columns are written)",
-      "fp64 top-k by (distance, id)", "1e-5: tests/test_gpu_knn.py", "two blocks, n_valid inside the second"),
+      "fp64 top-k by (distance, id)", "1e-5: tests/test_gpu_knn.py; bit for bit, ties included: tests/test_gpu_exact_select.py", "two blocks, n_valid inside the second"),
     E("knn_filter_x3", "cdml_knn_filter_x3", "in Q B planes q_sq b_sq tau; inout cnt[nq]; out cand[nq][cap][2] up to min(cnt, cap) slots, the guard right after cap entries",
-      "fp64 distances <= tau as a set", "1e-5: tests/test_gpu_knn.py", "a capacity no list reaches and one every list overflows"),
-    E("knn_merge_list", "cdml_knn_merge_list", "in cand; inout cnt (back to 0) best_d best_i; out overflow", "fp64 merge by (distance, id)", "1e-5: tests/test_gpu_knn.py", "with and without overflow"),
-    E("rank_tau_x3", "cdml_rank_tau_x3", "in Q[nq] P[nq up to 256] planes q_sq p_sq; out tau[nq]", "fp64 max(|q|^2 + |p|^2 - 2 q.p, 0)", "1e-5: tests/test_gpu_retrieval.py", "nq = 300"),
-    E("rank_count_x3", "cdml_rank_count_x3", "in Q B planes q_sq b_sq tau pos_id self_id; inout count[nq]", "fp64 rank by (distance, id)", "ranks equal off near-ties (1e-5): tests/test_gpu_retrieval.py",
+      "fp64 distances <= tau as a set", "1e-5: tests/test_gpu_knn.py; bit for bit, ties included: tests/test_gpu_exact_select.py", "a capacity no list reaches and one every list overflows"),
+    E("knn_merge_list", "cdml_knn_merge_list", "in cand; inout cnt (back to 0) best_d best_i; out overflow", "fp64 merge by (distance, id)", "1e-5: tests/test_gpu_knn.py; bit for bit, ties included: tests/test_gpu_exact_select.py", "with and without overflow"),
+    E("rank_tau_x3", "cdml_rank_tau_x3", "in Q[nq] P[nq up to 256] planes q_sq p_sq; out tau[nq]", "fp64 max(|q|^2 + |p|^2 - 2 q.p, 0)", "1e-5: tests/test_gpu_retrieval.py; bit for bit, ties included: tests/test_gpu_exact_select.py", "nq = 300"),
+    E("rank_count_x3", "cdml_rank_count_x3", "in Q B planes q_sq b_sq tau pos_id self_id; inout count[nq]", "fp64 rank by (distance, id)", "ranks equal off near-ties (1e-5): tests/test_gpu_retrieval.py; bit for bit, ties included: tests/test_gpu_exact_select.py",
       "n_valid = 700 inside the last 256-row tile, two launches accumulate"),
     E("knn_desim_prep", "cdml_knn_desim_prep", "in fI[n_f][kf] (ldf > kf) fD; out out[n_f][kp]", "oracle rule in numpy", "exact: tests/test_gpu_knn_desim.py", "int32 and int64 ids"),
     E("knn_desim", "cdml_knn_desim", "in eI[nq][ke] (lde > ke) f_filtered; out out[nq][ke] (ldo > ke)", "greedy rule in numpy", "exact: tests/test_gpu_knn_desim.py"),
