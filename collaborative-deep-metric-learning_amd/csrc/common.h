@@ -5,18 +5,10 @@
 #include <stdio.h>
 #include <stdarg.h>
 #include "../../include/cdml.h"
+#include "require.h"
 #include "gemm_plan.h"
 
 namespace cdml {
-
-// ---- per-thread error message ------------------------------------------------
-char *err_buf();
-int fail(int code, const char *fmt, ...);
-
-#define CDML_REQUIRE(cond, code, ...)                  \
-  do {                                                 \
-    if (!(cond)) return ::cdml::fail((code), __VA_ARGS__); \
-  } while (0)
 
 inline int check_launch(const char *what) {
   hipError_t e = hipGetLastError();

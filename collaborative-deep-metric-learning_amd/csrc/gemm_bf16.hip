@@ -16,6 +16,7 @@
 // keeps the shapes that kernel does not take (N % 256, K % 128, few tiles).
 #include <stdlib.h>
 #include "gemm_bf16.h"
+#include "gather_plan.h"
 
 namespace cdml {
 namespace {
@@ -696,22 +697,13 @@ extern "C" int cdml_gather_rows_f16(const uint16_t *table, int64_t row0, int64_t
                                     int64_t row_stride, const int32_t *idx, int n_idx, int F,
                                     uint16_t *x_out_bf16, int64_t out_stride, int32_t *oob_flag,
                                     cdml_stream_t stream) {
-  CDML_REQUIRE(table && idx && x_out_bf16 && n_rows > 0 && n_idx > 0 && row0 >= 0, CDML_E_BADARG,
-               "gather_rows_f16: bad argument");
-  CDML_REQUIRE(F > 0 && F <= 4096, CDML_E_UNSUPPORTED, "gather_rows_f16: feature size outside (0, 4096]");
-  CDML_REQUIRE(row_stride >= F && (row_stride & 7) == 0 && out_stride >= F && (out_stride & 7) == 0 &&
-                   aligned16(table) && aligned16(x_out_bf16),
-               CDML_E_ALIGN, "gather_rows_f16: strides must be >= F and multiples of 8, bases 16-B aligned");
-  int64_t blocks = ((int64_t)n_idx + 3) / 4;
-  if (blocks > kNumCU * 8) blocks = kNumCU * 8;
-  const int nch = ((F + 7) / 8 + 63) / 64;
-#define CDML_LAUNCH_GH(N)                                                                          \
-  hipLaunchKernelGGL(k_gather_rows_f16<N>, dim3((int)blocks), dim3(kThreads), 0, (hipStream_t)stream, \
-                     reinterpret_cast<const _Float16 *>(table), row0, n_rows, row_stride, idx, n_idx, F, \
-                     reinterpret_cast<bf16 *>(x_out_bf16), out_stride, oob_flag)
-  if (nch <= 1) CDML_LAUNCH_GH(1);
-  else if (nch <= 3) CDML_LAUNCH_GH(3);
-  else CDML_LAUNCH_GH(8);
-#undef CDML_LAUNCH_GH
-  return check_launch("gather_rows_f16");
+  const GatherRowsArgs a = {table, row0, n_rows, row_stride, idx, n_idx, F, x_out_bf16, out_stride};
+  GatherPlan p;
+  if (int rc = plan_gather_rows("gather_rows_f16", kGatherF16, a, p)) return rc;
+  const int rc = with_nch<kGatherF16, false>("gather_rows_f16", p.nch, [&](auto nch) {
+    hipLaunchKernelGGL(k_gather_rows_f16<decltype(nch)::value>, dim3(p.grid), dim3(kThreads), 0, (hipStream_t)stream,
+                       reinterpret_cast<const _Float16 *>(table), row0, n_rows, row_stride, idx, n_idx, F,
+                       reinterpret_cast<bf16 *>(x_out_bf16), out_stride, oob_flag);
+  });
+  return rc ? rc : check_launch("gather_rows_f16");
 }

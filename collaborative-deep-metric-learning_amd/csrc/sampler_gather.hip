@@ -11,6 +11,7 @@
 // a row's loads issued before the first use, wave-shuffle reduction for the
 // norm.  Rows start 128-B aligned when row_stride*4 is a multiple of 128.
 #include "common.h"
+#include "gather_plan.h"
 #include "../../include/cdml_hardneg.h"
 
 namespace cdml {
@@ -152,6 +153,55 @@ k_sample_inbatch(const int32_t *__restrict__ pairs, int64_t n_pairs, uint64_t se
 __global__ void k_step_advance(uint64_t *step_dev) { *step_dev += 1; }
 
 // -------------------------------------------------------------------- gather --
+// The arithmetic every fp32-table row shares, whatever it is stored as.  v: the row in registers, chunk c of lane l =
+// columns 4 * (l + 64 c) .. + 3.
+// The pad of the last chunk is masked, so the table's pad content never leaks in.
+template <int NCH>
+__device__ __forceinline__ void mask_row_pad(float4 (&v)[NCH], int F, int lane) {
+  if (F & 3) {
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+      const int j = 4 * (lane + kWave * c);
+      if (j + 1 >= F && j < F) v[c].y = 0.f;
+      if (j + 2 >= F && j < F) v[c].z = 0.f;
+      if (j + 3 >= F && j < F) v[c].w = 0.f;
+    }
+  }
+}
+
+// 1 / max(|row|, 1e-6) of the (masked) row a wave holds
+template <int NCH>
+__device__ __forceinline__ float row_inv_norm(const float4 (&v)[NCH]) {
+  float ss = 0.f;
+#pragma unroll
+  for (int c = 0; c < NCH; ++c)
+    ss += v[c].x * v[c].x + v[c].y * v[c].y + v[c].z * v[c].z + v[c].w * v[c].w;
+  ss = wave_sum(ss);
+  return 1.0f / sqrtf(fmaxf(ss, 1e-12f));
+}
+
+// The four ROUNDED products v * inv, the values the fp32 gather stores: what the plane formats split.  No contraction --
+// a product fused with the residual subtraction of the split into an fma on the unrounded one gives other planes, and two
+// evaluations contracted differently once moved a few rows by one ulp (RowF32X3::chunk_planes).
+__device__ __forceinline__ void scaled4(const float4 &v, float inv, float (&r)[4]) {
+#pragma clang fp contract(off)
+  r[0] = v.x * inv, r[1] = v.y * inv, r[2] = v.z * inv, r[3] = v.w * inv;
+}
+
+// The next bf16 plane of four columns: r rounded, and r left holding the residual.  Three calls: hi | mid | lo with
+// hi + mid + lo = r exactly (split3_bf16, four columns at a time).
+template <typename V4>
+__device__ __forceinline__ V4 next_plane4(float (&r)[4]) {
+#pragma clang fp contract(off)
+  V4 o;
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    o[u] = (__bf16)r[u];
+    r[u] -= (float)o[u];
+  }
+  return o;
+}
+
 // One wave gathers (and optionally l2-normalises) one row.  NCH = float4 chunks
 // per lane held in registers (covers F <= 256*NCH).
 template <int NCH>
@@ -167,7 +217,7 @@ __device__ __forceinline__ void gather_one_row(const float *__restrict__ table, 
     const int q = lane + kWave * c;
     v[c] = (q < nq) ? load_row_chunk(src + q) : make_float4(0.f, 0.f, 0.f, 0.f);
   }
-  if (F & 3) {  // mask the tail so the table's pad content never leaks in
+  if (F & 3) {  // (mask_row_pad, spelled out: through the helper this kernel's branch came out with the other polarity)
 #pragma unroll
     for (int c = 0; c < NCH; ++c) {
       const int j = 4 * (lane + kWave * c);
@@ -177,14 +227,7 @@ __device__ __forceinline__ void gather_one_row(const float *__restrict__ table, 
     }
   }
   float inv = 1.f;
-  if (normalize) {
-    float ss = 0.f;
-#pragma unroll
-    for (int c = 0; c < NCH; ++c)
-      ss += v[c].x * v[c].x + v[c].y * v[c].y + v[c].z * v[c].z + v[c].w * v[c].w;
-    ss = wave_sum(ss);
-    inv = 1.0f / sqrtf(fmaxf(ss, 1e-12f));
-  }
+  if (normalize) inv = row_inv_norm(v);
   if (inv_out && lane == 0) *inv_out = inv;
   float4 *d = reinterpret_cast<float4 *>(dst);
   const int oq = (int)(out_stride >> 2);
@@ -273,15 +316,7 @@ k_gather_rows_planes(const float *__restrict__ src, int64_t n_rows, int64_t row_
           for (int u = 0; u < 4; ++u) if (4 * q + u >= F) x[u] = 0.f;
         }
 #pragma unroll
-        for (int pl = 0; pl < 3; ++pl) {
-          bf16x4v o;
-#pragma unroll
-          for (int u = 0; u < 4; ++u) {
-            o[u] = (__bf16)x[u];
-            x[u] -= (float)o[u];
-          }
-          *reinterpret_cast<bf16x4v *>(dst + pl * plane + 4 * q) = o;
-        }
+        for (int pl = 0; pl < 3; ++pl) *reinterpret_cast<bf16x4v *>(dst + pl * plane + 4 * q) = next_plane4<bf16x4v>(x);
       }
     }
     const bf16x4v z4 = {0, 0, 0, 0};
@@ -306,10 +341,7 @@ k_gather_rows_planes(const float *__restrict__ src, int64_t n_rows, int64_t row_
 //     wave-shuffle norm and the stores.
 // MODE 0 = uniform negatives, MODE 1 = in-batch negatives, MODE 2 = listed negatives (3 rows per triplet as MODE 0; only
 // the id-staging lanes differ: the negative's lane reads the anchor's list, one more hop of the chain pair -> id -> row).
-#ifndef CDML_GATHER_ROWS_PER_WAVE
-#define CDML_GATHER_ROWS_PER_WAVE 2   // rows a wave keeps in flight (A/B'd: tools/gather_variants.sh)
-#endif
-constexpr int kRowsPerWave = CDML_GATHER_ROWS_PER_WAVE;
+constexpr int kRowsPerWave = CDML_GATHER_ROWS_PER_WAVE;   // (gather_plan.h, which sizes the grid by it)
 constexpr int kChunkRows = kRowsPerWave * kWavesPerBlock;
 
 template <int NCH>
@@ -330,21 +362,8 @@ __device__ __forceinline__ void row_issue(RowRegs<NCH> &R, const float *__restri
 template <int NCH>
 __device__ __forceinline__ void row_finish(RowRegs<NCH> &R, int F, float *__restrict__ dst, int64_t out_stride,
                                            int lane) {
-  if (F & 3) {
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-      const int j = 4 * (lane + kWave * c);
-      if (j + 1 >= F && j < F) R.v[c].y = 0.f;
-      if (j + 2 >= F && j < F) R.v[c].z = 0.f;
-      if (j + 3 >= F && j < F) R.v[c].w = 0.f;
-    }
-  }
-  float ss = 0.f;
-#pragma unroll
-  for (int c = 0; c < NCH; ++c)
-    ss += R.v[c].x * R.v[c].x + R.v[c].y * R.v[c].y + R.v[c].z * R.v[c].z + R.v[c].w * R.v[c].w;
-  ss = wave_sum(ss);
-  const float inv = 1.0f / sqrtf(fmaxf(ss, 1e-12f));
+  mask_row_pad(R.v, F, lane);
+  const float inv = row_inv_norm(R.v);
   float4 *d = reinterpret_cast<float4 *>(dst);
   const int oq = (int)(out_stride >> 2);
 #pragma unroll
@@ -395,36 +414,18 @@ struct RowF32X3 {
   // differently from the first and moved a few rows' factor by one ulp (tests: the copy == the interleaved row-major planes).
   template <typename V4>
   __device__ static __forceinline__ void chunk_planes(const Regs &R, int c, float inv, V4 (&o)[3]) {
-#pragma clang fp contract(off)
-    float r[4] = {R.v[c].x * inv, R.v[c].y * inv, R.v[c].z * inv, R.v[c].w * inv};
+    float r[4];
+    scaled4(R.v[c], inv, r);
 #pragma unroll
-    for (int pl = 0; pl < 3; ++pl)
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        o[pl][u] = (__bf16)r[u];
-        r[u] -= (float)o[pl][u];
-      }
+    for (int pl = 0; pl < 3; ++pl) o[pl] = next_plane4<V4>(r);
   }
   __device__ static __forceinline__ void issue(Regs &R, const In *table, int64_t lr, int64_t stride, int F, int lane) {
     row_issue<NCH>(R, table, lr, stride, (F + 3) >> 2, lane);
   }
   __device__ static __forceinline__ float finish(Regs &R, int F, Out *dst, int64_t out_stride, int lane) {
     using bf16x4v = __attribute__((ext_vector_type(4))) __bf16;
-    if (F & 3) {
-#pragma unroll
-      for (int c = 0; c < NCH; ++c) {
-        const int j = 4 * (lane + kWave * c);
-        if (j + 1 >= F && j < F) R.v[c].y = 0.f;
-        if (j + 2 >= F && j < F) R.v[c].z = 0.f;
-        if (j + 3 >= F && j < F) R.v[c].w = 0.f;
-      }
-    }
-    float ss = 0.f;
-#pragma unroll
-    for (int c = 0; c < NCH; ++c)
-      ss += R.v[c].x * R.v[c].x + R.v[c].y * R.v[c].y + R.v[c].z * R.v[c].z + R.v[c].w * R.v[c].w;
-    ss = wave_sum(ss);
-    const float inv = 1.0f / sqrtf(fmaxf(ss, 1e-12f));
+    mask_row_pad(R.v, F, lane);
+    const float inv = row_inv_norm(R.v);
     const int64_t plane = out_stride / 3;
     const int oq = (int)(plane >> 2);
     const bf16x4v z4 = {0, 0, 0, 0};
@@ -432,18 +433,11 @@ struct RowF32X3 {
     for (int c = 0; c < NCH; ++c) {
       const int q = lane + kWave * c;
       if (q < oq) {
-        // the planes are those of the ROUNDED product, the value the fp32 gather stores: no contraction of the
-        // product with the residual subtraction below into an fma on the unrounded one
-#pragma clang fp contract(off)
-        float r[4] = {R.v[c].x * inv, R.v[c].y * inv, R.v[c].z * inv, R.v[c].w * inv};
+        float r[4];
+        scaled4(R.v[c], inv, r);
 #pragma unroll
         for (int pl = 0; pl < 3; ++pl) {
-          bf16x4v o;
-#pragma unroll
-          for (int u = 0; u < 4; ++u) {
-            o[u] = (__bf16)r[u];
-            r[u] -= (float)o[u];
-          }
+          const bf16x4v o = next_plane4<bf16x4v>(r);
 #if CDML_GATHER_NT_STORE
           __builtin_nontemporal_store(o, reinterpret_cast<bf16x4v *>(dst + pl * plane + 4 * q));
 #else
@@ -476,21 +470,8 @@ struct RowF32H2 {
   }
   __device__ static __forceinline__ void finish(Regs &R, int F, Out *dst, int64_t out_stride, int lane) {
     using half4v = __attribute__((ext_vector_type(4))) _Float16;
-    if (F & 3) {
-#pragma unroll
-      for (int c = 0; c < NCH; ++c) {
-        const int j = 4 * (lane + kWave * c);
-        if (j + 1 >= F && j < F) R.v[c].y = 0.f;
-        if (j + 2 >= F && j < F) R.v[c].z = 0.f;
-        if (j + 3 >= F && j < F) R.v[c].w = 0.f;
-      }
-    }
-    float ss = 0.f;
-#pragma unroll
-    for (int c = 0; c < NCH; ++c)
-      ss += R.v[c].x * R.v[c].x + R.v[c].y * R.v[c].y + R.v[c].z * R.v[c].z + R.v[c].w * R.v[c].w;
-    ss = wave_sum(ss);
-    const float inv = 1.0f / sqrtf(fmaxf(ss, 1e-12f));
+    mask_row_pad(R.v, F, lane);
+    const float inv = row_inv_norm(R.v);
     const int64_t plane = out_stride / 2;
     const int oq = (int)(plane >> 2);
     const half4v z4 = {0, 0, 0, 0};
@@ -498,9 +479,11 @@ struct RowF32H2 {
     for (int c = 0; c < NCH; ++c) {
       const int q = lane + kWave * c;
       if (q < oq) {
-        // the planes are those of the ROUNDED product (the value the fp32 gather stores) times 2^14, exactly
+        // the planes are those of the ROUNDED product (scaled4: the value the fp32 gather stores) times 2^14, exactly; the
+        // pragma is for the arithmetic BELOW -- r * 2^14 and the hi / lo residual must not be contracted either
 #pragma clang fp contract(off)
-        float r[4] = {R.v[c].x * inv, R.v[c].y * inv, R.v[c].z * inv, R.v[c].w * inv};
+        float r[4];
+        scaled4(R.v[c], inv, r);
         half4v hi, lo;
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
@@ -532,9 +515,6 @@ struct RowF16 {
   using Out = __bf16;
   struct Regs { half8 v[NCH]; };
   static constexpr int kPerChunk = 8;
-#ifndef CDML_GATHER_ROWS_PER_WAVE_F16
-#define CDML_GATHER_ROWS_PER_WAVE_F16 4
-#endif
   static constexpr int kRows = CDML_GATHER_ROWS_PER_WAVE_F16;   // 3-KB rows: four in flight per wave
   __device__ static __forceinline__ void issue(Regs &R, const In *table, int64_t lr, int64_t stride, int F, int lane) {
     const half8 *src = reinterpret_cast<const half8 *>(table + lr * stride);
@@ -786,17 +766,6 @@ k_scatter_rows(const float *__restrict__ src, int64_t lds, const int32_t *__rest
   }
 }
 
-int grid_for(int64_t work_items, int per_block) {
-  int64_t b = (work_items + per_block - 1) / per_block;
-  const int64_t cap = (int64_t)kNumCU * 8;
-  if (b > cap) b = cap;
-  if (b < 1) b = 1;
-  return (int)b;
-}
-
-// (round 5: a grid with every block walking the same number of chunks -- 1 536 blocks x 3 chunks instead of 2 048 blocks x
-// 2.25 -- was measured SLOWER for the fp16 gather, 0.600 against 0.675 of 8 TB/s: what counts is 8 resident blocks per CU,
-// not an even chunk count)
 }  // namespace
 }  // namespace cdml
 
@@ -828,15 +797,6 @@ extern "C" int cdml_sample_uniform(const int32_t *pairs, int64_t n_pairs, int64_
                      (hipStream_t)stream, pairs, n_pairs, (uint32_t)n_rows, seed, step, step_dev,
                      batch, slot0, batch_global, idx_out);
   return check_launch("sample_uniform");
-}
-
-// the listed draw's own arguments (cdml_hardneg.h), checked before any HIP call
-static int check_listed(const char *who, const int32_t *lists, int64_t ldl, int L, uint64_t hard_thresh) {
-  CDML_REQUIRE(lists, CDML_E_BADARG, "%s: lists is null", who);
-  CDML_REQUIRE(L >= 1 && L <= 1024, CDML_E_BADARG, "%s: L = %d outside [1, 1024]", who, L);
-  CDML_REQUIRE(ldl >= L, CDML_E_BADARG, "%s: ldl < L", who);
-  CDML_REQUIRE(hard_thresh <= (1ull << 32), CDML_E_BADARG, "%s: hard_thresh > 2^32", who);
-  return CDML_OK;
 }
 
 extern "C" int cdml_sample_listed(const int32_t *pairs, int64_t n_pairs, int64_t n_rows, uint64_t seed, uint64_t step,
@@ -876,35 +836,21 @@ extern "C" int cdml_step_advance(uint64_t *step_dev, cdml_stream_t stream) {
   return check_launch("step_advance");
 }
 
-static int check_gather_layout(const char *who, const float *table, int64_t row_stride, int F,
-                               const float *x_out, int64_t out_stride) {
-  CDML_REQUIRE(F > 0 && F <= 2048, CDML_E_UNSUPPORTED, "%s: feature size %d outside (0, 2048]", who, F);
-  CDML_REQUIRE(row_stride >= F && (row_stride & 3) == 0 && out_stride >= F && (out_stride & 3) == 0,
-               CDML_E_ALIGN, "%s: strides must be >= F and multiples of 4", who);
-  CDML_REQUIRE(aligned16(table) && aligned16(x_out), CDML_E_ALIGN, "%s: bases must be 16-B aligned", who);
-  return CDML_OK;
-}
+// ---- the gather launches: gather_plan.h checks the call and plans it, the launcher picks the instantiation the plan names ----
+static_assert(kWave == kGatherWave && kWavesPerBlock == kGatherWavesPerBlock, "gather_plan.h plans for these blocks");
 
 extern "C" int cdml_gather_rows(const float *table, int64_t row0, int64_t n_rows, int64_t row_stride,
                                 const int32_t *idx, int n_idx, int F, int normalize, float *x_out,
                                 int64_t out_stride, float *inv_norm_out, int32_t *oob_flag,
                                 cdml_stream_t stream) {
-  CDML_REQUIRE(table && idx && x_out && n_rows > 0 && n_idx > 0 && row0 >= 0, CDML_E_BADARG,
-               "gather_rows: bad argument");
-  int rc = check_gather_layout("gather_rows", table, row_stride, F, x_out, out_stride);
-  if (rc) return rc;
-  const int grid = grid_for(n_idx, kWavesPerBlock);
-  const int nch = ((F + 3) / 4 + kWave - 1) / kWave;
-#define CDML_LAUNCH_GATHER(N)                                                                   \
-  hipLaunchKernelGGL(k_gather_rows<N>, dim3(grid), dim3(kThreads), 0, (hipStream_t)stream, table, \
-                     row0, n_rows, row_stride, idx, n_idx, F, normalize, x_out, out_stride,     \
-                     inv_norm_out, oob_flag)
-  if (nch <= 2) CDML_LAUNCH_GATHER(2);
-  else if (nch <= 4) CDML_LAUNCH_GATHER(4);
-  else if (nch <= 6) CDML_LAUNCH_GATHER(6);
-  else CDML_LAUNCH_GATHER(8);
-#undef CDML_LAUNCH_GATHER
-  return check_launch("gather_rows");
+  const GatherRowsArgs a = {table, row0, n_rows, row_stride, idx, n_idx, F, x_out, out_stride};
+  GatherPlan p;
+  if (int rc = plan_gather_rows("gather_rows", kGatherF32, a, p)) return rc;
+  const int rc = with_nch<kGatherF32, false>("gather_rows", p.nch, [&](auto nch) {
+    hipLaunchKernelGGL(k_gather_rows<decltype(nch)::value>, dim3(p.grid), dim3(kThreads), 0, (hipStream_t)stream, table, row0,
+                       n_rows, row_stride, idx, n_idx, F, normalize, x_out, out_stride, inv_norm_out, oob_flag);
+  });
+  return rc ? rc : check_launch("gather_rows");
 }
 
 // rows AS STORED (fp32, e.g. the receive buffer of the row exchange) -> request order AND the three bf16 planes of the split-fp32
@@ -913,164 +859,63 @@ extern "C" int cdml_gather_rows(const float *table, int64_t row0, int64_t n_rows
 extern "C" int cdml_gather_rows_x3(const float *src, int64_t n_rows, int64_t row_stride, const int32_t *idx, int n_idx, int F,
                                    int flags, uint16_t *x_out_planes, int64_t out_stride, int32_t *oob_flag,
                                    cdml_stream_t stream) {
-  CDML_REQUIRE(src && idx && x_out_planes && n_rows > 0 && n_idx > 0, CDML_E_BADARG, "gather_rows_x3: bad argument");
-  CDML_REQUIRE(F > 0 && F <= 2048, CDML_E_UNSUPPORTED, "gather_rows_x3: feature size %d outside (0, 2048]", F);
-  CDML_REQUIRE(row_stride >= F && (row_stride & 3) == 0 && out_stride % 3 == 0 && out_stride / 3 >= F && ((out_stride / 3) & 3) == 0 &&
-                   aligned16(src) && (reinterpret_cast<uintptr_t>(x_out_planes) & 7) == 0,
-               CDML_E_ALIGN, "gather_rows_x3: out_stride must be 3 planes of >= F columns (multiples of 4), 16-B aligned rows");
-  const int grid = grid_for(n_idx, kWavesPerBlock);
-  const int nch = ((F + 3) / 4 + kWave - 1) / kWave;
-#define CDML_LAUNCH_GRP(N)                                                                                          \
-  hipLaunchKernelGGL(k_gather_rows_planes<N>, dim3(grid), dim3(kThreads), 0, (hipStream_t)stream, src, n_rows, row_stride, \
-                     idx, n_idx, F, flags, reinterpret_cast<__bf16 *>(x_out_planes), out_stride, oob_flag)
-  if (nch <= 2) CDML_LAUNCH_GRP(2);
-  else if (nch <= 4) CDML_LAUNCH_GRP(4);
-  else if (nch <= 6) CDML_LAUNCH_GRP(6);
-  else CDML_LAUNCH_GRP(8);
-#undef CDML_LAUNCH_GRP
-  return check_launch("gather_rows_x3");
+  const GatherRowsArgs a = {src, 0, n_rows, row_stride, idx, n_idx, F, x_out_planes, out_stride};
+  GatherPlan p;
+  if (int rc = plan_gather_rows("gather_rows_x3", kGatherX3, a, p)) return rc;
+  const int rc = with_nch<kGatherX3, false>("gather_rows_x3", p.nch, [&](auto nch) {
+    hipLaunchKernelGGL(k_gather_rows_planes<decltype(nch)::value>, dim3(p.grid), dim3(kThreads), 0, (hipStream_t)stream, src, n_rows,
+                       row_stride, idx, n_idx, F, flags, reinterpret_cast<__bf16 *>(x_out_planes), out_stride, oob_flag);
+  });
+  return rc ? rc : check_launch("gather_rows_x3");
 }
 
-// mode 2 = listed negatives (ln: the listed entry points below); 0 and 1 are cdml_sample_gather's
-static int sample_gather_f32_impl(int mode, const int32_t *pairs, int64_t n_pairs, uint64_t seed,
-                                  uint64_t step, const uint64_t *step_dev, int batch, int64_t slot0,
-                                  int64_t batch_global, const float *table, int64_t n_rows,
-                                  int64_t row_stride, int F, int32_t *idx_out, int32_t *shift_out,
-                                  float *x_out, int64_t out_stride, int n_steps, int64_t x_step_stride,
-                                  int64_t idx_step_stride, int32_t *oob_flag, const ListedNeg &ln, cdml_stream_t stream) {
-  CDML_REQUIRE(n_steps >= 1 && n_steps <= 64, CDML_E_BADARG, "sample_gather: n_steps must be in [1, 64]");
-  CDML_REQUIRE(n_steps == 1 || (x_step_stride >= (int64_t)batch * (mode == 1 ? 2 : 3) * out_stride &&
-                                (x_step_stride & 3) == 0 && idx_step_stride >= (int64_t)batch * (mode == 1 ? 2 : 3)),
-               CDML_E_BADARG, "sample_gather: per-step strides too small for the batch");
-  CDML_REQUIRE(pairs && table && idx_out && x_out && n_pairs > 0 && slot0 >= 0, CDML_E_BADARG,
-               "sample_gather: bad argument");
-  CDML_REQUIRE(n_rows >= 3 && n_rows <= 0x7FFFFFFFll, CDML_E_BADARG,
-               "sample_gather: n_rows must be in [3, 2^31)");
-  CDML_REQUIRE(batch >= (mode == 1 ? 2 : 1), CDML_E_BADARG, "sample_gather: batch too small");
-  CDML_REQUIRE(mode != 1 || shift_out, CDML_E_BADARG, "sample_gather: shift_out required in mode 1");
-  CDML_REQUIRE(batch_global >= slot0 + batch, CDML_E_BADARG,
-               "sample_gather: batch_global < slot0 + batch");
-  int rc = check_gather_layout("sample_gather", table, row_stride, F, x_out, out_stride);
-  if (rc) return rc;
-  const int grid = grid_for((int64_t)batch * (mode == 1 ? 2 : 3) * n_steps, RowF32<6>::kRows * kWavesPerBlock);
-  const int nch = ((F + 3) / 4 + kWave - 1) / kWave;
-#define CDML_LAUNCH_SG(M, N)                                                                      \
-  hipLaunchKernelGGL((k_sample_gather<M, RowF32<N>>), dim3(grid), dim3(kThreads), 0, (hipStream_t)stream, \
-                     pairs, n_pairs, seed, step, step_dev, batch, slot0, batch_global, table,     \
-                     n_rows, row_stride, F, idx_out, shift_out, x_out, out_stride, n_steps,       \
-                     x_step_stride, idx_step_stride, oob_flag, (__bf16 *)nullptr, (int64_t)0, ln)
-  if (mode == 0) {
-    if (nch <= 2) CDML_LAUNCH_SG(0, 2);
-    else if (nch <= 6) CDML_LAUNCH_SG(0, 6);
-    else CDML_LAUNCH_SG(0, 8);
-  } else if (mode == 2) {
-    if (nch <= 2) CDML_LAUNCH_SG(2, 2);
-    else if (nch <= 6) CDML_LAUNCH_SG(2, 6);
-    else CDML_LAUNCH_SG(2, 8);
-  } else {
-    if (nch <= 2) CDML_LAUNCH_SG(1, 2);
-    else if (nch <= 6) CDML_LAUNCH_SG(1, 6);
-    else CDML_LAUNCH_SG(1, 8);
+// The fused launch of one row format: k_sample_gather<MODE, ROW<NCH>, KI> for the plan's mode, bucket and interleaved copy.
+// Mode 2 and KI are instantiated only for the formats that have them.
+template <const GatherFormat &FMT, template <int> class ROW>
+static int sample_gather(const char *who, const SampleGatherArgs &a, cdml_stream_t stream) {
+  static_assert(ROW<8>::kRows * kWavesPerBlock == FMT.rows_per_chunk && ROW<8>::kPerChunk == FMT.per_chunk,
+                "the format describes these row policies");
+  GatherPlan p;
+  if (int rc = plan_sample_gather(who, FMT, a, p)) return rc;
+  ListedNeg ln;
+  if (a.listed) {
+    ln.lists = a.listed->lists, ln.ldl = a.listed->ldl, ln.L = (uint32_t)a.listed->L, ln.hard_thresh = a.listed->hard_thresh;
+    ln.kind_out = a.listed->kind_out, ln.kind_step_stride = a.listed->kind_step_stride;
   }
-#undef CDML_LAUNCH_SG
-  return check_launch("sample_gather");
+  auto launch = [&](auto mode, auto ki) {
+    return with_nch<FMT, true>(who, p.nch, [&](auto nch) {
+      using Row = ROW<decltype(nch)::value>;
+      hipLaunchKernelGGL((k_sample_gather<decltype(mode)::value, Row, decltype(ki)::value>), dim3(p.grid), dim3(kThreads), 0,
+                         (hipStream_t)stream, a.pairs, a.n_pairs, a.seed, a.step, a.step_dev, a.batch, a.slot0, a.batch_global,
+                         static_cast<const typename Row::In *>(a.table), a.n_rows, a.row_stride, a.F, a.idx_out, a.shift_out,
+                         static_cast<typename Row::Out *>(a.x_out), a.out_stride, a.n_steps, a.x_step_stride, a.idx_step_stride,
+                         a.oob_flag, static_cast<__bf16 *>(a.x_ki), a.ki_step_stride, ln);
+    });
+  };
+  auto by_mode = [&](auto ki) {
+    if (a.mode == 0) return launch(std::integral_constant<int, 0>{}, ki);
+    if (a.mode == 1) return launch(std::integral_constant<int, 1>{}, ki);
+    if constexpr (FMT.who_listed != nullptr) return launch(std::integral_constant<int, 2>{}, ki);
+    return fail(CDML_E_UNSUPPORTED, "%s: no kernel for mode %d", who, a.mode);      // (the plan refuses it first)
+  };
+  int rc;
+  if constexpr (FMT.ki) rc = p.ki ? by_mode(std::true_type{}) : by_mode(std::false_type{});
+  else rc = by_mode(std::false_type{});
+  return rc ? rc : check_launch(who);
 }
 
+// The eight fused entry points: fill the struct, plan, launch.  (x_out: fp32 rows | bf16 [rows][3 planes of out_stride / 3 >= F
+// columns] (precision "f32x3") | fp16 [rows][2 planes of x_hat * 2^14] (precision "f16x2") | bf16 rows of an fp16 table.)
 extern "C" int cdml_sample_gather(int mode, const int32_t *pairs, int64_t n_pairs, uint64_t seed,
                                   uint64_t step, const uint64_t *step_dev, int batch, int64_t slot0,
                                   int64_t batch_global, const float *table, int64_t n_rows,
                                   int64_t row_stride, int F, int32_t *idx_out, int32_t *shift_out,
                                   float *x_out, int64_t out_stride, int n_steps, int64_t x_step_stride,
                                   int64_t idx_step_stride, int32_t *oob_flag, cdml_stream_t stream) {
-  CDML_REQUIRE(mode == 0 || mode == 1, CDML_E_BADARG, "sample_gather: mode must be 0 or 1");
-  return sample_gather_f32_impl(mode, pairs, n_pairs, seed, step, step_dev, batch, slot0, batch_global, table, n_rows, row_stride,
-                                F, idx_out, shift_out, x_out, out_stride, n_steps, x_step_stride, idx_step_stride, oob_flag,
-                                ListedNeg(), stream);
-}
-
-// ---- listed negatives (include/cdml_hardneg.h): the fused launch in sampler mode 2, one entry point per row format ----
-static int listed_args(const char *who, const int32_t *lists, int64_t ldl, int L, uint64_t hard_thresh, int32_t *kind_out,
-                       int batch, int n_steps, int64_t kind_step_stride, ListedNeg &ln) {
-  int rc = check_listed(who, lists, ldl, L, hard_thresh);
-  if (rc) return rc;
-  CDML_REQUIRE(!kind_out || n_steps <= 1 || kind_step_stride >= batch, CDML_E_BADARG, "%s: kind_step_stride < batch", who);
-  ln.lists = lists, ln.ldl = ldl, ln.L = (uint32_t)L, ln.hard_thresh = hard_thresh;
-  ln.kind_out = kind_out, ln.kind_step_stride = kind_step_stride;
-  return CDML_OK;
-}
-
-extern "C" int cdml_sample_gather_listed(const int32_t *pairs, int64_t n_pairs, uint64_t seed, uint64_t step,
-                                         const uint64_t *step_dev, int batch, int64_t slot0, int64_t batch_global,
-                                         const float *table, int64_t n_rows, int64_t row_stride, int F,
-                                         const int32_t *lists, int64_t ldl, int L, uint64_t hard_thresh, int32_t *idx_out,
-                                         int32_t *kind_out, float *x_out, int64_t out_stride, int n_steps,
-                                         int64_t x_step_stride, int64_t idx_step_stride, int64_t kind_step_stride,
-                                         int32_t *oob_flag, cdml_stream_t stream) {
-  ListedNeg ln;
-  int rc = listed_args("sample_gather_listed", lists, ldl, L, hard_thresh, kind_out, batch, n_steps, kind_step_stride, ln);
-  if (rc) return rc;
-  return sample_gather_f32_impl(2, pairs, n_pairs, seed, step, step_dev, batch, slot0, batch_global, table, n_rows, row_stride, F,
-                                idx_out, nullptr, x_out, out_stride, n_steps, x_step_stride, idx_step_stride, oob_flag, ln, stream);
-}
-
-// The fused sampler + gather writing each row as three bf16 planes (precision "f32x3"): x_out = bf16
-// [rows][out_stride], out_stride = 3 planes of out_stride / 3 >= F columns each (a multiple of 4).
-static int sample_gather_x3_impl(int mode, const int32_t *pairs, int64_t n_pairs, uint64_t seed,
-                                 uint64_t step, const uint64_t *step_dev, int batch, int64_t slot0,
-                                 int64_t batch_global, const float *table, int64_t n_rows,
-                                 int64_t row_stride, int F, int32_t *idx_out, int32_t *shift_out,
-                                 uint16_t *x_out_planes, int64_t out_stride, int n_steps, int64_t x_step_stride,
-                                 int64_t idx_step_stride, int32_t *oob_flag, uint16_t *x_ki, int64_t ki_step_stride,
-                                 cdml_stream_t stream, const ListedNeg &ln = ListedNeg()) {
-  CDML_REQUIRE(mode == 0 || mode == 1 || (mode == 2 && ln.lists), CDML_E_BADARG, "sample_gather_x3: mode must be 0 or 1");
-  CDML_REQUIRE(n_steps >= 1 && n_steps <= 64, CDML_E_BADARG, "sample_gather_x3: n_steps must be in [1, 64]");
-  const int rpt = mode == 1 ? 2 : 3;
-  CDML_REQUIRE(n_steps == 1 || (x_step_stride >= (int64_t)batch * rpt * out_stride && (x_step_stride & 3) == 0 &&
-                                idx_step_stride >= (int64_t)batch * rpt),
-               CDML_E_BADARG, "sample_gather_x3: per-step strides too small for the batch");
-  CDML_REQUIRE(pairs && table && idx_out && x_out_planes && n_pairs > 0 && slot0 >= 0, CDML_E_BADARG,
-               "sample_gather_x3: bad argument");
-  CDML_REQUIRE(n_rows >= 3 && n_rows <= 0x7FFFFFFFll, CDML_E_BADARG, "sample_gather_x3: n_rows must be in [3, 2^31)");
-  CDML_REQUIRE(batch >= (mode == 1 ? 2 : 1), CDML_E_BADARG, "sample_gather_x3: batch too small");
-  CDML_REQUIRE(mode != 1 || shift_out, CDML_E_BADARG, "sample_gather_x3: shift_out required in mode 1");
-  CDML_REQUIRE(batch_global >= slot0 + batch, CDML_E_BADARG, "sample_gather_x3: batch_global < slot0 + batch");
-  CDML_REQUIRE(F > 0 && F <= 2048, CDML_E_UNSUPPORTED, "sample_gather_x3: feature size %d outside (0, 2048]", F);
-  CDML_REQUIRE(row_stride >= F && (row_stride & 3) == 0 && out_stride % 3 == 0 && out_stride / 3 >= F &&
-                   ((out_stride / 3) & 3) == 0 && aligned16(table) && (reinterpret_cast<uintptr_t>(x_out_planes) & 7) == 0,
-               CDML_E_ALIGN, "sample_gather_x3: out_stride must be 3 planes of >= F columns (multiples of 4)");
-  const int grid = grid_for((int64_t)batch * rpt * n_steps, RowF32X3<6>::kRows * kWavesPerBlock);
-  const int nch = ((F + 3) / 4 + kWave - 1) / kWave;
-  const int plane = (int)(out_stride / 3);
-  if (x_ki) {
-    // the interleaved copy: [3][rows_per_step / 8][plane][8] per step; whole row groups per step, plane in 256-column slices
-    // that the row registers cover (NCH x 256 columns)
-    CDML_REQUIRE(((int64_t)batch * rpt) % 8 == 0 && plane % 256 == 0 && plane <= (nch <= 6 ? 6 : 8) * 256 && aligned16(x_ki) &&
-                     (n_steps == 1 || ki_step_stride >= (int64_t)3 * batch * rpt * plane) && RowF32X3<6>::kRows * kWavesPerBlock == 8,
-                 CDML_E_UNSUPPORTED, "sample_gather_x3k: needs 8 | rows per step, plane columns a multiple of 256 (<= %d), 16-B aligned x_ki",
-                 (nch <= 6 ? 6 : 8) * 256);
-  }
-#define CDML_LAUNCH_SGX(M, N, KI)                                                                              \
-  hipLaunchKernelGGL((k_sample_gather<M, RowF32X3<N>, KI>), dim3(grid), dim3(kThreads), 0, (hipStream_t)stream, \
-                     pairs, n_pairs, seed, step, step_dev, batch, slot0, batch_global, table,               \
-                     n_rows, row_stride, F, idx_out, shift_out, reinterpret_cast<__bf16 *>(x_out_planes),   \
-                     out_stride, n_steps, x_step_stride, idx_step_stride, oob_flag, reinterpret_cast<__bf16 *>(x_ki), ki_step_stride, ln)
-  if (x_ki) {
-    if (mode == 0) {
-      if (nch <= 6) CDML_LAUNCH_SGX(0, 6, true); else CDML_LAUNCH_SGX(0, 8, true);
-    } else if (mode == 2) {
-      if (nch <= 6) CDML_LAUNCH_SGX(2, 6, true); else CDML_LAUNCH_SGX(2, 8, true);
-    } else {
-      if (nch <= 6) CDML_LAUNCH_SGX(1, 6, true); else CDML_LAUNCH_SGX(1, 8, true);
-    }
-  } else if (mode == 0) {
-    if (nch <= 6) CDML_LAUNCH_SGX(0, 6, false); else CDML_LAUNCH_SGX(0, 8, false);
-  } else if (mode == 2) {
-    if (nch <= 6) CDML_LAUNCH_SGX(2, 6, false); else CDML_LAUNCH_SGX(2, 8, false);
-  } else {
-    if (nch <= 6) CDML_LAUNCH_SGX(1, 6, false); else CDML_LAUNCH_SGX(1, 8, false);
-  }
-#undef CDML_LAUNCH_SGX
-  return check_launch("sample_gather_x3");
+  const SampleGatherArgs a = {mode, pairs, n_pairs, seed, step, step_dev, batch, slot0, batch_global, table, n_rows, row_stride, F,
+                              idx_out, shift_out, x_out, out_stride, n_steps, x_step_stride, idx_step_stride, oob_flag,
+                              nullptr, 0, false, nullptr};
+  return sample_gather<kGatherF32, RowF32>("sample_gather", a, stream);
 }
 
 extern "C" int cdml_sample_gather_x3(int mode, const int32_t *pairs, int64_t n_pairs, uint64_t seed,
@@ -1079,9 +924,10 @@ extern "C" int cdml_sample_gather_x3(int mode, const int32_t *pairs, int64_t n_p
                                      int64_t row_stride, int F, int32_t *idx_out, int32_t *shift_out,
                                      uint16_t *x_out_planes, int64_t out_stride, int n_steps, int64_t x_step_stride,
                                      int64_t idx_step_stride, int32_t *oob_flag, cdml_stream_t stream) {
-  return sample_gather_x3_impl(mode, pairs, n_pairs, seed, step, step_dev, batch, slot0, batch_global, table, n_rows, row_stride, F,
-                               idx_out, shift_out, x_out_planes, out_stride, n_steps, x_step_stride, idx_step_stride, oob_flag,
-                               nullptr, 0, stream);
+  const SampleGatherArgs a = {mode, pairs, n_pairs, seed, step, step_dev, batch, slot0, batch_global, table, n_rows, row_stride, F,
+                              idx_out, shift_out, x_out_planes, out_stride, n_steps, x_step_stride, idx_step_stride, oob_flag,
+                              nullptr, 0, false, nullptr};
+  return sample_gather<kGatherX3, RowF32X3>("sample_gather_x3", a, stream);
 }
 
 // cdml_sample_gather_x3 that ALSO writes every step's rows k8-interleaved (x_ki: bf16 [3][rows per step / 8][out_stride / 3][8]
@@ -1093,13 +939,54 @@ extern "C" int cdml_sample_gather_x3k(int mode, const int32_t *pairs, int64_t n_
                                       uint16_t *x_out_planes, int64_t out_stride, int n_steps, int64_t x_step_stride,
                                       int64_t idx_step_stride, int32_t *oob_flag, uint16_t *x_ki, int64_t ki_step_stride,
                                       cdml_stream_t stream) {
-  CDML_REQUIRE(x_ki, CDML_E_BADARG, "sample_gather_x3k: x_ki required (cdml_sample_gather_x3 without it)");
-  return sample_gather_x3_impl(mode, pairs, n_pairs, seed, step, step_dev, batch, slot0, batch_global, table, n_rows, row_stride, F,
-                               idx_out, shift_out, x_out_planes, out_stride, n_steps, x_step_stride, idx_step_stride, oob_flag,
-                               x_ki, ki_step_stride, stream);
+  const SampleGatherArgs a = {mode, pairs, n_pairs, seed, step, step_dev, batch, slot0, batch_global, table, n_rows, row_stride, F,
+                              idx_out, shift_out, x_out_planes, out_stride, n_steps, x_step_stride, idx_step_stride, oob_flag,
+                              x_ki, ki_step_stride, true, nullptr};
+  return sample_gather<kGatherX3, RowF32X3>("sample_gather_x3", a, stream);
 }
 
-// listed negatives, three-plane rows; x_ki null = no k8-interleaved copy (cdml_sample_gather_x3's form), else _x3k's
+extern "C" int cdml_sample_gather_h2(int mode, const int32_t *pairs, int64_t n_pairs, uint64_t seed,
+                                     uint64_t step, const uint64_t *step_dev, int batch, int64_t slot0,
+                                     int64_t batch_global, const float *table, int64_t n_rows,
+                                     int64_t row_stride, int F, int32_t *idx_out, int32_t *shift_out,
+                                     uint16_t *x_out_planes, int64_t out_stride, int n_steps, int64_t x_step_stride,
+                                     int64_t idx_step_stride, int32_t *oob_flag, cdml_stream_t stream) {
+  const SampleGatherArgs a = {mode, pairs, n_pairs, seed, step, step_dev, batch, slot0, batch_global, table, n_rows, row_stride, F,
+                              idx_out, shift_out, x_out_planes, out_stride, n_steps, x_step_stride, idx_step_stride, oob_flag,
+                              nullptr, 0, false, nullptr};
+  return sample_gather<kGatherH2, RowF32H2>("sample_gather_h2", a, stream);
+}
+
+extern "C" int cdml_sample_gather_f16(int mode, const int32_t *pairs, int64_t n_pairs, uint64_t seed,
+                                      uint64_t step, const uint64_t *step_dev, int batch, int64_t slot0,
+                                      int64_t batch_global, const uint16_t *table, int64_t n_rows,
+                                      int64_t row_stride, int F, int32_t *idx_out, int32_t *shift_out,
+                                      uint16_t *x_out_bf16, int64_t out_stride, int n_steps,
+                                      int64_t x_step_stride, int64_t idx_step_stride, int32_t *oob_flag,
+                                      cdml_stream_t stream) {
+  const SampleGatherArgs a = {mode, pairs, n_pairs, seed, step, step_dev, batch, slot0, batch_global, table, n_rows, row_stride, F,
+                              idx_out, shift_out, x_out_bf16, out_stride, n_steps, x_step_stride, idx_step_stride, oob_flag,
+                              nullptr, 0, false, nullptr};
+  return sample_gather<kGatherF16, RowF16>("sample_gather_f16", a, stream);
+}
+
+// ---- listed negatives (include/cdml_hardneg.h): the fused launch in sampler mode 2, one entry point per row format that has
+// one; the common checks report under the format's unlisted name ----
+extern "C" int cdml_sample_gather_listed(const int32_t *pairs, int64_t n_pairs, uint64_t seed, uint64_t step,
+                                         const uint64_t *step_dev, int batch, int64_t slot0, int64_t batch_global,
+                                         const float *table, int64_t n_rows, int64_t row_stride, int F,
+                                         const int32_t *lists, int64_t ldl, int L, uint64_t hard_thresh, int32_t *idx_out,
+                                         int32_t *kind_out, float *x_out, int64_t out_stride, int n_steps,
+                                         int64_t x_step_stride, int64_t idx_step_stride, int64_t kind_step_stride,
+                                         int32_t *oob_flag, cdml_stream_t stream) {
+  const ListedArgs l = {lists, ldl, L, hard_thresh, kind_out, kind_step_stride};
+  const SampleGatherArgs a = {2, pairs, n_pairs, seed, step, step_dev, batch, slot0, batch_global, table, n_rows, row_stride, F,
+                              idx_out, nullptr, x_out, out_stride, n_steps, x_step_stride, idx_step_stride, oob_flag,
+                              nullptr, 0, false, &l};
+  return sample_gather<kGatherF32, RowF32>("sample_gather", a, stream);
+}
+
+// three-plane rows; x_ki null = no k8-interleaved copy (cdml_sample_gather_x3's form), else _x3k's
 extern "C" int cdml_sample_gather_listed_x3(const int32_t *pairs, int64_t n_pairs, uint64_t seed, uint64_t step,
                                             const uint64_t *step_dev, int batch, int64_t slot0, int64_t batch_global,
                                             const float *table, int64_t n_rows, int64_t row_stride, int F,
@@ -1108,52 +995,26 @@ extern "C" int cdml_sample_gather_listed_x3(const int32_t *pairs, int64_t n_pair
                                             int n_steps, int64_t x_step_stride, int64_t idx_step_stride,
                                             int64_t kind_step_stride, int32_t *oob_flag, uint16_t *x_ki,
                                             int64_t ki_step_stride, cdml_stream_t stream) {
-  ListedNeg ln;
-  int rc = listed_args("sample_gather_listed_x3", lists, ldl, L, hard_thresh, kind_out, batch, n_steps, kind_step_stride, ln);
-  if (rc) return rc;
-  return sample_gather_x3_impl(2, pairs, n_pairs, seed, step, step_dev, batch, slot0, batch_global, table, n_rows, row_stride, F,
-                               idx_out, nullptr, x_out_planes, out_stride, n_steps, x_step_stride, idx_step_stride, oob_flag,
-                               x_ki, ki_step_stride, stream, ln);
+  const ListedArgs l = {lists, ldl, L, hard_thresh, kind_out, kind_step_stride};
+  const SampleGatherArgs a = {2, pairs, n_pairs, seed, step, step_dev, batch, slot0, batch_global, table, n_rows, row_stride, F,
+                              idx_out, nullptr, x_out_planes, out_stride, n_steps, x_step_stride, idx_step_stride, oob_flag,
+                              x_ki, ki_step_stride, false, &l};
+  return sample_gather<kGatherX3, RowF32X3>("sample_gather_x3", a, stream);
 }
 
-// The fused sampler + gather writing each row as the two fp16 planes of x_hat * 2^14 (precision "f16x2"): x_out = fp16
-// [rows][out_stride], out_stride = 2 planes of out_stride / 2 >= F columns each (a multiple of 4).
-extern "C" int cdml_sample_gather_h2(int mode, const int32_t *pairs, int64_t n_pairs, uint64_t seed,
-                                     uint64_t step, const uint64_t *step_dev, int batch, int64_t slot0,
-                                     int64_t batch_global, const float *table, int64_t n_rows,
-                                     int64_t row_stride, int F, int32_t *idx_out, int32_t *shift_out,
-                                     uint16_t *x_out_planes, int64_t out_stride, int n_steps, int64_t x_step_stride,
-                                     int64_t idx_step_stride, int32_t *oob_flag, cdml_stream_t stream) {
-  CDML_REQUIRE(mode == 0 || mode == 1, CDML_E_BADARG, "sample_gather_h2: mode must be 0 or 1");
-  CDML_REQUIRE(n_steps >= 1 && n_steps <= 64, CDML_E_BADARG, "sample_gather_h2: n_steps must be in [1, 64]");
-  const int rpt = mode == 0 ? 3 : 2;
-  CDML_REQUIRE(n_steps == 1 || (x_step_stride >= (int64_t)batch * rpt * out_stride && (x_step_stride & 3) == 0 &&
-                                idx_step_stride >= (int64_t)batch * rpt),
-               CDML_E_BADARG, "sample_gather_h2: per-step strides too small for the batch");
-  CDML_REQUIRE(pairs && table && idx_out && x_out_planes && n_pairs > 0 && slot0 >= 0, CDML_E_BADARG,
-               "sample_gather_h2: bad argument");
-  CDML_REQUIRE(n_rows >= 3 && n_rows <= 0x7FFFFFFFll, CDML_E_BADARG, "sample_gather_h2: n_rows must be in [3, 2^31)");
-  CDML_REQUIRE(batch >= (mode == 1 ? 2 : 1), CDML_E_BADARG, "sample_gather_h2: batch too small");
-  CDML_REQUIRE(mode == 0 || shift_out, CDML_E_BADARG, "sample_gather_h2: shift_out required in mode 1");
-  CDML_REQUIRE(batch_global >= slot0 + batch, CDML_E_BADARG, "sample_gather_h2: batch_global < slot0 + batch");
-  CDML_REQUIRE(F > 0 && F <= 2048, CDML_E_UNSUPPORTED, "sample_gather_h2: feature size %d outside (0, 2048]", F);
-  CDML_REQUIRE(row_stride >= F && (row_stride & 3) == 0 && out_stride % 2 == 0 && out_stride / 2 >= F &&
-                   ((out_stride / 2) & 3) == 0 && aligned16(table) && (reinterpret_cast<uintptr_t>(x_out_planes) & 7) == 0,
-               CDML_E_ALIGN, "sample_gather_h2: out_stride must be 2 planes of >= F columns (multiples of 4)");
-  const int grid = grid_for((int64_t)batch * rpt * n_steps, RowF32H2<6>::kRows * kWavesPerBlock);
-  const int nch = ((F + 3) / 4 + kWave - 1) / kWave;
-#define CDML_LAUNCH_SGH2(M, N)                                                                             \
-  hipLaunchKernelGGL((k_sample_gather<M, RowF32H2<N>>), dim3(grid), dim3(kThreads), 0, (hipStream_t)stream, \
-                     pairs, n_pairs, seed, step, step_dev, batch, slot0, batch_global, table,               \
-                     n_rows, row_stride, F, idx_out, shift_out, reinterpret_cast<_Float16 *>(x_out_planes), \
-                     out_stride, n_steps, x_step_stride, idx_step_stride, oob_flag)
-  if (mode == 0) {
-    if (nch <= 6) CDML_LAUNCH_SGH2(0, 6); else CDML_LAUNCH_SGH2(0, 8);
-  } else {
-    if (nch <= 6) CDML_LAUNCH_SGH2(1, 6); else CDML_LAUNCH_SGH2(1, 8);
-  }
-#undef CDML_LAUNCH_SGH2
-  return check_launch("sample_gather_h2");
+// fp16 table -> bf16 rows
+extern "C" int cdml_sample_gather_listed_f16(const int32_t *pairs, int64_t n_pairs, uint64_t seed, uint64_t step,
+                                             const uint64_t *step_dev, int batch, int64_t slot0, int64_t batch_global,
+                                             const uint16_t *table, int64_t n_rows, int64_t row_stride, int F,
+                                             const int32_t *lists, int64_t ldl, int L, uint64_t hard_thresh,
+                                             int32_t *idx_out, int32_t *kind_out, uint16_t *x_out_bf16, int64_t out_stride,
+                                             int n_steps, int64_t x_step_stride, int64_t idx_step_stride,
+                                             int64_t kind_step_stride, int32_t *oob_flag, cdml_stream_t stream) {
+  const ListedArgs l = {lists, ldl, L, hard_thresh, kind_out, kind_step_stride};
+  const SampleGatherArgs a = {2, pairs, n_pairs, seed, step, step_dev, batch, slot0, batch_global, table, n_rows, row_stride, F,
+                              idx_out, nullptr, x_out_bf16, out_stride, n_steps, x_step_stride, idx_step_stride, oob_flag,
+                              nullptr, 0, false, &l};
+  return sample_gather<kGatherF16, RowF16>("sample_gather_f16", a, stream);
 }
 
 extern "C" int cdml_route_rows(const int32_t *ids, int n, int64_t rows_per_shard, int world, int capacity,
@@ -1177,74 +1038,4 @@ extern "C" int cdml_scatter_rows(const float *src, int64_t ld_src, const int32_t
   hipLaunchKernelGGL(k_scatter_rows, dim3(grid_for(n, kWavesPerBlock)), dim3(kThreads), 0, (hipStream_t)stream, src,
                      ld_src, slot, n, width, dst, ld_dst);
   return check_launch("scatter_rows");
-}
-
-static int sample_gather_f16_impl(int mode, const int32_t *pairs, int64_t n_pairs, uint64_t seed,
-                                  uint64_t step, const uint64_t *step_dev, int batch, int64_t slot0,
-                                  int64_t batch_global, const uint16_t *table, int64_t n_rows,
-                                  int64_t row_stride, int F, int32_t *idx_out, int32_t *shift_out,
-                                  uint16_t *x_out_bf16, int64_t out_stride, int n_steps,
-                                  int64_t x_step_stride, int64_t idx_step_stride, int32_t *oob_flag,
-                                  const ListedNeg &ln, cdml_stream_t stream) {
-  CDML_REQUIRE(pairs && table && idx_out && x_out_bf16 && n_pairs > 0 && slot0 >= 0, CDML_E_BADARG,
-               "sample_gather_f16: bad argument");
-  CDML_REQUIRE(n_rows >= 3 && n_rows <= 0x7FFFFFFFll, CDML_E_BADARG, "sample_gather_f16: n_rows must be in [3, 2^31)");
-  CDML_REQUIRE(batch >= (mode == 1 ? 2 : 1), CDML_E_BADARG, "sample_gather_f16: batch too small");
-  CDML_REQUIRE(mode != 1 || shift_out, CDML_E_BADARG, "sample_gather_f16: shift_out required in mode 1");
-  CDML_REQUIRE(batch_global >= slot0 + batch, CDML_E_BADARG, "sample_gather_f16: batch_global < slot0 + batch");
-  CDML_REQUIRE(n_steps >= 1 && n_steps <= 64, CDML_E_BADARG, "sample_gather_f16: n_steps must be in [1, 64]");
-  const int rpt = mode == 1 ? 2 : 3;
-  CDML_REQUIRE(n_steps == 1 || (x_step_stride >= (int64_t)batch * rpt * out_stride && (x_step_stride & 7) == 0 &&
-                                idx_step_stride >= (int64_t)batch * rpt),
-               CDML_E_BADARG, "sample_gather_f16: per-step strides too small for the batch");
-  CDML_REQUIRE(F > 0 && F <= 4096, CDML_E_UNSUPPORTED, "sample_gather_f16: feature size outside (0, 4096]");
-  CDML_REQUIRE(row_stride >= F && (row_stride & 7) == 0 && out_stride >= F && (out_stride & 7) == 0 &&
-                   aligned16(table) && aligned16(x_out_bf16),
-               CDML_E_ALIGN, "sample_gather_f16: strides must be >= F and multiples of 8, bases 16-B aligned");
-  const int grid = grid_for((int64_t)batch * rpt * n_steps, RowF16<3>::kRows * kWavesPerBlock);
-  const int nch = ((F + 7) / 8 + kWave - 1) / kWave;
-#define CDML_LAUNCH_SGH(M, N)                                                                               \
-  hipLaunchKernelGGL((k_sample_gather<M, RowF16<N>>), dim3(grid), dim3(kThreads), 0, (hipStream_t)stream,   \
-                     pairs, n_pairs, seed, step, step_dev, batch, slot0, batch_global,                       \
-                     reinterpret_cast<const _Float16 *>(table), n_rows, row_stride, F, idx_out, shift_out,   \
-                     reinterpret_cast<__bf16 *>(x_out_bf16), out_stride, n_steps, x_step_stride, idx_step_stride, \
-                     oob_flag, (__bf16 *)nullptr, (int64_t)0, ln)
-  if (mode == 0) {
-    if (nch <= 1) CDML_LAUNCH_SGH(0, 1); else if (nch <= 3) CDML_LAUNCH_SGH(0, 3); else CDML_LAUNCH_SGH(0, 8);
-  } else if (mode == 2) {
-    if (nch <= 1) CDML_LAUNCH_SGH(2, 1); else if (nch <= 3) CDML_LAUNCH_SGH(2, 3); else CDML_LAUNCH_SGH(2, 8);
-  } else {
-    if (nch <= 1) CDML_LAUNCH_SGH(1, 1); else if (nch <= 3) CDML_LAUNCH_SGH(1, 3); else CDML_LAUNCH_SGH(1, 8);
-  }
-#undef CDML_LAUNCH_SGH
-  return check_launch("sample_gather_f16");
-}
-
-extern "C" int cdml_sample_gather_f16(int mode, const int32_t *pairs, int64_t n_pairs, uint64_t seed,
-                                      uint64_t step, const uint64_t *step_dev, int batch, int64_t slot0,
-                                      int64_t batch_global, const uint16_t *table, int64_t n_rows,
-                                      int64_t row_stride, int F, int32_t *idx_out, int32_t *shift_out,
-                                      uint16_t *x_out_bf16, int64_t out_stride, int n_steps,
-                                      int64_t x_step_stride, int64_t idx_step_stride, int32_t *oob_flag,
-                                      cdml_stream_t stream) {
-  CDML_REQUIRE(mode == 0 || mode == 1, CDML_E_BADARG, "sample_gather_f16: mode must be 0 or 1");
-  return sample_gather_f16_impl(mode, pairs, n_pairs, seed, step, step_dev, batch, slot0, batch_global, table, n_rows, row_stride,
-                                F, idx_out, shift_out, x_out_bf16, out_stride, n_steps, x_step_stride, idx_step_stride, oob_flag,
-                                ListedNeg(), stream);
-}
-
-// listed negatives, fp16 table -> bf16 rows
-extern "C" int cdml_sample_gather_listed_f16(const int32_t *pairs, int64_t n_pairs, uint64_t seed, uint64_t step,
-                                             const uint64_t *step_dev, int batch, int64_t slot0, int64_t batch_global,
-                                             const uint16_t *table, int64_t n_rows, int64_t row_stride, int F,
-                                             const int32_t *lists, int64_t ldl, int L, uint64_t hard_thresh,
-                                             int32_t *idx_out, int32_t *kind_out, uint16_t *x_out_bf16, int64_t out_stride,
-                                             int n_steps, int64_t x_step_stride, int64_t idx_step_stride,
-                                             int64_t kind_step_stride, int32_t *oob_flag, cdml_stream_t stream) {
-  ListedNeg ln;
-  int rc = listed_args("sample_gather_listed_f16", lists, ldl, L, hard_thresh, kind_out, batch, n_steps, kind_step_stride, ln);
-  if (rc) return rc;
-  return sample_gather_f16_impl(2, pairs, n_pairs, seed, step, step_dev, batch, slot0, batch_global, table, n_rows, row_stride, F,
-                                idx_out, nullptr, x_out_bf16, out_stride, n_steps, x_step_stride, idx_step_stride, oob_flag, ln,
-                                stream);
 }

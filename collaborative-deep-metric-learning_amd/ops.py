@@ -89,6 +89,45 @@ def gather_rows_x3(src, idx, feature_size, x_out_planes, nan_missing=False, oob_
     return x_out_planes
 
 
+def _gather_format(table, x_out):
+    """The suffix of the row format's entry points, from the types: fp16 table -> bf16 rows ("_f16", config 4); fp32 table ->
+    fp32 rows (""), rows as three bf16 planes ("_x3", precision f32x3) or as two fp16 planes of x_hat * 2^14 ("_h2", f16x2)."""
+    if table.dtype == torch.float16:
+        return "_f16"
+    return {torch.bfloat16: "_x3", torch.float16: "_h2"}.get(x_out.dtype, "")
+
+
+def _gather_io(fmt, table, x_out, idx_out, n_steps, x_ki, x_ki_errors, kind_out=None, batch=0, lists=None):
+    """What a fused sampler + gather launch derives from its tensors: (table pointer and leading dimension, x_out pointer and
+    leading dimension, the per-step strides of x_out / idx_out / kind_out / x_ki, the listed draw's arguments or None).
+    x_ki_errors: the caller's words for (x_ki with a format that has none, x_ki that is no contiguous bf16 buffer);
+    lists: (lists, hard_fraction) of a listed launch, checked where that launch has always checked them."""
+    tp, tld = (_mat16 if fmt == "_f16" else _mat)(table)
+    listed = None if lists is None else _lists_args(lists[0], table.shape[0], lists[1])
+    omat = _mat16 if fmt else _mat
+    if n_steps > 1:
+        if x_out.dim() != 3 or idx_out.dim() != 2 or x_out.shape[0] != n_steps or idx_out.shape[0] != n_steps:
+            raise ValueError("n_steps > 1 needs x_out [n_steps, rows, stride] and idx_out [n_steps, rows]")
+        if kind_out is not None and (kind_out.dim() != 2 or kind_out.shape[0] != n_steps or kind_out.stride(1) != 1):
+            raise ValueError("n_steps > 1 needs kind_out [n_steps, batch]")
+        xp, xld = omat(x_out[0])
+        xss, iss = x_out.stride(0), idx_out.stride(0)
+        kss = kind_out.stride(0) if kind_out is not None else 0
+    else:
+        xp, xld = omat(x_out)
+        xss = iss = kss = 0
+    if kind_out is not None and kind_out.numel() < n_steps * batch:
+        raise ValueError("kind_out needs one int32 per triplet")
+    kis = 0
+    if x_ki is not None:
+        if fmt != "_x3":
+            raise ValueError(x_ki_errors[0])
+        if x_ki.dtype != torch.bfloat16 or not x_ki.is_contiguous():
+            raise ValueError(x_ki_errors[1])
+        kis = x_ki.stride(0) if (n_steps > 1 and x_ki.dim() > 1) else 0
+    return (tp, tld), (xp, xld), (xss, iss, kss, kis), listed
+
+
 def sample_gather(mode, pairs, seed, step, batch, table, feature_size, idx_out, x_out,
                   shift_out=None, slot0=0, batch_global=None, step_dev=None, n_steps=1, oob_flag=None, x_ki=None):
     """n_steps > 1: x_out is [n_steps, rows, stride], idx_out [n_steps, rows], shift_out [n_steps]
@@ -96,34 +135,14 @@ def sample_gather(mode, pairs, seed, step, batch, table, feature_size, idx_out, 
     outside the catalogue (the reference's IndexError, inputs.py:158).  x_ki (three-plane output only): a contiguous
     bf16 buffer [n_steps, 3 * rows * plane] that also receives every step's rows k8-interleaved."""
     bg = batch if batch_global is None else batch_global
-    f16 = table.dtype == torch.float16              # fp16 catalogue -> bf16 rows (config 4)
-    x3 = not f16 and x_out.dtype == torch.bfloat16   # fp32 catalogue -> rows as three bf16 planes (precision f32x3)
-    h2 = not f16 and x_out.dtype == torch.float16    # fp32 catalogue -> rows as two fp16 planes of x_hat * 2^14 (precision f16x2)
-    mat = _mat16 if f16 else _mat
-    omat = _mat16 if (f16 or x3 or h2) else _mat
-    tp, tld = mat(table)
-    if n_steps > 1:
-        if x_out.dim() != 3 or idx_out.dim() != 2 or x_out.shape[0] != n_steps or idx_out.shape[0] != n_steps:
-            raise ValueError("n_steps > 1 needs x_out [n_steps, rows, stride] and idx_out [n_steps, rows]")
-        xp, xld = omat(x_out[0])
-        xss, iss = x_out.stride(0), idx_out.stride(0)
-    else:
-        xp, xld = omat(x_out)
-        xss = iss = 0
-    if x_ki is not None:
-        if not x3 or x_ki.dtype != torch.bfloat16 or not x_ki.is_contiguous():
-            raise ValueError("x_ki goes with the three-plane output and must be a contiguous bf16 buffer")
-        kss = x_ki.stride(0) if (n_steps > 1 and x_ki.dim() > 1) else 0
-        call("cdml_sample_gather_x3k", mode, _p(pairs, torch.int32), pairs.shape[0], seed,
-             0 if step is None else step, _p(step_dev, torch.int64), batch, slot0, bg, tp,
-             table.shape[0], tld, feature_size, _p(idx_out, torch.int32), _p(shift_out, torch.int32),
-             xp, xld, n_steps, xss, iss, _p(oob_flag, torch.int32), C.c_void_p(x_ki.data_ptr()), kss, _stream())
-        return x_out
-    call("cdml_sample_gather_f16" if f16 else "cdml_sample_gather_x3" if x3 else "cdml_sample_gather_h2" if h2 else "cdml_sample_gather",
-         mode, _p(pairs, torch.int32), pairs.shape[0], seed,
+    fmt = _gather_format(table, x_out)
+    (tp, tld), (xp, xld), (xss, iss, _, kis), _ = _gather_io(
+        fmt, table, x_out, idx_out, n_steps, x_ki, ("x_ki goes with the three-plane output and must be a contiguous bf16 buffer",) * 2)
+    ki = () if x_ki is None else (C.c_void_p(x_ki.data_ptr()), kis)
+    call("cdml_sample_gather" + (fmt if x_ki is None else "_x3k"), mode, _p(pairs, torch.int32), pairs.shape[0], seed,
          0 if step is None else step, _p(step_dev, torch.int64), batch, slot0, bg, tp,
          table.shape[0], tld, feature_size, _p(idx_out, torch.int32), _p(shift_out, torch.int32),
-         xp, xld, n_steps, xss, iss, _p(oob_flag, torch.int32), _stream())
+         xp, xld, n_steps, xss, iss, _p(oob_flag, torch.int32), *ki, _stream())
     return x_out
 
 
@@ -161,41 +180,17 @@ def sample_gather_listed(pairs, seed, step, batch, table, feature_size, lists, h
     x_out's types as there (fp32 rows, three bf16 planes with or without x_ki, fp16 table -> bf16 rows; the two-fp16-plane
     output has no listed form).  kind_out: int32 [batch], or [n_steps, batch] with n_steps > 1."""
     bg = batch if batch_global is None else batch_global
-    f16 = table.dtype == torch.float16
-    x3 = not f16 and x_out.dtype == torch.bfloat16
-    if not f16 and x_out.dtype == torch.float16:
+    fmt = _gather_format(table, x_out)
+    if fmt == "_h2":
         raise ValueError("the two-fp16-plane rows (precision 'f16x2') have no listed form")
-    mat = _mat16 if f16 else _mat
-    omat = _mat16 if (f16 or x3) else _mat
-    tp, tld = mat(table)
-    lp, ldl, L, thresh = _lists_args(lists, table.shape[0], hard_fraction)
-    if n_steps > 1:
-        if x_out.dim() != 3 or idx_out.dim() != 2 or x_out.shape[0] != n_steps or idx_out.shape[0] != n_steps:
-            raise ValueError("n_steps > 1 needs x_out [n_steps, rows, stride] and idx_out [n_steps, rows]")
-        if kind_out is not None and (kind_out.dim() != 2 or kind_out.shape[0] != n_steps or kind_out.stride(1) != 1):
-            raise ValueError("n_steps > 1 needs kind_out [n_steps, batch]")
-        xp, xld = omat(x_out[0])
-        xss, iss = x_out.stride(0), idx_out.stride(0)
-        kss = kind_out.stride(0) if kind_out is not None else 0
-    else:
-        xp, xld = omat(x_out)
-        xss = iss = kss = 0
-    if kind_out is not None and kind_out.numel() < n_steps * batch:
-        raise ValueError("kind_out needs one int32 per triplet")
-    head = (_p(pairs, torch.int32), pairs.shape[0], seed, 0 if step is None else step, _p(step_dev, torch.int64), batch, slot0,
-            bg, tp, table.shape[0], tld, feature_size, lp, ldl, L, thresh, _p(idx_out, torch.int32),
-            _p(kind_out, torch.int32), xp, xld, n_steps, xss, iss, kss, _p(oob_flag, torch.int32))
-    if x3:
-        kis = 0
-        if x_ki is not None:
-            if x_ki.dtype != torch.bfloat16 or not x_ki.is_contiguous():
-                raise ValueError("x_ki must be a contiguous bf16 buffer")
-            kis = x_ki.stride(0) if (n_steps > 1 and x_ki.dim() > 1) else 0
-        call("cdml_sample_gather_listed_x3", *head, _p(x_ki), kis, _stream())
-        return x_out
-    if x_ki is not None:
-        raise ValueError("x_ki goes with the three-plane output")
-    call("cdml_sample_gather_listed_f16" if f16 else "cdml_sample_gather_listed", *head, _stream())
+    (tp, tld), (xp, xld), (xss, iss, kss, kis), (lp, ldl, L, thresh) = _gather_io(
+        fmt, table, x_out, idx_out, n_steps, x_ki, ("x_ki goes with the three-plane output", "x_ki must be a contiguous bf16 buffer"),
+        kind_out, batch, (lists, hard_fraction))
+    ki = (_p(x_ki), kis) if fmt == "_x3" else ()
+    call("cdml_sample_gather_listed" + fmt, _p(pairs, torch.int32), pairs.shape[0], seed, 0 if step is None else step,
+         _p(step_dev, torch.int64), batch, slot0, bg, tp, table.shape[0], tld, feature_size, lp, ldl, L, thresh,
+         _p(idx_out, torch.int32), _p(kind_out, torch.int32), xp, xld, n_steps, xss, iss, kss, _p(oob_flag, torch.int32), *ki,
+         _stream())
     return x_out
 
 

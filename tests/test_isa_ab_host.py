@@ -75,3 +75,14 @@ def test_missing_kernel_differs():
     assert not _same(b, A)
     # two copies of one body are two kernels: a multiset, not a set
     assert not _same(_file([_kernel("_Z1xv", 0), _kernel("_Z1yv", 1)]), _file([_kernel("_Z1xv", 0)]))
+
+
+def test_names_are_compared_as_multisets_of_demangled_names():
+    """--names: equal bodies under other names (which the body comparison accepts) differ; order does not"""
+    a = isa_ab.demangled(["_Z1aILb1ELi3EEvv", "_Z1bv"])
+    assert a == ["void a<true, 3>()", "b()"]
+    report, ok = isa_ab.compare_names(a, a[::-1])
+    assert ok and report == ["names: the same 2 demangled kernel names"]
+    report, ok = isa_ab.compare_names(a, isa_ab.demangled(["_Z1aI7VariantILb1ELi3EEEvv", "_Z1bv"]))
+    assert not ok and len(report) == 2 and "only in A" in report[0] and "only in B" in report[1]
+    assert not isa_ab.compare_names(a, a + a[:1])[1]

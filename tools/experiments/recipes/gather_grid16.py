@@ -1,2 +1,2 @@
 # A/B: the persistent gather kernels on up to 16 blocks per CU instead of 8
-EDITS = [("sampler_gather.hip", "const int64_t cap = (int64_t)kNumCU * 8;", "const int64_t cap = (int64_t)kNumCU * 16;")]
+EDITS = [("gather_plan.h", "const int64_t cap = (int64_t)kPlanNumCU * 8;", "const int64_t cap = (int64_t)kPlanNumCU * 16;")]

@@ -6,12 +6,14 @@ and csrc/gemm_f16x2_256.hip of two trees to gfx950 assembly with build()'s flags
     python tools/isa_ab.py --rev HEAD      # the last commit against uncommitted edits
     python tools/isa_ab.py --a DIR --b DIR # two checked-out trees
     python tools/isa_ab.py --sources gemm_bf16x3.hip gemm_bf16.hip   # other translation units of csrc/
+    python tools/isa_ab.py --names ...     # ... and the two trees' kernels must carry the same demangled names
 
 A kernel is its instructions plus its .amdhsa_kernel descriptor block (registers, LDS, scratch).  What may differ without
 the code differing is canonicalised: the kernel's own mangled name, the __hip_cuid_* symbol, comments, and the function
 number inside .LBB<n>_<m> / .Lfunc_end<n> labels.  The two trees are compared as MULTISETS of kernel bodies -- a refactor
-may rename template arguments, so names are reported and not matched.  Host tool: no GPU.  Exit status 0 = every kernel
-identical and the counts equal."""
+may rename template arguments, so names are reported and not matched -- unless --names asks for it: a benchmark or a
+profile that finds its kernels by name then needs the two trees' multisets of demangled names (llvm-cxxfilt) equal as well.
+Host tool: no GPU.  Exit status 0 = every kernel identical and the counts equal (and, with --names, the names)."""
 import argparse
 import collections
 import difflib
@@ -89,6 +91,29 @@ def compare(a, b):
     return report, ok
 
 
+def demangled(names):
+    """The demangled form of each mangled kernel name, by ROCm's llvm-cxxfilt, else the system's c++filt (a name the
+    demangler does not know stays mangled -- which compares just as well)."""
+    import shutil
+    filt = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin", "llvm-cxxfilt")
+    if not os.path.exists(filt):
+        filt = shutil.which("llvm-cxxfilt") or shutil.which("c++filt")
+    if not filt:
+        raise RuntimeError("--names needs llvm-cxxfilt or c++filt")
+    r = subprocess.run([filt], input="\n".join(names) + "\n", capture_output=True, text=True, check=True)
+    out = r.stdout.splitlines()
+    assert len(out) == len(names)
+    return out
+
+
+def compare_names(a, b):
+    """(report lines, ok) for two lists of demangled names compared as multisets."""
+    ca, cb = collections.Counter(a), collections.Counter(b)
+    report = ["NAME only in A (x%d): %s" % (n, k) for k, n in sorted((ca - cb).items())]
+    report += ["NAME only in B (x%d): %s" % (n, k) for k, n in sorted((cb - ca).items())]
+    return report or ["names: the same %d demangled kernel names" % len(a)], ca == cb
+
+
 def build_flags():
     sys.path.insert(0, ROOT)
     import __graft_entry__
@@ -112,6 +137,7 @@ def main():
     ap.add_argument("--b", default=ROOT, help="tree B (default: the working tree)")
     ap.add_argument("--sources", nargs="+", default=list(SOURCES), metavar="FILE.hip",
                     help="the translation units of csrc/ to compare (default: the two of the tile GEMM)")
+    ap.add_argument("--names", action="store_true", help="also require the same multiset of demangled kernel names")
     args = ap.parse_args()
     sources = tuple(args.sources)
     flags = build_flags()
@@ -140,9 +166,13 @@ def main():
             src, len(ka), len(kb), sum(k.n_instr for k in ka), sum(k.n_instr for k in kb),
             hashlib.sha256("\n".join(sorted(k.body for k in ka)).encode()).hexdigest()[:16],
             hashlib.sha256("\n".join(sorted(k.body for k in kb)).encode()).hexdigest()[:16]))
+        if args.names:
+            more, same = compare_names(demangled([k.name for k in ka]), demangled([k.name for k in kb]))
+            report += more
+            ok = ok and same
         for ln in report:
             print("  " + ln)
-    print("RESULT: %s" % ("every kernel identical" if ok else "DIFFERENCES"))
+    print("RESULT: %s" % (("every kernel identical" + (", every name the same" if args.names else "")) if ok else "DIFFERENCES"))
     return 0 if ok else 1
 
 
