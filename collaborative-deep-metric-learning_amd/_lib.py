@@ -245,6 +245,22 @@ SIGNATURES_HARDNEG = {
                                            _p, _p, _p, _i64, _i, _i64, _i64, _i64, _p, _p]),
 }
 
+# name -> (restype, argtypes); must list every symbol include/cdml_negweights.h declares (weighted negatives: sampler mode 3,
+# and the per-negative bias of the mixed N-pair chain)
+SIGNATURES_NEGW = {
+    "cdml_sample_weighted": (_i, [_p, _i64, _i64, _u64, _u64, _p, _i, _i64, _i64, _p, _i64, _p, _i, _p, _p, _p]),
+    "cdml_sample_gather_weighted": (_i, [_p, _i64, _u64, _u64, _p, _i, _i64, _i64, _p, _i64, _i64, _i, _p, _i64, _p, _i,
+                                         _p, _p, _p, _i64, _i, _i64, _i64, _i64, _p, _p]),
+    "cdml_sample_gather_weighted_x3": (_i, [_p, _i64, _u64, _u64, _p, _i, _i64, _i64, _p, _i64, _i64, _i, _p, _i64, _p, _i,
+                                            _p, _p, _p, _i64, _i, _i64, _i64, _i64, _p, _p, _i64, _p]),
+    "cdml_sample_gather_weighted_f16": (_i, [_p, _i64, _u64, _u64, _p, _i, _i64, _i64, _p, _i64, _i64, _i, _p, _i64, _p, _i,
+                                             _p, _p, _p, _i64, _i, _i64, _i64, _i64, _p, _p]),
+    "cdml_npair_mixed_stats_nb": (_i, [_p, _i64, _p, _i, _i64, _i64, _p, _i, _p, _p, _p, _f, _i, _p, _p, _p, _sz, _p]),
+    "cdml_npair_mixed_grad_x3_nb": (_i, [_p, _i64, _p, _i, _i64, _i64, _p, _i, _p, _p, _p, _f, _i, _p, _p, _i64, _i64, _p]),
+    "cdml_npair_mixed_grad_f32_nb": (_i, [_p, _i64, _p, _i, _i64, _i64, _p, _i, _p, _p, _p, _f, _i, _p, _p, _i64, _p]),
+    "cdml_negw_bias": (_i, [_p, _i64, _p, _i, _f, _p, _p]),
+}
+
 # name -> (restype, argtypes); must list every symbol include/cdml_x3_wide.h declares (dW1 with dz1 k8-interleaved)
 SIGNATURES_WIDE = {
     "cdml_gemm_bf16x3_tn_kb": (_i, [_p, _i64, _i64, _p, _i, _i, _i, _i, _i, _p, _i64, _p, _p, _sz, _p]),
@@ -269,7 +285,8 @@ def load_library():
     import torch  # noqa: F401
     lib = C.CDLL(path)
     for name, (res, args) in (list(SIGNATURES.items()) + list(SIGNATURES_MIXED.items()) + list(SIGNATURES_DP.items())
-                               + list(SIGNATURES_BF16.items()) + list(SIGNATURES_HARDNEG.items()) + list(SIGNATURES_WIDE.items())):
+                               + list(SIGNATURES_BF16.items()) + list(SIGNATURES_HARDNEG.items()) + list(SIGNATURES_WIDE.items())
+                               + list(SIGNATURES_NEGW.items())):
         fn = getattr(lib, name)          # AttributeError if the ABI lost a symbol
         fn.restype = res
         fn.argtypes = args

@@ -47,6 +47,8 @@ class TrainConfig:
     logq_alpha: float = 0.01                  # mode "npair": that estimator's smoothing rate (build-defined)
     uniform_negatives: bool = False           # mode "npair": mixed negative sampling -- a uniform catalogue negative per pair in the softmax
     uniform_logq: typing.Optional[float] = None   # with logq: the uniform block's log sampling probability (None: derived from logq)
+    negative_weights: typing.Optional[typing.List[float]] = None   # one weight >= 0 per catalogue row: weighted negatives
+                                              # (modes that draw one; negweights.NegativeWeights.from_counts builds unigram^0.75)
     seed: int = 1234
     weight_seed: int = 42
 
@@ -91,6 +93,9 @@ class TrainConfig:
                 kw.update(memory_size=self.memory_size)   # (TrainStep refuses it outside mode "npair")
             if self.logq:
                 kw.update(logq=self.logq)                 # (and this)
+        if self.negative_weights is not None:
+            import torch
+            kw.update(negative_weights=torch.tensor(self.negative_weights, dtype=torch.float64))
         kw.update(overrides)
         return train.TrainStep(table, pairs, self.batch_size, **kw)
 

@@ -62,9 +62,19 @@ struct ListedArgs {
   int64_t kind_step_stride;
 };
 
+// the weighted draw's own arguments (cdml_negweights.h); `who`: the name the entry point's own checks report under
+struct WeightedArgs {
+  const char *who;
+  const int32_t *start, *coarse;             // start: uint32 bits [n_live]; coarse [2^bits + 1]
+  int64_t n_live;
+  int bits;
+  int32_t *kind_out;
+  int64_t kind_step_stride;
+};
+
 // One fused launch, in the order of the C entry points' parameters.
 struct SampleGatherArgs {
-  int mode;                                  // 0 uniform, 1 in-batch, 2 listed (with `listed`)
+  int mode;                                  // 0 uniform, 1 in-batch, 2 listed (with `listed`), 3 weighted (with `weighted`)
   const int32_t *pairs; int64_t n_pairs;     // the pair stream
   uint64_t seed, step; const uint64_t *step_dev;
   int batch; int64_t slot0, batch_global;
@@ -76,6 +86,7 @@ struct SampleGatherArgs {
   void *x_ki; int64_t ki_step_stride;        // optional (formats with ki)
   bool ki_entry;                             // cdml_sample_gather_x3k: x_ki is not optional
   const ListedArgs *listed;                  // optional (formats with who_listed)
+  const WeightedArgs *weighted = nullptr;    // optional (the same formats)
 };
 
 struct GatherRowsArgs {
@@ -116,6 +127,14 @@ inline int check_listed(const char *who, const int32_t *lists, int64_t ldl, int 
   return CDML_OK;
 }
 
+inline int check_weighted(const char *who, const int32_t *start, const int32_t *coarse, int64_t n_live, int64_t n_rows, int bits) {
+  CDML_REQUIRE(start && coarse, CDML_E_BADARG, "%s: the start / coarse tables are null", who);
+  CDML_REQUIRE(n_live >= 3 && n_live <= n_rows, CDML_E_BADARG, "%s: n_live = %lld outside [3, n_rows = %lld]", who,
+               (long long)n_live, (long long)n_rows);
+  CDML_REQUIRE(bits >= 8 && bits <= 24, CDML_E_BADARG, "%s: bits = %d outside [8, 24]", who, bits);
+  return CDML_OK;
+}
+
 // F, strides and bases of a table -> rows copy.  Every format words its rule its own way (and the fp32 one in two steps).
 inline int check_gather_layout(const char *who, const GatherFormat &f, bool fused, const void *table, int64_t row_stride, int F,
                                const void *x_out, int64_t out_stride) {
@@ -137,9 +156,10 @@ inline int check_gather_layout(const char *who, const GatherFormat &f, bool fuse
   return CDML_OK;
 }
 
-// Every check of a fused launch, in ONE order for all formats: the entry's own arguments (x_ki of _x3k, the listed block,
-// under the entry's name), mode, n_steps, per-step strides, pointers, n_rows, batch, shift_out, batch_global, F, layout,
-// the interleave rule (under _x3k's name, whichever entry passed x_ki).  `who`: the name the format's checks report under.
+// Every check of a fused launch, in ONE order for all formats: the entry's own arguments (x_ki of _x3k, the listed block
+// and the weighted block, under the entry's name), mode, n_steps, per-step strides, pointers, n_rows, batch, shift_out,
+// batch_global, F, layout, the interleave rule (under _x3k's name, whichever entry passed x_ki).  `who`: the name the
+// format's checks report under.
 inline int plan_sample_gather(const char *who, const GatherFormat &f, const SampleGatherArgs &a, GatherPlan &p) {
   CDML_REQUIRE(!a.ki_entry || a.x_ki, CDML_E_BADARG, "sample_gather_x3k: x_ki required (cdml_sample_gather_x3 without it)");
   const bool listed = a.listed && f.who_listed;
@@ -150,7 +170,15 @@ inline int plan_sample_gather(const char *who, const GatherFormat &f, const Samp
     CDML_REQUIRE(!l.kind_out || a.n_steps <= 1 || l.kind_step_stride >= a.batch, CDML_E_BADARG, "%s: kind_step_stride < batch",
                  f.who_listed);
   }
-  CDML_REQUIRE(a.mode == 0 || a.mode == 1 || (a.mode == 2 && listed), CDML_E_BADARG, "%s: mode must be 0 or 1", who);
+  const bool weighted = a.weighted && f.who_listed;
+  if (weighted) {
+    const WeightedArgs &w = *a.weighted;
+    const int rc = check_weighted(w.who, w.start, w.coarse, w.n_live, a.n_rows, w.bits);
+    if (rc) return rc;
+    CDML_REQUIRE(!w.kind_out || a.n_steps <= 1 || w.kind_step_stride >= a.batch, CDML_E_BADARG, "%s: kind_step_stride < batch", w.who);
+  }
+  CDML_REQUIRE(a.mode == 0 || a.mode == 1 || (a.mode == 2 && listed) || (a.mode == 3 && weighted), CDML_E_BADARG,
+               "%s: mode must be 0 or 1", who);
   CDML_REQUIRE(a.n_steps >= 1 && a.n_steps <= 64, CDML_E_BADARG, "%s: n_steps must be in [1, 64]", who);
   p.rpt = a.mode == 1 ? 2 : 3;
   const int64_t rows_per_step = (int64_t)a.batch * p.rpt;

@@ -15,10 +15,15 @@
 //   k_mixed_stats     one block: the step scalars from the per-row partials in a fixed order (step_scalars)
 //   k_mixed_w<FMT>    W of all blocks in ONE launch, four columns per lane, as three bf16 planes or fp32 (store_w4)
 // BIAS (template switch): the logQ correction -- in-batch logits less bias[2j + 1] (the [2B] layout of the logQ gather),
-// the uniform block's less the scalar lq_u, a slot's less mem_bias[k].  No atomics; every sum in a fixed order.
+// the uniform block's less the scalar lq_u, a slot's less mem_bias[k].  NB (a further template switch, include/
+// cdml_negweights.h): the uniform block's correction is one value per column, neg_bias[j], read as one float4 beside u4 --
+// the argument slot of lq_u then holds the vector's pointer (LqArg), so the scalar instantiations are what they were.
+// No atomics; every sum in a fixed order.
 #include "npair_common.h"
 #include "../../include/cdml_npair_mixed.h"
+#include "../../include/cdml_negweights.h"
 #include <math.h>
+#include <type_traits>
 
 namespace cdml {
 namespace {
@@ -38,12 +43,16 @@ __device__ __forceinline__ void mx_ids4(const int32_t *ids, int j0, int (&a)[4],
 
 __device__ __forceinline__ bool mx_other(int q, int ida, int idp) { return q != ida && q != idp; }
 
+// the uniform block's correction as a kernel argument: the scalar lq_u, or (NB) the per-column vector neg_bias
+template <bool NB>
+using LqArg = typename std::conditional<NB, const float *, float>::type;
+
 // part[4 i .. 4 i + 3] = {lse_i - (S_ii / t - lq(p_i)), 2 - 2 S_ii, sum over the counted negatives of 2 - 2 S, their count}
-template <bool MEM, bool BIAS>
+template <bool MEM, bool BIAS, bool NB = false>
 __global__ void __launch_bounds__(kMxThreads)
 k_mixed_rows(const float *__restrict__ S, int64_t lds, const int32_t *__restrict__ ids, int B, float inv_t,
              float *__restrict__ lse, float *__restrict__ part, int64_t neg_col, int64_t mem_col,
-             const int32_t *__restrict__ mem_id, int n_mem, const float *__restrict__ bias, float lq_u,
+             const int32_t *__restrict__ mem_id, int n_mem, const float *__restrict__ bias, LqArg<NB> lq_u,
              const float *__restrict__ mem_bias) {
   const int i = blockIdx.x;
   const float *row = S + (int64_t)i * lds;
@@ -61,6 +70,11 @@ k_mixed_rows(const float *__restrict__ S, int64_t lds, const int32_t *__restrict
       const float4 b1 = *reinterpret_cast<const float4 *>(bias + 2 * (int64_t)j0 + 4);
       bp[0] = b0.y; bp[1] = b0.w; bp[2] = b1.y; bp[3] = b1.w;
     }
+    float nb[4] = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (BIAS && NB) {                          // the uniform block's per-column correction
+      const float4 n4 = *reinterpret_cast<const float4 *>(lq_u + j0);
+      nb[0] = n4.x; nb[1] = n4.y; nb[2] = n4.z; nb[3] = n4.w;
+    }
 #pragma unroll
     for (int q = 0; q < 4; ++q) {                        // the in-batch block
       const int j = j0 + q;
@@ -77,7 +91,9 @@ k_mixed_rows(const float *__restrict__ S, int64_t lds, const int32_t *__restrict
 #pragma unroll
     for (int q = 0; q < 4; ++q) {                        // the uniform block: no special diagonal
       if (ids && !mx_other(n[q], ida, idp)) continue;
-      if constexpr (BIAS)
+      if constexpr (BIAS && NB)
+        lse_add(m, s, u[q] * inv_t - nb[q]);
+      else if constexpr (BIAS)
         lse_add(m, s, u[q] * inv_t - lq_u);
       else
         lse_add(m, s, u[q] * inv_t);
@@ -132,11 +148,11 @@ k_mixed_stats(const float *__restrict__ part, const float *__restrict__ closs, i
 // Row i = blockIdx.x, columns c0 = 4 (blockIdx.y * kMxThreads + threadIdx.x) .. c0 + 3 of the span [0, mem_col + M) (without
 // a memory: [0, neg_col + B)).  Every block starts and ends on a multiple of 4, so the four columns lie in one block or in a
 // gap between two, which is not written.  scale = 1 / (B t); the uniform and the memory block halve it with `symmetric`.
-template <int FMT, bool MEM, bool BIAS>
+template <int FMT, bool MEM, bool BIAS, bool NB = false>
 __global__ void __launch_bounds__(kMxThreads)
 k_mixed_w(const float *__restrict__ S, int64_t lds, const int32_t *__restrict__ ids, int B, int64_t neg_col, int64_t mem_col,
           const int32_t *__restrict__ mem_id, int M, float inv_t, int symmetric, const float *__restrict__ lse, float scale,
-          void *__restrict__ Wout, int64_t ldw, int64_t plane, const float *__restrict__ bias, float lq_u,
+          void *__restrict__ Wout, int64_t ldw, int64_t plane, const float *__restrict__ bias, LqArg<NB> lq_u,
           const float *__restrict__ mem_bias) {
   const int i = blockIdx.x;
   const int64_t c0 = ((int64_t)blockIdx.y * kMxThreads + threadIdx.x) * 4;
@@ -190,10 +206,17 @@ k_mixed_w(const float *__restrict__ S, int64_t lds, const int32_t *__restrict__ 
     const int j0 = (int)(c0 - neg_col);
     int a[4], p[4], n[4] = {0, 0, 0, 0};
     if (ids) mx_ids4(ids, j0, a, p, n);
+    float nb[4] = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (BIAS && NB) {
+      const float4 n4 = *reinterpret_cast<const float4 *>(lq_u + j0);
+      nb[0] = n4.x; nb[1] = n4.y; nb[2] = n4.z; nb[3] = n4.w;
+    }
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const bool cn = !ids || mx_other(n[q], ida, idp);
-      if constexpr (BIAS)
+      if constexpr (BIAS && NB)
+        w[q] = cn ? expf(v[q] * inv_t - nb[q] - lr) * side : 0.f;
+      else if constexpr (BIAS)
         w[q] = cn ? expf(v[q] * inv_t - lq_u - lr) * side : 0.f;
       else
         w[q] = cn ? expf(v[q] * inv_t - lr) * side : 0.f;
@@ -296,14 +319,23 @@ int mx_check(const char *who, const float *S, int64_t lds, const int32_t *ids, i
   return CDML_OK;
 }
 
-template <bool MEM, bool BIAS>
+// the vector form's own argument (the scalar launches' check of lq_u, mx_check, is given 0)
+int mx_check_nb(const char *who, const float *bias, const float *neg_bias) {
+  CDML_REQUIRE(!bias || (neg_bias && aligned16(neg_bias)), CDML_E_BADARG,
+               "%s: the corrected loss needs neg_bias (fp32 [B], 16-B aligned)", who);
+  return CDML_OK;
+}
+
+// LQ: float (the scalar lq_u) or const float * (neg_bias, the NB kernels)
+template <bool MEM, bool BIAS, typename LQ>
 int mx_stats_launch(const float *S, int64_t lds, const int32_t *ids, int B, int64_t neg_col, int64_t mem_col,
-                    const int32_t *mem_id, int M, const float *bias, float lq_u, const float *mem_bias, float temperature,
+                    const int32_t *mem_id, int M, const float *bias, LQ lq_u, const float *mem_bias, float temperature,
                     int symmetric, float *lse, float *stats, void *workspace, cdml_stream_t stream) {
   const float inv_t = 1.0f / temperature;
   float *part = static_cast<float *>(workspace);
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL((k_mixed_rows<MEM, BIAS>), dim3(B), dim3(kMxThreads), 0, st, S, lds, ids, B, inv_t, lse, part, neg_col,
+  constexpr bool NB = std::is_pointer<LQ>::value;
+  hipLaunchKernelGGL((k_mixed_rows<MEM, BIAS, NB>), dim3(B), dim3(kMxThreads), 0, st, S, lds, ids, B, inv_t, lse, part, neg_col,
                      mem_col, mem_id, M, bias, lq_u, mem_bias);
   if (int rc = check_launch("npair_mixed_stats rows")) return rc;
   if (symmetric)
@@ -314,28 +346,35 @@ int mx_stats_launch(const float *S, int64_t lds, const int32_t *ids, int B, int6
   return check_launch("npair_mixed_stats");
 }
 
-template <int FMT>
+template <int FMT, typename LQ>
 int mx_w_launch(const char *who, const float *S, int64_t lds, const int32_t *ids, int B, int64_t neg_col, int64_t mem_col,
-                const int32_t *mem_id, int M, const float *bias, float lq_u, const float *mem_bias, float temperature,
+                const int32_t *mem_id, int M, const float *bias, LQ lq_u, const float *mem_bias, float temperature,
                 int symmetric, const float *lse, void *W, int64_t ldw, int64_t plane, cdml_stream_t stream) {
-  if (int rc = mx_check(who, S, lds, ids, B, neg_col, mem_col, mem_id, M, bias, lq_u, mem_bias, temperature, lse)) return rc;
+  constexpr bool NB = std::is_pointer<LQ>::value;
+  if constexpr (NB) {
+    if (int rc = mx_check(who, S, lds, ids, B, neg_col, mem_col, mem_id, M, bias, 0.f, mem_bias, temperature, lse)) return rc;
+    if (int rc = mx_check_nb(who, bias, lq_u)) return rc;
+  } else {
+    if (int rc = mx_check(who, S, lds, ids, B, neg_col, mem_col, mem_id, M, bias, lq_u, mem_bias, temperature, lse)) return rc;
+  }
   const int64_t span = M ? mem_col + M : neg_col + B;
   if (int rc = np_w_check(who, FMT, span, W, ldw, plane)) return rc;
   const dim3 grid((unsigned)B, (unsigned)((span + 4 * kMxThreads - 1) / (4 * kMxThreads)));
   const float inv_t = 1.0f / temperature, scale = 1.0f / ((float)B * temperature);
   const int sym = symmetric ? 1 : 0;
   hipStream_t st = (hipStream_t)stream;
-#define CDML_MX_W(MEM, BIAS)                                                                                                   \
-  hipLaunchKernelGGL((k_mixed_w<FMT, MEM, BIAS>), grid, dim3(kMxThreads), 0, st, S, lds, ids, B, neg_col, mem_col, mem_id, M,    \
-                     inv_t, sym, lse, scale, W, ldw, plane, bias, lq_u, mem_bias)
+  // (without a correction the block's bias is not read: the uncorrected kernels are the scalar form's, whichever entry asks)
+#define CDML_MX_W(MEM, BIAS, NBK, LQ_ARG)                                                                                       \
+  hipLaunchKernelGGL((k_mixed_w<FMT, MEM, BIAS, NBK>), grid, dim3(kMxThreads), 0, st, S, lds, ids, B, neg_col, mem_col, mem_id, M, \
+                     inv_t, sym, lse, scale, W, ldw, plane, bias, LQ_ARG, mem_bias)
   if (M && bias) {
-    CDML_MX_W(true, true);
+    CDML_MX_W(true, true, NB, lq_u);
   } else if (M) {
-    CDML_MX_W(true, false);
+    CDML_MX_W(true, false, false, 0.f);
   } else if (bias) {
-    CDML_MX_W(false, true);
+    CDML_MX_W(false, true, NB, lq_u);
   } else {
-    CDML_MX_W(false, false);
+    CDML_MX_W(false, false, false, 0.f);
   }
 #undef CDML_MX_W
   return check_launch(who);
@@ -348,26 +387,63 @@ using namespace cdml;
 
 extern "C" size_t cdml_npair_mixed_workspace(int B, int M) { return M >= 0 ? np_ws_bytes(B) : 0; }
 
-extern "C" int cdml_npair_mixed_stats(const float *S, int64_t lds, const int32_t *ids, int B, int64_t neg_col, int64_t mem_col,
-                                      const int32_t *mem_id, int M, const float *bias, float lq_u, const float *mem_bias,
-                                      float temperature, int symmetric, float *lse, float *stats, void *workspace,
-                                      size_t workspace_bytes, cdml_stream_t stream) {
-  const char *who = "npair_mixed_stats";
-  if (int rc = mx_check(who, S, lds, ids, B, neg_col, mem_col, mem_id, M, bias, lq_u, mem_bias, temperature, lse)) return rc;
+template <typename LQ>
+static int mx_stats(const char *who, const float *S, int64_t lds, const int32_t *ids, int B, int64_t neg_col, int64_t mem_col,
+                    const int32_t *mem_id, int M, const float *bias, LQ lq_u, const float *mem_bias, float temperature,
+                    int symmetric, float *lse, float *stats, void *workspace, size_t workspace_bytes, cdml_stream_t stream) {
+  if constexpr (std::is_pointer<LQ>::value) {
+    if (int rc = mx_check(who, S, lds, ids, B, neg_col, mem_col, mem_id, M, bias, 0.f, mem_bias, temperature, lse)) return rc;
+    if (int rc = mx_check_nb(who, bias, lq_u)) return rc;
+  } else {
+    if (int rc = mx_check(who, S, lds, ids, B, neg_col, mem_col, mem_id, M, bias, lq_u, mem_bias, temperature, lse)) return rc;
+  }
   CDML_REQUIRE(stats, CDML_E_BADARG, "%s: null pointer (stats)", who);
   if (int rc = np_ws_check(who, workspace, workspace_bytes, np_ws_bytes(B), "cdml_npair_mixed_workspace(B, M)")) return rc;
   if (M) {
     if (bias)
       return mx_stats_launch<true, true>(S, lds, ids, B, neg_col, mem_col, mem_id, M, bias, lq_u, mem_bias, temperature,
                                          symmetric, lse, stats, workspace, stream);
-    return mx_stats_launch<true, false>(S, lds, ids, B, neg_col, mem_col, mem_id, M, bias, lq_u, mem_bias, temperature, symmetric,
-                                        lse, stats, workspace, stream);
+    return mx_stats_launch<true, false>(S, lds, ids, B, neg_col, mem_col, mem_id, M, bias, 0.f, mem_bias, temperature, symmetric,
+                                        lse, stats, workspace, stream);       // (uncorrected: the block's bias is not read)
   }
   if (bias)
     return mx_stats_launch<false, true>(S, lds, ids, B, neg_col, mem_col, mem_id, M, bias, lq_u, mem_bias, temperature, symmetric,
                                         lse, stats, workspace, stream);
-  return mx_stats_launch<false, false>(S, lds, ids, B, neg_col, mem_col, mem_id, M, bias, lq_u, mem_bias, temperature, symmetric,
+  return mx_stats_launch<false, false>(S, lds, ids, B, neg_col, mem_col, mem_id, M, bias, 0.f, mem_bias, temperature, symmetric,
                                        lse, stats, workspace, stream);
+}
+
+extern "C" int cdml_npair_mixed_stats(const float *S, int64_t lds, const int32_t *ids, int B, int64_t neg_col, int64_t mem_col,
+                                      const int32_t *mem_id, int M, const float *bias, float lq_u, const float *mem_bias,
+                                      float temperature, int symmetric, float *lse, float *stats, void *workspace,
+                                      size_t workspace_bytes, cdml_stream_t stream) {
+  return mx_stats("npair_mixed_stats", S, lds, ids, B, neg_col, mem_col, mem_id, M, bias, lq_u, mem_bias, temperature, symmetric,
+                  lse, stats, workspace, workspace_bytes, stream);
+}
+
+// ---- the per-negative bias (include/cdml_negweights.h): the same launches on the NB instantiations ----
+extern "C" int cdml_npair_mixed_stats_nb(const float *S, int64_t lds, const int32_t *ids, int B, int64_t neg_col,
+                                         int64_t mem_col, const int32_t *mem_id, int M, const float *bias, const float *neg_bias,
+                                         const float *mem_bias, float temperature, int symmetric, float *lse, float *stats,
+                                         void *workspace, size_t workspace_bytes, cdml_stream_t stream) {
+  return mx_stats("npair_mixed_stats_nb", S, lds, ids, B, neg_col, mem_col, mem_id, M, bias, neg_bias, mem_bias, temperature,
+                  symmetric, lse, stats, workspace, workspace_bytes, stream);
+}
+
+extern "C" int cdml_npair_mixed_grad_x3_nb(const float *S, int64_t lds, const int32_t *ids, int B, int64_t neg_col,
+                                           int64_t mem_col, const int32_t *mem_id, int M, const float *bias,
+                                           const float *neg_bias, const float *mem_bias, float temperature, int symmetric,
+                                           const float *lse, uint16_t *W, int64_t ldw, int64_t plane, cdml_stream_t stream) {
+  return mx_w_launch<kWX3>("npair_mixed_grad_x3_nb", S, lds, ids, B, neg_col, mem_col, mem_id, M, bias, neg_bias, mem_bias,
+                           temperature, symmetric, lse, W, ldw, plane, stream);
+}
+
+extern "C" int cdml_npair_mixed_grad_f32_nb(const float *S, int64_t lds, const int32_t *ids, int B, int64_t neg_col,
+                                            int64_t mem_col, const int32_t *mem_id, int M, const float *bias,
+                                            const float *neg_bias, const float *mem_bias, float temperature, int symmetric,
+                                            const float *lse, float *W, int64_t ldw, cdml_stream_t stream) {
+  return mx_w_launch<kWF32>("npair_mixed_grad_f32_nb", S, lds, ids, B, neg_col, mem_col, mem_id, M, bias, neg_bias, mem_bias,
+                            temperature, symmetric, lse, W, ldw, 0, stream);
 }
 
 extern "C" int cdml_npair_mixed_grad_x3(const float *S, int64_t lds, const int32_t *ids, int B, int64_t neg_col,

@@ -13,6 +13,7 @@
 #include "common.h"
 #include "gather_plan.h"
 #include "../../include/cdml_hardneg.h"
+#include "../../include/cdml_negweights.h"
 
 namespace cdml {
 namespace {
@@ -133,6 +134,66 @@ k_sample_listed(const int32_t *__restrict__ pairs, int64_t n_pairs, uint32_t n_r
   idx_out[3 * i + 1] = p;
   idx_out[3 * i + 2] = n;
   if (ln.kind_out) ln.kind_out[i] = kind;
+}
+
+// Weighted negatives (include/cdml_negweights.h; host model: tests/negweights_ref.py).  A 32-bit word r of the purpose-3
+// stream falls into the interval of exactly one row: owner(r) = the largest v < n_live with start[v] <= r, found by one
+// load of coarse[r >> shift] (the owners of the bucket's two ends bracket it) and a binary search in start[lo..hi].  A
+// word that lands on a or p is redrawn; a stream that runs out leaves the triplet to the uniform draw.
+constexpr uint32_t kPurposeWeightedNeg = 3;
+struct WeightedNeg {
+  const uint32_t *start = nullptr;  // [n_live] exclusive prefix sums of the quanta
+  const int32_t *coarse = nullptr;  // [2^bits + 1]
+  int32_t n_live = 1;
+  int32_t shift = 16;               // 32 - bits
+  int32_t *kind_out = nullptr;      // as ListedNeg's
+  int64_t kind_step_stride = 0;
+};
+
+__device__ __forceinline__ int32_t weighted_owner(uint32_t r, const WeightedNeg &wn) {
+  const uint32_t b = r >> wn.shift;
+  const int32_t last = wn.n_live - 1;
+  // the bounds are clamped into [0, n_live): a malformed table cannot index outside start
+  int32_t lo = min(max(wn.coarse[b], 0), last);
+  int32_t hi = min(max(wn.coarse[b + 1], lo), last);
+  while (lo < hi) {
+    const int32_t mid = lo + ((hi - lo + 1) >> 1);     // in (lo, hi]
+    if (wn.start[mid] <= r) lo = mid;
+    else hi = mid - 1;
+  }
+  return lo;
+}
+
+__device__ __forceinline__ int32_t sample_weighted_negative(uint64_t seed, uint64_t step, uint32_t slot, int32_t a, int32_t p,
+                                                            uint32_t n_rows, const WeightedNeg &wn, int32_t &kind) {
+  WordStream hs(seed, step, slot, kPurposeWeightedNeg);
+  while (!hs.exhausted()) {
+    const int32_t v = weighted_owner(hs.next(), wn);
+    if (v != a && v != p) {
+      kind = 1;
+      return v;
+    }
+  }
+  kind = 0;
+  return sample_uniform_negative(seed, step, slot, a, p, n_rows);
+}
+
+__global__ void __launch_bounds__(kThreads)
+k_sample_weighted(const int32_t *__restrict__ pairs, int64_t n_pairs, uint32_t n_rows, uint64_t seed, uint64_t step_imm,
+                  const uint64_t *__restrict__ step_dev, int batch, int64_t slot0, int64_t batch_global, WeightedNeg wn,
+                  int32_t *__restrict__ idx_out) {
+  const uint64_t step = step_imm + (step_dev ? *step_dev : 0);
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= batch) return;
+  const uint64_t slot = (uint64_t)(slot0 + i);
+  const uint64_t q = (step * (uint64_t)batch_global + slot) % (uint64_t)n_pairs;
+  const int32_t a = pairs[2 * q], p = pairs[2 * q + 1];
+  int32_t kind;
+  const int32_t n = sample_weighted_negative(seed, step, (uint32_t)slot, a, p, n_rows, wn, kind);
+  idx_out[3 * i + 0] = a;
+  idx_out[3 * i + 1] = p;
+  idx_out[3 * i + 2] = n;
+  if (wn.kind_out) wn.kind_out[i] = kind;
 }
 
 __global__ void __launch_bounds__(kThreads)
@@ -340,7 +401,9 @@ k_gather_rows_planes(const float *__restrict__ src, int64_t n_rows, int64_t row_
 //     each, 16 B per lane = whole 128-B lines) are issued before the first use, then the
 //     wave-shuffle norm and the stores.
 // MODE 0 = uniform negatives, MODE 1 = in-batch negatives, MODE 2 = listed negatives (3 rows per triplet as MODE 0; only
-// the id-staging lanes differ: the negative's lane reads the anchor's list, one more hop of the chain pair -> id -> row).
+// the id-staging lanes differ: the negative's lane reads the anchor's list, one more hop of the chain pair -> id -> row),
+// MODE 3 = weighted negatives (as MODE 2, the hop being the search in the weight tables).  NEG: the struct of the mode's own
+// arguments -- ListedNeg for modes 0 - 2 (their kernel arguments are what they were), WeightedNeg for mode 3.
 constexpr int kRowsPerWave = CDML_GATHER_ROWS_PER_WAVE;   // (gather_plan.h, which sizes the grid by it)
 constexpr int kChunkRows = kRowsPerWave * kWavesPerBlock;
 
@@ -566,7 +629,7 @@ struct RowF16 {
 // slices of 256 columns: every wave drops its two rows' planes of the slice into 12 KiB of LDS as [plane][row][column]
 // (8-B writes), then 192 threads each read one 4-column group of all 8 rows (8-B reads), transpose 8 x 4 in registers and
 // store 4 x 16 B = 64 contiguous bytes of x_ki.
-template <int MODE, typename ROW, bool KI = false>
+template <int MODE, typename ROW, bool KI = false, typename NEG = ListedNeg>
 __global__ void __launch_bounds__(kThreads)
 k_sample_gather(const int32_t *__restrict__ pairs, int64_t n_pairs, uint64_t seed,
                 uint64_t step_imm, const uint64_t *__restrict__ step_dev, int batch,
@@ -575,7 +638,7 @@ k_sample_gather(const int32_t *__restrict__ pairs, int64_t n_pairs, uint64_t see
                 int32_t *__restrict__ shift_out, typename ROW::Out *__restrict__ x_out, int64_t out_stride,
                 int n_steps, int64_t x_step_stride, int64_t idx_step_stride,
                 int32_t *__restrict__ oob_flag, __bf16 *__restrict__ x_ki = nullptr, int64_t ki_step_stride = 0,
-                ListedNeg ln = ListedNeg()) {
+                NEG ln = NEG()) {
   constexpr int RPT = (MODE == 1) ? 2 : 3;  // rows per triplet
   constexpr int kRPW = ROW::kRows, kCR = kRPW * kWavesPerBlock;   // rows per wave / per chunk
   __shared__ int32_t s_id[2][kCR];
@@ -603,9 +666,17 @@ k_sample_gather(const int32_t *__restrict__ pairs, int64_t n_pairs, uint64_t see
         if (MODE == 0 && k == 2) {
           id = sample_uniform_negative(seed, step, (uint32_t)slot, pairs[2 * q], pairs[2 * q + 1], (uint32_t)n_rows);
         } else if (MODE == 2 && k == 2) {
-          int32_t kind;
-          id = sample_listed_negative(seed, step, (uint32_t)slot, pairs[2 * q], pairs[2 * q + 1], (uint32_t)n_rows, ln, kind);
-          if (ln.kind_out) ln.kind_out[(int64_t)s * ln.kind_step_stride + i] = kind;
+          if constexpr (MODE == 2) {
+            int32_t kind;
+            id = sample_listed_negative(seed, step, (uint32_t)slot, pairs[2 * q], pairs[2 * q + 1], (uint32_t)n_rows, ln, kind);
+            if (ln.kind_out) ln.kind_out[(int64_t)s * ln.kind_step_stride + i] = kind;
+          }
+        } else if (MODE == 3 && k == 2) {
+          if constexpr (MODE == 3) {
+            int32_t kind;
+            id = sample_weighted_negative(seed, step, (uint32_t)slot, pairs[2 * q], pairs[2 * q + 1], (uint32_t)n_rows, ln, kind);
+            if (ln.kind_out) ln.kind_out[(int64_t)s * ln.kind_step_stride + i] = kind;
+          }
         } else {
           id = pairs[2 * q + (k ? 1 : 0)];
           // a pair id outside the catalogue (the reference raises IndexError, inputs.py:158): the row
@@ -815,6 +886,23 @@ extern "C" int cdml_sample_listed(const int32_t *pairs, int64_t n_pairs, int64_t
   return check_launch("sample_listed");
 }
 
+extern "C" int cdml_sample_weighted(const int32_t *pairs, int64_t n_pairs, int64_t n_rows, uint64_t seed, uint64_t step,
+                                    const uint64_t *step_dev, int batch, int64_t slot0, int64_t batch_global,
+                                    const int32_t *start, int64_t n_live, const int32_t *coarse, int bits, int32_t *idx_out,
+                                    int32_t *kind_out, cdml_stream_t stream) {
+  CDML_REQUIRE(pairs && idx_out && n_pairs > 0 && batch > 0 && slot0 >= 0, CDML_E_BADARG, "sample_weighted: bad argument");
+  CDML_REQUIRE(n_rows >= 3 && n_rows <= 0x7FFFFFFFll, CDML_E_BADARG, "sample_weighted: n_rows must be in [3, 2^31)");
+  CDML_REQUIRE(batch_global >= slot0 + batch, CDML_E_BADARG, "sample_weighted: batch_global < slot0 + batch");
+  int rc = check_weighted("sample_weighted", start, coarse, n_live, n_rows, bits);
+  if (rc) return rc;
+  WeightedNeg wn;
+  wn.start = reinterpret_cast<const uint32_t *>(start), wn.coarse = coarse, wn.n_live = (int32_t)n_live, wn.shift = 32 - bits;
+  wn.kind_out = kind_out;
+  hipLaunchKernelGGL(k_sample_weighted, dim3((batch + kThreads - 1) / kThreads), dim3(kThreads), 0, (hipStream_t)stream,
+                     pairs, n_pairs, (uint32_t)n_rows, seed, step, step_dev, batch, slot0, batch_global, wn, idx_out);
+  return check_launch("sample_weighted");
+}
+
 extern "C" int cdml_sample_inbatch(const int32_t *pairs, int64_t n_pairs, uint64_t seed,
                                    uint64_t step, const uint64_t *step_dev, int batch,
                                    int64_t slot0, int64_t batch_global, int32_t *rows_out,
@@ -870,7 +958,7 @@ extern "C" int cdml_gather_rows_x3(const float *src, int64_t n_rows, int64_t row
 }
 
 // The fused launch of one row format: k_sample_gather<MODE, ROW<NCH>, KI> for the plan's mode, bucket and interleaved copy.
-// Mode 2 and KI are instantiated only for the formats that have them.
+// Modes 2 and 3 and KI are instantiated only for the formats that have them.
 template <const GatherFormat &FMT, template <int> class ROW>
 static int sample_gather(const char *who, const SampleGatherArgs &a, cdml_stream_t stream) {
   static_assert(ROW<8>::kRows * kWavesPerBlock == FMT.rows_per_chunk && ROW<8>::kPerChunk == FMT.per_chunk,
@@ -882,10 +970,16 @@ static int sample_gather(const char *who, const SampleGatherArgs &a, cdml_stream
     ln.lists = a.listed->lists, ln.ldl = a.listed->ldl, ln.L = (uint32_t)a.listed->L, ln.hard_thresh = a.listed->hard_thresh;
     ln.kind_out = a.listed->kind_out, ln.kind_step_stride = a.listed->kind_step_stride;
   }
-  auto launch = [&](auto mode, auto ki) {
+  WeightedNeg wn;
+  if (a.weighted) {
+    wn.start = reinterpret_cast<const uint32_t *>(a.weighted->start), wn.coarse = a.weighted->coarse;
+    wn.n_live = (int32_t)a.weighted->n_live, wn.shift = 32 - a.weighted->bits;
+    wn.kind_out = a.weighted->kind_out, wn.kind_step_stride = a.weighted->kind_step_stride;
+  }
+  auto launch = [&](auto mode, auto ki, auto ln) {
     return with_nch<FMT, true>(who, p.nch, [&](auto nch) {
       using Row = ROW<decltype(nch)::value>;
-      hipLaunchKernelGGL((k_sample_gather<decltype(mode)::value, Row, decltype(ki)::value>), dim3(p.grid), dim3(kThreads), 0,
+      hipLaunchKernelGGL((k_sample_gather<decltype(mode)::value, Row, decltype(ki)::value, decltype(ln)>), dim3(p.grid), dim3(kThreads), 0,
                          (hipStream_t)stream, a.pairs, a.n_pairs, a.seed, a.step, a.step_dev, a.batch, a.slot0, a.batch_global,
                          static_cast<const typename Row::In *>(a.table), a.n_rows, a.row_stride, a.F, a.idx_out, a.shift_out,
                          static_cast<typename Row::Out *>(a.x_out), a.out_stride, a.n_steps, a.x_step_stride, a.idx_step_stride,
@@ -893,9 +987,12 @@ static int sample_gather(const char *who, const SampleGatherArgs &a, cdml_stream
     });
   };
   auto by_mode = [&](auto ki) {
-    if (a.mode == 0) return launch(std::integral_constant<int, 0>{}, ki);
-    if (a.mode == 1) return launch(std::integral_constant<int, 1>{}, ki);
-    if constexpr (FMT.who_listed != nullptr) return launch(std::integral_constant<int, 2>{}, ki);
+    if (a.mode == 0) return launch(std::integral_constant<int, 0>{}, ki, ln);
+    if (a.mode == 1) return launch(std::integral_constant<int, 1>{}, ki, ln);
+    if constexpr (FMT.who_listed != nullptr) {
+      if (a.mode == 2) return launch(std::integral_constant<int, 2>{}, ki, ln);
+      return launch(std::integral_constant<int, 3>{}, ki, wn);
+    }
     return fail(CDML_E_UNSUPPORTED, "%s: no kernel for mode %d", who, a.mode);      // (the plan refuses it first)
   };
   int rc;
@@ -1014,6 +1111,52 @@ extern "C" int cdml_sample_gather_listed_f16(const int32_t *pairs, int64_t n_pai
   const SampleGatherArgs a = {2, pairs, n_pairs, seed, step, step_dev, batch, slot0, batch_global, table, n_rows, row_stride, F,
                               idx_out, nullptr, x_out_bf16, out_stride, n_steps, x_step_stride, idx_step_stride, oob_flag,
                               nullptr, 0, false, &l};
+  return sample_gather<kGatherF16, RowF16>("sample_gather_f16", a, stream);
+}
+
+// ---- weighted negatives (include/cdml_negweights.h): the fused launch in sampler mode 3, the listed entry points' twins ----
+extern "C" int cdml_sample_gather_weighted(const int32_t *pairs, int64_t n_pairs, uint64_t seed, uint64_t step,
+                                           const uint64_t *step_dev, int batch, int64_t slot0, int64_t batch_global,
+                                           const float *table, int64_t n_rows, int64_t row_stride, int F,
+                                           const int32_t *start, int64_t n_live, const int32_t *coarse, int bits,
+                                           int32_t *idx_out, int32_t *kind_out, float *x_out, int64_t out_stride, int n_steps,
+                                           int64_t x_step_stride, int64_t idx_step_stride, int64_t kind_step_stride,
+                                           int32_t *oob_flag, cdml_stream_t stream) {
+  const WeightedArgs w = {"sample_gather_weighted", start, coarse, n_live, bits, kind_out, kind_step_stride};
+  const SampleGatherArgs a = {3, pairs, n_pairs, seed, step, step_dev, batch, slot0, batch_global, table, n_rows, row_stride, F,
+                              idx_out, nullptr, x_out, out_stride, n_steps, x_step_stride, idx_step_stride, oob_flag,
+                              nullptr, 0, false, nullptr, &w};
+  return sample_gather<kGatherF32, RowF32>("sample_gather", a, stream);
+}
+
+// three-plane rows; x_ki null = no k8-interleaved copy
+extern "C" int cdml_sample_gather_weighted_x3(const int32_t *pairs, int64_t n_pairs, uint64_t seed, uint64_t step,
+                                              const uint64_t *step_dev, int batch, int64_t slot0, int64_t batch_global,
+                                              const float *table, int64_t n_rows, int64_t row_stride, int F,
+                                              const int32_t *start, int64_t n_live, const int32_t *coarse, int bits,
+                                              int32_t *idx_out, int32_t *kind_out, uint16_t *x_out_planes, int64_t out_stride,
+                                              int n_steps, int64_t x_step_stride, int64_t idx_step_stride,
+                                              int64_t kind_step_stride, int32_t *oob_flag, uint16_t *x_ki,
+                                              int64_t ki_step_stride, cdml_stream_t stream) {
+  const WeightedArgs w = {"sample_gather_weighted_x3", start, coarse, n_live, bits, kind_out, kind_step_stride};
+  const SampleGatherArgs a = {3, pairs, n_pairs, seed, step, step_dev, batch, slot0, batch_global, table, n_rows, row_stride, F,
+                              idx_out, nullptr, x_out_planes, out_stride, n_steps, x_step_stride, idx_step_stride, oob_flag,
+                              x_ki, ki_step_stride, false, nullptr, &w};
+  return sample_gather<kGatherX3, RowF32X3>("sample_gather_x3", a, stream);
+}
+
+// fp16 table -> bf16 rows
+extern "C" int cdml_sample_gather_weighted_f16(const int32_t *pairs, int64_t n_pairs, uint64_t seed, uint64_t step,
+                                               const uint64_t *step_dev, int batch, int64_t slot0, int64_t batch_global,
+                                               const uint16_t *table, int64_t n_rows, int64_t row_stride, int F,
+                                               const int32_t *start, int64_t n_live, const int32_t *coarse, int bits,
+                                               int32_t *idx_out, int32_t *kind_out, uint16_t *x_out_bf16, int64_t out_stride,
+                                               int n_steps, int64_t x_step_stride, int64_t idx_step_stride,
+                                               int64_t kind_step_stride, int32_t *oob_flag, cdml_stream_t stream) {
+  const WeightedArgs w = {"sample_gather_weighted_f16", start, coarse, n_live, bits, kind_out, kind_step_stride};
+  const SampleGatherArgs a = {3, pairs, n_pairs, seed, step, step_dev, batch, slot0, batch_global, table, n_rows, row_stride, F,
+                              idx_out, nullptr, x_out_bf16, out_stride, n_steps, x_step_stride, idx_step_stride, oob_flag,
+                              nullptr, 0, false, nullptr, &w};
   return sample_gather<kGatherF16, RowF16>("sample_gather_f16", a, stream);
 }
 

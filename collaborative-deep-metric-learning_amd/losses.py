@@ -108,8 +108,10 @@ class _NPairMixedFunction(torch.autograd.Function):
         de = torch.zeros_like(e) if need else None
         stats = torch.zeros(4, dtype=torch.float32, device=dev)
         bias = None if logq is None else logq.reshape(-1).to(device=dev, dtype=torch.float32)
+        vec = isinstance(negative_logq, torch.Tensor)     # one log-probability per negative: the chain's vector path
+        nb = negative_logq.reshape(-1).to(device=dev, dtype=torch.float32).contiguous() if vec and bias is not None else None
         ops.npair_mixed_loss(e, rows, B, Dp, temperature, symmetric, "f32x3", de=de, stats=stats, ws=ws, logq=bias,
-                             lq_u=negative_logq if bias is not None else 0.0)
+                             lq_u=negative_logq if bias is not None and not vec else 0.0, neg_bias=nb)
         part = ws.ws[:4 * B].view(B, 4)
         pos = part[:, 1].clone()
         neg = part[:, 2] / part[:, 3].clamp(min=1.0)
@@ -137,7 +139,8 @@ class NPairLoss(BaseLoss):
         catalogue negative per pair; every anchor's softmax then also runs over all of them, and they receive a gradient
         (the returned dict gains "negatives").  The batch must be a multiple of 256 pairs (a padding row would be a
         negative).  ``negative_ids`` (int [batch], required with ``ids``): a negative that is the anchor's or its positive's
-        video does not count; ``negative_logq`` (one float, with ``logq``; default 0): the uniform draw's log probability."""
+        video does not count; ``negative_logq`` (with ``logq``; default 0): one float -- the uniform draw's log probability
+        -- or a float tensor [batch], the log sampling probability of each negative (a non-uniform proposal)."""
         if pairs.dim() != 3 or pairs.shape[1] != 2:
             raise ValueError("pairs must be [batch, 2, embedding]")
         if negatives is None and (negative_ids is not None or negative_logq is not None):
@@ -155,9 +158,13 @@ class NPairLoss(BaseLoss):
             if negative_logq is not None:
                 if logq is None:
                     raise ValueError("negative_logq goes with logq (without one no logit is corrected)")
-                negative_logq = float(negative_logq)
-                if not (float("-inf") < negative_logq < float("inf")):
-                    raise ValueError("negative_logq must be a finite float")
+                if isinstance(negative_logq, torch.Tensor) and negative_logq.numel() != 1:
+                    if negative_logq.numel() != B or not bool(torch.isfinite(negative_logq).all()):
+                        raise ValueError("a negative_logq tensor must hold one finite log-probability per negative ([batch])")
+                else:
+                    negative_logq = float(negative_logq)
+                    if not (float("-inf") < negative_logq < float("inf")):
+                        raise ValueError("negative_logq must be a finite float")
         if ids is not None and ids.numel() != 2 * pairs.shape[0]:
             raise ValueError("ids must hold one video id per row ([batch, 2])")
         if logq is not None:
@@ -169,7 +176,7 @@ class NPairLoss(BaseLoss):
         if negatives is not None:
             negatives = negatives.to(torch.float32)
             loss, pos, neg, stats = _NPairMixedFunction.apply(pairs, negatives, float(temperature), bool(symmetric), ids, logq,
-                                                              negative_ids, negative_logq or 0.0)
+                                                              negative_ids, 0.0 if negative_logq is None else negative_logq)
             self.summary = {"mean_pos_dist": stats[1], "mean_neg_dist": stats[2]}
             return {"npair_loss": loss,
                     "anchors": pairs[:, 0:1, :],

@@ -194,6 +194,64 @@ def sample_gather_listed(pairs, seed, step, batch, table, feature_size, lists, h
     return x_out
 
 
+# ---- weighted negatives (sampler mode 3; include/cdml_negweights.h, the tables: negweights.NegativeWeights.tables) ----
+def _weighted_args(tables, n_rows):
+    """(start pointer, n_live, coarse pointer, bits) of a weighted draw; ``tables``: anything with device tensors ``start``
+    (int32, uint32 bits) and ``coarse`` (int32 [2^bits + 1]), ``bits`` and ``n_live`` (negweights.NegTables)."""
+    start, coarse, bits, n_live = tables.start, tables.coarse, int(tables.bits), int(tables.n_live)
+    if not 8 <= bits <= 24:
+        raise ValueError("bits must be in [8, 24], got %d" % bits)
+    if coarse.dim() != 1 or coarse.numel() != (1 << bits) + 1 or not coarse.is_contiguous():
+        raise ValueError("the coarse table holds 2^bits + 1 = %d int32 entries, got %s" % ((1 << bits) + 1, tuple(coarse.shape)))
+    if start.dim() != 1 or not start.is_contiguous() or not 3 <= n_live <= start.numel() or n_live > n_rows:
+        raise ValueError("the start table holds n_live int32 entries, 3 <= n_live <= n_rows = %d (got n_live = %d, %d entries)"
+                         % (n_rows, n_live, start.numel()))
+    return _p(start, torch.int32), n_live, _p(coarse, torch.int32), bits
+
+
+def sample_weighted(pairs, n_rows, seed, step, batch, tables, idx_out, kind_out=None, slot0=0, batch_global=None, step_dev=None):
+    """The ids of the weighted negative draw, the twin of sample_listed: idx_out int32 [3 * batch]; kind_out (int32 [batch]
+    or None) = 1 where the negative came from the weighted draw, 0 where the uniform fall-back drew it."""
+    bg = batch if batch_global is None else batch_global
+    sp, n_live, cp, bits = _weighted_args(tables, n_rows)
+    if kind_out is not None and kind_out.numel() < batch:
+        raise ValueError("kind_out needs one int32 per triplet")
+    call("cdml_sample_weighted", _p(pairs, torch.int32), pairs.shape[0], n_rows, seed, 0 if step is None else step,
+         _p(step_dev, torch.int64), batch, slot0, bg, sp, n_live, cp, bits, _p(idx_out, torch.int32), _p(kind_out, torch.int32),
+         _stream())
+    return idx_out
+
+
+def sample_gather_weighted(pairs, seed, step, batch, table, feature_size, tables, idx_out, x_out, kind_out=None,
+                           slot0=0, batch_global=None, step_dev=None, n_steps=1, oob_flag=None, x_ki=None):
+    """sample_gather in sampler mode 3 (weighted negatives, three rows per triplet): the row formats, x_ki and kind_out of
+    sample_gather_listed (the two-fp16-plane output has no weighted form)."""
+    bg = batch if batch_global is None else batch_global
+    fmt = _gather_format(table, x_out)
+    if fmt == "_h2":
+        raise ValueError("the two-fp16-plane rows (precision 'f16x2') have no weighted form")
+    (tp, tld), (xp, xld), (xss, iss, kss, kis), _ = _gather_io(
+        fmt, table, x_out, idx_out, n_steps, x_ki, ("x_ki goes with the three-plane output", "x_ki must be a contiguous bf16 buffer"),
+        kind_out, batch)
+    sp, n_live, cp, bits = _weighted_args(tables, table.shape[0])
+    ki = (_p(x_ki), kis) if fmt == "_x3" else ()
+    call("cdml_sample_gather_weighted" + fmt, _p(pairs, torch.int32), pairs.shape[0], seed, 0 if step is None else step,
+         _p(step_dev, torch.int64), batch, slot0, bg, tp, table.shape[0], tld, feature_size, sp, n_live, cp, bits,
+         _p(idx_out, torch.int32), _p(kind_out, torch.int32), xp, xld, n_steps, xss, iss, kss, _p(oob_flag, torch.int32), *ki,
+         _stream())
+    return x_out
+
+
+def negw_bias(lq, rows3, B, offset, neg_bias):
+    """neg_bias[j] = lq[rows3[3j + 2]] + offset for j < B: the per-negative logQ of the drawn negatives (lq fp32 [n_rows],
+    e.g. NegativeWeights' ``lq``); an id outside the catalogue gives 0."""
+    if rows3.numel() < 3 * B or neg_bias.numel() < B:
+        raise ValueError("negw_bias needs 3 B ids and B outputs")
+    call("cdml_negw_bias", _p(lq, torch.float32), lq.numel(), _p(rows3, torch.int32), int(B), float(offset),
+         _p(neg_bias, torch.float32), _stream())
+    return neg_bias
+
+
 def route_rows(ids, rows_per_shard, world, capacity, send_ids, slot_out, overflow_flag):
     call("cdml_route_rows", _p(ids, torch.int32), ids.numel(), rows_per_shard, world, capacity,
          _p(send_ids, torch.int32), _p(slot_out, torch.int32), _p(overflow_flag, torch.int32), _stream())
@@ -1002,18 +1060,25 @@ def npair_mixed_workspace(B, M):
 
 
 def _mixed_args(S, rows3, B, neg_col, mem_col, mem_id, bias, lq_u, mem_bias, temperature, symmetric):
+    """(suffix of the entry point, its leading arguments): ``lq_u`` a float -- the uniform block's scalar -- or a fp32 tensor
+    [B], the per-negative bias of the "_nb" entry points (include/cdml_negweights.h)."""
     sp, sld = _mat(S)
-    return (sp, sld, _p(rows3, torch.int32), int(B), int(neg_col), int(mem_col), _p(mem_id, torch.int32),
-            0 if mem_id is None else mem_id.numel(), _p(bias, torch.float32), float(lq_u), _p(mem_bias, torch.float32),
-            float(temperature), 1 if symmetric else 0)
+    nb = isinstance(lq_u, torch.Tensor)
+    if nb and (lq_u.dim() != 1 or lq_u.numel() != int(B) or not lq_u.is_contiguous()):
+        raise ValueError("neg_bias must be a contiguous fp32 tensor [B = %d], got %s" % (int(B), tuple(lq_u.shape)))
+    return "_nb" if nb else "", (sp, sld, _p(rows3, torch.int32), int(B), int(neg_col), int(mem_col), _p(mem_id, torch.int32),
+                                 0 if mem_id is None else mem_id.numel(), _p(bias, torch.float32),
+                                 _p(lq_u, torch.float32) if nb else float(lq_u), _p(mem_bias, torch.float32),
+                                 float(temperature), 1 if symmetric else 0)
 
 
 def npair_mixed_stats(S, rows3, B, neg_col, mem_col, mem_id, bias, lq_u, mem_bias, temperature, symmetric, lse, stats,
                       workspace):
     """cdml_npair_mixed_stats: lse and stats[0..3] over S = A [P; N; Mem]^T (blocks at columns 0, neg_col, mem_col), the
-    ids rows3 int32 [3B] in the uniform sampler's layout (a, p, n per triplet) or None.  bias None: uncorrected."""
-    call("cdml_npair_mixed_stats", *_mixed_args(S, rows3, B, neg_col, mem_col, mem_id, bias, lq_u, mem_bias, temperature,
-                                                symmetric), _p(lse), _p(stats), _p(workspace),
+    ids rows3 int32 [3B] in the uniform sampler's layout (a, p, n per triplet) or None.  bias None: uncorrected.
+    lq_u: the uniform block's scalar, or a fp32 tensor [B] -- one bias per drawn negative (cdml_npair_mixed_stats_nb)."""
+    nb, args = _mixed_args(S, rows3, B, neg_col, mem_col, mem_id, bias, lq_u, mem_bias, temperature, symmetric)
+    call("cdml_npair_mixed_stats" + nb, *args, _p(lse), _p(stats), _p(workspace),
          workspace.numel() * workspace.element_size(), _stream())
     return lse, stats
 
@@ -1022,15 +1087,15 @@ def npair_mixed_grad_x3(S, rows3, B, neg_col, mem_col, mem_id, bias, lq_u, mem_b
                         plane):
     """W_planes bf16 [>= B, >= 2 plane + span] <- the gradient weights of all blocks as three planes, one launch."""
     wp, wld = _mat16(W_planes)
-    call("cdml_npair_mixed_grad_x3", *_mixed_args(S, rows3, B, neg_col, mem_col, mem_id, bias, lq_u, mem_bias, temperature,
-                                                  symmetric), _p(lse), wp, wld, int(plane), _stream())
+    nb, args = _mixed_args(S, rows3, B, neg_col, mem_col, mem_id, bias, lq_u, mem_bias, temperature, symmetric)
+    call("cdml_npair_mixed_grad_x3" + nb, *args, _p(lse), wp, wld, int(plane), _stream())
     return W_planes
 
 
 def npair_mixed_grad_f32(S, rows3, B, neg_col, mem_col, mem_id, bias, lq_u, mem_bias, temperature, symmetric, lse, W):
     wp, wld = _mat(W)
-    call("cdml_npair_mixed_grad_f32", *_mixed_args(S, rows3, B, neg_col, mem_col, mem_id, bias, lq_u, mem_bias, temperature,
-                                                   symmetric), _p(lse), wp, wld, _stream())
+    nb, args = _mixed_args(S, rows3, B, neg_col, mem_col, mem_id, bias, lq_u, mem_bias, temperature, symmetric)
+    call("cdml_npair_mixed_grad_f32" + nb, *args, _p(lse), wp, wld, _stream())
     return W
 
 
@@ -1156,7 +1221,7 @@ def uniform_logq(logq, value=None):
 
 
 def npair_mixed_loss(e3, rows3, B, Dp, temperature=0.1, symmetric=True, precision="f32x3", de=None, stats=None, ws=None,
-                     step=0, step_dev=None, logq=None, lq_u=0.0):
+                     step=0, step_dev=None, logq=None, lq_u=0.0, neg_bias=None):
     """The N-pair loss with mixed negative sampling (include/cdml_npair_mixed.h) of B triplets and its gradient.
     e3: fp32 [3 B, >= Dp] unit rows in the uniform sampler's layout (row 3i = anchor, 3i+1 = positive, 3i+2 = uniform
     negative); rows3: int32 [3 B] video ids laid out the same, or None (no ring, no correction).  The chain: the plane
@@ -1164,7 +1229,9 @@ def npair_mixed_loss(e3, rows3, B, Dp, temperature=0.1, symmetric=True, precisio
     over K = 2 B + M into de[0::3], dP = W_p^T A into de[1::3], dN = W_n^T A into de[2::3] (de fp32 [3 B, Dp]; None: loss
     only) -> with a ring, the push of the step's positives.  ws: an NPairMixed (B == ws.Bp).  logq: a LogQTable /
     LogQEstimator (bias of the in-batch and memory blocks; an estimator is updated by the positives after W), or a fp32
-    tensor [2 B] of lq(a_i), lq(p_i) per pair (no ring), with the uniform block's scalar ``lq_u`` (``uniform_logq``).
+    tensor [2 B] of lq(a_i), lq(p_i) per pair (no ring), with the uniform block's scalar ``lq_u`` (``uniform_logq``) or
+    ``neg_bias``, a fp32 tensor [B] of one log sampling probability per drawn negative (``negw_bias``; the "_nb" entry
+    points of include/cdml_negweights.h; not together with a non-zero ``lq_u``; not read without a correction).
     Returns (stats, lse)."""
     if not (temperature > 0.0) or temperature == float("inf"):
         raise ValueError("temperature must be finite and > 0, got %r" % (temperature,))
@@ -1183,6 +1250,12 @@ def npair_mixed_loss(e3, rows3, B, Dp, temperature=0.1, symmetric=True, precisio
         raise ValueError("the cross-batch memory and the logQ correction need the rows' video ids")
     if logq is None and row_logq is None and lq_u:
         raise ValueError("lq_u goes with a logQ correction (logq=...)")
+    if neg_bias is not None:
+        if lq_u:
+            raise ValueError("neg_bias (one log-probability per negative) and a non-zero lq_u (one for the block) exclude each other")
+        if not isinstance(neg_bias, torch.Tensor) or neg_bias.dtype != torch.float32 or neg_bias.numel() != B:
+            raise ValueError("neg_bias must be a fp32 tensor [B = %d]" % B)
+        lq_u = neg_bias.reshape(-1)                         # (a tensor in lq_u's place routes the launches to the _nb entry points)
     if stats is None:
         stats = torch.zeros(4, dtype=torch.float32, device=e3.device)
     Bp, K, nc, mc = ws.Bp, ws.K, ws.neg_col, ws.mem_col

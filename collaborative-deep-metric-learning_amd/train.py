@@ -15,13 +15,14 @@ rate live in device memory so replays advance the sampler and Adam's bias
 correction.  ``Trainer`` mirrors the reference's loop (train.py:260-336).
 """
 import logging
+import math
 import os
 import time
 from types import SimpleNamespace
 
 import torch
 
-from . import engine, ops
+from . import engine, negweights, ops
 from .inputs import MODE_INBATCH, MODE_UNIFORM
 
 # sampler mode per negative policy: "semihard" samples like "inbatch" (rows a_i, p_i)
@@ -41,7 +42,7 @@ def exponential_decay(base_lr, global_step, decay_steps, decay_rate, staircase=T
 def validate_args(table, batch_size, mode="uniform", optimizer="adam", exchange=None, grad_sync=None, slot0=0,
                   batch_global=None, precision="auto", train_table=False, temperature=0.1, memory_size=0, memory_start=0,
                   logq=None, logq_alpha=0.01, logq_init_gap=None, uniform_negatives=False, uniform_logq=None,
-                  npair_sync=None, negative_lists=None, hard_fraction=1.0):
+                  npair_sync=None, negative_lists=None, hard_fraction=1.0, negative_weights=None):
     """The refusals of TrainStep's arguments that come before its device and pair-id checks, in its order; returns the values
     normalised on the way (``memory_size``, ``logq``, ``uniform_logq``, ...; ``precision``: resolved for mode "npair", else as
     given -- resolve_precision).  ``table``: anything with ``n_rows_global`` and a ``data`` of the catalogue's dtype."""
@@ -65,6 +66,20 @@ def validate_args(table, batch_size, mode="uniform", optimizer="adam", exchange=
                 or negative_lists.shape[0] != table.n_rows_global or not 1 <= negative_lists.shape[1] <= 1024):
             raise ValueError("negative_lists must be an int32 [n_rows = %d, L in [1, 1024]] tensor, got %s %s"
                              % (table.n_rows_global, negative_lists.dtype, tuple(negative_lists.shape)))
+    if negative_weights is not None:
+        for name, on in (("negative_lists", negative_lists is not None), ("uniform_logq", uniform_logq is not None),
+                         ("exchange", exchange is not None), ("grad_sync", grad_sync is not None),
+                         ("npair_sync", npair_sync is not None), ("train_table", bool(train_table))):
+            if on:
+                raise ValueError("negative_weights does not go with %s: weighted negatives run on one GPU over a frozen "
+                                 "catalogue, and their own log-probabilities correct the block" % name)
+        if precision == "f16x2":
+            raise ValueError("negative_weights does not go with precision 'f16x2' (its gather has no weighted form): use "
+                             "'f32x3', 'f32' or 'bf16'")
+        if not (mode == "uniform" or (mode == "npair" and uniform_negatives)):
+            raise ValueError("negative_weights goes with a mode that draws a negative (mode 'uniform', or mode 'npair' with "
+                             "uniform_negatives=True), not mode %r" % (mode,))
+        negative_weights = negweights.as_negative_weights(negative_weights, table.n_rows_global)
     if mode not in _MODES:
         raise ValueError("mode must be 'uniform', 'inbatch', 'semihard' or 'npair'")
     if npair_sync is not None:
@@ -146,7 +161,7 @@ def validate_args(table, batch_size, mode="uniform", optimizer="adam", exchange=
     return SimpleNamespace(precision=precision, temperature=temperature, memory_size=memory_size, memory_start=memory_start,
                            logq=logq, logq_stream=logq_stream, logq_alpha=logq_alpha, logq_init_gap=logq_init_gap,
                            uniform_negatives=uniform_negatives, uniform_logq=uniform_logq, negative_lists=negative_lists,
-                           hard_fraction=hard_fraction)
+                           hard_fraction=hard_fraction, negative_weights=negative_weights)
 
 
 def resolve_precision(table, rows, precision, use_graph=False, exchange=None, grad_sync=None):
@@ -174,7 +189,7 @@ class TrainStep:
                  clip_gradient_norm=0.0, regularization_penalty=0.0, l2_penalty=1e-8,
                  grad_sync_mode="bucketed", temperature=0.1, symmetric=True, memory_size=0, memory_start=0,
                  logq=None, logq_alpha=0.01, logq_init_gap=None, uniform_negatives=False, uniform_logq=None,
-                 npair_sync=None, negative_lists=None, hard_fraction=1.0):
+                 npair_sync=None, negative_lists=None, hard_fraction=1.0, negative_weights=None):
         """table: FeatureTable (whole catalogue, or this rank's shard when
         ``exchange`` is given); pairs: int32 [P,2] device tensor; ``exchange`` /
         ``grad_sync``: the multi-GPU hooks of cdml_amd.dist (None on one GPU).
@@ -261,13 +276,25 @@ class TrainStep:
         ``set_negative_lists(t)`` copies into it in place (captured graphs stay valid), ``refresh_negative_lists(k)`` mines
         them from the current weights, ``hard_share()`` is the last step's share of listed negatives; the lists and
         ``hard_fraction`` are part of ``state_dict``.  ``gather_ahead`` is 1 while lists are set: a refresh must not race
-        rows fetched ahead."""
+        rows fetched ahead.
+
+        ``negative_weights`` (a negweights.NegativeWeights, or a tensor of one finite weight >= 0 per catalogue row, at least
+        three of them positive; None = none): the negative is drawn from that distribution instead of uniformly -- sampler
+        mode 3 of the fused sampler + gather (include/cdml_negweights.h), e.g. ``NegativeWeights.from_counts(degrees,
+        power=0.75)``; a draw that keeps landing on the anchor or its positive falls back to the uniform one.  With mode
+        "uniform" the hinge takes the negative; with mode "npair" and ``uniform_negatives`` it is the N block of the mixed
+        softmax, and with ``logq`` that block is corrected per negative by exactly the log-probability the sampler used,
+        ``lq[n_j]`` + ``ops.uniform_logq(logq)`` + log(n_rows) (0 for a logq table, the estimator's scale for "stream"; equal
+        weights reproduce the scalar ``lq_u``).  One GPU, a frozen catalogue, precision "f32x3", "f32" or "bf16"; not with
+        ``negative_lists`` or ``uniform_logq``.  ``set_negative_weights(w)`` copies new tables in place (captured graphs
+        stay valid), ``weighted_share()`` is the last step's share of negatives the weighted draw gave; the quanta are
+        part of ``state_dict``.  ``gather_ahead`` is 1 while weights are set."""
         a = validate_args(table, batch_size, mode=mode, optimizer=optimizer, exchange=exchange, grad_sync=grad_sync,
                           slot0=slot0, batch_global=batch_global, precision=precision, train_table=train_table,
                           temperature=temperature, memory_size=memory_size, memory_start=memory_start, logq=logq,
                           logq_alpha=logq_alpha, logq_init_gap=logq_init_gap, uniform_negatives=uniform_negatives,
                           uniform_logq=uniform_logq, npair_sync=npair_sync, negative_lists=negative_lists,
-                          hard_fraction=hard_fraction)
+                          hard_fraction=hard_fraction, negative_weights=negative_weights)
         self.device = torch.device(device)
         if self.device.type == "cuda" and self.device.index is not None \
                 and torch.cuda.current_device() != self.device.index:
@@ -391,6 +418,17 @@ class TrainStep:
         if a.negative_lists is not None:
             self.neg_lists = a.negative_lists.to(dev).contiguous().clone()
             self.kind = torch.zeros(self.B, dtype=i32, device=dev)
+        # weighted negatives: ONE device copy of the tables (set_negative_weights copies into it; start padded to n_rows, so
+        # every later distribution fits), the last step's kinds and the N block's per-negative bias
+        self.neg_weights = self.neg_tables = self.neg_bias = None
+        if a.negative_weights is not None:
+            self.neg_weights = a.negative_weights
+            self.neg_tables = a.negative_weights.tables(dev, pad_to=self.table.n_rows_global)
+            self.kind = torch.zeros(self.B, dtype=i32, device=dev)
+            if a.uniform_negatives and self.npair_logq is not None:
+                self.neg_bias = torch.zeros(self.B, dtype=f32, device=dev)
+                self.neg_bias_offset = self.uniform_lq + math.log(self.table.n_rows_global)
+                self.uniform_lq = 0.0                        # (the block is corrected per negative, not by the scalar)
 
     def _build_optimizer_state(self, clip_gradient_norm, regularization_penalty, l2_penalty):
         """Step counter and learning rate on the device, the optimizer's slots, the clipping / regulariser scratch."""
@@ -438,8 +476,8 @@ class TrainStep:
             target = 230e6 if self.engine.table_dtype == torch.float16 else 300e6      # (fp16 -> bf16 rows: half the bytes read)
             gather_ahead = min(4, max(1, int(round(target / (self.R * row_bytes)))))
         self.gather_ahead = max(1, int(gather_ahead))
-        if self.exchange is not None or self.train_table or self.neg_lists is not None:
-            self.gather_ahead = 1                            # (lists: a refresh must not race rows fetched ahead)
+        if self.exchange is not None or self.train_table or self.neg_lists is not None or self.neg_tables is not None:
+            self.gather_ahead = 1                            # (lists, weights: a refresh must not race rows fetched ahead)
         self._ahead_base = None
         if self.gather_ahead > 1:
             # (fetching the NEXT block on a side stream under this block's GEMMs was measured: the
@@ -594,6 +632,11 @@ class TrainStep:
                                      slot0=self.slot0, batch_global=self.batch_global, step_dev=self.step_dev,
                                      oob_flag=self.oob,
                                      x_ki=self.ws.xk if self.ws.kint else None)
+        elif self.neg_tables is not None:
+            ops.sample_gather_weighted(self.pairs, self.seed, None, self.B, self.table.data, self.table.feature_size,
+                                       self.neg_tables, self.idx, self.ws.x_hat, kind_out=self.kind, slot0=self.slot0,
+                                       batch_global=self.batch_global, step_dev=self.step_dev, oob_flag=self.oob,
+                                       x_ki=self.ws.xk if self.ws.kint else None)
         elif self.exchange is None:
             ops.sample_gather(m, self.pairs, self.seed, None, self.B, self.table.data,
                               self.table.feature_size, self.idx, self.ws.x_hat,
@@ -641,6 +684,26 @@ class TrainStep:
         self.set_negative_lists(lists)
         return lists
 
+    # --------------------------------------------------- weighted negatives --
+    def set_negative_weights(self, w):
+        """Copy the tables of a new distribution (a NegativeWeights of the step's ``bits``, or a weight tensor [n_rows]) into
+        the step's device copies IN PLACE: the kernels keep reading the same buffers, so captured graphs stay valid."""
+        if self.neg_tables is None:
+            raise ValueError("this step has no negative weights (TrainStep(negative_weights=...))")
+        nw = negweights.as_negative_weights(w, self.table.n_rows_global, self.neg_weights.bits)
+        if nw.bits != self.neg_weights.bits:
+            raise ValueError("negative weights must stay at bits = %d, got %d" % (self.neg_weights.bits, nw.bits))
+        new = nw.tables(self.device, pad_to=self.table.n_rows_global)
+        for name in ("start", "coarse", "lq"):
+            getattr(self.neg_tables, name).copy_(getattr(new, name))
+        self.neg_weights = nw
+
+    def weighted_share(self):
+        """The share of the last step's triplets whose negative the weighted draw gave (synchronises)."""
+        if self.neg_tables is None:
+            raise ValueError("this step has no negative weights (TrainStep(negative_weights=...))")
+        return float(self.kind.sum().item()) / self.B
+
     def enable_variance(self, on=True):
         """Also compute build_graph's ``variance`` summary (calc_var, train.py:67-71,151) each
         step: stats[4]."""
@@ -686,9 +749,12 @@ class TrainStep:
         de = self.ws.de if with_grad else None
         if self.npair_mixed is not None:
             # mixed negative sampling: the chain over [P | N | Mem] on the uniform sampler's rows, de[2::3] = dN included
+            # (weighted negatives under a correction: the N block's bias is the drawn negatives' own log-probability)
+            if self.neg_bias is not None:
+                ops.negw_bias(self.neg_tables.lq, self.idx, self.B, self.neg_bias_offset, self.neg_bias)
             ops.npair_mixed_loss(self.ws.e, self.idx, self.B, L.Dp, self.temperature, self.symmetric, self.precision, de=de,
                                  stats=self.stats, ws=self.npair_mixed, step=0, step_dev=self.step_dev, logq=self.npair_logq,
-                                 lq_u=self.uniform_lq)
+                                 lq_u=self.uniform_lq, neg_bias=self.neg_bias)
         elif self.npair_dp is not None:
             # the global batch's softmax: all-gather of the positives -> S_r, statistics -> all-gather of the column partials
             # -> W_r, dA, partial dP -> all-to-all -> the positives' gradient, summed in rank order (ops.npair_dp_loss)
@@ -1073,6 +1139,9 @@ class TrainStep:
         if self.neg_lists is not None:                   # hard negatives: the lists the next step draws from
             state["negative_lists"] = self.neg_lists.detach().cpu().clone()
             state["hard_fraction"] = self.hard_fraction
+        if self.neg_weights is not None:                 # weighted negatives: the quanta (the tables are re-derived on load)
+            state["negative_quanta"] = self.neg_weights.quanta.clone()
+            state["negative_bits"] = self.neg_weights.bits
         return state
 
     def load_state_dict(self, state):
@@ -1114,6 +1183,12 @@ class TrainStep:
         if lists is not None:
             self.set_negative_lists(lists.to(self.device))
             self.hard_fraction = float(state["hard_fraction"])
+        quanta = state.get("negative_quanta")
+        if (quanta is None) != (self.neg_weights is None):
+            raise ValueError("the checkpoint %s negative weights, this step %s" % (
+                "holds" if quanta is not None else "holds no", "has none" if self.neg_weights is None else "draws from them"))
+        if quanta is not None:
+            self.set_negative_weights(negweights.NegativeWeights(quanta, int(state["negative_bits"])))
         self.global_step = int(state["global_step"])
         self.step_dev.fill_(self.global_step)
         self.seed = int(state["seed"])

@@ -16,7 +16,8 @@
  *   lse_i = log( sum_j m_ij exp(S_ij / t - lq(p_j)) + sum_j cn_ij exp(U_ij / t - lq_u) + sum_k cm_ik exp(Sm_ik / t - lq(mem_k)) )
  * The sampling-bias correction (logQ): bias fp32 [2B] laid out as cdml_logq_*_gather writes it for the [2B] ids (a_i, p_i)
  * -- bias[2i] = lq(a_i), bias[2i+1] = lq(p_i) --, mem_bias [M], and lq_u, ONE scalar for the whole uniform block (a
- * uniform draw has one probability).  bias == NULL: the uncorrected loss (lq_u and mem_bias are not read).
+ * uniform draw has one probability; a non-uniform proposal takes one value per negative through the _nb entry points of
+ * cdml_negweights.h).  bias == NULL: the uncorrected loss (lq_u and mem_bias are not read).
  *
  * cdml_npair_mixed_stats: lse[i] as above, symmetric != 0 also lse[B + j] = the in-batch column's (lse float [2B]);
  *   stats[0] = mean_i (lse_i - (S_ii / t - lq(p_i))) or the mean of that and the column term; [1] = mean 2 - 2 S_ii;
