@@ -266,6 +266,20 @@ SIGNATURES_WIDE = {
     "cdml_gemm_bf16x3_tn_kb": (_i, [_p, _i64, _i64, _p, _i, _i, _i, _i, _i, _p, _i64, _p, _p, _sz, _p]),
 }
 
+# name -> (restype, argtypes); must list every symbol include/cdml_f8.h declares (the fp8 catalogue of precision "bf16": its
+# gathers, the _f16 entry points' twins, and its quantiser)
+SIGNATURES_F8 = {
+    "cdml_sample_gather_f8": (_i, [_i, _p, _i64, _u64, _u64, _p, _i, _i64, _i64, _p, _i64, _i64, _i,
+                                   _p, _p, _p, _i64, _i, _i64, _i64, _p, _p]),
+    "cdml_sample_gather_listed_f8": (_i, [_p, _i64, _u64, _u64, _p, _i, _i64, _i64, _p, _i64, _i64, _i, _p, _i64, _i, _u64,
+                                          _p, _p, _p, _i64, _i, _i64, _i64, _i64, _p, _p]),
+    "cdml_sample_gather_weighted_f8": (_i, [_p, _i64, _u64, _u64, _p, _i, _i64, _i64, _p, _i64, _i64, _i, _p, _i64, _p, _i,
+                                            _p, _p, _p, _i64, _i, _i64, _i64, _i64, _p, _p]),
+    "cdml_gather_rows_f8": (_i, [_p, _i64, _i64, _i64, _p, _i, _i, _p, _i64, _p, _p]),
+    "cdml_quantize_rows_f8_f32": (_i, [_p, _i64, _i64, _i, _p, _i64, _i64, _p, _p]),
+    "cdml_quantize_rows_f8_f16": (_i, [_p, _i64, _i64, _i, _p, _i64, _i64, _p, _p]),
+}
+
 _lib = None
 
 
@@ -286,7 +300,7 @@ def load_library():
     lib = C.CDLL(path)
     for name, (res, args) in (list(SIGNATURES.items()) + list(SIGNATURES_MIXED.items()) + list(SIGNATURES_DP.items())
                                + list(SIGNATURES_BF16.items()) + list(SIGNATURES_HARDNEG.items()) + list(SIGNATURES_WIDE.items())
-                               + list(SIGNATURES_NEGW.items())):
+                               + list(SIGNATURES_NEGW.items()) + list(SIGNATURES_F8.items())):
         fn = getattr(lib, name)          # AttributeError if the ABI lost a symbol
         fn.restype = res
         fn.argtypes = args

@@ -1,5 +1,6 @@
 // The sampler + gather launches' argument checks and launch geometry: the ONE place where they are decided, for the eight
-// fused entry points (cdml_sample_gather*, sampler_gather.hip) and the three unfused ones (cdml_gather_rows, _x3, _f16).
+// fused entry points (cdml_sample_gather*, sampler_gather.hip) and the three unfused ones (cdml_gather_rows, _x3, _f16),
+// and for their fp8-table twins (include/cdml_f8.h).
 // A row format says what the kernels of that format are built for; plan_sample_gather / plan_gather_rows check a call
 // against it -- every check returns before any HIP call -- and fill the GatherPlan the launcher selects the kernel
 // instantiation from (with_nch: the NCH buckets of the format ARE the instantiations that exist).
@@ -19,6 +20,9 @@
 #ifndef CDML_GATHER_ROWS_PER_WAVE_F16
 #define CDML_GATHER_ROWS_PER_WAVE_F16 4   // 3-KB rows: four in flight per wave
 #endif
+#ifndef CDML_GATHER_ROWS_PER_WAVE_F8
+#define CDML_GATHER_ROWS_PER_WAVE_F8 4    // 1.5-KB rows of e4m3 codes (include/cdml_f8.h): the fp16 rows' value
+#endif
 
 namespace cdml {
 
@@ -32,12 +36,13 @@ enum class LayoutWording {
   kRows32,   // F with its value; "strides must be >= F and multiples of 4", then "bases must be 16-B aligned"
   kPlanes,   // F with its value; "out_stride must be <planes> planes of >= F columns (multiples of 4)"
   kRows16,   // F without its value; "strides must be >= F and multiples of 8, bases 16-B aligned"
+  kRows8,    // fp8 table: F with its value; the table's stride a multiple of 16 bytes, the bf16 rows' of 8 elements
 };
 
 struct GatherFormat {
   const char *who_listed;    // the name the listed entry point's own checks report under; null = the format has no mode 2
   int planes;                // planes per output row, out_stride / planes columns each
-  int per_chunk;             // elements per 16-B chunk of a table row: 4 (fp32) or 8 (fp16); strides are multiples of it
+  int per_chunk;             // elements per lane and chunk of a table row: 4 (fp32, 16 B), 8 (fp16, 16 B; fp8, 8 B); strides are multiples of it
   int max_f;
   int rows_per_chunk;        // rows a block takes per walk step of the fused kernel: ROW::kRows * waves per block
   NchBuckets fused, rows;    // the instantiations of k_sample_gather / of the format's unfused kernel
@@ -46,11 +51,14 @@ struct GatherFormat {
 };
 
 constexpr int kRowsF32 = CDML_GATHER_ROWS_PER_WAVE * kGatherWavesPerBlock, kRowsF16 = CDML_GATHER_ROWS_PER_WAVE_F16 * kGatherWavesPerBlock;
+constexpr int kRowsF8 = CDML_GATHER_ROWS_PER_WAVE_F8 * kGatherWavesPerBlock;
 // fp32 rows | three bf16 planes | two fp16 planes (no listed form, no unfused kernel) | fp16 table -> bf16 rows
 inline constexpr GatherFormat kGatherF32 = {"sample_gather_listed", 1, 4, 2048, kRowsF32, {3, {2, 6, 8}}, {4, {2, 4, 6, 8}}, false, LayoutWording::kRows32};
 inline constexpr GatherFormat kGatherX3 = {"sample_gather_listed_x3", 3, 4, 2048, kRowsF32, {2, {6, 8}}, {4, {2, 4, 6, 8}}, true, LayoutWording::kPlanes};
 inline constexpr GatherFormat kGatherH2 = {nullptr, 2, 4, 2048, kRowsF32, {2, {6, 8}}, {0, {}}, false, LayoutWording::kPlanes};
 inline constexpr GatherFormat kGatherF16 = {"sample_gather_listed_f16", 1, 8, 4096, kRowsF16, {3, {1, 3, 8}}, {3, {1, 3, 8}}, false, LayoutWording::kRows16};
+// fp8 (e4m3) table -> bf16 rows (include/cdml_f8.h): the fp16 format's lane -> column mapping and buckets, 8-B chunks
+inline constexpr GatherFormat kGatherF8 = {"sample_gather_listed_f8", 1, 8, 4096, kRowsF8, {3, {1, 3, 8}}, {3, {1, 3, 8}}, false, LayoutWording::kRows8};
 
 // the listed draw's own arguments (cdml_hardneg.h); kind_out null = not wanted
 struct ListedArgs {
@@ -140,15 +148,20 @@ inline int check_gather_layout(const char *who, const GatherFormat &f, bool fuse
                                const void *x_out, int64_t out_stride) {
   const bool f_ok = F > 0 && F <= f.max_f;
   if (f.wording == LayoutWording::kRows16) CDML_REQUIRE(f_ok, CDML_E_UNSUPPORTED, "%s: feature size outside (0, %d]", who, f.max_f);
+  else if (f.wording == LayoutWording::kRows8) CDML_REQUIRE(f_ok, CDML_E_UNSUPPORTED, "%s: F = %d outside (0, %d] of the fp8 gather", who, F, f.max_f);
   else CDML_REQUIRE(f_ok, CDML_E_UNSUPPORTED, "%s: feature size %d outside (0, %d]", who, F, f.max_f);
   const int64_t m = f.per_chunk - 1, plane = out_stride / f.planes;
-  const bool strides = row_stride >= F && (row_stride & m) == 0 && out_stride % f.planes == 0 && plane >= F && (plane & m) == 0;
+  const int64_t mt = f.wording == LayoutWording::kRows8 ? 15 : m;       // (the fp8 table's rows: whole 16-B units)
+  const bool strides = row_stride >= F && (row_stride & mt) == 0 && out_stride % f.planes == 0 && plane >= F && (plane & m) == 0;
   const bool bases = aligned_to(table, 16) && aligned_to(x_out, f.planes > 1 ? 8 : 16);
   if (f.wording == LayoutWording::kPlanes) {
     CDML_REQUIRE(strides && bases, CDML_E_ALIGN, "%s: out_stride must be %d planes of >= F columns (multiples of 4)%s", who, f.planes,
                  fused ? "" : ", 16-B aligned rows");
   } else if (f.wording == LayoutWording::kRows16) {
     CDML_REQUIRE(strides && bases, CDML_E_ALIGN, "%s: strides must be >= F and multiples of 8, bases 16-B aligned", who);
+  } else if (f.wording == LayoutWording::kRows8) {
+    CDML_REQUIRE(strides && bases, CDML_E_ALIGN,
+                 "%s: row_stride must be >= F and a multiple of 16, out_stride >= F and a multiple of 8, bases 16-B aligned", who);
   } else {
     CDML_REQUIRE(strides, CDML_E_ALIGN, "%s: strides must be >= F and multiples of 4", who);
     CDML_REQUIRE(bases, CDML_E_ALIGN, "%s: bases must be 16-B aligned", who);

@@ -14,6 +14,7 @@
 #include "gather_plan.h"
 #include "../../include/cdml_hardneg.h"
 #include "../../include/cdml_negweights.h"
+#include "../../include/cdml_f8.h"
 
 namespace cdml {
 namespace {
@@ -623,6 +624,77 @@ struct RowF16 {
   }
 };
 
+// RowF8: fp8 (OCP e4m3) table -> bf16 rows (include/cdml_f8.h).  A lane keeps the EIGHT codes of its chunk (one 8-B load: 512
+// contiguous bytes per wave instruction) -- the columns 8 (l + 64 c) .. + 7 a lane of RowF16 holds -- converts them exactly
+// to fp16 (every e4m3 value is an fp16 value: v_cvt_pk_f32_fp8, then f32 -> f16 of a value with 3 mantissa bits and an
+// exponent in [-9, 8]; a NaN code stays NaN) and hands the row to RowF16::finish: the same instructions in the same order,
+// so the output is bit for bit that of the fp16 gather of the same values.  (A 16-B load per lane would change which
+// columns a lane sums, hence the rounding of the sum of squares.)  The per-row scale cancels in the normalisation.
+using u32x2c = __attribute__((ext_vector_type(2))) uint32_t;
+using f32x2c = __attribute__((ext_vector_type(2))) float;
+__device__ __forceinline__ half8 f8x8_to_half8(u32x2c w) {
+  half8 h;
+#pragma unroll
+  for (int k = 0; k < 2; ++k) {
+    const f32x2c lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[k], false);   // bytes 0, 1
+    const f32x2c hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[k], true);    // bytes 2, 3
+    h[4 * k + 0] = (_Float16)lo[0], h[4 * k + 1] = (_Float16)lo[1];
+    h[4 * k + 2] = (_Float16)hi[0], h[4 * k + 3] = (_Float16)hi[1];
+  }
+  return h;
+}
+
+template <int NCH>
+struct RowF8 {
+  using In = uint8_t;
+  using Out = __bf16;
+  struct Regs { u32x2c v[NCH]; };
+  static constexpr int kPerChunk = 8;
+  static constexpr int kRows = CDML_GATHER_ROWS_PER_WAVE_F8;   // 1.5-KB rows, two registers per chunk while in flight
+  __device__ static __forceinline__ void issue(Regs &R, const In *table, int64_t lr, int64_t stride, int F, int lane) {
+    const u32x2c *src = reinterpret_cast<const u32x2c *>(table + lr * stride);
+    const int nq = (F + 7) >> 3;
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+      const int q = lane + kWave * c;
+      u32x2c x = {0u, 0u};
+      if (q < nq) {
+#if CDML_GATHER_NT
+        x = __builtin_nontemporal_load(src + q);
+#else
+        x = src[q];
+#endif
+      }
+      R.v[c] = x;
+    }
+  }
+  __device__ static __forceinline__ void finish(Regs &R, int F, Out *dst, int64_t out_stride, int lane) {
+    typename RowF16<NCH>::Regs H;
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) H.v[c] = f8x8_to_half8(R.v[c]);
+    RowF16<NCH>::finish(H, F, dst, out_stride, lane);
+  }
+};
+
+// The unfused twin of k_gather_rows_f16 on the fp8 table: one wave per row, RowF8's load and arithmetic.  idx -1: a
+// padding slot, left untouched.
+template <int NCH>
+__global__ void __launch_bounds__(kThreads)
+k_gather_rows_f8(const uint8_t *__restrict__ table, int64_t row0, int64_t n_rows, int64_t row_stride,
+                 const int32_t *__restrict__ idx, int n_idx, int F, __bf16 *__restrict__ x_out, int64_t out_stride,
+                 int32_t *__restrict__ oob_flag) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  for (int r = blockIdx.x * kWavesPerBlock + wave; r < n_idx; r += gridDim.x * kWavesPerBlock) {
+    const int32_t id = idx[r];
+    if (id == -1) continue;
+    const int64_t lr = clamp_row(id, row0, n_rows, oob_flag);
+    typename RowF8<NCH>::Regs R;
+    RowF8<NCH>::issue(R, table, lr, row_stride, F, lane);
+    RowF8<NCH>::finish(R, F, x_out + (int64_t)r * out_stride, out_stride, lane);
+  }
+}
+
 // KI (RowF32X3 only; round 5): the chunk's 8 rows = ONE row group of the k8-interleaved copy x_ki -- per step
 // [3 planes][rows_per_step / 8][plane columns][8 rows] bf16, what the weight gradient's k-strided product reads with one
 // 16-B LDS read per fragment (gemm_bf16_256.hip, KI).  After the row-major planes are stored the block walks the plane in
@@ -1158,6 +1230,59 @@ extern "C" int cdml_sample_gather_weighted_f16(const int32_t *pairs, int64_t n_p
                               idx_out, nullptr, x_out_bf16, out_stride, n_steps, x_step_stride, idx_step_stride, oob_flag,
                               nullptr, 0, false, nullptr, &w};
   return sample_gather<kGatherF16, RowF16>("sample_gather_f16", a, stream);
+}
+
+// ---- the fp8 catalogue (include/cdml_f8.h): e4m3 codes -> bf16 rows, the _f16 entry points' twins ----
+extern "C" int cdml_gather_rows_f8(const uint8_t *table, int64_t row0, int64_t n_rows, int64_t row_stride, const int32_t *idx,
+                                   int n_idx, int F, uint16_t *x_out_bf16, int64_t out_stride, int32_t *oob_flag,
+                                   cdml_stream_t stream) {
+  const GatherRowsArgs a = {table, row0, n_rows, row_stride, idx, n_idx, F, x_out_bf16, out_stride};
+  GatherPlan p;
+  if (int rc = plan_gather_rows("gather_rows_f8", kGatherF8, a, p)) return rc;
+  const int rc = with_nch<kGatherF8, false>("gather_rows_f8", p.nch, [&](auto nch) {
+    hipLaunchKernelGGL(k_gather_rows_f8<decltype(nch)::value>, dim3(p.grid), dim3(kThreads), 0, (hipStream_t)stream, table, row0,
+                       n_rows, row_stride, idx, n_idx, F, reinterpret_cast<__bf16 *>(x_out_bf16), out_stride, oob_flag);
+  });
+  return rc ? rc : check_launch("gather_rows_f8");
+}
+
+extern "C" int cdml_sample_gather_f8(int mode, const int32_t *pairs, int64_t n_pairs, uint64_t seed, uint64_t step,
+                                     const uint64_t *step_dev, int batch, int64_t slot0, int64_t batch_global,
+                                     const uint8_t *table, int64_t n_rows, int64_t row_stride, int F, int32_t *idx_out,
+                                     int32_t *shift_out, uint16_t *x_out_bf16, int64_t out_stride, int n_steps,
+                                     int64_t x_step_stride, int64_t idx_step_stride, int32_t *oob_flag, cdml_stream_t stream) {
+  const SampleGatherArgs a = {mode, pairs, n_pairs, seed, step, step_dev, batch, slot0, batch_global, table, n_rows, row_stride, F,
+                              idx_out, shift_out, x_out_bf16, out_stride, n_steps, x_step_stride, idx_step_stride, oob_flag,
+                              nullptr, 0, false, nullptr};
+  return sample_gather<kGatherF8, RowF8>("sample_gather_f8", a, stream);
+}
+
+extern "C" int cdml_sample_gather_listed_f8(const int32_t *pairs, int64_t n_pairs, uint64_t seed, uint64_t step,
+                                            const uint64_t *step_dev, int batch, int64_t slot0, int64_t batch_global,
+                                            const uint8_t *table, int64_t n_rows, int64_t row_stride, int F,
+                                            const int32_t *lists, int64_t ldl, int L, uint64_t hard_thresh,
+                                            int32_t *idx_out, int32_t *kind_out, uint16_t *x_out_bf16, int64_t out_stride,
+                                            int n_steps, int64_t x_step_stride, int64_t idx_step_stride,
+                                            int64_t kind_step_stride, int32_t *oob_flag, cdml_stream_t stream) {
+  const ListedArgs l = {lists, ldl, L, hard_thresh, kind_out, kind_step_stride};
+  const SampleGatherArgs a = {2, pairs, n_pairs, seed, step, step_dev, batch, slot0, batch_global, table, n_rows, row_stride, F,
+                              idx_out, nullptr, x_out_bf16, out_stride, n_steps, x_step_stride, idx_step_stride, oob_flag,
+                              nullptr, 0, false, &l};
+  return sample_gather<kGatherF8, RowF8>("sample_gather_f8", a, stream);
+}
+
+extern "C" int cdml_sample_gather_weighted_f8(const int32_t *pairs, int64_t n_pairs, uint64_t seed, uint64_t step,
+                                              const uint64_t *step_dev, int batch, int64_t slot0, int64_t batch_global,
+                                              const uint8_t *table, int64_t n_rows, int64_t row_stride, int F,
+                                              const int32_t *start, int64_t n_live, const int32_t *coarse, int bits,
+                                              int32_t *idx_out, int32_t *kind_out, uint16_t *x_out_bf16, int64_t out_stride,
+                                              int n_steps, int64_t x_step_stride, int64_t idx_step_stride,
+                                              int64_t kind_step_stride, int32_t *oob_flag, cdml_stream_t stream) {
+  const WeightedArgs w = {"sample_gather_weighted_f8", start, coarse, n_live, bits, kind_out, kind_step_stride};
+  const SampleGatherArgs a = {3, pairs, n_pairs, seed, step, step_dev, batch, slot0, batch_global, table, n_rows, row_stride, F,
+                              idx_out, nullptr, x_out_bf16, out_stride, n_steps, x_step_stride, idx_step_stride, oob_flag,
+                              nullptr, 0, false, nullptr, &w};
+  return sample_gather<kGatherF8, RowF8>("sample_gather_f8", a, stream);
 }
 
 extern "C" int cdml_route_rows(const int32_t *ids, int n, int64_t rows_per_shard, int world, int capacity,

@@ -140,6 +140,7 @@ class EngineWorkspace:
     WIDTHS = 1                      # ... and the layout's padded widths of this (beyond TowerLayout's own)
     MAX_ROWS = None                 # the most rows one forward pass takes (None: no limit below the 2 GiB operand range)
     TABLE_DTYPE = torch.float32     # the catalogue this precision gathers from
+    TABLE_DTYPES = None             # every catalogue dtype it accepts (None: TABLE_DTYPE alone)
     INFERENCE = "f32"               # the precision catalogue inference runs on for a step of this one
     EXCHANGE_PLANES = False         # the row exchange of a sharded catalogue writes x_hat in the gather's plane form
     # state that the kernel sequences and the callers read whatever the engine
@@ -280,6 +281,7 @@ class Engine:
     def __init__(self, name, module, layout, Workspace, **ws_args):
         self.name, self.layout, self.Workspace, self.ws_args = name, layout, Workspace, ws_args
         self.rows, self.table_dtype = self.Workspace.ROWS, self.Workspace.TABLE_DTYPE
+        self.table_dtypes = tuple(self.Workspace.TABLE_DTYPES or (self.table_dtype,))      # (bf16: fp16 or fp8 codes)
         self.refresh_weights, self.tower_forward, self.tower_backward = (
             module.refresh_weights, module.tower_forward, module.tower_backward)
 
@@ -302,6 +304,6 @@ def get_engine(precision):
 
 
 def auto_precision(table_dtype, rows, tile=128):
-    """precision "auto": "bf16" for an fp16 catalogue (config 4), else "f32x3" (what bench.py times) when ``rows`` -- the step's
-    rows, or an N-pair batch against its loss chain's ``tile`` -- is a multiple of ``tile``, else "f32" (the fp32 MFMA)."""
-    return "bf16" if table_dtype == torch.float16 else "f32x3" if rows % tile == 0 else "f32"
+    """precision "auto": "bf16" for an fp16 or fp8 catalogue (config 4), else "f32x3" (what bench.py times) when ``rows`` --
+    the step's rows, or an N-pair batch against its loss chain's ``tile`` -- is a multiple of ``tile``, else "f32" (the fp32 MFMA)."""
+    return "bf16" if table_dtype in (torch.float16, torch.float8_e4m3fn) else "f32x3" if rows % tile == 0 else "f32"

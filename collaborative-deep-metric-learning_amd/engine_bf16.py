@@ -15,13 +15,110 @@ import numpy as np
 import torch
 
 from . import ops
-from .engine import EngineWorkspace, FeatureTable, TowerLayout, dw1_in_blocks
+from .engine import EngineWorkspace, FeatureTable, TowerLayout, dw1_in_blocks, round_up
 
 
 class FeatureTableF16(FeatureTable):
     """fp16 catalogue shard [n_rows, row_stride] (3 KB rows at F=1500)."""
     DTYPE, NP_DTYPE, KIND = torch.float16, np.float16, "fp16"
     _fill = staticmethod(ops.fill_uniform_table_f16)
+
+
+def quantize_f8_host(features):
+    """(codes uint8 [n, F], scale fp32 [n]) of a float [n, F] array by the rule of include/cdml_f8.h, on the host: per row
+    scale = 2^(max(floor(log2 m), -119) - 7) for the largest finite |x| m (1 for m = 0), code = RNE_e4m3(x / scale) by
+    torch's CPU conversion, an Inf / NaN element -> the NaN code of its sign.  Exact exponent arithmetic (frexp / ldexp)."""
+    x = torch.from_numpy(np.ascontiguousarray(np.asarray(features, dtype=np.float32)))
+    finite = torch.isfinite(x)
+    m = torch.where(finite, x.abs(), torch.zeros_like(x)).amax(dim=1) if x.shape[1] else x.new_zeros(x.shape[0])
+    e = torch.frexp(m).exponent                                  # m = f 2^e, f in [0.5, 1): floor(log2 m) = e - 1
+    k = torch.where(m > 0, (e - 1).clamp(min=-119) - 7, torch.zeros_like(e))
+    one = torch.ones_like(m)
+    scale = torch.ldexp(one, k)
+    y = x * torch.ldexp(one, -k)[:, None]                        # exact: a power of two, |y| < 256
+    codes = torch.where(finite, y, torch.zeros_like(y)).to(torch.float8_e4m3fn).view(torch.uint8)
+    nan_code = (0x7F | ((x.view(torch.int32) >> 24) & 0x80)).to(torch.uint8)
+    return torch.where(finite, codes, nan_code).numpy(), scale.numpy()
+
+
+class FeatureTableF8(FeatureTable):
+    """fp8 catalogue shard (include/cdml_f8.h): OCP e4m3 codes [n_rows, row_stride] (1.5 KB rows at F=1500, rows on 128-B
+    lines, pad columns code 0) and ``scale`` fp32 [n_rows], one power of two per row, value = code x scale.  Precision "bf16"
+    gathers the codes (the scale cancels in the input l2-normalisation); read-only."""
+    DTYPE, NP_DTYPE, KIND = torch.float8_e4m3fn, np.float32, "fp8"
+
+    def __init__(self, data, feature_size, row0=0, n_rows_global=None, scale=None):
+        super().__init__(data, feature_size, row0, n_rows_global)
+        if scale is None:
+            scale = torch.ones(self.n_rows, dtype=torch.float32, device=data.device)
+        if scale.dtype != torch.float32 or scale.shape != (self.n_rows,) or scale.device != data.device:
+            raise ValueError("FeatureTableF8 needs one fp32 scale per row on the codes' device")
+        self.scale = scale
+
+    @staticmethod
+    def padded_stride(feature_size):
+        return round_up(feature_size, 128)
+
+    @classmethod
+    def from_numpy(cls, features, device, row0=0, n_rows_global=None):
+        """features.npy contents (float [N,F]) quantised on the host, codes and scales -> HBM."""
+        codes, scale = quantize_f8_host(features)
+        n, F = codes.shape
+        data = torch.zeros((n, cls.padded_stride(F)), dtype=torch.uint8, device=device)
+        data[:, :F] = torch.from_numpy(codes).to(device)
+        return cls(data.view(cls.DTYPE), F, row0, n_rows_global, torch.from_numpy(scale).to(device))
+
+    @classmethod
+    def _empty(cls, n_rows, feature_size, device):
+        return (torch.empty((n_rows, cls.padded_stride(feature_size)), dtype=cls.DTYPE, device=device),
+                torch.empty(n_rows, dtype=torch.float32, device=device))
+
+    @classmethod
+    def from_table(cls, table, chunk_rows=65536):
+        """A device FeatureTable (fp32) or FeatureTableF16 quantised by the HIP quantiser, ``chunk_rows`` rows per launch."""
+        F = table.feature_size
+        data, scale = cls._empty(table.n_rows, F, table.data.device)
+        for lo in range(0, table.n_rows, int(chunk_rows)):
+            hi = min(lo + int(chunk_rows), table.n_rows)
+            ops.quantize_rows_f8(table.data[lo:hi], F, data[lo:hi], scale[lo:hi])
+        return cls(data, F, table.row0, table.n_rows_global, scale)
+
+    @classmethod
+    def synthetic(cls, n_rows, feature_size, seed, device, row0=0, n_rows_global=None, chunk_rows=65536):
+        """The U[0,1) table of FeatureTableF16.synthetic, quantised: fp16 chunks from the fill kernel (its ``row0``) go
+        through the quantiser one after the other, so the content is from_table(FeatureTableF16.synthetic(...))'s and no
+        whole fp16 table ever exists."""
+        data, scale = cls._empty(n_rows, feature_size, device)
+        chunk = min(int(chunk_rows), n_rows)
+        tmp = torch.empty((chunk, FeatureTableF16.padded_stride(feature_size)), dtype=torch.float16, device=device)
+        for lo in range(0, n_rows, chunk):
+            hi = min(lo + chunk, n_rows)
+            ops.fill_uniform_table_f16(tmp[:hi - lo], row0 + lo, feature_size, seed)
+            ops.quantize_rows_f8(tmp[:hi - lo], feature_size, data[lo:hi], scale[lo:hi])
+        return cls(data, feature_size, row0, n_rows_global, scale)
+
+    def codes(self, idx=None):
+        """The codes as uint8 [n, F] (of the given LOCAL rows)."""
+        u = self.data.view(torch.uint8)
+        return (u if idx is None else u[idx])[:, :self.feature_size]
+
+    def rows(self, idx):
+        return self.dequantize(idx)
+
+    def dequantize(self, idx=None):
+        """fp32 rows code x scale, unpadded (of the given LOCAL rows)."""
+        c = self.codes(idx).contiguous().view(self.DTYPE).to(torch.float32)
+        return c * (self.scale if idx is None else self.scale[idx])[:, None]
+
+    def as_f16(self, chunk_rows=65536):
+        """The FeatureTableF16 holding the codes' values (every e4m3 value is an fp16 value: exact) -- what the fp8 gather is
+        bit-identical to the fp16 gather of."""
+        F = self.feature_size
+        data = torch.zeros((self.n_rows, FeatureTableF16.padded_stride(F)), dtype=torch.float16, device=self.data.device)
+        for lo in range(0, self.n_rows, int(chunk_rows)):
+            hi = min(lo + int(chunk_rows), self.n_rows)
+            data[lo:hi, :F] = self.data[lo:hi, :F].to(torch.float16)
+        return FeatureTableF16(data, F, self.row0, self.n_rows_global)
 
 
 def layout_bf16(feature_size, hidden=5000, output_size=256):
@@ -31,6 +128,7 @@ def layout_bf16(feature_size, hidden=5000, output_size=256):
 
 class TowerWorkspaceBF16(EngineWorkspace):
     ROWS, TABLE_DTYPE, INFERENCE = 64, torch.float16, "bf16"
+    TABLE_DTYPES = (torch.float16, torch.float8_e4m3fn)       # FeatureTableF16, or the codes of a FeatureTableF8
 
     def __init__(self, layout, n_rows, device, backward=True, **plane_options):
         L, R = layout, int(n_rows)

@@ -90,10 +90,13 @@ def gather_rows_x3(src, idx, feature_size, x_out_planes, nan_missing=False, oob_
 
 
 def _gather_format(table, x_out):
-    """The suffix of the row format's entry points, from the types: fp16 table -> bf16 rows ("_f16", config 4); fp32 table ->
-    fp32 rows (""), rows as three bf16 planes ("_x3", precision f32x3) or as two fp16 planes of x_hat * 2^14 ("_h2", f16x2)."""
+    """The suffix of the row format's entry points, from the types: fp16 table -> bf16 rows ("_f16", config 4), fp8 (e4m3)
+    table -> bf16 rows ("_f8", include/cdml_f8.h); fp32 table -> fp32 rows (""), rows as three bf16 planes ("_x3", precision
+    f32x3) or as two fp16 planes of x_hat * 2^14 ("_h2", f16x2)."""
     if table.dtype == torch.float16:
         return "_f16"
+    if table.dtype == torch.float8_e4m3fn:
+        return "_f8"
     return {torch.bfloat16: "_x3", torch.float16: "_h2"}.get(x_out.dtype, "")
 
 
@@ -102,7 +105,7 @@ def _gather_io(fmt, table, x_out, idx_out, n_steps, x_ki, x_ki_errors, kind_out=
     leading dimension, the per-step strides of x_out / idx_out / kind_out / x_ki, the listed draw's arguments or None).
     x_ki_errors: the caller's words for (x_ki with a format that has none, x_ki that is no contiguous bf16 buffer);
     lists: (lists, hard_fraction) of a listed launch, checked where that launch has always checked them."""
-    tp, tld = (_mat16 if fmt == "_f16" else _mat)(table)
+    tp, tld = {"_f16": _mat16, "_f8": _mat8}.get(fmt, _mat)(table)
     listed = None if lists is None else _lists_args(lists[0], table.shape[0], lists[1])
     omat = _mat16 if fmt else _mat
     if n_steps > 1:
@@ -1744,6 +1747,13 @@ def _mat16(t):
     return _p(t), t.stride(0)
 
 
+def _mat8(t):
+    """(pointer, leading dimension) of the codes of an fp8 catalogue (torch.float8_e4m3fn)."""
+    if t.dim() != 2 or t.stride(1) != 1 or t.dtype != torch.float8_e4m3fn:
+        raise ValueError("expected a 2-D float8_e4m3fn tensor with unit inner stride")
+    return _p(t), t.stride(0)
+
+
 def gemm_bf16_workspace(M, N, K):
     return int(load_library().cdml_gemm_bf16_workspace(M, N, K))
 
@@ -1973,6 +1983,29 @@ def gather_rows_f16(table, row0, idx, feature_size, x_out, oob_flag=None):
          _p(idx, torch.int32), idx.numel(), feature_size, _p(x_out, torch.bfloat16), x_out.stride(0),
          _p(oob_flag, torch.int32), _stream())
     return x_out
+
+
+# ---- the fp8 catalogue (include/cdml_f8.h): e4m3 codes -> l2-normalised bf16 rows, and the quantiser ----
+def gather_rows_f8(table, row0, idx, feature_size, x_out, oob_flag=None):
+    """gather_rows_f16 on the codes of an fp8 table: bit for bit its output on the fp16 table of the same values."""
+    tp, tld = _mat8(table)
+    call("cdml_gather_rows_f8", tp, row0, table.shape[0], tld, _p(idx, torch.int32), idx.numel(), feature_size,
+         _p(x_out, torch.bfloat16), x_out.stride(0), _p(oob_flag, torch.int32), _stream())
+    return x_out
+
+
+def quantize_rows_f8(src, feature_size, codes, scale):
+    """codes[r, :] (float8_e4m3fn, every column of the view written: the ones at or past feature_size as code 0) and scale[r]
+    (fp32, a power of two) of the rows src[r, :feature_size] -- src fp32 or fp16 [n, stride]; codes may be a slice of a larger
+    table, its stride is independent of src's."""
+    if src.dim() != 2 or src.stride(1) != 1 or src.dtype not in (torch.float32, torch.float16):
+        raise ValueError("quantize_rows_f8 needs a 2-D fp32 or fp16 source with unit inner stride")
+    cp, cld = _mat8(codes)
+    if codes.shape[0] != src.shape[0] or scale.numel() != src.shape[0] or not scale.is_contiguous():
+        raise ValueError("quantize_rows_f8 needs one row of codes and one contiguous fp32 scale per source row")
+    call("cdml_quantize_rows_f8_" + ("f32" if src.dtype == torch.float32 else "f16"), _p(src), src.shape[0], src.stride(0),
+         feature_size, cp, cld, codes.shape[1], _p(scale, torch.float32), _stream())
+    return codes, scale
 
 
 # ------------------------------------------------------------- optimizers -----

@@ -17,7 +17,7 @@ from . import engine, ops
 class Prediction():
     def __init__(self, params=None, ckpt=None, device="cuda:0", precision="f32", fc2_single_pass=False):
         """``precision``: "f32" (the reference's arithmetic), "f32x3" / "f16x2" (plane kernels) or "bf16" -- BASELINE config 4's
-        precision for catalogue inference: an fp16 ``FeatureTableF16`` in, bf16 MFMA projection,
+        precision for catalogue inference: an fp16 ``FeatureTableF16`` (or an fp8 ``FeatureTableF8``) in, bf16 MFMA projection,
         fp32 accumulation and output normalisation (build-defined; tolerance 5e-3 on the unit-norm
         embeddings, tests/test_gpu_bf16.py).  ``fc2_single_pass`` (precision "f32x3"): see
         engine_x3.TowerWorkspaceX3 -- off, an embedding's bits do not depend on the chunk size."""
@@ -83,7 +83,7 @@ class Prediction():
         L, N, E = self.params.layout, table.n_rows, self.engine
         if out is None:
             out = torch.empty((N, L.D), dtype=torch.float32, device=self.device)
-        if E.table_dtype == torch.float16 and table.data.dtype != torch.float16:
+        if E.table_dtype == torch.float16 and table.data.dtype not in E.table_dtypes:
             raise ValueError("precision 'bf16' reads an fp16 FeatureTableF16")
         if E.Workspace.MAX_ROWS:
             # h1 as three planes is 30 KB per row: the GEMMs' 2 GiB buffer descriptors take 65 536 rows at a time
@@ -94,7 +94,8 @@ class Prediction():
             for lo in range(0, N, batch_size):
                 n = min(batch_size, N - lo)
                 torch.add(self._ids[:n], lo, out=self._idx[:n])
-                ops.gather_rows_f16(table.data, 0, self._idx[:n], table.feature_size, ws.x_hat)   # rows lo..lo+n, l2-normalised
+                gather = ops.gather_rows_f8 if table.data.dtype == torch.float8_e4m3fn else ops.gather_rows_f16
+                gather(table.data, 0, self._idx[:n], table.feature_size, ws.x_hat)   # rows lo..lo+n, l2-normalised
                 E.tower_forward(self.params, ws)
                 out[lo:lo + n] = ws.e[:n, :L.D]
             return out

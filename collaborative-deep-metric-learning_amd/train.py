@@ -158,6 +158,13 @@ def validate_args(table, batch_size, mode="uniform", optimizer="adam", exchange=
                              % (int(batch_size), tile, precision, memory_size))
     if optimizer not in ("adam", "lars", "momentum"):
         raise ValueError("optimizer must be 'adam', 'lars' or 'momentum'")
+    if table.data.dtype == torch.float8_e4m3fn:
+        if train_table:
+            raise ValueError("train_table=True: an fp8 catalogue is read-only (train an fp32 FeatureTable and quantise it)")
+        for name, on in (("exchange", exchange is not None), ("grad_sync", grad_sync is not None)):
+            if on:
+                raise ValueError("%s does not go with an fp8 catalogue yet: the sharded row exchange of fp8 shards is not "
+                                 "built, a FeatureTableF8 trains on one GPU" % name)
     return SimpleNamespace(precision=precision, temperature=temperature, memory_size=memory_size, memory_start=memory_start,
                            logq=logq, logq_stream=logq_stream, logq_alpha=logq_alpha, logq_init_gap=logq_init_gap,
                            uniform_negatives=uniform_negatives, uniform_logq=uniform_logq, negative_lists=negative_lists,
@@ -169,7 +176,7 @@ def resolve_precision(table, rows, precision, use_graph=False, exchange=None, gr
     times), or the refusal of one that does not go with the table's dtype or the way the step is to replay."""
     if precision in ("auto", None):
         precision = engine.auto_precision(table.data.dtype, rows)
-    if engine.get_engine(precision).table_dtype != table.data.dtype:
+    if table.data.dtype not in engine.get_engine(precision).table_dtypes:      # ('bf16' also takes the fp8 FeatureTableF8)
         raise ValueError("precision 'bf16' goes with an fp16 FeatureTableF16, 'f32' / 'f32x3' with an fp32 table")
     if precision == "f16x2" and use_graph and (use_graph == "split" or exchange is not None or grad_sync is not None):
         raise ValueError("precision 'f16x2' replays from a hipGraph on one GPU only (its plane scales are kernel arguments "
@@ -195,7 +202,8 @@ class TrainStep:
         ``grad_sync``: the multi-GPU hooks of cdml_amd.dist (None on one GPU).
         ``train_table``: also train the catalogue rows (lazy Adam, states stored beside the
         shard; build-defined -- the reference keeps the features frozen, train.py:265).
-        ``precision``: "auto" (default) = "bf16" for an fp16 catalogue (BASELINE config 4), else "f32x3" -- fp32 operands as
+        ``precision``: "auto" (default) = "bf16" for an fp16 catalogue (BASELINE config 4) or an fp8 one (engine_bf16.FeatureTableF8:
+        e4m3 codes, half the bytes; the step is bit for bit the one on ``as_f16()``; read-only, one GPU), else "f32x3" -- fp32 operands as
         three exact bf16 planes, six plane products per fp32 product on the bf16 MFMA, held to the fp32 path's bounds; what
         bench.py times -- when the step's rows are a multiple of 128, else "f32" (the fp32 MFMA).  "f16x2" (never chosen by
         "auto"): fp32 operands as TWO fp16 planes under per-tensor power-of-two scales, three plane products on the fp16 MFMA
