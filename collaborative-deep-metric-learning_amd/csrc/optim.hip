@@ -7,6 +7,7 @@
 // LARS 5 (+2 for the norm pass).  16-B lane accesses, grid-stride.
 #include "common.h"
 #include <string.h>
+#include <type_traits>
 
 namespace cdml {
 
@@ -54,19 +55,33 @@ __device__ __forceinline__ void momentum1(float &w, const float g, float &a, con
   w = w - (nesterov ? __fmaf_rn(g, lr, a * momentum * lr) : a * lr);
 }
 
-__global__ void __launch_bounds__(kThreads)
-k_adam(float *__restrict__ w, const float *__restrict__ g, float *__restrict__ m,
-       float *__restrict__ v, int64_t n, float lr_imm, const float *__restrict__ lr_dev, float b1,
-       float b2, float eps, int64_t t_imm, uint64_t *__restrict__ t_dev, int advance,
-       uint32_t *__restrict__ tickets) {
-  __shared__ float s_lr_t;
+// Adam's bias-corrected rate lr_t = lr sqrt(1 - b2^t) / (1 - b1^t), t = t_imm + *t_dev: thread 0 in double, handed to the
+// block through the caller's LDS word.
+__device__ __forceinline__ float adam_lr_t(float &s_lr_t, const float lr_imm, const float *lr_dev, const float b1,
+                                           const float b2, const int64_t t_imm, const uint64_t *t_dev) {
   if (threadIdx.x == 0) {
     const double t = (double)t_imm + (t_dev ? (double)(*t_dev) : 0.0);
     const double lr = lr_dev ? (double)(*lr_dev) : (double)lr_imm;
     s_lr_t = (float)(lr * sqrt(1.0 - pow((double)b2, t)) / (1.0 - pow((double)b1, t)));
   }
   __syncthreads();
-  const float lr_t = s_lr_t;
+  return s_lr_t;
+}
+
+// A layer's bias vector riding along with its matrix' launch: element i of the first ceil(bn / 256) blocks.
+// (The kernels' lambdas capture by value: behind a by-reference capture the compiler read lr_imm where lr_dev is set.)
+template <class F>
+__device__ __forceinline__ void bias_ride(const int bn, F &&update1) {
+  for (int i = blockIdx.x * kThreads + threadIdx.x; i < bn; i += gridDim.x * kThreads) update1(i);
+}
+
+__global__ void __launch_bounds__(kThreads)
+k_adam(float *__restrict__ w, const float *__restrict__ g, float *__restrict__ m,
+       float *__restrict__ v, int64_t n, float lr_imm, const float *__restrict__ lr_dev, float b1,
+       float b2, float eps, int64_t t_imm, uint64_t *__restrict__ t_dev, int advance,
+       uint32_t *__restrict__ tickets) {
+  __shared__ float s_lr_t;
+  const float lr_t = adam_lr_t(s_lr_t, lr_imm, lr_dev, b1, b2, t_imm, t_dev);
   const float omb1 = 1.0f - b1, omb2 = 1.0f - b2;
   const int64_t n4 = n >> 2;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
@@ -111,55 +126,19 @@ constexpr int kAT = 64;
 template <int PLANES>
 __device__ __forceinline__ void tile_copies(float (&res)[2][2][4], uint32_t (&sT)[64][64 / 2 + 1], __bf16 *__restrict__ wt,
                                             int64_t ldt, __bf16 *__restrict__ wc, int64_t ldc, int64_t plane_t,
-                                            int64_t plane_c, int k0, int n0, float h2_scale = 0.f) {
-  using bf16x4 = __attribute__((ext_vector_type(4))) __bf16;
+                                            int64_t plane_c, int k0, int n0, float h2_scale) {
+  using word = std::conditional_t<PLANES == 2, _Float16, __bf16>;      // the copies' 16-bit type
+  using word4 = __attribute__((ext_vector_type(4))) word;
+  using word2 = __attribute__((ext_vector_type(2))) word;
   const int tr = threadIdx.x >> 4, c4 = (threadIdx.x & 15) * 4;
   if constexpr (PLANES == 2) {
-    // precision "f16x2": the copies are the two fp16 planes hi | lo of the new weights times h2_scale (saturating); the
-    // same tile walk, the 16-bit words being fp16
-    using half4v = __attribute__((ext_vector_type(4))) _Float16;
-    using half2v = __attribute__((ext_vector_type(2))) _Float16;
+    // precision "f16x2": the copies are the two fp16 planes hi | lo of the new weights times h2_scale (saturating)
 #pragma unroll
     for (int p = 0; p < 2; ++p)
 #pragma unroll
       for (int q = 0; q < 2; ++q)
 #pragma unroll
         for (int u = 0; u < 4; ++u) res[p][q][u] = __builtin_amdgcn_fmed3f(res[p][q][u] * h2_scale, -65504.f, 65504.f);
-#pragma unroll
-    for (int pl = 0; pl < 2; ++pl) {
-      if (pl && wt) __syncthreads();
-#pragma unroll
-      for (int p = 0; p < 2; ++p) {
-        const int r = p * 32 + 2 * tr;
-        half4v o[2];
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-#pragma unroll
-          for (int u = 0; u < 4; ++u) {
-            o[q][u] = (_Float16)res[p][q][u];
-            res[p][q][u] -= (float)o[q][u];
-          }
-          if (wc) *reinterpret_cast<half4v *>(wc + (int64_t)(k0 + r + q) * ldc + pl * plane_c + n0 + c4) = o[q];
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const half2v pr = {o[0][u], o[1][u]};
-          sT[c4 + u][r >> 1] = __builtin_bit_cast(uint32_t, pr);
-        }
-      }
-      if (wt) {
-        __syncthreads();
-        const int sr = threadIdx.x >> 3, seg = (threadIdx.x & 7) * 4;
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-          const int row = q * 32 + sr;
-          uint4 o;
-          o.x = sT[row][seg]; o.y = sT[row][seg + 1]; o.z = sT[row][seg + 2]; o.w = sT[row][seg + 3];
-          *reinterpret_cast<uint4 *>(wt + (int64_t)(n0 + row) * ldt + pl * plane_t + k0 + seg * 2) = o;
-        }
-      }
-    }
-    return;
   }
 #pragma unroll
   for (int pl = 0; pl < PLANES; ++pl) {
@@ -167,20 +146,19 @@ __device__ __forceinline__ void tile_copies(float (&res)[2][2][4], uint32_t (&sT
 #pragma unroll
     for (int p = 0; p < 2; ++p) {
       const int r = p * 32 + 2 * tr;
-      bf16x4 o[2];
+      word4 o[2];
 #pragma unroll
       for (int q = 0; q < 2; ++q) {
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
-          o[q][u] = (__bf16)res[p][q][u];
+          o[q][u] = (word)res[p][q][u];
           if (PLANES > 1) res[p][q][u] -= (float)o[q][u];
         }
-        if (wc) *reinterpret_cast<bf16x4 *>(wc + (int64_t)(k0 + r + q) * ldc + pl * plane_c + n0 + c4) = o[q];
+        if (wc) *reinterpret_cast<word4 *>(wc + (int64_t)(k0 + r + q) * ldc + pl * plane_c + n0 + c4) = o[q];
       }
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
-        using bf16x2 = __attribute__((ext_vector_type(2))) __bf16;
-        const bf16x2 pr = {o[0][u], o[1][u]};            // rows r (low half), r + 1 (high half)
+        const word2 pr = {o[0][u], o[1][u]};             // rows r (low half), r + 1 (high half)
         sT[c4 + u][r >> 1] = __builtin_bit_cast(uint32_t, pr);
       }
     }
@@ -199,6 +177,30 @@ __device__ __forceinline__ void tile_copies(float (&res)[2][2][4], uint32_t (&sT
   }
 }
 
+// The block's 64 x 64 tile of a weight matrix W[K][N] (ld = N) updated in place, and its operand copies written from the
+// update's registers.  update4(i) updates the four elements at W + i -- every fp32 stream of the rule, 16-B accesses --
+// and returns the new weights.  A thread takes two adjacent rows of four columns per pass: the transpose goes through LDS as
+// 32-bit words (the two rows' values of one column), 33-word rows -> at most 2-way bank conflicts.
+template <int PLANES, class F>
+__device__ __forceinline__ void tile_update(const int N, uint32_t (&sT)[64][64 / 2 + 1], __bf16 *__restrict__ wt, int64_t ldt,
+                                            __bf16 *__restrict__ wc, int64_t ldc, int64_t plane_t, int64_t plane_c,
+                                            float h2_scale, F &&update4) {
+  const int tiles_n = N / kAT;
+  const int k0 = (blockIdx.x / tiles_n) * kAT, n0 = (blockIdx.x % tiles_n) * kAT;
+  const int tr = threadIdx.x >> 4, c4 = (threadIdx.x & 15) * 4;
+  float res[2][2][4];                                  // the new weights (PLANES > 1: what the planes so far leave)
+#pragma unroll
+  for (int p = 0; p < 2; ++p) {
+    const int r = p * 32 + 2 * tr;
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      const float4 w4 = update4((int64_t)(k0 + r + q) * N + n0 + c4);
+      res[p][q][0] = w4.x; res[p][q][1] = w4.y; res[p][q][2] = w4.z; res[p][q][3] = w4.w;
+    }
+  }
+  tile_copies<PLANES>(res, sT, wt, ldt, wc, ldc, plane_t, plane_c, k0, n0, h2_scale);
+}
+
 template <int PLANES>
 __global__ void __launch_bounds__(kThreads)
 k_adam_matrix_bf16(float *__restrict__ w, const float *__restrict__ g, float *__restrict__ m,
@@ -210,50 +212,79 @@ k_adam_matrix_bf16(float *__restrict__ w, const float *__restrict__ g, float *__
                    int64_t plane_t, int64_t plane_c, float h2_scale) {
   __shared__ float s_lr_t;
   __shared__ uint32_t sT[kAT][kAT / 2 + 1];           // [column n][row pair]: two bf16 of one column per word
-  if (threadIdx.x == 0) {
-    const double t = (double)t_imm + (t_dev ? (double)(*t_dev) : 0.0);
-    const double lr = lr_dev ? (double)(*lr_dev) : (double)lr_imm;
-    s_lr_t = (float)(lr * sqrt(1.0 - pow((double)b2, t)) / (1.0 - pow((double)b1, t)));
-  }
-  __syncthreads();
-  const float lr_t = s_lr_t;
+  const float lr_t = adam_lr_t(s_lr_t, lr_imm, lr_dev, b1, b2, t_imm, t_dev);
   const float omb1 = 1.0f - b1, omb2 = 1.0f - b2;
-  const int tiles_n = N / kAT;
-  const int k0 = (blockIdx.x / tiles_n) * kAT, n0 = (blockIdx.x % tiles_n) * kAT;
-  const int tr = threadIdx.x >> 4, c4 = (threadIdx.x & 15) * 4;
-  // a thread takes two adjacent rows of four columns per pass: the transpose goes through LDS as
-  // 32-bit words (the two rows' values of one column), 33-word rows -> at most 2-way bank conflicts
-  float res[2][2][4];                                  // the new weights (PLANES > 1: what the planes so far leave)
-#pragma unroll
-  for (int p = 0; p < 2; ++p) {
-    const int r = p * 32 + 2 * tr;
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-      const int64_t i = (int64_t)(k0 + r + q) * N + n0 + c4;
-      float4 w4 = *reinterpret_cast<float4 *>(w + i);
-      const float4 g4 = *reinterpret_cast<const float4 *>(g + i);
-      float4 m4 = *reinterpret_cast<float4 *>(m + i);
-      float4 v4 = *reinterpret_cast<float4 *>(v + i);
+  tile_update<PLANES>(N, sT, wt, ldt, wc, ldc, plane_t, plane_c, h2_scale, [=](const int64_t i) {
+    float4 w4 = *reinterpret_cast<float4 *>(w + i);
+    const float4 g4 = *reinterpret_cast<const float4 *>(g + i);
+    float4 m4 = *reinterpret_cast<float4 *>(m + i);
+    float4 v4 = *reinterpret_cast<float4 *>(v + i);
 #define CDML_ADAM1(c) adam1(w4.c, g4.c, m4.c, v4.c, omb1, omb2, lr_t, eps);
-      CDML_ADAM1(x) CDML_ADAM1(y) CDML_ADAM1(z) CDML_ADAM1(w)
+    CDML_ADAM1(x) CDML_ADAM1(y) CDML_ADAM1(z) CDML_ADAM1(w)
 #undef CDML_ADAM1
-      *reinterpret_cast<float4 *>(w + i) = w4;
-      *reinterpret_cast<float4 *>(m + i) = m4;
-      *reinterpret_cast<float4 *>(v + i) = v4;
-      res[p][q][0] = w4.x; res[p][q][1] = w4.y; res[p][q][2] = w4.z; res[p][q][3] = w4.w;
-    }
-  }
-  tile_copies<PLANES>(res, sT, wt, ldt, wc, ldc, plane_t, plane_c, k0, n0, h2_scale);
-  if (bw) {                                          // the bias vector: element i of the first ceil(bn / 256) blocks
-    for (int i = blockIdx.x * kThreads + threadIdx.x; i < bn; i += gridDim.x * kThreads) {
+    *reinterpret_cast<float4 *>(w + i) = w4;
+    *reinterpret_cast<float4 *>(m + i) = m4;
+    *reinterpret_cast<float4 *>(v + i) = v4;
+    return w4;
+  });
+  if (bw)
+    bias_ride(bn, [=](const int i) {
       float wi = bw[i], mi = bm[i], vi = bv[i];
       adam1(wi, bg[i], mi, vi, omb1, omb2, lr_t, eps);
       bm[i] = mi;
       bv[i] = vi;
       bw[i] = wi;
-    }
-  }
+    });
   if (advance && grid_last_block(tickets) && threadIdx.x == 0) *t_dev += 1;
+}
+
+// The block's sums of two per-thread values, fixed order: wave_sum, the four wave partials through LDS, thread 0 adds
+// them in double and writes the pair to out[0], out[1].
+__device__ __forceinline__ void block_pair_sum(double (&s)[2][kThreads / kWave], float sw, float sg, float *out) {
+  sw = wave_sum(sw);
+  sg = wave_sum(sg);
+  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
+  if (lane == 0) { s[0][wave] = sw; s[1][wave] = sg; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double a = 0, b = 0;
+    for (int k = 0; k < kThreads / kWave; ++k) { a += s[0][k]; b += s[1][k]; }
+    out[0] = (float)a;
+    out[1] = (float)b;
+  }
+}
+
+// LARS' trust ratio of one variable from its norms |w|, |g| (compute_lr of tf.contrib.opt.LARSOptimizer)
+__device__ __forceinline__ float lars_trust(const float wn, const float gn, const float eeta, const float wd, const float eps) {
+  return (wn > 0.f && gn > 0.f) ? eeta * wn / (gn + wd * wn + eps) : 1.0f;
+}
+
+// One variable's norms from k_lars_multi_norms' partial pairs [b0, b1) of `scratch`, by the whole block in a fixed order:
+// double accumulation per thread, a shuffle tree, the four wave partials through LDS.  Thread 0 then calls
+// thread0(|w|, |g|).  Every block that reduces a segment goes through here -- the same order, the same bits, so the flat and
+// the matrix kernels scale a variable by the same trust ratio.  Ends in a barrier: s_part may be used again at once.
+template <class F>
+__device__ __forceinline__ void lars_segment_norms(double (&s_part)[2][kThreads / kWave], const float *scratch,
+                                                   const int b0, const int b1, F &&thread0) {
+  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
+  double a = 0, c = 0;
+  for (int k = b0 + threadIdx.x; k < b1; k += kThreads) {
+    a += (double)scratch[2 * k];
+    c += (double)scratch[2 * k + 1];
+  }
+#pragma unroll
+  for (int o = kWave / 2; o > 0; o >>= 1) {
+    a += __shfl_xor(a, o, kWave);
+    c += __shfl_xor(c, o, kWave);
+  }
+  if (lane == 0) { s_part[0][wave] = a; s_part[1][wave] = c; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double wn2 = 0, gn2 = 0;
+    for (int k = 0; k < kThreads / kWave; ++k) { wn2 += s_part[0][k]; gn2 += s_part[1][k]; }
+    thread0(sqrtf((float)wn2), sqrtf((float)gn2));
+  }
+  __syncthreads();
 }
 
 // scratch layout: [0]=|w|^2, [1]=|g|^2, then kLarsBlocks x 2 block partials
@@ -268,17 +299,7 @@ k_lars_norm_partial(const float *__restrict__ w, const float *__restrict__ g, in
     sw += a * a;
     sg += b * b;
   }
-  sw = wave_sum(sw);
-  sg = wave_sum(sg);
-  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
-  if (lane == 0) { s[0][wave] = sw; s[1][wave] = sg; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double a = 0, b = 0;
-    for (int k = 0; k < kThreads / kWave; ++k) { a += s[0][k]; b += s[1][k]; }
-    scratch[2 + 2 * blockIdx.x] = (float)a;
-    scratch[3 + 2 * blockIdx.x] = (float)b;
-  }
+  block_pair_sum(s, sw, sg, scratch + (2 + 2 * blockIdx.x));
 }
 
 __global__ void k_lars_norm_final(float *__restrict__ scratch, int blocks) {
@@ -296,8 +317,7 @@ k_lars_apply(float *__restrict__ w, const float *__restrict__ g, float *__restri
              float eps, const float *__restrict__ scratch) {
   const float lr = lr_dev ? *lr_dev : lr_imm;
   const float wn = sqrtf(scratch[0]), gn = sqrtf(scratch[1]);
-  const float trust = (wn > 0.f && gn > 0.f) ? eeta * wn / (gn + wd * wn + eps) : 1.0f;
-  const float slr = lr * trust;
+  const float slr = lr * lars_trust(wn, gn, eeta, wd, eps);
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
        i += (int64_t)gridDim.x * blockDim.x) {
     float wi = w[i], a = acc[i];
@@ -342,17 +362,7 @@ k_lars_multi_norms(const float *__restrict__ w, const float *__restrict__ g, Lar
     sw += a.x * a.x + a.y * a.y + a.z * a.z + a.w * a.w;
     sg += c.x * c.x + c.y * c.y + c.z * c.z + c.w * c.w;
   }
-  sw = wave_sum(sw);
-  sg = wave_sum(sg);
-  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
-  if (lane == 0) { s[0][wave] = sw; s[1][wave] = sg; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double a = 0, c = 0;
-    for (int k = 0; k < kThreads / kWave; ++k) { a += s[0][k]; c += s[1][k]; }
-    scratch[2 * blockIdx.x] = (float)a;
-    scratch[2 * blockIdx.x + 1] = (float)c;
-  }
+  block_pair_sum(s, sw, sg, scratch + 2 * blockIdx.x);
 }
 
 __global__ void __launch_bounds__(kThreads)
@@ -363,30 +373,11 @@ k_lars_multi_apply(float *__restrict__ w, const float *__restrict__ g, float *__
   __shared__ double s_part[2][kThreads / kWave];
   __shared__ float s_slr[kMaxSeg];
   const float lr = lr_dev ? *lr_dev : lr_imm;
-  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
-  for (int seg = 0; seg < S.n_seg; ++seg) {           // every block, the same order: the same trust ratios
-    double a = 0, c = 0;
-    for (int k = S.blk[seg] + threadIdx.x; k < S.blk[seg + 1]; k += kThreads) {
-      a += (double)scratch[2 * k];
-      c += (double)scratch[2 * k + 1];
-    }
-#pragma unroll
-    for (int o = kWave / 2; o > 0; o >>= 1) {
-      a += __shfl_xor(a, o, kWave);
-      c += __shfl_xor(c, o, kWave);
-    }
-    if (lane == 0) { s_part[0][wave] = a; s_part[1][wave] = c; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      double wn2 = 0, gn2 = 0;
-      for (int k = 0; k < kThreads / kWave; ++k) { wn2 += s_part[0][k]; gn2 += s_part[1][k]; }
-      const float wn = sqrtf((float)wn2), gn = sqrtf((float)gn2);
-      const float trust = (wn > 0.f && gn > 0.f) ? eeta * wn / (gn + wd * wn + eps) : 1.0f;
-      s_slr[seg] = lr * trust;
+  for (int seg = 0; seg < S.n_seg; ++seg)
+    lars_segment_norms(s_part, scratch, S.blk[seg], S.blk[seg + 1], [=](const float wn, const float gn) {
+      s_slr[seg] = lr * lars_trust(wn, gn, eeta, wd, eps);
       if (norms_out && blockIdx.x == 0) { norms_out[2 * seg] = wn; norms_out[2 * seg + 1] = gn; }
-    }
-    __syncthreads();
-  }
+    });
   const int64_t n4 = S.off[S.n_seg] >> 2;
   for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < n4; i += (int64_t)gridDim.x * kThreads) {
     int seg = 0;
@@ -409,8 +400,8 @@ k_lars_multi_apply(float *__restrict__ w, const float *__restrict__ g, float *__
 // What k_adam_matrix_bf16 is for Adam: the bf16 (config 4) or three-plane (precision "f32x3") copies of the new
 // weights come out of the update's own registers, so the reference's actual recipe (LARS, train.py:354) needs no
 // separate split / transpose / cast launches after the optimizer.  RULE 1 = LARS: the trust ratios of the matrix'
-// segment and of the bias' segment are reduced from k_lars_multi_norms' partials by every block itself, in the fixed
-// order k_lars_multi_apply uses (same bits); RULE 2 = momentum (Nesterov on request).  Same element arithmetic as the
+// segment and of the bias' segment are reduced from k_lars_multi_norms' partials by every block itself, through
+// lars_segment_norms like k_lars_multi_apply; RULE 2 = momentum (Nesterov on request).  Same element arithmetic as the
 // flat kernels (lars1 / momentum1).
 struct MatRule {
   float lr_imm; const float *lr_dev;
@@ -422,6 +413,14 @@ struct MatRule {
   float h2_scale;                // PLANES = 2 (precision "f16x2"): the copies are the fp16 planes of the new weights times this
 };
 
+// One element by RULE at the variable's rate (LARS: lr * trust; momentum: lr)
+template <int RULE>
+__device__ __forceinline__ void rule1(float &w, const float g, float &a, const float rate, const float momentum, const float wd,
+                                      const int nesterov) {
+  if (RULE == 1) lars1(w, g, a, rate, momentum, wd);
+  else momentum1(w, g, a, rate, momentum, nesterov);
+}
+
 template <int PLANES, int RULE>
 __global__ void __launch_bounds__(kThreads)
 k_rule_matrix(float *__restrict__ w, const float *__restrict__ g, float *__restrict__ acc, int K, int N, MatRule R,
@@ -432,68 +431,41 @@ k_rule_matrix(float *__restrict__ w, const float *__restrict__ g, float *__restr
   __shared__ double s_part[2][kThreads / kWave];
   __shared__ float s_slr[2];
   const float lr = R.lr_dev ? *R.lr_dev : R.lr_imm;
+  // the lambdas below capture by value, so they are given these scalars and not the whole rule: a copy of R reads
+  // lr_imm where lr_dev is set
+  const float momentum = R.momentum, wd = R.wd, eeta = R.eeta, eps = R.eps, h2_scale = R.h2_scale;
+  const int nesterov = R.nesterov;
   if (RULE == 1) {
-    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
     for (int v = 0; v < 2; ++v) {                        // the matrix, then its bias vector
       const int b0 = v ? R.blk_b0 : R.blk_w0, b1 = v ? R.blk_b1 : R.blk_w1;
-      double a = 0, c = 0;
-      for (int k = b0 + threadIdx.x; k < b1; k += kThreads) {
-        a += (double)R.scratch[2 * k];
-        c += (double)R.scratch[2 * k + 1];
-      }
-#pragma unroll
-      for (int o = kWave / 2; o > 0; o >>= 1) {
-        a += __shfl_xor(a, o, kWave);
-        c += __shfl_xor(c, o, kWave);
-      }
-      if (lane == 0) { s_part[0][wave] = a; s_part[1][wave] = c; }
-      __syncthreads();
-      if (threadIdx.x == 0) {
-        double wn2 = 0, gn2 = 0;
-        for (int k = 0; k < kThreads / kWave; ++k) { wn2 += s_part[0][k]; gn2 += s_part[1][k]; }
-        const float wn = sqrtf((float)wn2), gn = sqrtf((float)gn2);
-        const float trust = (wn > 0.f && gn > 0.f) ? R.eeta * wn / (gn + R.wd * wn + R.eps) : 1.0f;
+      float *const no = v ? R.norms_b : R.norms_w;
+      lars_segment_norms(s_part, R.scratch, b0, b1, [=](const float wn, const float gn) {
+        const float trust = lars_trust(wn, gn, eeta, wd, eps);
         s_slr[v] = (b1 > b0) ? lr * trust : lr;
-        float *no = v ? R.norms_b : R.norms_w;
         if (no && blockIdx.x == 0 && b1 > b0) { no[0] = wn; no[1] = gn; }
-      }
-      __syncthreads();
+      });
     }
   }
+  // the variable's rate: LARS' lr * trust, momentum's lr
   const float slr_w = RULE == 1 ? s_slr[0] : lr, slr_b = RULE == 1 ? s_slr[1] : lr;
-  const int tiles_n = N / kAT;
-  const int k0 = (blockIdx.x / tiles_n) * kAT, n0 = (blockIdx.x % tiles_n) * kAT;
-  const int tr = threadIdx.x >> 4, c4 = (threadIdx.x & 15) * 4;
-  float res[2][2][4];
-#pragma unroll
-  for (int p = 0; p < 2; ++p) {
-    const int r = p * 32 + 2 * tr;
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-      const int64_t i = (int64_t)(k0 + r + q) * N + n0 + c4;
-      float4 w4 = *reinterpret_cast<float4 *>(w + i);
-      const float4 g4 = *reinterpret_cast<const float4 *>(g + i);
-      float4 a4 = *reinterpret_cast<float4 *>(acc + i);
-#define CDML_RULE1(c)                                                  \
-  if (RULE == 1) lars1(w4.c, g4.c, a4.c, slr_w, R.momentum, R.wd);     \
-  else momentum1(w4.c, g4.c, a4.c, lr, R.momentum, R.nesterov);
-      CDML_RULE1(x) CDML_RULE1(y) CDML_RULE1(z) CDML_RULE1(w)
+  tile_update<PLANES>(N, sT, wt, ldt, wc, ldc, plane_t, plane_c, h2_scale, [=](const int64_t i) {
+    float4 w4 = *reinterpret_cast<float4 *>(w + i);
+    const float4 g4 = *reinterpret_cast<const float4 *>(g + i);
+    float4 a4 = *reinterpret_cast<float4 *>(acc + i);
+#define CDML_RULE1(c) rule1<RULE>(w4.c, g4.c, a4.c, slr_w, momentum, wd, nesterov);
+    CDML_RULE1(x) CDML_RULE1(y) CDML_RULE1(z) CDML_RULE1(w)
 #undef CDML_RULE1
-      *reinterpret_cast<float4 *>(w + i) = w4;
-      *reinterpret_cast<float4 *>(acc + i) = a4;
-      res[p][q][0] = w4.x; res[p][q][1] = w4.y; res[p][q][2] = w4.z; res[p][q][3] = w4.w;
-    }
-  }
-  tile_copies<PLANES>(res, sT, wt, ldt, wc, ldc, plane_t, plane_c, k0, n0, R.h2_scale);
-  if (bw) {
-    for (int i = blockIdx.x * kThreads + threadIdx.x; i < bn; i += gridDim.x * kThreads) {
+    *reinterpret_cast<float4 *>(w + i) = w4;
+    *reinterpret_cast<float4 *>(acc + i) = a4;
+    return w4;
+  });
+  if (bw)
+    bias_ride(bn, [=](const int i) {
       float wi = bw[i], ai = bacc[i];
-      if (RULE == 1) lars1(wi, bg[i], ai, slr_b, R.momentum, R.wd);
-      else momentum1(wi, bg[i], ai, lr, R.momentum, R.nesterov);
+      rule1<RULE>(wi, bg[i], ai, slr_b, momentum, wd, nesterov);
       bacc[i] = ai;
       bw[i] = wi;
-    }
-  }
+    });
   if (step_dev && grid_last_block(tickets) && threadIdx.x == 0) *step_dev += 1;
 }
 
@@ -514,17 +486,7 @@ k_prep_partial(const float *__restrict__ w, const float *__restrict__ g, int64_t
     sw += a * a;
     sg += b * b;
   }
-  sw = wave_sum(sw);
-  sg = wave_sum(sg);
-  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
-  if (lane == 0) { s[0][wave] = sw; s[1][wave] = sg; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double a = 0, b = 0;
-    for (int k = 0; k < kThreads / kWave; ++k) { a += s[0][k]; b += s[1][k]; }
-    scratch[2 + 2 * blockIdx.x] = (float)a;
-    scratch[3 + 2 * blockIdx.x] = (float)b;
-  }
+  block_pair_sum(s, sw, sg, scratch + (2 + 2 * blockIdx.x));
 }
 
 __global__ void __launch_bounds__(kThreads)
@@ -582,6 +544,33 @@ extern "C" int cdml_adam_step(float *w, const float *g, float *m, float *v, int6
   return check_launch("adam_step");
 }
 
+// planes -> the <1 | 2 | 3> instantiation of a matrix kernel, launched with one block per 64 x 64 tile
+template <class... P, class... A>
+static void launch_matrix(int planes, void (*k1)(P...), void (*k2)(P...), void (*k3)(P...), int K, int N, cdml_stream_t stream,
+                          A... args) {
+  hipLaunchKernelGGL(planes == 2 ? k2 : planes == 3 ? k3 : k1, dim3((K / kAT) * (N / kAT)), dim3(kThreads), 0,
+                     (hipStream_t)stream, args...);
+}
+
+// The operand copies of a K x N matrix as the matrix kernels write them: planes = 1 (bf16), 2 (fp16 hi | lo) or 3 (bf16
+// hi | mid | lo).  One copy has no planes: its strides are zeroed whatever the caller gave.
+static int check_copies(const char *who, int K, int N, const uint16_t *wt, int64_t ldt, int64_t &plane_t, const uint16_t *wc,
+                        int64_t ldc, int64_t &plane_c, int planes) {
+  CDML_REQUIRE(planes == 1 || planes == 2 || planes == 3, CDML_E_BADARG, "%s: planes must be 1 (bf16 copies), 2 (fp16 hi | lo) or 3 (hi | mid | lo)", who);
+  CDML_REQUIRE(K > 0 && N > 0 && K % kAT == 0 && N % kAT == 0, CDML_E_UNSUPPORTED,
+               "%s: K and N must be multiples of 64, got K=%d N=%d", who, K, N);
+  CDML_REQUIRE((!wt || (aligned16(wt) && (ldt & 7) == 0 && ldt >= K)) && (!wc || (aligned16(wc) && (ldc & 3) == 0 && ldc >= N)),
+               CDML_E_ALIGN, "%s: 16-B aligned copies, ldt a multiple of 8 (>= K), ldc of 4 (>= N)", who);
+  if (planes >= 2)
+    CDML_REQUIRE((!wt || (!(plane_t & 7) && plane_t >= K && ldt >= (planes - 1) * plane_t + K)) &&
+                     (!wc || (!(plane_c & 3) && plane_c >= N && ldc >= (planes - 1) * plane_c + N)),
+                 CDML_E_ALIGN, "%s: plane strides (W^T: multiple of 8, >= K; W: multiple of 4, >= N) and leading dimensions "
+                 ">= (planes - 1) planes + the matrix width", who);
+  else
+    plane_t = plane_c = 0;
+  return CDML_OK;
+}
+
 static int adam_matrix_impl(float *w, const float *g, float *m, float *v, int K, int N, float lr,
                             const float *lr_dev, float beta1, float beta2, float eps, int64_t t,
                             uint64_t *t_dev, uint16_t *wt_bf16, int64_t ldt, uint16_t *wc_bf16,
@@ -593,37 +582,18 @@ static int adam_matrix_impl(float *w, const float *g, float *m, float *v, int K,
                "adam_matrix_bf16: the bias vector needs its gradient and both moments");
   CDML_REQUIRE(!advance_step || (t_dev && tickets), CDML_E_BADARG,
                "adam_matrix_bf16: advance_step needs the device step counter and the ticket words");
+  // (the shape before the step, the step before the alignments: check_copies alone would answer in another order)
   CDML_REQUIRE(K % kAT == 0 && N % kAT == 0, CDML_E_UNSUPPORTED,
                "adam_matrix_bf16: K and N must be multiples of 64, got K=%d N=%d", K, N);
   CDML_REQUIRE(t >= (t_dev ? 0 : 1), CDML_E_BADARG, "adam_matrix_bf16: step t is 1-based");
-  CDML_REQUIRE(aligned16(w) && aligned16(g) && aligned16(m) && aligned16(v) &&
-                   (!wt_bf16 || (aligned16(wt_bf16) && (ldt & 7) == 0 && ldt >= K)) &&
-                   (!wc_bf16 || (aligned16(wc_bf16) && (ldc & 3) == 0 && ldc >= N)),
-               CDML_E_ALIGN, "adam_matrix_bf16: 16-B aligned buffers, ldt a multiple of 8 (>= K), ldc of 4 (>= N)");
-  if (planes == 2) {
-    CDML_REQUIRE(h2_scale > 0.f && (!wt_bf16 || (!(plane_t & 7) && plane_t >= K && ldt >= plane_t + K)) &&
-                     (!wc_bf16 || (!(plane_c & 3) && plane_c >= N && ldc >= plane_c + N)),
-                 CDML_E_ALIGN, "adam_matrix_h2: a positive scale, plane strides (W^T: multiple of 8, >= K; W: multiple of 4, >= N) and "
-                 "leading dimensions >= plane + the matrix width");
-    hipLaunchKernelGGL(k_adam_matrix_bf16<2>, dim3((K / kAT) * (N / kAT)), dim3(kThreads), 0, (hipStream_t)stream, w, g,
-                       m, v, K, N, lr, lr_dev, beta1, beta2, eps, t, t_dev, reinterpret_cast<__bf16 *>(wt_bf16), ldt,
-                       reinterpret_cast<__bf16 *>(wc_bf16), ldc, bias_w, bias_g, bias_m, bias_v, bias_w ? bias_n : 0,
-                       advance_step, tickets, plane_t, plane_c, h2_scale);
-  } else if (planes == 3) {
-    CDML_REQUIRE((!wt_bf16 || (!(plane_t & 7) && plane_t >= K && ldt >= 2 * plane_t + K)) &&
-                     (!wc_bf16 || (!(plane_c & 3) && plane_c >= N && ldc >= 2 * plane_c + N)),
-                 CDML_E_ALIGN, "adam_matrix_planes: plane strides (W^T: multiple of 8, >= K; W: multiple of 4, >= N) and "
-                 "leading dimensions >= 2 planes + the matrix width");
-    hipLaunchKernelGGL(k_adam_matrix_bf16<3>, dim3((K / kAT) * (N / kAT)), dim3(kThreads), 0, (hipStream_t)stream, w, g,
-                       m, v, K, N, lr, lr_dev, beta1, beta2, eps, t, t_dev, reinterpret_cast<__bf16 *>(wt_bf16), ldt,
-                       reinterpret_cast<__bf16 *>(wc_bf16), ldc, bias_w, bias_g, bias_m, bias_v, bias_w ? bias_n : 0,
-                       advance_step, tickets, plane_t, plane_c, 0.f);
-  } else {
-    hipLaunchKernelGGL(k_adam_matrix_bf16<1>, dim3((K / kAT) * (N / kAT)), dim3(kThreads), 0, (hipStream_t)stream, w, g,
-                       m, v, K, N, lr, lr_dev, beta1, beta2, eps, t, t_dev, reinterpret_cast<__bf16 *>(wt_bf16), ldt,
-                       reinterpret_cast<__bf16 *>(wc_bf16), ldc, bias_w, bias_g, bias_m, bias_v, bias_w ? bias_n : 0,
-                       advance_step, tickets, (int64_t)0, (int64_t)0, 0.f);
-  }
+  CDML_REQUIRE(aligned16(w) && aligned16(g) && aligned16(m) && aligned16(v), CDML_E_ALIGN,
+               "adam_matrix_bf16: buffers must be 16-B aligned");
+  if (int rc = check_copies("adam_matrix_bf16", K, N, wt_bf16, ldt, plane_t, wc_bf16, ldc, plane_c, planes)) return rc;
+  CDML_REQUIRE(planes != 2 || h2_scale > 0.f, CDML_E_ALIGN, "adam_matrix_h2: fp16 planes go with a positive scale");
+  launch_matrix(planes, k_adam_matrix_bf16<1>, k_adam_matrix_bf16<2>, k_adam_matrix_bf16<3>, K, N, stream, w, g, m, v, K, N, lr,
+                lr_dev, beta1, beta2, eps, t, t_dev, reinterpret_cast<__bf16 *>(wt_bf16), ldt, reinterpret_cast<__bf16 *>(wc_bf16),
+                ldc, bias_w, bias_g, bias_m, bias_v, bias_w ? bias_n : 0, advance_step, tickets, plane_t, plane_c,
+                planes == 2 ? h2_scale : 0.f);
   return check_launch("adam_matrix_bf16");
 }
 
@@ -678,13 +648,13 @@ extern "C" int cdml_lars_step(float *w, const float *g, float *acc, int64_t n, f
 }
 
 // segments -> LarsSegs: offsets, and the norm blocks dealt in proportion to the segment sizes (at least one each,
-// kLarsBlocks at most in all).  One function for every LARS entry point: the norms launch and the launches that
+// kLarsBlocks at most in all; S.blk[n_seg] of them, over S.off[n_seg] floats).  One function for every LARS entry point: the norms launch and the launches that
 // reduce its partials must agree on the layout.
-static int lars_layout(const int64_t *seg_offsets, const int64_t *seg_sizes, int n_seg, LarsSegs &S, int &nb, int64_t &total) {
+static int lars_layout(const int64_t *seg_offsets, const int64_t *seg_sizes, int n_seg, LarsSegs &S) {
   CDML_REQUIRE(seg_offsets && seg_sizes, CDML_E_BADARG, "lars: segment arrays required");
   CDML_REQUIRE(n_seg >= 1 && n_seg <= kMaxSeg, CDML_E_UNSUPPORTED, "lars: 1..%d segments, got %d", kMaxSeg, n_seg);
   S.n_seg = n_seg;
-  total = 0;
+  int64_t total = 0;
   for (int k = 0; k < n_seg; ++k) {
     CDML_REQUIRE(seg_sizes[k] > 0 && (seg_sizes[k] & 3) == 0 && seg_offsets[k] == total, CDML_E_BADARG,
                  "lars: segments must tile the buffer contiguously in multiples of 4 floats (segment %d)", k);
@@ -693,7 +663,7 @@ static int lars_layout(const int64_t *seg_offsets, const int64_t *seg_sizes, int
   }
   S.off[n_seg] = total;
   const int budget = kLarsBlocks - n_seg;
-  nb = 0;
+  int nb = 0;                                          // S.blk[n_seg]: the norms launch's grid
   for (int k = 0; k < n_seg; ++k) {
     S.blk[k] = nb;
     int64_t want = (seg_sizes[k] / 4 + kThreads * 8 - 1) / (kThreads * 8);          // >= 8 float4 per thread
@@ -717,12 +687,10 @@ extern "C" int cdml_lars_multi(float *w, const float *g, float *acc, const int64
   CDML_REQUIRE(!step_dev_advance || tickets, CDML_E_BADARG, "lars_multi: advancing the step counter needs the ticket words");
   CDML_REQUIRE(aligned16(w) && aligned16(g) && aligned16(acc), CDML_E_ALIGN, "lars_multi: buffers must be 16-B aligned");
   LarsSegs S;
-  int nb = 0;
-  int64_t total = 0;
-  if (int rc = lars_layout(seg_offsets, seg_sizes, n_seg, S, nb, total)) return rc;
+  if (int rc = lars_layout(seg_offsets, seg_sizes, n_seg, S)) return rc;
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(k_lars_multi_norms, dim3(nb), dim3(kThreads), 0, s, w, g, S, scratch);
-  hipLaunchKernelGGL(k_lars_multi_apply, dim3(grid_elems(total, 4)), dim3(kThreads), 0, s, w, g, acc, S, lr, lr_dev,
+  hipLaunchKernelGGL(k_lars_multi_norms, dim3(S.blk[n_seg]), dim3(kThreads), 0, s, w, g, S, scratch);
+  hipLaunchKernelGGL(k_lars_multi_apply, dim3(grid_elems(S.off[n_seg], 4)), dim3(kThreads), 0, s, w, g, acc, S, lr, lr_dev,
                      momentum, weight_decay, eeta, eps, scratch, norms_out, step_dev_advance, tickets);
   return check_launch("lars_multi");
 }
@@ -736,26 +704,9 @@ extern "C" int cdml_lars_multi_norms(const float *w, const float *g, const int64
   CDML_REQUIRE(w && g && scratch, CDML_E_BADARG, "lars_multi_norms: bad argument");
   CDML_REQUIRE(aligned16(w) && aligned16(g), CDML_E_ALIGN, "lars_multi_norms: buffers must be 16-B aligned");
   LarsSegs S;
-  int nb = 0;
-  int64_t total = 0;
-  if (int rc = lars_layout(seg_offsets, seg_sizes, n_seg, S, nb, total)) return rc;
-  hipLaunchKernelGGL(k_lars_multi_norms, dim3(nb), dim3(kThreads), 0, (hipStream_t)stream, w, g, S, scratch);
+  if (int rc = lars_layout(seg_offsets, seg_sizes, n_seg, S)) return rc;
+  hipLaunchKernelGGL(k_lars_multi_norms, dim3(S.blk[n_seg]), dim3(kThreads), 0, (hipStream_t)stream, w, g, S, scratch);
   return check_launch("lars_multi_norms");
-}
-
-static int check_copies(const char *who, int K, int N, const uint16_t *wt, int64_t ldt, int64_t plane_t, const uint16_t *wc,
-                        int64_t ldc, int64_t plane_c, int planes) {
-  CDML_REQUIRE(planes == 1 || planes == 2 || planes == 3, CDML_E_BADARG, "%s: planes must be 1 (bf16 copies), 2 (fp16 hi | lo) or 3 (hi | mid | lo)", who);
-  CDML_REQUIRE(K > 0 && N > 0 && K % kAT == 0 && N % kAT == 0, CDML_E_UNSUPPORTED,
-               "%s: K and N must be multiples of 64, got K=%d N=%d", who, K, N);
-  CDML_REQUIRE((!wt || (aligned16(wt) && (ldt & 7) == 0 && ldt >= K)) && (!wc || (aligned16(wc) && (ldc & 3) == 0 && ldc >= N)),
-               CDML_E_ALIGN, "%s: 16-B aligned copies, ldt a multiple of 8 (>= K), ldc of 4 (>= N)", who);
-  if (planes >= 2)
-    CDML_REQUIRE((!wt || (!(plane_t & 7) && plane_t >= K && ldt >= (planes - 1) * plane_t + K)) &&
-                     (!wc || (!(plane_c & 3) && plane_c >= N && ldc >= (planes - 1) * plane_c + N)),
-                 CDML_E_ALIGN, "%s: plane strides (W^T: multiple of 8, >= K; W: multiple of 4, >= N) and leading dimensions "
-                 ">= (planes - 1) planes + the matrix width", who);
-  return CDML_OK;
 }
 
 static int lars_matrix_impl(float h2_scale, float *w, const float *g, float *acc, const int64_t *seg_offsets, const int64_t *seg_sizes,
@@ -769,9 +720,7 @@ static int lars_matrix_impl(float h2_scale, float *w, const float *g, float *acc
   CDML_REQUIRE(!step_dev_advance || tickets, CDML_E_BADARG, "lars_matrix: advancing the step counter needs the ticket words");
   CDML_REQUIRE(aligned16(w) && aligned16(g) && aligned16(acc), CDML_E_ALIGN, "lars_matrix: buffers must be 16-B aligned");
   LarsSegs S;
-  int nb = 0;
-  int64_t total = 0;
-  if (int rc = lars_layout(seg_offsets, seg_sizes, n_seg, S, nb, total)) return rc;
+  if (int rc = lars_layout(seg_offsets, seg_sizes, n_seg, S)) return rc;
   CDML_REQUIRE(seg_matrix >= 0 && seg_matrix < n_seg && seg_bias < n_seg && seg_bias != seg_matrix, CDML_E_BADARG,
                "lars_matrix: segment indices out of range");
   CDML_REQUIRE(seg_sizes[seg_matrix] == (int64_t)K * N, CDML_E_BADARG, "lars_matrix: segment %d holds %lld floats, not %d x %d",
@@ -792,19 +741,9 @@ static int lars_matrix_impl(float h2_scale, float *w, const float *g, float *acc
     bn = (int)seg_sizes[seg_bias];
   }
   const int64_t o = S.off[seg_matrix];
-  const dim3 grid((K / kAT) * (N / kAT));
-  if (planes == 2)
-    hipLaunchKernelGGL((k_rule_matrix<2, 1>), grid, dim3(kThreads), 0, (hipStream_t)stream, w + o, g + o, acc + o, K, N, R,
-                       reinterpret_cast<__bf16 *>(wt), ldt, reinterpret_cast<__bf16 *>(wc), ldc, bw, bg, bacc, bn,
-                       step_dev_advance, tickets, plane_t, plane_c);
-  else if (planes == 3)
-    hipLaunchKernelGGL((k_rule_matrix<3, 1>), grid, dim3(kThreads), 0, (hipStream_t)stream, w + o, g + o, acc + o, K, N, R,
-                       reinterpret_cast<__bf16 *>(wt), ldt, reinterpret_cast<__bf16 *>(wc), ldc, bw, bg, bacc, bn,
-                       step_dev_advance, tickets, plane_t, plane_c);
-  else
-    hipLaunchKernelGGL((k_rule_matrix<1, 1>), grid, dim3(kThreads), 0, (hipStream_t)stream, w + o, g + o, acc + o, K, N, R,
-                       reinterpret_cast<__bf16 *>(wt), ldt, reinterpret_cast<__bf16 *>(wc), ldc, bw, bg, bacc, bn,
-                       step_dev_advance, tickets, (int64_t)0, (int64_t)0);
+  launch_matrix(planes, k_rule_matrix<1, 1>, k_rule_matrix<2, 1>, k_rule_matrix<3, 1>, K, N, stream, w + o, g + o, acc + o, K, N, R,
+                reinterpret_cast<__bf16 *>(wt), ldt, reinterpret_cast<__bf16 *>(wc), ldc, bw, bg, bacc, bn, step_dev_advance,
+                tickets, plane_t, plane_c);
   return check_launch("lars_matrix");
 }
 
@@ -847,19 +786,9 @@ static int momentum_matrix_impl(float h2_scale, float *w, const float *g, float 
   if (int rc = check_copies("momentum_matrix", K, N, wt, ldt, plane_t, wc, ldc, plane_c, planes)) return rc;
   MatRule R{};
   R.lr_imm = lr; R.lr_dev = lr_dev; R.momentum = momentum; R.nesterov = use_nesterov; R.h2_scale = h2_scale;
-  const dim3 grid((K / kAT) * (N / kAT));
-  if (planes == 2)
-    hipLaunchKernelGGL((k_rule_matrix<2, 2>), grid, dim3(kThreads), 0, (hipStream_t)stream, w, g, acc, K, N, R,
-                       reinterpret_cast<__bf16 *>(wt), ldt, reinterpret_cast<__bf16 *>(wc), ldc, bias_w, bias_g, bias_acc,
-                       bias_w ? bias_n : 0, step_dev_advance, tickets, plane_t, plane_c);
-  else if (planes == 3)
-    hipLaunchKernelGGL((k_rule_matrix<3, 2>), grid, dim3(kThreads), 0, (hipStream_t)stream, w, g, acc, K, N, R,
-                       reinterpret_cast<__bf16 *>(wt), ldt, reinterpret_cast<__bf16 *>(wc), ldc, bias_w, bias_g, bias_acc,
-                       bias_w ? bias_n : 0, step_dev_advance, tickets, plane_t, plane_c);
-  else
-    hipLaunchKernelGGL((k_rule_matrix<1, 2>), grid, dim3(kThreads), 0, (hipStream_t)stream, w, g, acc, K, N, R,
-                       reinterpret_cast<__bf16 *>(wt), ldt, reinterpret_cast<__bf16 *>(wc), ldc, bias_w, bias_g, bias_acc,
-                       bias_w ? bias_n : 0, step_dev_advance, tickets, (int64_t)0, (int64_t)0);
+  launch_matrix(planes, k_rule_matrix<1, 2>, k_rule_matrix<2, 2>, k_rule_matrix<3, 2>, K, N, stream, w, g, acc, K, N, R,
+                reinterpret_cast<__bf16 *>(wt), ldt, reinterpret_cast<__bf16 *>(wc), ldc, bias_w, bias_g, bias_acc,
+                bias_w ? bias_n : 0, step_dev_advance, tickets, plane_t, plane_c);
   return check_launch("momentum_matrix");
 }
 

@@ -2017,11 +2017,31 @@ def adam_step(w, g, m, v, lr, t, beta1=0.9, beta2=0.999, eps=1e-8, lr_dev=None, 
          _p(advance_tickets, torch.int32), _stream())
 
 
+def _seg_arrays(segments):
+    """(n, offsets, sizes) of ``segments`` = [(offset, numel), ...] as the C arrays the LARS entries read."""
+    n = len(segments)
+    offs = (C.c_int64 * n)(*[int(o) for o, _ in segments])
+    sizes = (C.c_int64 * n)(*[int(m) for _, m in segments])
+    return n, C.cast(offs, C.c_void_p), C.cast(sizes, C.c_void_p)
+
+
+def _copies(wt, wc, K, N, plane_t, plane_c, h2_scale=0.0):
+    """The operand copies a matrix rule writes: wt = W^T [N, >= K], wc = W [K, >= N] (either may be None), as one bf16 copy,
+    as three bf16 planes (plane_t / plane_c > 0, precision f32x3) or as two fp16 planes of W * h2_scale (precision f16x2)."""
+    tp, tld = (C.c_void_p(0), 0) if wt is None else _mat16(wt)
+    cp, cld = (C.c_void_p(0), 0) if wc is None else _mat16(wc)
+    planes = 2 if h2_scale else 3 if (plane_t or plane_c) else 1
+    if wt is not None and (wt.shape[0] < N or wt.shape[1] < ((planes - 1) * plane_t + K if planes > 1 else K)):
+        raise ValueError("wt must be at least [N, K] (planes: [N, 2 plane_t + K]; fp16 planes: [N, plane_t + K])")
+    if wc is not None and (wc.shape[0] < K or wc.shape[1] < ((planes - 1) * plane_c + N if planes > 1 else N)):
+        raise ValueError("wc must be at least [K, N] (planes: [K, 2 plane_c + N]; fp16 planes: [K, plane_c + N])")
+    return tp, tld, cp, cld, planes
+
+
 def adam_matrix_bf16(W, g, m, v, lr, t, wt=None, wc=None, beta1=0.9, beta2=0.999, eps=1e-8, lr_dev=None, t_dev=None,
                      bias=None, advance_tickets=None, plane_t=0, plane_c=0, h2_scale=0.0):
-    """Adam on the contiguous weight matrix W [K, N] (g, m, v alike) that also writes the bf16 operand
-    copies: wt = W^T as bf16 [N, >=K], wc = W as bf16 [K, >=N] (either may be None).  ``bias`` =
-    (b, gb, mb, vb): the layer's bias vector updated in the same launch; ``advance_tickets``
+    """Adam on the contiguous weight matrix W [K, N] (g, m, v alike) that also writes the operand copies (``_copies``).
+    ``bias`` = (b, gb, mb, vb): the layer's bias vector updated in the same launch; ``advance_tickets``
     (ops.new_tickets): also global_step += 1 on *t_dev by the last block."""
     if W.dim() != 2 or not W.is_contiguous() or W.dtype != torch.float32:
         raise ValueError("W must be a contiguous fp32 matrix")
@@ -2029,33 +2049,15 @@ def adam_matrix_bf16(W, g, m, v, lr, t, wt=None, wc=None, beta1=0.9, beta2=0.999
     for name, x in (("g", g), ("m", m), ("v", v)):
         if x.numel() != K * N or not x.is_contiguous() or x.dtype != torch.float32:
             raise ValueError("%s must be contiguous fp32 with W's size" % name)
-    tp, tld = (C.c_void_p(0), 0) if wt is None else _mat16(wt)
-    cp, cld = (C.c_void_p(0), 0) if wc is None else _mat16(wc)
-    planes = bool(plane_t or plane_c)                # the copies as three bf16 planes (precision f32x3)
-    np1 = 1 if h2_scale else 2                       # (h2_scale: as two fp16 planes of W * h2_scale, precision f16x2)
-    if wt is not None and (wt.shape[0] < N or wt.shape[1] < (np1 * plane_t + K if planes else K)):
-        raise ValueError("wt must be at least [N, K] (planes: [N, 2 plane_t + K])")
-    if wc is not None and (wc.shape[0] < K or wc.shape[1] < (np1 * plane_c + N if planes else N)):
-        raise ValueError("wc must be at least [K, N] (planes: [K, 2 plane_c + N])")
+    tp, tld, cp, cld, planes = _copies(wt, wc, K, N, plane_t, plane_c, h2_scale)
     b = bias if bias is not None else (None, None, None, None)
     if bias is not None and any(x.numel() != b[0].numel() or not x.is_contiguous() for x in b):
         raise ValueError("bias, its gradient and its moments must be contiguous vectors of one size")
-    if h2_scale:
-        call("cdml_adam_matrix_h2", _p(W), _p(g), _p(m), _p(v), K, N, lr, _p(lr_dev), beta1, beta2, eps,
-             0 if t is None else t, _p(t_dev, torch.int64), tp, tld, plane_t, cp, cld, plane_c, float(h2_scale), _p(b[0]), _p(b[1]),
-             _p(b[2]), _p(b[3]), 0 if bias is None else b[0].numel(), 0 if advance_tickets is None else 1,
-             _p(advance_tickets, torch.int32), _stream())
-        return
-    if planes:
-        call("cdml_adam_matrix_planes", _p(W), _p(g), _p(m), _p(v), K, N, lr, _p(lr_dev), beta1, beta2, eps,
-             0 if t is None else t, _p(t_dev, torch.int64), tp, tld, plane_t, cp, cld, plane_c, _p(b[0]), _p(b[1]),
-             _p(b[2]), _p(b[3]), 0 if bias is None else b[0].numel(), 0 if advance_tickets is None else 1,
-             _p(advance_tickets, torch.int32), _stream())
-        return
-    call("cdml_adam_matrix_bf16", _p(W), _p(g), _p(m), _p(v), K, N, lr, _p(lr_dev), beta1, beta2, eps,
-         0 if t is None else t, _p(t_dev, torch.int64), tp, tld, cp, cld, _p(b[0]), _p(b[1]), _p(b[2]), _p(b[3]),
-         0 if bias is None else b[0].numel(), 0 if advance_tickets is None else 1, _p(advance_tickets, torch.int32),
-         _stream())
+    copies = {1: (tp, tld, cp, cld), 2: (tp, tld, plane_t, cp, cld, plane_c, float(h2_scale)),
+              3: (tp, tld, plane_t, cp, cld, plane_c)}[planes]
+    call("cdml_adam_matrix_" + {1: "bf16", 2: "h2", 3: "planes"}[planes], _p(W), _p(g), _p(m), _p(v), K, N, lr, _p(lr_dev),
+         beta1, beta2, eps, 0 if t is None else t, _p(t_dev, torch.int64), *copies, _p(b[0]), _p(b[1]), _p(b[2]), _p(b[3]),
+         0 if bias is None else b[0].numel(), 0 if advance_tickets is None else 1, _p(advance_tickets, torch.int32), _stream())
 
 
 def table_adam_rows(table, row0, F, idx, grad_xhat, m_table, v_table, head, nxt, lr, t, beta1=0.9, beta2=0.999,
@@ -2101,36 +2103,15 @@ def lars_multi(w, g, acc, segments, lr, scratch, momentum=0.9, weight_decay=1e-4
                lr_dev=None, norms_out=None, step_dev=None, tickets=None):
     """LARS on every variable of the flat buffer in two launches: ``segments`` = [(offset, numel), ...]
     tiling w contiguously; step_dev (with tickets): also global_step += 1."""
-    n = len(segments)
-    offs = (C.c_int64 * n)(*[int(o) for o, _ in segments])
-    sizes = (C.c_int64 * n)(*[int(m) for _, m in segments])
-    call("cdml_lars_multi", _p(w), _p(g), _p(acc), C.cast(offs, C.c_void_p), C.cast(sizes, C.c_void_p), n, lr,
-         _p(lr_dev), momentum, weight_decay, eeta, eps, _p(scratch), _p(norms_out), _p(step_dev, torch.int64),
-         _p(tickets, torch.int32), _stream())
-
-
-def _seg_arrays(segments):
-    n = len(segments)
-    offs = (C.c_int64 * n)(*[int(o) for o, _ in segments])
-    sizes = (C.c_int64 * n)(*[int(m) for _, m in segments])
-    return n, offs, sizes
+    n, offs, sizes = _seg_arrays(segments)
+    call("cdml_lars_multi", _p(w), _p(g), _p(acc), offs, sizes, n, lr, _p(lr_dev), momentum, weight_decay, eeta, eps,
+         _p(scratch), _p(norms_out), _p(step_dev, torch.int64), _p(tickets, torch.int32), _stream())
 
 
 def lars_multi_norms(w, g, segments, scratch):
     """Launch 1 of LARS alone: the per-block |w|^2, |g|^2 partials of every segment (then ``lars_matrix`` per matrix)."""
     n, offs, sizes = _seg_arrays(segments)
-    call("cdml_lars_multi_norms", _p(w), _p(g), C.cast(offs, C.c_void_p), C.cast(sizes, C.c_void_p), n, _p(scratch), _stream())
-
-
-def _copies(wt, wc, K, N, plane_t, plane_c, h2_scale=0.0):
-    tp, tld = (C.c_void_p(0), 0) if wt is None else _mat16(wt)
-    cp, cld = (C.c_void_p(0), 0) if wc is None else _mat16(wc)
-    planes = 2 if h2_scale else 3 if (plane_t or plane_c) else 1
-    if wt is not None and (wt.shape[0] < N or wt.shape[1] < ((planes - 1) * plane_t + K if planes > 1 else K)):
-        raise ValueError("wt must be at least [N, K] (planes: [N, 2 plane_t + K]; fp16 planes: [N, plane_t + K])")
-    if wc is not None and (wc.shape[0] < K or wc.shape[1] < ((planes - 1) * plane_c + N if planes > 1 else N)):
-        raise ValueError("wc must be at least [K, N] (planes: [K, 2 plane_c + N]; fp16 planes: [K, plane_c + N])")
-    return tp, tld, cp, cld, planes
+    call("cdml_lars_multi_norms", _p(w), _p(g), offs, sizes, n, _p(scratch), _stream())
 
 
 def lars_matrix(w, g, acc, segments, seg_matrix, seg_bias, K, N, lr, scratch, wt=None, wc=None, plane_t=0, plane_c=0,
@@ -2138,19 +2119,13 @@ def lars_matrix(w, g, acc, segments, seg_matrix, seg_bias, K, N, lr, scratch, wt
                 tickets=None, h2_scale=0.0):
     """LARS on the K x N weight matrix in segment ``seg_matrix`` of the flat buffers (+ the bias vector in segment
     ``seg_bias``, or None), after ``lars_multi_norms`` on the same segments; also writes the operand copies wt = W^T,
-    wc = W as bf16 (plane_t / plane_c > 0: as three bf16 planes).  step_dev (with tickets): also global_step += 1."""
+    wc = W (``_copies``).  step_dev (with tickets): also global_step += 1."""
     n, offs, sizes = _seg_arrays(segments)
     tp, tld, cp, cld, planes = _copies(wt, wc, K, N, plane_t, plane_c, h2_scale)
-    if h2_scale:                                     # the copies as two fp16 planes of W * h2_scale (precision f16x2)
-        call("cdml_lars_matrix_h2", _p(w), _p(g), _p(acc), C.cast(offs, C.c_void_p), C.cast(sizes, C.c_void_p), n, seg_matrix,
-             -1 if seg_bias is None else seg_bias, K, N, lr, _p(lr_dev), momentum, weight_decay, eeta, eps, _p(scratch),
-             _p(norms_out), tp, tld, plane_t, cp, cld, plane_c, float(h2_scale), _p(step_dev, torch.int64),
-             _p(tickets, torch.int32), _stream())
-        return
-    call("cdml_lars_matrix", _p(w), _p(g), _p(acc), C.cast(offs, C.c_void_p), C.cast(sizes, C.c_void_p), n, seg_matrix,
+    call("cdml_lars_matrix_h2" if h2_scale else "cdml_lars_matrix", _p(w), _p(g), _p(acc), offs, sizes, n, seg_matrix,
          -1 if seg_bias is None else seg_bias, K, N, lr, _p(lr_dev), momentum, weight_decay, eeta, eps, _p(scratch),
-         _p(norms_out), tp, tld, plane_t, cp, cld, plane_c, planes, _p(step_dev, torch.int64), _p(tickets, torch.int32),
-         _stream())
+         _p(norms_out), tp, tld, plane_t, cp, cld, plane_c, float(h2_scale) if h2_scale else planes,
+         _p(step_dev, torch.int64), _p(tickets, torch.int32), _stream())
 
 
 def momentum_matrix(W, g, acc, lr, wt=None, wc=None, plane_t=0, plane_c=0, momentum=0.9, use_nesterov=True, lr_dev=None,
@@ -2162,11 +2137,7 @@ def momentum_matrix(W, g, acc, lr, wt=None, wc=None, plane_t=0, plane_c=0, momen
     K, N = W.shape
     tp, tld, cp, cld, planes = _copies(wt, wc, K, N, plane_t, plane_c, h2_scale)
     b = bias if bias is not None else (None, None, None)
-    if h2_scale:
-        call("cdml_momentum_matrix_h2", _p(W), _p(g), _p(acc), K, N, lr, _p(lr_dev), momentum, 1 if use_nesterov else 0, tp, tld,
-             plane_t, cp, cld, plane_c, float(h2_scale), _p(b[0]), _p(b[1]), _p(b[2]), 0 if bias is None else b[0].numel(),
-             _p(step_dev, torch.int64), _p(tickets, torch.int32), _stream())
-        return
-    call("cdml_momentum_matrix", _p(W), _p(g), _p(acc), K, N, lr, _p(lr_dev), momentum, 1 if use_nesterov else 0, tp, tld,
-         plane_t, cp, cld, plane_c, planes, _p(b[0]), _p(b[1]), _p(b[2]), 0 if bias is None else b[0].numel(),
-         _p(step_dev, torch.int64), _p(tickets, torch.int32), _stream())
+    call("cdml_momentum_matrix_h2" if h2_scale else "cdml_momentum_matrix", _p(W), _p(g), _p(acc), K, N, lr, _p(lr_dev),
+         momentum, 1 if use_nesterov else 0, tp, tld, plane_t, cp, cld, plane_c, float(h2_scale) if h2_scale else planes,
+         _p(b[0]), _p(b[1]), _p(b[2]), 0 if bias is None else b[0].numel(), _p(step_dev, torch.int64),
+         _p(tickets, torch.int32), _stream())

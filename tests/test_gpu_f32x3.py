@@ -342,13 +342,13 @@ def test_error_at_the_five_production_shapes_against_the_fp32_mfma_kernels():
 
 
 @pytest.mark.parametrize("planes", [3, 1])
-@pytest.mark.parametrize("rule", ["lars", "momentum"])
+@pytest.mark.parametrize("rule", ["lars", "momentum", "adam"])
 def test_lars_and_momentum_write_the_operand_copies_with_the_update(rule, planes):
-    """The reference's own optimizer (LARS, train.py:354) and Nesterov momentum (train.py:115-116) on the weight
-    matrices with the GEMMs' operand copies written by the update itself (cdml_lars_matrix / cdml_momentum_matrix):
-    weights and slots bit-equal to the flat kernels (cdml_lars_multi / cdml_momentum_step), the three planes summing to
-    the new fp32 weights exactly (planes = 3), the bf16 copies their rounding (planes = 1), the step counter advanced
-    once by the last launch."""
+    """The reference's own optimizer (LARS, train.py:354), Nesterov momentum (train.py:115-116) and Adam (train.py:82) on
+    the weight matrices with the GEMMs' operand copies written by the update itself (cdml_lars_matrix /
+    cdml_momentum_matrix / cdml_adam_matrix_bf16 | _planes): weights and slots bit-equal to the flat kernels
+    (cdml_lars_multi / cdml_momentum_step / cdml_adam_step), the three planes summing to the new fp32 weights exactly
+    (planes = 3), the bf16 copies their rounding (planes = 1), the step counter advanced once by the last launch."""
     torch.manual_seed(11)
     dev = _dev()
     Fp, Hp, Dp = 256, 512, 256
@@ -359,19 +359,22 @@ def test_lars_and_momentum_write_the_operand_copies_with_the_update(rule, planes
         o += n
     w0 = torch.randn(o, device=dev) * 0.05
     g = torch.randn(o, device=dev) * 1e-3
-    acc0 = torch.randn(o, device=dev) * 1e-4
+    acc0 = torch.randn(o, device=dev) * 1e-4             # (Adam: the first moment)
+    v0 = torch.rand(o, device=dev) * 1e-6                # Adam's second moment
     lr_dev = torch.full((1,), 0.5, device=dev)
     # flat kernels
-    wa, acca = w0.clone(), acc0.clone()
+    wa, acca, va = w0.clone(), acc0.clone(), v0.clone()
     step_a = torch.zeros(1, dtype=torch.int64, device=dev)
     scratch = torch.zeros(max(ops.lars_scratch_floats(), ops.lars_multi_scratch_floats()), device=dev)
     if rule == "lars":
         ops.lars_multi(wa, g, acca, segs, 0.0, scratch, lr_dev=lr_dev, step_dev=step_a, tickets=ops.new_tickets(dev))
+    elif rule == "adam":
+        ops.adam_step(wa, g, acca, va, 0.0, 1, lr_dev=lr_dev, t_dev=step_a, advance_tickets=ops.new_tickets(dev))
     else:
         ops.momentum_step(wa, g, acca, 0.0, 0.9, True, lr_dev=lr_dev)
         ops.step_advance(step_a)
     # matrix kernels
-    wb, accb = w0.clone(), acc0.clone()
+    wb, accb, vb = w0.clone(), acc0.clone(), v0.clone()
     step_b = torch.zeros(1, dtype=torch.int64, device=dev)
     tick = ops.new_tickets(dev)
     mult = 3 if planes == 3 else 1
@@ -385,6 +388,13 @@ def test_lars_and_momentum_write_the_operand_copies_with_the_update(rule, planes
         ops.lars_matrix(wb, g, accb, segs, 0, 1, Fp, Hp, 0.0, scratch2, wt=W1T, plane_t=pt1, lr_dev=lr_dev)
         ops.lars_matrix(wb, g, accb, segs, 2, 3, Hp, Dp, 0.0, scratch2, wt=W2T, wc=W2, plane_t=pt2, plane_c=pc2, lr_dev=lr_dev,
                         step_dev=step_b, tickets=tick)
+    elif rule == "adam":
+        v = lambda t, i, r, c: t[segs[i][0]:segs[i][0] + r * c].view(r, c)
+        b = lambda i: tuple(t[segs[i][0]:segs[i][0] + segs[i][1]] for t in (wb, g, accb, vb))
+        ops.adam_matrix_bf16(v(wb, 0, Fp, Hp), v(g, 0, Fp, Hp), v(accb, 0, Fp, Hp), v(vb, 0, Fp, Hp), 0.0, 1, wt=W1T, plane_t=pt1,
+                             lr_dev=lr_dev, t_dev=step_b, bias=b(1))
+        ops.adam_matrix_bf16(v(wb, 2, Hp, Dp), v(g, 2, Hp, Dp), v(accb, 2, Hp, Dp), v(vb, 2, Hp, Dp), 0.0, 1, wt=W2T, wc=W2,
+                             plane_t=pt2, plane_c=pc2, lr_dev=lr_dev, t_dev=step_b, bias=b(3), advance_tickets=tick)
     else:
         v = lambda t, i, r, c: t[segs[i][0]:segs[i][0] + r * c].view(r, c)
         b = lambda i: tuple(t[segs[i][0]:segs[i][0] + segs[i][1]] for t in (wb, g, accb))
@@ -393,7 +403,8 @@ def test_lars_and_momentum_write_the_operand_copies_with_the_update(rule, planes
         ops.momentum_matrix(v(wb, 2, Hp, Dp), v(g, 2, Hp, Dp), v(accb, 2, Hp, Dp), 0.0, wt=W2T, wc=W2, plane_t=pt2, plane_c=pc2,
                             lr_dev=lr_dev, bias=b(3), step_dev=step_b, tickets=tick)
     torch.cuda.synchronize()
-    assert torch.equal(wa, wb) and torch.equal(acca, accb), "matrix form differs from the flat kernel"
+    assert torch.equal(wa, wb) and torch.equal(acca, accb) and torch.equal(va, vb), "matrix form differs from the flat kernel"
+    assert (rule == "adam") == (not torch.equal(vb, v0))
     assert not torch.equal(wb, w0)
     assert int(step_a.item()) == 1 and int(step_b.item()) == 1
     W1 = wb[:Fp * Hp].view(Fp, Hp)
