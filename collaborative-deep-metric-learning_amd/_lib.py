@@ -280,6 +280,14 @@ SIGNATURES_F8 = {
     "cdml_quantize_rows_f8_f16": (_i, [_p, _i64, _i64, _i, _p, _i64, _i64, _p, _p]),
 }
 
+# name -> (restype, argtypes); must list every symbol include/cdml_ivf.h declares (the IVF index of the kNN: Lloyd's centroid
+# update, the grouped score product over probed lists, the merge over ragged score segments)
+SIGNATURES_IVF = {
+    "cdml_ivf_centroid_sums": (_i, [_p, _i64, _p, _p, _i, _i, _p, _i64, _p]),
+    "cdml_ivf_scan_f32": (_i, [_p, _i64, _i, _p, _p, _p, _p, _i64, _p, _i, _p, _i, _p, _p]),
+    "cdml_ivf_merge": (_i, [_p, _p, _p, _p, _i, _i, _p, _p, _p, _p, _i, _p, _p, _p]),
+}
+
 _lib = None
 
 
@@ -300,7 +308,7 @@ def load_library():
     lib = C.CDLL(path)
     for name, (res, args) in (list(SIGNATURES.items()) + list(SIGNATURES_MIXED.items()) + list(SIGNATURES_DP.items())
                                + list(SIGNATURES_BF16.items()) + list(SIGNATURES_HARDNEG.items()) + list(SIGNATURES_WIDE.items())
-                               + list(SIGNATURES_NEGW.items()) + list(SIGNATURES_F8.items())):
+                               + list(SIGNATURES_NEGW.items()) + list(SIGNATURES_F8.items()) + list(SIGNATURES_IVF.items())):
         fn = getattr(lib, name)          # AttributeError if the ABI lost a symbol
         fn.restype = res
         fn.argtypes = args

@@ -63,14 +63,20 @@ def filter_lists(I, k, skip_top=0, pairs=None):
     return out
 
 
-def mine_lists(embeddings, k, skip_top=0, pairs=None, device="cuda:0", precision="f32x3"):
+def mine_lists(embeddings, k, skip_top=0, pairs=None, device="cuda:0", precision="f32x3", nlist=0, nprobe=0, ivf_iters=10,
+               ivf_seed=0):
     """Candidate negatives of every row: int32 [n, L] device tensor, L = k rounded up to a multiple of 4.
 
     A self-kNN over ``embeddings`` ([n, D] ndarray or tensor; l2-normalised first, as ``knn.calc_knn`` does) with
     k + skip_top + 1 neighbours (``knn.knn_search``: exact, ties by id), then ``filter_lists``: the row itself, the
     ``skip_top`` nearest and -- with ``pairs`` (int [P, 2]) -- every known co-watch partner of the row are dropped; what
-    remains is left-packed, nearest first, and padded with -1."""
-    k, skip_top = int(k), int(skip_top)
+    remains is left-packed, nearest first, and padded with -1.
+    ``nlist`` > 0: the neighbours come from an IVF index over the embeddings instead (``knn.IVFIndex.build(e, nlist,
+    iters=ivf_iters, seed=ivf_seed)`` and its ``search(e, k + skip_top + 1, nprobe)``: approximate -- a neighbour outside a
+    row's ``nprobe`` nearest lists is missed -- and sub-linear in the catalogue); the filter is the same."""
+    k, skip_top, nlist, nprobe = int(k), int(skip_top), int(nlist), int(nprobe)
+    if nlist < 0 or (nlist == 0 and nprobe != 0):
+        raise ValueError("mine_lists takes nlist >= 0, and nprobe only with nlist > 0 (got nlist = %d, nprobe = %d)" % (nlist, nprobe))
     if k < 1 or skip_top < 0:
         raise ValueError("mine_lists needs k >= 1 and skip_top >= 0, got %d and %d" % (k, skip_top))
     if list_width(k) > 1024:
@@ -78,7 +84,11 @@ def mine_lists(embeddings, k, skip_top=0, pairs=None, device="cuda:0", precision
     dev = torch.device(device)
     e = embeddings if torch.is_tensor(embeddings) else torch.as_tensor(np.asarray(embeddings, dtype=np.float32))
     e = e.to(device=dev, dtype=torch.float32)
-    _, I = knn.knn_search(e, e, k + skip_top + 1, device=dev, precision=precision)
+    if nlist > 0:
+        index = knn.IVFIndex.build(e, nlist, iters=ivf_iters, seed=ivf_seed, device=dev, precision=precision)
+        _, I = index.search(e, k + skip_top + 1, nprobe)
+    else:
+        _, I = knn.knn_search(e, e, k + skip_top + 1, device=dev, precision=precision)
     if pairs is not None and not torch.is_tensor(pairs):
         pairs = torch.as_tensor(np.asarray(pairs))
     return filter_lists(I, k, skip_top, pairs)

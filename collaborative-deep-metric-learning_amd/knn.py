@@ -335,3 +335,296 @@ def export(embeddings, features, decode_map, out_dir, doc_location=343455, neare
     with open(os.path.join(out_dir, "decode_map.json"), "w") as f:
         json.dump({str(k): v for k, v in dm.items()}, f)
     return D, I_desim
+
+
+# ----------------------------------------------------------------------------------------------------------------------------
+# The approximate path: an inverted-file (IVF-Flat) index (include/cdml_ivf.h, csrc/ivf.hip).  k-means
+# cuts the catalogue into nlist lists; a query is scored only against the rows of its nprobe nearest lists.  ``calc_knn``
+# stays exact and keeps ignoring its HNSW arguments.
+
+IVF_TILE = 128              # slots x rows per work item of the grouped score product (csrc/ivf.hip kTile)
+IVF_SCORE_BYTES = 1 << 30   # default budget of a query chunk's ragged score buffer: 1 GiB, or ...
+IVF_SCORE_SLOTS = 512       # ... IVF_SCORE_SLOTS score rows per list and chunk (4 B x 512 x n_listed), whichever is more: a chunk of
+#                             B score bytes holds B / (4 n_listed) slots per list whatever nlist and nprobe are, and a 128-slot tile of
+#                             the scan is as full as that allows (1 GiB at 10 M rows: 27 slots, four fifths of the product padding)
+
+
+def ivf_plan_chunks(costs, score_bytes, max_queries=None):
+    """Query chunks [(q0, q1), ...] in order, each chunk's scores within ``score_bytes``: ``costs[q]`` = the score FLOATS of
+    query q (the padded lengths of its probed lists).  Every query is in exactly one chunk; a chunk holds at most
+    ``max_queries`` queries; a query whose own scores exceed the budget is refused.  Pure host arithmetic."""
+    c = np.asarray(costs, dtype=np.int64).reshape(-1)
+    budget = int(score_bytes) // 4
+    if c.size and int(c.max()) > budget:
+        q = int(c.argmax())
+        raise ValueError("score_bytes = %d is less than the %d bytes of query %d's own scores: raise score_bytes or lower nprobe"
+                         % (int(score_bytes), 4 * int(c[q]), q))
+    cum = np.concatenate([np.zeros(1, dtype=np.int64), np.cumsum(c)])
+    chunks, q0, n = [], 0, int(c.size)
+    while q0 < n:
+        q1 = int(np.searchsorted(cum, cum[q0] + budget, side="right")) - 1    # the last q1 with cum[q1] - cum[q0] <= budget
+        if max_queries is not None:
+            q1 = min(q1, q0 + int(max_queries))
+        q1 = min(max(q1, q0 + 1), n)
+        chunks.append((q0, q1))
+        q0 = q1
+    return chunks
+
+
+def ivf_tables(probe, list_len):
+    """The slot, tile and offset tables of one query chunk (plumbing: torch calls on ``probe``'s device, ONE host read).
+    probe int32 [m, nprobe] (-1 = no list); list_len int64 [nlist].  A slot is one (query, probed list) pair; slots are
+    sorted by list (stably: by query inside a list).  Returns a dict: n_slots, n_floats, n_tiles (ints), slot_query int32
+    [n_slots], slot_start int32 [nlist + 1], slot_off int64 [n_slots], slot_of int32 [m, nprobe] (-1 for a -1 probe), tiles
+    int32 [n_tiles, 4] = (list, first slot in the list's block, first row in the list, 0), ordered by list."""
+    m, nprobe = probe.shape
+    nlist = list_len.numel()
+    dev = probe.device
+    flat = probe.reshape(-1).to(torch.int64)
+    key = torch.where(flat >= 0, flat, torch.full_like(flat, nlist))
+    skey, order = torch.sort(key, stable=True)
+    cnt = torch.bincount(key, minlength=nlist + 1)[:nlist]
+    slot_start = torch.zeros(nlist + 1, dtype=torch.int64, device=dev)
+    slot_start[1:] = torch.cumsum(cnt, 0)
+    ld = (list_len + 3) // 4 * 4
+    blk = cnt * ld                                            # floats of list c's score block [cnt][ld]
+    blk_off = torch.cumsum(blk, 0) - blk
+    tn = (list_len + IVF_TILE - 1) // IVF_TILE
+    nt = (cnt + IVF_TILE - 1) // IVF_TILE * tn
+    tile_start = torch.cumsum(nt, 0) - nt
+    n_slots, n_floats, n_tiles = torch.stack([slot_start[-1], blk.sum(), nt.sum()]).tolist()      # the host read
+    slot_list = skey[:n_slots]
+    slot_of = torch.full((m * nprobe,), -1, dtype=torch.int32, device=dev)
+    slot_of[order[:n_slots]] = torch.arange(n_slots, dtype=torch.int32, device=dev)
+    slot_off = blk_off[slot_list] + (torch.arange(n_slots, device=dev) - slot_start[slot_list]) * ld[slot_list]
+    tc = torch.repeat_interleave(torch.arange(nlist, device=dev), nt, output_size=n_tiles)
+    loc = torch.arange(n_tiles, device=dev) - tile_start[tc]
+    tnc = tn[tc].clamp(min=1)
+    tiles = torch.stack([tc, loc // tnc * IVF_TILE, loc % tnc * IVF_TILE, torch.zeros_like(tc)], 1).to(torch.int32).contiguous()
+    return {"n_slots": n_slots, "n_floats": n_floats, "n_tiles": n_tiles,
+            "slot_query": (order[:n_slots] // nprobe).to(torch.int32), "slot_start": slot_start.to(torch.int32),
+            "slot_off": slot_off, "slot_of": slot_of.view(m, nprobe), "tiles": tiles}
+
+
+class IVFIndex:
+    """IVF-Flat index over a catalogue (the contract: include/cdml_ivf.h).  ``build`` runs Lloyd's k-means on the device and
+    ``from_assignment`` takes centroids and an assignment as they are; ``search`` returns EXACTLY the k best listed rows of
+    every query's ``nprobe`` nearest lists under the key (distance, id).  Attributes (device tensors): ``centroids`` fp32
+    [nlist, D], ``assign`` int64 [n] (-1 = unlisted: a row with a non-finite coordinate), ``ids`` int32 [n_listed] sorted by
+    (assign, id), ``list_start`` int32 [nlist + 1], ``rows`` fp32 [n_listed, Dp] and ``r_sq`` [n_listed] in that order;
+    ``init_rows`` and ``train_ids`` (int64, CPU, sorted: the rows the centroids started from and the rows k-means ran on),
+    ``objective`` (float64, CPU: one entry per Lloyd iteration), ``n_unlisted``."""
+
+    def __init__(self):
+        raise TypeError("use IVFIndex.build, IVFIndex.from_assignment or IVFIndex.load_state_dict")
+
+    # ---- construction ----
+    @staticmethod
+    def _as_tensor(a):
+        t = a if torch.is_tensor(a) else torch.as_tensor(np.asarray(a, dtype=np.float32))
+        if t.dim() != 2 or t.shape[0] < 1 or t.shape[1] < 1:
+            raise ValueError("the catalogue must be a non-empty [n, D] matrix")
+        return t
+
+    @staticmethod
+    def _prepared(t, device, l2_norm):
+        """[n, D] -> the fp32 device matrix [n, Dp] the index works on: zero-padded to Dp % 32 == 0, l2-normalised if asked."""
+        X = _device_matrix(t, device, 1, 32)
+        if l2_norm:
+            ops.l2norm_fwd(X, X.shape[1], X)
+        return X
+
+    @classmethod
+    def _blank(cls, nlist, D, l2_norm, device, precision):
+        self = object.__new__(cls)
+        self.nlist, self.dim, self.l2_norm, self.device, self.precision = int(nlist), int(D), bool(l2_norm), torch.device(device), precision
+        self.init_rows = self.train_ids = torch.empty(0, dtype=torch.int64)
+        self.objective = torch.empty(0, dtype=torch.float64)
+        return self
+
+    def _set_lists(self, X, C, assign):
+        """the cluster-major lists of (X, assign); rows with a non-finite coordinate are unlisted whatever ``assign`` says"""
+        n, Dp = X.shape
+        a = torch.where(torch.isfinite(X).all(1), assign.to(device=X.device, dtype=torch.int64), torch.full((n,), -1, dtype=torch.int64, device=X.device))
+        listed = a >= 0
+        key = torch.where(listed, a, torch.full_like(a, self.nlist))
+        order = torch.argsort(key, stable=True)               # ids ascend inside a list
+        cnt = torch.bincount(key, minlength=self.nlist + 1)
+        n_listed = n - int(cnt[self.nlist])
+        if n_listed < 1:
+            raise ValueError("assign lists no finite row")
+        start = torch.zeros(self.nlist + 1, dtype=torch.int64, device=X.device)
+        start[1:] = torch.cumsum(cnt[:self.nlist], 0)
+        self.assign = a
+        self.ids = order[:n_listed].to(torch.int32)
+        self.list_start = start.to(torch.int32)
+        self.list_len = cnt[:self.nlist].contiguous()
+        self.rows = X.index_select(0, order[:n_listed])
+        self.r_sq = torch.zeros(n_listed, dtype=torch.float32, device=X.device)
+        ops.row_sqnorm(self.rows, Dp, self.r_sq)
+        self._C = C
+        self.centroids = C[:, :self.dim]
+        self.n_rows, self.n_listed, self.n_unlisted = n, n_listed, n - n_listed
+        return self
+
+    @classmethod
+    def from_assignment(cls, base, centroids, assign, l2_norm=True, device="cuda:0", precision="f32x3"):
+        """The index of given ``centroids`` ([nlist, D]) and an arbitrary ``assign`` (int [n], values in [-1, nlist); -1 =
+        unlisted): the search contract does not need the assignment to be the nearest centroid."""
+        t = cls._as_tensor(base)
+        c = centroids if torch.is_tensor(centroids) else torch.as_tensor(np.asarray(centroids, dtype=np.float32))
+        a = assign if torch.is_tensor(assign) else torch.as_tensor(np.asarray(assign))
+        if c.dim() != 2 or c.shape[0] < 1 or c.shape[1] != t.shape[1]:
+            raise ValueError("centroid / catalogue dimension mismatch: centroids must be [nlist >= 1, D = %d]" % t.shape[1])
+        if a.dim() != 1 or a.shape[0] != t.shape[0] or a.is_floating_point():
+            raise ValueError("assign must be an integer vector with one entry per catalogue row (%d)" % t.shape[0])
+        nlist = c.shape[0]
+        if a.numel() and (int(a.min()) < -1 or int(a.max()) >= nlist):
+            raise ValueError("assign must lie in [-1, nlist = %d)" % nlist)
+        self = cls._blank(nlist, t.shape[1], l2_norm, device, precision)
+        X = cls._prepared(t, self.device, l2_norm)
+        return self._set_lists(X, _device_matrix(c, self.device, 1, 32), a)
+
+    @classmethod
+    def build(cls, base, nlist, iters=10, seed=0, train_rows=None, l2_norm=True, device="cuda:0", precision="f32x3"):
+        """Lloyd's k-means, deterministic (include/cdml_ivf.h BUILD).  ``precision`` is that of the coarse ``knn_search`` calls
+        (every assignment step, and ``probes``)."""
+        t = cls._as_tensor(base)
+        nlist, iters = int(nlist), int(iters)
+        n_finite = int(torch.isfinite(t).all(1).sum())
+        if not 1 <= nlist <= n_finite:
+            raise ValueError("nlist must be in [1, the number of finite rows = %d], got %d" % (n_finite, nlist))
+        if iters < 0:
+            raise ValueError("iters must be >= 0, got %d" % iters)
+        n_train = min(n_finite, 256 * nlist) if train_rows is None else int(train_rows)
+        if not nlist <= n_train <= n_finite:
+            raise ValueError("train_rows must be in [nlist = %d, the number of finite rows = %d], got %d" % (nlist, n_finite, n_train))
+        self = cls._blank(nlist, t.shape[1], l2_norm, device, precision)
+        dev = self.device
+        X = cls._prepared(t, dev, l2_norm)
+        n, Dp = X.shape
+        finite = torch.isfinite(X).all(1)
+        fin = torch.nonzero(finite).flatten().cpu()
+        if fin.numel() != n_finite:
+            raise ValueError("rows became non-finite under l2 normalisation (%d of %d finite rows left)" % (fin.numel(), n_finite))
+        g = torch.Generator()
+        g.manual_seed(int(seed))
+        perm = torch.randperm(n_finite, generator=g)
+        init_rows = torch.sort(fin[perm[:nlist]]).values
+        train_ids = torch.sort(fin[perm[:n_train]]).values
+        Xt = X if n_train == n else X.index_select(0, train_ids.to(dev))
+        C = X.index_select(0, init_rows.to(dev)).contiguous()
+        objective = []
+        for _ in range(iters):
+            Dt, It = knn_search(C, Xt, 1, l2_norm=False, device=dev, precision=precision)
+            a = It[:, 0]
+            ok = a >= 0
+            objective.append(torch.where(ok, Dt[:, 0], torch.zeros_like(Dt[:, 0])).double().sum())
+            key = torch.where(ok, a, torch.full_like(a, nlist))
+            order = torch.argsort(key, stable=True).to(torch.int32)
+            start = torch.zeros(nlist + 1, dtype=torch.int64, device=dev)
+            start[1:] = torch.cumsum(torch.bincount(key, minlength=nlist + 1)[:nlist], 0)
+            ops.ivf_centroid_sums(Xt, order, start.to(torch.int32), C, Dp)
+        _, Ia = knn_search(C, X, 1, l2_norm=False, device=dev, precision=precision)
+        self._set_lists(X, C, Ia[:, 0])
+        self.init_rows, self.train_ids = init_rows, train_ids
+        self.objective = torch.stack(objective).cpu() if objective else torch.empty(0, dtype=torch.float64)
+        return self
+
+    def state_dict(self):
+        """centroids + assign + the flags (CPU tensors); the lists are re-derived from the catalogue on load, bit for bit."""
+        return {"centroids": self.centroids.detach().cpu().clone(), "assign": self.assign.cpu().clone(), "l2_norm": self.l2_norm,
+                "precision": self.precision, "init_rows": self.init_rows.clone(), "objective": self.objective.clone()}
+
+    @classmethod
+    def load_state_dict(cls, state, base, device="cuda:0"):
+        """The index of ``state_dict()`` over the same catalogue ``base``."""
+        self = cls.from_assignment(base, state["centroids"], state["assign"], l2_norm=state["l2_norm"], device=device,
+                                   precision=state["precision"])
+        self.init_rows, self.objective = state["init_rows"].clone(), state["objective"].clone()
+        return self
+
+    # ---- search ----
+    def _check_queries(self, queries, nprobe, k=None):
+        cap = ops.knn_list_capacity()
+        if k is not None and not 1 <= int(k) <= cap:
+            raise ValueError("k must be in [1, %d], got %d" % (cap, int(k)))
+        if not 1 <= int(nprobe) <= min(self.nlist, cap):
+            raise ValueError("nprobe must be in [1, min(nlist = %d, %d)], got %d" % (self.nlist, cap, int(nprobe)))
+        shape = tuple(queries.shape)
+        if len(shape) != 2 or shape[1] != self.dim:
+            raise ValueError("query / index dimension mismatch: queries must be [nq, D = %d], got %s" % (self.dim, shape))
+
+    def _probes(self, Q, nprobe):
+        _, I = knn_search(self._C, Q, int(nprobe), l2_norm=False, device=self.device, precision=self.precision)
+        return I
+
+    def probes(self, queries, nprobe):
+        """int64 [nq, nprobe]: every query's nprobe nearest centroids, nearest first (the exact search; -1 throughout for a
+        non-finite query)."""
+        self._check_queries(queries, nprobe)
+        t = queries if torch.is_tensor(queries) else torch.as_tensor(np.asarray(queries, dtype=np.float32))
+        return self._probes(self._prepared(t, self.device, self.l2_norm), nprobe)
+
+    def scanned_share(self, probe):
+        """The mean share of the listed rows that a query of ``probe`` ([nq, nprobe] list ids, -1 = none) scores."""
+        p = probe.to(device=self.device, dtype=torch.int64)
+        rows = torch.where(p >= 0, self.list_len[p.clamp(min=0)], torch.zeros_like(p)).sum(1)
+        return float(rows.double().mean()) / self.n_listed
+
+    def default_score_bytes(self):
+        """max(1 GiB, 4 B x 512 x n_listed): the default ``score_bytes`` of ``search``"""
+        return max(IVF_SCORE_BYTES, 4 * IVF_SCORE_SLOTS * self.n_listed)
+
+    def search(self, queries, k, nprobe, score_bytes=None, stats=None, probe=None):
+        """(D [nq, k] fp32 squared L2 ascending, I [nq, k] int64; +inf / -1 where fewer than k rows were probed), device
+        tensors shaped and typed like ``knn_search``'s.  Queries go in chunks whose ragged score buffer fits ``score_bytes``
+        (default ``default_score_bytes()``: 1 GiB, or 2 KiB per listed row where that is more -- 20 GB at 10 M rows;
+        ``ivf_plan_chunks``); the result does not depend on the chunking.  ``stats`` (a dict, optional)
+        receives the chunk list, the tile count and the score floats.  ``probe`` (int [nq, nprobe], values in [-1, nlist),
+        a query's lists distinct; default: ``probes(queries, nprobe)``): the lists to scan, as given."""
+        self._check_queries(queries, nprobe, k)
+        k, nprobe = int(k), int(nprobe)
+        if probe is not None:
+            probe = torch.as_tensor(probe)
+            if tuple(probe.shape) != (queries.shape[0], nprobe) or probe.is_floating_point():
+                raise ValueError("probe must be an integer [nq = %d, nprobe = %d] table" % (queries.shape[0], nprobe))
+            if probe.numel() and (int(probe.min()) < -1 or int(probe.max()) >= self.nlist):
+                raise ValueError("probe ids must lie in [-1, nlist = %d)" % self.nlist)
+        t = queries if torch.is_tensor(queries) else torch.as_tensor(np.asarray(queries, dtype=np.float32))
+        dev = self.device
+        Q = self._prepared(t, dev, self.l2_norm)
+        nq, Dp = Q.shape
+        cap = ops.knn_list_capacity()
+        best_d = torch.empty((nq, cap), dtype=torch.float32, device=dev)
+        best_i = torch.empty((nq, cap), dtype=torch.int32, device=dev)
+        if nq:
+            q_sq = torch.zeros(nq, dtype=torch.float32, device=dev)
+            ops.row_sqnorm(Q, Dp, q_sq)
+            probe = (self._probes(Q, nprobe) if probe is None else probe.to(dev)).to(torch.int32).contiguous()
+            ld = (self.list_len + 3) // 4 * 4
+            p = probe.to(torch.int64)
+            costs = torch.where(p >= 0, ld[p.clamp(min=0)], torch.zeros_like(p)).sum(1).cpu().numpy()
+            chunks = ivf_plan_chunks(costs, self.default_score_bytes() if score_bytes is None else score_bytes,
+                                     max_queries=(2 ** 31 - 1) // nprobe)
+            n_tiles = n_floats = 0
+            for q0, q1 in chunks:
+                pc = probe[q0:q1].contiguous()
+                tb = ivf_tables(pc, self.list_len)
+                n_tiles += tb["n_tiles"]
+                n_floats += tb["n_floats"]
+                if tb["n_slots"] == 0:                        # nothing probed (non-finite queries only)
+                    best_d[q0:q1] = float("inf")
+                    best_i[q0:q1] = 0x7fffffff
+                    continue
+                scores = torch.empty(max(tb["n_floats"], 4), dtype=torch.float32, device=dev)
+                if tb["n_tiles"]:
+                    ops.ivf_scan_f32(Q[q0:q1], tb["slot_query"], tb["slot_start"], tb["slot_off"], self.rows, self.list_start,
+                                     tb["tiles"], scores)
+                ops.ivf_merge(scores, tb["slot_off"], tb["slot_of"], pc, self.list_start, self.ids, self.r_sq, q_sq[q0:q1], k,
+                              best_d[q0:q1], best_i[q0:q1])
+            if stats is not None:
+                stats.update(chunks=chunks, n_tiles=n_tiles, n_floats=n_floats, probe=probe)
+        I = best_i[:, :k].to(torch.int64)
+        I[I == 0x7fffffff] = -1
+        return best_d[:, :k].contiguous(), I

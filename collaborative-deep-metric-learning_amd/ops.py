@@ -1672,6 +1672,57 @@ def knn_merge_list(cand, cnt, cap, nq, k, best_d, best_i, overflow):
          _p(overflow, torch.int32), _stream())
 
 
+# ---------------------------------------- IVF index of the kNN (include/cdml_ivf.h) ------
+def _vec(t, dtype, n, what):
+    if t.dtype != dtype or not t.is_contiguous() or t.numel() < n:
+        raise ValueError("%s must be a contiguous %s tensor of at least %d elements" % (what, dtype, n))
+    return _p(t, dtype)
+
+
+def ivf_centroid_sums(x, order, list_start, centroids, D):
+    """Every non-empty list's column means over columns [0, D): centroids[c] = mean of x[order[list_start[c]:list_start[c+1]]];
+    an empty list's row is not written.  order: int32 row ids of x sorted by (list, id); list_start: int32 [nlist + 1]."""
+    xp, xld = _mat(x)
+    cp, cld = _mat(centroids)
+    nlist = centroids.shape[0]
+    call("cdml_ivf_centroid_sums", xp, xld, _vec(order, torch.int32, 0, "order"),
+         _vec(list_start, torch.int32, nlist + 1, "list_start"), nlist, D, cp, cld, _stream())
+    return centroids
+
+
+def ivf_scan_f32(Q, slot_query, slot_start, slot_off, rows, list_start, tiles, scores):
+    """The grouped score product over probed lists: for every tile (list c, slot tile, row tile) of ``tiles`` (int32
+    [n_tiles, 4]) the inner products of the queries Q[slot_query[...]] with the list's rows, into the ragged score buffer
+    (slot s owns the floats from scores[slot_off[s]])."""
+    qp, qld = _mat(Q)
+    rp, rld = _mat(rows)
+    if Q.shape[1] != rows.shape[1]:
+        raise ValueError("queries and list rows of one padded width")
+    nlist = list_start.numel() - 1
+    n_slots = slot_query.numel()
+    if tiles.dim() != 2 or tiles.shape[1] != 4:
+        raise ValueError("tiles must be int32 [n_tiles, 4]")
+    call("cdml_ivf_scan_f32", qp, qld, Q.shape[0], _vec(slot_query, torch.int32, 0, "slot_query"),
+         _vec(slot_start, torch.int32, nlist + 1, "slot_start"), _vec(slot_off, torch.int64, n_slots, "slot_off"), rp, rld,
+         _vec(list_start, torch.int32, nlist + 1, "list_start"), Q.shape[1], _vec(tiles, torch.int32, 4, "tiles"),
+         tiles.shape[0], _p(scores, torch.float32), _stream())
+    return scores
+
+
+def ivf_merge(scores, slot_off, slot_of, probe, list_start, ids, r_sq, q_sq, k, best_d, best_i):
+    """One wave per query: the k best (d, id) keys over the query's probed score segments; writes the query's whole sorted list
+    best_d / best_i [nq, knn_list_capacity()] (+inf / 0x7fffffff = empty)."""
+    nq, nprobe = probe.shape
+    cap = knn_list_capacity()
+    if tuple(slot_of.shape) != (nq, nprobe) or tuple(best_d.shape) != (nq, cap) or tuple(best_i.shape) != (nq, cap):
+        raise ValueError("slot_of [nq, nprobe] and best_d / best_i [nq, %d]" % cap)
+    call("cdml_ivf_merge", _p(scores, torch.float32), _vec(slot_off, torch.int64, 0, "slot_off"),
+         _vec(slot_of, torch.int32, nq * nprobe, "slot_of"), _vec(probe, torch.int32, nq * nprobe, "probe"), nq, nprobe,
+         _vec(list_start, torch.int32, 2, "list_start"), _vec(ids, torch.int32, 0, "ids"), _vec(r_sq, torch.float32, 0, "r_sq"),
+         _vec(q_sq, torch.float32, nq, "q_sq"), k, _vec(best_d, torch.float32, nq * cap, "best_d"),
+         _vec(best_i, torch.int32, nq * cap, "best_i"), _stream())
+
+
 def knn_desim_prep(fI, fD, fI_end, threshold, out):
     """The raw-feature lists fI (int32 | int64 [n_f, kf]) with their distances fD (fp32) filtered into out (int32
     [n_f, kp], kp = 32 | 64): fI[r, t] for t < fI_end where fD <= threshold (float32), fI != r, fI >= 0; else -1."""

@@ -1,0 +1,153 @@
+"""Times the IVF index (cdml_amd.knn.IVFIndex) against the exact search of the same size, by device events, each shape warmed.
+
+    python tools/ivf_bench.py                    # 343 455 x 256, self-search, k = 51, nlist in {256, 1024}, nprobe in {4, 16}
+    python tools/ivf_bench.py --big              # 10 M x 256, self-search, k = 40, nlist in {4096, 16384}, nprobe in {8, 16, 32}
+                                                 # (recall on a 65 536-query sample)
+    python tools/ivf_bench.py --n 50000 --nlist 64 --nprobe 4 8 --k 20
+
+Per run one JSON line: build time by stage (one assignment, one centroid update, the whole build), search time by stage
+(coarse / tables / scan / merge), the scan's FLOP from the tile table over its kernel time, recall@k against the exact search,
+max / mean list length, scanned share.  Rows are Gaussian mixtures (n / 64 centres, noise 0.5) so that lists mean something.
+No test gates a time."""
+import argparse
+import json
+import os
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def timed(fn):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    out = fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b), out
+
+
+def catalogue(n, D, dev, seed=0):
+    g = torch.Generator(device=dev)
+    g.manual_seed(seed)
+    centres = torch.randn(max(n // 64, 1), D, device=dev, generator=g)
+    which = torch.randint(0, centres.shape[0], (n,), device=dev, generator=g)
+    return centres[which] + 0.5 * torch.randn(n, D, device=dev, generator=g)
+
+
+def staged_search(idx, queries, k, nprobe, knn, ops, score_bytes):
+    """IVFIndex.search stage by stage (the same calls), every stage between device events; (ms by stage, D, I, stats)"""
+    ms = {"coarse": 0.0, "tables": 0.0, "scan": 0.0, "merge": 0.0}
+    dev = idx.device
+    cap = ops.knn_list_capacity()
+
+    def coarse():
+        Q = idx._prepared(queries, dev, idx.l2_norm)
+        q_sq = torch.zeros(Q.shape[0], dtype=torch.float32, device=dev)
+        ops.row_sqnorm(Q, Q.shape[1], q_sq)
+        return Q, q_sq, idx._probes(Q, nprobe).to(torch.int32)
+    ms["coarse"], (Q, q_sq, probe) = timed(coarse)
+    nq = Q.shape[0]
+    best_d = torch.empty((nq, cap), dtype=torch.float32, device=dev)
+    best_i = torch.empty((nq, cap), dtype=torch.int32, device=dev)
+
+    def plan():
+        ld = (idx.list_len + 3) // 4 * 4
+        p = probe.to(torch.int64)
+        costs = torch.where(p >= 0, ld[p.clamp(min=0)], torch.zeros_like(p)).sum(1).cpu().numpy()
+        return knn.ivf_plan_chunks(costs, score_bytes, max_queries=(2 ** 31 - 1) // nprobe)
+    t, chunks = timed(plan)
+    ms["tables"] += t
+    tiles = useful = floats = 0
+    for q0, q1 in chunks:
+        pc = probe[q0:q1].contiguous()
+        t, tb = timed(lambda: knn.ivf_tables(pc, idx.list_len))
+        ms["tables"] += t
+        if tb["n_slots"] == 0:
+            best_d[q0:q1], best_i[q0:q1] = float("inf"), 0x7fffffff
+            continue
+        scores = torch.empty(max(tb["n_floats"], 4), dtype=torch.float32, device=dev)
+        if tb["n_tiles"]:
+            t, _ = timed(lambda: ops.ivf_scan_f32(Q[q0:q1], tb["slot_query"], tb["slot_start"], tb["slot_off"], idx.rows,
+                                                  idx.list_start, tb["tiles"], scores))
+            ms["scan"] += t
+        t, _ = timed(lambda: ops.ivf_merge(scores, tb["slot_off"], tb["slot_of"], pc, idx.list_start, idx.ids, idx.r_sq,
+                                           q_sq[q0:q1], k, best_d[q0:q1], best_i[q0:q1]))
+        ms["merge"] += t
+        tiles += tb["n_tiles"]
+        floats += tb["n_floats"]
+        cnt = (tb["slot_start"][1:] - tb["slot_start"][:-1]).to(torch.int64)
+        useful += int((cnt * idx.list_len).sum())
+    I = best_i[:, :k].to(torch.int64)
+    I[I == 0x7fffffff] = -1
+    Dp = Q.shape[1]
+    stats = {"chunks": len(chunks), "tiles": tiles, "score_bytes": 4 * floats,
+             "scan_flop_tiles": 2.0 * tiles * knn.IVF_TILE * knn.IVF_TILE * Dp, "scan_flop_useful": 2.0 * useful * Dp, "probe": probe}
+    return ms, best_d[:, :k], I, stats
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--big", action="store_true")
+    ap.add_argument("--n", type=int, default=None)
+    ap.add_argument("--dim", type=int, default=256)
+    ap.add_argument("--k", type=int, default=None)
+    ap.add_argument("--nlist", type=int, nargs="*", default=None)
+    ap.add_argument("--nprobe", type=int, nargs="*", default=None)
+    ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--sample", type=int, default=65536, help="queries of the recall sample when n is above it (--big)")
+    ap.add_argument("--score-bytes", type=int, default=None)
+    a = ap.parse_args()
+    from cdml_amd import knn, ops
+    dev = torch.device("cuda:0")
+    n = a.n or (10_000_000 if a.big else 343455)
+    k = a.k or (40 if a.big else 51)
+    nlists = a.nlist or ([4096, 16384] if a.big else [256, 1024])
+    nprobes = a.nprobe or ([8, 16, 32] if a.big else [4, 16])
+    x = catalogue(n, a.dim, dev)
+    # the exact search of the same size, in the same call (warmed); at --big on the sample only
+    sample = None
+    if a.big or n >= 4_000_000:
+        sample = torch.randperm(n, device=dev, generator=torch.Generator(device=dev).manual_seed(1))[:a.sample]
+    xq = x if sample is None else x[sample]
+    knn.knn_search(x[:4096], x[:4096], k, device=dev)
+    exact_ms, (_, Ie) = timed(lambda: knn.knn_search(x, xq, k, device=dev))
+    print(json.dumps({"what": "exact", "n": n, "nq": xq.shape[0], "dim": a.dim, "k": k, "ms": round(exact_ms, 3)}), flush=True)
+    for nlist in nlists:
+        knn.IVFIndex.build(x[:max(4 * nlist, 4096)], min(nlist, 64), iters=1, device=dev)                 # warm the build's launches
+        build_ms, idx = timed(lambda: knn.IVFIndex.build(x, nlist, iters=a.iters, device=dev))
+        X = idx._prepared(x, dev, True)
+        assign_ms, _ = timed(lambda: knn.knn_search(idx._C, X, 1, l2_norm=False, device=dev))
+        C2 = idx._C.clone()
+        order = torch.argsort(idx.assign.clamp(min=0), stable=True).to(torch.int32)
+        update_ms, _ = timed(lambda: ops.ivf_centroid_sums(X, order, idx.list_start, C2, X.shape[1]))
+        del X
+        lens = idx.list_len.double()
+        score_bytes = a.score_bytes or idx.default_score_bytes()
+        for nprobe in nprobes:
+            staged_search(idx, x[:8192], k, nprobe, knn, ops, score_bytes)                                # warm
+            ms, _, I, st = staged_search(idx, x, k, nprobe, knn, ops, score_bytes)                        # the self-search, all rows
+            Is = I if sample is None else I[sample]
+            hit = found = 0
+            for r0 in range(0, Is.shape[0], 32768):                                                       # (recall in row blocks)
+                a_, b_ = Is[r0:r0 + 32768], Ie[r0:r0 + 32768]
+                hit += int(((a_.unsqueeze(2) == b_.unsqueeze(1)).any(2) & (a_ >= 0)).sum())
+                found += int((b_ >= 0).sum())
+            recall = hit / max(found, 1)
+            del I, Is
+            total = sum(ms.values())
+            print(json.dumps({
+                "what": "ivf", "n": n, "nq": n, "recall_queries": Ie.shape[0], "dim": a.dim, "k": k, "nlist": nlist, "nprobe": nprobe, "iters": a.iters,
+                "build_ms": round(build_ms, 2), "assign_all_rows_ms": round(assign_ms, 3), "centroid_update_ms": round(update_ms, 3),
+                "search_ms": round(total, 3), "stages_ms": {s: round(v, 3) for s, v in ms.items()},
+                "exact_ms": round(exact_ms, 3), "exact_nq": xq.shape[0], "speedup": round(exact_ms / total, 2) if sample is None else None,
+                "scan_tflops_tiles": round(st["scan_flop_tiles"] / max(ms["scan"], 1e-9) / 1e9, 2),
+                "scan_tflops_useful": round(st["scan_flop_useful"] / max(ms["scan"], 1e-9) / 1e9, 2),
+                "score_bytes": st["score_bytes"], "score_budget": score_bytes, "chunks": st["chunks"], "recall": round(recall, 4),
+                "list_max_over_mean": round(float(lens.max() / lens.mean()), 2), "empty_lists": int((lens == 0).sum()),
+                "scanned_share": round(idx.scanned_share(st["probe"]), 5), "nprobe_over_nlist": round(nprobe / nlist, 5)}), flush=True)
+
+
+if __name__ == "__main__":
+    main()
