@@ -288,6 +288,13 @@ SIGNATURES_IVF = {
     "cdml_ivf_merge": (_i, [_p, _p, _p, _p, _i, _i, _p, _p, _p, _p, _i, _p, _p, _p]),
 }
 
+# name -> (restype, argtypes); must list every symbol include/cdml_ivf_f16.h declares (the fp16 lists of the IVF index: the
+# grouped score product on the fp16 MFMA and the exact fp32 re-rank of the merge's candidates)
+SIGNATURES_IVF_F16 = {
+    "cdml_ivf_scan_f16": (_i, [_p, _i64, _i, _p, _p, _p, _p, _i64, _p, _i, _p, _i, _p, _p]),
+    "cdml_ivf_refine": (_i, [_p, _i64, _i, _p, _i64, _i64, _i, _p, _i, _i, _p, _p, _p]),
+}
+
 _lib = None
 
 
@@ -308,7 +315,8 @@ def load_library():
     lib = C.CDLL(path)
     for name, (res, args) in (list(SIGNATURES.items()) + list(SIGNATURES_MIXED.items()) + list(SIGNATURES_DP.items())
                                + list(SIGNATURES_BF16.items()) + list(SIGNATURES_HARDNEG.items()) + list(SIGNATURES_WIDE.items())
-                               + list(SIGNATURES_NEGW.items()) + list(SIGNATURES_F8.items()) + list(SIGNATURES_IVF.items())):
+                               + list(SIGNATURES_NEGW.items()) + list(SIGNATURES_F8.items()) + list(SIGNATURES_IVF.items())
+                               + list(SIGNATURES_IVF_F16.items())):
         fn = getattr(lib, name)          # AttributeError if the ABI lost a symbol
         fn.restype = res
         fn.argtypes = args

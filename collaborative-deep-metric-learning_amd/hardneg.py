@@ -64,7 +64,7 @@ def filter_lists(I, k, skip_top=0, pairs=None):
 
 
 def mine_lists(embeddings, k, skip_top=0, pairs=None, device="cuda:0", precision="f32x3", nlist=0, nprobe=0, ivf_iters=10,
-               ivf_seed=0):
+               ivf_seed=0, storage="f32", refine=0):
     """Candidate negatives of every row: int32 [n, L] device tensor, L = k rounded up to a multiple of 4.
 
     A self-kNN over ``embeddings`` ([n, D] ndarray or tensor; l2-normalised first, as ``knn.calc_knn`` does) with
@@ -73,10 +73,14 @@ def mine_lists(embeddings, k, skip_top=0, pairs=None, device="cuda:0", precision
     remains is left-packed, nearest first, and padded with -1.
     ``nlist`` > 0: the neighbours come from an IVF index over the embeddings instead (``knn.IVFIndex.build(e, nlist,
     iters=ivf_iters, seed=ivf_seed)`` and its ``search(e, k + skip_top + 1, nprobe)``: approximate -- a neighbour outside a
-    row's ``nprobe`` nearest lists is missed -- and sub-linear in the catalogue); the filter is the same."""
+    row's ``nprobe`` nearest lists is missed -- and sub-linear in the catalogue); the filter is the same.
+    ``storage`` ("f32" | "f16") and ``refine`` go to that index (``knn.IVFIndex``: fp16 lists at half the bytes, scanned on
+    the fp16 MFMA; ``refine=r`` re-ranks the r best candidates of a row against the fp32 embeddings given here)."""
     k, skip_top, nlist, nprobe = int(k), int(skip_top), int(nlist), int(nprobe)
     if nlist < 0 or (nlist == 0 and nprobe != 0):
         raise ValueError("mine_lists takes nlist >= 0, and nprobe only with nlist > 0 (got nlist = %d, nprobe = %d)" % (nlist, nprobe))
+    if nlist == 0 and (storage != "f32" or int(refine) != 0):
+        raise ValueError("mine_lists takes storage and refine only with nlist > 0 (got storage = %r, refine = %d)" % (storage, int(refine)))
     if k < 1 or skip_top < 0:
         raise ValueError("mine_lists needs k >= 1 and skip_top >= 0, got %d and %d" % (k, skip_top))
     if list_width(k) > 1024:
@@ -85,8 +89,8 @@ def mine_lists(embeddings, k, skip_top=0, pairs=None, device="cuda:0", precision
     e = embeddings if torch.is_tensor(embeddings) else torch.as_tensor(np.asarray(embeddings, dtype=np.float32))
     e = e.to(device=dev, dtype=torch.float32)
     if nlist > 0:
-        index = knn.IVFIndex.build(e, nlist, iters=ivf_iters, seed=ivf_seed, device=dev, precision=precision)
-        _, I = index.search(e, k + skip_top + 1, nprobe)
+        index = knn.IVFIndex.build(e, nlist, iters=ivf_iters, seed=ivf_seed, device=dev, precision=precision, storage=storage)
+        _, I = index.search(e, k + skip_top + 1, nprobe, refine=int(refine), base=index.prepare(e) if int(refine) else None)
     else:
         _, I = knn.knn_search(e, e, k + skip_top + 1, device=dev, precision=precision)
     if pairs is not None and not torch.is_tensor(pairs):

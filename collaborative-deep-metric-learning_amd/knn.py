@@ -413,7 +413,15 @@ class IVFIndex:
     [nlist, D], ``assign`` int64 [n] (-1 = unlisted: a row with a non-finite coordinate), ``ids`` int32 [n_listed] sorted by
     (assign, id), ``list_start`` int32 [nlist + 1], ``rows`` fp32 [n_listed, Dp] and ``r_sq`` [n_listed] in that order;
     ``init_rows`` and ``train_ids`` (int64, CPU, sorted: the rows the centroids started from and the rows k-means ran on),
-    ``objective`` (float64, CPU: one entry per Lloyd iteration), ``n_unlisted``."""
+    ``objective`` (float64, CPU: one entry per Lloyd iteration), ``n_unlisted``.
+
+    ``storage="f16"`` (include/cdml_ivf_f16.h): ``rows`` is the fp16 image of the prepared rows (half
+    the bytes; the fp32 prepared matrix is not kept), ``r_sq`` the fp32 squared norms of the rounded values, a row whose
+    image overflows is unlisted; k-means, ``assign``, ``centroids`` and the probes are those of the fp32 index.  ``search``
+    then scans on the fp16 MFMA, and ``refine=r`` re-scores the r best candidates against fp32 rows (``base=``)."""
+
+    STORAGES = ("f32", "f16")
+    _NORM_ROWS = 1 << 20        # rows per fp32 temporary when the squared norms of fp16 rows are taken
 
     def __init__(self):
         raise TypeError("use IVFIndex.build, IVFIndex.from_assignment or IVFIndex.load_state_dict")
@@ -434,10 +442,34 @@ class IVFIndex:
             ops.l2norm_fwd(X, X.shape[1], X)
         return X
 
+    def prepare(self, base):
+        """The fp32 device matrix [n, Dp] this index works on for ``base`` ([n, D]): zero-padded to Dp % 32 == 0 and
+        l2-normalised when the index is; what ``search(..., refine=r, base=)`` re-ranks against."""
+        t = base if torch.is_tensor(base) else torch.as_tensor(np.asarray(base, dtype=np.float32))
+        if t.dim() != 2 or t.shape[1] != self.dim:
+            raise ValueError("catalogue / index dimension mismatch: base must be [n, D = %d], got %s" % (self.dim, tuple(t.shape)))
+        return self._prepared(t, self.device, self.l2_norm)
+
     @classmethod
-    def _blank(cls, nlist, D, l2_norm, device, precision):
+    def _check_storage(cls, storage):
+        if storage not in cls.STORAGES:
+            raise ValueError("storage must be one of %s, got %r" % (cls.STORAGES, storage))
+        return storage
+
+    @classmethod
+    def _sqnorm_f16(cls, rows):
+        """fp32 |row|^2 of fp16 rows (the rounded values), through fp32 temporaries of at most _NORM_ROWS rows"""
+        out = torch.zeros(rows.shape[0], dtype=torch.float32, device=rows.device)
+        for r0 in range(0, rows.shape[0], cls._NORM_ROWS):
+            part = rows[r0:r0 + cls._NORM_ROWS].float()
+            ops.row_sqnorm(part, part.shape[1], out[r0:r0 + cls._NORM_ROWS])
+        return out
+
+    @classmethod
+    def _blank(cls, nlist, D, l2_norm, device, precision, storage="f32"):
         self = object.__new__(cls)
         self.nlist, self.dim, self.l2_norm, self.device, self.precision = int(nlist), int(D), bool(l2_norm), torch.device(device), precision
+        self.storage = cls._check_storage(storage)
         self.init_rows = self.train_ids = torch.empty(0, dtype=torch.int64)
         self.objective = torch.empty(0, dtype=torch.float64)
         return self
@@ -445,7 +477,9 @@ class IVFIndex:
     def _set_lists(self, X, C, assign):
         """the cluster-major lists of (X, assign); rows with a non-finite coordinate are unlisted whatever ``assign`` says"""
         n, Dp = X.shape
-        a = torch.where(torch.isfinite(X).all(1), assign.to(device=X.device, dtype=torch.int64), torch.full((n,), -1, dtype=torch.int64, device=X.device))
+        Xh = X.to(torch.float16) if self.storage == "f16" else None           # round to nearest even; overflow -> inf
+        finite = torch.isfinite(X if Xh is None else Xh).all(1)
+        a = torch.where(finite, assign.to(device=X.device, dtype=torch.int64), torch.full((n,), -1, dtype=torch.int64, device=X.device))
         listed = a >= 0
         key = torch.where(listed, a, torch.full_like(a, self.nlist))
         order = torch.argsort(key, stable=True)               # ids ascend inside a list
@@ -459,18 +493,23 @@ class IVFIndex:
         self.ids = order[:n_listed].to(torch.int32)
         self.list_start = start.to(torch.int32)
         self.list_len = cnt[:self.nlist].contiguous()
-        self.rows = X.index_select(0, order[:n_listed])
-        self.r_sq = torch.zeros(n_listed, dtype=torch.float32, device=X.device)
-        ops.row_sqnorm(self.rows, Dp, self.r_sq)
+        if self.storage == "f16":
+            self.rows = Xh.index_select(0, order[:n_listed])
+            self.r_sq = self._sqnorm_f16(self.rows)
+        else:
+            self.rows = X.index_select(0, order[:n_listed])
+            self.r_sq = torch.zeros(n_listed, dtype=torch.float32, device=X.device)
+            ops.row_sqnorm(self.rows, Dp, self.r_sq)
         self._C = C
         self.centroids = C[:, :self.dim]
         self.n_rows, self.n_listed, self.n_unlisted = n, n_listed, n - n_listed
         return self
 
     @classmethod
-    def from_assignment(cls, base, centroids, assign, l2_norm=True, device="cuda:0", precision="f32x3"):
+    def from_assignment(cls, base, centroids, assign, l2_norm=True, device="cuda:0", precision="f32x3", storage="f32"):
         """The index of given ``centroids`` ([nlist, D]) and an arbitrary ``assign`` (int [n], values in [-1, nlist); -1 =
         unlisted): the search contract does not need the assignment to be the nearest centroid."""
+        cls._check_storage(storage)
         t = cls._as_tensor(base)
         c = centroids if torch.is_tensor(centroids) else torch.as_tensor(np.asarray(centroids, dtype=np.float32))
         a = assign if torch.is_tensor(assign) else torch.as_tensor(np.asarray(assign))
@@ -481,14 +520,17 @@ class IVFIndex:
         nlist = c.shape[0]
         if a.numel() and (int(a.min()) < -1 or int(a.max()) >= nlist):
             raise ValueError("assign must lie in [-1, nlist = %d)" % nlist)
-        self = cls._blank(nlist, t.shape[1], l2_norm, device, precision)
+        self = cls._blank(nlist, t.shape[1], l2_norm, device, precision, storage)
         X = cls._prepared(t, self.device, l2_norm)
         return self._set_lists(X, _device_matrix(c, self.device, 1, 32), a)
 
     @classmethod
-    def build(cls, base, nlist, iters=10, seed=0, train_rows=None, l2_norm=True, device="cuda:0", precision="f32x3"):
+    def build(cls, base, nlist, iters=10, seed=0, train_rows=None, l2_norm=True, device="cuda:0", precision="f32x3",
+              storage="f32"):
         """Lloyd's k-means, deterministic (include/cdml_ivf.h BUILD).  ``precision`` is that of the coarse ``knn_search`` calls
-        (every assignment step, and ``probes``)."""
+        (every assignment step, and ``probes``).  ``storage`` ("f32" | "f16") is the format of the lists alone: k-means runs on
+        the fp32 rows either way, so (base, seed) gives the same ``assign`` and the same probes for both."""
+        cls._check_storage(storage)
         t = cls._as_tensor(base)
         nlist, iters = int(nlist), int(iters)
         n_finite = int(torch.isfinite(t).all(1).sum())
@@ -499,7 +541,7 @@ class IVFIndex:
         n_train = min(n_finite, 256 * nlist) if train_rows is None else int(train_rows)
         if not nlist <= n_train <= n_finite:
             raise ValueError("train_rows must be in [nlist = %d, the number of finite rows = %d], got %d" % (nlist, n_finite, n_train))
-        self = cls._blank(nlist, t.shape[1], l2_norm, device, precision)
+        self = cls._blank(nlist, t.shape[1], l2_norm, device, precision, storage)
         dev = self.device
         X = cls._prepared(t, dev, l2_norm)
         n, Dp = X.shape
@@ -532,15 +574,21 @@ class IVFIndex:
         return self
 
     def state_dict(self):
-        """centroids + assign + the flags (CPU tensors); the lists are re-derived from the catalogue on load, bit for bit."""
-        return {"centroids": self.centroids.detach().cpu().clone(), "assign": self.assign.cpu().clone(), "l2_norm": self.l2_norm,
-                "precision": self.precision, "init_rows": self.init_rows.clone(), "objective": self.objective.clone()}
+        """centroids + assign + the flags (CPU tensors); the lists are re-derived from the catalogue on load, bit for bit.
+        An f16 index adds ``"storage": "f16"``; an f32 index's keys are what they were (a missing key loads as "f32")."""
+        state = {"centroids": self.centroids.detach().cpu().clone(), "assign": self.assign.cpu().clone(), "l2_norm": self.l2_norm,
+                 "precision": self.precision, "init_rows": self.init_rows.clone(), "objective": self.objective.clone()}
+        if self.storage != "f32":
+            state["storage"] = self.storage
+        return state
 
     @classmethod
-    def load_state_dict(cls, state, base, device="cuda:0"):
-        """The index of ``state_dict()`` over the same catalogue ``base``."""
+    def load_state_dict(cls, state, base, device="cuda:0", storage=None):
+        """The index of ``state_dict()`` over the same catalogue ``base``.  ``storage`` (default: the state's, "f32" where
+        it names none) may re-derive the lists in the other format: centroids and assign do not depend on it."""
         self = cls.from_assignment(base, state["centroids"], state["assign"], l2_norm=state["l2_norm"], device=device,
-                                   precision=state["precision"])
+                                   precision=state["precision"],
+                                   storage=state.get("storage", "f32") if storage is None else storage)
         self.init_rows, self.objective = state["init_rows"].clone(), state["objective"].clone()
         return self
 
@@ -576,15 +624,45 @@ class IVFIndex:
         """max(1 GiB, 4 B x 512 x n_listed): the default ``score_bytes`` of ``search``"""
         return max(IVF_SCORE_BYTES, 4 * IVF_SCORE_SLOTS * self.n_listed)
 
-    def search(self, queries, k, nprobe, score_bytes=None, stats=None, probe=None):
+    def _check_refine(self, k, refine, base):
+        """(r, base) of ``search``: the refusals, by name, before any device work"""
+        r = int(refine)
+        if self.storage == "f32":
+            if r != 0 or base is not None:
+                raise ValueError("refine and base belong to an index with storage=\"f16\" (this one is \"f32\": its distances are exact already)")
+            return 0, None
+        if r == 0:
+            if base is not None:
+                raise ValueError("base is read only with refine > 0")
+            return 0, None
+        cap = ops.knn_list_capacity()
+        if not int(k) <= r <= cap:
+            raise ValueError("refine must be 0 or in [k = %d, %d], got %d" % (int(k), cap, r))
+        Dp = _round_up(self.dim, 32)
+        if base is None:
+            raise ValueError("refine > 0 needs base=: the fp32 rows to re-rank against (IVFIndex.prepare(catalogue))")
+        if not torch.is_tensor(base) or base.dtype != torch.float32 or base.dim() != 2 or base.stride(1) != 1 \
+                or tuple(base.shape) != (self.n_rows, Dp) or base.device.type != self.device.type \
+                or (self.device.index is not None and base.device.index != self.device.index):
+            raise ValueError("base must be an fp32 [n_rows = %d, Dp = %d] matrix on %s (IVFIndex.prepare(catalogue)), got %s"
+                             % (self.n_rows, Dp, self.device,
+                                (tuple(base.shape), base.dtype, str(base.device)) if torch.is_tensor(base) else type(base).__name__))
+        return r, base
+
+    def search(self, queries, k, nprobe, score_bytes=None, stats=None, probe=None, refine=0, base=None):
         """(D [nq, k] fp32 squared L2 ascending, I [nq, k] int64; +inf / -1 where fewer than k rows were probed), device
         tensors shaped and typed like ``knn_search``'s.  Queries go in chunks whose ragged score buffer fits ``score_bytes``
         (default ``default_score_bytes()``: 1 GiB, or 2 KiB per listed row where that is more -- 20 GB at 10 M rows;
         ``ivf_plan_chunks``); the result does not depend on the chunking.  ``stats`` (a dict, optional)
         receives the chunk list, the tile count and the score floats.  ``probe`` (int [nq, nprobe], values in [-1, nlist),
-        a query's lists distinct; default: ``probes(queries, nprobe)``): the lists to scan, as given."""
+        a query's lists distinct; default: ``probes(queries, nprobe)``): the lists to scan, as given.
+        On an index with storage "f16" a chunk's queries are rounded to fp16 as the rows were and the distances are those
+        of the rounded values (a query whose image is non-finite probes nothing); ``refine=r`` (k <= r <= 128, with
+        ``base`` = the fp32 matrix of ``prepare(catalogue)``) keeps the r best of them and returns the k best under the fp32
+        distances sum (q - x)^2 of the fp32 rows (include/cdml_ivf_f16.h)."""
         self._check_queries(queries, nprobe, k)
         k, nprobe = int(k), int(nprobe)
+        refine, base = self._check_refine(k, refine, base)
         if probe is not None:
             probe = torch.as_tensor(probe)
             if tuple(probe.shape) != (queries.shape[0], nprobe) or probe.is_floating_point():
@@ -593,6 +671,7 @@ class IVFIndex:
                 raise ValueError("probe ids must lie in [-1, nlist = %d)" % self.nlist)
         t = queries if torch.is_tensor(queries) else torch.as_tensor(np.asarray(queries, dtype=np.float32))
         dev = self.device
+        f16 = self.storage == "f16"
         Q = self._prepared(t, dev, self.l2_norm)
         nq, Dp = Q.shape
         cap = ops.knn_list_capacity()
@@ -600,14 +679,21 @@ class IVFIndex:
         best_i = torch.empty((nq, cap), dtype=torch.int32, device=dev)
         if nq:
             q_sq = torch.zeros(nq, dtype=torch.float32, device=dev)
-            ops.row_sqnorm(Q, Dp, q_sq)
+            if not f16:
+                ops.row_sqnorm(Q, Dp, q_sq)
             probe = (self._probes(Q, nprobe) if probe is None else probe.to(dev)).to(torch.int32).contiguous()
+            if f16:                                           # a query with no finite fp16 image probes nothing
+                lost = (Q.abs() >= 65520.0).any(1)            # (fp32 -> fp16 rounds to inf from 65520 on; NaN queries have -1 probes already)
+                probe = torch.where(lost[:, None], torch.full_like(probe, -1), probe)
             ld = (self.list_len + 3) // 4 * 4
             p = probe.to(torch.int64)
             costs = torch.where(p >= 0, ld[p.clamp(min=0)], torch.zeros_like(p)).sum(1).cpu().numpy()
             chunks = ivf_plan_chunks(costs, self.default_score_bytes() if score_bytes is None else score_bytes,
                                      max_queries=(2 ** 31 - 1) // nprobe)
             n_tiles = n_floats = 0
+            keep = refine or k                                # entries the merge must get right
+            cand_d = torch.empty_like(best_d) if refine else best_d
+            cand_i = torch.empty_like(best_i) if refine else best_i
             for q0, q1 in chunks:
                 pc = probe[q0:q1].contiguous()
                 tb = ivf_tables(pc, self.list_len)
@@ -616,15 +702,27 @@ class IVFIndex:
                 if tb["n_slots"] == 0:                        # nothing probed (non-finite queries only)
                     best_d[q0:q1] = float("inf")
                     best_i[q0:q1] = 0x7fffffff
+                    if refine:
+                        cand_i[q0:q1] = 0x7fffffff
                     continue
                 scores = torch.empty(max(tb["n_floats"], 4), dtype=torch.float32, device=dev)
-                if tb["n_tiles"]:
+                if f16:
+                    Qh = Q[q0:q1].to(torch.float16)
+                    ops.row_sqnorm(Qh.float(), Dp, q_sq[q0:q1])
+                    if tb["n_tiles"]:
+                        ops.ivf_scan_f16(Qh, tb["slot_query"], tb["slot_start"], tb["slot_off"], self.rows, self.list_start,
+                                         tb["tiles"], scores)
+                elif tb["n_tiles"]:
                     ops.ivf_scan_f32(Q[q0:q1], tb["slot_query"], tb["slot_start"], tb["slot_off"], self.rows, self.list_start,
                                      tb["tiles"], scores)
-                ops.ivf_merge(scores, tb["slot_off"], tb["slot_of"], pc, self.list_start, self.ids, self.r_sq, q_sq[q0:q1], k,
-                              best_d[q0:q1], best_i[q0:q1])
+                ops.ivf_merge(scores, tb["slot_off"], tb["slot_of"], pc, self.list_start, self.ids, self.r_sq, q_sq[q0:q1], keep,
+                              cand_d[q0:q1], cand_i[q0:q1])
+                if refine:
+                    ops.ivf_refine(Q[q0:q1], base, cand_i[q0:q1], refine, k, best_d[q0:q1], best_i[q0:q1])
             if stats is not None:
                 stats.update(chunks=chunks, n_tiles=n_tiles, n_floats=n_floats, probe=probe)
+                if refine:
+                    stats.update(candidates=cand_i[:, :refine])
         I = best_i[:, :k].to(torch.int64)
         I[I == 0x7fffffff] = -1
         return best_d[:, :k].contiguous(), I

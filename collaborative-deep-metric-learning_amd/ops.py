@@ -1723,6 +1723,44 @@ def ivf_merge(scores, slot_off, slot_of, probe, list_start, ids, r_sq, q_sq, k, 
          _vec(best_i, torch.int32, nq * cap, "best_i"), _stream())
 
 
+# ---------------------------------------- fp16 lists of the IVF index (include/cdml_ivf_f16.h) ------
+def ivf_scan_f16(Q, slot_query, slot_start, slot_off, rows, list_start, tiles, scores):
+    """``ivf_scan_f32`` with fp16 queries and list rows (torch.float16), fp32 scores: the grouped score product on the fp16
+    MFMA, same tables and score buffer."""
+    if Q.dtype != torch.float16 or rows.dtype != torch.float16:
+        raise ValueError("ivf_scan_f16 takes float16 queries and list rows")
+    if Q.dim() != 2 or rows.dim() != 2 or Q.stride(1) != 1 or rows.stride(1) != 1 or Q.shape[1] != rows.shape[1]:
+        raise ValueError("queries and list rows: 2-D, unit inner stride, one padded width")
+    nlist = list_start.numel() - 1
+    n_slots = slot_query.numel()
+    if tiles.dim() != 2 or tiles.shape[1] != 4:
+        raise ValueError("tiles must be int32 [n_tiles, 4]")
+    call("cdml_ivf_scan_f16", _p(Q), Q.stride(0), Q.shape[0], _vec(slot_query, torch.int32, 0, "slot_query"),
+         _vec(slot_start, torch.int32, nlist + 1, "slot_start"), _vec(slot_off, torch.int64, n_slots, "slot_off"), _p(rows),
+         rows.stride(0), _vec(list_start, torch.int32, nlist + 1, "list_start"), Q.shape[1],
+         _vec(tiles, torch.int32, 4, "tiles"), tiles.shape[0], _p(scores, torch.float32), _stream())
+    return scores
+
+
+def ivf_refine(Q, base, cand, r, k, best_d, best_i):
+    """One wave per query: the direct fp32 distances sum_j (q_j - x_j)^2 of the first ``r`` candidates of ``cand`` (int32
+    [nq, knn_list_capacity()], ``ivf_merge``'s best_i; 0x7fffffff = none) against the rows of ``base`` (fp32 [n_rows, >= Dp],
+    Dp = Q's width), sorted by (d, id) into best_d / best_i [nq, knn_list_capacity()] (+inf / 0x7fffffff behind the valid
+    ones).  ``cand`` and ``best_i`` are different tensors."""
+    qp, qld = _mat(Q)
+    bp, bld = _mat(base)
+    nq, Dp = Q.shape
+    cap = knn_list_capacity()
+    if base.shape[1] < Dp:
+        raise ValueError("base rows must be at least as wide as the queries (%d < %d)" % (base.shape[1], Dp))
+    if tuple(cand.shape) != (nq, cap) or tuple(best_d.shape) != (nq, cap) or tuple(best_i.shape) != (nq, cap):
+        raise ValueError("cand, best_d and best_i must be [nq, %d]" % cap)
+    if cand.data_ptr() == best_i.data_ptr():
+        raise ValueError("cand and best_i must be different tensors")
+    call("cdml_ivf_refine", qp, qld, nq, bp, bld, base.shape[0], Dp, _vec(cand, torch.int32, nq * cap, "cand"), int(r), int(k),
+         _vec(best_d, torch.float32, nq * cap, "best_d"), _vec(best_i, torch.int32, nq * cap, "best_i"), _stream())
+
+
 def knn_desim_prep(fI, fD, fI_end, threshold, out):
     """The raw-feature lists fI (int32 | int64 [n_f, kf]) with their distances fD (fp32) filtered into out (int32
     [n_f, kp], kp = 32 | 64): fI[r, t] for t < fI_end where fD <= threshold (float32), fI != r, fI >= 0; else -1."""

@@ -4,10 +4,13 @@
     python tools/ivf_bench.py --big              # 10 M x 256, self-search, k = 40, nlist in {4096, 16384}, nprobe in {8, 16, 32}
                                                  # (recall on a 65 536-query sample)
     python tools/ivf_bench.py --n 50000 --nlist 64 --nprobe 4 8 --k 20
+    python tools/ivf_bench.py --storage f32 f16 --refine 128   # fp16 lists beside the fp32 ones over the same (centroids, assign)
 
 Per run one JSON line: build time by stage (one assignment, one centroid update, the whole build), search time by stage
 (coarse / tables / scan / merge), the scan's FLOP from the tile table over its kernel time, recall@k against the exact search,
-max / mean list length, scanned share.  Rows are Gaussian mixtures (n / 64 centres, noise 0.5) so that lists mean something.
+max / mean list length, scanned share.  With --storage f16 the line of the fp16 index (storage "f16": the lists re-derived from
+the fp32 index's centroids and assign) follows the fp32 one: the same stages plus the re-rank, issued and useful scan TF/s,
+the index's bytes, and recall@k for refine 0 and --refine.  Rows are Gaussian mixtures (n / 64 centres, noise 0.5) so that lists mean something.
 No test gates a time."""
 import argparse
 import json
@@ -36,11 +39,16 @@ def catalogue(n, D, dev, seed=0):
     return centres[which] + 0.5 * torch.randn(n, D, device=dev, generator=g)
 
 
-def staged_search(idx, queries, k, nprobe, knn, ops, score_bytes):
+def staged_search(idx, queries, k, nprobe, knn, ops, score_bytes, refine=0, base=None):
     """IVFIndex.search stage by stage (the same calls), every stage between device events; (ms by stage, D, I, stats)"""
     ms = {"coarse": 0.0, "tables": 0.0, "scan": 0.0, "merge": 0.0}
     dev = idx.device
     cap = ops.knn_list_capacity()
+    f16 = idx.storage == "f16"
+    if f16:
+        ms["round"] = 0.0
+    if refine:
+        ms["refine"] = 0.0
 
     def coarse():
         Q = idx._prepared(queries, dev, idx.l2_norm)
@@ -51,6 +59,8 @@ def staged_search(idx, queries, k, nprobe, knn, ops, score_bytes):
     nq = Q.shape[0]
     best_d = torch.empty((nq, cap), dtype=torch.float32, device=dev)
     best_i = torch.empty((nq, cap), dtype=torch.int32, device=dev)
+    cand_d = torch.empty_like(best_d) if refine else best_d
+    cand_i = torch.empty_like(best_i) if refine else best_i
 
     def plan():
         ld = (idx.list_len + 3) // 4 * 4
@@ -68,13 +78,27 @@ def staged_search(idx, queries, k, nprobe, knn, ops, score_bytes):
             best_d[q0:q1], best_i[q0:q1] = float("inf"), 0x7fffffff
             continue
         scores = torch.empty(max(tb["n_floats"], 4), dtype=torch.float32, device=dev)
+        if f16:
+            def rounded():
+                Qh = Q[q0:q1].to(torch.float16)
+                ops.row_sqnorm(Qh.float(), Qh.shape[1], q_sq[q0:q1])
+                return Qh
+            t, Qh = timed(rounded)
+            ms["round"] += t
         if tb["n_tiles"]:
-            t, _ = timed(lambda: ops.ivf_scan_f32(Q[q0:q1], tb["slot_query"], tb["slot_start"], tb["slot_off"], idx.rows,
-                                                  idx.list_start, tb["tiles"], scores))
+            if f16:
+                t, _ = timed(lambda: ops.ivf_scan_f16(Qh, tb["slot_query"], tb["slot_start"], tb["slot_off"], idx.rows,
+                                                      idx.list_start, tb["tiles"], scores))
+            else:
+                t, _ = timed(lambda: ops.ivf_scan_f32(Q[q0:q1], tb["slot_query"], tb["slot_start"], tb["slot_off"], idx.rows,
+                                                      idx.list_start, tb["tiles"], scores))
             ms["scan"] += t
         t, _ = timed(lambda: ops.ivf_merge(scores, tb["slot_off"], tb["slot_of"], pc, idx.list_start, idx.ids, idx.r_sq,
-                                           q_sq[q0:q1], k, best_d[q0:q1], best_i[q0:q1]))
+                                           q_sq[q0:q1], refine or k, cand_d[q0:q1], cand_i[q0:q1]))
         ms["merge"] += t
+        if refine:
+            t, _ = timed(lambda: ops.ivf_refine(Q[q0:q1], base, cand_i[q0:q1], refine, k, best_d[q0:q1], best_i[q0:q1]))
+            ms["refine"] += t
         tiles += tb["n_tiles"]
         floats += tb["n_floats"]
         cnt = (tb["slot_start"][1:] - tb["slot_start"][:-1]).to(torch.int64)
@@ -98,6 +122,8 @@ def main():
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--sample", type=int, default=65536, help="queries of the recall sample when n is above it (--big)")
     ap.add_argument("--score-bytes", type=int, default=None)
+    ap.add_argument("--storage", nargs="*", default=["f32"], choices=["f32", "f16"], help="list formats to time, over one (centroids, assign)")
+    ap.add_argument("--refine", type=int, default=0, help="re-rank depth r of the f16 index (k <= r <= 128); 0 = none")
     a = ap.parse_args()
     from cdml_amd import knn, ops
     dev = torch.device("cuda:0")
@@ -125,29 +151,46 @@ def main():
         del X
         lens = idx.list_len.double()
         score_bytes = a.score_bytes or idx.default_score_bytes()
+        indexes = []
+        for storage in a.storage:
+            if storage == "f32":
+                indexes.append((idx, None))
+            else:                                                                                         # the same (centroids, assign), fp16 lists
+                h = knn.IVFIndex.load_state_dict(idx.state_dict(), x, device=dev, storage="f16")
+                indexes.append((h, h.prepare(x) if a.refine else None))
         for nprobe in nprobes:
-            staged_search(idx, x[:8192], k, nprobe, knn, ops, score_bytes)                                # warm
-            ms, _, I, st = staged_search(idx, x, k, nprobe, knn, ops, score_bytes)                        # the self-search, all rows
-            Is = I if sample is None else I[sample]
-            hit = found = 0
-            for r0 in range(0, Is.shape[0], 32768):                                                       # (recall in row blocks)
-                a_, b_ = Is[r0:r0 + 32768], Ie[r0:r0 + 32768]
-                hit += int(((a_.unsqueeze(2) == b_.unsqueeze(1)).any(2) & (a_ >= 0)).sum())
-                found += int((b_ >= 0).sum())
-            recall = hit / max(found, 1)
-            del I, Is
-            total = sum(ms.values())
-            print(json.dumps({
-                "what": "ivf", "n": n, "nq": n, "recall_queries": Ie.shape[0], "dim": a.dim, "k": k, "nlist": nlist, "nprobe": nprobe, "iters": a.iters,
-                "build_ms": round(build_ms, 2), "assign_all_rows_ms": round(assign_ms, 3), "centroid_update_ms": round(update_ms, 3),
-                "search_ms": round(total, 3), "stages_ms": {s: round(v, 3) for s, v in ms.items()},
-                "exact_ms": round(exact_ms, 3), "exact_nq": xq.shape[0], "speedup": round(exact_ms / total, 2) if sample is None else None,
-                "scan_tflops_tiles": round(st["scan_flop_tiles"] / max(ms["scan"], 1e-9) / 1e9, 2),
-                "scan_tflops_useful": round(st["scan_flop_useful"] / max(ms["scan"], 1e-9) / 1e9, 2),
-                "score_bytes": st["score_bytes"], "score_budget": score_bytes, "chunks": st["chunks"], "recall": round(recall, 4),
-                "list_max_over_mean": round(float(lens.max() / lens.mean()), 2), "empty_lists": int((lens == 0).sum()),
-                "scanned_share": round(idx.scanned_share(st["probe"]), 5), "nprobe_over_nlist": round(nprobe / nlist, 5)}), flush=True)
+            for index, base in indexes:
+                for refine in ([0] if base is None else [0, a.refine]):
+                    run_one(index, base, refine, nprobe, nlist, x, k, n, a, knn, ops, sample, Ie, xq, exact_ms, score_bytes,
+                            build_ms, assign_ms, update_ms, lens)
 
+
+def run_one(idx, base, refine, nprobe, nlist, x, k, n, a, knn, ops, sample, Ie, xq, exact_ms, score_bytes, build_ms, assign_ms,
+            update_ms, lens):
+    kw = dict(refine=refine, base=base) if refine else {}
+    staged_search(idx, x[:8192], k, nprobe, knn, ops, score_bytes, **kw)                                  # warm
+    ms, _, I, st = staged_search(idx, x, k, nprobe, knn, ops, score_bytes, **kw)                          # the self-search, all rows
+    Is = I if sample is None else I[sample]
+    hit = found = 0
+    for r0 in range(0, Is.shape[0], 32768):                                                               # (recall in row blocks)
+        a_, b_ = Is[r0:r0 + 32768], Ie[r0:r0 + 32768]
+        hit += int(((a_.unsqueeze(2) == b_.unsqueeze(1)).any(2) & (a_ >= 0)).sum())
+        found += int((b_ >= 0).sum())
+    recall = hit / max(found, 1)
+    del I, Is
+    total = sum(ms.values())
+    index_bytes = sum(t.numel() * t.element_size() for t in (idx.rows, idx.r_sq, idx.ids, idx.list_start, idx._C))
+    print(json.dumps({
+        "what": "ivf", "storage": idx.storage, "refine": refine, "index_bytes": index_bytes,
+        "n": n, "nq": n, "recall_queries": Ie.shape[0], "dim": a.dim, "k": k, "nlist": nlist, "nprobe": nprobe, "iters": a.iters,
+        "build_ms": round(build_ms, 2), "assign_all_rows_ms": round(assign_ms, 3), "centroid_update_ms": round(update_ms, 3),
+        "search_ms": round(total, 3), "stages_ms": {s: round(v, 3) for s, v in ms.items()},
+        "exact_ms": round(exact_ms, 3), "exact_nq": xq.shape[0], "speedup": round(exact_ms / total, 2) if sample is None else None,
+        "scan_tflops_tiles": round(st["scan_flop_tiles"] / max(ms["scan"], 1e-9) / 1e9, 2),
+        "scan_tflops_useful": round(st["scan_flop_useful"] / max(ms["scan"], 1e-9) / 1e9, 2),
+        "score_bytes": st["score_bytes"], "score_budget": score_bytes, "chunks": st["chunks"], "recall": round(recall, 4),
+        "list_max_over_mean": round(float(lens.max() / lens.mean()), 2), "empty_lists": int((lens == 0).sum()),
+        "scanned_share": round(idx.scanned_share(st["probe"]), 5), "nprobe_over_nlist": round(nprobe / nlist, 5)}), flush=True)
 
 if __name__ == "__main__":
     main()
