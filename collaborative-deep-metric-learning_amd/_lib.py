@@ -295,6 +295,14 @@ SIGNATURES_IVF_F16 = {
     "cdml_ivf_refine": (_i, [_p, _i64, _i, _p, _i64, _i64, _i, _p, _i, _i, _p, _p, _p]),
 }
 
+# name -> (restype, argtypes); must list every symbol include/cdml_ivf_filter.h declares (the threshold-filter scan of the IVF
+# index: the grouped score product whose epilogue appends what is within tau to the query's candidate list, no score buffer)
+_IVF_FILTER_ARGS = [_p, _i64, _i, _p, _p, _p, _p, _p, _p, _i64, _p, _p, _p, _i, _p, _i, _p, _i, _p]
+SIGNATURES_IVF_FILTER = {
+    "cdml_ivf_filter_f32": (_i, _IVF_FILTER_ARGS),
+    "cdml_ivf_filter_f16": (_i, list(_IVF_FILTER_ARGS)),
+}
+
 _lib = None
 
 
@@ -316,7 +324,7 @@ def load_library():
     for name, (res, args) in (list(SIGNATURES.items()) + list(SIGNATURES_MIXED.items()) + list(SIGNATURES_DP.items())
                                + list(SIGNATURES_BF16.items()) + list(SIGNATURES_HARDNEG.items()) + list(SIGNATURES_WIDE.items())
                                + list(SIGNATURES_NEGW.items()) + list(SIGNATURES_F8.items()) + list(SIGNATURES_IVF.items())
-                               + list(SIGNATURES_IVF_F16.items())):
+                               + list(SIGNATURES_IVF_F16.items()) + list(SIGNATURES_IVF_FILTER.items())):
         fn = getattr(lib, name)          # AttributeError if the ABI lost a symbol
         fn.restype = res
         fn.argtypes = args

@@ -64,7 +64,7 @@ def filter_lists(I, k, skip_top=0, pairs=None):
 
 
 def mine_lists(embeddings, k, skip_top=0, pairs=None, device="cuda:0", precision="f32x3", nlist=0, nprobe=0, ivf_iters=10,
-               ivf_seed=0, storage="f32", refine=0):
+               ivf_seed=0, storage="f32", refine=0, scan="buffer"):
     """Candidate negatives of every row: int32 [n, L] device tensor, L = k rounded up to a multiple of 4.
 
     A self-kNN over ``embeddings`` ([n, D] ndarray or tensor; l2-normalised first, as ``knn.calc_knn`` does) with
@@ -75,12 +75,16 @@ def mine_lists(embeddings, k, skip_top=0, pairs=None, device="cuda:0", precision
     iters=ivf_iters, seed=ivf_seed)`` and its ``search(e, k + skip_top + 1, nprobe)``: approximate -- a neighbour outside a
     row's ``nprobe`` nearest lists is missed -- and sub-linear in the catalogue); the filter is the same.
     ``storage`` ("f32" | "f16") and ``refine`` go to that index (``knn.IVFIndex``: fp16 lists at half the bytes, scanned on
-    the fp16 MFMA; ``refine=r`` re-ranks the r best candidates of a row against the fp32 embeddings given here)."""
+    the fp16 MFMA; ``refine=r`` re-ranks the r best candidates of a row against the fp32 embeddings given here); ``scan``
+    ("buffer" | "filter") is that index's search mode (``IVFIndex.search``: the same lists either way, "filter" without a score
+    buffer behind the seed probes)."""
     k, skip_top, nlist, nprobe = int(k), int(skip_top), int(nlist), int(nprobe)
     if nlist < 0 or (nlist == 0 and nprobe != 0):
         raise ValueError("mine_lists takes nlist >= 0, and nprobe only with nlist > 0 (got nlist = %d, nprobe = %d)" % (nlist, nprobe))
     if nlist == 0 and (storage != "f32" or int(refine) != 0):
         raise ValueError("mine_lists takes storage and refine only with nlist > 0 (got storage = %r, refine = %d)" % (storage, int(refine)))
+    if scan not in knn.IVFIndex.SCANS or (nlist == 0 and scan != "buffer"):
+        raise ValueError("mine_lists takes scan in %s, and \"filter\" only with nlist > 0 (got scan = %r)" % (knn.IVFIndex.SCANS, scan))
     if k < 1 or skip_top < 0:
         raise ValueError("mine_lists needs k >= 1 and skip_top >= 0, got %d and %d" % (k, skip_top))
     if list_width(k) > 1024:
@@ -90,7 +94,8 @@ def mine_lists(embeddings, k, skip_top=0, pairs=None, device="cuda:0", precision
     e = e.to(device=dev, dtype=torch.float32)
     if nlist > 0:
         index = knn.IVFIndex.build(e, nlist, iters=ivf_iters, seed=ivf_seed, device=dev, precision=precision, storage=storage)
-        _, I = index.search(e, k + skip_top + 1, nprobe, refine=int(refine), base=index.prepare(e) if int(refine) else None)
+        _, I = index.search(e, k + skip_top + 1, nprobe, refine=int(refine), base=index.prepare(e) if int(refine) else None,
+                            scan=scan)
     else:
         _, I = knn.knn_search(e, e, k + skip_top + 1, device=dev, precision=precision)
     if pairs is not None and not torch.is_tensor(pairs):

@@ -418,7 +418,11 @@ class IVFIndex:
     ``storage="f16"`` (include/cdml_ivf_f16.h): ``rows`` is the fp16 image of the prepared rows (half
     the bytes; the fp32 prepared matrix is not kept), ``r_sq`` the fp32 squared norms of the rounded values, a row whose
     image overflows is unlisted; k-means, ``assign``, ``centroids`` and the probes are those of the fp32 index.  ``search``
-    then scans on the fp16 MFMA, and ``refine=r`` re-scores the r best candidates against fp32 rows (``base=``)."""
+    then scans on the fp16 MFMA, and ``refine=r`` re-scores the r best candidates against fp32 rows (``base=``).
+
+    ``search(..., scan="filter")`` (include/cdml_ivf_filter.h) is the same search, bit for bit, with a
+    score buffer for the first ``seed_probes`` probe columns only: the other columns append what is within the seeded
+    threshold to ``filter_cap`` candidate slots per query."""
 
     STORAGES = ("f32", "f16")
     _NORM_ROWS = 1 << 20        # rows per fp32 temporary when the squared norms of fp16 rows are taken
@@ -649,7 +653,167 @@ class IVFIndex:
                                 (tuple(base.shape), base.dtype, str(base.device)) if torch.is_tensor(base) else type(base).__name__))
         return r, base
 
-    def search(self, queries, k, nprobe, score_bytes=None, stats=None, probe=None, refine=0, base=None):
+    SCANS = ("buffer", "filter")
+    FILTER_CAP_MIN, FILTER_CAP_MAX = 64, 65536
+
+    def default_seed_probes(self, keep, nprobe):
+        """min(nprobe, max(1, ceil(4 keep nlist / n_listed))): the probe columns whose lists hold 4 keep rows on average, so
+        that short lists do not leave the seeded threshold at +inf.  Pure host arithmetic."""
+        keep, nprobe = int(keep), int(nprobe)
+        return min(nprobe, max(1, -(-4 * keep * self.nlist // self.n_listed)))
+
+    @classmethod
+    def default_filter_cap(cls, keep):
+        """the smallest power of two >= 4 keep, at least 64: the candidate slots per query of ``scan="filter"``"""
+        cap = cls.FILTER_CAP_MIN
+        while cap < 4 * int(keep):
+            cap *= 2
+        return cap
+
+    def filter_costs(self, probe, seed_probes, filter_cap):
+        """int64 ndarray [nq]: a query's floats in a chunk of ``scan="filter"`` = the padded lengths of its SEED lists (the
+        first ``seed_probes`` columns of ``probe``, -1 = none) + 2 ``filter_cap`` (its candidate slots, 8 B each); what
+        ``ivf_plan_chunks`` plans that search with."""
+        p = probe[:, :int(seed_probes)].to(torch.int64)
+        ld = (self.list_len + 3) // 4 * 4
+        return (torch.where(p >= 0, ld[p.clamp(min=0)], torch.zeros_like(p)).sum(1) + 2 * int(filter_cap)).cpu().numpy()
+
+    def _check_scan(self, scan, filter_cap, seed_probes, nprobe):
+        """the refusals of ``search``'s scan arguments, by name, before any device work"""
+        if scan not in self.SCANS:
+            raise ValueError("scan must be one of %s, got %r" % (self.SCANS, scan))
+        if scan == "buffer":
+            if filter_cap is not None or seed_probes is not None:
+                raise ValueError("filter_cap and seed_probes belong to scan=\"filter\" (this search is scan=\"buffer\")")
+            return
+        if filter_cap is not None:
+            c = int(filter_cap)
+            if c != filter_cap or not self.FILTER_CAP_MIN <= c <= self.FILTER_CAP_MAX or c & (c - 1):
+                raise ValueError("filter_cap must be a power of two in [%d, %d], got %r"
+                                 % (self.FILTER_CAP_MIN, self.FILTER_CAP_MAX, filter_cap))
+        if seed_probes is not None and (int(seed_probes) != seed_probes or not 1 <= int(seed_probes) <= int(nprobe)):
+            raise ValueError("seed_probes must be in [1, nprobe = %d], got %r" % (int(nprobe), seed_probes))
+
+    def _scan_buffered(self, Q, q_sq, probe, k, refine, base, score_bytes, best_d, best_i, cand_d, cand_i):
+        """The buffered search of prepared queries ``Q`` over ``probe`` (int32 [nq, nprobe]) into best_d / best_i (and cand_d /
+        cand_i, the merge's lists, when they are other tensors: ``refine``): per chunk the slot tables, the grouped product
+        into the ragged score buffer, the merge, the re-rank.  Returns (chunks, n_tiles, n_floats)."""
+        f16 = self.storage == "f16"
+        Dp = Q.shape[1]
+        nprobe = probe.shape[1]
+        ld = (self.list_len + 3) // 4 * 4
+        p = probe.to(torch.int64)
+        costs = torch.where(p >= 0, ld[p.clamp(min=0)], torch.zeros_like(p)).sum(1).cpu().numpy()
+        chunks = ivf_plan_chunks(costs, score_bytes, max_queries=(2 ** 31 - 1) // nprobe)
+        n_tiles = n_floats = 0
+        keep = refine or k                                # entries the merge must get right
+        for q0, q1 in chunks:
+            pc = probe[q0:q1].contiguous()
+            tb = ivf_tables(pc, self.list_len)
+            n_tiles += tb["n_tiles"]
+            n_floats += tb["n_floats"]
+            if tb["n_slots"] == 0:                        # nothing probed (non-finite queries only)
+                best_d[q0:q1] = float("inf")
+                best_i[q0:q1] = 0x7fffffff
+                if refine:
+                    cand_i[q0:q1] = 0x7fffffff
+                continue
+            scores = torch.empty(max(tb["n_floats"], 4), dtype=torch.float32, device=Q.device)
+            if f16:
+                Qh = Q[q0:q1].to(torch.float16)
+                ops.row_sqnorm(Qh.float(), Dp, q_sq[q0:q1])
+                if tb["n_tiles"]:
+                    ops.ivf_scan_f16(Qh, tb["slot_query"], tb["slot_start"], tb["slot_off"], self.rows, self.list_start,
+                                     tb["tiles"], scores)
+            elif tb["n_tiles"]:
+                ops.ivf_scan_f32(Q[q0:q1], tb["slot_query"], tb["slot_start"], tb["slot_off"], self.rows, self.list_start,
+                                 tb["tiles"], scores)
+            ops.ivf_merge(scores, tb["slot_off"], tb["slot_of"], pc, self.list_start, self.ids, self.r_sq, q_sq[q0:q1], keep,
+                          cand_d[q0:q1], cand_i[q0:q1])
+            if refine:
+                ops.ivf_refine(Q[q0:q1], base, cand_i[q0:q1], refine, k, best_d[q0:q1], best_i[q0:q1])
+        return chunks, n_tiles, n_floats
+
+    def _scan_filtered(self, Q, q_sq, probe, k, refine, base, score_bytes, best_d, best_i, cand_d, cand_i, s, cap_f, stats):
+        """``scan="filter"`` (include/cdml_ivf_filter.h): per chunk, the first ``s`` probe columns through the buffered launches
+        (every query's list and its keep-th distance tau), the other columns through ONE filter launch that writes no score
+        and appends what is within tau to the query's ``cap_f`` candidate slots, ``knn_merge_list``, the re-rank.  A query
+        whose count exceeded ``cap_f`` is searched again through ``_scan_buffered`` over its whole probe row."""
+        f16 = self.storage == "f16"
+        dev = Q.device
+        Dp = Q.shape[1]
+        nq, nprobe = probe.shape
+        keep = refine or k
+        ld = (self.list_len + 3) // 4 * 4
+        seed_p, rest_p = probe.clone(), probe.clone()
+        seed_p[:, s:] = -1                                    # a list is scanned by the seed or by the filter, never by both
+        rest_p[:, :s] = -1
+        chunks = ivf_plan_chunks(self.filter_costs(probe, s, cap_f), score_bytes, max_queries=(2 ** 31 - 1) // nprobe)
+        n_tiles = n_floats = n_appended = 0
+        redo = []
+        overflow = torch.zeros(1, dtype=torch.int32, device=dev)
+        for q0, q1 in chunks:
+            m = q1 - q0
+            pc = seed_p[q0:q1].contiguous()
+            tb = ivf_tables(pc, self.list_len)
+            n_tiles += tb["n_tiles"]
+            n_floats += tb["n_floats"]
+            Qc = Q[q0:q1]
+            if f16:
+                Qc = Qc.to(torch.float16)
+                ops.row_sqnorm(Qc.float(), Dp, q_sq[q0:q1])
+            if tb["n_slots"] == 0:                        # nothing seeded: the lists ivf_merge leaves for no row
+                cand_d[q0:q1] = float("inf")
+                cand_i[q0:q1] = 0x7fffffff
+            else:
+                scores = torch.empty(max(tb["n_floats"], 4), dtype=torch.float32, device=dev)
+                if tb["n_tiles"]:
+                    (ops.ivf_scan_f16 if f16 else ops.ivf_scan_f32)(Qc, tb["slot_query"], tb["slot_start"], tb["slot_off"], self.rows,
+                                                                   self.list_start, tb["tiles"], scores)
+                ops.ivf_merge(scores, tb["slot_off"], tb["slot_of"], pc, self.list_start, self.ids, self.r_sq, q_sq[q0:q1], keep,
+                              cand_d[q0:q1], cand_i[q0:q1])
+                del scores
+            if s < nprobe:
+                tr = ivf_tables(rest_p[q0:q1].contiguous(), self.list_len)
+                n_tiles += tr["n_tiles"]
+                if tr["n_tiles"]:
+                    tau = cand_d[q0:q1, keep - 1].contiguous()            # +inf where fewer than keep rows were seeded
+                    cnt = torch.zeros(m, dtype=torch.int32, device=dev)
+                    cand = torch.empty((m, cap_f, 2), dtype=torch.int32, device=dev)
+                    (ops.ivf_filter_f16 if f16 else ops.ivf_filter_f32)(Qc, tr["slot_query"], tr["slot_start"], q_sq[q0:q1], tau, cnt,
+                                                                       self.rows, self.list_start, self.r_sq, self.ids, tr["tiles"],
+                                                                       cand, cap_f)
+                    over = cnt > cap_f                        # (before the merge puts cnt back to 0)
+                    n_over, n_app = torch.stack([over.sum(), cnt.sum()]).tolist()         # the host read
+                    n_appended += n_app
+                    ops.knn_merge_list(cand, cnt, cap_f, m, keep, cand_d[q0:q1], cand_i[q0:q1], overflow)
+                    if n_over:
+                        redo.append(torch.nonzero(over).flatten() + q0)
+            if refine:
+                ops.ivf_refine(Q[q0:q1], base, cand_i[q0:q1], refine, k, best_d[q0:q1], best_i[q0:q1])
+        n_redo = 0
+        if redo:                                              # candidates were dropped: these queries go through the score buffer
+            idx = torch.cat(redo)
+            n_redo = int(idx.numel())
+            po = probe.index_select(0, idx)
+            pl = po.to(torch.int64)
+            own = int(torch.where(pl >= 0, ld[pl.clamp(min=0)], torch.zeros_like(pl)).sum(1).max())
+            bd = torch.empty((n_redo, best_d.shape[1]), dtype=torch.float32, device=dev)
+            bi = torch.empty((n_redo, best_i.shape[1]), dtype=torch.int32, device=dev)
+            cd = torch.empty_like(bd) if refine else bd
+            ci = torch.empty_like(bi) if refine else bi
+            # (the budget covers one such query's own scores even where ``score_bytes`` is below them)
+            self._scan_buffered(Q.index_select(0, idx), q_sq.index_select(0, idx), po, k, refine, base, max(int(score_bytes), 4 * own),
+                                bd, bi, cd, ci)
+            best_d[idx], best_i[idx] = bd, bi
+            if refine:
+                cand_d[idx], cand_i[idx] = cd, ci
+        if stats is not None:
+            stats.update(scan="filter", seed_probes=s, filter_cap=cap_f, n_appended=int(n_appended), refiltered=n_redo)
+        return chunks, n_tiles, n_floats
+
+    def search(self, queries, k, nprobe, score_bytes=None, stats=None, probe=None, refine=0, base=None, scan="buffer",
+               filter_cap=None, seed_probes=None):
         """(D [nq, k] fp32 squared L2 ascending, I [nq, k] int64; +inf / -1 where fewer than k rows were probed), device
         tensors shaped and typed like ``knn_search``'s.  Queries go in chunks whose ragged score buffer fits ``score_bytes``
         (default ``default_score_bytes()``: 1 GiB, or 2 KiB per listed row where that is more -- 20 GB at 10 M rows;
@@ -659,10 +823,23 @@ class IVFIndex:
         On an index with storage "f16" a chunk's queries are rounded to fp16 as the rows were and the distances are those
         of the rounded values (a query whose image is non-finite probes nothing); ``refine=r`` (k <= r <= 128, with
         ``base`` = the fp32 matrix of ``prepare(catalogue)``) keeps the r best of them and returns the k best under the fp32
-        distances sum (q - x)^2 of the fp32 rows (include/cdml_ivf_f16.h)."""
+        distances sum (q - x)^2 of the fp32 rows (include/cdml_ivf_f16.h).
+        ``scan="filter"`` (include/cdml_ivf_filter.h) writes scores only for the first ``seed_probes``
+        probe columns (default ``default_seed_probes(refine or k, nprobe)``): they give every query a keep-th distance tau
+        (keep = refine or k), and one launch over the other columns appends what is within tau to ``filter_cap`` candidate
+        slots per query (a power of two in [64, 65536]; default ``default_filter_cap(keep)``).  (D, I) are those of
+        ``scan="buffer"`` bit for bit, for either storage and any refine, chunking, query order, ``filter_cap`` and
+        ``seed_probes`` (the merged lists agree in their first keep entries; what lies behind them is not promised): a query
+        that collects more than ``filter_cap`` candidates is searched again through the score buffer over its whole probe
+        row (with the budget raised to its own scores where ``score_bytes`` is below them), so nothing is lost.  A chunk then
+        holds the SEED lists' scores plus 8 B x ``filter_cap`` per query within ``score_bytes``: a query whose own probed
+        lists exceed the budget is accepted whenever its seed lists fit.  ``stats`` gains ``scan``, ``seed_probes``,
+        ``filter_cap``, ``n_appended`` (candidates counted over all chunks, dropped ones included) and ``refiltered`` (queries
+        searched again); ``n_floats`` is the seed floats, ``n_tiles`` the tiles of the seed and filter scans."""
         self._check_queries(queries, nprobe, k)
         k, nprobe = int(k), int(nprobe)
         refine, base = self._check_refine(k, refine, base)
+        self._check_scan(scan, filter_cap, seed_probes, nprobe)
         if probe is not None:
             probe = torch.as_tensor(probe)
             if tuple(probe.shape) != (queries.shape[0], nprobe) or probe.is_floating_point():
@@ -685,40 +862,18 @@ class IVFIndex:
             if f16:                                           # a query with no finite fp16 image probes nothing
                 lost = (Q.abs() >= 65520.0).any(1)            # (fp32 -> fp16 rounds to inf from 65520 on; NaN queries have -1 probes already)
                 probe = torch.where(lost[:, None], torch.full_like(probe, -1), probe)
-            ld = (self.list_len + 3) // 4 * 4
-            p = probe.to(torch.int64)
-            costs = torch.where(p >= 0, ld[p.clamp(min=0)], torch.zeros_like(p)).sum(1).cpu().numpy()
-            chunks = ivf_plan_chunks(costs, self.default_score_bytes() if score_bytes is None else score_bytes,
-                                     max_queries=(2 ** 31 - 1) // nprobe)
-            n_tiles = n_floats = 0
+            budget = self.default_score_bytes() if score_bytes is None else score_bytes
             keep = refine or k                                # entries the merge must get right
             cand_d = torch.empty_like(best_d) if refine else best_d
             cand_i = torch.empty_like(best_i) if refine else best_i
-            for q0, q1 in chunks:
-                pc = probe[q0:q1].contiguous()
-                tb = ivf_tables(pc, self.list_len)
-                n_tiles += tb["n_tiles"]
-                n_floats += tb["n_floats"]
-                if tb["n_slots"] == 0:                        # nothing probed (non-finite queries only)
-                    best_d[q0:q1] = float("inf")
-                    best_i[q0:q1] = 0x7fffffff
-                    if refine:
-                        cand_i[q0:q1] = 0x7fffffff
-                    continue
-                scores = torch.empty(max(tb["n_floats"], 4), dtype=torch.float32, device=dev)
-                if f16:
-                    Qh = Q[q0:q1].to(torch.float16)
-                    ops.row_sqnorm(Qh.float(), Dp, q_sq[q0:q1])
-                    if tb["n_tiles"]:
-                        ops.ivf_scan_f16(Qh, tb["slot_query"], tb["slot_start"], tb["slot_off"], self.rows, self.list_start,
-                                         tb["tiles"], scores)
-                elif tb["n_tiles"]:
-                    ops.ivf_scan_f32(Q[q0:q1], tb["slot_query"], tb["slot_start"], tb["slot_off"], self.rows, self.list_start,
-                                     tb["tiles"], scores)
-                ops.ivf_merge(scores, tb["slot_off"], tb["slot_of"], pc, self.list_start, self.ids, self.r_sq, q_sq[q0:q1], keep,
-                              cand_d[q0:q1], cand_i[q0:q1])
-                if refine:
-                    ops.ivf_refine(Q[q0:q1], base, cand_i[q0:q1], refine, k, best_d[q0:q1], best_i[q0:q1])
+            if scan == "filter":
+                chunks, n_tiles, n_floats = self._scan_filtered(
+                    Q, q_sq, probe, k, refine, base, budget, best_d, best_i, cand_d, cand_i,
+                    self.default_seed_probes(keep, nprobe) if seed_probes is None else int(seed_probes),
+                    self.default_filter_cap(keep) if filter_cap is None else int(filter_cap), stats)
+            else:
+                chunks, n_tiles, n_floats = self._scan_buffered(Q, q_sq, probe, k, refine, base, budget, best_d, best_i, cand_d,
+                                                                cand_i)
             if stats is not None:
                 stats.update(chunks=chunks, n_tiles=n_tiles, n_floats=n_floats, probe=probe)
                 if refine:

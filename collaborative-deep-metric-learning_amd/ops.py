@@ -1761,6 +1761,44 @@ def ivf_refine(Q, base, cand, r, k, best_d, best_i):
          _vec(best_d, torch.float32, nq * cap, "best_d"), _vec(best_i, torch.int32, nq * cap, "best_i"), _stream())
 
 
+# ---------------------------------------- threshold-filter scan of the IVF index (include/cdml_ivf_filter.h) ------
+def _ivf_filter(name, qp, qld, rp, rld, Q, slot_query, slot_start, q_sq, tau, cnt, rows, list_start, r_sq, ids, tiles, cand, cap):
+    nlist = list_start.numel() - 1
+    nq, n_listed, cap = Q.shape[0], rows.shape[0], int(cap)
+    if tiles.dim() != 2 or tiles.shape[1] != 4:
+        raise ValueError("tiles must be int32 [n_tiles, 4]")
+    if cand.dtype != torch.int32 or not cand.is_contiguous() or cand.numel() < 2 * nq * cap:
+        raise ValueError("cand must be a contiguous int32 tensor of at least [nq = %d, cap = %d, 2]" % (nq, cap))
+    call(name, qp, qld, nq, _vec(slot_query, torch.int32, 0, "slot_query"), _vec(slot_start, torch.int32, nlist + 1, "slot_start"),
+         _vec(q_sq, torch.float32, nq, "q_sq"), _vec(tau, torch.float32, nq, "tau"), _vec(cnt, torch.int32, nq, "cnt"), rp, rld,
+         _vec(list_start, torch.int32, nlist + 1, "list_start"), _vec(r_sq, torch.float32, n_listed, "r_sq"),
+         _vec(ids, torch.int32, n_listed, "ids"), Q.shape[1], _vec(tiles, torch.int32, 4, "tiles"), tiles.shape[0],
+         _p(cand, torch.int32), cap, _stream())
+    return cnt
+
+
+def ivf_filter_f32(Q, slot_query, slot_start, q_sq, tau, cnt, rows, list_start, r_sq, ids, tiles, cand, cap):
+    """``ivf_scan_f32``'s grouped product over the tiles of ``tiles`` with no score buffer: every (query q, listed row)
+    element with d = max((q_sq[q] + r_sq[row]) - 2 s, 0) <= tau[q] takes slot pos = cnt[q]++ of the query's candidate list and,
+    when pos < cap, writes cand[q, pos] = (the bits of d, ids[row]) (cand int32 [nq, cap, 2]; cap a power of two)."""
+    qp, qld = _mat(Q)
+    rp, rld = _mat(rows)
+    if Q.shape[1] != rows.shape[1]:
+        raise ValueError("queries and list rows of one padded width")
+    return _ivf_filter("cdml_ivf_filter_f32", qp, qld, rp, rld, Q, slot_query, slot_start, q_sq, tau, cnt, rows, list_start, r_sq,
+                       ids, tiles, cand, cap)
+
+
+def ivf_filter_f16(Q, slot_query, slot_start, q_sq, tau, cnt, rows, list_start, r_sq, ids, tiles, cand, cap):
+    """``ivf_filter_f32`` with fp16 queries and list rows (torch.float16): ``ivf_scan_f16``'s product on the fp16 MFMA."""
+    if Q.dtype != torch.float16 or rows.dtype != torch.float16:
+        raise ValueError("ivf_filter_f16 takes float16 queries and list rows")
+    if Q.dim() != 2 or rows.dim() != 2 or Q.stride(1) != 1 or rows.stride(1) != 1 or Q.shape[1] != rows.shape[1]:
+        raise ValueError("queries and list rows: 2-D, unit inner stride, one padded width")
+    return _ivf_filter("cdml_ivf_filter_f16", _p(Q), Q.stride(0), _p(rows), rows.stride(0), Q, slot_query, slot_start, q_sq, tau,
+                       cnt, rows, list_start, r_sq, ids, tiles, cand, cap)
+
+
 def knn_desim_prep(fI, fD, fI_end, threshold, out):
     """The raw-feature lists fI (int32 | int64 [n_f, kf]) with their distances fD (fp32) filtered into out (int32
     [n_f, kp], kp = 32 | 64): fI[r, t] for t < fI_end where fD <= threshold (float32), fI != r, fI >= 0; else -1."""

@@ -673,13 +673,15 @@ class TrainStep:
             raise ValueError("this step has no negative lists (TrainStep(negative_lists=...))")
         return float(self.kind.sum().item()) / self.B
 
-    def refresh_negative_lists(self, k, skip_top=0, drop_partners=True, nlist=0, nprobe=0, storage="f32", refine=0):
+    def refresh_negative_lists(self, k, skip_top=0, drop_partners=True, nlist=0, nprobe=0, storage="f32", refine=0,
+                               scan="buffer"):
         """Embed the catalogue with the CURRENT weights (the catalogue-inference path: predict.Prediction.embed_table),
         mine every row's k nearest neighbours behind the ``skip_top`` nearest (hardneg.mine_lists; ``drop_partners``: less the
         row's known co-watch partners, the step's own pairs) and copy them into the step's lists.  L = k rounded up to a
         multiple of 4 must be the width the step was built with.  ``nlist`` > 0: the neighbours come from an IVF index over
         the embeddings, ``nprobe`` lists per row (hardneg.mine_lists: approximate, sub-linear in the catalogue); ``storage`` and
-        ``refine`` are that index's (fp16 lists, re-ranked against the embeddings).  Off the step path (allocates and
+        ``refine`` are that index's (fp16 lists, re-ranked against the embeddings), ``scan`` its search mode ("buffer" | "filter": the
+        same lists).  Off the step path (allocates and
         synchronises)."""
         from . import hardneg
         from .predict import Prediction
@@ -692,7 +694,7 @@ class TrainStep:
             self._list_predictor = Prediction(params=self.params, precision=self.ws.INFERENCE)
         emb = self._list_predictor.embed_table(self.table, 16384)
         lists = hardneg.mine_lists(emb, k, skip_top=skip_top, pairs=self.pairs if drop_partners else None, device=self.device,
-                                   nlist=nlist, nprobe=nprobe, storage=storage, refine=refine)
+                                   nlist=nlist, nprobe=nprobe, storage=storage, refine=refine, scan=scan)
         self.set_negative_lists(lists)
         return lists
 
@@ -1241,7 +1243,7 @@ class Trainer:
     hard-negative lists are re-mined from the current weights (``TrainStep.refresh_negative_lists(negative_k,
     skip_top=negative_skip_top, nlist=negative_nlist, nprobe=negative_nprobe)``; ``negative_k`` defaults to the lists' width;
     ``negative_nlist`` > 0 mines through an IVF index, ``negative_nprobe`` lists per row; ``negative_storage`` and
-    ``negative_refine`` are that index's ``storage`` and ``refine``).
+    ``negative_refine`` are that index's ``storage`` and ``refine``, ``negative_scan`` its search's ``scan``).
 
     Unlike the reference (which always re-initialises, train.py:280) a
     checkpoint also carries optimizer slots, step and sampler state, so
@@ -1251,7 +1253,7 @@ class Trainer:
                  eval_cowatches=None, check_stop_epoch=3, best_eval_dist=1.0, eval_per_epoch=100,
                  require_improve_num=10, logger=None, summary_path=None, eval_retrieval_ks=None,
                  refresh_negatives_every=None, negative_k=None, negative_skip_top=0, negative_nlist=0, negative_nprobe=0,
-                 negative_storage="f32", negative_refine=0):
+                 negative_storage="f32", negative_refine=0, negative_scan="buffer"):
         from .evaluate import Evaluation
         from .predict import Prediction
         self.ts = train_step
@@ -1276,6 +1278,7 @@ class Trainer:
         self.negative_skip_top = int(negative_skip_top)
         self.negative_nlist, self.negative_nprobe = int(negative_nlist), int(negative_nprobe)
         self.negative_storage, self.negative_refine = negative_storage, int(negative_refine)
+        self.negative_scan = negative_scan
         if self.refresh_negatives_every:
             if self.refresh_negatives_every < 1 or train_step.neg_lists is None:
                 raise ValueError("refresh_negatives_every needs a positive step count and a TrainStep(negative_lists=...)")
@@ -1390,7 +1393,7 @@ class Trainer:
             if self.refresh_negatives_every and gs % self.refresh_negatives_every == 0:
                 self.ts.refresh_negative_lists(self.negative_k, skip_top=self.negative_skip_top, nlist=self.negative_nlist,
                                                nprobe=self.negative_nprobe, storage=self.negative_storage,
-                                               refine=self.negative_refine)
+                                               refine=self.negative_refine, scan=self.negative_scan)
             self.ts.step()
             gs += 1
             if gs % self.show_step == 0 or gs == n:

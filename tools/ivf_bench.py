@@ -5,12 +5,16 @@
                                                  # (recall on a 65 536-query sample)
     python tools/ivf_bench.py --n 50000 --nlist 64 --nprobe 4 8 --k 20
     python tools/ivf_bench.py --storage f32 f16 --refine 128   # fp16 lists beside the fp32 ones over the same (centroids, assign)
+    python tools/ivf_bench.py --scan buffer filter             # the threshold-filter scan beside the buffered one, same index, same call
 
 Per run one JSON line: build time by stage (one assignment, one centroid update, the whole build), search time by stage
 (coarse / tables / scan / merge), the scan's FLOP from the tile table over its kernel time, recall@k against the exact search,
 max / mean list length, scanned share.  With --storage f16 the line of the fp16 index (storage "f16": the lists re-derived from
 the fp32 index's centroids and assign) follows the fp32 one: the same stages plus the re-rank, issued and useful scan TF/s,
-the index's bytes, and recall@k for refine 0 and --refine.  Rows are Gaussian mixtures (n / 64 centres, noise 0.5) so that lists mean something.
+the index's bytes, and recall@k for refine 0 and --refine.  With --scan filter a line "scan": "filter" follows every buffered
+line (under --score-bytes and under every --filter-score-bytes): the stages seed scan / seed merge / filter / merge_list /
+re-search, issued and useful TF/s of the seed scan and of the filter, the peak score + candidate bytes of a chunk, the candidates
+appended per query, the re-searched share, and whether (D, I) equal the buffered search's bit for bit.  Rows are Gaussian mixtures (n / 64 centres, noise 0.5) so that lists mean something.
 No test gates a time."""
 import argparse
 import json
@@ -111,6 +115,120 @@ def staged_search(idx, queries, k, nprobe, knn, ops, score_bytes, refine=0, base
     return ms, best_d[:, :k], I, stats
 
 
+def staged_filter_search(idx, queries, k, nprobe, knn, ops, score_bytes, refine=0, base=None, filter_cap=None, seed_probes=None):
+    """IVFIndex.search(scan="filter") stage by stage (the same calls as IVFIndex._scan_filtered), every stage between device
+    events; (ms by stage, D, I, stats)"""
+    ms = {"coarse": 0.0, "tables": 0.0, "seed_scan": 0.0, "seed_merge": 0.0, "filter": 0.0, "merge_list": 0.0, "research": 0.0}
+    dev = idx.device
+    cap = ops.knn_list_capacity()
+    f16 = idx.storage == "f16"
+    if f16:
+        ms["round"] = 0.0
+    if refine:
+        ms["refine"] = 0.0
+    keep = refine or k
+    s = seed_probes or idx.default_seed_probes(keep, nprobe)
+    cap_f = filter_cap or idx.default_filter_cap(keep)
+
+    def coarse():
+        Q = idx._prepared(queries, dev, idx.l2_norm)
+        q_sq = torch.zeros(Q.shape[0], dtype=torch.float32, device=dev)
+        ops.row_sqnorm(Q, Q.shape[1], q_sq)
+        return Q, q_sq, idx._probes(Q, nprobe).to(torch.int32)
+    ms["coarse"], (Q, q_sq, probe) = timed(coarse)
+    nq, Dp = Q.shape
+    best_d = torch.empty((nq, cap), dtype=torch.float32, device=dev)
+    best_i = torch.empty((nq, cap), dtype=torch.int32, device=dev)
+    cand_d = torch.empty_like(best_d) if refine else best_d
+    cand_i = torch.empty_like(best_i) if refine else best_i
+    seed_p, rest_p = probe.clone(), probe.clone()
+    seed_p[:, s:] = -1
+    rest_p[:, :s] = -1
+    t, chunks = timed(lambda: knn.ivf_plan_chunks(idx.filter_costs(probe, s, cap_f), score_bytes, max_queries=(2 ** 31 - 1) // nprobe))
+    ms["tables"] += t
+    tiles = {"seed": 0, "filter": 0}
+    useful = {"seed": 0, "filter": 0}
+    peak = n_appended = 0
+    redo = []
+    overflow = torch.zeros(1, dtype=torch.int32, device=dev)
+    for q0, q1 in chunks:
+        m = q1 - q0
+        pc = seed_p[q0:q1].contiguous()
+        t, tb = timed(lambda: knn.ivf_tables(pc, idx.list_len))
+        ms["tables"] += t
+        Qc = Q[q0:q1]
+        if f16:
+            def rounded():
+                Qh = Q[q0:q1].to(torch.float16)
+                ops.row_sqnorm(Qh.float(), Dp, q_sq[q0:q1])
+                return Qh
+            t, Qc = timed(rounded)
+            ms["round"] += t
+        peak = max(peak, 4 * tb["n_floats"] + 8 * cap_f * m)
+        if tb["n_slots"] == 0:
+            cand_d[q0:q1], cand_i[q0:q1] = float("inf"), 0x7fffffff
+        else:
+            scores = torch.empty(max(tb["n_floats"], 4), dtype=torch.float32, device=dev)
+            if tb["n_tiles"]:
+                t, _ = timed(lambda: (ops.ivf_scan_f16 if f16 else ops.ivf_scan_f32)(
+                    Qc, tb["slot_query"], tb["slot_start"], tb["slot_off"], idx.rows, idx.list_start, tb["tiles"], scores))
+                ms["seed_scan"] += t
+            t, _ = timed(lambda: ops.ivf_merge(scores, tb["slot_off"], tb["slot_of"], pc, idx.list_start, idx.ids, idx.r_sq,
+                                               q_sq[q0:q1], keep, cand_d[q0:q1], cand_i[q0:q1]))
+            ms["seed_merge"] += t
+            del scores
+            tiles["seed"] += tb["n_tiles"]
+            useful["seed"] += int(((tb["slot_start"][1:] - tb["slot_start"][:-1]).to(torch.int64) * idx.list_len).sum())
+        if s < nprobe:
+            pr = rest_p[q0:q1].contiguous()
+            t, tr = timed(lambda: knn.ivf_tables(pr, idx.list_len))
+            ms["tables"] += t
+            if tr["n_tiles"]:
+                tau = cand_d[q0:q1, keep - 1].contiguous()
+                cnt = torch.zeros(m, dtype=torch.int32, device=dev)
+                cand = torch.empty((m, cap_f, 2), dtype=torch.int32, device=dev)
+                t, _ = timed(lambda: (ops.ivf_filter_f16 if f16 else ops.ivf_filter_f32)(
+                    Qc, tr["slot_query"], tr["slot_start"], q_sq[q0:q1], tau, cnt, idx.rows, idx.list_start, idx.r_sq, idx.ids,
+                    tr["tiles"], cand, cap_f))
+                ms["filter"] += t
+                over = cnt > cap_f
+                n_over, n_app = torch.stack([over.sum(), cnt.sum()]).tolist()
+                n_appended += n_app
+                t, _ = timed(lambda: ops.knn_merge_list(cand, cnt, cap_f, m, keep, cand_d[q0:q1], cand_i[q0:q1], overflow))
+                ms["merge_list"] += t
+                if n_over:
+                    redo.append(torch.nonzero(over).flatten() + q0)
+                tiles["filter"] += tr["n_tiles"]
+                useful["filter"] += int(((tr["slot_start"][1:] - tr["slot_start"][:-1]).to(torch.int64) * idx.list_len).sum())
+        if refine:
+            t, _ = timed(lambda: ops.ivf_refine(Q[q0:q1], base, cand_i[q0:q1], refine, k, best_d[q0:q1], best_i[q0:q1]))
+            ms["refine"] += t
+    n_redo = 0
+    if redo:                                                  # (as IVFIndex._scan_filtered: the buffered search of these queries)
+        def again():
+            ix = torch.cat(redo)
+            po = probe.index_select(0, ix)
+            ld = (idx.list_len + 3) // 4 * 4
+            pl = po.to(torch.int64)
+            own = int(torch.where(pl >= 0, ld[pl.clamp(min=0)], torch.zeros_like(pl)).sum(1).max())
+            bd = torch.empty((ix.numel(), cap), dtype=torch.float32, device=dev)
+            bi = torch.empty((ix.numel(), cap), dtype=torch.int32, device=dev)
+            cd_ = torch.empty_like(bd) if refine else bd
+            ci_ = torch.empty_like(bi) if refine else bi
+            idx._scan_buffered(Q.index_select(0, ix), q_sq.index_select(0, ix), po, k, refine, base, max(int(score_bytes), 4 * own),
+                               bd, bi, cd_, ci_)
+            best_d[ix], best_i[ix] = bd, bi
+            return int(ix.numel())
+        ms["research"], n_redo = timed(again)
+    I = best_i[:, :k].to(torch.int64)
+    I[I == 0x7fffffff] = -1
+    fl = 2.0 * knn.IVF_TILE * knn.IVF_TILE * Dp
+    stats = {"chunks": len(chunks), "seed_probes": s, "filter_cap": cap_f, "peak_bytes": peak, "n_appended": n_appended,
+             "refiltered": n_redo, "tiles": tiles, "flop_tiles": {w: fl * v for w, v in tiles.items()},
+             "flop_useful": {w: 2.0 * v * Dp for w, v in useful.items()}, "probe": probe}
+    return ms, best_d[:, :k], I, stats
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--big", action="store_true")
@@ -124,6 +242,11 @@ def main():
     ap.add_argument("--score-bytes", type=int, default=None)
     ap.add_argument("--storage", nargs="*", default=["f32"], choices=["f32", "f16"], help="list formats to time, over one (centroids, assign)")
     ap.add_argument("--refine", type=int, default=0, help="re-rank depth r of the f16 index (k <= r <= 128); 0 = none")
+    ap.add_argument("--scan", nargs="*", default=["buffer"], choices=["buffer", "filter"],
+                    help="search modes to time over the same index; \"filter\" is compared with the buffered search of the same call")
+    ap.add_argument("--filter-score-bytes", type=int, nargs="*", default=[], help="further budgets for the filter runs (e.g. 1073741824)")
+    ap.add_argument("--filter-cap", type=int, default=None)
+    ap.add_argument("--seed-probes", type=int, default=None)
     a = ap.parse_args()
     from cdml_amd import knn, ops
     dev = torch.device("cuda:0")
@@ -169,7 +292,11 @@ def run_one(idx, base, refine, nprobe, nlist, x, k, n, a, knn, ops, sample, Ie, 
             update_ms, lens):
     kw = dict(refine=refine, base=base) if refine else {}
     staged_search(idx, x[:8192], k, nprobe, knn, ops, score_bytes, **kw)                                  # warm
-    ms, _, I, st = staged_search(idx, x, k, nprobe, knn, ops, score_bytes, **kw)                          # the self-search, all rows
+    ms, Db, I, st = staged_search(idx, x, k, nprobe, knn, ops, score_bytes, **kw)                         # the self-search, all rows
+    if "filter" in a.scan:
+        run_filter(idx, refine, nprobe, nlist, x, k, n, a, knn, ops, score_bytes, Db, I, sum(ms.values()), ms, st, kw)
+    if "buffer" not in a.scan:
+        return
     Is = I if sample is None else I[sample]
     hit = found = 0
     for r0 in range(0, Is.shape[0], 32768):                                                               # (recall in row blocks)
@@ -191,6 +318,31 @@ def run_one(idx, base, refine, nprobe, nlist, x, k, n, a, knn, ops, sample, Ie, 
         "score_bytes": st["score_bytes"], "score_budget": score_bytes, "chunks": st["chunks"], "recall": round(recall, 4),
         "list_max_over_mean": round(float(lens.max() / lens.mean()), 2), "empty_lists": int((lens == 0).sum()),
         "scanned_share": round(idx.scanned_share(st["probe"]), 5), "nprobe_over_nlist": round(nprobe / nlist, 5)}), flush=True)
+
+def run_filter(idx, refine, nprobe, nlist, x, k, n, a, knn, ops, score_bytes, Db, Ib, buffer_ms, buffer_stages, buffer_st, kw):
+    """the filter scan over the same index and queries, under the buffered run's budget and every --filter-score-bytes"""
+    fkw = dict(kw, filter_cap=a.filter_cap, seed_probes=a.seed_probes)
+    staged_filter_search(idx, x[:8192], k, nprobe, knn, ops, score_bytes, **fkw)                          # warm
+    tf = lambda flop, ms: round(flop / max(ms, 1e-9) / 1e9, 2)
+    for budget in [score_bytes] + [b for b in a.filter_score_bytes if b != score_bytes]:
+        ms, D, I, st = staged_filter_search(idx, x, k, nprobe, knn, ops, budget, **fkw)
+        total = sum(ms.values())
+        print(json.dumps({
+            "what": "ivf", "scan": "filter", "storage": idx.storage, "refine": refine, "n": n, "nq": n, "dim": a.dim, "k": k,
+            "nlist": nlist, "nprobe": nprobe, "seed_probes": st["seed_probes"], "filter_cap": st["filter_cap"],
+            "search_ms": round(total, 3), "stages_ms": {s: round(v, 3) for s, v in ms.items()},
+            "buffer_search_ms": round(buffer_ms, 3), "buffer_scan_ms": round(buffer_stages["scan"], 3),
+            "buffer_merge_ms": round(buffer_stages["merge"], 3), "buffer_score_bytes": buffer_st["score_bytes"],
+            "buffer_chunks": buffer_st["chunks"], "buffer_budget": score_bytes, "speedup_over_buffer": round(buffer_ms / total, 3),
+            "seed_tflops_tiles": tf(st["flop_tiles"]["seed"], ms["seed_scan"]), "seed_tflops_useful": tf(st["flop_useful"]["seed"], ms["seed_scan"]),
+            "filter_tflops_tiles": tf(st["flop_tiles"]["filter"], ms["filter"]),
+            "filter_tflops_useful": tf(st["flop_useful"]["filter"], ms["filter"]),
+            "peak_score_plus_candidate_bytes": st["peak_bytes"], "score_budget": budget, "chunks": st["chunks"],
+            "n_appended_per_query": round(st["n_appended"] / max(n, 1), 2), "refiltered": st["refiltered"],
+            "refiltered_share": round(st["refiltered"] / max(n, 1), 5),
+            "equal_to_buffer": bool(torch.equal(D, Db) and torch.equal(I, Ib))}), flush=True)
+        del D, I
+
 
 if __name__ == "__main__":
     main()
