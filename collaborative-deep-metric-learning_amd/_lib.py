@@ -303,6 +303,14 @@ SIGNATURES_IVF_FILTER = {
     "cdml_ivf_filter_f16": (_i, list(_IVF_FILTER_ARGS)),
 }
 
+# name -> (restype, argtypes); must list every symbol include/cdml_knn_writer.h declares (the export's text lists formatted on
+# the device: the host entry point of the shortest-repr routine and the two launches)
+SIGNATURES_KNN_WRITER = {
+    "cdml_f32_shortest": (_i, [_f, C.c_char_p]),
+    "cdml_knn_line_sizes": (_i, [_p, _i64, _p, _i64, _i64, _i, _i, _p, _i64, _i64, _p, _p, _p]),
+    "cdml_knn_line_write": (_i, [_p, _i64, _p, _i64, _i64, _i, _i, _p, _p, _i64, _i64, _p, _p, _i64, _p]),
+}
+
 _lib = None
 
 
@@ -324,7 +332,8 @@ def load_library():
     for name, (res, args) in (list(SIGNATURES.items()) + list(SIGNATURES_MIXED.items()) + list(SIGNATURES_DP.items())
                                + list(SIGNATURES_BF16.items()) + list(SIGNATURES_HARDNEG.items()) + list(SIGNATURES_WIDE.items())
                                + list(SIGNATURES_NEGW.items()) + list(SIGNATURES_F8.items()) + list(SIGNATURES_IVF.items())
-                               + list(SIGNATURES_IVF_F16.items()) + list(SIGNATURES_IVF_FILTER.items())):
+                               + list(SIGNATURES_IVF_F16.items()) + list(SIGNATURES_IVF_FILTER.items())
+                               + list(SIGNATURES_KNN_WRITER.items())):
         fn = getattr(lib, name)          # AttributeError if the ABI lost a symbol
         fn.restype = res
         fn.argtypes = args

@@ -238,13 +238,110 @@ def iter_desim_mp(eI, fI, fD, fD_threshold=DESIM_THRESHOLD, fI_end=DESIM_FI_END,
     return desim(eI, fI, fD, fD_threshold=fD_threshold, fI_end=fI_end)
 
 
-def cross_knn(embeddings, doc_location, nearest_num=81, precision="f32x3", device="cuda:0"):
+IVF_STORAGES = ("f32", "f16")        # IVFIndex.STORAGES / IVFIndex.SCANS, named here for the checks that run before the class exists
+IVF_SCANS = ("buffer", "filter")
+
+
+def _check_ivf_options(storage, refine, scan, ks=()):
+    """The refusals of the IVF options the export's call sites share, by name, before any device work.  ``ks``: the list
+    lengths the searches will ask for (a re-rank must keep at least that many)."""
+    if storage not in IVF_STORAGES:
+        raise ValueError("storage must be one of %s, got %r" % (IVF_STORAGES, storage))
+    if scan not in IVF_SCANS:
+        raise ValueError("scan must be one of %s, got %r" % (IVF_SCANS, scan))
+    r = int(refine)
+    if r != refine or r < 0:
+        raise ValueError("refine must be an integer >= 0, got %r" % (refine,))
+    if r and storage != "f16":
+        raise ValueError("refine belongs to storage=\"f16\" (the distances of storage=\"f32\" are exact already)")
+    if r and ks and not max(ks) <= r <= ops.knn_list_capacity():
+        raise ValueError("refine must be 0 or in [k = %d, %d], got %d" % (max(ks), ops.knn_list_capacity(), r))
+    return r
+
+
+def _check_ivf_lists(what, nlist, nprobe, n_rows):
+    """(nlist, nprobe) of one index over ``n_rows`` rows: both 0 (the exact search), or 1 <= nprobe <= nlist <= n_rows."""
+    nlist, nprobe = int(nlist), int(nprobe)
+    if nlist < 0 or nprobe < 0:
+        raise ValueError("%snlist and %snprobe must be >= 0, got %d and %d" % (what, what, nlist, nprobe))
+    if nlist == 0:
+        if nprobe:
+            raise ValueError("%snprobe = %d without %snlist: the exact search probes nothing (set %snlist > 0)"
+                             % (what, nprobe, what, what))
+        return 0, 0
+    if nlist > n_rows:
+        raise ValueError("%snlist = %d exceeds the %d rows of its index" % (what, nlist, n_rows))
+    if not 1 <= nprobe <= nlist:
+        raise ValueError("%snprobe must be in [1, %snlist = %d], got %d" % (what, what, nlist, nprobe))
+    return nlist, nprobe
+
+
+def ivf_knn(base, queries=None, k=51, nlist=1024, nprobe=16, l2_norm=True, storage="f32", refine=0, scan="buffer", iters=10,
+            seed=0, device="cuda:0", precision="f32x3", index=None, stats=None):
+    """Device (D, I) of ``IVFIndex.search``, shaped and typed like ``knn_search``'s: the index of ``base`` (built here with
+    ``nlist`` lists, ``iters`` Lloyd iterations and ``seed``, or taken as ``index=``), every query's ``nprobe`` nearest lists
+    scanned exactly.  ``queries=None`` is the self-search.  ``refine>0`` (storage "f16") re-ranks the ``refine`` best against
+    the fp32 rows ``index.prepare(base)``.  The one place the export's approximate searches go through; its launches are
+    those of DESIGN.md sections 9f-9f.2.  ``stats`` (a dict, optional) receives ``IVFIndex.search``'s."""
+    if index is None:
+        _check_ivf_options(storage, refine, scan, (int(k),))
+        index = IVFIndex.build(base, int(nlist), iters=iters, seed=seed, l2_norm=l2_norm, device=device, precision=precision,
+                               storage=storage)
+    q = base if queries is None else queries
+    kw = {"refine": int(refine), "base": index.prepare(base)} if int(refine) > 0 else {}
+    return index.search(q, int(k), int(nprobe), stats=stats, scan=scan, **kw)
+
+
+def cross_nlist(nlist, n_side, n):
+    """max(1, ceil(nlist n_side / n)): the lists of one side's index of a cross search, so that a list of either side is as
+    long on average as a list of ``nlist`` over the whole catalogue.  Pure host arithmetic."""
+    nlist, n_side, n = int(nlist), int(n_side), int(n)
+    if nlist < 1 or n_side < 1 or n < n_side:
+        raise ValueError("cross_nlist needs nlist >= 1 and 1 <= n_side <= n, got %d, %d, %d" % (nlist, n_side, n))
+    return max(1, -(-nlist * n_side // n))
+
+
+def _check_cross_lists(nlist, nprobe, doc_location, n):
+    """(nlist, nprobe) of a cross search checked for the whole catalogue and for either side, before any device work"""
+    nlist, nprobe = _check_ivf_lists("", nlist, nprobe, n)
+    if nlist:
+        for n_side in (doc_location, n - doc_location):
+            if n_side < 1 or cross_nlist(nlist, n_side, n) > n_side:
+                raise ValueError("nlist = %d gives a side of %d rows more lists than rows" % (nlist, n_side))
+    return nlist, nprobe
+
+
+def cross_knn(embeddings, doc_location, nearest_num=81, precision="f32x3", device="cuda:0", nlist=0, nprobe=0, storage="f32",
+              refine=0, scan="buffer", ivf_iters=10, ivf_seed=0, stats=None):
     """(crossD, crossI) as faiss_knn.py:325-336 builds them: rows [0, doc_location) (videos) search the documents, their
     ids offset by ``doc_location`` into global ids; rows [doc_location, n) (documents) search the videos.  Rows are in
     global order, so the query of row r is r.  The exact search (``knn_search``) stands for the reference's HNSW.  A -1
     ("no neighbour": a side with fewer than nearest_num rows) stays -1 instead of taking the offset.  Returns the kind
-    of ``embeddings``."""
+    of ``embeddings``.
+    ``nlist > 0``: either side is searched through an ``IVFIndex`` of its own (``ivf_knn``) with ``cross_nlist(nlist, n_side,
+    n)`` lists, of which min(nprobe, that many) are probed; ``storage``, ``refine``, ``scan``, ``ivf_iters`` and ``ivf_seed`` go
+    to both.  ``stats`` (a dict, optional) receives the two searches' under "video_to_doc" and "doc_to_video"."""
     t = embeddings if torch.is_tensor(embeddings) else torch.from_numpy(np.asarray(embeddings, dtype=np.float32))
+    if int(nlist) or int(nprobe):
+        n = t.shape[0]
+        nlist, nprobe = _check_cross_lists(nlist, nprobe, int(doc_location), n)
+        _check_ivf_options(storage, refine, scan, (int(nearest_num),))
+        video, doc = t[:doc_location], t[doc_location:]
+        out = []
+        for name, base, q in (("video_to_doc", doc, video), ("doc_to_video", video, doc)):
+            nl = cross_nlist(nlist, base.shape[0], n)
+            st = None if stats is None else stats.setdefault(name, {})
+            out.append(ivf_knn(base, q, int(nearest_num), nlist=nl, nprobe=min(nprobe, nl), storage=storage, refine=refine,
+                               scan=scan, iters=ivf_iters, seed=ivf_seed, device=device, precision=precision, stats=st))
+        (vdD, vdI), (dvD, dvI) = out
+        vdI = torch.where(vdI >= 0, vdI + doc_location, vdI)
+        D, I = torch.cat([vdD, dvD]), torch.cat([vdI, dvI])
+        if torch.is_tensor(embeddings):
+            return D, I
+        return D.cpu().numpy(), I.cpu().numpy()
+    _check_ivf_options(storage, refine, scan)
+    if storage != "f32" or int(refine) or scan != "buffer":
+        raise ValueError("storage, refine and scan belong to nlist > 0 (this search is exact)")
     video, doc = t[:doc_location], t[doc_location:]
     vdD, vdI = knn_search(doc, video, int(nearest_num), device=device, precision=precision)
     vdI = torch.where(vdI >= 0, vdI + doc_location, vdI)
@@ -271,69 +368,330 @@ def _host(a):
     return a.cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
 
 
-def write_knn(out_dir, D, I, decode_map, split_num=10, prefix="knn_result"):
+WRITERS = ("host", "device")
+WRITER_BUFFER_BYTES = 1 << 30   # the device writer's output buffer: a part longer than this goes out in row ranges of at most so many bytes
+
+
+def _part_text_host(D, I, b, e, decode_map, row0=None):
+    """the text of rows [b, e) of D / I as write_knn writes them, formatted on the host (one numpy str() pass for the part);
+    the rows are rows ``row0`` (default b) and up of the catalogue"""
+    row0 = b if row0 is None else row0
+    Dt = D[b:e, 1:].astype(np.float32, copy=False)
+    It = I[b:e, 1:].astype(np.int64, copy=False)
+    m = (It > 0) & (Dt > np.float32(0.0)) & (Dt < np.float32(1.4))        # the float32 compares numpy makes
+    ds = Dt[m].astype(str).tolist()                  # one call for the part: numpy's str of a float32 is its shortest repr
+    ids = It[m].tolist()
+    ends = np.cumsum(m.sum(1)).tolist()
+    lines, p = [], 0
+    for r, q in zip(range(row0, row0 + e - b), ends):
+        lines.append(decode_map[r] + "," + "".join([decode_map[ids[t]] + "#" + ds[t] + "<" for t in range(p, q)]) + "\n")
+        p = q
+    return "".join(lines)
+
+
+def guid_table(decode_map, device="cuda:0"):
+    """(guid_bytes uint8 [total + 1], guid_off int64 [n + 1]) on ``device``: the utf-8 bytes of decode_map[0 .. n - 1], one
+    after the other, and where each starts (include/cdml_knn_writer.h; the last byte is a pad, so that a table of empty
+    guids still has an address).  ``decode_map``: a sequence, or a dict whose keys are exactly 0 .. n - 1."""
+    n = len(decode_map)
+    try:
+        enc = [decode_map[i].encode("utf-8") for i in range(n)]
+    except (KeyError, IndexError):
+        raise ValueError("writer=\"device\" needs a decode_map with the keys 0 .. %d" % (n - 1))
+    off = np.zeros(n + 1, dtype=np.int64)
+    if n:
+        off[1:] = np.cumsum(np.fromiter((len(b) for b in enc), dtype=np.int64, count=n))
+    data = np.frombuffer(b"".join(enc) + b"\0", dtype=np.uint8).copy()
+    return torch.from_numpy(data).to(device), torch.from_numpy(off).to(device)
+
+
+def _write_knn_device(out_dir, D, I, decode_map, split_num, prefix, device, buffer_bytes, stats):
+    import os
+    n, k = D.shape
+    if not 1 <= k <= ops.knn_list_capacity():
+        raise ValueError("writer=\"device\" takes at most %d columns, got %d" % (ops.knn_list_capacity(), k))
+    gbytes, goff = guid_table(decode_map, device)
+    n_guid = goff.numel() - 1
+    if n > n_guid:
+        raise ValueError("decode_map names %d rows, the lists have %d" % (n_guid, n))
+    Dd = _dev_tensor(D, torch.float32, device)
+    Id = _dev_tensor(I, torch.int64, device)
+    patch = n // split_num
+    host_parts = launches = 0
+    for s in range(split_num):
+        b = s * patch
+        e = n if s == split_num - 1 else (s + 1) * patch
+        path = os.path.join(out_dir, prefix + str(s))
+        if e <= b:
+            open(path, "wb").close()
+            continue
+        Dp, Ip = Dd[b:e], Id[b:e]
+        sizes = torch.empty(e - b, dtype=torch.int64, device=device)
+        flags = torch.empty(e - b, dtype=torch.int32, device=device)
+        ops.knn_line_sizes(Dp, Ip, b, goff, gbytes.numel(), sizes, flags)
+        off = torch.zeros(e - b + 1, dtype=torch.int64, device=device)
+        off[1:] = torch.cumsum(sizes, 0)
+        lost = ((Ip[:, 1:] >= n_guid) & (Dp[:, 1:] > 0.0) & (Dp[:, 1:] < float(np.float32(1.4)))).any()
+        n_flag, n_lost = torch.stack([flags.sum(), lost.to(torch.int64)]).tolist()       # the host read
+        if n_lost:
+            raise ValueError("a kept neighbour id is not in decode_map (%d guids)" % n_guid)
+        if n_flag:              # a kept distance below the digit routine's range: this part is formatted on the host
+            host_parts += 1
+            with open(path, "w", encoding="utf-8", newline="\n") as f:
+                f.write(_part_text_host(Dp.cpu().numpy(), Ip.cpu().numpy(), 0, e - b, decode_map, row0=b))
+            continue
+        off_h = off.cpu().numpy()
+        with open(path, "wb") as f:
+            r0 = 0
+            while r0 < e - b:
+                # the longest row range from r0 within the buffer (one row at least: a longer line gets a buffer of its own)
+                r1 = int(np.searchsorted(off_h, off_h[r0] + int(buffer_bytes), side="right")) - 1
+                r1 = min(max(r1, r0 + 1), e - b)
+                nbytes = int(off_h[r1] - off_h[r0])
+                out = torch.empty(nbytes, dtype=torch.uint8, device=device)
+                ops.knn_line_write(Dp[r0:r1], Ip[r0:r1], b + r0, gbytes, goff,
+                                   off if (r0, r1) == (0, e - b) else (off[r0:r1 + 1] - off[r0]).contiguous(), out)
+                launches += 1
+                f.write(memoryview(out.cpu().numpy()))
+                r0 = r1
+    if stats is not None:
+        stats.update(writer="device", host_parts=host_parts, write_launches=launches)
+
+
+def write_knn(out_dir, D, I, decode_map, split_num=10, prefix="knn_result", writer="host", device="cuda:0",
+              buffer_bytes=WRITER_BUFFER_BYTES, stats=None):
     """The text lists of faiss_knn.py:267-305 (``write_knn`` / ``write_process``), byte for byte: ``split_num`` files
     ``prefix + str(index)``, parts of ``n // split_num`` rows, the remainder in the last one.  A line is
     ``decode_map[row] + "," + "".join(decode_map[id] + "#" + str(d) + "<")`` over columns 1.. where id > 0 and
     0.0 < d < 1.4 (d a float32, printed as its shortest repr).  Reproduced as the reference has them: column 0 is skipped
     in every mode (in a cross list it is a real neighbour), and catalogue row 0 never appears as a neighbour (id > 0).
-    ``decode_map`` is an argument (the reference's workers read a global its ``main`` never sets)."""
+    ``decode_map`` is an argument (the reference's workers read a global its ``main`` never sets).
+    ``writer="device"`` (csrc/knn_writer.hip) writes the same bytes: per part, one launch sizes
+    every line, an int64 scan places them, one launch formats them into a byte buffer (at most ``buffer_bytes`` per launch)
+    and the part is copied out and written as it is.  A part with a kept distance outside the digit routine's range
+    (below 2^-64) is formatted on the host instead.  ``stats`` (a dict, optional) receives ``host_parts`` and
+    ``write_launches``."""
     import os
+    if writer not in WRITERS:
+        raise ValueError("writer must be one of %s, got %r" % (WRITERS, writer))
+    if writer == "device":
+        D, I = (a if torch.is_tensor(a) else np.asarray(a) for a in (D, I))
+        if tuple(D.shape) != tuple(I.shape) or len(D.shape) != 2:
+            raise ValueError("D and I of one shape [n, k]")
+        os.makedirs(out_dir, exist_ok=True)
+        return _write_knn_device(out_dir, D, I, decode_map, int(split_num), prefix, device, buffer_bytes, stats)
     D, I = _host(D), _host(I)
     if D.shape != I.shape or D.ndim != 2:
         raise ValueError("D and I of one shape [n, k]")
     os.makedirs(out_dir, exist_ok=True)
     n = D.shape[0]
-    Dt = D[:, 1:].astype(np.float32, copy=False)
-    It = I[:, 1:].astype(np.int64, copy=False)
-    ok = (It > 0) & (Dt > np.float32(0.0)) & (Dt < np.float32(1.4))       # the float32 compares numpy makes
     patch = n // split_num
     for s in range(split_num):
         b = s * patch
         e = n if s == split_num - 1 else (s + 1) * patch
-        m = ok[b:e]
-        ds = Dt[b:e][m].astype(str).tolist()         # one call for the part: numpy's str of a float32 is its shortest repr
-        ids = It[b:e][m].tolist()
-        ends = np.cumsum(m.sum(1)).tolist()
-        lines, p = [], 0
-        for r, q in zip(range(b, e), ends):
-            lines.append(decode_map[r] + "," + "".join([decode_map[ids[t]] + "#" + ds[t] + "<" for t in range(p, q)]) + "\n")
-            p = q
         with open(os.path.join(out_dir, prefix + str(s)), "w", encoding="utf-8", newline="\n") as f:
-            f.write("".join(lines))
+            f.write(_part_text_host(D, I, b, e, decode_map))
+
+
+def audit_sample(n, audit_rows, audit_seed=0):
+    """The rows the export's audit looks at: the first ``audit_rows`` entries of a seeded CPU ``torch.randperm(n)``, sorted
+    (int64, CPU)."""
+    g = torch.Generator()
+    g.manual_seed(int(audit_seed))
+    return torch.sort(torch.randperm(int(n), generator=g)[:int(audit_rows)]).values
+
+
+def _set_counts(got, want):
+    """(hits, possible) = (sum over rows of |got[r] & want[r]|, the number of entries of want) over the entries >= 0"""
+    hits = possible = 0
+    for g, w in zip(got.tolist(), want.tolist()):
+        w = set(x for x in w if x >= 0)
+        hits += len(w & set(x for x in g if x >= 0))
+        possible += len(w)
+    return hits, possible
+
+
+def _export_audit(emb, features, doc_location, cross, sample, I, fI, I_desim, k, k_f, fD_threshold, fI_end, precision, device):
+    """The recall statement of an export, integer counts only: what the export's lists of the
+    ``sample`` rows share with the exact search's, for the embedding lists, the raw-feature lists and the desimmed lists."""
+    n = emb.shape[0]
+    smp = sample.to(device)
+    if cross:
+        ex = torch.full((smp.numel(), k), -1, dtype=torch.int64, device=device)
+        is_video = smp < doc_location
+        for rows, base, shift in ((is_video, emb[doc_location:], doc_location), (~is_video, emb[:doc_location], 0)):
+            if bool(rows.any()):
+                _, Ie = knn_search(base, emb[smp[rows]], k, device=device, precision=precision)
+                ex[rows] = torch.where(Ie >= 0, Ie + shift, Ie)
+    else:
+        _, ex = knn_search(emb, emb[smp], k, device=device, precision=precision)
+    e_hits, e_possible = _set_counts(I[smp].cpu(), ex.cpu())
+    U = torch.unique(torch.cat([smp, ex[ex >= 0]]))                     # sorted
+    feats = features if torch.is_tensor(features) else torch.from_numpy(np.asarray(features, dtype=np.float32))
+    fDx, fIx = knn_search(feats, feats[U.to(feats.device)], k_f, device=device, precision=precision)
+    at = torch.searchsorted(U, smp)                                     # the sample's rows of U
+    f_hits, f_possible = _set_counts(_dev_tensor(fI, torch.int64, device)[smp].cpu(), fIx[at].cpu())
+    full_i = torch.full((n, k_f), -1, dtype=torch.int64, device=device)
+    full_d = torch.full((n, k_f), float("inf"), dtype=torch.float32, device=device)
+    full_i[U], full_d[U] = fIx, fDx
+    dx = desim(ex, full_i, full_d, fD_threshold=fD_threshold, fI_end=fI_end, query_ids=smp, device=device)
+    rows_equal = inter = union = 0
+    for g, w in zip(I_desim[smp].cpu().tolist(), dx.cpu().tolist()):
+        g, w = set(x for x in g if x >= 0), set(x for x in w if x >= 0)
+        rows_equal += int(g == w)
+        inter += len(g & w)
+        union += len(g | w)
+    return {"audit_rows": int(smp.numel()), "union_rows": int(U.numel()), "e_hits": e_hits, "e_possible": e_possible,
+            "f_hits": f_hits, "f_possible": f_possible, "desim_rows_equal": rows_equal, "desim_kept_intersection": inter,
+            "desim_kept_union": union}
+
+
+def _load_feature_knn(feature_knn, n):
+    """(fD, fI) of ``feature_knn`` -- a pair of arrays, or a directory that holds fD.npy and fI.npy -- checked by name"""
+    import os
+    if isinstance(feature_knn, (str, os.PathLike)):
+        feature_knn = (np.load(os.path.join(feature_knn, "fD.npy")), np.load(os.path.join(feature_knn, "fI.npy")))
+    try:
+        fD, fI = feature_knn
+        shapes = (tuple(fD.shape), tuple(fI.shape))
+    except (TypeError, ValueError, AttributeError):
+        raise ValueError("feature_knn must be a pair (fD, fI) of arrays or a directory that holds fD.npy and fI.npy")
+    if shapes[0] != shapes[1] or len(shapes[0]) != 2 or shapes[0][0] != n or shapes[0][1] < 1:
+        raise ValueError("feature_knn must be two [n = %d, >= 1] arrays of one shape, got %s and %s" % (n, shapes[0], shapes[1]))
+    return fD, fI
+
+
+def _scalars(st):
+    """the host numbers of an ``IVFIndex.search`` stats dict (its device tensors stay out of a report)"""
+    out = {}
+    for key, v in st.items():
+        if isinstance(v, dict):
+            out[key] = _scalars(v)
+        elif key == "chunks":
+            out["n_chunks"] = len(v)
+        elif isinstance(v, (int, float, str)):
+            out[key] = v
+    return out
 
 
 def export(embeddings, features, decode_map, out_dir, doc_location=343455, nearest_num=81, desim_nearest_num=26,
-           fD_threshold=DESIM_THRESHOLD, fI_end=DESIM_FI_END, precision="f32x3", device="cuda:0", split_num=10):
+           fD_threshold=DESIM_THRESHOLD, fI_end=DESIM_FI_END, precision="f32x3", device="cuda:0", split_num=10,
+           nlist=0, nprobe=0, feature_nlist=0, feature_nprobe=0, storage="f32", refine=0, scan="buffer", ivf_iters=10,
+           ivf_seed=0, feature_knn=None, writer="host", audit_rows=0, audit_seed=0, stats=None):
     """faiss_knn.main (faiss_knn.py:359-400) with explicit arguments: the raw-feature kNN (fD, fI; k = min(desim_nearest_num,
     nearest_num)), then -- cross mode when 0 < doc_location < n, strict mode otherwise -- the embedding kNN, desim and the
     text lists.  Writes fD.npy, fI.npy, {strict,cross}D.npy, {strict,cross}I.npy, {strict,cross}I_desim.npy, the
     ``split_num`` text files {strict,cross}_knn<i> and decode_map.json.  The text lists are written from the DESIMMED ids
     in both modes (the reference's cross branch writes the un-desimmed crossI: faiss_knn.py:350, marked TODO; crossI.npy
-    keeps those).  Returns (D, I_desim) as device tensors."""
+    keeps those).  Returns (D, I_desim) as device tensors.
+
+    At catalogue scale; every default keeps the exact path and its bytes:
+    ``nlist`` / ``nprobe``: the embedding search through ``ivf_knn`` (strict) or ``cross_knn(nlist=...)`` (cross: an index per
+    side).  ``feature_nlist`` / ``feature_nprobe``: the raw-feature search through ``ivf_knn``, independently.  ``storage``,
+    ``refine``, ``scan``, ``ivf_iters``, ``ivf_seed`` go to every index.  ``feature_knn``: (fD, fI) or a directory holding
+    fD.npy / fI.npy of an earlier export -- raw features do not change when the model is retrained -- written as given, no
+    feature search (``features`` may then be None unless the audit needs them).  ``writer``: "host" | "device"
+    (``write_knn``).  ``audit_rows = m > 0``: the recall statement -- for the rows ``audit_sample(n, m, audit_seed)`` the
+    exact searches are run and the export's lists compared with them; integer counts, written to export_audit.json and
+    ``stats["audit"]``, no threshold.  ``stats`` (a dict, optional): per stage {"seconds", "max_memory_allocated"} and the
+    ``IVFIndex.search`` numbers.  Bad combinations are ValueErrors raised before any device work."""
     import json
     import os
-    os.makedirs(out_dir, exist_ok=True)
+    import time
     n = embeddings.shape[0]
-    k_f = min(int(desim_nearest_num), int(nearest_num))
-    fD, fI = knn_search(features, features, k_f, device=device, precision=precision)
-    np.save(os.path.join(out_dir, "fD.npy"), fD.cpu().numpy())
-    np.save(os.path.join(out_dir, "fI.npy"), fI.cpu().numpy())
+    k, k_f = int(nearest_num), min(int(desim_nearest_num), int(nearest_num))
+    cross = 0 < doc_location < n
+    # ---- the refusals, before any device work ----
+    if writer not in WRITERS:
+        raise ValueError("writer must be one of %s, got %r" % (WRITERS, writer))
+    nlist, nprobe = _check_cross_lists(nlist, nprobe, int(doc_location), n) if cross else _check_ivf_lists("", nlist, nprobe, n)
+    feature_nlist, feature_nprobe = _check_ivf_lists("feature_", feature_nlist, feature_nprobe, n)
+    refine = _check_ivf_options(storage, refine, scan, ((k,) if nlist else ()) + ((k_f,) if feature_nlist else ()))
+    if not (nlist or feature_nlist) and (storage != "f32" or refine or scan != "buffer"):
+        raise ValueError("storage, refine and scan belong to an IVF search: set nlist or feature_nlist (both are 0)")
+    if feature_knn is not None:
+        if feature_nlist:
+            raise ValueError("feature_knn and feature_nlist > 0 exclude each other: the given lists are written as they are")
+        feature_knn = _load_feature_knn(feature_knn, n)
+    elif features is None:
+        raise ValueError("features is None and no feature_knn was given")
+    audit_rows = int(audit_rows)
+    if not 0 <= audit_rows <= n:
+        raise ValueError("audit_rows must be in [0, n = %d], got %d" % (n, audit_rows))
+    if audit_rows and features is None:
+        raise ValueError("the audit runs the exact raw-feature search: it needs features")
+    ivf = {"storage": storage, "refine": refine, "scan": scan}
+
+    def stage(name, t0, extra=None):
+        if stats is not None:
+            torch.cuda.synchronize(device)
+            stats[name] = dict(extra or {}, seconds=time.perf_counter() - t0,
+                               max_memory_allocated=torch.cuda.max_memory_allocated(device))
+        return time.perf_counter()
+
+    os.makedirs(out_dir, exist_ok=True)
+    t0 = time.perf_counter()
+    if feature_knn is not None:
+        fD, fI = feature_knn
+    elif feature_nlist:
+        st = {}
+        fD, fI = ivf_knn(features, None, k_f, nlist=feature_nlist, nprobe=feature_nprobe, iters=ivf_iters, seed=ivf_seed,
+                         device=device, precision=precision, stats=st, **ivf)
+        t0 = stage("feature_knn", t0, {"ivf": _scalars(st)})
+    else:
+        fD, fI = knn_search(features, features, k_f, device=device, precision=precision)
+        t0 = stage("feature_knn", t0)
+    np.save(os.path.join(out_dir, "fD.npy"), _host(fD))
+    np.save(os.path.join(out_dir, "fI.npy"), _host(fI))
     emb = embeddings if torch.is_tensor(embeddings) else torch.from_numpy(np.asarray(embeddings, dtype=np.float32))
-    if 0 < doc_location < n:
+    t0 = time.perf_counter()
+    st = {}
+    if cross:
         mode = "cross"
-        D, I = cross_knn(emb.to(device), doc_location, nearest_num=nearest_num, precision=precision, device=device)
+        if nlist:
+            D, I = cross_knn(emb.to(device), doc_location, nearest_num=nearest_num, precision=precision, device=device,
+                             nlist=nlist, nprobe=nprobe, ivf_iters=ivf_iters, ivf_seed=ivf_seed, stats=st, **ivf)
+        else:
+            D, I = cross_knn(emb.to(device), doc_location, nearest_num=nearest_num, precision=precision, device=device)
     else:
         mode = "strict"
-        D, I = knn_search(emb, emb, int(nearest_num), device=device, precision=precision)
+        if nlist:
+            D, I = ivf_knn(emb, None, k, nlist=nlist, nprobe=nprobe, iters=ivf_iters, seed=ivf_seed, device=device,
+                           precision=precision, stats=st, **ivf)
+        else:
+            D, I = knn_search(emb, emb, int(nearest_num), device=device, precision=precision)
+    t0 = stage("embedding_knn", t0, {"ivf": _scalars(st)} if nlist else None)
     np.save(os.path.join(out_dir, mode + "D.npy"), D.cpu().numpy())
     np.save(os.path.join(out_dir, mode + "I.npy"), I.cpu().numpy())
+    t0 = time.perf_counter()
     I_desim = desim(I, fI, fD, fD_threshold=fD_threshold, fI_end=fI_end, device=device)
+    t0 = stage("desim", t0)
     np.save(os.path.join(out_dir, mode + "I_desim.npy"), I_desim.cpu().numpy())
-    write_knn(out_dir, D, I_desim, decode_map, split_num=split_num, prefix=mode + "_knn")
+    t0 = time.perf_counter()
+    if writer == "host":
+        write_knn(out_dir, D, I_desim, decode_map, split_num=split_num, prefix=mode + "_knn")
+        t0 = stage("write", t0, {"writer": "host"})
+    else:
+        st = {}
+        write_knn(out_dir, D, I_desim, decode_map, split_num=split_num, prefix=mode + "_knn", writer=writer, device=device,
+                  stats=st)
+        t0 = stage("write", t0, st)
     dm = decode_map if isinstance(decode_map, dict) else dict(enumerate(decode_map))
     with open(os.path.join(out_dir, "decode_map.json"), "w") as f:
         json.dump({str(k): v for k, v in dm.items()}, f)
+    if audit_rows:
+        t0 = time.perf_counter()
+        counts = _export_audit(emb.to(device), features, int(doc_location), cross, audit_sample(n, audit_rows, audit_seed), I, fI,
+                               I_desim, k, k_f, fD_threshold, fI_end, precision, device)
+        report = dict(counts, mode=mode, n=n, doc_location=int(doc_location), nearest_num=k, desim_nearest_num=k_f,
+                      fD_threshold=float(fD_threshold), fI_end=int(fI_end), precision=precision, nlist=nlist, nprobe=nprobe,
+                      feature_nlist=feature_nlist, feature_nprobe=feature_nprobe, ivf_iters=int(ivf_iters), ivf_seed=int(ivf_seed),
+                      feature_knn_given=feature_knn is not None, audit_seed=int(audit_seed), **ivf)
+        with open(os.path.join(out_dir, "export_audit.json"), "w") as f:
+            json.dump(report, f, indent=1, sort_keys=True)
+        stage("audit", t0)
+        if stats is not None:
+            stats["audit"].update(report)
     return D, I_desim
 
 

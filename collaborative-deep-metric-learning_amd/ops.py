@@ -1829,6 +1829,38 @@ def knn_desim(eI, f_filtered, out, query_id=None, row0=0):
     return out
 
 
+def _knn_lines_args(D, I, row0, guid_off):
+    if D.dim() != 2 or tuple(D.shape) != tuple(I.shape):
+        raise ValueError("D and I of one shape [n, k]")
+    dp, dld = _mat(D)
+    ip, ild = _mat(I, torch.int64)
+    if not guid_off.is_contiguous() or guid_off.dim() != 1 or guid_off.numel() < 2:
+        raise ValueError("guid_off must be a contiguous int64 vector of n_guid + 1 offsets")
+    return dp, dld, ip, ild, int(row0), D.shape[0], D.shape[1], _p(guid_off, torch.int64), guid_off.numel() - 1
+
+
+def knn_line_sizes(D, I, row0, guid_off, guid_total, sizes, flags):
+    """sizes[r] (int64) = the bytes of the export's text line of row r of D (fp32) / I (int64) [n, k <= 128], whose own guid is
+    ``row0 + r``; flags[r] (int32) = 1 where a kept distance is outside the shortest-repr routine's range
+    (include/cdml_knn_writer.h).  guid_off int64 [n_guid + 1]: the byte offsets of the guid table (``guid_total`` bytes)."""
+    a = _knn_lines_args(D, I, row0, guid_off)
+    if sizes.numel() < D.shape[0] or flags.numel() < D.shape[0] or not sizes.is_contiguous() or not flags.is_contiguous():
+        raise ValueError("sizes and flags: contiguous vectors of n entries")
+    call("cdml_knn_line_sizes", *a, int(guid_total), _p(sizes, torch.int64), _p(flags, torch.int32), _stream())
+    return sizes, flags
+
+
+def knn_line_write(D, I, row0, guid_bytes, guid_off, off, out):
+    """The lines ``knn_line_sizes`` measured, written into out (uint8): row r's bytes at [off[r], off[r + 1]) (off int64
+    [n + 1], the exclusive scan of the sizes); no store leaves that extent or the buffer."""
+    a = _knn_lines_args(D, I, row0, guid_off)
+    if off.numel() < D.shape[0] + 1 or not off.is_contiguous() or not out.is_contiguous() or not guid_bytes.is_contiguous():
+        raise ValueError("off: a contiguous vector of n + 1 entries; out and guid_bytes contiguous")
+    call("cdml_knn_line_write", *a[:7], _p(guid_bytes, torch.uint8), a[7], a[8], guid_bytes.numel(), _p(off, torch.int64),
+         _p(out, torch.uint8), out.numel(), _stream())
+    return out
+
+
 # ------------------------------------------------- fusion towers (N4) ---------
 EW_MUL, EW_MUL_RES, EW_ADD = 0, 1, 2
 
