@@ -311,6 +311,15 @@ SIGNATURES_KNN_WRITER = {
     "cdml_knn_line_write": (_i, [_p, _i64, _p, _i64, _i64, _i, _i, _p, _p, _i64, _i64, _p, _p, _i64, _p]),
 }
 
+# name -> (restype, argtypes); must list every symbol include/cdml_ivf_pq.h declares (the product-quantised lists of the IVF
+# index: the encoder, the per-query lookup tables, the scan's tile and the table-lookup scan)
+SIGNATURES_IVF_PQ = {
+    "cdml_pq_encode": (_i, [_p, _i64, _i64, _p, _i, _i, _p, _i64, _p, _i64, _p]),
+    "cdml_pq_lut": (_i, [_p, _i64, _i, _p, _i, _i, _p, _p]),
+    "cdml_ivf_pq_tile": (_i, [_i, _p, _p]),
+    "cdml_ivf_scan_pq": (_i, [_p, _i, _p, _p, _p, _p, _i64, _p, _i, _p, _i, _p, _p]),
+}
+
 _lib = None
 
 
@@ -333,7 +342,7 @@ def load_library():
                                + list(SIGNATURES_BF16.items()) + list(SIGNATURES_HARDNEG.items()) + list(SIGNATURES_WIDE.items())
                                + list(SIGNATURES_NEGW.items()) + list(SIGNATURES_F8.items()) + list(SIGNATURES_IVF.items())
                                + list(SIGNATURES_IVF_F16.items()) + list(SIGNATURES_IVF_FILTER.items())
-                               + list(SIGNATURES_KNN_WRITER.items())):
+                               + list(SIGNATURES_KNN_WRITER.items()) + list(SIGNATURES_IVF_PQ.items())):
         fn = getattr(lib, name)          # AttributeError if the ABI lost a symbol
         fn.restype = res
         fn.argtypes = args

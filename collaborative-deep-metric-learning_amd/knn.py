@@ -238,22 +238,46 @@ def iter_desim_mp(eI, fI, fD, fD_threshold=DESIM_THRESHOLD, fI_end=DESIM_FI_END,
     return desim(eI, fI, fD, fD_threshold=fD_threshold, fI_end=fI_end)
 
 
-IVF_STORAGES = ("f32", "f16")        # IVFIndex.STORAGES / IVFIndex.SCANS, named here for the checks that run before the class exists
+IVF_STORAGES = ("f32", "f16", "pq")      # IVFIndex.STORAGES / IVFIndex.SCANS, named here for the checks that run before the class exists
 IVF_SCANS = ("buffer", "filter")
 
 
-def _check_ivf_options(storage, refine, scan, ks=()):
+PQ_M_MIN, PQ_M_MAX, PQ_CODEWORDS = 8, 64, 256     # include/cdml_ivf_pq.h
+
+
+def _check_pq_m(storage, pq_m, Dp=None, what="pq_m"):
+    """``pq_m`` of an index with ``storage``: None for "f32" / "f16" (anything else is refused), a multiple of 8 in [8, 64]
+    that divides ``Dp`` (where known) for "pq".  Pure host arithmetic."""
+    if storage != "pq":
+        if pq_m is not None:
+            raise ValueError("%s belongs to storage=\"pq\" (got storage=%r)" % (what, storage))
+        return None
+    if pq_m is None:
+        raise ValueError("storage=\"pq\" needs pq_m: the bytes per listed row, a multiple of 8 in [%d, %d] that divides Dp"
+                         % (PQ_M_MIN, PQ_M_MAX))
+    m = int(pq_m)
+    if m != pq_m or not PQ_M_MIN <= m <= PQ_M_MAX or m % 8:
+        raise ValueError("%s must be a multiple of 8 in [%d, %d], got %r" % (what, PQ_M_MIN, PQ_M_MAX, pq_m))
+    if Dp is not None and Dp % m:
+        raise ValueError("%s = %d does not divide the padded dimension Dp = %d" % (what, m, Dp))
+    return m
+
+
+def _check_ivf_options(storage, refine, scan, ks=(), pq_m=None):
     """The refusals of the IVF options the export's call sites share, by name, before any device work.  ``ks``: the list
     lengths the searches will ask for (a re-rank must keep at least that many)."""
     if storage not in IVF_STORAGES:
         raise ValueError("storage must be one of %s, got %r" % (IVF_STORAGES, storage))
     if scan not in IVF_SCANS:
         raise ValueError("scan must be one of %s, got %r" % (IVF_SCANS, scan))
+    _check_pq_m(storage, pq_m)
+    if storage == "pq" and scan == "filter":
+        raise ValueError("scan=\"filter\" (DESIGN.md section 9f.2) has no launch for storage=\"pq\": use scan=\"buffer\"")
     r = int(refine)
     if r != refine or r < 0:
         raise ValueError("refine must be an integer >= 0, got %r" % (refine,))
-    if r and storage != "f16":
-        raise ValueError("refine belongs to storage=\"f16\" (the distances of storage=\"f32\" are exact already)")
+    if r and storage == "f32":
+        raise ValueError("refine belongs to storage=\"f16\" or \"pq\" (the distances of storage=\"f32\" are exact already)")
     if r and ks and not max(ks) <= r <= ops.knn_list_capacity():
         raise ValueError("refine must be 0 or in [k = %d, %d], got %d" % (max(ks), ops.knn_list_capacity(), r))
     return r
@@ -277,16 +301,16 @@ def _check_ivf_lists(what, nlist, nprobe, n_rows):
 
 
 def ivf_knn(base, queries=None, k=51, nlist=1024, nprobe=16, l2_norm=True, storage="f32", refine=0, scan="buffer", iters=10,
-            seed=0, device="cuda:0", precision="f32x3", index=None, stats=None):
+            seed=0, device="cuda:0", precision="f32x3", index=None, stats=None, pq_m=None):
     """Device (D, I) of ``IVFIndex.search``, shaped and typed like ``knn_search``'s: the index of ``base`` (built here with
     ``nlist`` lists, ``iters`` Lloyd iterations and ``seed``, or taken as ``index=``), every query's ``nprobe`` nearest lists
-    scanned exactly.  ``queries=None`` is the self-search.  ``refine>0`` (storage "f16") re-ranks the ``refine`` best against
-    the fp32 rows ``index.prepare(base)``.  The one place the export's approximate searches go through; its launches are
-    those of DESIGN.md sections 9f-9f.2.  ``stats`` (a dict, optional) receives ``IVFIndex.search``'s."""
+    scanned exactly.  ``queries=None`` is the self-search.  ``refine>0`` (storage "f16" or "pq"; "pq" takes ``pq_m``, the
+    bytes per listed row) re-ranks the ``refine`` best against the fp32 rows ``index.prepare(base)``.  The one place the export's approximate searches go through; its launches are
+    those of DESIGN.md sections 9f-9f.3.  ``stats`` (a dict, optional) receives ``IVFIndex.search``'s."""
     if index is None:
-        _check_ivf_options(storage, refine, scan, (int(k),))
+        _check_ivf_options(storage, refine, scan, (int(k),), pq_m)
         index = IVFIndex.build(base, int(nlist), iters=iters, seed=seed, l2_norm=l2_norm, device=device, precision=precision,
-                               storage=storage)
+                               storage=storage, pq_m=pq_m)
     q = base if queries is None else queries
     kw = {"refine": int(refine), "base": index.prepare(base)} if int(refine) > 0 else {}
     return index.search(q, int(k), int(nprobe), stats=stats, scan=scan, **kw)
@@ -312,34 +336,35 @@ def _check_cross_lists(nlist, nprobe, doc_location, n):
 
 
 def cross_knn(embeddings, doc_location, nearest_num=81, precision="f32x3", device="cuda:0", nlist=0, nprobe=0, storage="f32",
-              refine=0, scan="buffer", ivf_iters=10, ivf_seed=0, stats=None):
+              refine=0, scan="buffer", ivf_iters=10, ivf_seed=0, stats=None, pq_m=None):
     """(crossD, crossI) as faiss_knn.py:325-336 builds them: rows [0, doc_location) (videos) search the documents, their
     ids offset by ``doc_location`` into global ids; rows [doc_location, n) (documents) search the videos.  Rows are in
     global order, so the query of row r is r.  The exact search (``knn_search``) stands for the reference's HNSW.  A -1
     ("no neighbour": a side with fewer than nearest_num rows) stays -1 instead of taking the offset.  Returns the kind
     of ``embeddings``.
     ``nlist > 0``: either side is searched through an ``IVFIndex`` of its own (``ivf_knn``) with ``cross_nlist(nlist, n_side,
-    n)`` lists, of which min(nprobe, that many) are probed; ``storage``, ``refine``, ``scan``, ``ivf_iters`` and ``ivf_seed`` go
+    n)`` lists, of which min(nprobe, that many) are probed; ``storage``, ``pq_m``, ``refine``, ``scan``, ``ivf_iters`` and ``ivf_seed`` go
     to both.  ``stats`` (a dict, optional) receives the two searches' under "video_to_doc" and "doc_to_video"."""
     t = embeddings if torch.is_tensor(embeddings) else torch.from_numpy(np.asarray(embeddings, dtype=np.float32))
     if int(nlist) or int(nprobe):
         n = t.shape[0]
         nlist, nprobe = _check_cross_lists(nlist, nprobe, int(doc_location), n)
-        _check_ivf_options(storage, refine, scan, (int(nearest_num),))
+        _check_ivf_options(storage, refine, scan, (int(nearest_num),), pq_m)
         video, doc = t[:doc_location], t[doc_location:]
         out = []
         for name, base, q in (("video_to_doc", doc, video), ("doc_to_video", video, doc)):
             nl = cross_nlist(nlist, base.shape[0], n)
             st = None if stats is None else stats.setdefault(name, {})
             out.append(ivf_knn(base, q, int(nearest_num), nlist=nl, nprobe=min(nprobe, nl), storage=storage, refine=refine,
-                               scan=scan, iters=ivf_iters, seed=ivf_seed, device=device, precision=precision, stats=st))
+                               scan=scan, iters=ivf_iters, seed=ivf_seed, device=device, precision=precision, stats=st,
+                               pq_m=pq_m))
         (vdD, vdI), (dvD, dvI) = out
         vdI = torch.where(vdI >= 0, vdI + doc_location, vdI)
         D, I = torch.cat([vdD, dvD]), torch.cat([vdI, dvI])
         if torch.is_tensor(embeddings):
             return D, I
         return D.cpu().numpy(), I.cpu().numpy()
-    _check_ivf_options(storage, refine, scan)
+    _check_ivf_options(storage, refine, scan, pq_m=pq_m)
     if storage != "f32" or int(refine) or scan != "buffer":
         raise ValueError("storage, refine and scan belong to nlist > 0 (this search is exact)")
     video, doc = t[:doc_location], t[doc_location:]
@@ -577,7 +602,7 @@ def _scalars(st):
 def export(embeddings, features, decode_map, out_dir, doc_location=343455, nearest_num=81, desim_nearest_num=26,
            fD_threshold=DESIM_THRESHOLD, fI_end=DESIM_FI_END, precision="f32x3", device="cuda:0", split_num=10,
            nlist=0, nprobe=0, feature_nlist=0, feature_nprobe=0, storage="f32", refine=0, scan="buffer", ivf_iters=10,
-           ivf_seed=0, feature_knn=None, writer="host", audit_rows=0, audit_seed=0, stats=None):
+           ivf_seed=0, feature_knn=None, writer="host", audit_rows=0, audit_seed=0, stats=None, pq_m=None, feature_pq_m=None):
     """faiss_knn.main (faiss_knn.py:359-400) with explicit arguments: the raw-feature kNN (fD, fI; k = min(desim_nearest_num,
     nearest_num)), then -- cross mode when 0 < doc_location < n, strict mode otherwise -- the embedding kNN, desim and the
     text lists.  Writes fD.npy, fI.npy, {strict,cross}D.npy, {strict,cross}I.npy, {strict,cross}I_desim.npy, the
@@ -588,7 +613,8 @@ def export(embeddings, features, decode_map, out_dir, doc_location=343455, neare
     At catalogue scale; every default keeps the exact path and its bytes:
     ``nlist`` / ``nprobe``: the embedding search through ``ivf_knn`` (strict) or ``cross_knn(nlist=...)`` (cross: an index per
     side).  ``feature_nlist`` / ``feature_nprobe``: the raw-feature search through ``ivf_knn``, independently.  ``storage``,
-    ``refine``, ``scan``, ``ivf_iters``, ``ivf_seed`` go to every index.  ``feature_knn``: (fD, fI) or a directory holding
+    ``refine``, ``scan``, ``ivf_iters``, ``ivf_seed`` go to every index; with ``storage="pq"`` the embedding indexes take ``pq_m``
+    and the raw-feature index ``feature_pq_m`` (default: ``pq_m``).  ``feature_knn``: (fD, fI) or a directory holding
     fD.npy / fI.npy of an earlier export -- raw features do not change when the model is retrained -- written as given, no
     feature search (``features`` may then be None unless the audit needs them).  ``writer``: "host" | "device"
     (``write_knn``).  ``audit_rows = m > 0``: the recall statement -- for the rows ``audit_sample(n, m, audit_seed)`` the
@@ -606,7 +632,8 @@ def export(embeddings, features, decode_map, out_dir, doc_location=343455, neare
         raise ValueError("writer must be one of %s, got %r" % (WRITERS, writer))
     nlist, nprobe = _check_cross_lists(nlist, nprobe, int(doc_location), n) if cross else _check_ivf_lists("", nlist, nprobe, n)
     feature_nlist, feature_nprobe = _check_ivf_lists("feature_", feature_nlist, feature_nprobe, n)
-    refine = _check_ivf_options(storage, refine, scan, ((k,) if nlist else ()) + ((k_f,) if feature_nlist else ()))
+    refine = _check_ivf_options(storage, refine, scan, ((k,) if nlist else ()) + ((k_f,) if feature_nlist else ()), pq_m)
+    feature_pq_m = _check_pq_m(storage, pq_m if feature_pq_m is None else feature_pq_m, what="feature_pq_m")
     if not (nlist or feature_nlist) and (storage != "f32" or refine or scan != "buffer"):
         raise ValueError("storage, refine and scan belong to an IVF search: set nlist or feature_nlist (both are 0)")
     if feature_knn is not None:
@@ -621,6 +648,7 @@ def export(embeddings, features, decode_map, out_dir, doc_location=343455, neare
     if audit_rows and features is None:
         raise ValueError("the audit runs the exact raw-feature search: it needs features")
     ivf = {"storage": storage, "refine": refine, "scan": scan}
+    pq = {"pq_m": int(pq_m), "feature_pq_m": feature_pq_m} if storage == "pq" else {}
 
     def stage(name, t0, extra=None):
         if stats is not None:
@@ -636,7 +664,7 @@ def export(embeddings, features, decode_map, out_dir, doc_location=343455, neare
     elif feature_nlist:
         st = {}
         fD, fI = ivf_knn(features, None, k_f, nlist=feature_nlist, nprobe=feature_nprobe, iters=ivf_iters, seed=ivf_seed,
-                         device=device, precision=precision, stats=st, **ivf)
+                         device=device, precision=precision, stats=st, pq_m=pq.get("feature_pq_m"), **ivf)
         t0 = stage("feature_knn", t0, {"ivf": _scalars(st)})
     else:
         fD, fI = knn_search(features, features, k_f, device=device, precision=precision)
@@ -650,14 +678,15 @@ def export(embeddings, features, decode_map, out_dir, doc_location=343455, neare
         mode = "cross"
         if nlist:
             D, I = cross_knn(emb.to(device), doc_location, nearest_num=nearest_num, precision=precision, device=device,
-                             nlist=nlist, nprobe=nprobe, ivf_iters=ivf_iters, ivf_seed=ivf_seed, stats=st, **ivf)
+                             nlist=nlist, nprobe=nprobe, ivf_iters=ivf_iters, ivf_seed=ivf_seed, stats=st, pq_m=pq.get("pq_m"),
+                             **ivf)
         else:
             D, I = cross_knn(emb.to(device), doc_location, nearest_num=nearest_num, precision=precision, device=device)
     else:
         mode = "strict"
         if nlist:
             D, I = ivf_knn(emb, None, k, nlist=nlist, nprobe=nprobe, iters=ivf_iters, seed=ivf_seed, device=device,
-                           precision=precision, stats=st, **ivf)
+                           precision=precision, stats=st, pq_m=pq.get("pq_m"), **ivf)
         else:
             D, I = knn_search(emb, emb, int(nearest_num), device=device, precision=precision)
     t0 = stage("embedding_knn", t0, {"ivf": _scalars(st)} if nlist else None)
@@ -686,7 +715,7 @@ def export(embeddings, features, decode_map, out_dir, doc_location=343455, neare
         report = dict(counts, mode=mode, n=n, doc_location=int(doc_location), nearest_num=k, desim_nearest_num=k_f,
                       fD_threshold=float(fD_threshold), fI_end=int(fI_end), precision=precision, nlist=nlist, nprobe=nprobe,
                       feature_nlist=feature_nlist, feature_nprobe=feature_nprobe, ivf_iters=int(ivf_iters), ivf_seed=int(ivf_seed),
-                      feature_knn_given=feature_knn is not None, audit_seed=int(audit_seed), **ivf)
+                      feature_knn_given=feature_knn is not None, audit_seed=int(audit_seed), **ivf, **pq)
         with open(os.path.join(out_dir, "export_audit.json"), "w") as f:
             json.dump(report, f, indent=1, sort_keys=True)
         stage("audit", t0)
@@ -729,12 +758,14 @@ def ivf_plan_chunks(costs, score_bytes, max_queries=None):
     return chunks
 
 
-def ivf_tables(probe, list_len):
+def ivf_tables(probe, list_len, tile_slots=IVF_TILE, tile_rows=IVF_TILE):
     """The slot, tile and offset tables of one query chunk (plumbing: torch calls on ``probe``'s device, ONE host read).
     probe int32 [m, nprobe] (-1 = no list); list_len int64 [nlist].  A slot is one (query, probed list) pair; slots are
     sorted by list (stably: by query inside a list).  Returns a dict: n_slots, n_floats, n_tiles (ints), slot_query int32
     [n_slots], slot_start int32 [nlist + 1], slot_off int64 [n_slots], slot_of int32 [m, nprobe] (-1 for a -1 probe), tiles
-    int32 [n_tiles, 4] = (list, first slot in the list's block, first row in the list, 0), ordered by list."""
+    int32 [n_tiles, 4] = (list, first slot in the list's block, first row in the list, 0), ordered by list.  A tile is
+    ``tile_slots`` x ``tile_rows`` (the MFMA scans' 128 x 128; the PQ scan's ``ops.ivf_pq_tile(M)``)."""
+    tile_slots, tile_rows = int(tile_slots), int(tile_rows)
     m, nprobe = probe.shape
     nlist = list_len.numel()
     dev = probe.device
@@ -747,8 +778,8 @@ def ivf_tables(probe, list_len):
     ld = (list_len + 3) // 4 * 4
     blk = cnt * ld                                            # floats of list c's score block [cnt][ld]
     blk_off = torch.cumsum(blk, 0) - blk
-    tn = (list_len + IVF_TILE - 1) // IVF_TILE
-    nt = (cnt + IVF_TILE - 1) // IVF_TILE * tn
+    tn = (list_len + tile_rows - 1) // tile_rows
+    nt = (cnt + tile_slots - 1) // tile_slots * tn
     tile_start = torch.cumsum(nt, 0) - nt
     n_slots, n_floats, n_tiles = torch.stack([slot_start[-1], blk.sum(), nt.sum()]).tolist()      # the host read
     slot_list = skey[:n_slots]
@@ -758,10 +789,71 @@ def ivf_tables(probe, list_len):
     tc = torch.repeat_interleave(torch.arange(nlist, device=dev), nt, output_size=n_tiles)
     loc = torch.arange(n_tiles, device=dev) - tile_start[tc]
     tnc = tn[tc].clamp(min=1)
-    tiles = torch.stack([tc, loc // tnc * IVF_TILE, loc % tnc * IVF_TILE, torch.zeros_like(tc)], 1).to(torch.int32).contiguous()
+    tiles = torch.stack([tc, loc // tnc * tile_slots, loc % tnc * tile_rows, torch.zeros_like(tc)], 1).to(torch.int32).contiguous()
     return {"n_slots": n_slots, "n_floats": n_floats, "n_tiles": n_tiles,
             "slot_query": (order[:n_slots] // nprobe).to(torch.int32), "slot_start": slot_start.to(torch.int32),
             "slot_off": slot_off, "slot_of": slot_of.view(m, nprobe), "tiles": tiles}
+
+
+def pq_query_floats(pq_m):
+    """256 M: the floats of one query's lookup table, what a query of a pq index costs a chunk beside its scores"""
+    return PQ_CODEWORDS * int(pq_m)
+
+
+PQ_TRAIN_ROWS = 65536       # default training rows of pq_train (256 per codeword)
+
+
+def _check_pq_train(n_finite, iters, train_rows):
+    """(n_train, iters) of ``pq_train``: the refusals, by name"""
+    iters = int(iters)
+    if iters < 0:
+        raise ValueError("pq_iters must be >= 0, got %d" % iters)
+    if n_finite < PQ_CODEWORDS:
+        raise ValueError("storage=\"pq\" needs at least %d finite rows to start its codebooks from, got %d" % (PQ_CODEWORDS, n_finite))
+    n_train = min(n_finite, PQ_TRAIN_ROWS) if train_rows is None else int(train_rows)
+    if not PQ_CODEWORDS <= n_train <= n_finite:
+        raise ValueError("pq_train_rows must be in [%d, the number of finite rows = %d], got %d" % (PQ_CODEWORDS, n_finite, n_train))
+    return n_train, iters
+
+
+def pq_train(X_prepared, pq_m, iters=10, seed=0, train_rows=None):
+    """(codebooks fp32 [M, 256, Dp / M] on X's device, pq_objective float64 [M, iters] on the CPU): the deterministic Lloyd's of
+    ``IVFIndex.build`` per subspace (include/cdml_ivf_pq.h).  ``X_prepared``: the fp32 device matrix [n, Dp] of
+    ``IVFIndex.prepare``.  The training rows are the (sorted) first ``train_rows`` ids of the seeded CPU permutation of the
+    finite rows (default min(n_finite, 65 536)); every subspace's 256 initial codewords are the sub-vectors of the sorted
+    first 256 ids.  An iteration encodes the training rows (``ops.pq_encode``) and replaces every non-empty codeword by the
+    mean of its rows (``ops.ivf_centroid_sums``, rows ordered by (code, id)); an empty codeword keeps its value.
+    pq_objective[m, t] = the sum of iteration t's attained distances in subspace m."""
+    X = X_prepared
+    if not torch.is_tensor(X) or X.dtype != torch.float32 or X.dim() != 2 or X.stride(1) != 1:
+        raise ValueError("pq_train takes the prepared fp32 [n, Dp] matrix (IVFIndex.prepare)")
+    n, Dp = X.shape
+    M = _check_pq_m("pq", pq_m, Dp)
+    dsub = Dp // M
+    dev = X.device
+    fin = torch.nonzero(torch.isfinite(X).all(1)).flatten().cpu()
+    n_finite = int(fin.numel())
+    n_train, iters = _check_pq_train(n_finite, iters, train_rows)
+    g = torch.Generator()
+    g.manual_seed(int(seed))
+    perm = torch.randperm(n_finite, generator=g)
+    init_rows = torch.sort(fin[perm[:PQ_CODEWORDS]]).values
+    train_ids = torch.sort(fin[perm[:n_train]]).values
+    Xt = X if n_train == n else X.index_select(0, train_ids.to(dev))
+    cb = X.index_select(0, init_rows.to(dev)).view(PQ_CODEWORDS, M, dsub).permute(1, 0, 2).contiguous()
+    codes = torch.empty((n_train, M), dtype=torch.uint8, device=dev)
+    dist = torch.empty((n_train, M), dtype=torch.float32, device=dev)
+    objective = torch.zeros((M, iters), dtype=torch.float64)
+    for it in range(iters):
+        ops.pq_encode(Xt, cb, codes, dist)
+        objective[:, it] = dist.double().sum(0).cpu()
+        for m in range(M):
+            key = codes[:, m].to(torch.int64)
+            order = torch.argsort(key, stable=True).to(torch.int32)       # by (code, id)
+            start = torch.zeros(PQ_CODEWORDS + 1, dtype=torch.int64, device=dev)
+            start[1:] = torch.cumsum(torch.bincount(key, minlength=PQ_CODEWORDS), 0)
+            ops.ivf_centroid_sums(Xt[:, m * dsub:(m + 1) * dsub], order, start.to(torch.int32), cb[m], dsub)
+    return cb, objective
 
 
 class IVFIndex:
@@ -778,11 +870,16 @@ class IVFIndex:
     image overflows is unlisted; k-means, ``assign``, ``centroids`` and the probes are those of the fp32 index.  ``search``
     then scans on the fp16 MFMA, and ``refine=r`` re-scores the r best candidates against fp32 rows (``base=``).
 
+    ``storage="pq"`` (include/cdml_ivf_pq.h): product-quantised lists.  ``codes`` uint8 [n_listed,
+    pq_m] stands where ``rows`` stood (there is no ``rows``), ``codebooks`` fp32 [pq_m, 256, Dp / pq_m] (``pq_train``, or given),
+    ``pq_objective`` float64 [pq_m, pq_iters] (CPU), ``r_sq`` the norms of the decoded rows, ``decode(positions)`` the decoded
+    rows.  ``search`` scans by table lookup (one lookup table per query); ``refine=r`` re-ranks as for "f16".
+
     ``search(..., scan="filter")`` (include/cdml_ivf_filter.h) is the same search, bit for bit, with a
     score buffer for the first ``seed_probes`` probe columns only: the other columns append what is within the seeded
     threshold to ``filter_cap`` candidate slots per query."""
 
-    STORAGES = ("f32", "f16")
+    STORAGES = ("f32", "f16", "pq")
     _NORM_ROWS = 1 << 20        # rows per fp32 temporary when the squared norms of fp16 rows are taken
 
     def __init__(self):
@@ -828,10 +925,13 @@ class IVFIndex:
         return out
 
     @classmethod
-    def _blank(cls, nlist, D, l2_norm, device, precision, storage="f32"):
+    def _blank(cls, nlist, D, l2_norm, device, precision, storage="f32", pq_m=None):
         self = object.__new__(cls)
         self.nlist, self.dim, self.l2_norm, self.device, self.precision = int(nlist), int(D), bool(l2_norm), torch.device(device), precision
         self.storage = cls._check_storage(storage)
+        if storage == "pq":
+            self.pq_m = int(pq_m)
+            self.pq_objective = torch.empty((self.pq_m, 0), dtype=torch.float64)
         self.init_rows = self.train_ids = torch.empty(0, dtype=torch.int64)
         self.objective = torch.empty(0, dtype=torch.float64)
         return self
@@ -855,7 +955,15 @@ class IVFIndex:
         self.ids = order[:n_listed].to(torch.int32)
         self.list_start = start.to(torch.int32)
         self.list_len = cnt[:self.nlist].contiguous()
-        if self.storage == "f16":
+        if self.storage == "pq":
+            codes = torch.empty((n, self.pq_m), dtype=torch.uint8, device=X.device)
+            ops.pq_encode(X, self.codebooks, codes)           # (an unlisted row's codes are computed and dropped)
+            self.codes = codes.index_select(0, order[:n_listed])
+            self.r_sq = torch.zeros(n_listed, dtype=torch.float32, device=X.device)
+            for r0 in range(0, n_listed, self._NORM_ROWS):
+                part = self.decode(torch.arange(r0, min(r0 + self._NORM_ROWS, n_listed), device=X.device))
+                ops.row_sqnorm(part, Dp, self.r_sq[r0:r0 + self._NORM_ROWS])
+        elif self.storage == "f16":
             self.rows = Xh.index_select(0, order[:n_listed])
             self.r_sq = self._sqnorm_f16(self.rows)
         else:
@@ -867,12 +975,39 @@ class IVFIndex:
         self.n_rows, self.n_listed, self.n_unlisted = n, n_listed, n - n_listed
         return self
 
+    def decode(self, positions):
+        """fp32 [len, Dp]: the decoded rows (the concatenated codewords) at ``positions`` of the cluster-major lists
+        (plumbing: a torch gather).  storage "pq" only."""
+        if self.storage != "pq":
+            raise ValueError("decode belongs to an index with storage=\"pq\" (this one is %r)" % self.storage)
+        c = self.codes.index_select(0, positions.to(device=self.device, dtype=torch.int64)).to(torch.int64)
+        m = torch.arange(self.pq_m, device=self.device)
+        return self.codebooks[m[None, :], c].reshape(c.shape[0], -1)
+
+    @staticmethod
+    def _check_codebooks(codebooks, Dp):
+        """(codebooks as a CPU-or-device fp32 tensor, M): the refusals of a given ``codebooks``, by name"""
+        cb = codebooks if torch.is_tensor(codebooks) else torch.as_tensor(np.asarray(codebooks))
+        if cb.dtype != torch.float32 or cb.dim() != 3 or cb.shape[1] != PQ_CODEWORDS or cb.shape[0] * cb.shape[2] != Dp:
+            raise ValueError("codebooks must be a float32 [M, %d, Dp / M] tensor with M dsub = Dp = %d, got %s %s"
+                             % (PQ_CODEWORDS, Dp, tuple(cb.shape), cb.dtype))
+        return cb, _check_pq_m("pq", cb.shape[0], Dp, what="the codebooks' M")
+
     @classmethod
-    def from_assignment(cls, base, centroids, assign, l2_norm=True, device="cuda:0", precision="f32x3", storage="f32"):
+    def from_assignment(cls, base, centroids, assign, l2_norm=True, device="cuda:0", precision="f32x3", storage="f32",
+                        codebooks=None):
         """The index of given ``centroids`` ([nlist, D]) and an arbitrary ``assign`` (int [n], values in [-1, nlist); -1 =
-        unlisted): the search contract does not need the assignment to be the nearest centroid."""
+        unlisted): the search contract does not need the assignment to be the nearest centroid.  ``storage="pq"`` takes
+        ``codebooks`` (fp32 [M, 256, Dp / M]) as they are."""
         cls._check_storage(storage)
         t = cls._as_tensor(base)
+        pq_m = None
+        if storage == "pq":
+            if codebooks is None:
+                raise ValueError("from_assignment(storage=\"pq\") needs codebooks= (fp32 [M, 256, Dp / M]; knn.pq_train)")
+            codebooks, pq_m = cls._check_codebooks(codebooks, _round_up(t.shape[1], 32))
+        elif codebooks is not None:
+            raise ValueError("codebooks belongs to storage=\"pq\" (got storage=%r)" % storage)
         c = centroids if torch.is_tensor(centroids) else torch.as_tensor(np.asarray(centroids, dtype=np.float32))
         a = assign if torch.is_tensor(assign) else torch.as_tensor(np.asarray(assign))
         if c.dim() != 2 or c.shape[0] < 1 or c.shape[1] != t.shape[1]:
@@ -882,18 +1017,25 @@ class IVFIndex:
         nlist = c.shape[0]
         if a.numel() and (int(a.min()) < -1 or int(a.max()) >= nlist):
             raise ValueError("assign must lie in [-1, nlist = %d)" % nlist)
-        self = cls._blank(nlist, t.shape[1], l2_norm, device, precision, storage)
+        self = cls._blank(nlist, t.shape[1], l2_norm, device, precision, storage, pq_m)
+        if storage == "pq":
+            self.codebooks = codebooks.detach().to(self.device).contiguous().clone()
         X = cls._prepared(t, self.device, l2_norm)
         return self._set_lists(X, _device_matrix(c, self.device, 1, 32), a)
 
     @classmethod
     def build(cls, base, nlist, iters=10, seed=0, train_rows=None, l2_norm=True, device="cuda:0", precision="f32x3",
-              storage="f32"):
+              storage="f32", pq_m=None, pq_iters=None, pq_seed=None, pq_train_rows=None):
         """Lloyd's k-means, deterministic (include/cdml_ivf.h BUILD).  ``precision`` is that of the coarse ``knn_search`` calls
-        (every assignment step, and ``probes``).  ``storage`` ("f32" | "f16") is the format of the lists alone: k-means runs on
-        the fp32 rows either way, so (base, seed) gives the same ``assign`` and the same probes for both."""
+        (every assignment step, and ``probes``).  ``storage`` ("f32" | "f16" | "pq") is the format of the lists alone: k-means
+        runs on the fp32 rows either way, so (base, seed) gives the same ``assign`` and the same probes for all three.
+        ``storage="pq"``: ``pq_m`` bytes per row; the codebooks come from ``pq_train(X, pq_m, pq_iters (default 10), pq_seed
+        (default ``seed``), pq_train_rows)`` on the prepared rows."""
         cls._check_storage(storage)
         t = cls._as_tensor(base)
+        pq_m = _check_pq_m(storage, pq_m, _round_up(t.shape[1], 32))
+        if storage != "pq" and (pq_iters is not None or pq_seed is not None or pq_train_rows is not None):
+            raise ValueError("pq_iters, pq_seed and pq_train_rows belong to storage=\"pq\" (got storage=%r)" % storage)
         nlist, iters = int(nlist), int(iters)
         n_finite = int(torch.isfinite(t).all(1).sum())
         if not 1 <= nlist <= n_finite:
@@ -903,7 +1045,9 @@ class IVFIndex:
         n_train = min(n_finite, 256 * nlist) if train_rows is None else int(train_rows)
         if not nlist <= n_train <= n_finite:
             raise ValueError("train_rows must be in [nlist = %d, the number of finite rows = %d], got %d" % (nlist, n_finite, n_train))
-        self = cls._blank(nlist, t.shape[1], l2_norm, device, precision, storage)
+        if storage == "pq":
+            _check_pq_train(n_finite, 10 if pq_iters is None else pq_iters, pq_train_rows)
+        self = cls._blank(nlist, t.shape[1], l2_norm, device, precision, storage, pq_m)
         dev = self.device
         X = cls._prepared(t, dev, l2_norm)
         n, Dp = X.shape
@@ -930,6 +1074,9 @@ class IVFIndex:
             start[1:] = torch.cumsum(torch.bincount(key, minlength=nlist + 1)[:nlist], 0)
             ops.ivf_centroid_sums(Xt, order, start.to(torch.int32), C, Dp)
         _, Ia = knn_search(C, X, 1, l2_norm=False, device=dev, precision=precision)
+        if storage == "pq":
+            self.codebooks, self.pq_objective = pq_train(X, pq_m, iters=10 if pq_iters is None else pq_iters,
+                                                         seed=seed if pq_seed is None else pq_seed, train_rows=pq_train_rows)
         self._set_lists(X, C, Ia[:, 0])
         self.init_rows, self.train_ids = init_rows, train_ids
         self.objective = torch.stack(objective).cpu() if objective else torch.empty(0, dtype=torch.float64)
@@ -942,15 +1089,25 @@ class IVFIndex:
                  "precision": self.precision, "init_rows": self.init_rows.clone(), "objective": self.objective.clone()}
         if self.storage != "f32":
             state["storage"] = self.storage
+        if self.storage == "pq":
+            state["pq_m"] = self.pq_m
+            state["codebooks"] = self.codebooks.detach().cpu().clone()
         return state
 
     @classmethod
     def load_state_dict(cls, state, base, device="cuda:0", storage=None):
         """The index of ``state_dict()`` over the same catalogue ``base``.  ``storage`` (default: the state's, "f32" where
-        it names none) may re-derive the lists in the other format: centroids and assign do not depend on it."""
+        it names none) may re-derive the lists in another format: centroids and assign do not depend on it.  "pq" needs
+        the state's codebooks (a state of a pq index); its codes are re-derived from ``base``, bit for bit."""
+        storage = cls._check_storage(state.get("storage", "f32") if storage is None else storage)
+        kw = {}
+        if storage == "pq":
+            if "codebooks" not in state:
+                raise ValueError("this state holds no codebooks (it is not the state of a storage=\"pq\" index): it cannot be "
+                                 "loaded as \"pq\"")
+            kw["codebooks"] = state["codebooks"]
         self = cls.from_assignment(base, state["centroids"], state["assign"], l2_norm=state["l2_norm"], device=device,
-                                   precision=state["precision"],
-                                   storage=state.get("storage", "f32") if storage is None else storage)
+                                   precision=state["precision"], storage=storage, **kw)
         self.init_rows, self.objective = state["init_rows"].clone(), state["objective"].clone()
         return self
 
@@ -991,7 +1148,7 @@ class IVFIndex:
         r = int(refine)
         if self.storage == "f32":
             if r != 0 or base is not None:
-                raise ValueError("refine and base belong to an index with storage=\"f16\" (this one is \"f32\": its distances are exact already)")
+                raise ValueError("refine and base belong to an index with storage=\"f16\" or \"pq\" (this one is \"f32\": its distances are exact already)")
             return 0, None
         if r == 0:
             if base is not None:
@@ -1040,6 +1197,8 @@ class IVFIndex:
         """the refusals of ``search``'s scan arguments, by name, before any device work"""
         if scan not in self.SCANS:
             raise ValueError("scan must be one of %s, got %r" % (self.SCANS, scan))
+        if scan == "filter" and self.storage == "pq":
+            raise ValueError("scan=\"filter\" (DESIGN.md section 9f.2) has no launch for storage=\"pq\": use scan=\"buffer\"")
         if scan == "buffer":
             if filter_cap is not None or seed_probes is not None:
                 raise ValueError("filter_cap and seed_probes belong to scan=\"filter\" (this search is scan=\"buffer\")")
@@ -1056,18 +1215,22 @@ class IVFIndex:
         """The buffered search of prepared queries ``Q`` over ``probe`` (int32 [nq, nprobe]) into best_d / best_i (and cand_d /
         cand_i, the merge's lists, when they are other tensors: ``refine``): per chunk the slot tables, the grouped product
         into the ragged score buffer, the merge, the re-rank.  Returns (chunks, n_tiles, n_floats)."""
-        f16 = self.storage == "f16"
+        f16, pq = self.storage == "f16", self.storage == "pq"
         Dp = Q.shape[1]
         nprobe = probe.shape[1]
         ld = (self.list_len + 3) // 4 * 4
         p = probe.to(torch.int64)
         costs = torch.where(p >= 0, ld[p.clamp(min=0)], torch.zeros_like(p)).sum(1).cpu().numpy()
+        tile = {}
+        if pq:                                            # a chunk's scores AND lookup tables fit score_bytes together
+            costs = costs + pq_query_floats(self.pq_m)
+            tile["tile_slots"], tile["tile_rows"] = ops.ivf_pq_tile(self.pq_m)
         chunks = ivf_plan_chunks(costs, score_bytes, max_queries=(2 ** 31 - 1) // nprobe)
         n_tiles = n_floats = 0
         keep = refine or k                                # entries the merge must get right
         for q0, q1 in chunks:
             pc = probe[q0:q1].contiguous()
-            tb = ivf_tables(pc, self.list_len)
+            tb = ivf_tables(pc, self.list_len, **tile)
             n_tiles += tb["n_tiles"]
             n_floats += tb["n_floats"]
             if tb["n_slots"] == 0:                        # nothing probed (non-finite queries only)
@@ -1083,6 +1246,12 @@ class IVFIndex:
                 if tb["n_tiles"]:
                     ops.ivf_scan_f16(Qh, tb["slot_query"], tb["slot_start"], tb["slot_off"], self.rows, self.list_start,
                                      tb["tiles"], scores)
+            elif pq:
+                if tb["n_tiles"]:
+                    lut = torch.empty((q1 - q0, self.pq_m, PQ_CODEWORDS), dtype=torch.float32, device=Q.device)
+                    ops.pq_lut(Q[q0:q1], self.codebooks, lut)
+                    ops.ivf_scan_pq(lut, tb["slot_query"], tb["slot_start"], tb["slot_off"], self.codes, self.list_start,
+                                    tb["tiles"], scores)
             elif tb["n_tiles"]:
                 ops.ivf_scan_f32(Q[q0:q1], tb["slot_query"], tb["slot_start"], tb["slot_off"], self.rows, self.list_start,
                                  tb["tiles"], scores)
@@ -1182,6 +1351,9 @@ class IVFIndex:
         of the rounded values (a query whose image is non-finite probes nothing); ``refine=r`` (k <= r <= 128, with
         ``base`` = the fp32 matrix of ``prepare(catalogue)``) keeps the r best of them and returns the k best under the fp32
         distances sum (q - x)^2 of the fp32 rows (include/cdml_ivf_f16.h).
+        On an index with storage "pq" (include/cdml_ivf_pq.h) the distances are those of the decoded rows to the unrounded
+        query, scored by table lookup; a chunk holds its queries' lookup tables (256 ``pq_m`` floats each) beside its scores
+        within ``score_bytes``; ``refine=r`` re-ranks as for "f16"; ``scan="filter"`` is refused.
         ``scan="filter"`` (include/cdml_ivf_filter.h) writes scores only for the first ``seed_probes``
         probe columns (default ``default_seed_probes(refine or k, nprobe)``): they give every query a keep-th distance tau
         (keep = refine or k), and one launch over the other columns appends what is within tau to ``filter_cap`` candidate

@@ -1761,6 +1761,68 @@ def ivf_refine(Q, base, cand, r, k, best_d, best_i):
          _vec(best_d, torch.float32, nq * cap, "best_d"), _vec(best_i, torch.int32, nq * cap, "best_i"), _stream())
 
 
+# ---------------------------------------- product-quantised lists of the IVF index (include/cdml_ivf_pq.h) ------
+def _codebooks(codebooks):
+    if codebooks.dtype != torch.float32 or codebooks.dim() != 3 or codebooks.shape[1] != 256 or not codebooks.is_contiguous():
+        raise ValueError("codebooks must be a contiguous float32 [M, 256, dsub] tensor")
+    return _p(codebooks), codebooks.shape[0], codebooks.shape[2]
+
+
+def ivf_pq_tile(M):
+    """(S, R): the slots x rows of one work item of ``ivf_scan_pq`` for ``M`` bytes per row (host arithmetic)"""
+    s, r = C.c_int(0), C.c_int(0)
+    call("cdml_ivf_pq_tile", int(M), C.byref(s), C.byref(r))
+    return s.value, r.value
+
+
+def pq_encode(x, codebooks, codes, dist=None):
+    """codes[r, m] (uint8 [n, >= M]; columns past M are not written) = the lowest codeword of subspace m nearest to
+    x[r, m dsub:(m + 1) dsub] (x fp32 [n, >= M dsub]); ``dist`` (fp32 [n, >= M], optional) receives the attained minima."""
+    xp, xld = _mat(x)
+    cp, M, dsub = _codebooks(codebooks)
+    n = x.shape[0]
+    if codes.dtype != torch.uint8 or codes.dim() != 2 or codes.stride(1) != 1 or codes.shape[0] < n or codes.shape[1] < M:
+        raise ValueError("codes must be a uint8 [n, >= M] tensor with unit inner stride")
+    if x.shape[1] < M * dsub:
+        raise ValueError("x rows must hold M dsub = %d columns, got %d" % (M * dsub, x.shape[1]))
+    dp, dld = (C.c_void_p(0), 0) if dist is None else _mat(dist)
+    if dist is not None and (dist.shape[0] < n or dist.shape[1] < M):
+        raise ValueError("dist must be a float32 [n, >= M] tensor")
+    call("cdml_pq_encode", xp, xld, n, cp, M, dsub, _p(codes), codes.stride(0), dp, dld, _stream())
+    return codes
+
+
+def pq_lut(Q, codebooks, lut):
+    """lut[q, m, c] (fp32 [nq, M, 256], contiguous) = the inner product of Q[q, m dsub:(m + 1) dsub] with codeword c of
+    subspace m."""
+    qp, qld = _mat(Q)
+    cp, M, dsub = _codebooks(codebooks)
+    if Q.shape[1] < M * dsub:
+        raise ValueError("query rows must hold M dsub = %d columns, got %d" % (M * dsub, Q.shape[1]))
+    call("cdml_pq_lut", qp, qld, Q.shape[0], cp, M, dsub, _vec(lut, torch.float32, Q.shape[0] * M * 256, "lut"), _stream())
+    return lut
+
+
+def ivf_scan_pq(lut, slot_query, slot_start, slot_off, codes, list_start, tiles, scores):
+    """``ivf_scan_f32`` by table lookup: for every tile (list c, slot tile, row tile; ``ivf_pq_tile(M)`` slots x rows) of
+    ``tiles`` the sums over m of lut[query, m, codes[row, m]] into the ragged score buffer.  lut fp32 [n_queries, M, 256],
+    codes uint8 [n_listed, M]."""
+    if lut.dim() != 3 or lut.shape[2] != 256 or not lut.is_contiguous():
+        raise ValueError("lut must be a contiguous float32 [n_queries, M, 256] tensor")
+    M = lut.shape[1]
+    if codes.dtype != torch.uint8 or codes.dim() != 2 or codes.stride(1) != 1 or codes.shape[1] < M:
+        raise ValueError("codes must be a uint8 [n_listed, >= M] tensor with unit inner stride")
+    nlist = list_start.numel() - 1
+    n_slots = slot_query.numel()
+    if tiles.dim() != 2 or tiles.shape[1] != 4:
+        raise ValueError("tiles must be int32 [n_tiles, 4]")
+    call("cdml_ivf_scan_pq", _p(lut, torch.float32), lut.shape[0], _vec(slot_query, torch.int32, 0, "slot_query"),
+         _vec(slot_start, torch.int32, nlist + 1, "slot_start"), _vec(slot_off, torch.int64, n_slots, "slot_off"), _p(codes),
+         codes.stride(0), _vec(list_start, torch.int32, nlist + 1, "list_start"), M, _vec(tiles, torch.int32, 4, "tiles"),
+         tiles.shape[0], _p(scores, torch.float32), _stream())
+    return scores
+
+
 # ---------------------------------------- threshold-filter scan of the IVF index (include/cdml_ivf_filter.h) ------
 def _ivf_filter(name, qp, qld, rp, rld, Q, slot_query, slot_start, q_sq, tau, cnt, rows, list_start, r_sq, ids, tiles, cand, cap):
     nlist = list_start.numel() - 1

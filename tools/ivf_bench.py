@@ -5,13 +5,16 @@
                                                  # (recall on a 65 536-query sample)
     python tools/ivf_bench.py --n 50000 --nlist 64 --nprobe 4 8 --k 20
     python tools/ivf_bench.py --storage f32 f16 --refine 128   # fp16 lists beside the fp32 ones over the same (centroids, assign)
+    python tools/ivf_bench.py --storage f16 pq --pq-m 32 --refine 128   # product-quantised lists (32 bytes a row) beside the fp16 ones
     python tools/ivf_bench.py --scan buffer filter             # the threshold-filter scan beside the buffered one, same index, same call
 
 Per run one JSON line: build time by stage (one assignment, one centroid update, the whole build), search time by stage
 (coarse / tables / scan / merge), the scan's FLOP from the tile table over its kernel time, recall@k against the exact search,
 max / mean list length, scanned share.  With --storage f16 the line of the fp16 index (storage "f16": the lists re-derived from
 the fp32 index's centroids and assign) follows the fp32 one: the same stages plus the re-rank, issued and useful scan TF/s,
-the index's bytes, and recall@k for refine 0 and --refine.  With --scan filter a line "scan": "filter" follows every buffered
+the index's bytes, and recall@k for refine 0 and --refine.  With --storage pq (--pq-m M) the line of the pq index follows in the
+same way: the codebooks trained once per nlist (pq_train_ms) and the catalogue encoded (pq_encode_ms), the stages with the lookup
+tables ("lut") and the table-lookup scan apart, the scan's lookups per second instead of FLOP/s.  With --scan filter a line "scan": "filter" follows every buffered
 line (under --score-bytes and under every --filter-score-bytes): the stages seed scan / seed merge / filter / merge_list /
 re-search, issued and useful TF/s of the seed scan and of the filter, the peak score + candidate bytes of a chunk, the candidates
 appended per query, the re-searched share, and whether (D, I) equal the buffered search's bit for bit.  Rows are Gaussian mixtures (n / 64 centres, noise 0.5) so that lists mean something.
@@ -48,9 +51,13 @@ def staged_search(idx, queries, k, nprobe, knn, ops, score_bytes, refine=0, base
     ms = {"coarse": 0.0, "tables": 0.0, "scan": 0.0, "merge": 0.0}
     dev = idx.device
     cap = ops.knn_list_capacity()
-    f16 = idx.storage == "f16"
+    f16, pq = idx.storage == "f16", idx.storage == "pq"
+    tile = {}
     if f16:
         ms["round"] = 0.0
+    if pq:
+        ms["lut"] = 0.0
+        tile["tile_slots"], tile["tile_rows"] = ops.ivf_pq_tile(idx.pq_m)
     if refine:
         ms["refine"] = 0.0
 
@@ -70,13 +77,15 @@ def staged_search(idx, queries, k, nprobe, knn, ops, score_bytes, refine=0, base
         ld = (idx.list_len + 3) // 4 * 4
         p = probe.to(torch.int64)
         costs = torch.where(p >= 0, ld[p.clamp(min=0)], torch.zeros_like(p)).sum(1).cpu().numpy()
+        if pq:
+            costs = costs + knn.pq_query_floats(idx.pq_m)
         return knn.ivf_plan_chunks(costs, score_bytes, max_queries=(2 ** 31 - 1) // nprobe)
     t, chunks = timed(plan)
     ms["tables"] += t
     tiles = useful = floats = 0
     for q0, q1 in chunks:
         pc = probe[q0:q1].contiguous()
-        t, tb = timed(lambda: knn.ivf_tables(pc, idx.list_len))
+        t, tb = timed(lambda: knn.ivf_tables(pc, idx.list_len, **tile))
         ms["tables"] += t
         if tb["n_slots"] == 0:
             best_d[q0:q1], best_i[q0:q1] = float("inf"), 0x7fffffff
@@ -89,7 +98,15 @@ def staged_search(idx, queries, k, nprobe, knn, ops, score_bytes, refine=0, base
                 return Qh
             t, Qh = timed(rounded)
             ms["round"] += t
-        if tb["n_tiles"]:
+        if pq and tb["n_tiles"]:
+            lut = torch.empty((q1 - q0, idx.pq_m, 256), dtype=torch.float32, device=dev)
+            t, _ = timed(lambda: ops.pq_lut(Q[q0:q1], idx.codebooks, lut))
+            ms["lut"] += t
+            t, _ = timed(lambda: ops.ivf_scan_pq(lut, tb["slot_query"], tb["slot_start"], tb["slot_off"], idx.codes, idx.list_start,
+                                                 tb["tiles"], scores))
+            ms["scan"] += t
+            del lut
+        elif tb["n_tiles"]:
             if f16:
                 t, _ = timed(lambda: ops.ivf_scan_f16(Qh, tb["slot_query"], tb["slot_start"], tb["slot_off"], idx.rows,
                                                       idx.list_start, tb["tiles"], scores))
@@ -112,6 +129,9 @@ def staged_search(idx, queries, k, nprobe, knn, ops, score_bytes, refine=0, base
     Dp = Q.shape[1]
     stats = {"chunks": len(chunks), "tiles": tiles, "score_bytes": 4 * floats,
              "scan_flop_tiles": 2.0 * tiles * knn.IVF_TILE * knn.IVF_TILE * Dp, "scan_flop_useful": 2.0 * useful * Dp, "probe": probe}
+    if pq:                                                    # lookups (one LDS gather + one add each) in place of FLOP
+        stats.update(scan_lookups_tiles=float(tiles) * tile["tile_slots"] * tile["tile_rows"] * idx.pq_m,
+                     scan_lookups_useful=float(useful) * idx.pq_m)
     return ms, best_d[:, :k], I, stats
 
 
@@ -240,8 +260,9 @@ def main():
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--sample", type=int, default=65536, help="queries of the recall sample when n is above it (--big)")
     ap.add_argument("--score-bytes", type=int, default=None)
-    ap.add_argument("--storage", nargs="*", default=["f32"], choices=["f32", "f16"], help="list formats to time, over one (centroids, assign)")
-    ap.add_argument("--refine", type=int, default=0, help="re-rank depth r of the f16 index (k <= r <= 128); 0 = none")
+    ap.add_argument("--storage", nargs="*", default=["f32"], choices=["f32", "f16", "pq"], help="list formats to time, over one (centroids, assign)")
+    ap.add_argument("--pq-m", type=int, default=32, help="bytes per listed row of the pq index")
+    ap.add_argument("--refine", type=int, default=0, help="re-rank depth r of the f16 / pq index (k <= r <= 128); 0 = none")
     ap.add_argument("--scan", nargs="*", default=["buffer"], choices=["buffer", "filter"],
                     help="search modes to time over the same index; \"filter\" is compared with the buffered search of the same call")
     ap.add_argument("--filter-score-bytes", type=int, nargs="*", default=[], help="further budgets for the filter runs (e.g. 1073741824)")
@@ -278,6 +299,16 @@ def main():
         for storage in a.storage:
             if storage == "f32":
                 indexes.append((idx, None))
+            elif storage == "pq":                                                                         # the same (centroids, assign), pq codes
+                Xp = idx.prepare(x)
+                knn.pq_train(Xp[:4096], a.pq_m, iters=1)                                                  # warm
+                train_ms, (cb, _) = timed(lambda: knn.pq_train(Xp, a.pq_m))
+                codes = torch.empty((n, a.pq_m), dtype=torch.uint8, device=dev)
+                encode_ms, _ = timed(lambda: ops.pq_encode(Xp, cb, codes))
+                del codes
+                h = knn.IVFIndex.load_state_dict(dict(idx.state_dict(), codebooks=cb), x, device=dev, storage="pq")
+                h.bench = {"pq_m": a.pq_m, "pq_train_ms": round(train_ms, 2), "pq_encode_ms": round(encode_ms, 3)}
+                indexes.append((h, Xp if a.refine else None))
             else:                                                                                         # the same (centroids, assign), fp16 lists
                 h = knn.IVFIndex.load_state_dict(idx.state_dict(), x, device=dev, storage="f16")
                 indexes.append((h, h.prepare(x) if a.refine else None))
@@ -306,15 +337,21 @@ def run_one(idx, base, refine, nprobe, nlist, x, k, n, a, knn, ops, sample, Ie, 
     recall = hit / max(found, 1)
     del I, Is
     total = sum(ms.values())
-    index_bytes = sum(t.numel() * t.element_size() for t in (idx.rows, idx.r_sq, idx.ids, idx.list_start, idx._C))
+    lists = (idx.codes, idx.codebooks) if idx.storage == "pq" else (idx.rows,)
+    index_bytes = sum(t.numel() * t.element_size() for t in lists + (idx.r_sq, idx.ids, idx.list_start, idx._C))
+    extra = dict(getattr(idx, "bench", {}))
+    if idx.storage == "pq":
+        extra.update(scan_glookups_tiles=round(st["scan_lookups_tiles"] / max(ms["scan"], 1e-9) / 1e6, 2),
+                     scan_glookups_useful=round(st["scan_lookups_useful"] / max(ms["scan"], 1e-9) / 1e6, 2),
+                     list_bytes=idx.codes.numel())
     print(json.dumps({
-        "what": "ivf", "storage": idx.storage, "refine": refine, "index_bytes": index_bytes,
+        **extra, "what": "ivf", "storage": idx.storage, "refine": refine, "index_bytes": index_bytes,
         "n": n, "nq": n, "recall_queries": Ie.shape[0], "dim": a.dim, "k": k, "nlist": nlist, "nprobe": nprobe, "iters": a.iters,
         "build_ms": round(build_ms, 2), "assign_all_rows_ms": round(assign_ms, 3), "centroid_update_ms": round(update_ms, 3),
         "search_ms": round(total, 3), "stages_ms": {s: round(v, 3) for s, v in ms.items()},
         "exact_ms": round(exact_ms, 3), "exact_nq": xq.shape[0], "speedup": round(exact_ms / total, 2) if sample is None else None,
-        "scan_tflops_tiles": round(st["scan_flop_tiles"] / max(ms["scan"], 1e-9) / 1e9, 2),
-        "scan_tflops_useful": round(st["scan_flop_useful"] / max(ms["scan"], 1e-9) / 1e9, 2),
+        "scan_tflops_tiles": None if idx.storage == "pq" else round(st["scan_flop_tiles"] / max(ms["scan"], 1e-9) / 1e9, 2),
+        "scan_tflops_useful": None if idx.storage == "pq" else round(st["scan_flop_useful"] / max(ms["scan"], 1e-9) / 1e9, 2),
         "score_bytes": st["score_bytes"], "score_budget": score_bytes, "chunks": st["chunks"], "recall": round(recall, 4),
         "list_max_over_mean": round(float(lens.max() / lens.mean()), 2), "empty_lists": int((lens == 0).sum()),
         "scanned_share": round(idx.scanned_share(st["probe"]), 5), "nprobe_over_nlist": round(nprobe / nlist, 5)}), flush=True)
