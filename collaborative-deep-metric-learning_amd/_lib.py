@@ -320,6 +320,14 @@ SIGNATURES_IVF_PQ = {
     "cdml_ivf_scan_pq": (_i, [_p, _i, _p, _p, _p, _p, _i64, _p, _i, _p, _i, _p, _p]),
 }
 
+# name -> (restype, argtypes); must list every symbol include/cdml_ivf_pqr.h declares (residual product quantisation: the fused
+# residual encoder, the slot scalars <query, centroid> and the table-lookup scan that starts from them)
+SIGNATURES_IVF_PQR = {
+    "cdml_pqr_encode": (_i, [_p, _i64, _i64, _p, _i64, _i, _p, _p, _i, _i, _p, _i64, _p, _i64, _p]),
+    "cdml_ivf_slot_dots": (_i, [_p, _i64, _i, _p, _i64, _i, _p, _p, _i, _p, _p]),
+    "cdml_ivf_scan_pqr": (_i, [_p, _i, _p, _p, _p, _p, _p, _i64, _p, _i, _p, _i, _p, _p]),
+}
+
 _lib = None
 
 
@@ -342,7 +350,8 @@ def load_library():
                                + list(SIGNATURES_BF16.items()) + list(SIGNATURES_HARDNEG.items()) + list(SIGNATURES_WIDE.items())
                                + list(SIGNATURES_NEGW.items()) + list(SIGNATURES_F8.items()) + list(SIGNATURES_IVF.items())
                                + list(SIGNATURES_IVF_F16.items()) + list(SIGNATURES_IVF_FILTER.items())
-                               + list(SIGNATURES_KNN_WRITER.items()) + list(SIGNATURES_IVF_PQ.items())):
+                               + list(SIGNATURES_KNN_WRITER.items()) + list(SIGNATURES_IVF_PQ.items())
+                               + list(SIGNATURES_IVF_PQR.items())):
         fn = getattr(lib, name)          # AttributeError if the ABI lost a symbol
         fn.restype = res
         fn.argtypes = args

@@ -263,11 +263,19 @@ def _check_pq_m(storage, pq_m, Dp=None, what="pq_m"):
     return m
 
 
-def _check_ivf_options(storage, refine, scan, ks=(), pq_m=None):
+def _check_pq_residual(storage, pq_residual):
+    """``pq_residual`` of an index with ``storage``: the refusal, by name"""
+    if pq_residual and storage != "pq":
+        raise ValueError("pq_residual belongs to storage=\"pq\" (got storage=%r)" % (storage,))
+    return bool(pq_residual)
+
+
+def _check_ivf_options(storage, refine, scan, ks=(), pq_m=None, pq_residual=False):
     """The refusals of the IVF options the export's call sites share, by name, before any device work.  ``ks``: the list
     lengths the searches will ask for (a re-rank must keep at least that many)."""
     if storage not in IVF_STORAGES:
         raise ValueError("storage must be one of %s, got %r" % (IVF_STORAGES, storage))
+    _check_pq_residual(storage, pq_residual)
     if scan not in IVF_SCANS:
         raise ValueError("scan must be one of %s, got %r" % (IVF_SCANS, scan))
     _check_pq_m(storage, pq_m)
@@ -301,16 +309,16 @@ def _check_ivf_lists(what, nlist, nprobe, n_rows):
 
 
 def ivf_knn(base, queries=None, k=51, nlist=1024, nprobe=16, l2_norm=True, storage="f32", refine=0, scan="buffer", iters=10,
-            seed=0, device="cuda:0", precision="f32x3", index=None, stats=None, pq_m=None):
+            seed=0, device="cuda:0", precision="f32x3", index=None, stats=None, pq_m=None, pq_residual=False):
     """Device (D, I) of ``IVFIndex.search``, shaped and typed like ``knn_search``'s: the index of ``base`` (built here with
     ``nlist`` lists, ``iters`` Lloyd iterations and ``seed``, or taken as ``index=``), every query's ``nprobe`` nearest lists
     scanned exactly.  ``queries=None`` is the self-search.  ``refine>0`` (storage "f16" or "pq"; "pq" takes ``pq_m``, the
-    bytes per listed row) re-ranks the ``refine`` best against the fp32 rows ``index.prepare(base)``.  The one place the export's approximate searches go through; its launches are
+    bytes per listed row, and ``pq_residual``: codes of the row minus its list's centroid) re-ranks the ``refine`` best against the fp32 rows ``index.prepare(base)``.  The one place the export's approximate searches go through; its launches are
     those of DESIGN.md sections 9f-9f.3.  ``stats`` (a dict, optional) receives ``IVFIndex.search``'s."""
     if index is None:
-        _check_ivf_options(storage, refine, scan, (int(k),), pq_m)
+        _check_ivf_options(storage, refine, scan, (int(k),), pq_m, pq_residual)
         index = IVFIndex.build(base, int(nlist), iters=iters, seed=seed, l2_norm=l2_norm, device=device, precision=precision,
-                               storage=storage, pq_m=pq_m)
+                               storage=storage, pq_m=pq_m, pq_residual=pq_residual)
     q = base if queries is None else queries
     kw = {"refine": int(refine), "base": index.prepare(base)} if int(refine) > 0 else {}
     return index.search(q, int(k), int(nprobe), stats=stats, scan=scan, **kw)
@@ -336,20 +344,20 @@ def _check_cross_lists(nlist, nprobe, doc_location, n):
 
 
 def cross_knn(embeddings, doc_location, nearest_num=81, precision="f32x3", device="cuda:0", nlist=0, nprobe=0, storage="f32",
-              refine=0, scan="buffer", ivf_iters=10, ivf_seed=0, stats=None, pq_m=None):
+              refine=0, scan="buffer", ivf_iters=10, ivf_seed=0, stats=None, pq_m=None, pq_residual=False):
     """(crossD, crossI) as faiss_knn.py:325-336 builds them: rows [0, doc_location) (videos) search the documents, their
     ids offset by ``doc_location`` into global ids; rows [doc_location, n) (documents) search the videos.  Rows are in
     global order, so the query of row r is r.  The exact search (``knn_search``) stands for the reference's HNSW.  A -1
     ("no neighbour": a side with fewer than nearest_num rows) stays -1 instead of taking the offset.  Returns the kind
     of ``embeddings``.
     ``nlist > 0``: either side is searched through an ``IVFIndex`` of its own (``ivf_knn``) with ``cross_nlist(nlist, n_side,
-    n)`` lists, of which min(nprobe, that many) are probed; ``storage``, ``pq_m``, ``refine``, ``scan``, ``ivf_iters`` and ``ivf_seed`` go
+    n)`` lists, of which min(nprobe, that many) are probed; ``storage``, ``pq_m``, ``pq_residual``, ``refine``, ``scan``, ``ivf_iters`` and ``ivf_seed`` go
     to both.  ``stats`` (a dict, optional) receives the two searches' under "video_to_doc" and "doc_to_video"."""
     t = embeddings if torch.is_tensor(embeddings) else torch.from_numpy(np.asarray(embeddings, dtype=np.float32))
     if int(nlist) or int(nprobe):
         n = t.shape[0]
         nlist, nprobe = _check_cross_lists(nlist, nprobe, int(doc_location), n)
-        _check_ivf_options(storage, refine, scan, (int(nearest_num),), pq_m)
+        _check_ivf_options(storage, refine, scan, (int(nearest_num),), pq_m, pq_residual)
         video, doc = t[:doc_location], t[doc_location:]
         out = []
         for name, base, q in (("video_to_doc", doc, video), ("doc_to_video", video, doc)):
@@ -357,14 +365,14 @@ def cross_knn(embeddings, doc_location, nearest_num=81, precision="f32x3", devic
             st = None if stats is None else stats.setdefault(name, {})
             out.append(ivf_knn(base, q, int(nearest_num), nlist=nl, nprobe=min(nprobe, nl), storage=storage, refine=refine,
                                scan=scan, iters=ivf_iters, seed=ivf_seed, device=device, precision=precision, stats=st,
-                               pq_m=pq_m))
+                               pq_m=pq_m, pq_residual=pq_residual))
         (vdD, vdI), (dvD, dvI) = out
         vdI = torch.where(vdI >= 0, vdI + doc_location, vdI)
         D, I = torch.cat([vdD, dvD]), torch.cat([vdI, dvI])
         if torch.is_tensor(embeddings):
             return D, I
         return D.cpu().numpy(), I.cpu().numpy()
-    _check_ivf_options(storage, refine, scan, pq_m=pq_m)
+    _check_ivf_options(storage, refine, scan, pq_m=pq_m, pq_residual=pq_residual)
     if storage != "f32" or int(refine) or scan != "buffer":
         raise ValueError("storage, refine and scan belong to nlist > 0 (this search is exact)")
     video, doc = t[:doc_location], t[doc_location:]
@@ -602,7 +610,8 @@ def _scalars(st):
 def export(embeddings, features, decode_map, out_dir, doc_location=343455, nearest_num=81, desim_nearest_num=26,
            fD_threshold=DESIM_THRESHOLD, fI_end=DESIM_FI_END, precision="f32x3", device="cuda:0", split_num=10,
            nlist=0, nprobe=0, feature_nlist=0, feature_nprobe=0, storage="f32", refine=0, scan="buffer", ivf_iters=10,
-           ivf_seed=0, feature_knn=None, writer="host", audit_rows=0, audit_seed=0, stats=None, pq_m=None, feature_pq_m=None):
+           ivf_seed=0, feature_knn=None, writer="host", audit_rows=0, audit_seed=0, stats=None, pq_m=None, feature_pq_m=None,
+           pq_residual=False):
     """faiss_knn.main (faiss_knn.py:359-400) with explicit arguments: the raw-feature kNN (fD, fI; k = min(desim_nearest_num,
     nearest_num)), then -- cross mode when 0 < doc_location < n, strict mode otherwise -- the embedding kNN, desim and the
     text lists.  Writes fD.npy, fI.npy, {strict,cross}D.npy, {strict,cross}I.npy, {strict,cross}I_desim.npy, the
@@ -614,7 +623,7 @@ def export(embeddings, features, decode_map, out_dir, doc_location=343455, neare
     ``nlist`` / ``nprobe``: the embedding search through ``ivf_knn`` (strict) or ``cross_knn(nlist=...)`` (cross: an index per
     side).  ``feature_nlist`` / ``feature_nprobe``: the raw-feature search through ``ivf_knn``, independently.  ``storage``,
     ``refine``, ``scan``, ``ivf_iters``, ``ivf_seed`` go to every index; with ``storage="pq"`` the embedding indexes take ``pq_m``
-    and the raw-feature index ``feature_pq_m`` (default: ``pq_m``).  ``feature_knn``: (fD, fI) or a directory holding
+    and the raw-feature index ``feature_pq_m`` (default: ``pq_m``), and ``pq_residual`` goes to every pq index.  ``feature_knn``: (fD, fI) or a directory holding
     fD.npy / fI.npy of an earlier export -- raw features do not change when the model is retrained -- written as given, no
     feature search (``features`` may then be None unless the audit needs them).  ``writer``: "host" | "device"
     (``write_knn``).  ``audit_rows = m > 0``: the recall statement -- for the rows ``audit_sample(n, m, audit_seed)`` the
@@ -632,7 +641,8 @@ def export(embeddings, features, decode_map, out_dir, doc_location=343455, neare
         raise ValueError("writer must be one of %s, got %r" % (WRITERS, writer))
     nlist, nprobe = _check_cross_lists(nlist, nprobe, int(doc_location), n) if cross else _check_ivf_lists("", nlist, nprobe, n)
     feature_nlist, feature_nprobe = _check_ivf_lists("feature_", feature_nlist, feature_nprobe, n)
-    refine = _check_ivf_options(storage, refine, scan, ((k,) if nlist else ()) + ((k_f,) if feature_nlist else ()), pq_m)
+    refine = _check_ivf_options(storage, refine, scan, ((k,) if nlist else ()) + ((k_f,) if feature_nlist else ()), pq_m,
+                                pq_residual)
     feature_pq_m = _check_pq_m(storage, pq_m if feature_pq_m is None else feature_pq_m, what="feature_pq_m")
     if not (nlist or feature_nlist) and (storage != "f32" or refine or scan != "buffer"):
         raise ValueError("storage, refine and scan belong to an IVF search: set nlist or feature_nlist (both are 0)")
@@ -649,6 +659,7 @@ def export(embeddings, features, decode_map, out_dir, doc_location=343455, neare
         raise ValueError("the audit runs the exact raw-feature search: it needs features")
     ivf = {"storage": storage, "refine": refine, "scan": scan}
     pq = {"pq_m": int(pq_m), "feature_pq_m": feature_pq_m} if storage == "pq" else {}
+    pqr = {"pq_residual": True} if pq_residual else {}        # (absent when off: the stats of a plain export keep their keys)
 
     def stage(name, t0, extra=None):
         if stats is not None:
@@ -664,7 +675,7 @@ def export(embeddings, features, decode_map, out_dir, doc_location=343455, neare
     elif feature_nlist:
         st = {}
         fD, fI = ivf_knn(features, None, k_f, nlist=feature_nlist, nprobe=feature_nprobe, iters=ivf_iters, seed=ivf_seed,
-                         device=device, precision=precision, stats=st, pq_m=pq.get("feature_pq_m"), **ivf)
+                         device=device, precision=precision, stats=st, pq_m=pq.get("feature_pq_m"), **ivf, **pqr)
         t0 = stage("feature_knn", t0, {"ivf": _scalars(st)})
     else:
         fD, fI = knn_search(features, features, k_f, device=device, precision=precision)
@@ -679,14 +690,14 @@ def export(embeddings, features, decode_map, out_dir, doc_location=343455, neare
         if nlist:
             D, I = cross_knn(emb.to(device), doc_location, nearest_num=nearest_num, precision=precision, device=device,
                              nlist=nlist, nprobe=nprobe, ivf_iters=ivf_iters, ivf_seed=ivf_seed, stats=st, pq_m=pq.get("pq_m"),
-                             **ivf)
+                             **ivf, **pqr)
         else:
             D, I = cross_knn(emb.to(device), doc_location, nearest_num=nearest_num, precision=precision, device=device)
     else:
         mode = "strict"
         if nlist:
             D, I = ivf_knn(emb, None, k, nlist=nlist, nprobe=nprobe, iters=ivf_iters, seed=ivf_seed, device=device,
-                           precision=precision, stats=st, pq_m=pq.get("pq_m"), **ivf)
+                           precision=precision, stats=st, pq_m=pq.get("pq_m"), **ivf, **pqr)
         else:
             D, I = knn_search(emb, emb, int(nearest_num), device=device, precision=precision)
     t0 = stage("embedding_knn", t0, {"ivf": _scalars(st)} if nlist else None)
@@ -715,7 +726,7 @@ def export(embeddings, features, decode_map, out_dir, doc_location=343455, neare
         report = dict(counts, mode=mode, n=n, doc_location=int(doc_location), nearest_num=k, desim_nearest_num=k_f,
                       fD_threshold=float(fD_threshold), fI_end=int(fI_end), precision=precision, nlist=nlist, nprobe=nprobe,
                       feature_nlist=feature_nlist, feature_nprobe=feature_nprobe, ivf_iters=int(ivf_iters), ivf_seed=int(ivf_seed),
-                      feature_knn_given=feature_knn is not None, audit_seed=int(audit_seed), **ivf, **pq)
+                      feature_knn_given=feature_knn is not None, audit_seed=int(audit_seed), **ivf, **pq, **pqr)
         with open(os.path.join(out_dir, "export_audit.json"), "w") as f:
             json.dump(report, f, indent=1, sort_keys=True)
         stage("audit", t0)
@@ -795,9 +806,10 @@ def ivf_tables(probe, list_len, tile_slots=IVF_TILE, tile_rows=IVF_TILE):
             "slot_off": slot_off, "slot_of": slot_of.view(m, nprobe), "tiles": tiles}
 
 
-def pq_query_floats(pq_m):
-    """256 M: the floats of one query's lookup table, what a query of a pq index costs a chunk beside its scores"""
-    return PQ_CODEWORDS * int(pq_m)
+def pq_query_floats(pq_m, nprobe=0):
+    """256 M: the floats of one query's lookup table, what a query of a pq index costs a chunk beside its scores; a residual
+    index (``pq_residual``) adds its ``nprobe`` slot scalars"""
+    return PQ_CODEWORDS * int(pq_m) + int(nprobe)
 
 
 PQ_TRAIN_ROWS = 65536       # default training rows of pq_train (256 per codeword)
@@ -816,15 +828,20 @@ def _check_pq_train(n_finite, iters, train_rows):
     return n_train, iters
 
 
-def pq_train(X_prepared, pq_m, iters=10, seed=0, train_rows=None):
+def pq_train(X_prepared, pq_m, iters=10, seed=0, train_rows=None, centroids=None, assign=None):
     """(codebooks fp32 [M, 256, Dp / M] on X's device, pq_objective float64 [M, iters] on the CPU): the deterministic Lloyd's of
     ``IVFIndex.build`` per subspace (include/cdml_ivf_pq.h).  ``X_prepared``: the fp32 device matrix [n, Dp] of
     ``IVFIndex.prepare``.  The training rows are the (sorted) first ``train_rows`` ids of the seeded CPU permutation of the
     finite rows (default min(n_finite, 65 536)); every subspace's 256 initial codewords are the sub-vectors of the sorted
     first 256 ids.  An iteration encodes the training rows (``ops.pq_encode``) and replaces every non-empty codeword by the
     mean of its rows (``ops.ivf_centroid_sums``, rows ordered by (code, id)); an empty codeword keeps its value.
-    pq_objective[m, t] = the sum of iteration t's attained distances in subspace m."""
+    pq_objective[m, t] = the sum of iteration t's attained distances in subspace m.
+    ``centroids`` (fp32 [nlist, Dp], the padded matrix) and ``assign`` (int64 [n]) together: the same Lloyd's on the
+    RESIDUALS x - centroids[assign] of the same rows (include/cdml_ivf_pqr.h; one fp32 subtract per column, materialised
+    for the training rows only); every finite row then needs an assign in [0, nlist)."""
     X = X_prepared
+    if (centroids is None) != (assign is None):
+        raise ValueError("pq_train takes centroids and assign together (residual codebooks) or neither (plain codebooks)")
     if not torch.is_tensor(X) or X.dtype != torch.float32 or X.dim() != 2 or X.stride(1) != 1:
         raise ValueError("pq_train takes the prepared fp32 [n, Dp] matrix (IVFIndex.prepare)")
     n, Dp = X.shape
@@ -840,7 +857,19 @@ def pq_train(X_prepared, pq_m, iters=10, seed=0, train_rows=None):
     init_rows = torch.sort(fin[perm[:PQ_CODEWORDS]]).values
     train_ids = torch.sort(fin[perm[:n_train]]).values
     Xt = X if n_train == n else X.index_select(0, train_ids.to(dev))
-    cb = X.index_select(0, init_rows.to(dev)).view(PQ_CODEWORDS, M, dsub).permute(1, 0, 2).contiguous()
+    X0 = X.index_select(0, init_rows.to(dev))
+    if centroids is not None:
+        Cp, a = centroids, assign
+        if not torch.is_tensor(Cp) or Cp.dtype != torch.float32 or Cp.dim() != 2 or Cp.shape[1] != Dp \
+                or not torch.is_tensor(a) or a.dtype != torch.int64 or tuple(a.shape) != (n,):
+            raise ValueError("pq_train takes centroids fp32 [nlist, Dp = %d] and assign int64 [n = %d]" % (Dp, n))
+        Cp, a = Cp.to(dev), a.to(dev)
+        a_fin = a.index_select(0, fin.to(dev))
+        if int(a_fin.min()) < 0 or int(a_fin.max()) >= Cp.shape[0]:
+            raise ValueError("pq_train: every finite row needs an assign in [0, nlist = %d)" % Cp.shape[0])
+        Xt = X.index_select(0, train_ids.to(dev)) - Cp.index_select(0, a.index_select(0, train_ids.to(dev)))
+        X0 = X0 - Cp.index_select(0, a.index_select(0, init_rows.to(dev)))
+    cb = X0.view(PQ_CODEWORDS, M, dsub).permute(1, 0, 2).contiguous()
     codes = torch.empty((n_train, M), dtype=torch.uint8, device=dev)
     dist = torch.empty((n_train, M), dtype=torch.float32, device=dev)
     objective = torch.zeros((M, iters), dtype=torch.float64)
@@ -874,6 +903,8 @@ class IVFIndex:
     pq_m] stands where ``rows`` stood (there is no ``rows``), ``codebooks`` fp32 [pq_m, 256, Dp / pq_m] (``pq_train``, or given),
     ``pq_objective`` float64 [pq_m, pq_iters] (CPU), ``r_sq`` the norms of the decoded rows, ``decode(positions)`` the decoded
     rows.  ``search`` scans by table lookup (one lookup table per query); ``refine=r`` re-ranks as for "f16".
+    ``pq_residual=True`` (include/cdml_ivf_pqr.h): the codes describe the row minus its list's
+    centroid, a decoded row is centroid + codewords, and a score starts from the slot's <query, centroid>.
 
     ``search(..., scan="filter")`` (include/cdml_ivf_filter.h) is the same search, bit for bit, with a
     score buffer for the first ``seed_probes`` probe columns only: the other columns append what is within the seeded
@@ -925,8 +956,9 @@ class IVFIndex:
         return out
 
     @classmethod
-    def _blank(cls, nlist, D, l2_norm, device, precision, storage="f32", pq_m=None):
+    def _blank(cls, nlist, D, l2_norm, device, precision, storage="f32", pq_m=None, pq_residual=False):
         self = object.__new__(cls)
+        self.pq_residual = _check_pq_residual(storage, pq_residual)
         self.nlist, self.dim, self.l2_norm, self.device, self.precision = int(nlist), int(D), bool(l2_norm), torch.device(device), precision
         self.storage = cls._check_storage(storage)
         if storage == "pq":
@@ -955,9 +987,13 @@ class IVFIndex:
         self.ids = order[:n_listed].to(torch.int32)
         self.list_start = start.to(torch.int32)
         self.list_len = cnt[:self.nlist].contiguous()
+        self._C = C
         if self.storage == "pq":
             codes = torch.empty((n, self.pq_m), dtype=torch.uint8, device=X.device)
-            ops.pq_encode(X, self.codebooks, codes)           # (an unlisted row's codes are computed and dropped)
+            if self.pq_residual:
+                ops.pqr_encode(X, C, a, self.codebooks, codes)
+            else:
+                ops.pq_encode(X, self.codebooks, codes)       # (an unlisted row's codes are computed and dropped)
             self.codes = codes.index_select(0, order[:n_listed])
             self.r_sq = torch.zeros(n_listed, dtype=torch.float32, device=X.device)
             for r0 in range(0, n_listed, self._NORM_ROWS):
@@ -970,19 +1006,23 @@ class IVFIndex:
             self.rows = X.index_select(0, order[:n_listed])
             self.r_sq = torch.zeros(n_listed, dtype=torch.float32, device=X.device)
             ops.row_sqnorm(self.rows, Dp, self.r_sq)
-        self._C = C
         self.centroids = C[:, :self.dim]
         self.n_rows, self.n_listed, self.n_unlisted = n, n_listed, n - n_listed
         return self
 
     def decode(self, positions):
-        """fp32 [len, Dp]: the decoded rows (the concatenated codewords) at ``positions`` of the cluster-major lists
-        (plumbing: a torch gather).  storage "pq" only."""
+        """fp32 [len, Dp]: the decoded rows (the concatenated codewords; with ``pq_residual`` the list's centroid + them, one
+        fp32 add) at ``positions`` of the cluster-major lists (plumbing: a torch gather).  storage "pq" only."""
         if self.storage != "pq":
             raise ValueError("decode belongs to an index with storage=\"pq\" (this one is %r)" % self.storage)
-        c = self.codes.index_select(0, positions.to(device=self.device, dtype=torch.int64)).to(torch.int64)
+        pos = positions.to(device=self.device, dtype=torch.int64)
+        c = self.codes.index_select(0, pos).to(torch.int64)
         m = torch.arange(self.pq_m, device=self.device)
-        return self.codebooks[m[None, :], c].reshape(c.shape[0], -1)
+        out = self.codebooks[m[None, :], c].reshape(c.shape[0], -1)
+        if self.pq_residual:                              # the list of a position: the last c with list_start[c] <= position
+            lst = torch.searchsorted(self.list_start[1:].to(torch.int64), pos, right=True)
+            out = self._C.index_select(0, lst) + out
+        return out
 
     @staticmethod
     def _check_codebooks(codebooks, Dp):
@@ -995,11 +1035,12 @@ class IVFIndex:
 
     @classmethod
     def from_assignment(cls, base, centroids, assign, l2_norm=True, device="cuda:0", precision="f32x3", storage="f32",
-                        codebooks=None):
+                        codebooks=None, pq_residual=False):
         """The index of given ``centroids`` ([nlist, D]) and an arbitrary ``assign`` (int [n], values in [-1, nlist); -1 =
         unlisted): the search contract does not need the assignment to be the nearest centroid.  ``storage="pq"`` takes
-        ``codebooks`` (fp32 [M, 256, Dp / M]) as they are."""
+        ``codebooks`` (fp32 [M, 256, Dp / M]) as they are; with ``pq_residual=True`` they are codebooks of residuals."""
         cls._check_storage(storage)
+        _check_pq_residual(storage, pq_residual)
         t = cls._as_tensor(base)
         pq_m = None
         if storage == "pq":
@@ -1017,7 +1058,7 @@ class IVFIndex:
         nlist = c.shape[0]
         if a.numel() and (int(a.min()) < -1 or int(a.max()) >= nlist):
             raise ValueError("assign must lie in [-1, nlist = %d)" % nlist)
-        self = cls._blank(nlist, t.shape[1], l2_norm, device, precision, storage, pq_m)
+        self = cls._blank(nlist, t.shape[1], l2_norm, device, precision, storage, pq_m, pq_residual)
         if storage == "pq":
             self.codebooks = codebooks.detach().to(self.device).contiguous().clone()
         X = cls._prepared(t, self.device, l2_norm)
@@ -1025,13 +1066,15 @@ class IVFIndex:
 
     @classmethod
     def build(cls, base, nlist, iters=10, seed=0, train_rows=None, l2_norm=True, device="cuda:0", precision="f32x3",
-              storage="f32", pq_m=None, pq_iters=None, pq_seed=None, pq_train_rows=None):
+              storage="f32", pq_m=None, pq_iters=None, pq_seed=None, pq_train_rows=None, pq_residual=False):
         """Lloyd's k-means, deterministic (include/cdml_ivf.h BUILD).  ``precision`` is that of the coarse ``knn_search`` calls
         (every assignment step, and ``probes``).  ``storage`` ("f32" | "f16" | "pq") is the format of the lists alone: k-means
         runs on the fp32 rows either way, so (base, seed) gives the same ``assign`` and the same probes for all three.
         ``storage="pq"``: ``pq_m`` bytes per row; the codebooks come from ``pq_train(X, pq_m, pq_iters (default 10), pq_seed
-        (default ``seed``), pq_train_rows)`` on the prepared rows."""
+        (default ``seed``), pq_train_rows)`` on the prepared rows; with ``pq_residual=True`` on their residuals against the
+        final centroids and assignment."""
         cls._check_storage(storage)
+        _check_pq_residual(storage, pq_residual)
         t = cls._as_tensor(base)
         pq_m = _check_pq_m(storage, pq_m, _round_up(t.shape[1], 32))
         if storage != "pq" and (pq_iters is not None or pq_seed is not None or pq_train_rows is not None):
@@ -1047,7 +1090,7 @@ class IVFIndex:
             raise ValueError("train_rows must be in [nlist = %d, the number of finite rows = %d], got %d" % (nlist, n_finite, n_train))
         if storage == "pq":
             _check_pq_train(n_finite, 10 if pq_iters is None else pq_iters, pq_train_rows)
-        self = cls._blank(nlist, t.shape[1], l2_norm, device, precision, storage, pq_m)
+        self = cls._blank(nlist, t.shape[1], l2_norm, device, precision, storage, pq_m, pq_residual)
         dev = self.device
         X = cls._prepared(t, dev, l2_norm)
         n, Dp = X.shape
@@ -1075,8 +1118,10 @@ class IVFIndex:
             ops.ivf_centroid_sums(Xt, order, start.to(torch.int32), C, Dp)
         _, Ia = knn_search(C, X, 1, l2_norm=False, device=dev, precision=precision)
         if storage == "pq":
+            res = {"centroids": C, "assign": Ia[:, 0].to(torch.int64)} if pq_residual else {}
             self.codebooks, self.pq_objective = pq_train(X, pq_m, iters=10 if pq_iters is None else pq_iters,
-                                                         seed=seed if pq_seed is None else pq_seed, train_rows=pq_train_rows)
+                                                         seed=seed if pq_seed is None else pq_seed, train_rows=pq_train_rows,
+                                                         **res)
         self._set_lists(X, C, Ia[:, 0])
         self.init_rows, self.train_ids = init_rows, train_ids
         self.objective = torch.stack(objective).cpu() if objective else torch.empty(0, dtype=torch.float64)
@@ -1092,6 +1137,8 @@ class IVFIndex:
         if self.storage == "pq":
             state["pq_m"] = self.pq_m
             state["codebooks"] = self.codebooks.detach().cpu().clone()
+            if self.pq_residual:
+                state["pq_residual"] = True
         return state
 
     @classmethod
@@ -1106,6 +1153,7 @@ class IVFIndex:
                 raise ValueError("this state holds no codebooks (it is not the state of a storage=\"pq\" index): it cannot be "
                                  "loaded as \"pq\"")
             kw["codebooks"] = state["codebooks"]
+            kw["pq_residual"] = bool(state.get("pq_residual", False))
         self = cls.from_assignment(base, state["centroids"], state["assign"], l2_norm=state["l2_norm"], device=device,
                                    precision=state["precision"], storage=storage, **kw)
         self.init_rows, self.objective = state["init_rows"].clone(), state["objective"].clone()
@@ -1223,7 +1271,7 @@ class IVFIndex:
         costs = torch.where(p >= 0, ld[p.clamp(min=0)], torch.zeros_like(p)).sum(1).cpu().numpy()
         tile = {}
         if pq:                                            # a chunk's scores AND lookup tables fit score_bytes together
-            costs = costs + pq_query_floats(self.pq_m)
+            costs = costs + pq_query_floats(self.pq_m, nprobe if self.pq_residual else 0)
             tile["tile_slots"], tile["tile_rows"] = ops.ivf_pq_tile(self.pq_m)
         chunks = ivf_plan_chunks(costs, score_bytes, max_queries=(2 ** 31 - 1) // nprobe)
         n_tiles = n_floats = 0
@@ -1250,8 +1298,14 @@ class IVFIndex:
                 if tb["n_tiles"]:
                     lut = torch.empty((q1 - q0, self.pq_m, PQ_CODEWORDS), dtype=torch.float32, device=Q.device)
                     ops.pq_lut(Q[q0:q1], self.codebooks, lut)
-                    ops.ivf_scan_pq(lut, tb["slot_query"], tb["slot_start"], tb["slot_off"], self.codes, self.list_start,
-                                    tb["tiles"], scores)
+                    if self.pq_residual:
+                        slot_base = torch.empty(tb["n_slots"], dtype=torch.float32, device=Q.device)
+                        ops.ivf_slot_dots(Q[q0:q1], self._C, tb["slot_query"], tb["slot_start"], slot_base)
+                        ops.ivf_scan_pqr(lut, tb["slot_query"], tb["slot_start"], tb["slot_off"], slot_base, self.codes,
+                                         self.list_start, tb["tiles"], scores)
+                    else:
+                        ops.ivf_scan_pq(lut, tb["slot_query"], tb["slot_start"], tb["slot_off"], self.codes, self.list_start,
+                                        tb["tiles"], scores)
             elif tb["n_tiles"]:
                 ops.ivf_scan_f32(Q[q0:q1], tb["slot_query"], tb["slot_start"], tb["slot_off"], self.rows, self.list_start,
                                  tb["tiles"], scores)

@@ -1823,6 +1823,62 @@ def ivf_scan_pq(lut, slot_query, slot_start, slot_off, codes, list_start, tiles,
     return scores
 
 
+# ---------------------------------------- residual product quantisation (include/cdml_ivf_pqr.h) ------
+def pqr_encode(x, centroids, assign, codebooks, codes, dist=None):
+    """``pq_encode`` of the residuals x[r] - centroids[assign[r]] (never materialised): centroids fp32 [nlist, >= M dsub],
+    assign int64 [n]; a row whose assign is outside [0, nlist) gets codes 0 (and dist +inf)."""
+    xp, xld = _mat(x)
+    ep, eld = _mat(centroids)
+    cp, M, dsub = _codebooks(codebooks)
+    n = x.shape[0]
+    if codes.dtype != torch.uint8 or codes.dim() != 2 or codes.stride(1) != 1 or codes.shape[0] < n or codes.shape[1] < M:
+        raise ValueError("codes must be a uint8 [n, >= M] tensor with unit inner stride")
+    if x.shape[1] < M * dsub or centroids.shape[1] < M * dsub:
+        raise ValueError("x rows and centroids must hold M dsub = %d columns, got %d and %d"
+                         % (M * dsub, x.shape[1], centroids.shape[1]))
+    dp, dld = (C.c_void_p(0), 0) if dist is None else _mat(dist)
+    if dist is not None and (dist.shape[0] < n or dist.shape[1] < M):
+        raise ValueError("dist must be a float32 [n, >= M] tensor")
+    call("cdml_pqr_encode", xp, xld, n, ep, eld, centroids.shape[0], _vec(assign, torch.int64, n, "assign"), cp, M, dsub,
+         _p(codes), codes.stride(0), dp, dld, _stream())
+    return codes
+
+
+def ivf_slot_dots(Q, centroids, slot_query, slot_start, slot_base):
+    """slot_base[s] (fp32 [n_slots]) = <Q[slot_query[s]], centroids[list of slot s]> over Q's (padded) width, in the fixed
+    order of include/cdml_ivf_pqr.h; slot_start int32 [nlist + 1] names every slot's list."""
+    qp, qld = _mat(Q)
+    ep, eld = _mat(centroids)
+    if Q.shape[1] != centroids.shape[1]:
+        raise ValueError("queries and centroids of one padded width")
+    nlist = centroids.shape[0]
+    n_slots = slot_query.numel()
+    call("cdml_ivf_slot_dots", qp, qld, Q.shape[0], ep, eld, Q.shape[1], _vec(slot_query, torch.int32, 0, "slot_query"),
+         _vec(slot_start, torch.int32, nlist + 1, "slot_start"), nlist, _vec(slot_base, torch.float32, n_slots, "slot_base"),
+         _stream())
+    return slot_base
+
+
+def ivf_scan_pqr(lut, slot_query, slot_start, slot_off, slot_base, codes, list_start, tiles, scores):
+    """``ivf_scan_pq`` with every slot's sums starting from ``slot_base[slot]`` (``ivf_slot_dots``): the scan of an index with
+    ``pq_residual=True``."""
+    if lut.dim() != 3 or lut.shape[2] != 256 or not lut.is_contiguous():
+        raise ValueError("lut must be a contiguous float32 [n_queries, M, 256] tensor")
+    M = lut.shape[1]
+    if codes.dtype != torch.uint8 or codes.dim() != 2 or codes.stride(1) != 1 or codes.shape[1] < M:
+        raise ValueError("codes must be a uint8 [n_listed, >= M] tensor with unit inner stride")
+    nlist = list_start.numel() - 1
+    n_slots = slot_query.numel()
+    if tiles.dim() != 2 or tiles.shape[1] != 4:
+        raise ValueError("tiles must be int32 [n_tiles, 4]")
+    call("cdml_ivf_scan_pqr", _p(lut, torch.float32), lut.shape[0], _vec(slot_query, torch.int32, 0, "slot_query"),
+         _vec(slot_start, torch.int32, nlist + 1, "slot_start"), _vec(slot_off, torch.int64, n_slots, "slot_off"),
+         _vec(slot_base, torch.float32, n_slots, "slot_base"), _p(codes), codes.stride(0),
+         _vec(list_start, torch.int32, nlist + 1, "list_start"), M, _vec(tiles, torch.int32, 4, "tiles"), tiles.shape[0],
+         _p(scores, torch.float32), _stream())
+    return scores
+
+
 # ---------------------------------------- threshold-filter scan of the IVF index (include/cdml_ivf_filter.h) ------
 def _ivf_filter(name, qp, qld, rp, rld, Q, slot_query, slot_start, q_sq, tau, cnt, rows, list_start, r_sq, ids, tiles, cand, cap):
     nlist = list_start.numel() - 1

@@ -6,6 +6,7 @@
     python tools/ivf_bench.py --n 50000 --nlist 64 --nprobe 4 8 --k 20
     python tools/ivf_bench.py --storage f32 f16 --refine 128   # fp16 lists beside the fp32 ones over the same (centroids, assign)
     python tools/ivf_bench.py --storage f16 pq --pq-m 32 --refine 128   # product-quantised lists (32 bytes a row) beside the fp16 ones
+    python tools/ivf_bench.py --storage pq --pq-m 16 32 --pq-residual 0 1 --refine 0 128   # residual codes beside the plain ones, per M
     python tools/ivf_bench.py --scan buffer filter             # the threshold-filter scan beside the buffered one, same index, same call
 
 Per run one JSON line: build time by stage (one assignment, one centroid update, the whole build), search time by stage
@@ -14,7 +15,9 @@ max / mean list length, scanned share.  With --storage f16 the line of the fp16 
 the fp32 index's centroids and assign) follows the fp32 one: the same stages plus the re-rank, issued and useful scan TF/s,
 the index's bytes, and recall@k for refine 0 and --refine.  With --storage pq (--pq-m M) the line of the pq index follows in the
 same way: the codebooks trained once per nlist (pq_train_ms) and the catalogue encoded (pq_encode_ms), the stages with the lookup
-tables ("lut") and the table-lookup scan apart, the scan's lookups per second instead of FLOP/s.  With --scan filter a line "scan": "filter" follows every buffered
+tables ("lut") and the table-lookup scan apart, the scan's lookups per second instead of FLOP/s.  With --pq-residual 1 the line of the
+residual pq index (codes of the row minus its list's centroid; the same (centroids, assign)) follows, with the slot scalars' launch
+("slot_dots") as a stage of its own.  With --scan filter a line "scan": "filter" follows every buffered
 line (under --score-bytes and under every --filter-score-bytes): the stages seed scan / seed merge / filter / merge_list /
 re-search, issued and useful TF/s of the seed scan and of the filter, the peak score + candidate bytes of a chunk, the candidates
 appended per query, the re-searched share, and whether (D, I) equal the buffered search's bit for bit.  Rows are Gaussian mixtures (n / 64 centres, noise 0.5) so that lists mean something.
@@ -55,8 +58,11 @@ def staged_search(idx, queries, k, nprobe, knn, ops, score_bytes, refine=0, base
     tile = {}
     if f16:
         ms["round"] = 0.0
+    pqr = pq and idx.pq_residual
     if pq:
         ms["lut"] = 0.0
+        if pqr:
+            ms["slot_dots"] = 0.0
         tile["tile_slots"], tile["tile_rows"] = ops.ivf_pq_tile(idx.pq_m)
     if refine:
         ms["refine"] = 0.0
@@ -78,7 +84,7 @@ def staged_search(idx, queries, k, nprobe, knn, ops, score_bytes, refine=0, base
         p = probe.to(torch.int64)
         costs = torch.where(p >= 0, ld[p.clamp(min=0)], torch.zeros_like(p)).sum(1).cpu().numpy()
         if pq:
-            costs = costs + knn.pq_query_floats(idx.pq_m)
+            costs = costs + knn.pq_query_floats(idx.pq_m, nprobe if pqr else 0)
         return knn.ivf_plan_chunks(costs, score_bytes, max_queries=(2 ** 31 - 1) // nprobe)
     t, chunks = timed(plan)
     ms["tables"] += t
@@ -102,8 +108,15 @@ def staged_search(idx, queries, k, nprobe, knn, ops, score_bytes, refine=0, base
             lut = torch.empty((q1 - q0, idx.pq_m, 256), dtype=torch.float32, device=dev)
             t, _ = timed(lambda: ops.pq_lut(Q[q0:q1], idx.codebooks, lut))
             ms["lut"] += t
-            t, _ = timed(lambda: ops.ivf_scan_pq(lut, tb["slot_query"], tb["slot_start"], tb["slot_off"], idx.codes, idx.list_start,
-                                                 tb["tiles"], scores))
+            if pqr:
+                slot_base = torch.empty(tb["n_slots"], dtype=torch.float32, device=dev)
+                t, _ = timed(lambda: ops.ivf_slot_dots(Q[q0:q1], idx._C, tb["slot_query"], tb["slot_start"], slot_base))
+                ms["slot_dots"] += t
+                t, _ = timed(lambda: ops.ivf_scan_pqr(lut, tb["slot_query"], tb["slot_start"], tb["slot_off"], slot_base,
+                                                      idx.codes, idx.list_start, tb["tiles"], scores))
+            else:
+                t, _ = timed(lambda: ops.ivf_scan_pq(lut, tb["slot_query"], tb["slot_start"], tb["slot_off"], idx.codes,
+                                                     idx.list_start, tb["tiles"], scores))
             ms["scan"] += t
             del lut
         elif tb["n_tiles"]:
@@ -261,8 +274,11 @@ def main():
     ap.add_argument("--sample", type=int, default=65536, help="queries of the recall sample when n is above it (--big)")
     ap.add_argument("--score-bytes", type=int, default=None)
     ap.add_argument("--storage", nargs="*", default=["f32"], choices=["f32", "f16", "pq"], help="list formats to time, over one (centroids, assign)")
-    ap.add_argument("--pq-m", type=int, default=32, help="bytes per listed row of the pq index")
-    ap.add_argument("--refine", type=int, default=0, help="re-rank depth r of the f16 / pq index (k <= r <= 128); 0 = none")
+    ap.add_argument("--pq-m", type=int, nargs="*", default=[32], help="bytes per listed row of the pq index (one index per value)")
+    ap.add_argument("--pq-residual", type=int, nargs="*", default=[0], choices=[0, 1],
+                    help="0 = plain codes, 1 = codes of the row minus its list's centroid (one index per value)")
+    ap.add_argument("--refine", type=int, nargs="*", default=[0],
+                    help="re-rank depths r of the f16 / pq index (k <= r <= 128); 0 = none, always run")
     ap.add_argument("--scan", nargs="*", default=["buffer"], choices=["buffer", "filter"],
                     help="search modes to time over the same index; \"filter\" is compared with the buffered search of the same call")
     ap.add_argument("--filter-score-bytes", type=int, nargs="*", default=[], help="further budgets for the filter runs (e.g. 1073741824)")
@@ -275,6 +291,7 @@ def main():
     k = a.k or (40 if a.big else 51)
     nlists = a.nlist or ([4096, 16384] if a.big else [256, 1024])
     nprobes = a.nprobe or ([8, 16, 32] if a.big else [4, 16])
+    refines = sorted(set([0] + list(a.refine)))
     x = catalogue(n, a.dim, dev)
     # the exact search of the same size, in the same call (warmed); at --big on the sample only
     sample = None
@@ -301,20 +318,30 @@ def main():
                 indexes.append((idx, None))
             elif storage == "pq":                                                                         # the same (centroids, assign), pq codes
                 Xp = idx.prepare(x)
-                knn.pq_train(Xp[:4096], a.pq_m, iters=1)                                                  # warm
-                train_ms, (cb, _) = timed(lambda: knn.pq_train(Xp, a.pq_m))
-                codes = torch.empty((n, a.pq_m), dtype=torch.uint8, device=dev)
-                encode_ms, _ = timed(lambda: ops.pq_encode(Xp, cb, codes))
-                del codes
-                h = knn.IVFIndex.load_state_dict(dict(idx.state_dict(), codebooks=cb), x, device=dev, storage="pq")
-                h.bench = {"pq_m": a.pq_m, "pq_train_ms": round(train_ms, 2), "pq_encode_ms": round(encode_ms, 3)}
-                indexes.append((h, Xp if a.refine else None))
+                for pq_m in a.pq_m:
+                    for residual in a.pq_residual:
+                        res = {"centroids": idx._C, "assign": idx.assign} if residual else {}
+                        knn.pq_train(Xp[:4096], pq_m, iters=1)                                            # warm
+                        train_ms, (cb, obj) = timed(lambda: knn.pq_train(Xp, pq_m, **res))
+                        codes = torch.empty((n, pq_m), dtype=torch.uint8, device=dev)
+                        if residual:
+                            ops.pqr_encode(Xp[:4096], idx._C, idx.assign[:4096].contiguous(), cb, codes)  # warm
+                            encode_ms, _ = timed(lambda: ops.pqr_encode(Xp, idx._C, idx.assign, cb, codes))
+                        else:
+                            encode_ms, _ = timed(lambda: ops.pq_encode(Xp, cb, codes))
+                        del codes
+                        state = dict(idx.state_dict(), codebooks=cb, **({"pq_residual": True} if residual else {}))
+                        h = knn.IVFIndex.load_state_dict(state, x, device=dev, storage="pq")
+                        h.bench = {"pq_m": pq_m, "pq_residual": bool(residual), "pq_train_ms": round(train_ms, 2),
+                                   "pq_encode_ms": round(encode_ms, 3),
+                                   "pq_objective_last": float(obj[:, -1].sum()) if obj.shape[1] else None}
+                        indexes.append((h, Xp if refines != [0] else None))
             else:                                                                                         # the same (centroids, assign), fp16 lists
                 h = knn.IVFIndex.load_state_dict(idx.state_dict(), x, device=dev, storage="f16")
-                indexes.append((h, h.prepare(x) if a.refine else None))
+                indexes.append((h, h.prepare(x) if refines != [0] else None))
         for nprobe in nprobes:
             for index, base in indexes:
-                for refine in ([0] if base is None else [0, a.refine]):
+                for refine in ([0] if base is None else refines):
                     run_one(index, base, refine, nprobe, nlist, x, k, n, a, knn, ops, sample, Ie, xq, exact_ms, score_bytes,
                             build_ms, assign_ms, update_ms, lens)
 
