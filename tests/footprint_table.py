@@ -71,15 +71,15 @@ ENTRIES = [
       "K = 384; K = 3072"),
     # ---- tail and loss ---------------------------------------------------------------------------------------------------------
     E("vnet_tail_planes", "cdml_vnet_tail_planes", "in z[rows][D] (ldz > D) rows shift; out e pos neg hinge valid dz2 planes (plane_bf > D) stats[0..3]",
-      "fp64 l2norm -> hinge -> gradients in torch", "1e-6 abs: test_gpu_parity tail tests; planes == split of dz2", "modes 0 and 1"),
+      "fp64 l2norm -> hinge -> gradients in torch", "1e-6 abs: test_gpu_parity tail tests; planes == split of dz2; bit for bit on exact operands, corner / clamp / masks included: tests/test_gpu_exact_tail.py", "modes 0 and 1"),
     E("triplet_hinge_indexed", "cdml_triplet_hinge_indexed", "in e[2B][D] (lde > D) neg_row[B]; out pos neg hinge stats de[2B][D]; ws scale_scratch[B]",
-      "fp64 hinge over (2i, 2i+1, neg_row[i]) in torch", "1e-6: test_gpu_parity indexed hinge tests", "masked triplets (-1), rows mined twice"),
+      "fp64 hinge over (2i, 2i+1, neg_row[i]) in torch", "1e-6: test_gpu_parity indexed hinge tests; bit for bit on exact operands, corner / clamp / masks included: tests/test_gpu_exact_tail.py", "masked triplets (-1), rows mined twice"),
     E("triplet_hinge_indexed_tail", "cdml_triplet_hinge_indexed_tail", "as triplet_hinge_indexed + in z; out dz2 dz2 planes (plane_bf > D)",
-      "fp64 hinge + l2norm backward + lrelu' in torch", "1e-6: test_gpu_parity indexed hinge tests; planes == split of dz2"),
+      "fp64 hinge + l2norm backward + lrelu' in torch", "1e-6: test_gpu_parity indexed hinge tests; planes == split of dz2; bit for bit on exact operands, corner / clamp / masks included: tests/test_gpu_exact_tail.py"),
     E("semihard_mine_x3", "cdml_semihard_mine_x3", "in e[2B][D] rows[2B]; out e_planes sqn dp neg_row; ws",
       "fp64 distances, the semi-hard rule", "2e-6 on the distances: test_gpu_parity / test_gpu_f32x3 semi-hard checks; bit for bit, ties included: tests/test_gpu_exact_select.py"),
-    E("l2norm_fwd", "cdml_l2norm_fwd", "in x[M][N] (ldx > N); out y[M][N] (ldy > N) inv[M]", "fp64 x rsqrt(max(sum x^2, 1e-12))", "1e-6: test_gpu_parity l2norm"),
-    E("l2norm_bwd", "cdml_l2norm_bwd", "in z g; out dz (ld > N)", "fp64 l2norm backward (+ lrelu')", "1e-6: test_gpu_parity l2norm"),
+    E("l2norm_fwd", "cdml_l2norm_fwd", "in x[M][N] (ldx > N); out y[M][N] (ldy > N) inv[M]", "fp64 x rsqrt(max(sum x^2, 1e-12))", "1e-6: test_gpu_parity l2norm; bit for bit on exact operands, corner / clamp / masks included: tests/test_gpu_exact_tail.py"),
+    E("l2norm_bwd", "cdml_l2norm_bwd", "in z g; out dz (ld > N)", "fp64 l2norm backward (+ lrelu')", "1e-6: test_gpu_parity l2norm; bit for bit on exact operands, corner / clamp / masks included: tests/test_gpu_exact_tail.py"),
     # ---- N-pair family ---------------------------------------------------------------------------------------------------------
     E("npair_stats", "cdml_npair_stats", "in S ids; out lse[2B] stats[4]; ws", "tests/npair_ref.py", "1e-5: tests/test_gpu_npair.py", "B = 200 in Bp = 256"),
     E("npair_grad_x3", "cdml_npair_grad_x3", _NPAIR_OPS, "tests/npair_ref.py W", "1e-4 rel: tests/test_gpu_npair.py", "B = 200 in Bp = 256: the pad of W keeps its poison"),

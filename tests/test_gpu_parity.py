@@ -491,7 +491,6 @@ def test_vnet_tail_fused_equals_separate_kernels_and_oracle(cd, mode, B, D):
     R = rpt * B
     z = (rng.randn(R, D) * 0.3 + 0.05).astype(np.float32)
     z[1] *= 1e-8                                            # a row below the 1e-12 clamp
-    dz = dt(z, cd.dev)
     n_vid = 40 if B < 100 else 3000
     pairs = osynth.cowatch_pairs(n_vid, max(30, B // 8), 2)
     step = 1
@@ -504,6 +503,11 @@ def test_vnet_tail_fused_equals_separate_kernels_and_oracle(cd, mode, B, D):
         rows_np, tri, valid, sh = osampler.device_inbatch(pairs, 3, step, B)
         valid = valid.astype(bool)
         rows, shift = dt(rows_np, cd.dev, torch.int32), dt([sh], cd.dev, torch.int32)
+    # ... and two more in an ACTIVE triplet: the anchor and the negative of the first valid triplet shrunk together
+    # (e_a, e_n ~ 0: pos ~ 1, neg ~ 0, t ~ 1.8), so the clamped branch dz = inv g runs at a non-zero gradient
+    sub = [int(r) for r in tri[int(np.nonzero(valid)[0][0]), [0, 2]]]
+    z[sub] *= 1e-8
+    dz = dt(z, cd.dev)
     # separate kernels
     e0, de0, dz0 = f(R, D), f(R, D), f(R, D)
     p0, n0, h0, st0 = f(B), f(B), f(B), f(4)
@@ -545,6 +549,15 @@ def test_vnet_tail_fused_equals_separate_kernels_and_oracle(cd, mode, B, D):
                                           otower.l2_normalize_backward(z.astype(np.float64), inv, dE, np.float64))
         scale = max(np.abs(want).max(), 1e-30)
         assert np.abs(dz1.cpu().numpy() - want).max() < 1e-5 * max(scale, 1.0)
+        # the sub-clamp rows of the active triplet carry a gradient, by the oracle ...
+        assert (z[sub].astype(np.float64) ** 2).sum(1).max() < 1e-12
+        assert (np.abs(want[sub]).max(1) > 0).all()
+        # ... and every row is compared against its OWN largest expected magnitude (at B = 4096 the largest |dz2| is 4e-5:
+        # one absolute 1e-5 allows a quarter of it): 1e-5 relative, ~170 fp32 ulp for a row of a few hundred roundings
+        row_max = np.abs(want).max(1)
+        row_err = np.abs(dz1.cpu().numpy().astype(np.float64) - want).max(1)
+        worst = int(np.argmax(row_err - TOL * row_max))
+        assert (row_err <= TOL * row_max).all(), (worst, row_err[worst], row_max[worst])
     var = otower.calc_var(e64[tri], np.float64)
     np.testing.assert_allclose(st1[4].item(), var, rtol=1e-5, atol=1e-8)
 
