@@ -328,6 +328,15 @@ SIGNATURES_IVF_PQR = {
     "cdml_ivf_scan_pqr": (_i, [_p, _i, _p, _p, _p, _p, _p, _i64, _p, _i, _p, _i, _p, _p]),
 }
 
+# name -> (restype, argtypes); must list every symbol include/cdml_ivf_pq4.h declares (4-bit product quantisation: two codes a
+# byte, 16-entry lookup tables; the argument lists are those of the 8-bit entry points)
+SIGNATURES_IVF_PQ4 = {
+    "cdml_pq4_encode": (_i, [_p, _i64, _i64, _p, _i, _i, _p, _i64, _p, _i64, _p]),
+    "cdml_pq4_lut": (_i, [_p, _i64, _i, _p, _i, _i, _p, _p]),
+    "cdml_ivf_pq4_tile": (_i, [_i, _p, _p]),
+    "cdml_ivf_scan_pq4": (_i, [_p, _i, _p, _p, _p, _p, _i64, _p, _i, _p, _i, _p, _p]),
+}
+
 _lib = None
 
 
@@ -351,7 +360,7 @@ def load_library():
                                + list(SIGNATURES_NEGW.items()) + list(SIGNATURES_F8.items()) + list(SIGNATURES_IVF.items())
                                + list(SIGNATURES_IVF_F16.items()) + list(SIGNATURES_IVF_FILTER.items())
                                + list(SIGNATURES_KNN_WRITER.items()) + list(SIGNATURES_IVF_PQ.items())
-                               + list(SIGNATURES_IVF_PQR.items())):
+                               + list(SIGNATURES_IVF_PQR.items()) + list(SIGNATURES_IVF_PQ4.items())):
         fn = getattr(lib, name)          # AttributeError if the ABI lost a symbol
         fn.restype = res
         fn.argtypes = args

@@ -243,6 +243,8 @@ IVF_SCANS = ("buffer", "filter")
 
 
 PQ_M_MIN, PQ_M_MAX, PQ_CODEWORDS = 8, 64, 256     # include/cdml_ivf_pq.h
+PQ4_CODEWORDS = 16                                # include/cdml_ivf_pq4.h
+PQ_BITS = (4, 8)
 
 
 def _check_pq_m(storage, pq_m, Dp=None, what="pq_m"):
@@ -268,6 +270,29 @@ def _check_pq_residual(storage, pq_residual):
     if pq_residual and storage != "pq":
         raise ValueError("pq_residual belongs to storage=\"pq\" (got storage=%r)" % (storage,))
     return bool(pq_residual)
+
+
+def pq_codewords(bits):
+    """256 or 16: the codewords of a subspace under ``pq_bits``"""
+    return PQ4_CODEWORDS if int(bits) == 4 else PQ_CODEWORDS
+
+
+def _check_pq_bits(storage, pq_bits, pq_m=None, Dp=None, pq_residual=False):
+    """``pq_bits`` of an index with ``storage``: 8 (include/cdml_ivf_pq.h) or 4 (include/cdml_ivf_pq4.h: two codes a byte, 2
+    ``pq_m`` subspaces of 16 codewords).  The refusals, by name; pure host arithmetic."""
+    if isinstance(pq_bits, bool) or pq_bits not in PQ_BITS:
+        raise ValueError("pq_bits must be one of %s, got %r" % (PQ_BITS, pq_bits))
+    bits = int(pq_bits)
+    if bits != 8 and storage != "pq":
+        raise ValueError("pq_bits belongs to storage=\"pq\" (got storage=%r)" % (storage,))
+    if bits == 4:
+        if pq_residual:
+            raise ValueError("pq_bits=4 with pq_residual=True is not built (residual 4-bit codes: DESIGN.md section 10): use "
+                             "pq_bits=8 or pq_residual=False")
+        if pq_m is not None and Dp is not None and Dp % (2 * int(pq_m)):
+            raise ValueError("pq_bits=4 has 2 pq_m = %d subspaces: they do not divide the padded dimension Dp = %d"
+                             % (2 * int(pq_m), Dp))
+    return bits
 
 
 def _check_ivf_options(storage, refine, scan, ks=(), pq_m=None, pq_residual=False):
@@ -309,16 +334,17 @@ def _check_ivf_lists(what, nlist, nprobe, n_rows):
 
 
 def ivf_knn(base, queries=None, k=51, nlist=1024, nprobe=16, l2_norm=True, storage="f32", refine=0, scan="buffer", iters=10,
-            seed=0, device="cuda:0", precision="f32x3", index=None, stats=None, pq_m=None, pq_residual=False):
+            seed=0, device="cuda:0", precision="f32x3", index=None, stats=None, pq_m=None, pq_residual=False, pq_bits=8):
     """Device (D, I) of ``IVFIndex.search``, shaped and typed like ``knn_search``'s: the index of ``base`` (built here with
     ``nlist`` lists, ``iters`` Lloyd iterations and ``seed``, or taken as ``index=``), every query's ``nprobe`` nearest lists
     scanned exactly.  ``queries=None`` is the self-search.  ``refine>0`` (storage "f16" or "pq"; "pq" takes ``pq_m``, the
-    bytes per listed row, and ``pq_residual``: codes of the row minus its list's centroid) re-ranks the ``refine`` best against the fp32 rows ``index.prepare(base)``.  The one place the export's approximate searches go through; its launches are
+    bytes per listed row, ``pq_residual``: codes of the row minus its list's centroid, DESIGN.md section 9f.4, and ``pq_bits``: 8, or 4 for two 16-codeword codes a byte, section 9f.5) re-ranks the ``refine`` best against the fp32 rows ``index.prepare(base)``.  The one place the export's approximate searches go through; its launches are
     those of DESIGN.md sections 9f-9f.3.  ``stats`` (a dict, optional) receives ``IVFIndex.search``'s."""
     if index is None:
         _check_ivf_options(storage, refine, scan, (int(k),), pq_m, pq_residual)
+        _check_pq_bits(storage, pq_bits, pq_m, _round_up(int(base.shape[1]), 32), pq_residual)
         index = IVFIndex.build(base, int(nlist), iters=iters, seed=seed, l2_norm=l2_norm, device=device, precision=precision,
-                               storage=storage, pq_m=pq_m, pq_residual=pq_residual)
+                               storage=storage, pq_m=pq_m, pq_residual=pq_residual, pq_bits=pq_bits)
     q = base if queries is None else queries
     kw = {"refine": int(refine), "base": index.prepare(base)} if int(refine) > 0 else {}
     return index.search(q, int(k), int(nprobe), stats=stats, scan=scan, **kw)
@@ -344,20 +370,21 @@ def _check_cross_lists(nlist, nprobe, doc_location, n):
 
 
 def cross_knn(embeddings, doc_location, nearest_num=81, precision="f32x3", device="cuda:0", nlist=0, nprobe=0, storage="f32",
-              refine=0, scan="buffer", ivf_iters=10, ivf_seed=0, stats=None, pq_m=None, pq_residual=False):
+              refine=0, scan="buffer", ivf_iters=10, ivf_seed=0, stats=None, pq_m=None, pq_residual=False, pq_bits=8):
     """(crossD, crossI) as faiss_knn.py:325-336 builds them: rows [0, doc_location) (videos) search the documents, their
     ids offset by ``doc_location`` into global ids; rows [doc_location, n) (documents) search the videos.  Rows are in
     global order, so the query of row r is r.  The exact search (``knn_search``) stands for the reference's HNSW.  A -1
     ("no neighbour": a side with fewer than nearest_num rows) stays -1 instead of taking the offset.  Returns the kind
     of ``embeddings``.
     ``nlist > 0``: either side is searched through an ``IVFIndex`` of its own (``ivf_knn``) with ``cross_nlist(nlist, n_side,
-    n)`` lists, of which min(nprobe, that many) are probed; ``storage``, ``pq_m``, ``pq_residual``, ``refine``, ``scan``, ``ivf_iters`` and ``ivf_seed`` go
+    n)`` lists, of which min(nprobe, that many) are probed; ``storage``, ``pq_m``, ``pq_residual``, ``pq_bits``, ``refine``, ``scan``, ``ivf_iters`` and ``ivf_seed`` go
     to both.  ``stats`` (a dict, optional) receives the two searches' under "video_to_doc" and "doc_to_video"."""
     t = embeddings if torch.is_tensor(embeddings) else torch.from_numpy(np.asarray(embeddings, dtype=np.float32))
     if int(nlist) or int(nprobe):
         n = t.shape[0]
         nlist, nprobe = _check_cross_lists(nlist, nprobe, int(doc_location), n)
         _check_ivf_options(storage, refine, scan, (int(nearest_num),), pq_m, pq_residual)
+        _check_pq_bits(storage, pq_bits, pq_m, _round_up(int(t.shape[1]), 32), pq_residual)
         video, doc = t[:doc_location], t[doc_location:]
         out = []
         for name, base, q in (("video_to_doc", doc, video), ("doc_to_video", video, doc)):
@@ -365,7 +392,7 @@ def cross_knn(embeddings, doc_location, nearest_num=81, precision="f32x3", devic
             st = None if stats is None else stats.setdefault(name, {})
             out.append(ivf_knn(base, q, int(nearest_num), nlist=nl, nprobe=min(nprobe, nl), storage=storage, refine=refine,
                                scan=scan, iters=ivf_iters, seed=ivf_seed, device=device, precision=precision, stats=st,
-                               pq_m=pq_m, pq_residual=pq_residual))
+                               pq_m=pq_m, pq_residual=pq_residual, pq_bits=pq_bits))
         (vdD, vdI), (dvD, dvI) = out
         vdI = torch.where(vdI >= 0, vdI + doc_location, vdI)
         D, I = torch.cat([vdD, dvD]), torch.cat([vdI, dvI])
@@ -373,6 +400,7 @@ def cross_knn(embeddings, doc_location, nearest_num=81, precision="f32x3", devic
             return D, I
         return D.cpu().numpy(), I.cpu().numpy()
     _check_ivf_options(storage, refine, scan, pq_m=pq_m, pq_residual=pq_residual)
+    _check_pq_bits(storage, pq_bits, pq_residual=pq_residual)
     if storage != "f32" or int(refine) or scan != "buffer":
         raise ValueError("storage, refine and scan belong to nlist > 0 (this search is exact)")
     video, doc = t[:doc_location], t[doc_location:]
@@ -611,7 +639,7 @@ def export(embeddings, features, decode_map, out_dir, doc_location=343455, neare
            fD_threshold=DESIM_THRESHOLD, fI_end=DESIM_FI_END, precision="f32x3", device="cuda:0", split_num=10,
            nlist=0, nprobe=0, feature_nlist=0, feature_nprobe=0, storage="f32", refine=0, scan="buffer", ivf_iters=10,
            ivf_seed=0, feature_knn=None, writer="host", audit_rows=0, audit_seed=0, stats=None, pq_m=None, feature_pq_m=None,
-           pq_residual=False):
+           pq_residual=False, pq_bits=8):
     """faiss_knn.main (faiss_knn.py:359-400) with explicit arguments: the raw-feature kNN (fD, fI; k = min(desim_nearest_num,
     nearest_num)), then -- cross mode when 0 < doc_location < n, strict mode otherwise -- the embedding kNN, desim and the
     text lists.  Writes fD.npy, fI.npy, {strict,cross}D.npy, {strict,cross}I.npy, {strict,cross}I_desim.npy, the
@@ -623,7 +651,7 @@ def export(embeddings, features, decode_map, out_dir, doc_location=343455, neare
     ``nlist`` / ``nprobe``: the embedding search through ``ivf_knn`` (strict) or ``cross_knn(nlist=...)`` (cross: an index per
     side).  ``feature_nlist`` / ``feature_nprobe``: the raw-feature search through ``ivf_knn``, independently.  ``storage``,
     ``refine``, ``scan``, ``ivf_iters``, ``ivf_seed`` go to every index; with ``storage="pq"`` the embedding indexes take ``pq_m``
-    and the raw-feature index ``feature_pq_m`` (default: ``pq_m``), and ``pq_residual`` goes to every pq index.  ``feature_knn``: (fD, fI) or a directory holding
+    and the raw-feature index ``feature_pq_m`` (default: ``pq_m``), and ``pq_residual`` and ``pq_bits`` go to every pq index.  ``feature_knn``: (fD, fI) or a directory holding
     fD.npy / fI.npy of an earlier export -- raw features do not change when the model is retrained -- written as given, no
     feature search (``features`` may then be None unless the audit needs them).  ``writer``: "host" | "device"
     (``write_knn``).  ``audit_rows = m > 0``: the recall statement -- for the rows ``audit_sample(n, m, audit_seed)`` the
@@ -643,7 +671,12 @@ def export(embeddings, features, decode_map, out_dir, doc_location=343455, neare
     feature_nlist, feature_nprobe = _check_ivf_lists("feature_", feature_nlist, feature_nprobe, n)
     refine = _check_ivf_options(storage, refine, scan, ((k,) if nlist else ()) + ((k_f,) if feature_nlist else ()), pq_m,
                                 pq_residual)
+    pq_bits = _check_pq_bits(storage, pq_bits, pq_residual=pq_residual)
     feature_pq_m = _check_pq_m(storage, pq_m if feature_pq_m is None else feature_pq_m, what="feature_pq_m")
+    if nlist:                                                 # (2 pq_m subspaces must divide either index's padded dimension)
+        _check_pq_bits(storage, pq_bits, pq_m, _round_up(int(embeddings.shape[1]), 32), pq_residual)
+    if feature_nlist and features is not None and feature_knn is None:
+        _check_pq_bits(storage, pq_bits, feature_pq_m, _round_up(int(features.shape[1]), 32), pq_residual)
     if not (nlist or feature_nlist) and (storage != "f32" or refine or scan != "buffer"):
         raise ValueError("storage, refine and scan belong to an IVF search: set nlist or feature_nlist (both are 0)")
     if feature_knn is not None:
@@ -660,6 +693,8 @@ def export(embeddings, features, decode_map, out_dir, doc_location=343455, neare
     ivf = {"storage": storage, "refine": refine, "scan": scan}
     pq = {"pq_m": int(pq_m), "feature_pq_m": feature_pq_m} if storage == "pq" else {}
     pqr = {"pq_residual": True} if pq_residual else {}        # (absent when off: the stats of a plain export keep their keys)
+    if int(pq_bits) != 8:
+        pqr["pq_bits"] = int(pq_bits)                         # (absent at 8, for the same reason)
 
     def stage(name, t0, extra=None):
         if stats is not None:
@@ -806,25 +841,27 @@ def ivf_tables(probe, list_len, tile_slots=IVF_TILE, tile_rows=IVF_TILE):
             "slot_off": slot_off, "slot_of": slot_of.view(m, nprobe), "tiles": tiles}
 
 
-def pq_query_floats(pq_m, nprobe=0):
-    """256 M: the floats of one query's lookup table, what a query of a pq index costs a chunk beside its scores; a residual
-    index (``pq_residual``) adds its ``nprobe`` slot scalars"""
-    return PQ_CODEWORDS * int(pq_m) + int(nprobe)
+def pq_query_floats(pq_m, nprobe=0, bits=8):
+    """256 M (``bits=4``: 2 M tables of 16 = 32 M): the floats of one query's lookup table, what a query of a pq index costs a
+    chunk beside its scores; a residual index (``pq_residual``) adds its ``nprobe`` slot scalars"""
+    return (2 * PQ4_CODEWORDS if int(bits) == 4 else PQ_CODEWORDS) * int(pq_m) + int(nprobe)
 
 
 PQ_TRAIN_ROWS = 65536       # default training rows of pq_train (256 per codeword)
+PQ4_TRAIN_ROWS = 4096       # ... with bits=4 (256 per codeword again)
 
 
-def _check_pq_train(n_finite, iters, train_rows):
+def _check_pq_train(n_finite, iters, train_rows, bits=8):
     """(n_train, iters) of ``pq_train``: the refusals, by name"""
     iters = int(iters)
+    K = pq_codewords(bits)
     if iters < 0:
         raise ValueError("pq_iters must be >= 0, got %d" % iters)
-    if n_finite < PQ_CODEWORDS:
-        raise ValueError("storage=\"pq\" needs at least %d finite rows to start its codebooks from, got %d" % (PQ_CODEWORDS, n_finite))
-    n_train = min(n_finite, PQ_TRAIN_ROWS) if train_rows is None else int(train_rows)
-    if not PQ_CODEWORDS <= n_train <= n_finite:
-        raise ValueError("pq_train_rows must be in [%d, the number of finite rows = %d], got %d" % (PQ_CODEWORDS, n_finite, n_train))
+    if n_finite < K:
+        raise ValueError("storage=\"pq\" needs at least %d finite rows to start its codebooks from, got %d" % (K, n_finite))
+    n_train = min(n_finite, PQ4_TRAIN_ROWS if K == PQ4_CODEWORDS else PQ_TRAIN_ROWS) if train_rows is None else int(train_rows)
+    if not K <= n_train <= n_finite:
+        raise ValueError("pq_train_rows must be in [%d, the number of finite rows = %d], got %d" % (K, n_finite, n_train))
     return n_train, iters
 
 
@@ -839,6 +876,20 @@ def pq_train(X_prepared, pq_m, iters=10, seed=0, train_rows=None, centroids=None
     ``centroids`` (fp32 [nlist, Dp], the padded matrix) and ``assign`` (int64 [n]) together: the same Lloyd's on the
     RESIDUALS x - centroids[assign] of the same rows (include/cdml_ivf_pqr.h; one fp32 subtract per column, materialised
     for the training rows only); every finite row then needs an assign in [0, nlist)."""
+    return _pq_lloyd(X_prepared, pq_m, iters, seed, train_rows, centroids, assign, 8)
+
+
+def pq4_train(X_prepared, pq_m, iters=10, seed=0, train_rows=None):
+    """``pq_train`` for ``pq_bits=4`` (include/cdml_ivf_pq4.h): the same deterministic Lloyd's over Ms = 2 ``pq_m`` subspaces of 16
+    codewords -- (codebooks fp32 [2 M, 16, Dp / (2 M)], pq_objective float64 [2 M, iters]); the initial codewords are the
+    sub-vectors of the sorted first 16 ids of the seeded permutation, the default training rows min(n_finite, 4 096) (256 per
+    codeword, as 65 536 is for 256), at least 16 finite rows are needed, the encoder is ``ops.pq4_encode``, an empty codeword
+    keeps its value.  Plain codebooks only: residual 4-bit codes are not built."""
+    return _pq_lloyd(X_prepared, pq_m, iters, seed, train_rows, None, None, 4)
+
+
+def _pq_lloyd(X_prepared, pq_m, iters, seed, train_rows, centroids, assign, bits):
+    """``pq_train`` (bits = 8) and ``pq4_train`` (bits = 4)"""
     X = X_prepared
     if (centroids is None) != (assign is None):
         raise ValueError("pq_train takes centroids and assign together (residual codebooks) or neither (plain codebooks)")
@@ -846,15 +897,18 @@ def pq_train(X_prepared, pq_m, iters=10, seed=0, train_rows=None, centroids=None
         raise ValueError("pq_train takes the prepared fp32 [n, Dp] matrix (IVFIndex.prepare)")
     n, Dp = X.shape
     M = _check_pq_m("pq", pq_m, Dp)
-    dsub = Dp // M
+    _check_pq_bits("pq", bits, M, Dp)
+    K = pq_codewords(bits)
+    Ms = 2 * M if bits == 4 else M                        # subspaces; M stays the bytes per row
+    dsub = Dp // Ms
     dev = X.device
     fin = torch.nonzero(torch.isfinite(X).all(1)).flatten().cpu()
     n_finite = int(fin.numel())
-    n_train, iters = _check_pq_train(n_finite, iters, train_rows)
+    n_train, iters = _check_pq_train(n_finite, iters, train_rows, bits)
     g = torch.Generator()
     g.manual_seed(int(seed))
     perm = torch.randperm(n_finite, generator=g)
-    init_rows = torch.sort(fin[perm[:PQ_CODEWORDS]]).values
+    init_rows = torch.sort(fin[perm[:K]]).values
     train_ids = torch.sort(fin[perm[:n_train]]).values
     Xt = X if n_train == n else X.index_select(0, train_ids.to(dev))
     X0 = X.index_select(0, init_rows.to(dev))
@@ -869,20 +923,29 @@ def pq_train(X_prepared, pq_m, iters=10, seed=0, train_rows=None, centroids=None
             raise ValueError("pq_train: every finite row needs an assign in [0, nlist = %d)" % Cp.shape[0])
         Xt = X.index_select(0, train_ids.to(dev)) - Cp.index_select(0, a.index_select(0, train_ids.to(dev)))
         X0 = X0 - Cp.index_select(0, a.index_select(0, init_rows.to(dev)))
-    cb = X0.view(PQ_CODEWORDS, M, dsub).permute(1, 0, 2).contiguous()
+    cb = X0.view(K, Ms, dsub).permute(1, 0, 2).contiguous()
     codes = torch.empty((n_train, M), dtype=torch.uint8, device=dev)
-    dist = torch.empty((n_train, M), dtype=torch.float32, device=dev)
-    objective = torch.zeros((M, iters), dtype=torch.float64)
+    dist = torch.empty((n_train, Ms), dtype=torch.float32, device=dev)
+    objective = torch.zeros((Ms, iters), dtype=torch.float64)
     for it in range(iters):
-        ops.pq_encode(Xt, cb, codes, dist)
+        if bits == 4:
+            ops.pq4_encode(Xt, cb, codes, dist)
+        else:
+            ops.pq_encode(Xt, cb, codes, dist)
         objective[:, it] = dist.double().sum(0).cpu()
-        for m in range(M):
-            key = codes[:, m].to(torch.int64)
+        sub = pq_unpack(codes) if bits == 4 else codes
+        for m in range(Ms):
+            key = sub[:, m].to(torch.int64)
             order = torch.argsort(key, stable=True).to(torch.int32)       # by (code, id)
-            start = torch.zeros(PQ_CODEWORDS + 1, dtype=torch.int64, device=dev)
-            start[1:] = torch.cumsum(torch.bincount(key, minlength=PQ_CODEWORDS), 0)
+            start = torch.zeros(K + 1, dtype=torch.int64, device=dev)
+            start[1:] = torch.cumsum(torch.bincount(key, minlength=K), 0)
             ops.ivf_centroid_sums(Xt[:, m * dsub:(m + 1) * dsub], order, start.to(torch.int32), cb[m], dsub)
     return cb, objective
+
+
+def pq_unpack(codes):
+    """uint8 [n, 2 M]: the per-subspace codes of 4-bit ``codes`` (uint8 [n, M]; byte b = code(2b) | code(2b + 1) << 4)"""
+    return torch.stack((codes & 15, codes >> 4), dim=2).reshape(codes.shape[0], -1)
 
 
 class IVFIndex:
@@ -905,6 +968,9 @@ class IVFIndex:
     rows.  ``search`` scans by table lookup (one lookup table per query); ``refine=r`` re-ranks as for "f16".
     ``pq_residual=True`` (include/cdml_ivf_pqr.h): the codes describe the row minus its list's
     centroid, a decoded row is centroid + codewords, and a score starts from the slot's <query, centroid>.
+    ``pq_bits=4`` (include/cdml_ivf_pq4.h): the same ``pq_m`` bytes per row hold two 4-bit codes each
+    (the even subspace in the low nibble), ``codebooks`` is fp32 [2 pq_m, 16, Dp / (2 pq_m)], a query's lookup table 32 ``pq_m``
+    floats instead of 256 ``pq_m``.  Not with ``pq_residual``.
 
     ``search(..., scan="filter")`` (include/cdml_ivf_filter.h) is the same search, bit for bit, with a
     score buffer for the first ``seed_probes`` probe columns only: the other columns append what is within the seeded
@@ -956,14 +1022,15 @@ class IVFIndex:
         return out
 
     @classmethod
-    def _blank(cls, nlist, D, l2_norm, device, precision, storage="f32", pq_m=None, pq_residual=False):
+    def _blank(cls, nlist, D, l2_norm, device, precision, storage="f32", pq_m=None, pq_residual=False, pq_bits=8):
         self = object.__new__(cls)
         self.pq_residual = _check_pq_residual(storage, pq_residual)
+        self.pq_bits = _check_pq_bits(storage, pq_bits, pq_m, _round_up(int(D), 32), pq_residual)
         self.nlist, self.dim, self.l2_norm, self.device, self.precision = int(nlist), int(D), bool(l2_norm), torch.device(device), precision
         self.storage = cls._check_storage(storage)
         if storage == "pq":
             self.pq_m = int(pq_m)
-            self.pq_objective = torch.empty((self.pq_m, 0), dtype=torch.float64)
+            self.pq_objective = torch.empty((self.pq_m * (2 if self.pq_bits == 4 else 1), 0), dtype=torch.float64)
         self.init_rows = self.train_ids = torch.empty(0, dtype=torch.int64)
         self.objective = torch.empty(0, dtype=torch.float64)
         return self
@@ -992,6 +1059,8 @@ class IVFIndex:
             codes = torch.empty((n, self.pq_m), dtype=torch.uint8, device=X.device)
             if self.pq_residual:
                 ops.pqr_encode(X, C, a, self.codebooks, codes)
+            elif self.pq_bits == 4:
+                ops.pq4_encode(X, self.codebooks, codes)
             else:
                 ops.pq_encode(X, self.codebooks, codes)       # (an unlisted row's codes are computed and dropped)
             self.codes = codes.index_select(0, order[:n_listed])
@@ -1012,12 +1081,13 @@ class IVFIndex:
 
     def decode(self, positions):
         """fp32 [len, Dp]: the decoded rows (the concatenated codewords; with ``pq_residual`` the list's centroid + them, one
-        fp32 add) at ``positions`` of the cluster-major lists (plumbing: a torch gather).  storage "pq" only."""
+        fp32 add; with ``pq_bits=4`` the 2 pq_m codewords of the unpacked nibbles) at ``positions`` of the cluster-major lists (plumbing: a torch gather).  storage "pq" only."""
         if self.storage != "pq":
             raise ValueError("decode belongs to an index with storage=\"pq\" (this one is %r)" % self.storage)
         pos = positions.to(device=self.device, dtype=torch.int64)
-        c = self.codes.index_select(0, pos).to(torch.int64)
-        m = torch.arange(self.pq_m, device=self.device)
+        c = self.codes.index_select(0, pos)
+        c = (pq_unpack(c) if self.pq_bits == 4 else c).to(torch.int64)
+        m = torch.arange(c.shape[1], device=self.device)
         out = self.codebooks[m[None, :], c].reshape(c.shape[0], -1)
         if self.pq_residual:                              # the list of a position: the last c with list_start[c] <= position
             lst = torch.searchsorted(self.list_start[1:].to(torch.int64), pos, right=True)
@@ -1025,29 +1095,42 @@ class IVFIndex:
         return out
 
     @staticmethod
-    def _check_codebooks(codebooks, Dp):
-        """(codebooks as a CPU-or-device fp32 tensor, M): the refusals of a given ``codebooks``, by name"""
+    def _check_codebooks(codebooks, Dp, pq_bits=None):
+        """(codebooks as a CPU-or-device fp32 tensor, M, bits): the refusals of a given ``codebooks``, by name.  [M, 256, Dp / M]
+        is an 8-bit set, [2 M, 16, Dp / (2 M)] a 4-bit one; ``pq_bits`` (None = whatever the shape says) must agree."""
         cb = codebooks if torch.is_tensor(codebooks) else torch.as_tensor(np.asarray(codebooks))
-        if cb.dtype != torch.float32 or cb.dim() != 3 or cb.shape[1] != PQ_CODEWORDS or cb.shape[0] * cb.shape[2] != Dp:
-            raise ValueError("codebooks must be a float32 [M, %d, Dp / M] tensor with M dsub = Dp = %d, got %s %s"
-                             % (PQ_CODEWORDS, Dp, tuple(cb.shape), cb.dtype))
-        return cb, _check_pq_m("pq", cb.shape[0], Dp, what="the codebooks' M")
+        if pq_bits is not None:
+            _check_pq_bits("pq", pq_bits)
+        bits = 4 if cb.dim() == 3 and cb.shape[1] == PQ4_CODEWORDS else 8
+        if cb.dtype != torch.float32 or cb.dim() != 3 or cb.shape[1] != pq_codewords(bits) or cb.shape[0] % (2 if bits == 4 else 1) \
+                or cb.shape[0] * cb.shape[2] != Dp:
+            raise ValueError("codebooks must be a float32 [M, %d, Dp / M] (or, 4-bit, [2 M, %d, Dp / (2 M)]) tensor with M dsub = "
+                             "Dp = %d, got %s %s" % (PQ_CODEWORDS, PQ4_CODEWORDS, Dp, tuple(cb.shape), cb.dtype))
+        if pq_bits is not None and int(pq_bits) != bits:
+            raise ValueError("pq_bits=%d contradicts codebooks of shape %s (a %d-bit set)" % (int(pq_bits), tuple(cb.shape), bits))
+        return cb, _check_pq_m("pq", cb.shape[0] // (2 if bits == 4 else 1), Dp, what="the codebooks' M"), bits
 
     @classmethod
     def from_assignment(cls, base, centroids, assign, l2_norm=True, device="cuda:0", precision="f32x3", storage="f32",
-                        codebooks=None, pq_residual=False):
+                        codebooks=None, pq_residual=False, pq_bits=None):
         """The index of given ``centroids`` ([nlist, D]) and an arbitrary ``assign`` (int [n], values in [-1, nlist); -1 =
         unlisted): the search contract does not need the assignment to be the nearest centroid.  ``storage="pq"`` takes
-        ``codebooks`` (fp32 [M, 256, Dp / M]) as they are; with ``pq_residual=True`` they are codebooks of residuals."""
+        ``codebooks`` (fp32 [M, 256, Dp / M]) as they are; with ``pq_residual=True`` they are codebooks of residuals.
+        ``pq_bits`` (default: 8, or what the codebooks say) -- codebooks of shape [2 M, 16, Dp / (2 M)] make a 4-bit index; a
+        ``pq_bits`` that contradicts the codebooks' shape is refused."""
         cls._check_storage(storage)
         _check_pq_residual(storage, pq_residual)
         t = cls._as_tensor(base)
         pq_m = None
+        bits = 8
         if storage == "pq":
             if codebooks is None:
                 raise ValueError("from_assignment(storage=\"pq\") needs codebooks= (fp32 [M, 256, Dp / M]; knn.pq_train)")
-            codebooks, pq_m = cls._check_codebooks(codebooks, _round_up(t.shape[1], 32))
-        elif codebooks is not None:
+            codebooks, pq_m, bits = cls._check_codebooks(codebooks, _round_up(t.shape[1], 32), pq_bits)
+            _check_pq_bits(storage, bits, pq_m, _round_up(t.shape[1], 32), pq_residual)
+        elif pq_bits is not None:
+            _check_pq_bits(storage, pq_bits)
+        if storage != "pq" and codebooks is not None:
             raise ValueError("codebooks belongs to storage=\"pq\" (got storage=%r)" % storage)
         c = centroids if torch.is_tensor(centroids) else torch.as_tensor(np.asarray(centroids, dtype=np.float32))
         a = assign if torch.is_tensor(assign) else torch.as_tensor(np.asarray(assign))
@@ -1058,7 +1141,7 @@ class IVFIndex:
         nlist = c.shape[0]
         if a.numel() and (int(a.min()) < -1 or int(a.max()) >= nlist):
             raise ValueError("assign must lie in [-1, nlist = %d)" % nlist)
-        self = cls._blank(nlist, t.shape[1], l2_norm, device, precision, storage, pq_m, pq_residual)
+        self = cls._blank(nlist, t.shape[1], l2_norm, device, precision, storage, pq_m, pq_residual, bits)
         if storage == "pq":
             self.codebooks = codebooks.detach().to(self.device).contiguous().clone()
         X = cls._prepared(t, self.device, l2_norm)
@@ -1066,17 +1149,18 @@ class IVFIndex:
 
     @classmethod
     def build(cls, base, nlist, iters=10, seed=0, train_rows=None, l2_norm=True, device="cuda:0", precision="f32x3",
-              storage="f32", pq_m=None, pq_iters=None, pq_seed=None, pq_train_rows=None, pq_residual=False):
+              storage="f32", pq_m=None, pq_iters=None, pq_seed=None, pq_train_rows=None, pq_residual=False, pq_bits=8):
         """Lloyd's k-means, deterministic (include/cdml_ivf.h BUILD).  ``precision`` is that of the coarse ``knn_search`` calls
         (every assignment step, and ``probes``).  ``storage`` ("f32" | "f16" | "pq") is the format of the lists alone: k-means
         runs on the fp32 rows either way, so (base, seed) gives the same ``assign`` and the same probes for all three.
         ``storage="pq"``: ``pq_m`` bytes per row; the codebooks come from ``pq_train(X, pq_m, pq_iters (default 10), pq_seed
         (default ``seed``), pq_train_rows)`` on the prepared rows; with ``pq_residual=True`` on their residuals against the
-        final centroids and assignment."""
+        final centroids and assignment; ``pq_bits=4``: 2 ``pq_m`` subspaces of 16 codewords (``pq4_train``)."""
         cls._check_storage(storage)
         _check_pq_residual(storage, pq_residual)
         t = cls._as_tensor(base)
         pq_m = _check_pq_m(storage, pq_m, _round_up(t.shape[1], 32))
+        pq_bits = _check_pq_bits(storage, pq_bits, pq_m, _round_up(t.shape[1], 32), pq_residual)
         if storage != "pq" and (pq_iters is not None or pq_seed is not None or pq_train_rows is not None):
             raise ValueError("pq_iters, pq_seed and pq_train_rows belong to storage=\"pq\" (got storage=%r)" % storage)
         nlist, iters = int(nlist), int(iters)
@@ -1089,8 +1173,8 @@ class IVFIndex:
         if not nlist <= n_train <= n_finite:
             raise ValueError("train_rows must be in [nlist = %d, the number of finite rows = %d], got %d" % (nlist, n_finite, n_train))
         if storage == "pq":
-            _check_pq_train(n_finite, 10 if pq_iters is None else pq_iters, pq_train_rows)
-        self = cls._blank(nlist, t.shape[1], l2_norm, device, precision, storage, pq_m, pq_residual)
+            _check_pq_train(n_finite, 10 if pq_iters is None else pq_iters, pq_train_rows, pq_bits)
+        self = cls._blank(nlist, t.shape[1], l2_norm, device, precision, storage, pq_m, pq_residual, pq_bits)
         dev = self.device
         X = cls._prepared(t, dev, l2_norm)
         n, Dp = X.shape
@@ -1119,9 +1203,9 @@ class IVFIndex:
         _, Ia = knn_search(C, X, 1, l2_norm=False, device=dev, precision=precision)
         if storage == "pq":
             res = {"centroids": C, "assign": Ia[:, 0].to(torch.int64)} if pq_residual else {}
-            self.codebooks, self.pq_objective = pq_train(X, pq_m, iters=10 if pq_iters is None else pq_iters,
-                                                         seed=seed if pq_seed is None else pq_seed, train_rows=pq_train_rows,
-                                                         **res)
+            train = pq4_train if pq_bits == 4 else pq_train
+            self.codebooks, self.pq_objective = train(X, pq_m, iters=10 if pq_iters is None else pq_iters,
+                                                      seed=seed if pq_seed is None else pq_seed, train_rows=pq_train_rows, **res)
         self._set_lists(X, C, Ia[:, 0])
         self.init_rows, self.train_ids = init_rows, train_ids
         self.objective = torch.stack(objective).cpu() if objective else torch.empty(0, dtype=torch.float64)
@@ -1139,6 +1223,8 @@ class IVFIndex:
             state["codebooks"] = self.codebooks.detach().cpu().clone()
             if self.pq_residual:
                 state["pq_residual"] = True
+            if self.pq_bits == 4:                             # (absent at 8: the state of an 8-bit index keeps its keys)
+                state["pq_bits"] = 4
         return state
 
     @classmethod
@@ -1154,6 +1240,7 @@ class IVFIndex:
                                  "loaded as \"pq\"")
             kw["codebooks"] = state["codebooks"]
             kw["pq_residual"] = bool(state.get("pq_residual", False))
+            kw["pq_bits"] = state.get("pq_bits")              # (None: what the codebooks' shape says)
         self = cls.from_assignment(base, state["centroids"], state["assign"], l2_norm=state["l2_norm"], device=device,
                                    precision=state["precision"], storage=storage, **kw)
         self.init_rows, self.objective = state["init_rows"].clone(), state["objective"].clone()
@@ -1271,8 +1358,9 @@ class IVFIndex:
         costs = torch.where(p >= 0, ld[p.clamp(min=0)], torch.zeros_like(p)).sum(1).cpu().numpy()
         tile = {}
         if pq:                                            # a chunk's scores AND lookup tables fit score_bytes together
-            costs = costs + pq_query_floats(self.pq_m, nprobe if self.pq_residual else 0)
-            tile["tile_slots"], tile["tile_rows"] = ops.ivf_pq_tile(self.pq_m)
+            costs = costs + (pq_query_floats(self.pq_m, bits=4) if self.pq_bits == 4
+                             else pq_query_floats(self.pq_m, nprobe if self.pq_residual else 0))
+            tile["tile_slots"], tile["tile_rows"] = (ops.ivf_pq4_tile if self.pq_bits == 4 else ops.ivf_pq_tile)(self.pq_m)
         chunks = ivf_plan_chunks(costs, score_bytes, max_queries=(2 ** 31 - 1) // nprobe)
         n_tiles = n_floats = 0
         keep = refine or k                                # entries the merge must get right
@@ -1293,6 +1381,12 @@ class IVFIndex:
                 ops.row_sqnorm(Qh.float(), Dp, q_sq[q0:q1])
                 if tb["n_tiles"]:
                     ops.ivf_scan_f16(Qh, tb["slot_query"], tb["slot_start"], tb["slot_off"], self.rows, self.list_start,
+                                     tb["tiles"], scores)
+            elif pq and self.pq_bits == 4:
+                if tb["n_tiles"]:
+                    lut = torch.empty((q1 - q0, 2 * self.pq_m, PQ4_CODEWORDS), dtype=torch.float32, device=Q.device)
+                    ops.pq4_lut(Q[q0:q1], self.codebooks, lut)
+                    ops.ivf_scan_pq4(lut, tb["slot_query"], tb["slot_start"], tb["slot_off"], self.codes, self.list_start,
                                      tb["tiles"], scores)
             elif pq:
                 if tb["n_tiles"]:

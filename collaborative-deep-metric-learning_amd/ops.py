@@ -1879,6 +1879,70 @@ def ivf_scan_pqr(lut, slot_query, slot_start, slot_off, slot_base, codes, list_s
     return scores
 
 
+# ---------------------------------------- 4-bit product quantisation (include/cdml_ivf_pq4.h) ------
+def _codebooks4(codebooks):
+    if codebooks.dtype != torch.float32 or codebooks.dim() != 3 or codebooks.shape[1] != 16 or codebooks.shape[0] % 2 \
+            or not codebooks.is_contiguous():
+        raise ValueError("codebooks must be a contiguous float32 [2 M, 16, dsub] tensor")
+    return _p(codebooks), codebooks.shape[0] // 2, codebooks.shape[2]
+
+
+def ivf_pq4_tile(M):
+    """(S, R): the slots x rows of one work item of ``ivf_scan_pq4`` for ``M`` bytes per row (host arithmetic)"""
+    s, r = C.c_int(0), C.c_int(0)
+    call("cdml_ivf_pq4_tile", int(M), C.byref(s), C.byref(r))
+    return s.value, r.value
+
+
+def pq4_encode(x, codebooks, codes, dist=None):
+    """codes[r, b] (uint8 [n, >= M]; columns past M are not written) = code(2b) | code(2b + 1) << 4, code(m) the lowest of
+    subspace m's 16 codewords nearest to x[r, m dsub:(m + 1) dsub] (x fp32 [n, >= 2 M dsub], codebooks fp32 [2 M, 16, dsub]);
+    ``dist`` (fp32 [n, >= 2 M], optional) receives the attained minima per subspace."""
+    xp, xld = _mat(x)
+    cp, M, dsub = _codebooks4(codebooks)
+    n = x.shape[0]
+    if codes.dtype != torch.uint8 or codes.dim() != 2 or codes.stride(1) != 1 or codes.shape[0] < n or codes.shape[1] < M:
+        raise ValueError("codes must be a uint8 [n, >= M] tensor with unit inner stride")
+    if x.shape[1] < 2 * M * dsub:
+        raise ValueError("x rows must hold 2 M dsub = %d columns, got %d" % (2 * M * dsub, x.shape[1]))
+    dp, dld = (C.c_void_p(0), 0) if dist is None else _mat(dist)
+    if dist is not None and (dist.shape[0] < n or dist.shape[1] < 2 * M):
+        raise ValueError("dist must be a float32 [n, >= 2 M] tensor")
+    call("cdml_pq4_encode", xp, xld, n, cp, M, dsub, _p(codes), codes.stride(0), dp, dld, _stream())
+    return codes
+
+
+def pq4_lut(Q, codebooks, lut):
+    """lut[q, m, c] (fp32 [nq, 2 M, 16], contiguous) = the inner product of Q[q, m dsub:(m + 1) dsub] with codeword c of
+    subspace m."""
+    qp, qld = _mat(Q)
+    cp, M, dsub = _codebooks4(codebooks)
+    if Q.shape[1] < 2 * M * dsub:
+        raise ValueError("query rows must hold 2 M dsub = %d columns, got %d" % (2 * M * dsub, Q.shape[1]))
+    call("cdml_pq4_lut", qp, qld, Q.shape[0], cp, M, dsub, _vec(lut, torch.float32, Q.shape[0] * 2 * M * 16, "lut"), _stream())
+    return lut
+
+
+def ivf_scan_pq4(lut, slot_query, slot_start, slot_off, codes, list_start, tiles, scores):
+    """``ivf_scan_pq`` on 4-bit codes: for every tile (``ivf_pq4_tile(M)`` slots x rows) the sums over the row's bytes b of
+    lut[query, 2b, low nibble] + lut[query, 2b + 1, high nibble] (the pair added first) into the ragged score buffer.  lut fp32
+    [n_queries, 2 M, 16], codes uint8 [n_listed, M]."""
+    if lut.dim() != 3 or lut.shape[2] != 16 or lut.shape[1] % 2 or not lut.is_contiguous():
+        raise ValueError("lut must be a contiguous float32 [n_queries, 2 M, 16] tensor")
+    M = lut.shape[1] // 2
+    if codes.dtype != torch.uint8 or codes.dim() != 2 or codes.stride(1) != 1 or codes.shape[1] < M:
+        raise ValueError("codes must be a uint8 [n_listed, >= M] tensor with unit inner stride")
+    nlist = list_start.numel() - 1
+    n_slots = slot_query.numel()
+    if tiles.dim() != 2 or tiles.shape[1] != 4:
+        raise ValueError("tiles must be int32 [n_tiles, 4]")
+    call("cdml_ivf_scan_pq4", _p(lut, torch.float32), lut.shape[0], _vec(slot_query, torch.int32, 0, "slot_query"),
+         _vec(slot_start, torch.int32, nlist + 1, "slot_start"), _vec(slot_off, torch.int64, n_slots, "slot_off"), _p(codes),
+         codes.stride(0), _vec(list_start, torch.int32, nlist + 1, "list_start"), M, _vec(tiles, torch.int32, 4, "tiles"),
+         tiles.shape[0], _p(scores, torch.float32), _stream())
+    return scores
+
+
 # ---------------------------------------- threshold-filter scan of the IVF index (include/cdml_ivf_filter.h) ------
 def _ivf_filter(name, qp, qld, rp, rld, Q, slot_query, slot_start, q_sq, tau, cnt, rows, list_start, r_sq, ids, tiles, cand, cap):
     nlist = list_start.numel() - 1

@@ -7,6 +7,7 @@
     python tools/ivf_bench.py --storage f32 f16 --refine 128   # fp16 lists beside the fp32 ones over the same (centroids, assign)
     python tools/ivf_bench.py --storage f16 pq --pq-m 32 --refine 128   # product-quantised lists (32 bytes a row) beside the fp16 ones
     python tools/ivf_bench.py --storage pq --pq-m 16 32 --pq-residual 0 1 --refine 0 128   # residual codes beside the plain ones, per M
+    python tools/ivf_bench.py --storage f16 pq --pq-m 32 --pq-bits 8 4 --refine 0 128 --repeats 3   # 4-bit codes (two a byte, 16-entry tables) beside the 8-bit ones
     python tools/ivf_bench.py --scan buffer filter             # the threshold-filter scan beside the buffered one, same index, same call
 
 Per run one JSON line: build time by stage (one assignment, one centroid update, the whole build), search time by stage
@@ -17,7 +18,9 @@ the index's bytes, and recall@k for refine 0 and --refine.  With --storage pq (-
 same way: the codebooks trained once per nlist (pq_train_ms) and the catalogue encoded (pq_encode_ms), the stages with the lookup
 tables ("lut") and the table-lookup scan apart, the scan's lookups per second instead of FLOP/s.  With --pq-residual 1 the line of the
 residual pq index (codes of the row minus its list's centroid; the same (centroids, assign)) follows, with the slot scalars' launch
-("slot_dots") as a stage of its own.  With --scan filter a line "scan": "filter" follows every buffered
+("slot_dots") as a stage of its own.  With --pq-bits 8 4 the line of the 4-bit index (include/cdml_ivf_pq4.h; the same bytes per row, the
+same (centroids, assign)) follows the 8-bit one, with its own training and encoding times; --repeats N times every buffered search N
+times and reports the median per stage, with the min and max of the total and of the scan ("search_ms_spread", "scan_ms_spread").  With --scan filter a line "scan": "filter" follows every buffered
 line (under --score-bytes and under every --filter-score-bytes): the stages seed scan / seed merge / filter / merge_list /
 re-search, issued and useful TF/s of the seed scan and of the filter, the peak score + candidate bytes of a chunk, the candidates
 appended per query, the re-searched share, and whether (D, I) equal the buffered search's bit for bit.  Rows are Gaussian mixtures (n / 64 centres, noise 0.5) so that lists mean something.
@@ -59,11 +62,12 @@ def staged_search(idx, queries, k, nprobe, knn, ops, score_bytes, refine=0, base
     if f16:
         ms["round"] = 0.0
     pqr = pq and idx.pq_residual
+    pq4 = pq and idx.pq_bits == 4
     if pq:
         ms["lut"] = 0.0
         if pqr:
             ms["slot_dots"] = 0.0
-        tile["tile_slots"], tile["tile_rows"] = ops.ivf_pq_tile(idx.pq_m)
+        tile["tile_slots"], tile["tile_rows"] = (ops.ivf_pq4_tile if pq4 else ops.ivf_pq_tile)(idx.pq_m)
     if refine:
         ms["refine"] = 0.0
 
@@ -84,7 +88,7 @@ def staged_search(idx, queries, k, nprobe, knn, ops, score_bytes, refine=0, base
         p = probe.to(torch.int64)
         costs = torch.where(p >= 0, ld[p.clamp(min=0)], torch.zeros_like(p)).sum(1).cpu().numpy()
         if pq:
-            costs = costs + knn.pq_query_floats(idx.pq_m, nprobe if pqr else 0)
+            costs = costs + knn.pq_query_floats(idx.pq_m, nprobe if pqr else 0, idx.pq_bits)
         return knn.ivf_plan_chunks(costs, score_bytes, max_queries=(2 ** 31 - 1) // nprobe)
     t, chunks = timed(plan)
     ms["tables"] += t
@@ -105,10 +109,13 @@ def staged_search(idx, queries, k, nprobe, knn, ops, score_bytes, refine=0, base
             t, Qh = timed(rounded)
             ms["round"] += t
         if pq and tb["n_tiles"]:
-            lut = torch.empty((q1 - q0, idx.pq_m, 256), dtype=torch.float32, device=dev)
-            t, _ = timed(lambda: ops.pq_lut(Q[q0:q1], idx.codebooks, lut))
+            lut = torch.empty((q1 - q0, 2 * idx.pq_m, 16) if pq4 else (q1 - q0, idx.pq_m, 256), dtype=torch.float32, device=dev)
+            t, _ = timed(lambda: (ops.pq4_lut if pq4 else ops.pq_lut)(Q[q0:q1], idx.codebooks, lut))
             ms["lut"] += t
-            if pqr:
+            if pq4:
+                t, _ = timed(lambda: ops.ivf_scan_pq4(lut, tb["slot_query"], tb["slot_start"], tb["slot_off"], idx.codes,
+                                                      idx.list_start, tb["tiles"], scores))
+            elif pqr:
                 slot_base = torch.empty(tb["n_slots"], dtype=torch.float32, device=dev)
                 t, _ = timed(lambda: ops.ivf_slot_dots(Q[q0:q1], idx._C, tb["slot_query"], tb["slot_start"], slot_base))
                 ms["slot_dots"] += t
@@ -143,8 +150,9 @@ def staged_search(idx, queries, k, nprobe, knn, ops, score_bytes, refine=0, base
     stats = {"chunks": len(chunks), "tiles": tiles, "score_bytes": 4 * floats,
              "scan_flop_tiles": 2.0 * tiles * knn.IVF_TILE * knn.IVF_TILE * Dp, "scan_flop_useful": 2.0 * useful * Dp, "probe": probe}
     if pq:                                                    # lookups (one LDS gather + one add each) in place of FLOP
-        stats.update(scan_lookups_tiles=float(tiles) * tile["tile_slots"] * tile["tile_rows"] * idx.pq_m,
-                     scan_lookups_useful=float(useful) * idx.pq_m)
+        per_row = idx.pq_m * (2 if pq4 else 1)                # (4-bit: two gathers a byte)
+        stats.update(scan_lookups_tiles=float(tiles) * tile["tile_slots"] * tile["tile_rows"] * per_row,
+                     scan_lookups_useful=float(useful) * per_row)
     return ms, best_d[:, :k], I, stats
 
 
@@ -277,6 +285,9 @@ def main():
     ap.add_argument("--pq-m", type=int, nargs="*", default=[32], help="bytes per listed row of the pq index (one index per value)")
     ap.add_argument("--pq-residual", type=int, nargs="*", default=[0], choices=[0, 1],
                     help="0 = plain codes, 1 = codes of the row minus its list's centroid (one index per value)")
+    ap.add_argument("--pq-bits", type=int, nargs="*", default=[8], choices=[8, 4],
+                    help="8 = one code a byte (256 codewords), 4 = two codes a byte (16 codewords each); one index per value")
+    ap.add_argument("--repeats", type=int, default=1, help="timed runs of every buffered search (median per stage, spread of the total)")
     ap.add_argument("--refine", type=int, nargs="*", default=[0],
                     help="re-rank depths r of the f16 / pq index (k <= r <= 128); 0 = none, always run")
     ap.add_argument("--scan", nargs="*", default=["buffer"], choices=["buffer", "filter"],
@@ -318,24 +329,32 @@ def main():
                 indexes.append((idx, None))
             elif storage == "pq":                                                                         # the same (centroids, assign), pq codes
                 Xp = idx.prepare(x)
-                for pq_m in a.pq_m:
-                    for residual in a.pq_residual:
-                        res = {"centroids": idx._C, "assign": idx.assign} if residual else {}
-                        knn.pq_train(Xp[:4096], pq_m, iters=1)                                            # warm
-                        train_ms, (cb, obj) = timed(lambda: knn.pq_train(Xp, pq_m, **res))
-                        codes = torch.empty((n, pq_m), dtype=torch.uint8, device=dev)
-                        if residual:
-                            ops.pqr_encode(Xp[:4096], idx._C, idx.assign[:4096].contiguous(), cb, codes)  # warm
-                            encode_ms, _ = timed(lambda: ops.pqr_encode(Xp, idx._C, idx.assign, cb, codes))
-                        else:
-                            encode_ms, _ = timed(lambda: ops.pq_encode(Xp, cb, codes))
-                        del codes
-                        state = dict(idx.state_dict(), codebooks=cb, **({"pq_residual": True} if residual else {}))
-                        h = knn.IVFIndex.load_state_dict(state, x, device=dev, storage="pq")
-                        h.bench = {"pq_m": pq_m, "pq_residual": bool(residual), "pq_train_ms": round(train_ms, 2),
-                                   "pq_encode_ms": round(encode_ms, 3),
-                                   "pq_objective_last": float(obj[:, -1].sum()) if obj.shape[1] else None}
-                        indexes.append((h, Xp if refines != [0] else None))
+                for pq_m, bits, residual in [(m, b, r) for m in a.pq_m for b in a.pq_bits for r in a.pq_residual]:
+                    if bits == 4 and residual:                                                            # (not built: DESIGN.md section 10)
+                        print("ivf_bench: --pq-bits 4 with --pq-residual 1 is not built (the library refuses it by name): no "
+                              "line for pq_m = %d" % pq_m, file=sys.stderr, flush=True)
+                        continue
+                    res = {"centroids": idx._C, "assign": idx.assign} if residual else {}
+                    train = knn.pq4_train if bits == 4 else knn.pq_train
+                    train(Xp[:4096], pq_m, iters=1)                                                       # warm
+                    train_ms, (cb, obj) = timed(lambda: train(Xp, pq_m, **res))
+                    codes = torch.empty((n, pq_m), dtype=torch.uint8, device=dev)
+                    if bits == 4:
+                        ops.pq4_encode(Xp[:4096], cb, codes)                                              # warm
+                        encode_ms, _ = timed(lambda: ops.pq4_encode(Xp, cb, codes))
+                    elif residual:
+                        ops.pqr_encode(Xp[:4096], idx._C, idx.assign[:4096].contiguous(), cb, codes)  # warm
+                        encode_ms, _ = timed(lambda: ops.pqr_encode(Xp, idx._C, idx.assign, cb, codes))
+                    else:
+                        encode_ms, _ = timed(lambda: ops.pq_encode(Xp, cb, codes))
+                    del codes
+                    state = dict(idx.state_dict(), codebooks=cb, **({"pq_residual": True} if residual else {}),
+                                 **({"pq_bits": 4} if bits == 4 else {}))
+                    h = knn.IVFIndex.load_state_dict(state, x, device=dev, storage="pq")
+                    h.bench = {"pq_m": pq_m, "pq_bits": bits, "pq_residual": bool(residual), "pq_train_ms": round(train_ms, 2),
+                               "pq_encode_ms": round(encode_ms, 3),
+                               "pq_objective_last": float(obj[:, -1].sum()) if obj.shape[1] else None}
+                    indexes.append((h, Xp if refines != [0] else None))
             else:                                                                                         # the same (centroids, assign), fp16 lists
                 h = knn.IVFIndex.load_state_dict(idx.state_dict(), x, device=dev, storage="f16")
                 indexes.append((h, h.prepare(x) if refines != [0] else None))
@@ -351,6 +370,13 @@ def run_one(idx, base, refine, nprobe, nlist, x, k, n, a, knn, ops, sample, Ie, 
     kw = dict(refine=refine, base=base) if refine else {}
     staged_search(idx, x[:8192], k, nprobe, knn, ops, score_bytes, **kw)                                  # warm
     ms, Db, I, st = staged_search(idx, x, k, nprobe, knn, ops, score_bytes, **kw)                         # the self-search, all rows
+    spread = {}
+    if a.repeats > 1:                                                                                     # median per stage; (D, I) of the first run
+        runs = [ms] + [staged_search(idx, x, k, nprobe, knn, ops, score_bytes, **kw)[0] for _ in range(a.repeats - 1)]
+        ms = {s: sorted(r[s] for r in runs)[len(runs) // 2] for s in ms}
+        tot = [sum(r.values()) for r in runs]
+        spread = {"repeats": a.repeats, "search_ms_spread": [round(min(tot), 3), round(max(tot), 3)],
+                  "scan_ms_spread": [round(min(r["scan"] for r in runs), 3), round(max(r["scan"] for r in runs), 3)]}
     if "filter" in a.scan:
         run_filter(idx, refine, nprobe, nlist, x, k, n, a, knn, ops, score_bytes, Db, I, sum(ms.values()), ms, st, kw)
     if "buffer" not in a.scan:
@@ -372,7 +398,7 @@ def run_one(idx, base, refine, nprobe, nlist, x, k, n, a, knn, ops, sample, Ie, 
                      scan_glookups_useful=round(st["scan_lookups_useful"] / max(ms["scan"], 1e-9) / 1e6, 2),
                      list_bytes=idx.codes.numel())
     print(json.dumps({
-        **extra, "what": "ivf", "storage": idx.storage, "refine": refine, "index_bytes": index_bytes,
+        **extra, **spread, "what": "ivf", "storage": idx.storage, "refine": refine, "index_bytes": index_bytes,
         "n": n, "nq": n, "recall_queries": Ie.shape[0], "dim": a.dim, "k": k, "nlist": nlist, "nprobe": nprobe, "iters": a.iters,
         "build_ms": round(build_ms, 2), "assign_all_rows_ms": round(assign_ms, 3), "centroid_update_ms": round(update_ms, 3),
         "search_ms": round(total, 3), "stages_ms": {s: round(v, 3) for s, v in ms.items()},
