@@ -337,6 +337,14 @@ SIGNATURES_IVF_PQ4 = {
     "cdml_ivf_scan_pq4": (_i, [_p, _i, _p, _p, _p, _p, _i64, _p, _i, _p, _i, _p, _p]),
 }
 
+# name -> (restype, argtypes); must list every symbol include/cdml_ivf_update.h declares (the index's add / remove: the one
+# launch that writes the new lists, and the id -> position search)
+SIGNATURES_IVF_UPDATE = {
+    "cdml_ivf_lists_move": (_i, [_p, _i64, _p, _p, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _i64, _i, _p, _p, _p, _i, _i64, _p, _i64,
+                                 _p, _p, _i64, _p]),
+    "cdml_ivf_locate": (_i, [_p, _i64, _p, _i64, _p, _i64, _p, _i, _p, _p]),
+}
+
 _lib = None
 
 
@@ -360,7 +368,8 @@ def load_library():
                                + list(SIGNATURES_NEGW.items()) + list(SIGNATURES_F8.items()) + list(SIGNATURES_IVF.items())
                                + list(SIGNATURES_IVF_F16.items()) + list(SIGNATURES_IVF_FILTER.items())
                                + list(SIGNATURES_KNN_WRITER.items()) + list(SIGNATURES_IVF_PQ.items())
-                               + list(SIGNATURES_IVF_PQR.items()) + list(SIGNATURES_IVF_PQ4.items())):
+                               + list(SIGNATURES_IVF_PQR.items()) + list(SIGNATURES_IVF_PQ4.items())
+                               + list(SIGNATURES_IVF_UPDATE.items())):
         fn = getattr(lib, name)          # AttributeError if the ABI lost a symbol
         fn.restype = res
         fn.argtypes = args

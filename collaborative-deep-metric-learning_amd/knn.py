@@ -974,13 +974,20 @@ class IVFIndex:
 
     ``search(..., scan="filter")`` (include/cdml_ivf_filter.h) is the same search, bit for bit, with a
     score buffer for the first ``seed_probes`` probe columns only: the other columns append what is within the seeded
-    threshold to ``filter_cap`` candidate slots per query."""
+    threshold to ``filter_cap`` candidate slots per query.
+
+    The index can change after it is born (include/cdml_ivf_update.h): ``train`` (``build`` on a sample,
+    then ``reset``) gives an index that lists no row, ``add(rows)`` appends rows under new ids in blocks and merges them into the
+    lists in one launch, ``remove(ids)`` unlists rows (ids are stable: ``n_rows`` stays), ``locate`` / ``reconstruct`` find an
+    id's position and what is stored for it, and ``state_dict(lists=True)`` / ``load_state_dict(state)`` carry the lists
+    themselves, so that no step needs the whole catalogue as one fp32 matrix.  After any sequence of these the index equals
+    ``from_assignment`` of all rows ever added with its own ``assign``, bit for bit."""
 
     STORAGES = ("f32", "f16", "pq")
     _NORM_ROWS = 1 << 20        # rows per fp32 temporary when the squared norms of fp16 rows are taken
 
     def __init__(self):
-        raise TypeError("use IVFIndex.build, IVFIndex.from_assignment or IVFIndex.load_state_dict")
+        raise TypeError("use IVFIndex.build, IVFIndex.train, IVFIndex.from_assignment or IVFIndex.load_state_dict")
 
     # ---- construction ----
     @staticmethod
@@ -1037,12 +1044,10 @@ class IVFIndex:
 
     def _set_lists(self, X, C, assign):
         """the cluster-major lists of (X, assign); rows with a non-finite coordinate are unlisted whatever ``assign`` says"""
-        n, Dp = X.shape
-        Xh = X.to(torch.float16) if self.storage == "f16" else None           # round to nearest even; overflow -> inf
-        finite = torch.isfinite(X if Xh is None else Xh).all(1)
-        a = torch.where(finite, assign.to(device=X.device, dtype=torch.int64), torch.full((n,), -1, dtype=torch.int64, device=X.device))
-        listed = a >= 0
-        key = torch.where(listed, a, torch.full_like(a, self.nlist))
+        n = X.shape[0]
+        self._C = C
+        payload, r_sq, a = self._encode_block(X, assign.to(device=X.device))  # (an unlisted row's payload is computed and dropped)
+        key = torch.where(a >= 0, a, torch.full_like(a, self.nlist))
         order = torch.argsort(key, stable=True)               # ids ascend inside a list
         cnt = torch.bincount(key, minlength=self.nlist + 1)
         n_listed = n - int(cnt[self.nlist])
@@ -1054,27 +1059,8 @@ class IVFIndex:
         self.ids = order[:n_listed].to(torch.int32)
         self.list_start = start.to(torch.int32)
         self.list_len = cnt[:self.nlist].contiguous()
-        self._C = C
-        if self.storage == "pq":
-            codes = torch.empty((n, self.pq_m), dtype=torch.uint8, device=X.device)
-            if self.pq_residual:
-                ops.pqr_encode(X, C, a, self.codebooks, codes)
-            elif self.pq_bits == 4:
-                ops.pq4_encode(X, self.codebooks, codes)
-            else:
-                ops.pq_encode(X, self.codebooks, codes)       # (an unlisted row's codes are computed and dropped)
-            self.codes = codes.index_select(0, order[:n_listed])
-            self.r_sq = torch.zeros(n_listed, dtype=torch.float32, device=X.device)
-            for r0 in range(0, n_listed, self._NORM_ROWS):
-                part = self.decode(torch.arange(r0, min(r0 + self._NORM_ROWS, n_listed), device=X.device))
-                ops.row_sqnorm(part, Dp, self.r_sq[r0:r0 + self._NORM_ROWS])
-        elif self.storage == "f16":
-            self.rows = Xh.index_select(0, order[:n_listed])
-            self.r_sq = self._sqnorm_f16(self.rows)
-        else:
-            self.rows = X.index_select(0, order[:n_listed])
-            self.r_sq = torch.zeros(n_listed, dtype=torch.float32, device=X.device)
-            ops.row_sqnorm(self.rows, Dp, self.r_sq)
+        setattr(self, self._payload_name(), payload.index_select(0, order[:n_listed]))
+        self.r_sq = r_sq.index_select(0, order[:n_listed])
         self.centroids = C[:, :self.dim]
         self.n_rows, self.n_listed, self.n_unlisted = n, n_listed, n - n_listed
         return self
@@ -1085,13 +1071,18 @@ class IVFIndex:
         if self.storage != "pq":
             raise ValueError("decode belongs to an index with storage=\"pq\" (this one is %r)" % self.storage)
         pos = positions.to(device=self.device, dtype=torch.int64)
-        c = self.codes.index_select(0, pos)
-        c = (pq_unpack(c) if self.pq_bits == 4 else c).to(torch.int64)
-        m = torch.arange(c.shape[1], device=self.device)
-        out = self.codebooks[m[None, :], c].reshape(c.shape[0], -1)
+        lst = None
         if self.pq_residual:                              # the list of a position: the last c with list_start[c] <= position
             lst = torch.searchsorted(self.list_start[1:].to(torch.int64), pos, right=True)
-            out = self._C.index_select(0, lst) + out
+        return self._decode_codes(self.codes.index_select(0, pos), lst)
+
+    def _decode_codes(self, codes, lists):
+        """``decode`` of given code rows (uint8 [len, pq_m]); ``lists`` (int64 [len]; residual indexes only): each row's list"""
+        c = (pq_unpack(codes) if self.pq_bits == 4 else codes).to(torch.int64)
+        m = torch.arange(c.shape[1], device=self.device)
+        out = self.codebooks[m[None, :], c].reshape(c.shape[0], -1)
+        if self.pq_residual:
+            out = self._C.index_select(0, lists) + out
         return out
 
     @staticmethod
@@ -1211,9 +1202,11 @@ class IVFIndex:
         self.objective = torch.stack(objective).cpu() if objective else torch.empty(0, dtype=torch.float64)
         return self
 
-    def state_dict(self):
+    def state_dict(self, lists=False):
         """centroids + assign + the flags (CPU tensors); the lists are re-derived from the catalogue on load, bit for bit.
-        An f16 index adds ``"storage": "f16"``; an f32 index's keys are what they were (a missing key loads as "f32")."""
+        An f16 index adds ``"storage": "f16"``; an f32 index's keys are what they were (a missing key loads as "f32").
+        ``lists=True`` adds the lists themselves -- ``n_rows``, ``ids``, ``list_start``, ``r_sq`` and ``rows`` or ``codes`` -- so
+        that ``load_state_dict(state, base=None)`` needs no catalogue (an index built by ``add`` may never have had one)."""
         state = {"centroids": self.centroids.detach().cpu().clone(), "assign": self.assign.cpu().clone(), "l2_norm": self.l2_norm,
                  "precision": self.precision, "init_rows": self.init_rows.clone(), "objective": self.objective.clone()}
         if self.storage != "f32":
@@ -1225,13 +1218,22 @@ class IVFIndex:
                 state["pq_residual"] = True
             if self.pq_bits == 4:                             # (absent at 8: the state of an 8-bit index keeps its keys)
                 state["pq_bits"] = 4
+        if lists:
+            state["n_rows"] = int(self.n_rows)
+            state["ids"], state["list_start"], state["r_sq"] = self.ids.cpu().clone(), self.list_start.cpu().clone(), self.r_sq.cpu().clone()
+            payload = "codes" if self.storage == "pq" else "rows"
+            state[payload] = getattr(self, payload).cpu().clone()
         return state
 
     @classmethod
-    def load_state_dict(cls, state, base, device="cuda:0", storage=None):
+    def load_state_dict(cls, state, base=None, device="cuda:0", storage=None):
         """The index of ``state_dict()`` over the same catalogue ``base``.  ``storage`` (default: the state's, "f32" where
         it names none) may re-derive the lists in another format: centroids and assign do not depend on it.  "pq" needs
-        the state's codebooks (a state of a pq index); its codes are re-derived from ``base``, bit for bit."""
+        the state's codebooks (a state of a pq index); its codes are re-derived from ``base``, bit for bit.
+        ``base=None``: the lists are taken from the state as they are (``state_dict(lists=True)``), in the state's format;
+        a state without lists is refused by name."""
+        if base is None:
+            return cls._load_lists(state, device, storage)
         storage = cls._check_storage(state.get("storage", "f32") if storage is None else storage)
         kw = {}
         if storage == "pq":
@@ -1245,6 +1247,243 @@ class IVFIndex:
                                    precision=state["precision"], storage=storage, **kw)
         self.init_rows, self.objective = state["init_rows"].clone(), state["objective"].clone()
         return self
+
+    @classmethod
+    def _load_lists(cls, state, device, storage):
+        """``load_state_dict(state, base=None)``: the refusals by name, then the state's lists as they are"""
+        own = cls._check_storage(state.get("storage", "f32"))
+        payload = "codes" if own == "pq" else "rows"
+        missing = [k for k in ("n_rows", "ids", "list_start", "r_sq", payload) if k not in state]
+        if missing:
+            raise ValueError("load_state_dict(base=None) needs a state that carries its lists (state_dict(lists=True)): this one "
+                             "lacks %s; give base= (the catalogue) instead" % ", ".join(missing))
+        if storage is not None and cls._check_storage(storage) != own:
+            raise ValueError("load_state_dict(base=None) takes the lists in the state's format (%r): storage=%r needs base= to "
+                             "re-derive them" % (own, storage))
+        c = state["centroids"]
+        pq_m = bits = None
+        if own == "pq":
+            _, pq_m, bits = cls._check_codebooks(state["codebooks"], _round_up(c.shape[1], 32), state.get("pq_bits"))
+        self = cls._blank(c.shape[0], c.shape[1], state["l2_norm"], device, state["precision"], own, pq_m,
+                          bool(state.get("pq_residual", False)), 8 if bits is None else bits)
+        dev = self.device
+        if own == "pq":
+            self.codebooks = state["codebooks"].detach().to(dev).contiguous().clone()
+        self._C = _device_matrix(c, dev, 1, 32)
+        self.centroids = self._C[:, :self.dim]
+        self.assign = state["assign"].to(device=dev, dtype=torch.int64).clone()
+        self.ids = state["ids"].to(device=dev, dtype=torch.int32).clone()
+        self.list_start = state["list_start"].to(device=dev, dtype=torch.int32).clone()
+        self.list_len = (self.list_start[1:] - self.list_start[:-1]).to(torch.int64).contiguous()
+        self.r_sq = state["r_sq"].to(device=dev, dtype=torch.float32).clone()
+        setattr(self, payload, state[payload].to(dev).contiguous().clone())
+        self.n_rows, self.n_listed = int(state["n_rows"]), int(self.ids.numel())
+        self.n_unlisted = self.n_rows - self.n_listed
+        if tuple(self.assign.shape) != (self.n_rows,) or tuple(self.list_start.shape) != (self.nlist + 1,) \
+                or self.r_sq.numel() != self.n_listed or getattr(self, payload).shape[0] != self.n_listed:
+            raise ValueError("the state's lists disagree with each other (n_rows = %d, n_listed = %d)" % (self.n_rows, self.n_listed))
+        self.init_rows, self.objective = state["init_rows"].clone(), state["objective"].clone()
+        return self
+
+    # ---- train / add / remove (include/cdml_ivf_update.h; DESIGN.md section 9f.6) ----
+    @classmethod
+    def train(cls, sample, nlist, iters=10, seed=0, train_rows=None, l2_norm=True, device="cuda:0", precision="f32x3",
+              storage="f32", pq_m=None, pq_iters=None, pq_seed=None, pq_train_rows=None, pq_residual=False, pq_bits=8):
+        """``build(sample, nlist, ...)`` followed by ``reset()``: an index that knows its centroids (and codebooks) and lists no
+        row yet; ``add`` fills it.  ``train(sample, ...).add(sample)`` IS ``build(sample, ...)``, attribute for attribute."""
+        return cls.build(sample, nlist, iters=iters, seed=seed, train_rows=train_rows, l2_norm=l2_norm, device=device,
+                         precision=precision, storage=storage, pq_m=pq_m, pq_iters=pq_iters, pq_seed=pq_seed,
+                         pq_train_rows=pq_train_rows, pq_residual=pq_residual, pq_bits=pq_bits).reset()
+
+    def _payload_name(self):
+        return "codes" if self.storage == "pq" else "rows"
+
+    def _row_shape(self):
+        """(columns, dtype) of one payload row"""
+        Dp = _round_up(self.dim, 32)
+        return (self.pq_m, torch.uint8) if self.storage == "pq" else (Dp, torch.float16 if self.storage == "f16" else torch.float32)
+
+    def reset(self):
+        """Drop every row: n_rows = n_listed = 0, empty ids / payload / r_sq / assign, list_start all zero.  Centroids,
+        codebooks, init_rows, train_ids and the objectives stay.  Returns the index."""
+        dev = self.device
+        cols, dt = self._row_shape()
+        setattr(self, self._payload_name(), torch.empty((0, cols), dtype=dt, device=dev))
+        self.ids = torch.empty(0, dtype=torch.int32, device=dev)
+        self.r_sq = torch.empty(0, dtype=torch.float32, device=dev)
+        self.assign = torch.empty(0, dtype=torch.int64, device=dev)
+        self.list_start = torch.zeros(self.nlist + 1, dtype=torch.int32, device=dev)
+        self.list_len = torch.zeros(self.nlist, dtype=torch.int64, device=dev)
+        self.n_rows = self.n_listed = self.n_unlisted = 0
+        return self
+
+    def _check_listed(self):
+        if getattr(self, "n_listed", None) == 0:
+            raise ValueError("the index lists no row: add rows first (IVFIndex.add)")
+
+    def _check_ids(self, ids, what):
+        """int64 ids on the index's device; an id outside [0, n_rows) is refused by name (checked where the ids live)"""
+        q = ids if torch.is_tensor(ids) else torch.as_tensor(np.asarray(ids))
+        if q.dim() != 1 or q.is_floating_point() or q.dtype == torch.bool:
+            raise ValueError("%s takes an integer vector of catalogue ids" % what)
+        q = q.to(torch.int64)
+        if q.numel() and (int(q.min()) < 0 or int(q.max()) >= self.n_rows):
+            raise ValueError("%s: an id is outside [0, n_rows = %d) (got ids in [%d, %d])"
+                             % (what, self.n_rows, int(q.min()), int(q.max())))
+        return q.to(self.device).contiguous()
+
+    def _encode_block(self, X, a, stages=None):
+        """(payload [b, row], r_sq fp32 [b], a int64 [b] with -1 for an unlisted row) of one prepared block ``X`` whose nearest
+        centroids are ``a``: what the index stores per row, a function of the row and of the centroids / codebooks alone (which is
+        why ``_set_lists`` may take it for the whole catalogue and ``add`` chunk by chunk)"""
+        b, Dp = X.shape
+        dev = X.device
+        mark = (lambda name: None) if stages is None else stages
+        Xh = X.to(torch.float16) if self.storage == "f16" else None           # round to nearest even; overflow -> inf
+        finite = torch.isfinite(X if Xh is None else Xh).all(1)
+        a = torch.where(finite, a.to(torch.int64), torch.full((b,), -1, dtype=torch.int64, device=dev))
+        if self.storage == "pq":
+            codes = torch.empty((b, self.pq_m), dtype=torch.uint8, device=dev)
+            if self.pq_residual:
+                ops.pqr_encode(X, self._C, a, self.codebooks, codes)
+            elif self.pq_bits == 4:
+                ops.pq4_encode(X, self.codebooks, codes)
+            else:
+                ops.pq_encode(X, self.codebooks, codes)
+            mark("encode")
+            r_sq = torch.zeros(b, dtype=torch.float32, device=dev)
+            for r0 in range(0, b, self._NORM_ROWS):
+                lst = a[r0:r0 + self._NORM_ROWS].clamp(min=0) if self.pq_residual else None      # (an unlisted row's norm is dropped)
+                part = self._decode_codes(codes[r0:r0 + self._NORM_ROWS], lst)
+                ops.row_sqnorm(part, Dp, r_sq[r0:r0 + self._NORM_ROWS])
+            mark("r_sq")
+            return codes, r_sq, a
+        if self.storage == "f16":
+            mark("encode")
+            r_sq = self._sqnorm_f16(Xh)
+            mark("r_sq")
+            return Xh, r_sq, a
+        mark("encode")
+        r_sq = torch.zeros(b, dtype=torch.float32, device=dev)
+        ops.row_sqnorm(X, Dp, r_sq)
+        mark("r_sq")
+        return X, r_sq, a
+
+    def _move(self, old_pos, kept_start, payload, r_sq, order, add_start, id0, n_rows):
+        """the one launch of an update: new lists from the kept old rows (``old_pos``: None = all of them, in place) and the
+        chunk (``payload`` / ``r_sq`` / ``order`` / ``add_start``; None for a removal); ``n_rows`` = the ids consumed after it.
+        Out of place: the old arrays are freed when this returns, so the peak is twice the list bytes.  The index changes only
+        after the launch has been enqueued: an allocation that fails leaves it as it was."""
+        dev = self.device
+        name = self._payload_name()
+        cols, dt = self._row_shape()
+        zeros = torch.zeros(self.nlist + 1, dtype=torch.int32, device=dev)
+        add_start = zeros if add_start is None else add_start
+        new_start = kept_start + add_start
+        n_new = int(new_start[-1])                            # the host read
+        new_rows = torch.empty((n_new, cols), dtype=dt, device=dev)
+        new_ids = torch.empty(n_new, dtype=torch.int32, device=dev)
+        new_r_sq = torch.empty(n_new, dtype=torch.float32, device=dev)
+        if n_new:
+            ops.ivf_lists_move(getattr(self, name), self.ids, self.r_sq, old_pos, payload, r_sq, order, id0, kept_start, add_start,
+                               new_start, new_rows, new_ids, new_r_sq)
+        setattr(self, name, new_rows)
+        self.ids, self.r_sq, self.list_start = new_ids, new_r_sq, new_start
+        self.list_len = (new_start[1:] - new_start[:-1]).to(torch.int64).contiguous()
+        self.n_rows, self.n_listed, self.n_unlisted = n_rows, n_new, n_rows - n_new
+
+    def add(self, rows, block_rows=1 << 20, stages=None):
+        """Append ``rows`` ([m, D]; numpy, CPU or device tensor) as catalogue ids n_rows .. n_rows + m - 1; returns the first
+        new id.  In blocks of at most ``block_rows`` rows (the fp32 temporaries are block_rows x Dp) the rows are prepared,
+        assigned to their nearest centroid (``build``'s final assignment call), rounded / encoded and their r_sq taken as
+        ``from_assignment`` does; the chunk's payload is kept in the list format, and ONE launch (``ops.ivf_lists_move``)
+        merges it into the lists: a list = its old rows, then its new rows in chunk order.  A row with a non-finite
+        coordinate (storage "f16": an overflowing image) consumes its id and is unlisted.  The index then equals
+        ``from_assignment`` of all rows ever added with ``self.assign``, bit for bit.  Only the m keys of the chunk are sorted;
+        the lists are written out of place (peak: twice the list bytes).  ``stages`` (a callable, optional; tools/ivf_add_bench.py)
+        is called with a stage's name when its work has been enqueued."""
+        t = rows if torch.is_tensor(rows) else torch.as_tensor(np.asarray(rows, dtype=np.float32))
+        if t.dim() != 2 or t.shape[1] != self.dim:
+            raise ValueError("add: row / index dimension mismatch: rows must be [m, D = %d], got %s" % (self.dim, tuple(t.shape)))
+        m, block_rows = int(t.shape[0]), int(block_rows)
+        if m < 1:
+            raise ValueError("add needs m >= 1 rows, got %d" % m)
+        if block_rows < 1:
+            raise ValueError("block_rows must be >= 1, got %d" % block_rows)
+        id0 = int(self.n_rows)
+        if id0 + m > 2 ** 31 - 1:
+            raise ValueError("add: n_rows + m = %d exceeds 2^31 - 1 (catalogue ids are int32)" % (id0 + m))
+        dev = self.device
+        mark = (lambda name: None) if stages is None else stages
+        cols, dt = self._row_shape()
+        payload = torch.empty((m, cols), dtype=dt, device=dev)
+        r_sq = torch.empty(m, dtype=torch.float32, device=dev)
+        a = torch.empty(m, dtype=torch.int64, device=dev)
+        for b0 in range(0, m, block_rows):
+            b1 = min(b0 + block_rows, m)
+            Xb = t[b0:b1].to(device=dev, dtype=torch.float32)
+            mark("copy_in")
+            X = self._prepared(Xb, dev, self.l2_norm)
+            mark("prepare")
+            _, Ia = knn_search(self._C, X, 1, l2_norm=False, device=dev, precision=self.precision)
+            mark("assign")
+            payload[b0:b1], r_sq[b0:b1], a[b0:b1] = self._encode_block(X, Ia[:, 0], stages)
+        key = torch.where(a >= 0, a, torch.full_like(a, self.nlist))
+        order = torch.argsort(key, stable=True)               # the chunk alone: m keys
+        cnt = torch.bincount(key, minlength=self.nlist + 1)
+        add_start = torch.zeros(self.nlist + 1, dtype=torch.int32, device=dev)
+        add_start[1:] = torch.cumsum(cnt[:self.nlist], 0)
+        n_add = m - int(cnt[self.nlist])                      # the host read
+        assign = torch.cat([self.assign, a])
+        mark("tables")
+        self._move(None, self.list_start, payload, r_sq, order[:n_add].to(torch.int32), add_start, id0, id0 + m)
+        self.assign = assign
+        mark("move")
+        return id0
+
+    def locate(self, ids):
+        """int32 [len]: the position of every id of ``ids`` in the cluster-major lists (``ids[position] == id``), -1 for an
+        unlisted id.  An id outside [0, n_rows) is refused by name."""
+        q = self._check_ids(ids, "locate")
+        pos = torch.full((q.numel(),), -1, dtype=torch.int32, device=self.device)
+        if q.numel() and self.n_listed:
+            ops.ivf_locate(q, self.assign, self.ids, self.list_start, pos)
+        return pos
+
+    def reconstruct(self, ids):
+        """fp32 [len, Dp]: what the index stores for ``ids`` -- the listed row (fp16 widened), or for storage "pq" the
+        decoded row ``decode(locate(ids))``.  An unlisted id is refused by name."""
+        q = self._check_ids(ids, "reconstruct")
+        gone = self.assign.index_select(0, q.to(self.assign.device)) < 0
+        if bool(gone.any()):
+            raise ValueError("reconstruct: id %d is unlisted (removed, or a row with a non-finite coordinate): the index stores "
+                             "nothing for it" % int(q[torch.nonzero(gone)[0, 0]]))
+        pos = self.locate(q).to(torch.int64)
+        if self.storage == "pq":
+            return self.decode(pos)
+        return self.rows.index_select(0, pos).float()
+
+    def remove(self, ids):
+        """Unlist ``ids`` (an integer vector; duplicates and already-unlisted ids are allowed, an id outside [0, n_rows) is
+        refused by name); returns how many rows were listed and are no longer.  Ids are stable: n_rows stays, assign[id]
+        becomes -1, and the lists close up in ONE launch (``ops.ivf_lists_move`` over the kept positions).  The index then
+        equals ``from_assignment`` of the catalogue with the new ``assign``."""
+        q = self._check_ids(ids, "remove")
+        if q.numel() == 0 or self.n_listed == 0:
+            return 0
+        dev = self.device
+        pos = self.locate(q)
+        keep = torch.ones(self.n_listed, dtype=torch.bool, device=dev)
+        keep[pos[pos >= 0].to(torch.int64)] = False
+        cs = torch.zeros(self.n_listed + 1, dtype=torch.int64, device=dev)
+        cs[1:] = torch.cumsum(keep, 0)
+        kept_start = cs.index_select(0, self.list_start.to(torch.int64)).to(torch.int32)
+        n_removed = self.n_listed - int(cs[-1])               # the host read
+        if n_removed == 0:
+            return 0
+        self._move(torch.nonzero(keep).flatten().to(torch.int32), kept_start, None, None, None, None, 0, self.n_rows)
+        self.assign[q] = -1
+        return n_removed
 
     # ---- search ----
     def _check_queries(self, queries, nprobe, k=None):
@@ -1270,6 +1509,7 @@ class IVFIndex:
 
     def scanned_share(self, probe):
         """The mean share of the listed rows that a query of ``probe`` ([nq, nprobe] list ids, -1 = none) scores."""
+        self._check_listed()
         p = probe.to(device=self.device, dtype=torch.int64)
         rows = torch.where(p >= 0, self.list_len[p.clamp(min=0)], torch.zeros_like(p)).sum(1)
         return float(rows.double().mean()) / self.n_listed
@@ -1309,6 +1549,7 @@ class IVFIndex:
     def default_seed_probes(self, keep, nprobe):
         """min(nprobe, max(1, ceil(4 keep nlist / n_listed))): the probe columns whose lists hold 4 keep rows on average, so
         that short lists do not leave the seeded threshold at +inf.  Pure host arithmetic."""
+        self._check_listed()
         keep, nprobe = int(keep), int(nprobe)
         return min(nprobe, max(1, -(-4 * keep * self.nlist // self.n_listed)))
 
@@ -1518,6 +1759,7 @@ class IVFIndex:
         k, nprobe = int(k), int(nprobe)
         refine, base = self._check_refine(k, refine, base)
         self._check_scan(scan, filter_cap, seed_probes, nprobe)
+        self._check_listed()
         if probe is not None:
             probe = torch.as_tensor(probe)
             if tuple(probe.shape) != (queries.shape[0], nprobe) or probe.is_floating_point():

@@ -1943,6 +1943,56 @@ def ivf_scan_pq4(lut, slot_query, slot_start, slot_off, codes, list_start, tiles
     return scores
 
 
+# ---------------------------------------- add / remove of the IVF index (include/cdml_ivf_update.h) ------
+def _payload(t, what, allow_none=False):
+    """(pointer, stride in bytes, rows, row bytes) of a list payload: any 2-D tensor with unit inner stride (opaque bytes)"""
+    if t is None or (allow_none and t.shape[0] == 0):
+        if not allow_none:
+            raise ValueError("%s must be given" % what)
+        return C.c_void_p(0), 0, 0, None
+    if t.dim() != 2 or t.stride(1) != 1:
+        raise ValueError("%s must be a 2-D tensor with unit inner stride" % what)
+    es = t.element_size()
+    return _p(t), t.stride(0) * es, t.shape[0], t.shape[1] * es
+
+
+def ivf_lists_move(old_rows, old_ids, old_r_sq, old_pos, add_rows, add_r_sq, add_order, id0, kept_start, add_start, new_start,
+                   new_rows, new_ids, new_r_sq):
+    """The lists of an updated index in ONE launch (include/cdml_ivf_update.h): destination position o of list c takes kept old
+    row ``kept_start[c] + off`` (through ``old_pos``, int32, when it is not None) while off = o - new_start[c] is below the
+    list's kept count, else chunk row j = ``add_order[add_start[c] + off - kept]`` with the id ``id0 + j``.  The payloads
+    (``old_rows``, ``add_rows``, ``new_rows``) are 2-D tensors of one row length in bytes (a multiple of 8) and any row stride;
+    ids int32, r_sq fp32; the three start tables int32 [nlist + 1].  ``old_*`` may be None / empty (an index without rows),
+    ``add_*`` too (a removal).  Writes rows [0, new_rows.shape[0]) of the three new arrays."""
+    np_, nld, n_new, rb = _payload(new_rows, "new_rows")
+    op, old_ld, n_old, rb_o = _payload(old_rows, "old_rows", True)
+    ap, add_ld, n_chunk, rb_a = _payload(add_rows, "add_rows", True)
+    if (rb_o is not None and rb_o != rb) or (rb_a is not None and rb_a != rb):
+        raise ValueError("old, added and new payload rows must have one length in bytes (%s / %s / %s)" % (rb_o, rb_a, rb))
+    nlist = new_start.numel() - 1
+    n_kept = n_old if old_pos is None else old_pos.numel()
+    n_add = 0 if add_order is None else add_order.numel()
+    call("cdml_ivf_lists_move", op, old_ld, _vec(old_ids, torch.int32, n_old, "old_ids") if n_old else C.c_void_p(0),
+         _vec(old_r_sq, torch.float32, n_old, "old_r_sq") if n_old else C.c_void_p(0), n_old,
+         None if old_pos is None else _vec(old_pos, torch.int32, n_kept, "old_pos") if n_kept else C.c_void_p(0), n_kept,
+         ap, add_ld, _vec(add_r_sq, torch.float32, n_chunk, "add_r_sq") if n_chunk else C.c_void_p(0), n_chunk,
+         _vec(add_order, torch.int32, n_add, "add_order") if n_add else C.c_void_p(0), n_add, int(id0),
+         _vec(kept_start, torch.int32, nlist + 1, "kept_start"), _vec(add_start, torch.int32, nlist + 1, "add_start"),
+         _vec(new_start, torch.int32, nlist + 1, "new_start"), nlist, rb, np_, nld,
+         _vec(new_ids, torch.int32, n_new, "new_ids"), _vec(new_r_sq, torch.float32, n_new, "new_r_sq"), n_new, _stream())
+    return new_rows, new_ids, new_r_sq
+
+
+def ivf_locate(q_ids, assign, ids, list_start, pos):
+    """pos[q] (int32) = the position of catalogue id ``q_ids[q]`` (int64) in the cluster-major lists -- a binary search among
+    the ascending ``ids`` (int32) of list ``assign[id]`` (int64 [n_rows]) -- or -1 where the id is in no list."""
+    nq, nlist = q_ids.numel(), list_start.numel() - 1
+    call("cdml_ivf_locate", _vec(q_ids, torch.int64, nq, "q_ids"), nq, _vec(assign, torch.int64, 0, "assign"), assign.numel(),
+         _vec(ids, torch.int32, 0, "ids") if ids.numel() else C.c_void_p(0), ids.numel(),
+         _vec(list_start, torch.int32, nlist + 1, "list_start"), nlist, _vec(pos, torch.int32, nq, "pos"), _stream())
+    return pos
+
+
 # ---------------------------------------- threshold-filter scan of the IVF index (include/cdml_ivf_filter.h) ------
 def _ivf_filter(name, qp, qld, rp, rld, Q, slot_query, slot_start, q_sq, tau, cnt, rows, list_start, r_sq, ids, tiles, cand, cap):
     nlist = list_start.numel() - 1
