@@ -2,13 +2,16 @@
 // for 8 bits, but Ms = 2 M subspaces of 16 codewords, two codes a byte (the even subspace in the low nibble).  A query's
 // lookup table is Ms x 16 floats = 128 M bytes, an eighth of the 8-bit one.
 //
+// The encoders' codeword walk, the any-dsub lookup-table body, the argument checks and the dispatches are those of the 8-bit
+// forms (csrc/pq_common.h); k_pq4_lut and the scan keep their own text (DESIGN.md section 9f.7 says why).
+//
 //   k_pq4_encode     one block per (256 rows, byte): the 32 codewords of the byte's two subspaces in LDS, a lane owns its
-//                    row's two sub-vectors in registers, walks each subspace's 16 codewords in order (every lane reads the
-//                    same LDS address: a broadcast) and stores the WHOLE byte once.  dsub is a template parameter for {1, 2,
-//                    4, 8, 16, 32}; k_pq4_encode_any reads both operands from memory for any other dsub (the same sums in
-//                    the same order).
+//                    row's two sub-vectors in registers, walks each subspace's 16 codewords in order and stores the WHOLE byte
+//                    once.  dsub is a template parameter for {1, 2, 4, 8, 16, 32}; k_pq4_encode_any reads both operands from
+//                    memory for any other dsub (the same sums in the same order).
 //   k_pq4_lut        LUT[q][m][c] = <q_m, cb[m][c]>: one block per (64 queries, 16 subspaces), thread (m', c) keeps its
-//                    codeword in registers; a block stores 256 consecutive floats per query.
+//                    codeword in registers; a block stores 256 consecutive floats per query.  k_pq4_lut_any is
+//                    pq_lut_any_body<16> for a dsub outside the set.
 //   k_ivf_scan_pq4   the scan.  Work item = (list, S-slot tile, R-row tile) from the tile table, 512 lanes.  A lane keeps the
 //                    M code bytes of its two rows in M / 4 registers each (8-byte loads) across the tile's slots; the S =
 //                    min(16, 512 / M) lookup tables of the slots are staged into LDS with 16-byte accesses (128 M bytes
@@ -18,15 +21,13 @@
 //                    immediate offset, the group's table base is or-ed in (tables are 64-byte multiples).
 //                    A subspace's 16 entries are 16 consecutive dwords: the distinct addresses of a 32-lane group sit in
 //                    distinct banks, equal ones broadcast -- no bank conflict by construction.
-// The slot / offset tables and the store rules are k_ivf_scan's (csrc/ivf.hip).
-#include "common.h"
+#include "pq_common.h"
 #include "../../include/cdml_ivf_pq4.h"
 
 namespace cdml {
 namespace {
 
 constexpr int kCw4 = CDML_PQ4_CODEWORDS;
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // ---- encode --------------------------------------------------------------------------------------------------------
 template <int DS>
@@ -50,20 +51,9 @@ k_pq4_encode(const float *__restrict__ x, int64_t ldx, int64_t n, const float *_
   uint32_t byte = 0;
 #pragma unroll
   for (int h = 0; h < 2; ++h) {                // h = 0: subspace 2 b, the low nibble
-    float best = __builtin_inff();
-    uint32_t code = 0;
-#pragma unroll 4
-    for (int c = 0; c < kCw4; ++c) {
-      float d = 0.f;
-#pragma unroll
-      for (int j = 0; j < DS; ++j) {
-        const float diff = xv[h * DS + j] - sC[(h * kCw4 + c) * DS + j];
-        d = __builtin_fmaf(diff, diff, d);
-      }
-      if (d < best) { best = d; code = c; }    // ties keep the lower c; a NaN passes nothing
-    }
-    byte |= code << (4 * h);
-    if (dist) dist[r * ldd + 2 * b + h] = best;
+    const Nearest nn = nearest_codeword<kCw4, DS>(xv + h * DS, sC + h * kCw4 * DS);
+    byte |= (uint32_t)nn.code << (4 * h);
+    if (dist) dist[r * ldd + 2 * b + h] = nn.dist;
   }
   codes[r * ldc + b] = (uint8_t)byte;          // the whole byte, once
 }
@@ -77,26 +67,15 @@ k_pq4_encode_any(const float *__restrict__ x, int64_t ldx, int64_t n, const floa
   uint32_t byte = 0;
   for (int h = 0; h < 2; ++h) {
     const int m = 2 * b + h;
-    const float *cbm = cb + (int64_t)m * kCw4 * dsub;    // block-uniform addresses: scalar loads
-    const float *xr = x + r * ldx + (int64_t)m * dsub;
-    float best = __builtin_inff();
-    uint32_t code = 0;
-    for (int c = 0; c < kCw4; ++c) {
-      float d = 0.f;
-      for (int j = 0; j < dsub; ++j) {
-        const float diff = xr[j] - cbm[(int64_t)c * dsub + j];
-        d = __builtin_fmaf(diff, diff, d);
-      }
-      if (d < best) { best = d; code = c; }
-    }
-    byte |= code << (4 * h);
-    if (dist) dist[r * ldd + m] = best;
+    const Nearest nn = nearest_codeword_any<kCw4, false>(x + r * ldx + (int64_t)m * dsub, nullptr,
+                                                         cb + (int64_t)m * kCw4 * dsub, dsub);
+    byte |= (uint32_t)nn.code << (4 * h);
+    if (dist) dist[r * ldd + m] = nn.dist;
   }
   codes[r * ldc + b] = (uint8_t)byte;
 }
 
 // ---- lookup tables -------------------------------------------------------------------------------------------------
-constexpr int kLutQ = 64;                     // queries per block
 constexpr int kLutSub = 256 / kCw4;           // subspaces per block: thread t is (subspace t / 16, codeword t % 16)
 
 template <int DS>
@@ -120,21 +99,10 @@ k_pq4_lut(const float *__restrict__ Q, int64_t ldq, int nq, const float *__restr
 __global__ void __launch_bounds__(256)
 k_pq4_lut_any(const float *__restrict__ Q, int64_t ldq, int nq, const float *__restrict__ cb, int Ms, int dsub,
               float *__restrict__ lut) {
-  const int t = threadIdx.x, m = blockIdx.y * kLutSub + (t >> 4);
-  const float *cw = cb + ((int64_t)blockIdx.y * 256 + t) * dsub;
-  const int q1 = min(nq, ((int)blockIdx.x + 1) * kLutQ);
-  for (int q = blockIdx.x * kLutQ; q < q1; ++q) {
-    const float *qm = Q + (int64_t)q * ldq + (int64_t)m * dsub;
-    float acc = 0.f;
-    for (int j = 0; j < dsub; ++j) acc = __builtin_fmaf(qm[j], cw[j], acc);
-    lut[((int64_t)q * Ms + blockIdx.y * kLutSub) * kCw4 + t] = acc;
-  }
+  pq_lut_any_body<kCw4, unsigned>(Q, ldq, nq, cb, Ms, dsub, lut);
 }
 
 // ---- the scan --------------------------------------------------------------------------------------------------------
-constexpr int kScanThreads = 512;
-constexpr int kRowsPerLane = 2;
-constexpr int kTileRows = kScanThreads * kRowsPerLane;        // R = 1024
 constexpr int kMaxSlots = 16;
 constexpr int kLutBytes = 65536;              // LDS of a block's lookup tables, 128 M bytes each
 
@@ -201,6 +169,8 @@ k_ivf_scan_pq4(const float *__restrict__ lut, int n_queries, const int32_t *__re
   const int ns = min(S, nq_c - i0);
 
   // the lane's rows j0 + t and j0 + t + 512: their codes stay in registers across the tile's slots
+  // (this prologue is pq_common.h's ScanTile and load_row_codes written out: through them this kernel, which is steered to
+  // its register count, gets other machine code than it had -- DESIGN.md section 9f.7)
   uint32_t cw[kRowsPerLane][W];
 #pragma unroll
   for (int u = 0; u < kRowsPerLane; ++u) {
@@ -247,8 +217,6 @@ k_ivf_scan_pq4(const float *__restrict__ lut, int n_queries, const int32_t *__re
   }
 }
 
-bool pq_m_ok(int M) { return M >= CDML_PQ_M_MIN && M <= CDML_PQ_M_MAX && M % 8 == 0; }
-
 }  // namespace
 }  // namespace cdml
 
@@ -256,31 +224,18 @@ using namespace cdml;
 
 extern "C" int cdml_pq4_encode(const float *x, int64_t ldx, int64_t n, const float *codebooks, int M, int dsub, uint8_t *codes,
                                int64_t ldc, float *dist, int64_t ldd, cdml_stream_t stream) {
-  CDML_REQUIRE(x && codebooks && codes, CDML_E_BADARG, "pq4_encode: null pointer");
-  CDML_REQUIRE(n > 0, CDML_E_BADARG, "pq4_encode: n must be positive");
-  CDML_REQUIRE(pq_m_ok(M), CDML_E_BADARG, "pq4_encode: M must be a multiple of 8 in [%d, %d], got %d", CDML_PQ_M_MIN,
-               CDML_PQ_M_MAX, M);
-  CDML_REQUIRE(dsub >= 1, CDML_E_BADARG, "pq4_encode: dsub must be >= 1, got %d", dsub);
-  CDML_REQUIRE(ldx >= (int64_t)2 * M * dsub && ldc >= M && (!dist || ldd >= 2 * M), CDML_E_BADARG,
-               "pq4_encode: ldx >= 2 M dsub, ldc >= M and ldd >= 2 M (M = %d, dsub = %d)", M, dsub);
-  CDML_REQUIRE((n + 255) / 256 <= 0x7fffffff, CDML_E_UNSUPPORTED, "pq4_encode: too many rows");
+  if (int rc = check_pq_encode_args("pq4_encode", x && codebooks && codes, n, 1, M, dsub,
+                                    ldx >= (int64_t)2 * M * dsub && ldc >= M && (!dist || ldd >= 2 * M),
+                                    "ldx >= 2 M dsub, ldc >= M and ldd >= 2 M"))
+    return rc;
   const dim3 grid((unsigned)((n + 255) / 256), M);
   hipStream_t st = (hipStream_t)stream;
-#define CDML_PQ4_ENC(DS)                                                                                               \
-  case DS:                                                                                                             \
-    hipLaunchKernelGGL(k_pq4_encode<DS>, grid, dim3(256), 0, st, x, ldx, n, codebooks, codes, ldc, dist, ldd);         \
-    break;
-  switch (dsub) {
-    CDML_PQ4_ENC(1)
-    CDML_PQ4_ENC(2)
-    CDML_PQ4_ENC(4)
-    CDML_PQ4_ENC(8)
-    CDML_PQ4_ENC(16)
-    CDML_PQ4_ENC(32)
-    default:
-      hipLaunchKernelGGL(k_pq4_encode_any, grid, dim3(256), 0, st, x, ldx, n, codebooks, dsub, codes, ldc, dist, ldd);
-  }
-#undef CDML_PQ4_ENC
+  dispatch_dsub(
+      dsub,
+      [&](auto ds) {
+        hipLaunchKernelGGL(k_pq4_encode<decltype(ds)::value>, grid, dim3(256), 0, st, x, ldx, n, codebooks, codes, ldc, dist, ldd);
+      },
+      [&] { hipLaunchKernelGGL(k_pq4_encode_any, grid, dim3(256), 0, st, x, ldx, n, codebooks, dsub, codes, ldc, dist, ldd); });
   return check_launch("pq4_encode");
 }
 
@@ -288,36 +243,23 @@ extern "C" int cdml_pq4_lut(const float *Q, int64_t ldq, int nq, const float *co
                             cdml_stream_t stream) {
   CDML_REQUIRE(Q && codebooks && lut, CDML_E_BADARG, "pq4_lut: null pointer");
   CDML_REQUIRE(nq > 0, CDML_E_BADARG, "pq4_lut: nq must be positive");
-  CDML_REQUIRE(pq_m_ok(M), CDML_E_BADARG, "pq4_lut: M must be a multiple of 8 in [%d, %d], got %d", CDML_PQ_M_MIN,
-               CDML_PQ_M_MAX, M);
+  CDML_REQUIRE_PQ_M("pq4_lut", M);
   CDML_REQUIRE(dsub >= 1, CDML_E_BADARG, "pq4_lut: dsub must be >= 1, got %d", dsub);
   CDML_REQUIRE(ldq >= (int64_t)2 * M * dsub, CDML_E_BADARG, "pq4_lut: ldq >= 2 M dsub (M = %d, dsub = %d)", M, dsub);
   CDML_REQUIRE(aligned16(lut), CDML_E_ALIGN, "pq4_lut: lut must be 16-B aligned");
   const int Ms = 2 * M;                                   // a multiple of 16: Ms / kLutSub blocks of 16 subspaces
   const dim3 grid((nq + kLutQ - 1) / kLutQ, Ms / kLutSub);
   hipStream_t st = (hipStream_t)stream;
-#define CDML_PQ4_LUT(DS)                                                                                               \
-  case DS:                                                                                                             \
-    hipLaunchKernelGGL(k_pq4_lut<DS>, grid, dim3(256), 0, st, Q, ldq, nq, codebooks, Ms, lut);                         \
-    break;
-  switch (dsub) {
-    CDML_PQ4_LUT(1)
-    CDML_PQ4_LUT(2)
-    CDML_PQ4_LUT(4)
-    CDML_PQ4_LUT(8)
-    CDML_PQ4_LUT(16)
-    CDML_PQ4_LUT(32)
-    default:
-      hipLaunchKernelGGL(k_pq4_lut_any, grid, dim3(256), 0, st, Q, ldq, nq, codebooks, Ms, dsub, lut);
-  }
-#undef CDML_PQ4_LUT
+  dispatch_dsub(
+      dsub,
+      [&](auto ds) { hipLaunchKernelGGL(k_pq4_lut<decltype(ds)::value>, grid, dim3(256), 0, st, Q, ldq, nq, codebooks, Ms, lut); },
+      [&] { hipLaunchKernelGGL(k_pq4_lut_any, grid, dim3(256), 0, st, Q, ldq, nq, codebooks, Ms, dsub, lut); });
   return check_launch("pq4_lut");
 }
 
 extern "C" int cdml_ivf_pq4_tile(int M, int *slots, int *rows) {
   CDML_REQUIRE(slots && rows, CDML_E_BADARG, "ivf_pq4_tile: null pointer");
-  CDML_REQUIRE(pq_m_ok(M), CDML_E_BADARG, "ivf_pq4_tile: M must be a multiple of 8 in [%d, %d], got %d", CDML_PQ_M_MIN,
-               CDML_PQ_M_MAX, M);
+  CDML_REQUIRE_PQ_M("ivf_pq4_tile", M);
   *slots = scan_slots(M);
   *rows = kTileRows;
   return CDML_OK;
@@ -326,32 +268,14 @@ extern "C" int cdml_ivf_pq4_tile(int M, int *slots, int *rows) {
 extern "C" int cdml_ivf_scan_pq4(const float *lut, int n_queries, const int32_t *slot_query, const int32_t *slot_start,
                                  const int64_t *slot_off, const uint8_t *codes, int64_t ldc, const int32_t *list_start, int M,
                                  const int32_t *tiles, int n_tiles, float *scores, cdml_stream_t stream) {
-  CDML_REQUIRE(lut && slot_query && slot_start && slot_off && codes && list_start && tiles && scores, CDML_E_BADARG,
-               "ivf_scan_pq4: null pointer");
-  CDML_REQUIRE(n_queries > 0 && n_tiles > 0, CDML_E_BADARG, "ivf_scan_pq4: bad size");
-  CDML_REQUIRE(pq_m_ok(M), CDML_E_BADARG, "ivf_scan_pq4: M must be a multiple of 8 in [%d, %d], got %d", CDML_PQ_M_MIN,
-               CDML_PQ_M_MAX, M);
-  CDML_REQUIRE(ldc >= M, CDML_E_BADARG, "ivf_scan_pq4: ldc >= M (got %lld, M = %d)", (long long)ldc, M);
-  CDML_REQUIRE(aligned16(lut) && aligned16(scores) && aligned16(tiles) && !(ldc & 7) &&
-                   !(reinterpret_cast<uintptr_t>(codes) & 7),
-               CDML_E_ALIGN, "ivf_scan_pq4: lut, scores and tiles 16-B aligned, codes 8-B aligned, ldc a multiple of 8");
+  if (int rc = check_pq_scan_args("ivf_scan_pq4", lut && slot_query && slot_start && slot_off && codes && list_start && tiles && scores,
+                                  lut, n_queries, codes, ldc, M, tiles, n_tiles, scores))
+    return rc;
   const int4 *tl = reinterpret_cast<const int4 *>(tiles);
   hipStream_t st = (hipStream_t)stream;
-#define CDML_PQ4_SCAN(M8)                                                                                              \
-  case M8:                                                                                                             \
-    hipLaunchKernelGGL(k_ivf_scan_pq4<M8>, dim3(n_tiles), dim3(kScanThreads), 0, st, lut, n_queries, slot_query,       \
-                       slot_start, slot_off, codes, ldc, list_start, tl, scores);                                      \
-    break;
-  switch (M / 8) {
-    CDML_PQ4_SCAN(1)
-    CDML_PQ4_SCAN(2)
-    CDML_PQ4_SCAN(3)
-    CDML_PQ4_SCAN(4)
-    CDML_PQ4_SCAN(5)
-    CDML_PQ4_SCAN(6)
-    CDML_PQ4_SCAN(7)
-    CDML_PQ4_SCAN(8)
-  }
-#undef CDML_PQ4_SCAN
+  dispatch_m8(M, [&](auto m8) {
+    hipLaunchKernelGGL(k_ivf_scan_pq4<decltype(m8)::value>, dim3(n_tiles), dim3(kScanThreads), 0, st, lut, n_queries, slot_query,
+                       slot_start, slot_off, codes, ldc, list_start, tl, scores);
+  });
   return check_launch("ivf_scan_pq4");
 }

@@ -1,27 +1,26 @@
 // Residual product-quantised lists of the IVF index (include/cdml_ivf_pqr.h): the codes describe the
 // row minus its list's centroid.  The codebooks are shared by all lists, so the lookup table stays per query
 // (cdml_pq_lut, csrc/ivf_pq.hip) and the centroid's share of a score is one scalar per (query, probed list) slot.
+// The scan and the any-dsub encoder are the residual instances of the plain form's bodies (csrc/pq_common.h).
 //
 //   k_pqr_encode     k_pq_encode's launch (one block per (256 rows, subspace), the 256 codewords in LDS, a lane's sub-vector
 //                    in registers) with the centroid's sub-vector subtracted as the row's is loaded: the residual matrix is
 //                    never in memory.  A lane whose assign is outside [0, nlist) reads no centroid and writes codes 0,
-//                    dist +inf.  k_pqr_encode_any for a dsub outside {1, 2, 4, 8, 16, 32}.
+//                    dist +inf.  k_pqr_encode_any (pq_encode_any_body<true>) for a dsub outside {1, 2, 4, 8, 16, 32}.
 //   k_ivf_slot_dots  one wave per slot: b(q, c) = <q, C[c]> over Dp columns, lane-strided fmaf chains and a fixed xor fold
 //                    (the order is in the header).  grid = (nlist, Y): a list's 4 Y waves take its slots round robin, four
 //                    slots of a wave in flight at a time.
-//   k_ivf_scan_pqr   k_ivf_scan_pq's work item (copied from csrc/ivf_pq.hip, as csrc/ivf.hip copied knn.hip's list keeper)
-//                    with the accumulator of a slot starting from its base: one block-uniform load per slot and tile, one
-//                    add per (slot, row).
+//   k_ivf_scan_pqr   pq_scan_body<M8, true>: k_ivf_scan_pq's work item with the accumulator of a slot starting from its base
+//                    -- one block-uniform load per slot and tile, one add per (slot, row).
 #include <algorithm>
 
-#include "common.h"
+#include "pq_common.h"
 #include "../../include/cdml_ivf_pqr.h"
 
 namespace cdml {
 namespace {
 
 constexpr int kCw = CDML_PQ_CODEWORDS;
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // ---- encode --------------------------------------------------------------------------------------------------------
 template <int DS>
@@ -46,6 +45,7 @@ k_pqr_encode(const float *__restrict__ x, int64_t ldx, int64_t n, const float *_
     const float *cr = cen + a * ldcen + (int64_t)m * DS;
 #pragma unroll
     for (int j = 0; j < DS; ++j) ev[j] = xr[j] - cr[j];
+    // (nearest_codeword's walk, written out: the helper gives this kernel other machine code than it had -- DESIGN.md 9f.7)
 #pragma unroll 4
     for (int c = 0; c < kCw; ++c) {
       float d = 0.f;
@@ -65,27 +65,7 @@ __global__ void __launch_bounds__(256)
 k_pqr_encode_any(const float *__restrict__ x, int64_t ldx, int64_t n, const float *__restrict__ cen, int64_t ldcen, int nlist,
                  const int64_t *__restrict__ assign, const float *__restrict__ cb, int dsub, uint8_t *__restrict__ codes,
                  int64_t ldc, float *__restrict__ dist, int64_t ldd) {
-  const int m = blockIdx.y;
-  const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (r >= n) return;
-  const int64_t a = assign[r];
-  float best = __builtin_inff();
-  int code = 0;
-  if (a >= 0 && a < nlist) {
-    const float *cbm = cb + (int64_t)m * kCw * dsub;   // block-uniform addresses: scalar loads
-    const float *xr = x + r * ldx + (int64_t)m * dsub;
-    const float *cr = cen + a * ldcen + (int64_t)m * dsub;
-    for (int c = 0; c < kCw; ++c) {
-      float d = 0.f;
-      for (int j = 0; j < dsub; ++j) {
-        const float diff = (xr[j] - cr[j]) - cbm[(int64_t)c * dsub + j];
-        d = __builtin_fmaf(diff, diff, d);
-      }
-      if (d < best) { best = d; code = c; }
-    }
-  }
-  codes[r * ldc + m] = (uint8_t)code;
-  if (dist) dist[r * ldd + m] = best;
+  pq_encode_any_body<true>(x, ldx, n, cen, ldcen, nlist, assign, cb, dsub, codes, ldc, dist, ldd);
 }
 
 // ---- the slot scalars ----------------------------------------------------------------------------------------------
@@ -130,87 +110,14 @@ k_ivf_slot_dots(const float *__restrict__ Q, int64_t ldq, int n_queries, const f
   }
 }
 
-// ---- the ADC scan, from a base ---------------------------------------------------------------------------------------
-constexpr int kScanThreads = 512;
-constexpr int kRowsPerLane = 2;               // R = 512 * 2 = 1024 rows a tile (cdml_ivf_pq_tile)
-constexpr int kLutKiB = 64;                  // LDS of a block's lookup tables: S(M) = kLutKiB / M slots
-
 template <int M8>
 __global__ void __launch_bounds__(kScanThreads)
 k_ivf_scan_pqr(const float *__restrict__ lut, int n_queries, const int32_t *__restrict__ slot_query,
                const int32_t *__restrict__ slot_start, const int64_t *__restrict__ slot_off, const float *__restrict__ slot_base,
                const uint8_t *__restrict__ codes, int64_t ldc, const int32_t *__restrict__ list_start,
                const int4 *__restrict__ tiles, float *__restrict__ scores) {
-  constexpr int M = 8 * M8, S = kLutKiB / M, W = M / 4;
-  __shared__ __attribute__((aligned(16))) float sL[S * M * kCw];
-  const int t = threadIdx.x;
-
-  const int4 tl = tiles[blockIdx.x];
-  const int c = tl.x, i0 = tl.y, j0 = tl.z;
-  const int s0 = slot_start[c], nq_c = slot_start[c + 1] - s0;
-  const int r0 = list_start[c], len = list_start[c + 1] - r0;
-  if (i0 < 0 || j0 < 0 || i0 >= nq_c || j0 >= len) return;    // block-uniform, before any barrier
-  const int ld_c = (len + 3) & ~3;
-  const int ns = min(S, nq_c - i0);
-
-  // the lane's rows j0 + t and j0 + t + 512: their codes stay in registers across the tile's slots
-  uint32_t cw[kRowsPerLane][W];
-#pragma unroll
-  for (int u = 0; u < kRowsPerLane; ++u) {
-    const int j = j0 + t + kScanThreads * u;
-    if (j < len) {
-      const uint2 *p = reinterpret_cast<const uint2 *>(codes + (int64_t)(r0 + j) * ldc);
-#pragma unroll
-      for (int g = 0; g < M8; ++g) {
-        const uint2 v = p[g];
-        cw[u][2 * g] = v.x;
-        cw[u][2 * g + 1] = v.y;
-      }
-    } else {
-#pragma unroll
-      for (int g = 0; g < W; ++g) cw[u][g] = 0u;
-    }
-  }
-
-  // the slots' lookup tables: M * 256 floats each, M * 64 16-byte pieces over 512 lanes = M8 pieces a lane
-#pragma unroll
-  for (int s = 0; s < S; ++s) {
-    if (s < ns) {
-      const int q = min(max(slot_query[s0 + i0 + s], 0), n_queries - 1);
-      const f32x4 *src = reinterpret_cast<const f32x4 *>(lut + (int64_t)q * (M * kCw));
-      f32x4 *dst = reinterpret_cast<f32x4 *>(sL + s * (M * kCw));
-#pragma unroll
-      for (int g = 0; g < M8; ++g) dst[t + kScanThreads * g] = src[t + kScanThreads * g];
-    }
-  }
-  __syncthreads();
-
-  float *blk = scores + slot_off[s0];
-#pragma unroll
-  for (int s = 0; s < S; ++s) {
-    if (s < ns) {                                // block-uniform
-      const float *L = sL + s * (M * kCw);
-      const float base = slot_base[s0 + i0 + s]; // block-uniform: a scalar load
-      float acc[kRowsPerLane];
-#pragma unroll
-      for (int u = 0; u < kRowsPerLane; ++u) acc[u] = base;
-#pragma unroll
-      for (int m = 0; m < M; ++m)
-#pragma unroll
-        for (int u = 0; u < kRowsPerLane; ++u) {
-          const uint32_t code = (cw[u][m >> 2] >> (8 * (m & 3))) & 255u;
-          acc[u] = acc[u] + L[m * kCw + code];   // ascending m, from the base
-        }
-#pragma unroll
-      for (int u = 0; u < kRowsPerLane; ++u) {
-        const int j = j0 + t + kScanThreads * u;
-        if (j < len) blk[(int64_t)(i0 + s) * ld_c + j] = acc[u];
-      }
-    }
-  }
+  pq_scan_body<M8, true>(lut, n_queries, slot_query, slot_start, slot_off, slot_base, codes, ldc, list_start, tiles, scores);
 }
-
-bool pq_m_ok(int M) { return M >= CDML_PQ_M_MIN && M <= CDML_PQ_M_MAX && M % 8 == 0; }
 
 }  // namespace
 }  // namespace cdml
@@ -220,34 +127,23 @@ using namespace cdml;
 extern "C" int cdml_pqr_encode(const float *x, int64_t ldx, int64_t n, const float *centroids, int64_t ldcen, int nlist,
                                const int64_t *assign, const float *codebooks, int M, int dsub, uint8_t *codes, int64_t ldc,
                                float *dist, int64_t ldd, cdml_stream_t stream) {
-  CDML_REQUIRE(x && centroids && assign && codebooks && codes, CDML_E_BADARG, "pqr_encode: null pointer");
-  CDML_REQUIRE(n > 0, CDML_E_BADARG, "pqr_encode: n must be positive");
-  CDML_REQUIRE(nlist >= 1, CDML_E_BADARG, "pqr_encode: nlist must be >= 1, got %d", nlist);
-  CDML_REQUIRE(pq_m_ok(M), CDML_E_BADARG, "pqr_encode: M must be a multiple of 8 in [%d, %d], got %d", CDML_PQ_M_MIN,
-               CDML_PQ_M_MAX, M);
-  CDML_REQUIRE(dsub >= 1, CDML_E_BADARG, "pqr_encode: dsub must be >= 1, got %d", dsub);
-  CDML_REQUIRE(ldx >= (int64_t)M * dsub && ldcen >= (int64_t)M * dsub && ldc >= M && (!dist || ldd >= M), CDML_E_BADARG,
-               "pqr_encode: ldx >= M dsub, ldcen >= M dsub, ldc >= M and ldd >= M (M = %d, dsub = %d)", M, dsub);
-  CDML_REQUIRE((n + 255) / 256 <= 0x7fffffff, CDML_E_UNSUPPORTED, "pqr_encode: too many rows");
+  if (int rc = check_pq_encode_args(
+          "pqr_encode", x && centroids && assign && codebooks && codes, n, nlist, M, dsub,
+          ldx >= (int64_t)M * dsub && ldcen >= (int64_t)M * dsub && ldc >= M && (!dist || ldd >= M),
+          "ldx >= M dsub, ldcen >= M dsub, ldc >= M and ldd >= M"))
+    return rc;
   const dim3 grid((unsigned)((n + 255) / 256), M);
   hipStream_t st = (hipStream_t)stream;
-#define CDML_PQR_ENC(DS)                                                                                               \
-  case DS:                                                                                                             \
-    hipLaunchKernelGGL(k_pqr_encode<DS>, grid, dim3(256), 0, st, x, ldx, n, centroids, ldcen, nlist, assign, codebooks, \
-                       codes, ldc, dist, ldd);                                                                         \
-    break;
-  switch (dsub) {
-    CDML_PQR_ENC(1)
-    CDML_PQR_ENC(2)
-    CDML_PQR_ENC(4)
-    CDML_PQR_ENC(8)
-    CDML_PQR_ENC(16)
-    CDML_PQR_ENC(32)
-    default:
-      hipLaunchKernelGGL(k_pqr_encode_any, grid, dim3(256), 0, st, x, ldx, n, centroids, ldcen, nlist, assign, codebooks, dsub,
-                         codes, ldc, dist, ldd);
-  }
-#undef CDML_PQR_ENC
+  dispatch_dsub(
+      dsub,
+      [&](auto ds) {
+        hipLaunchKernelGGL(k_pqr_encode<decltype(ds)::value>, grid, dim3(256), 0, st, x, ldx, n, centroids, ldcen, nlist, assign,
+                           codebooks, codes, ldc, dist, ldd);
+      },
+      [&] {
+        hipLaunchKernelGGL(k_pqr_encode_any, grid, dim3(256), 0, st, x, ldx, n, centroids, ldcen, nlist, assign, codebooks, dsub,
+                           codes, ldc, dist, ldd);
+      });
   return check_launch("pqr_encode");
 }
 
@@ -269,32 +165,15 @@ extern "C" int cdml_ivf_scan_pqr(const float *lut, int n_queries, const int32_t 
                                  const int64_t *slot_off, const float *slot_base, const uint8_t *codes, int64_t ldc,
                                  const int32_t *list_start, int M, const int32_t *tiles, int n_tiles, float *scores,
                                  cdml_stream_t stream) {
-  CDML_REQUIRE(lut && slot_query && slot_start && slot_off && slot_base && codes && list_start && tiles && scores, CDML_E_BADARG,
-               "ivf_scan_pqr: null pointer");
-  CDML_REQUIRE(n_queries > 0 && n_tiles > 0, CDML_E_BADARG, "ivf_scan_pqr: bad size");
-  CDML_REQUIRE(pq_m_ok(M), CDML_E_BADARG, "ivf_scan_pqr: M must be a multiple of 8 in [%d, %d], got %d", CDML_PQ_M_MIN,
-               CDML_PQ_M_MAX, M);
-  CDML_REQUIRE(ldc >= M, CDML_E_BADARG, "ivf_scan_pqr: ldc >= M (got %lld, M = %d)", (long long)ldc, M);
-  CDML_REQUIRE(aligned16(lut) && aligned16(scores) && aligned16(tiles) && !(ldc & 7) &&
-                   !(reinterpret_cast<uintptr_t>(codes) & 7),
-               CDML_E_ALIGN, "ivf_scan_pqr: lut, scores and tiles 16-B aligned, codes 8-B aligned, ldc a multiple of 8");
+  if (int rc = check_pq_scan_args(
+          "ivf_scan_pqr", lut && slot_query && slot_start && slot_off && slot_base && codes && list_start && tiles && scores, lut,
+          n_queries, codes, ldc, M, tiles, n_tiles, scores))
+    return rc;
   const int4 *tl = reinterpret_cast<const int4 *>(tiles);
   hipStream_t st = (hipStream_t)stream;
-#define CDML_PQR_SCAN(M8)                                                                                              \
-  case M8:                                                                                                             \
-    hipLaunchKernelGGL(k_ivf_scan_pqr<M8>, dim3(n_tiles), dim3(kScanThreads), 0, st, lut, n_queries, slot_query,       \
-                       slot_start, slot_off, slot_base, codes, ldc, list_start, tl, scores);                           \
-    break;
-  switch (M / 8) {
-    CDML_PQR_SCAN(1)
-    CDML_PQR_SCAN(2)
-    CDML_PQR_SCAN(3)
-    CDML_PQR_SCAN(4)
-    CDML_PQR_SCAN(5)
-    CDML_PQR_SCAN(6)
-    CDML_PQR_SCAN(7)
-    CDML_PQR_SCAN(8)
-  }
-#undef CDML_PQR_SCAN
+  dispatch_m8(M, [&](auto m8) {
+    hipLaunchKernelGGL(k_ivf_scan_pqr<decltype(m8)::value>, dim3(n_tiles), dim3(kScanThreads), 0, st, lut, n_queries, slot_query,
+                       slot_start, slot_off, slot_base, codes, ldc, list_start, tl, scores);
+  });
   return check_launch("ivf_scan_pqr");
 }

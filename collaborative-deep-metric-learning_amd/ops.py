@@ -1768,11 +1768,51 @@ def _codebooks(codebooks):
     return _p(codebooks), codebooks.shape[0], codebooks.shape[2]
 
 
+def _pq_tile(symbol, M):
+    s, r = C.c_int(0), C.c_int(0)
+    call(symbol, int(M), C.byref(s), C.byref(r))
+    return s.value, r.value
+
+
+def _check_codes(codes, n, M):
+    if codes.dtype != torch.uint8 or codes.dim() != 2 or codes.stride(1) != 1 or codes.shape[0] < n or codes.shape[1] < M:
+        raise ValueError("codes must be a uint8 [n, >= M] tensor with unit inner stride")
+
+
+def _check_dist(dist, n, cols, cols_text):
+    """(pointer, leading dimension) of the optional ``dist`` of an encoder: fp32 [n, >= cols], one column per subspace"""
+    if dist is None:
+        return C.c_void_p(0), 0
+    dp, dld = _mat(dist)
+    if dist.shape[0] < n or dist.shape[1] < cols:
+        raise ValueError("dist must be a float32 [n, >= %s] tensor" % cols_text)
+    return dp, dld
+
+
+def _ivf_scan_pq_call(symbol, lut, codewords, slot_query, slot_start, slot_off, codes, list_start, tiles, scores, slot_base=None):
+    """The three table-lookup scans: ``lut`` fp32 [n_queries, subspaces, codewords] with one subspace per code byte for 256
+    codewords and two for 16; ``slot_base`` (fp32 [n_slots]) for the scan that starts its sums from it."""
+    per_byte = 1 if codewords == 256 else 2
+    if lut.dim() != 3 or lut.shape[2] != codewords or lut.shape[1] % per_byte or not lut.is_contiguous():
+        raise ValueError("lut must be a contiguous float32 [n_queries, %s, %d] tensor" % ("M" if per_byte == 1 else "2 M", codewords))
+    M = lut.shape[1] // per_byte
+    if codes.dtype != torch.uint8 or codes.dim() != 2 or codes.stride(1) != 1 or codes.shape[1] < M:
+        raise ValueError("codes must be a uint8 [n_listed, >= M] tensor with unit inner stride")
+    nlist = list_start.numel() - 1
+    n_slots = slot_query.numel()
+    if tiles.dim() != 2 or tiles.shape[1] != 4:
+        raise ValueError("tiles must be int32 [n_tiles, 4]")
+    base = () if slot_base is None else (_vec(slot_base, torch.float32, n_slots, "slot_base"),)
+    call(symbol, _p(lut, torch.float32), lut.shape[0], _vec(slot_query, torch.int32, 0, "slot_query"),
+         _vec(slot_start, torch.int32, nlist + 1, "slot_start"), _vec(slot_off, torch.int64, n_slots, "slot_off"), *base, _p(codes),
+         codes.stride(0), _vec(list_start, torch.int32, nlist + 1, "list_start"), M, _vec(tiles, torch.int32, 4, "tiles"),
+         tiles.shape[0], _p(scores, torch.float32), _stream())
+    return scores
+
+
 def ivf_pq_tile(M):
     """(S, R): the slots x rows of one work item of ``ivf_scan_pq`` for ``M`` bytes per row (host arithmetic)"""
-    s, r = C.c_int(0), C.c_int(0)
-    call("cdml_ivf_pq_tile", int(M), C.byref(s), C.byref(r))
-    return s.value, r.value
+    return _pq_tile("cdml_ivf_pq_tile", M)
 
 
 def pq_encode(x, codebooks, codes, dist=None):
@@ -1781,13 +1821,10 @@ def pq_encode(x, codebooks, codes, dist=None):
     xp, xld = _mat(x)
     cp, M, dsub = _codebooks(codebooks)
     n = x.shape[0]
-    if codes.dtype != torch.uint8 or codes.dim() != 2 or codes.stride(1) != 1 or codes.shape[0] < n or codes.shape[1] < M:
-        raise ValueError("codes must be a uint8 [n, >= M] tensor with unit inner stride")
+    _check_codes(codes, n, M)
     if x.shape[1] < M * dsub:
         raise ValueError("x rows must hold M dsub = %d columns, got %d" % (M * dsub, x.shape[1]))
-    dp, dld = (C.c_void_p(0), 0) if dist is None else _mat(dist)
-    if dist is not None and (dist.shape[0] < n or dist.shape[1] < M):
-        raise ValueError("dist must be a float32 [n, >= M] tensor")
+    dp, dld = _check_dist(dist, n, M, "M")
     call("cdml_pq_encode", xp, xld, n, cp, M, dsub, _p(codes), codes.stride(0), dp, dld, _stream())
     return codes
 
@@ -1807,20 +1844,7 @@ def ivf_scan_pq(lut, slot_query, slot_start, slot_off, codes, list_start, tiles,
     """``ivf_scan_f32`` by table lookup: for every tile (list c, slot tile, row tile; ``ivf_pq_tile(M)`` slots x rows) of
     ``tiles`` the sums over m of lut[query, m, codes[row, m]] into the ragged score buffer.  lut fp32 [n_queries, M, 256],
     codes uint8 [n_listed, M]."""
-    if lut.dim() != 3 or lut.shape[2] != 256 or not lut.is_contiguous():
-        raise ValueError("lut must be a contiguous float32 [n_queries, M, 256] tensor")
-    M = lut.shape[1]
-    if codes.dtype != torch.uint8 or codes.dim() != 2 or codes.stride(1) != 1 or codes.shape[1] < M:
-        raise ValueError("codes must be a uint8 [n_listed, >= M] tensor with unit inner stride")
-    nlist = list_start.numel() - 1
-    n_slots = slot_query.numel()
-    if tiles.dim() != 2 or tiles.shape[1] != 4:
-        raise ValueError("tiles must be int32 [n_tiles, 4]")
-    call("cdml_ivf_scan_pq", _p(lut, torch.float32), lut.shape[0], _vec(slot_query, torch.int32, 0, "slot_query"),
-         _vec(slot_start, torch.int32, nlist + 1, "slot_start"), _vec(slot_off, torch.int64, n_slots, "slot_off"), _p(codes),
-         codes.stride(0), _vec(list_start, torch.int32, nlist + 1, "list_start"), M, _vec(tiles, torch.int32, 4, "tiles"),
-         tiles.shape[0], _p(scores, torch.float32), _stream())
-    return scores
+    return _ivf_scan_pq_call("cdml_ivf_scan_pq", lut, 256, slot_query, slot_start, slot_off, codes, list_start, tiles, scores)
 
 
 # ---------------------------------------- residual product quantisation (include/cdml_ivf_pqr.h) ------
@@ -1831,14 +1855,11 @@ def pqr_encode(x, centroids, assign, codebooks, codes, dist=None):
     ep, eld = _mat(centroids)
     cp, M, dsub = _codebooks(codebooks)
     n = x.shape[0]
-    if codes.dtype != torch.uint8 or codes.dim() != 2 or codes.stride(1) != 1 or codes.shape[0] < n or codes.shape[1] < M:
-        raise ValueError("codes must be a uint8 [n, >= M] tensor with unit inner stride")
+    _check_codes(codes, n, M)
     if x.shape[1] < M * dsub or centroids.shape[1] < M * dsub:
         raise ValueError("x rows and centroids must hold M dsub = %d columns, got %d and %d"
                          % (M * dsub, x.shape[1], centroids.shape[1]))
-    dp, dld = (C.c_void_p(0), 0) if dist is None else _mat(dist)
-    if dist is not None and (dist.shape[0] < n or dist.shape[1] < M):
-        raise ValueError("dist must be a float32 [n, >= M] tensor")
+    dp, dld = _check_dist(dist, n, M, "M")
     call("cdml_pqr_encode", xp, xld, n, ep, eld, centroids.shape[0], _vec(assign, torch.int64, n, "assign"), cp, M, dsub,
          _p(codes), codes.stride(0), dp, dld, _stream())
     return codes
@@ -1862,21 +1883,8 @@ def ivf_slot_dots(Q, centroids, slot_query, slot_start, slot_base):
 def ivf_scan_pqr(lut, slot_query, slot_start, slot_off, slot_base, codes, list_start, tiles, scores):
     """``ivf_scan_pq`` with every slot's sums starting from ``slot_base[slot]`` (``ivf_slot_dots``): the scan of an index with
     ``pq_residual=True``."""
-    if lut.dim() != 3 or lut.shape[2] != 256 or not lut.is_contiguous():
-        raise ValueError("lut must be a contiguous float32 [n_queries, M, 256] tensor")
-    M = lut.shape[1]
-    if codes.dtype != torch.uint8 or codes.dim() != 2 or codes.stride(1) != 1 or codes.shape[1] < M:
-        raise ValueError("codes must be a uint8 [n_listed, >= M] tensor with unit inner stride")
-    nlist = list_start.numel() - 1
-    n_slots = slot_query.numel()
-    if tiles.dim() != 2 or tiles.shape[1] != 4:
-        raise ValueError("tiles must be int32 [n_tiles, 4]")
-    call("cdml_ivf_scan_pqr", _p(lut, torch.float32), lut.shape[0], _vec(slot_query, torch.int32, 0, "slot_query"),
-         _vec(slot_start, torch.int32, nlist + 1, "slot_start"), _vec(slot_off, torch.int64, n_slots, "slot_off"),
-         _vec(slot_base, torch.float32, n_slots, "slot_base"), _p(codes), codes.stride(0),
-         _vec(list_start, torch.int32, nlist + 1, "list_start"), M, _vec(tiles, torch.int32, 4, "tiles"), tiles.shape[0],
-         _p(scores, torch.float32), _stream())
-    return scores
+    return _ivf_scan_pq_call("cdml_ivf_scan_pqr", lut, 256, slot_query, slot_start, slot_off, codes, list_start, tiles, scores,
+                             slot_base=slot_base)
 
 
 # ---------------------------------------- 4-bit product quantisation (include/cdml_ivf_pq4.h) ------
@@ -1889,9 +1897,7 @@ def _codebooks4(codebooks):
 
 def ivf_pq4_tile(M):
     """(S, R): the slots x rows of one work item of ``ivf_scan_pq4`` for ``M`` bytes per row (host arithmetic)"""
-    s, r = C.c_int(0), C.c_int(0)
-    call("cdml_ivf_pq4_tile", int(M), C.byref(s), C.byref(r))
-    return s.value, r.value
+    return _pq_tile("cdml_ivf_pq4_tile", M)
 
 
 def pq4_encode(x, codebooks, codes, dist=None):
@@ -1901,13 +1907,10 @@ def pq4_encode(x, codebooks, codes, dist=None):
     xp, xld = _mat(x)
     cp, M, dsub = _codebooks4(codebooks)
     n = x.shape[0]
-    if codes.dtype != torch.uint8 or codes.dim() != 2 or codes.stride(1) != 1 or codes.shape[0] < n or codes.shape[1] < M:
-        raise ValueError("codes must be a uint8 [n, >= M] tensor with unit inner stride")
+    _check_codes(codes, n, M)
     if x.shape[1] < 2 * M * dsub:
         raise ValueError("x rows must hold 2 M dsub = %d columns, got %d" % (2 * M * dsub, x.shape[1]))
-    dp, dld = (C.c_void_p(0), 0) if dist is None else _mat(dist)
-    if dist is not None and (dist.shape[0] < n or dist.shape[1] < 2 * M):
-        raise ValueError("dist must be a float32 [n, >= 2 M] tensor")
+    dp, dld = _check_dist(dist, n, 2 * M, "2 M")
     call("cdml_pq4_encode", xp, xld, n, cp, M, dsub, _p(codes), codes.stride(0), dp, dld, _stream())
     return codes
 
@@ -1927,20 +1930,7 @@ def ivf_scan_pq4(lut, slot_query, slot_start, slot_off, codes, list_start, tiles
     """``ivf_scan_pq`` on 4-bit codes: for every tile (``ivf_pq4_tile(M)`` slots x rows) the sums over the row's bytes b of
     lut[query, 2b, low nibble] + lut[query, 2b + 1, high nibble] (the pair added first) into the ragged score buffer.  lut fp32
     [n_queries, 2 M, 16], codes uint8 [n_listed, M]."""
-    if lut.dim() != 3 or lut.shape[2] != 16 or lut.shape[1] % 2 or not lut.is_contiguous():
-        raise ValueError("lut must be a contiguous float32 [n_queries, 2 M, 16] tensor")
-    M = lut.shape[1] // 2
-    if codes.dtype != torch.uint8 or codes.dim() != 2 or codes.stride(1) != 1 or codes.shape[1] < M:
-        raise ValueError("codes must be a uint8 [n_listed, >= M] tensor with unit inner stride")
-    nlist = list_start.numel() - 1
-    n_slots = slot_query.numel()
-    if tiles.dim() != 2 or tiles.shape[1] != 4:
-        raise ValueError("tiles must be int32 [n_tiles, 4]")
-    call("cdml_ivf_scan_pq4", _p(lut, torch.float32), lut.shape[0], _vec(slot_query, torch.int32, 0, "slot_query"),
-         _vec(slot_start, torch.int32, nlist + 1, "slot_start"), _vec(slot_off, torch.int64, n_slots, "slot_off"), _p(codes),
-         codes.stride(0), _vec(list_start, torch.int32, nlist + 1, "list_start"), M, _vec(tiles, torch.int32, 4, "tiles"),
-         tiles.shape[0], _p(scores, torch.float32), _stream())
-    return scores
+    return _ivf_scan_pq_call("cdml_ivf_scan_pq4", lut, 16, slot_query, slot_start, slot_off, codes, list_start, tiles, scores)
 
 
 # ---------------------------------------- add / remove of the IVF index (include/cdml_ivf_update.h) ------

@@ -7,6 +7,7 @@ call sites, ``ivf_knn`` and ``export``.
 
 The Gaussian rows are l2-normalised HERE and indexed with l2_norm=False, so that the fp32 values the index encodes are bit
 for bit the ones the host model encodes."""
+import math
 import os
 import sys
 
@@ -128,12 +129,20 @@ def test_lossy_grid_codes_search_and_rerank_bit_for_bit(cd, D, M):
 
 
 # ---- tile edges ----------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("M", [8, 32])
+# every instance of the scan (M / 8 = 1..8); D = lcm(2 M, 32): M (8 bits) and 2 M (4 bits) divide the padded width, dsub is 1, 2 or 4
+TILE_MS = list(range(8, 72, 8))
+
+
+def tile_dim(M):
+    return math.lcm(2 * M, 32)
+
+
+@pytest.mark.parametrize("M", TILE_MS)
 def test_tile_edges(cd, M):
     """list lengths 0, 1, R - 1, R, R + 1, 2 R + 5 and lists probed by S - 1, S and S + 1 queries, against the int64 model"""
     S, R = cd.ops.ivf_pq_tile(M)
     assert (S, R) == (64 // M, 1024)
-    D = 64
+    D = tile_dim(M)
     dsub = D // M
     lens = (0, 1, R - 1, R, R + 1, 2 * R + 5)
     nlist, n = len(lens), sum(lens)

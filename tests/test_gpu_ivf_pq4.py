@@ -8,6 +8,7 @@ the refusals from the device-side call sites, ``ivf_knn`` and ``export``.
 
 The Gaussian rows are l2-normalised HERE and indexed with l2_norm=False, so that the fp32 values the index encodes are bit
 for bit the ones the host model encodes."""
+import math
 import os
 import sys
 
@@ -133,13 +134,21 @@ def test_lossy_grid_codes_search_and_rerank_bit_for_bit(cd, D, M):
 
 
 # ---- tile edges ----------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("M", [8, 32])
+# every instance of the scan (M / 8 = 1..8); D = lcm(2 M, 32): M (8 bits) and 2 M (4 bits) divide the padded width, dsub is 1, 2 or 4
+TILE_MS = list(range(8, 72, 8))
+
+
+def tile_dim(M):
+    return math.lcm(2 * M, 32)
+
+
+@pytest.mark.parametrize("M", TILE_MS)
 def test_tile_edges(cd, M):
     """list lengths 0, 1, R - 1, R, R + 1, 2 R + 5 and lists probed by S - 1, S, S + 1 and S + 2 queries, against the int64
     model"""
     S, R = cd.ops.ivf_pq4_tile(M)
     assert (S, R) == (min(16, 512 // M), 1024)
-    D, Ms = 64, 2 * M
+    D, Ms = tile_dim(M), 2 * M
     dsub = D // Ms
     lens = (0, 1, R - 1, R, R + 1, 2 * R + 5)
     nlist, n = len(lens), sum(lens)

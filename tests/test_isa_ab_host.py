@@ -64,6 +64,18 @@ def test_changed_instruction_differs():
     assert [ln.split()[0] for ln in report] == ["identical", "DIFFERS"]
 
 
+def test_differs_says_which_descriptor_lines_and_opcode_counts():
+    b = _file([_kernel("_Z1aILb1ELi3EEv", 0, add="v_add_u32_e32 v1, v0, v1\n\tds_read_b32 v2, v1\n\ts_nop 0", vgpr=43),
+               _kernel("_Z1bv", 1, add="v_mul_f32_e32 v1, v0, v0")])
+    report, ok = isa_ab.compare(isa_ab.kernels(A), isa_ab.kernels(b))
+    assert not ok and len(report) == 2
+    more = report[1].split("\n")[1:]
+    assert [ln.strip() for ln in more] == ["descriptor: .amdhsa_next_free_vgpr 42 -> 43", "opcodes: ds_read_b32 0 -> 1"]   # (no s_nop)
+    same = _file([_kernel("_Z1aILb1ELi3EEv", 0, add="s_nop 0"), _kernel("_Z1bv", 1, add="v_mul_f32_e32 v1, v0, v0")])
+    more = isa_ab.compare(isa_ab.kernels(A), isa_ab.kernels(same))[0][1].split("\n")[1:]
+    assert [ln.strip() for ln in more] == ["descriptor: the same", "opcodes: v_add_u32_e32 1 -> 0"]
+
+
 def test_changed_descriptor_field_differs():
     assert not _same(A, _file([_kernel("_Z1aILb1ELi3EEv", 0, vgpr=43), _kernel("_Z1bv", 1, add="v_mul_f32_e32 v1, v0, v0")]))
 

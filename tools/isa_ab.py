@@ -13,6 +13,8 @@ the code differing is canonicalised: the kernel's own mangled name, the __hip_cu
 number inside .LBB<n>_<m> / .Lfunc_end<n> labels.  The two trees are compared as MULTISETS of kernel bodies -- a refactor
 may rename template arguments, so names are reported and not matched -- unless --names asks for it: a benchmark or a
 profile that finds its kernels by name then needs the two trees' multisets of demangled names (llvm-cxxfilt) equal as well.
+For a kernel that DIFFERS the report adds the descriptor lines that differ and the difference of the two kernels' counts of
+v_ / ds_ / global_ / buffer_ opcodes: what a change that is accepted on measurements has to show.
 Host tool: no GPU.  Exit status 0 = every kernel identical and the counts equal (and, with --names, the names)."""
 import argparse
 import collections
@@ -63,6 +65,26 @@ def kernels(asm):
     return found
 
 
+def split_body(k):
+    """(instruction lines, descriptor lines) of a Kernel"""
+    body = k.body.split("\n")
+    cut = body.index(".amdhsa_kernel @KERNEL")
+    return [c for c in body[:cut] if not c.startswith(".") and not c.endswith(":")], body[cut + 1:-1]
+
+
+def differences(a, b):
+    """Report lines on two kernels whose bodies differ: the descriptor lines that differ, and the difference of their counts
+    of vector, LDS and memory opcodes (scalar code and branches left out: address arithmetic moves freely between the two)."""
+    (ca, da), (cb, db) = split_body(a), split_body(b)
+    fa, fb = (dict(ln.split(None, 1) for ln in d if " " in ln) for d in (da, db))
+    out = ["    descriptor: %s %s -> %s" % (key, fa.get(key, "(none)"), fb.get(key, "(none)"))
+           for key in sorted(set(fa) | set(fb)) if fa.get(key) != fb.get(key)] or ["    descriptor: the same"]
+    na, nb = (collections.Counter(c.split()[0] for c in code if c.startswith(("v_", "ds_", "global_", "buffer_"))) for code in (ca, cb))
+    out += ["    opcodes: " + (", ".join("%s %d -> %d" % (op, na[op], nb[op]) for op in sorted(set(na) | set(nb)) if na[op] != nb[op])
+                               or "the same counts of v_ / ds_ / global_ / buffer_ opcodes")]
+    return out
+
+
 def compare(a, b):
     """(report lines, ok) for two lists of Kernel compared as multisets of bodies."""
     rest = collections.defaultdict(list)
@@ -82,6 +104,8 @@ def compare(a, b):
         if o is not None:
             left.remove(o)
         report.append("DIFFERS    %6d instr  %s  !=  %s" % (k.n_instr, k.name, "%s (%d instr)" % (o.name, o.n_instr) if o else "(missing)"))
+        if o is not None:                                  # (further lines of the same report entry)
+            report[-1] += "".join("\n  " + ln for ln in differences(k, o))
         ok = False
     for o in left:
         report.append("DIFFERS    %6d instr  (missing)  !=  %s" % (o.n_instr, o.name))
