@@ -345,6 +345,13 @@ SIGNATURES_IVF_UPDATE = {
     "cdml_ivf_locate": (_i, [_p, _i64, _p, _i64, _p, _i64, _p, _i, _p, _p]),
 }
 
+# name -> (restype, argtypes); must list every symbol include/cdml_ivf_range.h declares (the filter scan over 8-bit
+# product-quantised lists: the scans' arguments with the filter's candidate set in place of the score buffer)
+SIGNATURES_IVF_RANGE = {
+    "cdml_ivf_filter_pq": (_i, [_p, _i, _p, _p, _p, _p, _p, _p, _i64, _p, _p, _p, _i, _p, _i, _p, _i, _p]),
+    "cdml_ivf_filter_pqr": (_i, [_p, _i, _p, _p, _p, _p, _p, _p, _p, _i64, _p, _p, _p, _i, _p, _i, _p, _i, _p]),
+}
+
 _lib = None
 
 
@@ -369,7 +376,7 @@ def load_library():
                                + list(SIGNATURES_IVF_F16.items()) + list(SIGNATURES_IVF_FILTER.items())
                                + list(SIGNATURES_KNN_WRITER.items()) + list(SIGNATURES_IVF_PQ.items())
                                + list(SIGNATURES_IVF_PQR.items()) + list(SIGNATURES_IVF_PQ4.items())
-                               + list(SIGNATURES_IVF_UPDATE.items())):
+                               + list(SIGNATURES_IVF_UPDATE.items()) + list(SIGNATURES_IVF_RANGE.items())):
         fn = getattr(lib, name)          # AttributeError if the ABI lost a symbol
         fn.restype = res
         fn.argtypes = args

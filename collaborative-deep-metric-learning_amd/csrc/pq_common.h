@@ -162,12 +162,21 @@ constexpr int kLutKiB = 64;                   // LDS of a block's lookup tables:
 // and per slot and row does M ds_read_b32 gathers and the adds in ascending m -- from the first term, or with kBase from
 // slot_base[slot] (block-uniform: a scalar load).  The order of the additions is the contract of the two headers.  The gather
 // address is 256 m + code: the bank is code mod 32, random; nothing is done about it (DESIGN.md section 9f.3 says why).
-template <int M8, bool kBase>
+//
+// What becomes of a slot's sums is the body's last step.  The buffered scans store them (Out = ScoreStore: the text below, as
+// it always stood -- handing that store to a functor too moved instructions of k_ivf_scan_pq / _pqr).
+// Any other Out (the filter's append, csrc/ivf_range.hip) takes no slot_off / scores (null) and is called instead:
+// out.begin(tile, t) once, behind the barrier that publishes the tables, then out.slot(tile, s, t, acc) per slot with the lane's
+// two sums (rows tile.j0 + t and + 512; a row past the list's end has the sums of code 0: the step masks it).
+struct ScoreStore {};
+
+template <int M8, bool kBase, class Out = ScoreStore>
 __device__ __forceinline__ void pq_scan_body(const float *__restrict__ lut, int n_queries, const int32_t *__restrict__ slot_query,
                                              const int32_t *__restrict__ slot_start, const int64_t *__restrict__ slot_off,
                                              const float *__restrict__ slot_base, const uint8_t *__restrict__ codes, int64_t ldc,
                                              const int32_t *__restrict__ list_start, const int4 *__restrict__ tiles,
-                                             float *__restrict__ scores) {
+                                             float *__restrict__ scores, Out out = Out()) {
+  constexpr bool kStore = std::is_same<Out, ScoreStore>::value;
   constexpr int kCw = CDML_PQ_CODEWORDS;
   constexpr int M = 8 * M8, S = kLutKiB / M, W = M / 4;
   __shared__ __attribute__((aligned(16))) float sL[S * M * kCw];
@@ -195,7 +204,9 @@ __device__ __forceinline__ void pq_scan_body(const float *__restrict__ lut, int 
   }
   __syncthreads();
 
-  float *blk = scores + slot_off[s0];
+  float *blk = nullptr;
+  if constexpr (kStore) blk = scores + slot_off[s0];
+  else out.begin(tile, t);
 #pragma unroll
   for (int s = 0; s < S; ++s) {
     if (s < ns) {                                // block-uniform
@@ -214,10 +225,14 @@ __device__ __forceinline__ void pq_scan_body(const float *__restrict__ lut, int 
           const float v = L[m * kCw + code];
           acc[u] = !kBase && m == 0 ? v : acc[u] + v;
         }
+      if constexpr (kStore) {
 #pragma unroll
-      for (int u = 0; u < kRowsPerLane; ++u) {
-        const int j = j0 + t + kScanThreads * u;
-        if (j < len) blk[(int64_t)(i0 + s) * ld_c + j] = acc[u];
+        for (int u = 0; u < kRowsPerLane; ++u) {
+          const int j = j0 + t + kScanThreads * u;
+          if (j < len) blk[(int64_t)(i0 + s) * ld_c + j] = acc[u];
+        }
+      } else {
+        out.slot(tile, s, t, acc);
       }
     }
   }

@@ -1496,6 +1496,17 @@ class IVFIndex:
         if len(shape) != 2 or shape[1] != self.dim:
             raise ValueError("query / index dimension mismatch: queries must be [nq, D = %d], got %s" % (self.dim, shape))
 
+    def _check_probe(self, probe, nq, nprobe):
+        """a given probe table as a tensor (None stays None): the refusals, by name"""
+        if probe is None:
+            return None
+        probe = torch.as_tensor(probe)
+        if tuple(probe.shape) != (nq, nprobe) or probe.is_floating_point():
+            raise ValueError("probe must be an integer [nq = %d, nprobe = %d] table" % (nq, nprobe))
+        if probe.numel() and (int(probe.min()) < -1 or int(probe.max()) >= self.nlist):
+            raise ValueError("probe ids must lie in [-1, nlist = %d)" % self.nlist)
+        return probe
+
     def _probes(self, Q, nprobe):
         _, I = knn_search(self._C, Q, int(nprobe), l2_norm=False, device=self.device, precision=self.precision)
         return I
@@ -1760,12 +1771,7 @@ class IVFIndex:
         refine, base = self._check_refine(k, refine, base)
         self._check_scan(scan, filter_cap, seed_probes, nprobe)
         self._check_listed()
-        if probe is not None:
-            probe = torch.as_tensor(probe)
-            if tuple(probe.shape) != (queries.shape[0], nprobe) or probe.is_floating_point():
-                raise ValueError("probe must be an integer [nq = %d, nprobe = %d] table" % (queries.shape[0], nprobe))
-            if probe.numel() and (int(probe.min()) < -1 or int(probe.max()) >= self.nlist):
-                raise ValueError("probe ids must lie in [-1, nlist = %d)" % self.nlist)
+        probe = self._check_probe(probe, queries.shape[0], nprobe)
         t = queries if torch.is_tensor(queries) else torch.as_tensor(np.asarray(queries, dtype=np.float32))
         dev = self.device
         f16 = self.storage == "f16"
@@ -1801,3 +1807,215 @@ class IVFIndex:
         I = best_i[:, :k].to(torch.int64)
         I[I == 0x7fffffff] = -1
         return best_d[:, :k].contiguous(), I
+
+    # ---- range search ----
+    RANGE_CAP = 256             # default candidate slots per query of ``range_search``'s first pass (a tuning choice, not a gate)
+
+    def _check_range_cap(self, range_cap):
+        if range_cap is None:
+            return self.RANGE_CAP
+        c = int(range_cap)
+        if isinstance(range_cap, bool) or c != range_cap or not self.FILTER_CAP_MIN <= c <= self.FILTER_CAP_MAX or c & (c - 1):
+            raise ValueError("range_cap must be a power of two in [%d, %d], got %r"
+                             % (self.FILTER_CAP_MIN, self.FILTER_CAP_MAX, range_cap))
+        return c
+
+    def range_costs(self, nq, nprobe, cap):
+        """int64 ndarray [nq]: a query's floats in a chunk of ``range_search`` = 2 ``cap`` (its candidate slots, 8 B each) and,
+        on storage "pq", its lookup table (and the ``nprobe`` slot scalars of a residual index).  Pure host arithmetic."""
+        own = 2 * int(cap)
+        if self.storage == "pq":
+            own += pq_query_floats(self.pq_m, int(nprobe) if self.pq_residual else 0)
+        return np.full(int(nq), own, dtype=np.int64)
+
+    def _range_plan(self, nq, nprobe, cap, result_bytes):
+        """the chunks of one pass of ``range_search`` over ``nq`` queries with ``cap`` slots each; a budget below one query's own
+        bytes is refused by name, before the launch"""
+        costs = self.range_costs(nq, nprobe, cap)
+        if nq and 4 * int(costs[0]) > int(result_bytes):
+            raise ValueError("result_bytes = %d is less than the %d bytes of one query's %d candidate slots%s: raise result_bytes"
+                             % (int(result_bytes), 4 * int(costs[0]), int(cap),
+                                " and lookup table" if self.storage == "pq" else ""))
+        return ivf_plan_chunks(costs, result_bytes, max_queries=(2 ** 31 - 1) // int(nprobe))
+
+    def _range_filter(self, Qc, q_sq, pc, tau, cap):
+        """ONE filter launch over the probe rows ``pc`` of the prepared queries ``Qc`` with tau = the radii: (cnt int32 [m],
+        cand int32 [m, cap, 2], tiles).  ``q_sq``: the norms of fp32 queries (fp16 lists take them of the rounded queries here)."""
+        dev = Qc.device
+        m = Qc.shape[0]
+        pq = self.storage == "pq"
+        tile = dict(zip(("tile_slots", "tile_rows"), ops.ivf_pq_tile(self.pq_m))) if pq else {}
+        tb = ivf_tables(pc, self.list_len, **tile)
+        cnt = torch.zeros(m, dtype=torch.int32, device=dev)
+        cand = torch.empty((m, cap, 2), dtype=torch.int32, device=dev)
+        if not tb["n_tiles"]:                             # nothing probed, or empty lists only
+            return cnt, cand, 0
+        if pq:
+            lut = torch.empty((m, self.pq_m, PQ_CODEWORDS), dtype=torch.float32, device=dev)
+            ops.pq_lut(Qc, self.codebooks, lut)
+            if self.pq_residual:
+                slot_base = torch.empty(tb["n_slots"], dtype=torch.float32, device=dev)
+                ops.ivf_slot_dots(Qc, self._C, tb["slot_query"], tb["slot_start"], slot_base)
+                ops.ivf_filter_pqr(lut, tb["slot_query"], tb["slot_start"], slot_base, q_sq, tau, cnt, self.codes, self.list_start,
+                                   self.r_sq, self.ids, tb["tiles"], cand, cap)
+            else:
+                ops.ivf_filter_pq(lut, tb["slot_query"], tb["slot_start"], q_sq, tau, cnt, self.codes, self.list_start, self.r_sq,
+                                  self.ids, tb["tiles"], cand, cap)
+        elif self.storage == "f16":
+            Qh = Qc.to(torch.float16)
+            q_sq = torch.zeros(m, dtype=torch.float32, device=dev)
+            ops.row_sqnorm(Qh.float(), Qc.shape[1], q_sq)
+            ops.ivf_filter_f16(Qh, tb["slot_query"], tb["slot_start"], q_sq, tau, cnt, self.rows, self.list_start, self.r_sq, self.ids,
+                               tb["tiles"], cand, cap)
+        else:
+            ops.ivf_filter_f32(Qc, tb["slot_query"], tb["slot_start"], q_sq, tau, cnt, self.rows, self.list_start, self.r_sq, self.ids,
+                               tb["tiles"], cand, cap)
+        return cnt, cand, tb["n_tiles"]
+
+    def range_search(self, queries, radius, nprobe, probe=None, range_cap=None, result_bytes=None, stats=None):
+        """(lims int64 [nq + 1], D fp32 [total], I int64 [total]), device tensors: query q owns D[lims[q]:lims[q + 1]] and the
+        same span of I, sorted by (d, id) ascending -- EVERY listed row of the query's ``nprobe`` probed lists with
+        d <= radius[q], where d is the distance ``search(..., scan="buffer")`` forms for that (query, row), bit for bit.
+        ``radius``: a float or an [nq] tensor, in the squared-L2 units of ``search``; a negative or NaN radius returns nothing
+        for its query, +inf every probed listed row; a NaN query returns nothing.  ``probe`` as ``search`` takes it.
+        There is no re-rank: on storage "f16" the distances are those of the rounded rows to the rounded query, on "pq" those
+        of the decoded rows, as in ``search`` without ``refine``.  An index with ``pq_bits=4`` is refused (its scan has no filter
+        launch).
+        Per chunk of queries: the slot tables, the lookup tables of a pq index, ONE filter launch (include/cdml_ivf_filter.h,
+        include/cdml_ivf_range.h) with tau = radius into ``range_cap`` candidate slots per query (a power
+        of two in [64, 65536], default 256) and one host read of the counts.  A chunk holds 8 B x ``range_cap`` per query (and
+        a pq query's lookup table) within ``result_bytes`` (default ``default_score_bytes()``).  The queries that counted more
+        than ``range_cap`` go through the launch ONCE more with the smallest power of two that holds the largest count; when
+        ``result_bytes`` cannot hold one such query, a ValueError says how many bytes it needs.  The result does not depend
+        on ``range_cap``, ``result_bytes``, the chunking or the order of the queries.  ``stats`` (a dict, optional) receives
+        ``chunks``, ``n_tiles``, ``range_cap``, ``n_results``, ``second_pass`` (queries) and ``second_cap``."""
+        self._check_queries(queries, nprobe)
+        nprobe = int(nprobe)
+        if self.storage == "pq" and self.pq_bits == 4:
+            raise ValueError("range_search has no launch for pq_bits=4 (the 4-bit scan has no filter form: DESIGN.md section 10): "
+                             "use pq_bits=8")
+        cap = self._check_range_cap(range_cap)
+        nq = int(queries.shape[0])
+        if torch.is_tensor(radius) or isinstance(radius, np.ndarray):
+            radius = torch.as_tensor(radius)
+            if tuple(radius.shape) != (nq,):
+                raise ValueError("radius must be a float or an [nq = %d] tensor, got shape %s" % (nq, tuple(radius.shape)))
+        else:
+            radius = float(radius)
+        self._check_listed()
+        probe = self._check_probe(probe, nq, nprobe)
+        t = queries if torch.is_tensor(queries) else torch.as_tensor(np.asarray(queries, dtype=np.float32))
+        dev = self.device
+        budget = self.default_score_bytes() if result_bytes is None else int(result_bytes)
+        chunks = self._range_plan(nq, nprobe, cap, budget)
+        Q = self._prepared(t, dev, self.l2_norm)
+        Dp = Q.shape[1]
+        st = dict(chunks=chunks, n_tiles=0, range_cap=cap, n_results=0, second_pass=0, second_cap=0)
+        if stats is not None:
+            stats.update(st)
+        if not nq:
+            z = torch.zeros(1, dtype=torch.int64, device=dev)
+            return z, torch.empty(0, dtype=torch.float32, device=dev), torch.empty(0, dtype=torch.int64, device=dev)
+        tau = (radius.to(device=dev, dtype=torch.float32) if torch.is_tensor(radius)
+               else torch.full((nq,), radius, dtype=torch.float32, device=dev)).contiguous()
+        q_sq = torch.zeros(nq, dtype=torch.float32, device=dev)
+        if self.storage != "f16":
+            ops.row_sqnorm(Q, Dp, q_sq)
+        probe = (self._probes(Q, nprobe) if probe is None else probe.to(dev)).to(torch.int32).contiguous()
+        if self.storage == "f16":                         # a query with no finite fp16 image probes nothing, as in ``search``
+            lost = (Q.abs() >= 65520.0).any(1)
+            probe = torch.where(lost[:, None], torch.full_like(probe, -1), probe)
+        parts, redo, redo_cnt = [], [], []
+        for q0, q1 in chunks:
+            cnt, cand, nt = self._range_filter(Q[q0:q1], q_sq[q0:q1], probe[q0:q1].contiguous(), tau[q0:q1], cap)
+            st["n_tiles"] += nt
+            cnt_h = cnt.cpu()                             # the host read
+            over = cnt_h > cap
+            if bool(over.any()):                          # these queries lost candidates: none of theirs is kept from this pass
+                idx = torch.nonzero(over).flatten()
+                redo.append(idx + q0)
+                redo_cnt.append(cnt_h[idx])
+                cnt = torch.where(over.to(dev), torch.zeros_like(cnt), cnt)
+            parts.append(range_compact(cand, cnt, cap))
+            del cand
+        n1 = torch.cat([p[0][1:] - p[0][:-1] for p in parts])
+        D1, I1 = torch.cat([p[1] for p in parts]), torch.cat([p[2] for p in parts])
+        if not redo:
+            lims = torch.zeros(nq + 1, dtype=torch.int64, device=dev)
+            lims[1:] = torch.cumsum(n1, 0)
+            st["n_results"] = int(D1.numel())
+            if stats is not None:
+                stats.update(st)
+            return lims, D1, I1
+        # the second pass, once: the queries over capacity with room for the largest count
+        idx = torch.cat(redo).to(dev)
+        want = torch.cat(redo_cnt)
+        cap2 = 1 << (int(want.max()) - 1).bit_length()
+        chunks2 = self._range_plan(int(idx.numel()), nprobe, cap2, budget)
+        Q2, s2, p2, t2 = Q.index_select(0, idx), q_sq.index_select(0, idx), probe.index_select(0, idx), tau.index_select(0, idx)
+        parts2 = []
+        for q0, q1 in chunks2:
+            cnt, cand, nt = self._range_filter(Q2[q0:q1], s2[q0:q1], p2[q0:q1].contiguous(), t2[q0:q1], cap2)
+            st["n_tiles"] += nt
+            if not torch.equal(cnt.cpu(), want[q0:q1]):
+                raise RuntimeError("range_search: the second launch counted other candidates than the first")
+            parts2.append(range_compact(cand, cnt, cap2))
+            del cand
+        D2, I2 = torch.cat([p[1] for p in parts2]), torch.cat([p[2] for p in parts2])
+        n2 = want.to(device=dev, dtype=torch.int64)
+        n = n1.clone()
+        n[idx] = n2
+        lims = torch.zeros(nq + 1, dtype=torch.int64, device=dev)
+        lims[1:] = torch.cumsum(n, 0)
+        D = torch.empty(int(lims[-1]), dtype=torch.float32, device=dev)
+        I = torch.empty(int(lims[-1]), dtype=torch.int64, device=dev)
+        for Dx, Ix, nx, owner in ((D1, I1, n1, torch.arange(nq, device=dev)), (D2, I2, n2, idx)):
+            start = torch.cumsum(nx, 0) - nx                  # where each query's span begins in this pass's output
+            own = torch.repeat_interleave(torch.arange(nx.numel(), device=dev), nx)
+            dest = lims[owner[own]] + (torch.arange(Dx.numel(), device=dev) - start[own])
+            D[dest], I[dest] = Dx, Ix
+        st.update(n_results=int(D.numel()), second_pass=int(idx.numel()), second_cap=cap2)
+        if stats is not None:
+            stats.update(st)
+        return lims, D, I
+
+
+def range_compact(cand, cnt, cap):
+    """(lims int64 [m + 1], D fp32 [total], I int64 [total]) of the candidate lists a filter launch filled: ``cand`` int32
+    [m, cap, 2] pairs (the bits of d, id), ``cnt`` int32 [m] the candidates counted.  The first min(cnt, cap) slots of every query
+    are kept and sorted by (d, id) ascending.  d is never negative and never NaN there, so its bits order as integers.  Plain
+    torch on the tensors' device (CPU tensors too)."""
+    cap = int(cap)
+    m = int(cnt.numel())
+    dev = cand.device
+    c = cand.reshape(-1)[:2 * m * cap].view(m, cap, 2)
+    n = cnt.to(torch.int64).clamp(min=0, max=cap)
+    lims = torch.zeros(m + 1, dtype=torch.int64, device=dev)
+    lims[1:] = torch.cumsum(n, 0)
+    keep = torch.arange(cap, device=dev)[None, :] < n[:, None]
+    owner = torch.repeat_interleave(torch.arange(m, device=dev), n)       # ascending: the mask selects row by row
+    key = (c[..., 0][keep].to(torch.int64) << 32) | c[..., 1][keep].to(torch.int64)       # d's bits < 2^31, id in [0, 2^31)
+    key, order = torch.sort(key)
+    key = key[torch.sort(owner[order], stable=True)[1]]                   # back into the queries' spans, (d, id) kept inside
+    D = (key >> 32).to(torch.int32).view(torch.float32)
+    return lims, D, key & 0xffffffff
+
+
+def ivf_range(base, queries=None, radius=None, nlist=1024, nprobe=16, l2_norm=True, storage="f32", iters=10, seed=0,
+              device="cuda:0", precision="f32x3", index=None, stats=None, pq_m=None, pq_residual=False, range_cap=None,
+              result_bytes=None):
+    """Device (lims, D, I) of ``IVFIndex.range_search``: the index of ``base`` (built here as ``ivf_knn`` builds it, or taken as
+    ``index=``), every listed row of a query's ``nprobe`` nearest lists within ``radius`` (a float or an [nq] tensor, squared
+    L2).  ``queries=None`` searches the catalogue against itself.  No re-rank: the distances of storage "f16" / "pq" are
+    those of the stored values."""
+    if radius is None:
+        raise ValueError("ivf_range needs radius: a float or an [nq] tensor of squared-L2 radii")
+    if index is None:
+        if storage not in IVF_STORAGES:
+            raise ValueError("storage must be one of %s, got %r" % (IVF_STORAGES, storage))
+        _check_pq_residual(storage, pq_residual)
+        _check_pq_m(storage, pq_m)
+        index = IVFIndex.build(base, int(nlist), iters=iters, seed=seed, l2_norm=l2_norm, device=device, precision=precision,
+                               storage=storage, pq_m=pq_m, pq_residual=pq_residual)
+    return index.range_search(base if queries is None else queries, radius, int(nprobe), range_cap=range_cap,
+                              result_bytes=result_bytes, stats=stats)

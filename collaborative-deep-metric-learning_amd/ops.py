@@ -2021,6 +2021,46 @@ def ivf_filter_f16(Q, slot_query, slot_start, q_sq, tau, cnt, rows, list_start, 
                        cnt, rows, list_start, r_sq, ids, tiles, cand, cap)
 
 
+# ---------------------------------------- filter scan over product-quantised lists (include/cdml_ivf_range.h) ------
+def _ivf_filter_pq_call(symbol, lut, slot_query, slot_start, q_sq, tau, cnt, codes, list_start, r_sq, ids, tiles, cand, cap,
+                        slot_base=None):
+    """The two filter scans over 8-bit codes: ``_ivf_scan_pq_call``'s checks of lut / codes / tiles, ``_ivf_filter``'s of the
+    candidate set."""
+    if lut.dim() != 3 or lut.shape[2] != 256 or not lut.is_contiguous():
+        raise ValueError("lut must be a contiguous float32 [n_queries, M, 256] tensor")
+    nq, M, cap = lut.shape[0], lut.shape[1], int(cap)
+    if codes.dtype != torch.uint8 or codes.dim() != 2 or codes.stride(1) != 1 or codes.shape[1] < M:
+        raise ValueError("codes must be a uint8 [n_listed, >= M] tensor with unit inner stride")
+    nlist = list_start.numel() - 1
+    n_slots, n_listed = slot_query.numel(), codes.shape[0]
+    if tiles.dim() != 2 or tiles.shape[1] != 4:
+        raise ValueError("tiles must be int32 [n_tiles, 4]")
+    if cand.dtype != torch.int32 or not cand.is_contiguous() or cand.numel() < 2 * nq * cap:
+        raise ValueError("cand must be a contiguous int32 tensor of at least [nq = %d, cap = %d, 2]" % (nq, cap))
+    base = () if slot_base is None else (_vec(slot_base, torch.float32, n_slots, "slot_base"),)
+    call(symbol, _p(lut, torch.float32), nq, _vec(slot_query, torch.int32, 0, "slot_query"),
+         _vec(slot_start, torch.int32, nlist + 1, "slot_start"), *base, _vec(q_sq, torch.float32, nq, "q_sq"),
+         _vec(tau, torch.float32, nq, "tau"), _vec(cnt, torch.int32, nq, "cnt"), _p(codes), codes.stride(0),
+         _vec(list_start, torch.int32, nlist + 1, "list_start"), _vec(r_sq, torch.float32, n_listed, "r_sq"),
+         _vec(ids, torch.int32, n_listed, "ids"), M, _vec(tiles, torch.int32, 4, "tiles"), tiles.shape[0], _p(cand, torch.int32),
+         cap, _stream())
+    return cnt
+
+
+def ivf_filter_pq(lut, slot_query, slot_start, q_sq, tau, cnt, codes, list_start, r_sq, ids, tiles, cand, cap):
+    """``ivf_scan_pq``'s sums over the tiles of ``tiles`` (``ivf_pq_tile(M)`` slots x rows) with no score buffer: every (query q,
+    listed row) with d = max((q_sq[q] + r_sq[row]) - 2 s, 0) <= tau[q] takes slot pos = cnt[q]++ of the query's candidate list
+    and, when pos < cap, writes cand[q, pos] = (the bits of d, ids[row]) (cand int32 [nq, cap, 2]; cap a power of two)."""
+    return _ivf_filter_pq_call("cdml_ivf_filter_pq", lut, slot_query, slot_start, q_sq, tau, cnt, codes, list_start, r_sq, ids,
+                               tiles, cand, cap)
+
+
+def ivf_filter_pqr(lut, slot_query, slot_start, slot_base, q_sq, tau, cnt, codes, list_start, r_sq, ids, tiles, cand, cap):
+    """``ivf_filter_pq`` with every slot's sums starting from ``slot_base[slot]`` (``ivf_slot_dots``): ``ivf_scan_pqr``'s sums."""
+    return _ivf_filter_pq_call("cdml_ivf_filter_pqr", lut, slot_query, slot_start, q_sq, tau, cnt, codes, list_start, r_sq, ids,
+                               tiles, cand, cap, slot_base=slot_base)
+
+
 def knn_desim_prep(fI, fD, fI_end, threshold, out):
     """The raw-feature lists fI (int32 | int64 [n_f, kf]) with their distances fD (fp32) filtered into out (int32
     [n_f, kp], kp = 32 | 64): fI[r, t] for t < fI_end where fD <= threshold (float32), fI != r, fI >= 0; else -1."""
